@@ -7,10 +7,14 @@ composite [-> RCCL all-gather of the row bands when N > 1]) with weights and all
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 Both launch forms run the same rank code: one process per GPU, torch.distributed over RCCL ("nccl"), row bands + ONE
 all-gather of the framebuffer.  Rank 0 prints ONE JSON line.  `roofline` is the fine-network MLP kernel (the dominant
-launch) measured with HIP events on the render stream inside the timed region; `cpu_baseline` is the CPU oracle (a
-port of the reference's algorithm) timed on this host's cores in the REFERENCE'S OWN LOOP ORDER (forward_fallback,
-src/network.rs:124-147) on one 8x8 block per thread at the reference CLI's 256x256 geometry; the oracle's cache-blocked
-nest (bit-identical results) is reported beside it as `blocked_rays_per_s`.
+launch) measured with HIP events on the render stream inside the timed region.
+
+A plain run sets up, warms up, times the K steps and prints the line.  Everything else it can report needs --full: the
+separately timed modes and arithmetics (`extra_*`), the frame's device-to-host copy, the multi-context bit-identity check of
+--launch inproc, and `cpu_baseline` -- the CPU oracle (a port of the reference's algorithm) timed on this host's cores in the
+REFERENCE'S OWN LOOP ORDER (forward_fallback, src/network.rs:124-147) on one 8x8 block per thread at the reference CLI's
+256x256 geometry, with the oracle's cache-blocked nest (bit-identical results) beside it as `blocked_rays_per_s`.
+--dump-outputs DIR writes the frame of the last timed step to DIR/frame.npy (float32, h x w x 3).
 """
 import argparse
 import json
@@ -43,6 +47,25 @@ def pmc_traffic_bytes(kernel_prefix="void nerf_mlp_kernel<true"):
                 n = max(int(row["dispatches"]), 1)
                 return (2.0 * float(row["FETCH_SIZE"]) + float(row.get("WRITE_SIZE", 0) or 0)) * 1024.0 / n, os.path.relpath(f, ROOT), None
     return None, None, f"no profiles/{PROFILE_ROUND}*_pmc_summary.csv row for kernel '{kernel_prefix}...' (PMC passes of this round not committed for it)"
+
+
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: all files together stay below this
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: each (h, w, c) array as out_dir/<name>.npy in float32.  An array over its share of `limit` is written as
+    <name>_sample.npy instead: the pixels at a fixed, seeded choice of indices (sorted), shape (k, c) -- the same for the same shape."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = limit // max(len(arrays), 1) - 4096  # room for the .npy header
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.nbytes > share:
+            px = a.reshape(a.shape[0] * a.shape[1], -1)
+            k = share // px[0].nbytes
+            a = px[np.sort(np.random.default_rng(0).choice(px.shape[0], k, replace=False))]
+            name += "_sample"
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def host_cores():
@@ -174,8 +197,10 @@ def main_inproc(args):
         walls.append(1e3 * (time.perf_counter() - t1))
     dt = time.perf_counter() - t0
     dom = [r.kernel_time_query(reset=True) for r in rs]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"frame": img})
     one = None
-    if n > 1:  # the same frame from one context: the bits must be the same
+    if n > 1 and args.full:  # the same frame from one context: the bits must be the same
         one = N.render_image(rs[0].coarse, rs[0].fine, cam, args.fine, **{k: v for k, v in kw.items() if k != "gather"})
     import numpy as np
     n_rays = args.width * args.height * args.ssaa * args.ssaa
@@ -266,11 +291,18 @@ def main():
                          "no torch involved.  On a box with fewer GPUs than --gpus the contexts share device 0 and the line says REHEARSAL")
     ap.add_argument("--gather", choices=["host", "peer", "rccl"], default="rccl",
                     help="--launch inproc: how the bands meet (NERF_GATHER_HOST / _PEER / _RCCL)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the separately reported skip_empty frames (profiling runs)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the separately reported extra_* frames, the frame's device-to-host copy, cpu_baseline "
+                         "and (--launch inproc) the one-context bit-identity check; a plain run (default) times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the frame of the last timed step to DIR/frame.npy (float32; a seeded sample of it beyond 64 MB)")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the separately reported skip_empty frames (profiling runs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
     ap.add_argument("--no-cpu-reference-order", action="store_true",
                     help="quick runs: time only the oracle's cache-blocked nest (skips the ~2 min reference-loop-order sample)")
     args = ap.parse_args()
+    if not args.full:  # a plain run: nothing beyond what the headline needs
+        args.no_extra = args.no_cpu_baseline = True
     if args.launch == "inproc":
         return main_inproc(args)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -361,6 +393,8 @@ def main():
     if use_dist:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = float(tmax.item())
+    if args.dump_outputs and rank == 0:  # every rank holds the whole frame; taken before the untimed frames below overwrite `frame`
+        dump_outputs(args.dump_outputs, {"frame": out.cpu().numpy()})
     # N > 1: attribute the step to render vs gather, per rank (events recorded inside the timed region, read here)
     per_rank = None
     if use_dist and marks:
@@ -635,9 +669,9 @@ def main():
             extra_c5["same_geometry_at_f32_accuracy_f16x2_certify_zero"] = {"error": e.msg}
         r.kernel_time_query(reset=True)
     # The timed region leaves the frame in HBM (`value` never includes PCIe); the host-pointer entry point additionally pays
-    # one D2H copy of the frame (BASELINE.md section 4 counts it on the GPU side): measured here, reported beside `value`.
+    # one D2H copy of the frame (BASELINE.md section 4 counts it on the GPU side): measured here (--full), reported beside `value`.
     d2h_ms = None
-    if world == 1:
+    if world == 1 and args.full:
         host_frame = torch.empty(frame.shape, dtype=frame.dtype, pin_memory=True)
         host_frame.copy_(frame, non_blocking=True); torch.cuda.synchronize(dev)
         t1 = time.perf_counter()

@@ -202,7 +202,7 @@ def test_bench_inproc_times_the_c_abi_multi_entry_point(gather, extra):
     on this box's one GPU -- labelled a rehearsal -- and the frame must be the one-context frame bit for bit."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--launch", "inproc", "--gather", gather, "--gpus", "2", "--steps", "2",
-                        "--warmup", "1", "--width", "96", "--height", "81"] + extra, capture_output=True, text=True, timeout=600, env=env)
+                        "--warmup", "1", "--width", "96", "--height", "81", "--full"] + extra, capture_output=True, text=True, timeout=600, env=env)
     assert p.returncode == 0, p.stderr[-2000:]
     d = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][0])
     assert d["n_gpus"] == 2 and d["launch"].startswith("inproc") and d["gather"] == gather and "REHEARSAL" in d["backend"]

@@ -17,6 +17,6 @@ timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/prof_$TAG
 timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/prof_$TAG/pmc_write -o bench -- python3 $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-extra $ARGS > $O/prof_$TAG/pmc_write.log 2>&1 || { tail -5 $O/prof_$TAG/pmc_write.log; exit 1; }
 timeout -k 10 300 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_LDS_UNALIGNED_STALL SQ_LDS_ADDR_CONFLICT --output-format csv -d $O/prof_$TAG/pmc_lds -o bench -- python3 $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-extra $ARGS > $O/prof_$TAG/pmc_lds.log 2>&1 || { tail -5 $O/prof_$TAG/pmc_lds.log; exit 1; }
 if [ -n "$ARGS" ]; then find $O/prof_$TAG -name "*.csv" | head -30; exit 0; fi
-timeout -k 10 400 python3 $R/bench.py --steps 5 --warmup 1 > $O/bench_$TAG.json 2> $O/bench_$TAG.err; echo "bench rc=$?"; cat $O/bench_$TAG.json
+timeout -k 10 600 python3 $R/bench.py --full --steps 5 --warmup 1 > $O/bench_$TAG.json 2> $O/bench_$TAG.err; echo "bench rc=$?"; cat $O/bench_$TAG.json
 cd $R && timeout -k 10 120 ./nerf-rs_amd/nerf_cli --scene lego_rust --out $O/output_256.ppm --frames 2 > $O/cli_$TAG.log 2>&1; tail -3 $O/cli_$TAG.log
 find $O/prof_$TAG -name "*.csv" | head -30
