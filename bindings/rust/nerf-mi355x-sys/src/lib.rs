@@ -127,10 +127,19 @@ extern "C" {
                              rgb_out: *mut f32, stats: *mut nerf_stats) -> c_int;
     pub fn nerf_render_image_device(ctx: *mut nerf_ctx, cam: *const nerf_camera, opts: *const nerf_render_opts,
                                     d_rgb_out: *mut f32, stream: *mut c_void, stats: *mut nerf_stats) -> c_int;
+    /// render_image + the expected-depth and opacity maps (h x w each; either may be null): include/nerf_mi355x.h defines them.
+    pub fn nerf_render_image_aux(ctx: *mut nerf_ctx, cam: *const nerf_camera, opts: *const nerf_render_opts, rgb_out: *mut f32,
+                                 depth_out: *mut f32, opacity_out: *mut f32, stats: *mut nerf_stats) -> c_int;
+    pub fn nerf_render_image_aux_device(ctx: *mut nerf_ctx, cam: *const nerf_camera, opts: *const nerf_render_opts,
+                                        d_rgb_out: *mut f32, d_depth_out: *mut f32, d_opacity_out: *mut f32, stream: *mut c_void,
+                                        stats: *mut nerf_stats) -> c_int;
     /// render_image over several GPUs: `ctxs[i]` = one context per device, row bands on per-context host threads + streams,
     /// gathered into `rgb_out` by `gather` (NERF_GATHER_*).  The reference's counterpart is the rayon fan-out, src/lib.rs:533-557.
     pub fn nerf_render_image_multi(ctxs: *const *mut nerf_ctx, n: c_int, cam: *const nerf_camera, opts: *const nerf_render_opts,
                                    gather: c_int, rgb_out: *mut f32, per_ctx: *mut nerf_stats) -> c_int;
+    pub fn nerf_render_image_multi_aux(ctxs: *const *mut nerf_ctx, n: c_int, cam: *const nerf_camera, opts: *const nerf_render_opts,
+                                       gather: c_int, rgb_out: *mut f32, depth_out: *mut f32, opacity_out: *mut f32,
+                                       per_ctx: *mut nerf_stats) -> c_int;
     pub fn nerf_create_multi(device_ids: *const c_int, n: c_int, out: *mut *mut nerf_ctx) -> c_int;
     pub fn nerf_multi_release();
     pub fn nerf_band_rows(window_rows: c_int, band_index: c_int, band_count: c_int, band_stripe_rows: c_int) -> c_int;
@@ -141,6 +150,8 @@ extern "C" {
     pub fn nerf_camera_from_values(near: f32, far: f32, origin: *const f32, forward: *const f32, up: *const f32,
                                    hwf: *const f32, width: c_int, height: c_int, out: *mut nerf_camera) -> c_int;
     pub fn nerf_save_ppm(path: *const c_char, width: c_int, height: c_int, rgb: *const f32) -> c_int;
+    /// one-channel PFM ("Pf", little-endian, rows bottom-up) of a width x height map given top row first
+    pub fn nerf_save_pfm(path: *const c_char, width: c_int, height: c_int, values: *const f32) -> c_int;
     pub fn nerf_quantize_rgb8(rgb: *const f32, n_pixels: usize, out: *mut u8);
     pub fn nerf_quantize_rgba8(rgb: *const f32, n_pixels: usize, out: *mut u8);
     pub fn nerf_stage_ray_dirs(ctx: *mut nerf_ctx, cam: *const nerf_camera, x0: c_int, y0: c_int, w: c_int, h: c_int,

@@ -58,6 +58,12 @@ pub fn save_ppm(path: &Path, width: i32, height: i32, rgb: &[f32]) -> Result<(),
     check(std::ptr::null(), unsafe { sys::nerf_save_ppm(cpath(path)?.as_ptr(), width, height, rgb.as_ptr()) })
 }
 
+/// A depth or opacity map of `Gpu::render_image_aux` as a one-channel PFM (little-endian, rows bottom-up).
+pub fn save_pfm(path: &Path, width: i32, height: i32, values: &[f32]) -> Result<(), Error> {
+    assert_eq!(values.len(), (width * height) as usize, "values.len() != width * height");
+    check(std::ptr::null(), unsafe { sys::nerf_save_pfm(cpath(path)?.as_ptr(), width, height, values.as_ptr()) })
+}
+
 /// One GPU with both networks resident (`coarse_network` / `fine_network` of render_cli_image, src/lib.rs:651-652).
 pub struct Gpu {
     ctx: *mut sys::nerf_ctx,
@@ -99,6 +105,19 @@ impl Gpu {
         let mut stats = Stats::default();
         check(self.ctx, unsafe { sys::nerf_render_image(self.ctx, cam, opts, image.as_mut_ptr(), &mut stats) })?;
         Ok((image, stats))
+    }
+
+    /// `render_image` plus the expected-depth map (distance along the unit ray, 0 for the background) and the opacity map
+    /// (accumulated weight), one f32 per pixel each in the same pixel order (nerf_render_image_aux).
+    pub fn render_image_aux(&self, cam: &Camera, opts: &RenderOpts) -> Result<(Vec<f32>, Vec<f32>, Vec<f32>, Stats), Error> {
+        let (w, h) = if opts.crop_w > 0 || opts.crop_h > 0 { (opts.crop_w, opts.crop_h) } else { (cam.nx, cam.ny) };
+        let px = (w.max(0) as usize) * (h.max(0) as usize);
+        let (mut image, mut depth, mut opacity) = (vec![0f32; px * 3], vec![0f32; px], vec![0f32; px]);
+        let mut stats = Stats::default();
+        check(self.ctx, unsafe {
+            sys::nerf_render_image_aux(self.ctx, cam, opts, image.as_mut_ptr(), depth.as_mut_ptr(), opacity.as_mut_ptr(), &mut stats)
+        })?;
+        Ok((image, depth, opacity, stats))
     }
 }
 

@@ -231,6 +231,21 @@ int nerf_render_image(nerf_ctx *ctx, const nerf_camera *cam, const nerf_render_o
 /* device output, asynchronous on `stream`; stats != NULL synchronises the stream before returning. */
 int nerf_render_image_device(nerf_ctx *ctx, const nerf_camera *cam, const nerf_render_opts *opts, float *d_rgb_out,
                              void *stream, nerf_stats *stats);
+/* Colour plus the two other per-pixel maps of a NeRF renderer (nerf-pytorch's rgb_map, depth_map, acc_map).  For each ray, with w_i the
+ * exact compositing weights (the T < 1e-4 cut included: zero after it) and t_i its sample positions (the merged fine samples; the coarse
+ * ones for coarse_only or when no fine sample is drawn):
+ *   opacity = sum_i w_i          in sample order, f32 -- the reference's `acc` (src/lib.rs:185-194); rgb = sum_i w_i c_i + (1 - opacity)
+ *   depth   = sum_i (t_i * w_i)  in sample order, f32, separate multiply and add: the expected termination distance along the UNIT ray
+ *                                direction (src/lib.rs:371) -- Euclidean distance from the camera centre, not z-depth.  The background
+ *                                adds 0: an empty ray has depth 0 and opacity 0; depth / opacity is the depth of the surface hit.
+ * SSAA: each map is the box mean of its s x s sub-rays (same order as the colour).  Windows and bands: each map is h x w floats with
+ * the colour output's layout.  rgb_out is required, either map may be NULL; with both NULL a call is its counterpart without _aux.
+ * The colour is bit-identical whether or not maps are asked for.  Device variant: asynchronous on `stream`, like
+ * nerf_render_image_device. */
+int nerf_render_image_aux(nerf_ctx *ctx, const nerf_camera *cam, const nerf_render_opts *opts, float *rgb_out,
+                          float *depth_out /* h x w or NULL */, float *opacity_out /* h x w or NULL */, nerf_stats *stats);
+int nerf_render_image_aux_device(nerf_ctx *ctx, const nerf_camera *cam, const nerf_render_opts *opts, float *d_rgb_out,
+                                 float *d_depth_out, float *d_opacity_out, void *stream, nerf_stats *stats);
 /* ---- S3 over several GPUs of one node (reference: the rayon fan-out over blocks + scatter, src/lib.rs:533-557) ------
  * ctxs[i] is one context per device (nerf_create / nerf_create_multi), each with both networks loaded (weights are
  * replicated).  Context i renders band i of n of the output rows (nerf_render_opts.band_*, set here: the caller's values are
@@ -250,6 +265,10 @@ int nerf_render_image_device(nerf_ctx *ctx, const nerf_camera *cam, const nerf_r
 enum { NERF_GATHER_HOST = 0, NERF_GATHER_PEER = 1, NERF_GATHER_RCCL = 2 };
 int nerf_render_image_multi(nerf_ctx *const *ctxs, int n, const nerf_camera *cam, const nerf_render_opts *opts, int gather,
                             float *rgb_out, nerf_stats *per_ctx /* n entries or NULL */);
+/* ... with the depth and opacity maps of nerf_render_image_aux (either may be NULL).  Every gather works the same way; the maps ride in
+ * the same band slots as the colour (still one all-gather per frame with NERF_GATHER_RCCL). */
+int nerf_render_image_multi_aux(nerf_ctx *const *ctxs, int n, const nerf_camera *cam, const nerf_render_opts *opts, int gather,
+                                float *rgb_out, float *depth_out, float *opacity_out, nerf_stats *per_ctx);
 /* n contexts, device_ids[i] each (NULL => devices 0..n-1); all-or-nothing. */
 int nerf_create_multi(const int *device_ids, int n, nerf_ctx **out /* n entries */);
 /* Frees the cached RCCL communicators of NERF_GATHER_RCCL (optional; call after the contexts are idle). */
@@ -283,6 +302,9 @@ int nerf_save_ppm(const char *path, int width, int height, const float *rgb);
 void nerf_quantize_rgb8(const float *rgb, size_t n_pixels, uint8_t *out);
 /* pixels_to_rgba (src/lib.rs:582-592; the reference's wasm canvas path): the same quantisation, alpha = 255 */
 void nerf_quantize_rgba8(const float *rgb, size_t n_pixels, uint8_t *out /* 4 n_pixels */);
+/* One-channel PFM ("Pf"; scale -1 = little-endian; rows bottom-up as the format stores them) of width x height floats given top row
+ * first (a depth or opacity map of nerf_render_image_aux).  Host-only. */
+int nerf_save_pfm(const char *path, int width, int height, const float *values);
 
 /* ---- stage entry points (device execution, host buffers): the individual functions of render_block, exposed so
  * that a host that owns ray setup can call them and so that each stage has its own parity test ------------- */
@@ -315,7 +337,8 @@ const char *nerf_build_variant(void);
 /* ABI version (currently 5): bumped on any signature or struct change (2: multi-GPU entry points, skip_dead, n_exec_* statistics; 3: nerf_stats.
  * n_nonfinite_points, nerf_check_network_blob, nerf_stage_hybrid_flags, nerf_build_variant; 4: nerf_render_opts.certify_zero; 5: nerf_stats.
  * n_certify_* / certify_margin / certify_headroom / certify_max_error, renders fail on n_nonfinite_points != 0,
- * nerf_render_opts.band_*, nerf_band_rows, nerf_debug_certify_policy). */
+ * nerf_render_opts.band_*, nerf_band_rows, nerf_debug_certify_policy; additive: nerf_render_image_aux, nerf_render_image_aux_device,
+ * nerf_render_image_multi_aux, nerf_save_pfm). */
 int nerf_abi_version(void);
 /* sizeof(nerf_camera), sizeof(nerf_render_opts), sizeof(nerf_stats) as this library was built: lets a binding written in
  * another language (the Rust `-sys` crate, ctypes) check its struct mirrors at start-up. */

@@ -75,6 +75,11 @@ PROTOTYPES = {
                                            C.POINTER(CStats)]),
     "nerf_render_image_multi": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(CCamera), C.POINTER(COpts), C.c_int, f32p,
                                           C.POINTER(CStats)]),
+    "nerf_render_image_aux": (C.c_int, [C.c_void_p, C.POINTER(CCamera), C.POINTER(COpts), f32p, f32p, f32p, C.POINTER(CStats)]),
+    "nerf_render_image_aux_device": (C.c_int, [C.c_void_p, C.POINTER(CCamera), C.POINTER(COpts), C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.POINTER(CStats)]),
+    "nerf_render_image_multi_aux": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(CCamera), C.POINTER(COpts), C.c_int, f32p,
+                                              f32p, f32p, C.POINTER(CStats)]),
     "nerf_create_multi": (C.c_int, [C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p)]),
     "nerf_multi_release": (None, []),
     "nerf_band_rows": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
@@ -85,6 +90,7 @@ PROTOTYPES = {
     "nerf_camera_from_values": (C.c_int, [C.c_float, C.c_float, f32p, f32p, f32p, f32p, C.c_int, C.c_int,
                                           C.POINTER(CCamera)]),
     "nerf_save_ppm": (C.c_int, [C.c_char_p, C.c_int, C.c_int, f32p]),
+    "nerf_save_pfm": (C.c_int, [C.c_char_p, C.c_int, C.c_int, f32p]),
     "nerf_quantize_rgb8": (None, [f32p, C.c_size_t, C.POINTER(C.c_uint8)]),
     "nerf_quantize_rgba8": (None, [f32p, C.c_size_t, C.POINTER(C.c_uint8)]),
     "nerf_stage_ray_dirs": (C.c_int, [C.c_void_p, C.POINTER(CCamera), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p]),

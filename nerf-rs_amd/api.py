@@ -271,8 +271,12 @@ def band_row_indices(window_rows, index, count, stripe_rows=0):
 
 def render_image(coarse, fine, camera, fine_samples_per_ray=128, *, seed=0, coarse_only=False, crop=None, ssaa=1,
                  dtype="f32", skip_empty=False, skip_dead=False, hybrid_sampling=False, certify_zero=False, band=None, return_stats=False,
-                 device_out=None, stream=0):
+                 device_out=None, stream=0, aux=False, device_depth=None, device_opacity=None):
     """render_image (src/lib.rs:474-565) -> (h, w, 3) float32 linear RGB.
+
+    aux=True: (rgb, depth, opacity), the two maps (h, w) float32 as nerf_render_image_aux defines them (expected distance along the
+    unit ray, accumulated weight); followed by the stats if return_stats.  With device_out, device_depth / device_opacity are the maps'
+    device pointers (either may be None).
 
     band = (index, count, stripe_rows): only that band of the window's rows, packed (nerf_render_opts.band_*).
 
@@ -286,14 +290,22 @@ def render_image(coarse, fine, camera, fine_samples_per_ray=128, *, seed=0, coar
     o = opts.to_c()
     st = CStats()
     if device_out is not None:
-        check(R._L.nerf_render_image_device(R.handle, C.byref(camera.c), C.byref(o), device_out, stream,
-                                            C.byref(st) if return_stats else None), R.handle)
+        if aux:
+            check(R._L.nerf_render_image_aux_device(R.handle, C.byref(camera.c), C.byref(o), device_out, device_depth, device_opacity, stream,
+                                                    C.byref(st) if return_stats else None), R.handle)
+        else:
+            check(R._L.nerf_render_image_device(R.handle, C.byref(camera.c), C.byref(o), device_out, stream,
+                                                C.byref(st) if return_stats else None), R.handle)
         return Stats(st) if return_stats else None
     shape = opts.out_shape(camera)
     if shape[0] <= 0 or shape[1] <= 0:
         raise NerfError(-1, "this band has no rows (more bands than rows)" if opts.band and opts.band[1] > 1 and shape[1] > 0 and
                         (crop[3] if crop else camera.ny) > 0 else "crop window outside the frame")
     out = np.empty(shape, np.float32)
+    if aux:
+        depth, opacity = np.empty(shape[:2], np.float32), np.empty(shape[:2], np.float32)
+        check(R._L.nerf_render_image_aux(R.handle, C.byref(camera.c), C.byref(o), _p(out), _p(depth), _p(opacity), C.byref(st)), R.handle)
+        return (out, depth, opacity, Stats(st)) if return_stats else (out, depth, opacity)
     check(R._L.nerf_render_image(R.handle, C.byref(camera.c), C.byref(o), _p(out), C.byref(st)), R.handle)
     return (out, Stats(st)) if return_stats else out
 
@@ -303,11 +315,13 @@ _GATHERS = {"host": 0, "peer": 1, "rccl": 2, 0: 0, 1: 1, 2: 2}
 
 
 def render_image_multi(renderers, camera, fine_samples_per_ray=128, *, gather="host", seed=0, coarse_only=False, crop=None,
-                       ssaa=1, dtype="f32", skip_empty=False, skip_dead=False, hybrid_sampling=False, certify_zero=False, return_stats=False):
+                       ssaa=1, dtype="f32", skip_empty=False, skip_dead=False, hybrid_sampling=False, certify_zero=False, return_stats=False,
+                       aux=False):
     """render_image fanned out over several Renderers (one per GPU) inside ONE process, through nerf_render_image_multi:
     row bands on per-context host threads + streams, gathered by direct D2H ("host"), GPU-to-GPU peer copies ("peer") or one
     RCCL all-gather ("rccl").  The reference's counterpart is the rayon fan-out + scatter of src/lib.rs:533-557.
-    Every Renderer must have both networks loaded."""
+    Every Renderer must have both networks loaded.  aux=True: (rgb, depth, opacity) as render_image(aux=True)
+    (nerf_render_image_multi_aux), followed by the stats if return_stats."""
     L = _lib.load_library()
     n = len(renderers)
     handles = (C.c_void_p * n)(*[r.handle for r in renderers])
@@ -318,6 +332,11 @@ def render_image_multi(renderers, camera, fine_samples_per_ray=128, *, gather="h
         raise NerfError(-1, "crop window outside the frame")
     out = np.empty(shape, np.float32)
     st = (CStats * n)()
+    if aux:
+        depth, opacity = np.empty(shape[:2], np.float32), np.empty(shape[:2], np.float32)
+        check(L.nerf_render_image_multi_aux(handles, n, C.byref(camera.c), C.byref(o), _GATHERS[gather], _p(out), _p(depth), _p(opacity),
+                                            st if return_stats else None), renderers[0].handle if n else None)
+        return (out, depth, opacity, [Stats(s) for s in st]) if return_stats else (out, depth, opacity)
     check(L.nerf_render_image_multi(handles, n, C.byref(camera.c), C.byref(o), _GATHERS[gather], _p(out), st if return_stats else None),
           renderers[0].handle if n else None)
     return (out, [Stats(s) for s in st]) if return_stats else out
@@ -344,6 +363,14 @@ def save_ppm(path, width, height, pixels):
     if a.size != width * height * 3:
         raise NerfError(-1, "pixels.len() != width * height")  # assert_eq! src/lib.rs:569
     check(_lib.load_library().nerf_save_ppm(str(path).encode(), width, height, _p(a)))
+
+
+def save_pfm(path, width, height, values):
+    """A depth or opacity map as a one-channel PFM (nerf_save_pfm: "Pf", little-endian, rows bottom-up); values: (height, width)."""
+    a = _f32(values)
+    if a.size != width * height:
+        raise NerfError(-1, "values.len() != width * height")
+    check(_lib.load_library().nerf_save_pfm(str(path).encode(), width, height, _p(a)))
 
 
 def load_tf_samples(path):

@@ -3,7 +3,7 @@
 // touches the device).  tests/test_host_asan.py feeds it valid, truncated, oversized and malformed weight directories, blobs and
 // camera JSON files: every call must come back with a status code and a message -- a sanitizer report aborts with a non-zero exit.
 //   host_asan_driver check_dir <dir> | pack_dir <dir> <blob> | check_blob <blob> | camera_json <json> <w> <h> |
-//                    debug_pack <dir> | quantize | save_ppm <path> <w> <h> | split
+//                    debug_pack <dir> | quantize | save_ppm <path> <w> <h> | save_pfm <path> <w> <h> | split
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -62,6 +62,12 @@ int main(int argc, char **argv) {
         std::vector<float> img(w > 0 && h > 0 ? (size_t)w * h * 3 : 0);
         for (size_t i = 0; i < img.size(); ++i) img[i] = (float)(i % 97) / 96.f - 0.01f;
         return report("save_ppm", nerf_save_ppm(argv[2], w, h, img.data()));
+    }
+    if (cmd == "save_pfm" && argc == 5) {
+        const int w = atoi(argv[3]), h = atoi(argv[4]);
+        std::vector<float> m(w > 0 && h > 0 ? (size_t)w * h : 0);
+        for (size_t i = 0; i < m.size(); ++i) m[i] = (float)(i % 89) * 0.0625f - 1.5f;
+        return report("save_pfm", nerf_save_pfm(argv[2], w, h, m.data()));
     }
     if (cmd == "split") {
         const float v[] = {0.f, -0.f, 1.f, -3.14159274f, 65504.f, 7e4f, 1e-8f, 6e-8f, 1e30f, -1e-30f, NAN, INFINITY};

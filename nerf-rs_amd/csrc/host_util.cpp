@@ -452,6 +452,27 @@ int save_ppm(const std::string &path, int width, int height, const float *rgb, s
     return NERF_OK;
 }
 
+int save_pfm(const std::string &path, int width, int height, const float *values, std::string &err) {
+    if (width <= 0 || height <= 0) { err = "save_pfm: bad size"; return NERF_ERR_INVALID; }
+    FILE *f = fopen(path.c_str(), "wb");
+    if (!f) { err = "save_pfm: cannot create " + path; return NERF_ERR_IO; }
+    fprintf(f, "Pf\n%d %d\n-1.0\n", width, height); // negative scale: little-endian floats
+    std::vector<uint8_t> row((size_t)width * 4);
+    bool ok = true;
+    for (int i = height - 1; i >= 0 && ok; --i) { // PFM stores the bottom row first
+        const float *src = values + (size_t)i * width;
+        for (int j = 0; j < width; ++j) {
+            uint32_t u;
+            memcpy(&u, &src[j], 4);
+            for (int k = 0; k < 4; ++k) row[4 * (size_t)j + k] = (uint8_t)(u >> (8 * k));
+        }
+        ok = fwrite(row.data(), 1, row.size(), f) == row.size();
+    }
+    if (fclose(f) != 0) ok = false;
+    if (!ok) { err = "save_pfm: short write " + path; return NERF_ERR_IO; }
+    return NERF_OK;
+}
+
 int certify_policy(float margin, uint64_t audited, uint64_t violations, float headroom, float max_error, float *new_margin) {
     if (new_margin) *new_margin = margin;
     if (!audited) return 0; // nothing was certified in front of a predicted cut: nothing to judge

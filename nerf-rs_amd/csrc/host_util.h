@@ -60,6 +60,8 @@ int fail_noctx(int code, const std::string &msg);
 const char *last_error_noctx();
 int read_blob_file(const std::string &path, std::vector<float> &wstream, std::vector<float> &small, std::string &err);
 int save_ppm(const std::string &path, int width, int height, const float *rgb, std::string &err);
+// 1-channel PFM ("Pf", little-endian, rows bottom-up) of a top-row-first map
+int save_pfm(const std::string &path, int width, int height, const float *values, std::string &err);
 
 // certify_zero's audit policy (nerf_api.cpp render_device; exposed host-only as nerf_debug_certify_policy so that it is tested without a
 // GPU).  Given what the audit of one network found in one frame, decide whether the frame stands and, if not, the widened margin:

@@ -361,8 +361,8 @@ struct CertOutcome {
     bool used[2] = {false, false};
 };
 
-int render_once(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *o, float *d_out, hipStream_t st, nerf_stats *stats,
-                CertOutcome *cert) {
+int render_once(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *o, float *d_out, float *d_depth, float *d_opacity, hipStream_t st,
+                nerf_stats *stats, CertOutcome *cert) {
     int rc;
     if ((rc = check_camera(c, cam))) return rc;
     if (!o) return fail(c, NERF_ERR_INVALID, "opts is NULL");
@@ -449,10 +449,15 @@ int render_once(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *o, 
     if ((size_t)RW > pass_cap && (size_t)RW * M > (size_t)0x3fffffff) return fail(c, NERF_ERR_INVALID, "ray row too wide for one pass");
     const size_t rows_per_pass = std::max<size_t>(1, std::min<size_t>(RH, pass_cap / (size_t)RW));
     if ((rc = ensure_workspace(c, rows_per_pass * RW, nc, M, o->coarse_only != 0))) return rc;
-    float *ray_out = d_out;
+    float *ray_out = d_out, *ray_depth = d_depth, *ray_opacity = d_opacity;
     if (s > 1) {
         if ((rc = ensure_bytes(c, (void **)&c->d_rayfb, &c->rayfb_floats, (size_t)RW * RH * 3 * sizeof(float)))) return rc;
         ray_out = c->d_rayfb;
+        if (d_depth || d_opacity) { // ray-level maps, one plane each, box-filtered like the colour below
+            if ((rc = ensure_bytes(c, (void **)&c->d_rayaux, &c->rayaux_bytes, (size_t)RW * RH * 2 * sizeof(float)))) return rc;
+            ray_depth = d_depth ? c->d_rayaux : nullptr;
+            ray_opacity = d_opacity ? c->d_rayaux + (size_t)RW * RH : nullptr;
+        }
     }
     const uint32_t n_passes_total = (uint32_t)((RH + rows_per_pass - 1) / rows_per_pass);
     if (seq) { // per MLP launch: {u32 ray queue head, u32 live-sample count, u64 evaluated samples}
@@ -653,6 +658,8 @@ int render_once(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *o, 
         float *pass_out = ray_out + (size_t)row * RW * 3;
         CompositeArgs ca{};
         ca.n_rays = n_rays; ca.far_ = cam->far_; ca.out = pass_out;
+        ca.depth = ray_depth ? ray_depth + (size_t)row * RW : nullptr;
+        ca.opacity = ray_opacity ? ray_opacity + (size_t)row * RW : nullptr;
         if (o->coarse_only) {
             ca.n = nc; ca.t = c->d_tc; ca.sigma = c->d_sc; ca.rgb = c->d_rgbc;
             Timed t(c, st, 2, 0, timing);
@@ -721,7 +728,9 @@ int render_once(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *o, 
     }
     if (s > 1) {
         Timed t(c, st, 2, 0, timing);
-        HIP_TRY(c, launch_box_downsample(c->d_rayfb, d_out, cw, ch, s, st));
+        HIP_TRY(c, launch_box_downsample(c->d_rayfb, d_out, cw, ch, s, 3, st));
+        if (d_depth) HIP_TRY(c, launch_box_downsample(ray_depth, d_depth, cw, ch, s, 1, st));
+        if (d_opacity) HIP_TRY(c, launch_box_downsample(ray_opacity, d_opacity, cw, ch, s, 1, st));
         t.done(c->last_render);
     }
     // the dominant-kernel events also feed nerf_kernel_time_query (ownership: see recycle_render)
@@ -831,14 +840,15 @@ int render_once(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *o, 
 // and the frame is rendered again.  The same loop grows the sample list when a pass wanted more entries than it had.  Margins are
 // measurements, not proofs: what this buys is that a network on which bf16 is less accurate than on the lego scene
 // calibrates itself or fails loudly (NERF_ERR_STATE) instead of returning a silently different frame.
-int nerfint::render_device(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *o, float *d_out, hipStream_t st,
-                           nerf_stats *stats) {
-    if (!o || !o->certify_zero) return render_once(c, cam, o, d_out, st, stats, nullptr);
+// Every attempt writes the whole frame -- colour and the requested maps -- so the maps returned are those of the frame that stands.
+int nerfint::render_device(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *o, float *d_out, float *d_depth, float *d_opacity,
+                           hipStream_t st, nerf_stats *stats) {
+    if (!o || !o->certify_zero) return render_once(c, cam, o, d_out, d_depth, d_opacity, st, stats, nullptr);
     constexpr int kMaxRetries = 8;
     uint64_t violations = 0;
     for (int attempt = 0;; ++attempt) {
         CertOutcome oc;
-        const int rc = render_once(c, cam, o, d_out, st, stats, &oc);
+        const int rc = render_once(c, cam, o, d_out, d_depth, d_opacity, st, stats, &oc);
         if (rc) return rc;
         bool again = false;
         std::string why;
@@ -986,7 +996,7 @@ void nerf_destroy(nerf_ctx *c) {
     DeviceGuard dg(c->device);
     (void)hipDeviceSynchronize();
     for (auto &n : c->net) { if (n.wstream) (void)hipFree(n.wstream); if (n.small) (void)hipFree(n.small); if (n.wstream_bf16v2) (void)hipFree(n.wstream_bf16v2); if (n.wstream_bf16v3) (void)hipFree(n.wstream_bf16v3); if (n.wstream_x3) (void)hipFree(n.wstream_x3); if (n.wstream_x2) (void)hipFree(n.wstream_x2); if (n.wstream_f16v2) (void)hipFree(n.wstream_f16v2); }
-    float *ptrs[] = {c->d_dirs, c->d_tc, c->d_sc, c->d_rgbc, c->d_tf, c->d_sf, c->d_rgbf, c->d_rayfb, c->d_out};
+    float *ptrs[] = {c->d_dirs, c->d_tc, c->d_sc, c->d_rgbc, c->d_tf, c->d_sf, c->d_rgbf, c->d_rayfb, c->d_rayaux, c->d_out};
     for (float *p : ptrs) if (p) (void)hipFree(p);
     if (c->d_scratch) (void)hipFree(c->d_scratch);
     if (c->d_clock) (void)hipFree(c->d_clock);
@@ -1127,14 +1137,20 @@ int nerf_forward_batch_ex(nerf_ctx *c, int which, int dtype, const float *pts, c
     return NERF_OK;
 } NERF_CATCH(c)
 
-int nerf_render_image_device(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *opts, float *d_rgb_out,
-                             void *stream, nerf_stats *stats) try {
+int nerf_render_image_aux_device(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *opts, float *d_rgb_out,
+                                 float *d_depth_out, float *d_opacity_out, void *stream, nerf_stats *stats) try {
     if (!c) return fail(nullptr, NERF_ERR_INVALID, "ctx is NULL");
     DeviceGuard dg(c->device);
-    return render_device(c, cam, opts, d_rgb_out, (hipStream_t)stream, stats);
+    return render_device(c, cam, opts, d_rgb_out, d_depth_out, d_opacity_out, (hipStream_t)stream, stats);
 } NERF_CATCH(c)
 
-int nerf_render_image(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *opts, float *rgb_out, nerf_stats *stats) try {
+int nerf_render_image_device(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *opts, float *d_rgb_out,
+                             void *stream, nerf_stats *stats) {
+    return nerf_render_image_aux_device(c, cam, opts, d_rgb_out, nullptr, nullptr, stream, stats);
+}
+
+int nerf_render_image_aux(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *opts, float *rgb_out, float *depth_out,
+                          float *opacity_out, nerf_stats *stats) try {
     if (!c) return fail(nullptr, NERF_ERR_INVALID, "ctx is NULL");
     if (!rgb_out) return fail(c, NERF_ERR_INVALID, "output pointer is NULL");
     int rc;
@@ -1150,14 +1166,24 @@ int nerf_render_image(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opt
         h = band_rows((int)h, opts->band_index, opts->band_count, opts->band_stripe_rows);
         if (h <= 0) return fail(c, NERF_ERR_INVALID, "this band has no rows (more bands than rows)");
     }
-    const size_t bytes = (size_t)w * h * 3 * sizeof(float);
-    if ((rc = ensure_bytes(c, (void **)&c->d_out, &c->out_floats, bytes))) return rc;
+    // staging: the colour, then each requested map (w x h floats)
+    const size_t px = (size_t)w * h, bytes = px * 3 * sizeof(float);
+    const size_t maps = (depth_out ? 1 : 0) + (opacity_out ? 1 : 0);
+    if ((rc = ensure_bytes(c, (void **)&c->d_out, &c->out_floats, bytes + maps * px * sizeof(float)))) return rc;
+    float *d_depth = depth_out ? c->d_out + 3 * px : nullptr;
+    float *d_opacity = opacity_out ? c->d_out + (3 + (depth_out ? 1 : 0)) * px : nullptr;
     nerf_stats local; // a synchronous render always reads its counters: a frame computed outside a split arithmetic's range is an error
-    if ((rc = render_device(c, cam, opts, c->d_out, c->stream, stats ? stats : &local))) return rc;
+    if ((rc = render_device(c, cam, opts, c->d_out, d_depth, d_opacity, c->stream, stats ? stats : &local))) return rc;
     HIP_TRY(c, hipMemcpyAsync(rgb_out, c->d_out, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (d_depth) HIP_TRY(c, hipMemcpyAsync(depth_out, d_depth, px * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (d_opacity) HIP_TRY(c, hipMemcpyAsync(opacity_out, d_opacity, px * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return NERF_OK;
 } NERF_CATCH(c)
+
+int nerf_render_image(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *opts, float *rgb_out, nerf_stats *stats) {
+    return nerf_render_image_aux(c, cam, opts, rgb_out, nullptr, nullptr, stats);
+}
 
 int nerf_band_rows(int window_rows, int band_index, int band_count, int band_stripe_rows) {
     if (window_rows < 0 || band_count < 0 || band_stripe_rows < 0 || (band_count > 1 && (band_index < 0 || band_index >= band_count)))

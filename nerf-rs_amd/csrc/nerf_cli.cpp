@@ -4,6 +4,7 @@
 // (include/nerf_mi355x.h) -- exactly what a Rust main.rs would do through the extern "C" block of INTEGRATION.md.
 //
 // With no flags it reproduces the reference's run: 256x256, 64 coarse + 128 fine samples, ./output.ppm.
+// --depth / --opacity add the expected-depth and opacity maps (nerf_render_image_aux) as one-channel PFM files.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -18,13 +19,14 @@ static void usage(const char *argv0) {
             "usage: %s [--scene DIR] [--width W] [--height H] [--coarse N] [--fine N] [--seed S] [--ssaa S]\n"
             "          [--coarse-only] [--crop X0,Y0,W,H] [--dtype f32|bf16|bf16x3|f16x2] [--skip-empty] [--skip-dead] [--hybrid-sampling] [--certify-zero]\n"
             "          [--device ID | --gpus N | --devices ID,ID,... [--gather host|peer|rccl]] [--frames K] [--out FILE.ppm]\n"
+            "          [--depth FILE.pfm] [--opacity FILE.pfm]\n"
             "defaults: --scene lego_rust --width 256 --height 256 --coarse 64 --fine 128 --out output.ppm\n",
             argv0);
 }
 
 int main(int argc, char **argv) {
     std::string scene = getenv("NERF_SCENE_DIR") ? getenv("NERF_SCENE_DIR") : "lego_rust";
-    std::string out = "output.ppm";
+    std::string out = "output.ppm", depth_path, opacity_path;
     int width = 256, height = 256, device = 0, frames = 1, gpus = 1, gather = NERF_GATHER_HOST; // src/lib.rs:657-658
     std::vector<int> devices;
     nerf_render_opts opts;
@@ -56,6 +58,8 @@ int main(int argc, char **argv) {
         else if (a == "--device") device = atoi(next());
         else if (a == "--frames") frames = atoi(next());
         else if (a == "--out") out = next();
+        else if (a == "--depth") depth_path = next();
+        else if (a == "--opacity") opacity_path = next();
         else if (a == "--crop") {
             if (sscanf(next(), "%d,%d,%d,%d", &opts.crop_x0, &opts.crop_y0, &opts.crop_w, &opts.crop_h) != 4) { usage(argv[0]); return 2; }
         } else { usage(argv[0]); return a == "--help" || a == "-h" ? 0 : 2; }
@@ -80,14 +84,16 @@ int main(int argc, char **argv) {
     printf("Rendering with %d coarse samples and %d fine samples per ray\n", opts.n_coarse, opts.n_fine); // :660-663
     const int ow = opts.crop_w > 0 ? opts.crop_w : width, oh = opts.crop_h > 0 ? opts.crop_h : height;
     std::vector<float> image((size_t)ow * oh * 3);
+    std::vector<float> depth(depth_path.empty() ? 0 : (size_t)ow * oh), opacity(opacity_path.empty() ? 0 : (size_t)ow * oh);
+    float *d_map = depth.empty() ? nullptr : depth.data(), *o_map = opacity.empty() ? nullptr : opacity.data();
     printf("Starting image rendering...\n"); // :667
     nerf_stats st;
     std::vector<nerf_stats> per(gpus);
     double best = 1e30;
     for (int f = 0; f < frames; ++f) {
         const auto t0 = std::chrono::steady_clock::now(); // Instant::now() :668
-        if (gpus == 1 ? nerf_render_image(ctx, &cam, &opts, image.data(), &st)
-                      : nerf_render_image_multi(ctxs.data(), gpus, &cam, &opts, gather, image.data(), per.data())) {
+        if (gpus == 1 ? nerf_render_image_aux(ctx, &cam, &opts, image.data(), d_map, o_map, &st)
+                      : nerf_render_image_multi_aux(ctxs.data(), gpus, &cam, &opts, gather, image.data(), d_map, o_map, per.data())) {
             fprintf(stderr, "error: %s\n", nerf_last_error(ctx));
             return 1;
         }
@@ -129,6 +135,10 @@ int main(int argc, char **argv) {
                (double)st.certify_margin[0], (double)st.certify_margin[1], (double)st.certify_headroom[0], (double)st.certify_headroom[1],
                (double)st.certify_max_error[0], (double)st.certify_max_error[1], st.n_certify_retries, st.n_certify_fallback_rays);
     if (nerf_save_ppm(out.c_str(), ow, oh, image.data())) { fprintf(stderr, "error: %s\n", nerf_last_error(nullptr)); return 1; } // :676
+    if ((d_map && nerf_save_pfm(depth_path.c_str(), ow, oh, d_map)) || (o_map && nerf_save_pfm(opacity_path.c_str(), ow, oh, o_map))) {
+        fprintf(stderr, "error: %s\n", nerf_last_error(nullptr));
+        return 1;
+    }
     for (nerf_ctx *c : ctxs) nerf_destroy(c);
     return 0;
 }

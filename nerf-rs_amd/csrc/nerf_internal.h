@@ -56,6 +56,7 @@ struct nerf_ctx {
     float *d_dirs = nullptr, *d_tc = nullptr, *d_sc = nullptr, *d_rgbc = nullptr, *d_tf = nullptr, *d_sf = nullptr,
           *d_rgbf = nullptr;
     float *d_rayfb = nullptr; size_t rayfb_floats = 0; // SSAA ray framebuffer
+    float *d_rayaux = nullptr; size_t rayaux_bytes = 0; // SSAA ray-level depth + opacity maps (nerf_render_image_aux)
     float *d_out = nullptr; size_t out_floats = 0;       // host-pointer render output staging
     // scratch for forward_batch / stage calls
     void *d_scratch = nullptr; size_t scratch_bytes = 0;
@@ -129,8 +130,9 @@ inline int band_rows(int h, int i, int n, int stripe) {
 inline int band_first_row(int h, int i, int n) { return i * (h / n) + std::min(i, h % n); } // contiguous bands only
 
 int ensure_bytes(nerf_ctx *c, void **p, size_t *cur, size_t need);
-// render_image on the context's device, asynchronous on `st` (synchronises only when stats != NULL)
-int render_device(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *o, float *d_out, hipStream_t st,
-                  nerf_stats *stats);
+// render_image on the context's device, asynchronous on `st` (synchronises only when stats != NULL); d_depth / d_opacity
+// (h x w floats each, like d_out's pixels) may be NULL (nerf_render_image_aux)
+int render_device(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *o, float *d_out, float *d_depth, float *d_opacity,
+                  hipStream_t st, nerf_stats *stats);
 
 } // namespace nerfint

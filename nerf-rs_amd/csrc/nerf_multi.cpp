@@ -73,11 +73,20 @@ struct Job {
     nerf_ctx *c;
     nerf_render_opts o;  // this context's band as a crop window
     float *d_band;       // where the band is rendered (device memory of c->device)
-    size_t band_floats;
-    size_t frame_off;    // float offset of the band inside the frame (contiguous bands)
+    int cap = 0;         // rows the buffer at d_band has room for (its planes are cap rows apart, see Plane)
+    int b0 = 0;          // first row of the band inside the frame (contiguous bands)
     int rows = 0;        // rows of the band
     nerf_stats *stats;
     int rc = NERF_OK;
+};
+
+// The colour and each requested map (nerf_render_image_multi_aux) travel as PLANES of one buffer: a buffer (band, slot or frame) of
+// R rows holds plane p at float offset w * R * off, rows packed (w * nch floats each).  Colour alone: one plane, the layout of
+// nerf_render_image_multi.  A slot of the all-gather holds every plane of its band: still ONE collective per frame.
+struct Plane {
+    float *host; // the caller's h x w x nch buffer
+    int nch;     // floats per pixel
+    int off;     // floats per pixel of the planes in front of it
 };
 
 } // namespace
@@ -104,8 +113,8 @@ void nerf_multi_release(void) {
     g_rccl.comms.clear();
 }
 
-int nerf_render_image_multi(nerf_ctx *const *ctxs, int n, const nerf_camera *cam, const nerf_render_opts *opts, int gather,
-                            float *rgb_out, nerf_stats *per_ctx) try {
+int nerf_render_image_multi_aux(nerf_ctx *const *ctxs, int n, const nerf_camera *cam, const nerf_render_opts *opts, int gather,
+                                float *rgb_out, float *depth_out, float *opacity_out, nerf_stats *per_ctx) try {
     if (!ctxs || n <= 0) return fail(nullptr, NERF_ERR_INVALID, "nerf_render_image_multi: no contexts");
     std::set<const nerf_ctx *> seen;
     for (int i = 0; i < n; ++i) {
@@ -122,7 +131,12 @@ int nerf_render_image_multi(nerf_ctx *const *ctxs, int n, const nerf_camera *cam
     if (opts->crop_w > 0 || opts->crop_h > 0) { x0 = opts->crop_x0; y0 = opts->crop_y0; cw = opts->crop_w; ch = opts->crop_h; }
     if (cw <= 0 || ch <= 0 || x0 < 0 || y0 < 0 || x0 + cw > cam->nx || y0 + ch > cam->ny)
         return fail(c0, NERF_ERR_INVALID, "crop window outside the frame");
-    const size_t row_floats = (size_t)cw * 3, frame_floats = row_floats * ch;
+    Plane planes[3];
+    int np = 0, unit = 0;
+    for (const Plane q : {Plane{rgb_out, 3, 0}, Plane{depth_out, 1, 0}, Plane{opacity_out, 1, 0}})
+        if (q.host) { planes[np] = q; planes[np++].off = unit; unit += q.nch; }
+    auto at = [&](float *base, int rows, int p) { return base + (size_t)cw * rows * planes[p].off; }; // plane p of a buffer of `rows` rows
+    const size_t row_floats = (size_t)cw * unit, frame_floats = row_floats * ch; // every plane
     // cost follows the scene => rows round-robin (stripes of one row); uniform cost => contiguous bands
     const int stripe = (n > 1 && (opts->skip_dead || opts->skip_empty || opts->certify_zero)) ? 1 : 0;
     const int max_rows = band_rows(ch, 0, n, stripe);   // band 0 is never shorter than another band
@@ -155,7 +169,7 @@ int nerf_render_image_multi(nerf_ctx *const *ctxs, int n, const nerf_camera *cam
     // Destination buffers.  HOST: each context's d_out holds its band.  PEER: ctxs[0]'s d_out holds the frame (its own band is
     // rendered in place), the others hold their band -- striped: ctxs[0]'s d_out = n slots + the frame.  RCCL: every d_out = n slots
     // (the in-place all-gather buffer), then the frame is assembled behind them when the bands are ragged or striped.
-    const bool ragged = (ch % n) != 0 || stripe > 0;
+    const bool ragged = (ch % n) != 0 || stripe > 0 || np > 1; // with maps a slot is not the frame's rows: compact it as well
     std::vector<Job> jobs(n);
     for (int i = 0; i < n; ++i) {
         nerf_ctx *c = ctxs[i];
@@ -171,11 +185,10 @@ int nerf_render_image_multi(nerf_ctx *const *ctxs, int n, const nerf_camera *cam
         J.o.crop_x0 = x0; J.o.crop_y0 = y0; J.o.crop_w = cw; J.o.crop_h = ch; // the caller's window; the band is selected by band_*
         J.o.band_index = i; J.o.band_count = n; J.o.band_stripe_rows = stripe;
         J.rows = rows;
-        J.band_floats = row_floats * rows;
-        J.frame_off = row_floats * b0;                                          // contiguous bands only
-        J.d_band = c->d_out;
-        if (gather == NERF_GATHER_PEER && i == 0) J.d_band = c->d_out + J.frame_off; // b0 == 0: the frame (contiguous) or slot 0 (striped)
-        if (gather == NERF_GATHER_RCCL) J.d_band = c->d_out + slot_floats * i;
+        J.b0 = b0;                                                              // contiguous bands only
+        J.d_band = c->d_out; J.cap = rows;
+        if (gather == NERF_GATHER_PEER && i == 0) J.cap = stripe ? max_rows : ch; // b0 == 0: the frame (contiguous) or slot 0 (striped)
+        if (gather == NERF_GATHER_RCCL) { J.d_band = c->d_out + slot_floats * i; J.cap = max_rows; }
         J.stats = per_ctx ? &per_ctx[i] : nullptr;
         if (per_ctx) memset(&per_ctx[i], 0, sizeof(nerf_stats));
     }
@@ -189,21 +202,27 @@ int nerf_render_image_multi(nerf_ctx *const *ctxs, int n, const nerf_camera *cam
         nerf_ctx *c = J.c;
         if (hipSetDevice(c->device) != hipSuccess) { J.rc = fail(c, NERF_ERR_HIP, "hipSetDevice failed"); return; }
         if (J.rows > 0) {
-            J.rc = render_device(c, cam, &J.o, J.d_band, c->stream, J.stats);
+            float *d_depth = depth_out ? at(J.d_band, J.cap, 1) : nullptr, *d_opacity = opacity_out ? at(J.d_band, J.cap, np - 1) : nullptr;
+            J.rc = render_device(c, cam, &J.o, J.d_band, d_depth, d_opacity, c->stream, J.stats);
             if (J.rc) return;
         }
         hipError_t e = hipSuccess;
-        if (gather == NERF_GATHER_HOST && J.band_floats) {
-            if (!stripe) e = hipMemcpyAsync(rgb_out + J.frame_off, J.d_band, J.band_floats * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-            else { // packed stripes -> every n-th stripe of the caller's frame: ONE strided copy (+ the frame's last, shorter stripe if it is ours)
-                const size_t sb = (size_t)stripe * row_floats * sizeof(float);
-                const int full = J.rows / stripe, tail = J.rows % stripe;
-                if (full) e = hipMemcpy2DAsync(rgb_out + (size_t)i * stripe * row_floats, sb * n, J.d_band, sb, sb, full, hipMemcpyDeviceToHost, c->stream);
-                if (e == hipSuccess && tail)
-                    e = hipMemcpyAsync(rgb_out + ((size_t)full * n + i) * stripe * row_floats, J.d_band + (size_t)full * stripe * row_floats,
-                                       (size_t)tail * row_floats * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+        if (gather == NERF_GATHER_HOST && J.rows) {
+            for (int p = 0; p < np && e == hipSuccess; ++p) {
+                const size_t rf = (size_t)cw * planes[p].nch; // floats per row of this plane
+                float *host = planes[p].host;
+                const float *src = at(J.d_band, J.cap, p);
+                if (!stripe) e = hipMemcpyAsync(host + rf * J.b0, src, rf * J.rows * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+                else { // packed stripes -> every n-th stripe of the caller's frame: ONE strided copy (+ the frame's last, shorter stripe if it is ours)
+                    const size_t sb = (size_t)stripe * rf * sizeof(float);
+                    const int full = J.rows / stripe, tail = J.rows % stripe;
+                    if (full) e = hipMemcpy2DAsync(host + (size_t)i * stripe * rf, sb * n, src, sb, sb, full, hipMemcpyDeviceToHost, c->stream);
+                    if (e == hipSuccess && tail)
+                        e = hipMemcpyAsync(host + ((size_t)full * n + i) * stripe * rf, src + (size_t)full * stripe * rf,
+                                           (size_t)tail * rf * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+                }
             }
-        } else if (gather == NERF_GATHER_PEER && i != 0 && J.band_floats) {
+        } else if (gather == NERF_GATHER_PEER && i != 0 && J.rows) {
             if (c->device != dev0) { // direct xGMI writes when the devices are peers (otherwise HIP stages the copy)
                 int can = 0;
                 if (hipDeviceCanAccessPeer(&can, c->device, dev0) == hipSuccess && can) {
@@ -212,7 +231,11 @@ int nerf_render_image_multi(nerf_ctx *const *ctxs, int n, const nerf_camera *cam
                 }
             }
             // contiguous: straight to the band's place in the frame; striped: to slot i, the copy kernel below assembles the frame
-            e = hipMemcpyPeerAsync(d_frame0 + (stripe ? slot_floats * i : J.frame_off), dev0, J.d_band, c->device, J.band_floats * sizeof(float), c->stream);
+            for (int p = 0; p < np && e == hipSuccess; ++p) {
+                const size_t rf = (size_t)cw * planes[p].nch;
+                float *dst = stripe ? at(d_frame0 + slot_floats * i, max_rows, p) : at(d_frame0, ch, p) + rf * J.b0;
+                e = hipMemcpyPeerAsync(dst, dev0, at(J.d_band, J.cap, p), c->device, rf * J.rows * sizeof(float), c->stream);
+            }
         }
         if (e == hipSuccess && gather != NERF_GATHER_RCCL) e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) J.rc = fail(c, NERF_ERR_HIP, std::string("band gather: ") + hipGetErrorString(e));
@@ -285,19 +308,24 @@ int nerf_render_image_multi(nerf_ctx *const *ctxs, int n, const nerf_camera *cam
         for (int i = 0; i < n; ++i) {
             nerf_ctx *c = ctxs[i];
             DeviceGuard dg(c->device);
-            if (stripe && rc_first == NERF_OK) // slots of packed rows -> frame behind them (every device ends up with the whole frame)
-                note(launch_bands_to_frame(c->d_out, c->d_out + slot_floats * n, cw, ch, n, stripe, slot_floats, c->stream), "bands -> frame");
-            else if (ragged && rc_first == NERF_OK) { // slots -> contiguous frame behind them (every device ends up with the whole frame)
-                float *frame = c->d_out + slot_floats * n;
-                for (int k = 0; k < n; ++k)
-                    if (jobs[k].band_floats)
-                        note(hipMemcpyAsync(frame + jobs[k].frame_off, c->d_out + slot_floats * k, jobs[k].band_floats * sizeof(float), hipMemcpyDeviceToDevice, c->stream), "slot compaction");
+            float *frame = c->d_out + slot_floats * n;
+            for (int p = 0; p < np && rc_first == NERF_OK; ++p) {
+                const size_t rf = (size_t)cw * planes[p].nch;
+                if (stripe) // slots of packed rows -> frame behind them (every device ends up with the whole frame)
+                    note(launch_bands_to_frame(at(c->d_out, max_rows, p), at(frame, ch, p), cw, ch, n, stripe, slot_floats, planes[p].nch, c->stream), "bands -> frame");
+                else if (ragged) { // slots -> contiguous frame behind them (every device ends up with the whole frame)
+                    for (int k = 0; k < n; ++k)
+                        if (jobs[k].rows)
+                            note(hipMemcpyAsync(at(frame, ch, p) + rf * jobs[k].b0, at(c->d_out + slot_floats * k, max_rows, p), rf * jobs[k].rows * sizeof(float),
+                                                hipMemcpyDeviceToDevice, c->stream), "slot compaction");
+                }
             }
         }
         d_frame0 = ragged ? c0->d_out + slot_floats * n : c0->d_out;
         if (rc_first == NERF_OK) {
             DeviceGuard dg(c0->device);
-            note(hipMemcpyAsync(rgb_out, d_frame0, frame_floats * sizeof(float), hipMemcpyDeviceToHost, c0->stream), "frame D2H");
+            for (int p = 0; p < np; ++p)
+                note(hipMemcpyAsync(planes[p].host, at(d_frame0, ch, p), (size_t)cw * planes[p].nch * ch * sizeof(float), hipMemcpyDeviceToHost, c0->stream), "frame D2H");
         }
         for (int i = 0; i < n; ++i) { // every stream, on every path: a context's buffers are read by the other contexts' streams
             DeviceGuard dg(ctxs[i]->device);
@@ -309,15 +337,22 @@ int nerf_render_image_multi(nerf_ctx *const *ctxs, int n, const nerf_camera *cam
     if (gather == NERF_GATHER_PEER) {
         DeviceGuard dg(c0->device);
         if (stripe) { // every band has arrived in its slot (the threads synchronised their streams): rows -> their places
-            HIP_TRY(c0, launch_bands_to_frame(c0->d_out, c0->d_out + slot_floats * n, cw, ch, n, stripe, slot_floats, c0->stream));
+            for (int p = 0; p < np; ++p)
+                HIP_TRY(c0, launch_bands_to_frame(at(c0->d_out, max_rows, p), at(c0->d_out + slot_floats * n, ch, p), cw, ch, n, stripe, slot_floats, planes[p].nch, c0->stream));
             d_frame0 = c0->d_out + slot_floats * n;
         }
-        HIP_TRY(c0, hipMemcpyAsync(rgb_out, d_frame0, frame_floats * sizeof(float), hipMemcpyDeviceToHost, c0->stream));
+        for (int p = 0; p < np; ++p)
+            HIP_TRY(c0, hipMemcpyAsync(planes[p].host, at(d_frame0, ch, p), (size_t)cw * planes[p].nch * ch * sizeof(float), hipMemcpyDeviceToHost, c0->stream));
         HIP_TRY(c0, hipStreamSynchronize(c0->stream));
     }
     return NERF_OK;
 } catch (const std::exception &e) {
     return fail(ctxs && n > 0 ? ctxs[0] : nullptr, NERF_ERR_INVALID, std::string("nerf_render_image_multi: ") + e.what());
+}
+
+int nerf_render_image_multi(nerf_ctx *const *ctxs, int n, const nerf_camera *cam, const nerf_render_opts *opts, int gather,
+                            float *rgb_out, nerf_stats *per_ctx) {
+    return nerf_render_image_multi_aux(ctxs, n, cam, opts, gather, rgb_out, nullptr, nullptr, per_ctx);
 }
 
 } // extern "C"

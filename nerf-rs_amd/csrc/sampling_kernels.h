@@ -51,6 +51,8 @@ struct CompositeArgs {
     const float *rgb;   // n_rays x n x 3
     float *out;         // n_rays x 3
     float *w_out;       // optional n_rays x n
+    float *depth;       // optional n_rays: sum_i (t_i * w_i) (nerf_render_image_aux)
+    float *opacity;     // optional n_rays: sum_i w_i
 };
 
 hipError_t sampling_init(void);
@@ -59,9 +61,10 @@ hipError_t launch_stratified(const RayGenArgs &a, int count, float near_, float 
                              hipStream_t st);
 hipError_t launch_resample(const ResampleArgs &a, hipStream_t st);
 hipError_t launch_composite(const CompositeArgs &a, hipStream_t st);
-hipError_t launch_box_downsample(const float *rays, float *out, int w, int h, int s, hipStream_t st);
-// multi-GPU: n gathered bands (slot_floats apart, rows packed) -> the h x w x 3 frame; stripe = 0: contiguous bands
-hipError_t launch_bands_to_frame(const float *slots, float *frame, int w, int h, int n, int stripe, size_t slot_floats, hipStream_t st);
+// nch floats per pixel (3: colour, 1: a depth or opacity map)
+hipError_t launch_box_downsample(const float *rays, float *out, int w, int h, int s, int nch, hipStream_t st);
+// multi-GPU: n gathered bands (slot_floats apart, rows packed) -> the h x w x nch frame; stripe = 0: contiguous bands
+hipError_t launch_bands_to_frame(const float *slots, float *frame, int w, int h, int n, int stripe, size_t slot_floats, int nch, hipStream_t st);
 size_t resample_lds_bytes(int nc, int nf);
 size_t composite_lds_bytes(int n);
 // ---- zero certification (nerf_render_opts.certify_zero; kernels and protocol: sampling_kernels.hip) ------------------------------------

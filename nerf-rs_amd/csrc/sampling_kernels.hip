@@ -305,10 +305,14 @@ __global__ __launch_bounds__(256) void k_resample(ResampleArgs a) {
 // samples of its 64 rays at a time in LDS (16 consecutive floats of t / sigma = one 64-B line per ray, 48 floats of rgb =
 // three lines), rows padded to odd strides so that the per-lane walk is bank-conflict free.  One wave per workgroup:
 // 21 KiB of LDS each, seven workgroups per CU.
+// kAux (nerf_render_image_aux): the same walk also sums the expected depth sum_i (t_i * w_i) and writes it with the opacity
+// (acc = sum_i w_i) -- two more registers and two 4-B stores per ray; the colour arithmetic is the same either way.  The
+// colour-only instance is the one compiled without it.
 constexpr int kCompChunk = 16;
 constexpr int kCompTS = kCompChunk + 1;     // row strides (floats)
 constexpr int kCompCS = 3 * kCompChunk + 1;
 
+template <bool kAux>
 __global__ __launch_bounds__(64) void k_composite(CompositeArgs a) {
     __shared__ float s_t[64 * kCompTS], s_sg[64 * kCompTS], s_col[64 * kCompCS];
     const int lane = threadIdx.x;
@@ -318,6 +322,7 @@ __global__ __launch_bounds__(64) void k_composite(CompositeArgs a) {
     const bool live = my_ray < a.n_rays;
     const int sub = lane & 15, rq = lane >> 4; // staging: 4 rays x 16 samples per wave-instruction
     float T = 1.0f, r = 0.0f, g = 0.0f, b = 0.0f, acc = 0.0f;
+    float dep = 0.0f;                           // kAux only
     bool cut = false;                           // compute_weights' early break (src/lib.rs:273-279): later weights are 0
     float t_cur = 0.0f;
     for (int c0 = 0; c0 < n; c0 += kCompChunk) {
@@ -358,6 +363,7 @@ __global__ __launch_bounds__(64) void k_composite(CompositeArgs a) {
             float delta = t_next - t_cur;              // sample_alpha
             if (delta < 0.0f) delta = 0.0f;
             const float al = 1.0f - expf(-s_sg[lane * kCompTS + i] * delta);
+            const float t_i = t_cur;                   // this sample's own t (== s_t[lane * kCompTS + i]), before the walk moves on
             t_cur = t_next;
             float wi = 0.0f;
             if (!cut) {
@@ -369,6 +375,7 @@ __global__ __launch_bounds__(64) void k_composite(CompositeArgs a) {
             const float *col = &s_col[lane * kCompCS + 3 * i];
             r += col[0] * wi; g += col[1] * wi; b += col[2] * wi; // integrate_ray :185-194, sample order
             acc += wi;
+            if constexpr (kAux) dep = dep + t_i * wi; // sample order, separate multiply and add (-ffp-contract=off)
         }
         __syncthreads();
     }
@@ -376,18 +383,23 @@ __global__ __launch_bounds__(64) void k_composite(CompositeArgs a) {
         const float bg = 1.0f * (1.0f - acc);
         float *o = a.out + 3 * (size_t)my_ray;
         o[0] = r + bg; o[1] = g + bg; o[2] = b + bg;
+        if constexpr (kAux) {
+            if (a.depth) a.depth[my_ray] = dep;
+            if (a.opacity) a.opacity[my_ray] = acc;
+        }
     }
 }
 
 // ---- SSAA box filter: out[i][j][c] = (sum over s x s sub-rays, row-major) * (1/(s*s)) -------------------
-__global__ void k_box_downsample(const float *__restrict__ rays, float *__restrict__ out, int w, int h, int s) {
+// nch channels per pixel: 3 for colour, 1 for a depth or opacity map (each map is its own plane: the colour pass stays as it was)
+__global__ void k_box_downsample(const float *__restrict__ rays, float *__restrict__ out, int w, int h, int s, int nch) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= w * h * 3) return;
-    const int c = idx % 3, j = (idx / 3) % w, i = idx / (3 * w);
+    if (idx >= w * h * nch) return;
+    const int c = idx % nch, j = (idx / nch) % w, i = idx / (nch * w);
     const int RW = w * s;
     float acc = 0.0f;
     for (int di = 0; di < s; ++di)
-        for (int dj = 0; dj < s; ++dj) acc += rays[3 * ((size_t)(i * s + di) * RW + (j * s + dj)) + c];
+        for (int dj = 0; dj < s; ++dj) acc += rays[nch * ((size_t)(i * s + di) * RW + (j * s + dj)) + c];
     out[idx] = acc * (1.0f / (float)(s * s));
 }
 
@@ -632,10 +644,10 @@ hipError_t launch_cert_audit(const unsigned *aux, const unsigned *aux_count, uns
 // ---- multi-GPU: bands -> frame ---------------------------------------------------------------------------------------------------
 // `slots` = n bands of slot_floats floats each (band b's rows packed at its start); band b holds the rows of the stripes b, b + n, ... of
 // the frame (stripe = `stripe` rows; stripe == 0: contiguous bands, the first h % n bands one row longer).  One thread per float4-less float:
-// the frame is 7.7 MB -- a copy kernel, HBM-bound.
-__global__ void k_bands_to_frame(const float *__restrict__ slots, float *__restrict__ frame, int w, int h, int n, int stripe, size_t slot_floats) {
+// the frame is 7.7 MB -- a copy kernel, HBM-bound.  nch floats per pixel: 3 for colour, 1 for a depth or opacity plane.
+__global__ void k_bands_to_frame(const float *__restrict__ slots, float *__restrict__ frame, int w, int h, int n, int stripe, size_t slot_floats, int nch) {
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t row_floats = (size_t)w * 3;
+    const size_t row_floats = (size_t)w * nch;
     if (idx >= row_floats * h) return;
     const int y = (int)(idx / row_floats);
     const size_t x = idx % row_floats;
@@ -648,10 +660,10 @@ __global__ void k_bands_to_frame(const float *__restrict__ slots, float *__restr
     frame[idx] = slots[(size_t)b * slot_floats + (size_t)j * row_floats + x];
 }
 
-hipError_t launch_bands_to_frame(const float *slots, float *frame, int w, int h, int n, int stripe, size_t slot_floats, hipStream_t st) {
-    const size_t total = (size_t)w * 3 * h;
+hipError_t launch_bands_to_frame(const float *slots, float *frame, int w, int h, int n, int stripe, size_t slot_floats, int nch, hipStream_t st) {
+    const size_t total = (size_t)w * nch * h;
     if (total == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_bands_to_frame, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, slots, frame, w, h, n, stripe, slot_floats);
+    hipLaunchKernelGGL(k_bands_to_frame, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, slots, frame, w, h, n, stripe, slot_floats, nch);
     return hipGetLastError();
 }
 
@@ -692,13 +704,14 @@ hipError_t launch_resample(const ResampleArgs &a, hipStream_t st) {
 
 hipError_t launch_composite(const CompositeArgs &a, hipStream_t st) {
     if (a.n_rays <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_composite, dim3((a.n_rays + 63) / 64), dim3(64), 0, st, a);
+    if (a.depth || a.opacity) hipLaunchKernelGGL(k_composite<true>, dim3((a.n_rays + 63) / 64), dim3(64), 0, st, a);
+    else hipLaunchKernelGGL(k_composite<false>, dim3((a.n_rays + 63) / 64), dim3(64), 0, st, a);
     return hipGetLastError();
 }
 
-hipError_t launch_box_downsample(const float *rays, float *out, int w, int h, int s, hipStream_t st) {
-    const int total = w * h * 3;
+hipError_t launch_box_downsample(const float *rays, float *out, int w, int h, int s, int nch, hipStream_t st) {
+    const int total = w * h * nch;
     if (total <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_box_downsample, dim3((total + 255) / 256), dim3(256), 0, st, rays, out, w, h, s);
+    hipLaunchKernelGGL(k_box_downsample, dim3((total + 255) / 256), dim3(256), 0, st, rays, out, w, h, s, nch);
     return hipGetLastError();
 }
