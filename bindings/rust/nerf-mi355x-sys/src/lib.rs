@@ -85,6 +85,11 @@ pub const NERF_GATHER_HOST: c_int = 0;
 pub const NERF_GATHER_PEER: c_int = 1;
 pub const NERF_GATHER_RCCL: c_int = 2;
 
+/// `alpha_mode` of `nerf_render_image_rgba8`: colour over the background with alpha 255; premultiplied colour + opacity; colour / opacity + opacity
+pub const NERF_ALPHA_OPAQUE: c_int = 0;
+pub const NERF_ALPHA_PREMULTIPLIED: c_int = 1;
+pub const NERF_ALPHA_STRAIGHT: c_int = 2;
+
 pub const NERF_OK: c_int = 0;
 pub const NERF_ERR_INVALID: c_int = -1;
 pub const NERF_ERR_IO: c_int = -2;
@@ -133,6 +138,13 @@ extern "C" {
     pub fn nerf_render_image_aux_device(ctx: *mut nerf_ctx, cam: *const nerf_camera, opts: *const nerf_render_opts,
                                         d_rgb_out: *mut f32, d_depth_out: *mut f32, d_opacity_out: *mut f32, stream: *mut c_void,
                                         stats: *mut nerf_stats) -> c_int;
+    /// The display-ready frame, packed on the device: h x w x 4 bytes R,G,B,A (the reference's render_image_rgba, src/lib.rs:700-726).
+    /// `background` null = white; `alpha_mode` = NERF_ALPHA_*.
+    pub fn nerf_render_image_rgba8(ctx: *mut nerf_ctx, cam: *const nerf_camera, opts: *const nerf_render_opts, background: *const f32,
+                                   alpha_mode: c_int, rgba_out: *mut u8, stats: *mut nerf_stats) -> c_int;
+    pub fn nerf_render_image_rgba8_device(ctx: *mut nerf_ctx, cam: *const nerf_camera, opts: *const nerf_render_opts,
+                                          background: *const f32, alpha_mode: c_int, d_rgba_out: *mut u8, stream: *mut c_void,
+                                          stats: *mut nerf_stats) -> c_int;
     /// render_image over several GPUs: `ctxs[i]` = one context per device, row bands on per-context host threads + streams,
     /// gathered into `rgb_out` by `gather` (NERF_GATHER_*).  The reference's counterpart is the rayon fan-out, src/lib.rs:533-557.
     pub fn nerf_render_image_multi(ctxs: *const *mut nerf_ctx, n: c_int, cam: *const nerf_camera, opts: *const nerf_render_opts,
@@ -140,6 +152,9 @@ extern "C" {
     pub fn nerf_render_image_multi_aux(ctxs: *const *mut nerf_ctx, n: c_int, cam: *const nerf_camera, opts: *const nerf_render_opts,
                                        gather: c_int, rgb_out: *mut f32, depth_out: *mut f32, opacity_out: *mut f32,
                                        per_ctx: *mut nerf_stats) -> c_int;
+    pub fn nerf_render_image_multi_rgba8(ctxs: *const *mut nerf_ctx, n: c_int, cam: *const nerf_camera, opts: *const nerf_render_opts,
+                                         gather: c_int, background: *const f32, alpha_mode: c_int, rgba_out: *mut u8,
+                                         per_ctx: *mut nerf_stats) -> c_int;
     pub fn nerf_create_multi(device_ids: *const c_int, n: c_int, out: *mut *mut nerf_ctx) -> c_int;
     pub fn nerf_multi_release();
     pub fn nerf_band_rows(window_rows: c_int, band_index: c_int, band_count: c_int, band_stripe_rows: c_int) -> c_int;
@@ -152,6 +167,8 @@ extern "C" {
     pub fn nerf_save_ppm(path: *const c_char, width: c_int, height: c_int, rgb: *const f32) -> c_int;
     /// one-channel PFM ("Pf", little-endian, rows bottom-up) of a width x height map given top row first
     pub fn nerf_save_pfm(path: *const c_char, width: c_int, height: c_int, values: *const f32) -> c_int;
+    /// PAM ("P7", RGB_ALPHA, MAXVAL 255) of height x width x 4 bytes
+    pub fn nerf_save_pam(path: *const c_char, width: c_int, height: c_int, rgba: *const u8) -> c_int;
     pub fn nerf_quantize_rgb8(rgb: *const f32, n_pixels: usize, out: *mut u8);
     pub fn nerf_quantize_rgba8(rgb: *const f32, n_pixels: usize, out: *mut u8);
     pub fn nerf_stage_ray_dirs(ctx: *mut nerf_ctx, cam: *const nerf_camera, x0: c_int, y0: c_int, w: c_int, h: c_int,
@@ -166,6 +183,9 @@ extern "C" {
                                    tau: f32, flags_out: *mut u8, t_new_out: *mut f32) -> c_int;
     pub fn nerf_stage_integrate(ctx: *mut nerf_ctx, n_rays: usize, n: c_int, far: f32, rgb_aos: *const f32,
                                 sigma: *const f32, t: *const f32, rgb_out: *mut f32, w_out: *mut f32) -> c_int;
+    pub fn nerf_stage_integrate_rgba8(ctx: *mut nerf_ctx, n_rays: usize, n: c_int, far: f32, rgb_aos: *const f32,
+                                      sigma: *const f32, t: *const f32, background: *const f32, alpha_mode: c_int,
+                                      rgba_out: *mut u8) -> c_int;
 }
 
 /// Compares the sizes of the `#[repr(C)]` mirrors above with the library's own structs; call once before anything else.

@@ -45,6 +45,17 @@ pub enum Gather {
     Rccl = sys::NERF_GATHER_RCCL as isize,
 }
 
+/// What the fourth byte of `Gpu::render_rgba8` holds, and what the colour bytes are relative to it (`NERF_ALPHA_*`).
+#[derive(Clone, Copy, Debug)]
+pub enum Alpha {
+    /// colour over the background, alpha 255 (the reference's `render_image_rgba`)
+    Opaque = sys::NERF_ALPHA_OPAQUE as isize,
+    /// colour = sum of weight x sample colour, alpha = opacity; the background is ignored
+    Premultiplied = sys::NERF_ALPHA_PREMULTIPLIED as isize,
+    /// colour = premultiplied colour / opacity (0 where the opacity is 0), alpha = opacity
+    Straight = sys::NERF_ALPHA_STRAIGHT as isize,
+}
+
 /// `camera_from_samples` (reference src/lib.rs:614-645) from the scene's tf_reference_samples.json.
 pub fn camera_from_json(json: &Path, width: i32, height: i32) -> Result<Camera, Error> {
     let mut cam = Camera::default();
@@ -118,6 +129,17 @@ impl Gpu {
             sys::nerf_render_image_aux(self.ctx, cam, opts, image.as_mut_ptr(), depth.as_mut_ptr(), opacity.as_mut_ptr(), &mut stats)
         })?;
         Ok((image, depth, opacity, stats))
+    }
+
+    /// The display-ready frame, packed on the device: R,G,B,A bytes, pixel (i, j) at `(i * w + j) * 4` (the reference's
+    /// `render_image_rgba`, src/lib.rs:700-726, is `render_rgba8(cam, opts, None, Alpha::Opaque)`).  `background` None = white.
+    pub fn render_rgba8(&self, cam: &Camera, opts: &RenderOpts, background: Option<[f32; 3]>, alpha: Alpha) -> Result<(Vec<u8>, Stats), Error> {
+        let (w, h) = if opts.crop_w > 0 || opts.crop_h > 0 { (opts.crop_w, opts.crop_h) } else { (cam.nx, cam.ny) };
+        let mut rgba = vec![0u8; (w.max(0) as usize) * (h.max(0) as usize) * 4];
+        let mut stats = Stats::default();
+        let bg = background.as_ref().map_or(std::ptr::null(), |b| b.as_ptr());
+        check(self.ctx, unsafe { sys::nerf_render_image_rgba8(self.ctx, cam, opts, bg, alpha as i32, rgba.as_mut_ptr(), &mut stats) })?;
+        Ok((rgba, stats))
     }
 }
 

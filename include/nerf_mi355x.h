@@ -246,6 +246,34 @@ int nerf_render_image_aux(nerf_ctx *ctx, const nerf_camera *cam, const nerf_rend
                           float *depth_out /* h x w or NULL */, float *opacity_out /* h x w or NULL */, nerf_stats *stats);
 int nerf_render_image_aux_device(nerf_ctx *ctx, const nerf_camera *cam, const nerf_render_opts *opts, float *d_rgb_out,
                                  float *d_depth_out, float *d_opacity_out, void *stream, nerf_stats *stats);
+/* ---- display-ready RGBA8, packed on the device, over any background -------------------------------------------------------------
+ * The reference's public display entry point is render_image_rgba(width, height) -> Uint8Array (src/lib.rs:700-726, pixels_to_rgba
+ * :582-592): the frame over white, quantised, alpha 255.  These entry points produce those bytes on the device -- 4 bytes per pixel come
+ * back instead of 12 -- and add what a compositor needs: another background, or a real alpha channel.
+ * For each ray, with w_i the exact compositing weights (zero after the T < 1e-4 cut) and c_i the sample colours:
+ *   C = sum_i w_i c_i per channel, A = sum_i w_i: summed in sample order in f32, separate multiply and add -- the sums of nerf_render_image
+ *   and the opacity of nerf_render_image_aux.  background B = (B_r, B_g, B_b); NULL = white, the reference.
+ *   NERF_ALPHA_OPAQUE         rgb = C + B * (1 - A), multiply and add rounded separately; alpha byte 255.  With B = 1 (or NULL) these are
+ *                             the bits of nerf_render_image.
+ *   NERF_ALPHA_PREMULTIPLIED  rgb = C (the opaque arithmetic with B = 0, which yields C exactly), alpha = A.  B is ignored.
+ *   NERF_ALPHA_STRAIGHT       rgb = C / A where A > 0, else 0 (correctly rounded f32 division, no reciprocal approximation), alpha = A.
+ * Every channel, alpha included, is quantised like nerf_quantize_rgb8 (save_ppm, src/lib.rs:573-577): clamp(v, 0, 1) * 255 + 0.5
+ * truncated, multiply and add separate; NaN becomes 0 by an explicit test.  Byte for byte the host quantiser.
+ * SSAA: the per-ray colour over B, and the per-ray A when the mode needs it, go through the same box filter as nerf_render_image_aux's
+ * maps; mode conversion and quantisation happen once per PIXEL on the filtered values (straight alpha divides the mean C by the mean A).
+ * Windows, bands, every mlp_dtype, coarse_only, skip_empty, skip_dead, hybrid_sampling and certify_zero behave as in the float entry
+ * points; with certify_zero the pack runs on the frame that stands after the retry loop.
+ * rgba_out: h x w x 4 bytes, row-major, R,G,B,A per pixel -- the layout nerf_quantize_rgba8 writes.  The f32 frame lives in the
+ * context's workspace (grown on demand: a warm call allocates nothing; the single-caller rule above covers it).
+ * NERF_ERR_INVALID: alpha_mode outside 0..2, a non-finite background component (finite values outside [0, 1] are allowed: the quantiser
+ * clamps), a NULL output. */
+enum { NERF_ALPHA_OPAQUE = 0, NERF_ALPHA_PREMULTIPLIED = 1, NERF_ALPHA_STRAIGHT = 2 };
+int nerf_render_image_rgba8(nerf_ctx *ctx, const nerf_camera *cam, const nerf_render_opts *opts, const float background[3],
+                            int alpha_mode, uint8_t *rgba_out, nerf_stats *stats);
+/* device output, asynchronous on `stream` like nerf_render_image_device (stats != NULL and certify_zero synchronise) */
+int nerf_render_image_rgba8_device(nerf_ctx *ctx, const nerf_camera *cam, const nerf_render_opts *opts, const float background[3],
+                                   int alpha_mode, uint8_t *d_rgba_out, void *stream, nerf_stats *stats);
+
 /* ---- S3 over several GPUs of one node (reference: the rayon fan-out over blocks + scatter, src/lib.rs:533-557) ------
  * ctxs[i] is one context per device (nerf_create / nerf_create_multi), each with both networks loaded (weights are
  * replicated).  Context i renders band i of n of the output rows (nerf_render_opts.band_*, set here: the caller's values are
@@ -269,6 +297,12 @@ int nerf_render_image_multi(nerf_ctx *const *ctxs, int n, const nerf_camera *cam
  * the same band slots as the colour (still one all-gather per frame with NERF_GATHER_RCCL). */
 int nerf_render_image_multi_aux(nerf_ctx *const *ctxs, int n, const nerf_camera *cam, const nerf_render_opts *opts, int gather,
                                 float *rgb_out, float *depth_out, float *opacity_out, nerf_stats *per_ctx);
+/* ... as RGBA8 (nerf_render_image_rgba8).  Each context packs its own band; a band is then one 32-bit word per pixel, which the gathers
+ * move as integers (one plane: still one all-gather per frame with NERF_GATHER_RCCL).  Same band partition.  Every band's counters are
+ * read (nerf_stats.n_nonfinite_points fails the call as in nerf_render_image), whether or not per_ctx is given.  rgba_out must be
+ * 4-byte aligned. */
+int nerf_render_image_multi_rgba8(nerf_ctx *const *ctxs, int n, const nerf_camera *cam, const nerf_render_opts *opts, int gather,
+                                  const float background[3], int alpha_mode, uint8_t *rgba_out, nerf_stats *per_ctx);
 /* n contexts, device_ids[i] each (NULL => devices 0..n-1); all-or-nothing. */
 int nerf_create_multi(const int *device_ids, int n, nerf_ctx **out /* n entries */);
 /* Frees the cached RCCL communicators of NERF_GATHER_RCCL (optional; call after the contexts are idle). */
@@ -305,6 +339,9 @@ void nerf_quantize_rgba8(const float *rgb, size_t n_pixels, uint8_t *out /* 4 n_
 /* One-channel PFM ("Pf"; scale -1 = little-endian; rows bottom-up as the format stores them) of width x height floats given top row
  * first (a depth or opacity map of nerf_render_image_aux).  Host-only. */
 int nerf_save_pfm(const char *path, int width, int height, const float *values);
+/* PAM ("P7", DEPTH 4, MAXVAL 255, TUPLTYPE RGB_ALPHA): the Netpbm format that holds an alpha channel; rgba = height x width x 4 bytes as
+ * nerf_render_image_rgba8 writes them.  Host-only. */
+int nerf_save_pam(const char *path, int width, int height, const uint8_t *rgba);
 
 /* ---- stage entry points (device execution, host buffers): the individual functions of render_block, exposed so
  * that a host that owns ray setup can call them and so that each stage has its own parity test ------------- */
@@ -330,6 +367,10 @@ int nerf_stage_hybrid_flags(nerf_ctx *ctx, size_t n_rays, int nc, int nf, float 
 /* integrate_ray (src/lib.rs:176-195); w_out (n_rays x n) optional */
 int nerf_stage_integrate(nerf_ctx *ctx, size_t n_rays, int n, float far_, const float *rgb_aos, const float *sigma,
                          const float *t, float *rgb_out, float *w_out);
+/* integrate_ray + the RGBA8 pack (nerf_render_image_rgba8's arithmetic for n_rays rays of n > 0 samples each, one "pixel" per ray);
+ * rgba_out: n_rays x 4 bytes */
+int nerf_stage_integrate_rgba8(nerf_ctx *ctx, size_t n_rays, int n, float far_, const float *rgb_aos, const float *sigma,
+                               const float *t, const float background[3], int alpha_mode, uint8_t *rgba_out);
 
 /* "" for the product build.  Tuning / timing-only builds (make variant: some of their switches make results WRONG on purpose)
  * report "NAME: compile definitions"; a host should refuse such a library outside experiments (the Python loader does). */
@@ -338,7 +379,8 @@ const char *nerf_build_variant(void);
  * n_nonfinite_points, nerf_check_network_blob, nerf_stage_hybrid_flags, nerf_build_variant; 4: nerf_render_opts.certify_zero; 5: nerf_stats.
  * n_certify_* / certify_margin / certify_headroom / certify_max_error, renders fail on n_nonfinite_points != 0,
  * nerf_render_opts.band_*, nerf_band_rows, nerf_debug_certify_policy; additive: nerf_render_image_aux, nerf_render_image_aux_device,
- * nerf_render_image_multi_aux, nerf_save_pfm). */
+ * nerf_render_image_multi_aux, nerf_save_pfm, nerf_render_image_rgba8, nerf_render_image_rgba8_device, nerf_render_image_multi_rgba8,
+ * nerf_stage_integrate_rgba8, nerf_save_pam, NERF_ALPHA_*). */
 int nerf_abi_version(void);
 /* sizeof(nerf_camera), sizeof(nerf_render_opts), sizeof(nerf_stats) as this library was built: lets a binding written in
  * another language (the Rust `-sys` crate, ctypes) check its struct mirrors at start-up. */

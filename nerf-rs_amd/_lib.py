@@ -7,6 +7,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
 
 f32p = C.POINTER(C.c_float)
+u8p = C.POINTER(C.c_uint8)
 u32p = C.POINTER(C.c_uint32)
 
 
@@ -80,6 +81,11 @@ PROTOTYPES = {
                                                C.c_void_p, C.POINTER(CStats)]),
     "nerf_render_image_multi_aux": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(CCamera), C.POINTER(COpts), C.c_int, f32p,
                                               f32p, f32p, C.POINTER(CStats)]),
+    "nerf_render_image_rgba8": (C.c_int, [C.c_void_p, C.POINTER(CCamera), C.POINTER(COpts), f32p, C.c_int, u8p, C.POINTER(CStats)]),
+    "nerf_render_image_rgba8_device": (C.c_int, [C.c_void_p, C.POINTER(CCamera), C.POINTER(COpts), f32p, C.c_int, C.c_void_p, C.c_void_p,
+                                                 C.POINTER(CStats)]),
+    "nerf_render_image_multi_rgba8": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(CCamera), C.POINTER(COpts), C.c_int, f32p, C.c_int,
+                                                u8p, C.POINTER(CStats)]),
     "nerf_create_multi": (C.c_int, [C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p)]),
     "nerf_multi_release": (None, []),
     "nerf_band_rows": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
@@ -91,6 +97,7 @@ PROTOTYPES = {
                                           C.POINTER(CCamera)]),
     "nerf_save_ppm": (C.c_int, [C.c_char_p, C.c_int, C.c_int, f32p]),
     "nerf_save_pfm": (C.c_int, [C.c_char_p, C.c_int, C.c_int, f32p]),
+    "nerf_save_pam": (C.c_int, [C.c_char_p, C.c_int, C.c_int, u8p]),
     "nerf_quantize_rgb8": (None, [f32p, C.c_size_t, C.POINTER(C.c_uint8)]),
     "nerf_quantize_rgba8": (None, [f32p, C.c_size_t, C.POINTER(C.c_uint8)]),
     "nerf_stage_ray_dirs": (C.c_int, [C.c_void_p, C.POINTER(CCamera), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p]),
@@ -101,6 +108,7 @@ PROTOTYPES = {
     "nerf_stage_hybrid_flags": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_float, C.c_uint64, u32p, f32p, f32p, f32p,
                                           C.c_float, C.POINTER(C.c_uint8), f32p]),
     "nerf_stage_integrate": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_float, f32p, f32p, f32p, f32p, f32p]),
+    "nerf_stage_integrate_rgba8": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_float, f32p, f32p, f32p, f32p, C.c_int, u8p]),
 }
 
 

@@ -14,10 +14,12 @@ import json
 import numpy as np
 
 from . import _lib
-from ._lib import CCamera, COpts, CStats, NerfError, check, f32p, u32p
+from ._lib import CCamera, COpts, CStats, NerfError, check, f32p, u8p, u32p
 
 NET_COARSE, NET_FINE = 0, 1
 MLP_F32, MLP_BF16 = 0, 1
+ALPHA_OPAQUE, ALPHA_PREMULTIPLIED, ALPHA_STRAIGHT = 0, 1, 2
+_ALPHAS = {"opaque": 0, "premultiplied": 1, "straight": 2}
 _DTYPES = {"f32": 0, "float32": 0, 0: 0, "bf16": 1, "bfloat16": 1, 1: 1, "bf16x3": 2, 2: 2, "f16x2": 3, 3: 3}
 
 
@@ -27,6 +29,25 @@ def _f32(a):
 
 def _p(a):
     return a.ctypes.data_as(f32p)
+
+
+def _background(background):
+    """None (white, the reference) or three floats -> what the C ABI takes (the array must outlive the call)."""
+    if background is None:
+        return None, None
+    b = _f32(background).reshape(-1)
+    if b.size != 3:
+        raise NerfError(-1, "background must be None or three floats (R, G, B)")
+    return b, _p(b)
+
+
+def _alpha(alpha):
+    """'opaque' | 'premultiplied' | 'straight' or the NERF_ALPHA_* number (the library rejects a number out of range)."""
+    if isinstance(alpha, str):
+        if alpha not in _ALPHAS:
+            raise NerfError(-1, "alpha must be 'opaque', 'premultiplied' or 'straight'")
+        return _ALPHAS[alpha]
+    return int(alpha)
 
 
 class Stats:
@@ -127,6 +148,16 @@ class Renderer:
         out = np.empty((R, 3), np.float32); w = np.empty((R, n), np.float32)
         check(self._L.nerf_stage_integrate(self.handle, R, n, far, _p(c), _p(s), _p(t), _p(out), _p(w)), self.handle)
         return out, w
+
+    def stage_integrate_rgba8(self, rgb, sigma, t, far, background=None, alpha="opaque"):
+        """integrate_ray + the RGBA8 pack (nerf_stage_integrate_rgba8) -> (R, 4) uint8."""
+        c = _f32(rgb); s = _f32(sigma); t = _f32(t)
+        R, n = t.shape
+        out = np.empty((R, 4), np.uint8)
+        keep, bg = _background(background)
+        check(self._L.nerf_stage_integrate_rgba8(self.handle, R, n, far, _p(c), _p(s), _p(t), bg, _alpha(alpha),
+                                                 out.ctypes.data_as(u8p)), self.handle)
+        return out
 
 
 class Network:
@@ -310,6 +341,35 @@ def render_image(coarse, fine, camera, fine_samples_per_ray=128, *, seed=0, coar
     return (out, Stats(st)) if return_stats else out
 
 
+def render_image_rgba8(coarse, fine, camera, fine_samples_per_ray=128, *, background=None, alpha="opaque", seed=0, coarse_only=False,
+                       crop=None, ssaa=1, dtype="f32", skip_empty=False, skip_dead=False, hybrid_sampling=False, certify_zero=False,
+                       band=None, return_stats=False, device_out=None, stream=0):
+    """The display-ready frame (nerf_render_image_rgba8; the reference's render_image_rgba, src/lib.rs:700-726) -> (h, w, 4) uint8,
+    R,G,B,A per pixel, packed on the device.
+
+    background: None (white, the reference) or (R, G, B) floats.  alpha: "opaque" (colour over the background, alpha 255),
+    "premultiplied" (colour sum_i w_i c_i, alpha = opacity; the background is ignored) or "straight" (colour / opacity).
+    The other options are render_image's.  device_out: raw device pointer (int) of h * w * 4 bytes, asynchronous on `stream`
+    (returns None / stats)."""
+    R = coarse.renderer
+    if fine is not None and fine.renderer is not R:
+        raise NerfError(-1, "coarse and fine networks must live in the same Renderer")
+    opts = RenderOpts(camera.samples_per_ray, fine_samples_per_ray, coarse_only, crop, ssaa, seed, dtype, skip_empty, skip_dead, hybrid_sampling, certify_zero, band)
+    o = opts.to_c()
+    st = CStats()
+    keep, bg = _background(background)
+    if device_out is not None:
+        check(R._L.nerf_render_image_rgba8_device(R.handle, C.byref(camera.c), C.byref(o), bg, _alpha(alpha), device_out, stream,
+                                                  C.byref(st) if return_stats else None), R.handle)
+        return Stats(st) if return_stats else None
+    shape = opts.out_shape(camera)
+    if shape[0] <= 0 or shape[1] <= 0:
+        raise NerfError(-1, "crop window outside the frame")
+    out = np.empty(shape[:2] + (4,), np.uint8)
+    check(R._L.nerf_render_image_rgba8(R.handle, C.byref(camera.c), C.byref(o), bg, _alpha(alpha), out.ctypes.data_as(u8p), C.byref(st)), R.handle)
+    return (out, Stats(st)) if return_stats else out
+
+
 GATHER_HOST, GATHER_PEER, GATHER_RCCL = 0, 1, 2
 _GATHERS = {"host": 0, "peer": 1, "rccl": 2, 0: 0, 1: 1, 2: 2}
 
@@ -342,6 +402,27 @@ def render_image_multi(renderers, camera, fine_samples_per_ray=128, *, gather="h
     return (out, [Stats(s) for s in st]) if return_stats else out
 
 
+def render_image_multi_rgba8(renderers, camera, fine_samples_per_ray=128, *, gather="host", background=None, alpha="opaque", seed=0,
+                             coarse_only=False, crop=None, ssaa=1, dtype="f32", skip_empty=False, skip_dead=False, hybrid_sampling=False,
+                             certify_zero=False, return_stats=False):
+    """render_image_rgba8 fanned out over several Renderers (nerf_render_image_multi_rgba8): every context packs its own band, the
+    gathers move one 32-bit word per pixel.  Options as render_image_multi / render_image_rgba8."""
+    L = _lib.load_library()
+    n = len(renderers)
+    handles = (C.c_void_p * n)(*[r.handle for r in renderers])
+    opts = RenderOpts(camera.samples_per_ray, fine_samples_per_ray, coarse_only, crop, ssaa, seed, dtype, skip_empty, skip_dead, hybrid_sampling, certify_zero)
+    o = opts.to_c()
+    shape = opts.out_shape(camera)
+    if shape[0] <= 0 or shape[1] <= 0:
+        raise NerfError(-1, "crop window outside the frame")
+    out = np.empty(shape[:2] + (4,), np.uint8)
+    st = (CStats * n)()
+    keep, bg = _background(background)
+    check(L.nerf_render_image_multi_rgba8(handles, n, C.byref(camera.c), C.byref(o), _GATHERS[gather], bg, _alpha(alpha),
+                                          out.ctypes.data_as(u8p), st if return_stats else None), renderers[0].handle if n else None)
+    return (out, [Stats(s) for s in st]) if return_stats else out
+
+
 def quantize_rgb8(pixels):
     a = _f32(pixels)
     out = np.empty(a.shape, np.uint8)
@@ -371,6 +452,14 @@ def save_pfm(path, width, height, values):
     if a.size != width * height:
         raise NerfError(-1, "values.len() != width * height")
     check(_lib.load_library().nerf_save_pfm(str(path).encode(), width, height, _p(a)))
+
+
+def save_pam(path, width, height, rgba):
+    """An RGBA8 frame as a PAM (nerf_save_pam: "P7", TUPLTYPE RGB_ALPHA, MAXVAL 255); rgba: (height, width, 4) uint8."""
+    a = np.ascontiguousarray(rgba, dtype=np.uint8)
+    if a.size != width * height * 4:
+        raise NerfError(-1, "rgba.len() != width * height * 4")
+    check(_lib.load_library().nerf_save_pam(str(path).encode(), width, height, a.ctypes.data_as(u8p)))
 
 
 def load_tf_samples(path):

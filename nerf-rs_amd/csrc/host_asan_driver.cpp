@@ -3,7 +3,7 @@
 // touches the device).  tests/test_host_asan.py feeds it valid, truncated, oversized and malformed weight directories, blobs and
 // camera JSON files: every call must come back with a status code and a message -- a sanitizer report aborts with a non-zero exit.
 //   host_asan_driver check_dir <dir> | pack_dir <dir> <blob> | check_blob <blob> | camera_json <json> <w> <h> |
-//                    debug_pack <dir> | quantize | save_ppm <path> <w> <h> | save_pfm <path> <w> <h> | split
+//                    debug_pack <dir> | quantize | save_ppm <path> <w> <h> | save_pfm <path> <w> <h> | save_pam <path> <w> <h> | split
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -68,6 +68,21 @@ int main(int argc, char **argv) {
         std::vector<float> m(w > 0 && h > 0 ? (size_t)w * h : 0);
         for (size_t i = 0; i < m.size(); ++i) m[i] = (float)(i % 89) * 0.0625f - 1.5f;
         return report("save_pfm", nerf_save_pfm(argv[2], w, h, m.data()));
+    }
+    if (cmd == "save_pam" && argc == 5) { // the buffer is exactly w x h x 4 bytes: an over-read is a report (1 x 1 included)
+        const int w = atoi(argv[3]), h = atoi(argv[4]);
+        std::vector<uint8_t> px(w > 0 && h > 0 ? (size_t)w * h * 4 : 0);
+        for (size_t i = 0; i < px.size(); ++i) px[i] = (uint8_t)(i * 37u + 11u);
+        int rc = nerf_save_pam(argv[2], w, h, px.data());
+        if (!rc) { // read it back: header + bytes, nothing more
+            const std::string hdr = "P7\nWIDTH " + std::to_string(w) + "\nHEIGHT " + std::to_string(h) + "\nDEPTH 4\nMAXVAL 255\nTUPLTYPE RGB_ALPHA\nENDHDR\n";
+            std::vector<char> got(hdr.size() + px.size() + 1);
+            FILE *f = fopen(argv[2], "rb");
+            const size_t n = f ? fread(got.data(), 1, got.size(), f) : 0;
+            if (f) fclose(f);
+            if (n != hdr.size() + px.size() || memcmp(got.data(), hdr.data(), hdr.size()) || memcmp(got.data() + hdr.size(), px.data(), px.size())) rc = 99;
+        }
+        return report("save_pam", rc);
     }
     if (cmd == "split") {
         const float v[] = {0.f, -0.f, 1.f, -3.14159274f, 65504.f, 7e4f, 1e-8f, 6e-8f, 1e30f, -1e-30f, NAN, INFINITY};

@@ -473,6 +473,18 @@ int save_pfm(const std::string &path, int width, int height, const float *values
     return NERF_OK;
 }
 
+int save_pam(const std::string &path, int width, int height, const uint8_t *rgba, std::string &err) {
+    if (width <= 0 || height <= 0) { err = "save_pam: bad size"; return NERF_ERR_INVALID; }
+    FILE *f = fopen(path.c_str(), "wb");
+    if (!f) { err = "save_pam: cannot create " + path; return NERF_ERR_IO; }
+    fprintf(f, "P7\nWIDTH %d\nHEIGHT %d\nDEPTH 4\nMAXVAL 255\nTUPLTYPE RGB_ALPHA\nENDHDR\n", width, height);
+    const size_t bytes = (size_t)width * height * 4;
+    bool ok = fwrite(rgba, 1, bytes, f) == bytes;
+    if (fclose(f) != 0) ok = false;
+    if (!ok) { err = "save_pam: short write " + path; return NERF_ERR_IO; }
+    return NERF_OK;
+}
+
 int certify_policy(float margin, uint64_t audited, uint64_t violations, float headroom, float max_error, float *new_margin) {
     if (new_margin) *new_margin = margin;
     if (!audited) return 0; // nothing was certified in front of a predicted cut: nothing to judge

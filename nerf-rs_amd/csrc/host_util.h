@@ -62,6 +62,8 @@ int read_blob_file(const std::string &path, std::vector<float> &wstream, std::ve
 int save_ppm(const std::string &path, int width, int height, const float *rgb, std::string &err);
 // 1-channel PFM ("Pf", little-endian, rows bottom-up) of a top-row-first map
 int save_pfm(const std::string &path, int width, int height, const float *values, std::string &err);
+// PAM (P7, RGB_ALPHA, MAXVAL 255) of height x width x 4 bytes
+int save_pam(const std::string &path, int width, int height, const uint8_t *rgba, std::string &err);
 
 // certify_zero's audit policy (nerf_api.cpp render_device; exposed host-only as nerf_debug_certify_policy so that it is tested without a
 // GPU).  Given what the audit of one network found in one frame, decide whether the frame stands and, if not, the widened margin:

@@ -12,6 +12,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <mutex>
 #include <set>
 #include <string>
@@ -362,7 +363,7 @@ struct CertOutcome {
 };
 
 int render_once(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *o, float *d_out, float *d_depth, float *d_opacity, hipStream_t st,
-                nerf_stats *stats, CertOutcome *cert) {
+                nerf_stats *stats, CertOutcome *cert, const float *background) {
     int rc;
     if ((rc = check_camera(c, cam))) return rc;
     if (!o) return fail(c, NERF_ERR_INVALID, "opts is NULL");
@@ -660,6 +661,7 @@ int render_once(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *o, 
         ca.n_rays = n_rays; ca.far_ = cam->far_; ca.out = pass_out;
         ca.depth = ray_depth ? ray_depth + (size_t)row * RW : nullptr;
         ca.opacity = ray_opacity ? ray_opacity + (size_t)row * RW : nullptr;
+        if (background) { ca.use_bg = 1; ca.bg[0] = background[0]; ca.bg[1] = background[1]; ca.bg[2] = background[2]; }
         if (o->coarse_only) {
             ca.n = nc; ca.t = c->d_tc; ca.sigma = c->d_sc; ca.rgb = c->d_rgbc;
             Timed t(c, st, 2, 0, timing);
@@ -842,13 +844,13 @@ int render_once(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *o, 
 // calibrates itself or fails loudly (NERF_ERR_STATE) instead of returning a silently different frame.
 // Every attempt writes the whole frame -- colour and the requested maps -- so the maps returned are those of the frame that stands.
 int nerfint::render_device(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *o, float *d_out, float *d_depth, float *d_opacity,
-                           hipStream_t st, nerf_stats *stats) {
-    if (!o || !o->certify_zero) return render_once(c, cam, o, d_out, d_depth, d_opacity, st, stats, nullptr);
+                           hipStream_t st, nerf_stats *stats, const float *background) {
+    if (!o || !o->certify_zero) return render_once(c, cam, o, d_out, d_depth, d_opacity, st, stats, nullptr, background);
     constexpr int kMaxRetries = 8;
     uint64_t violations = 0;
     for (int attempt = 0;; ++attempt) {
         CertOutcome oc;
-        const int rc = render_once(c, cam, o, d_out, d_depth, d_opacity, st, stats, &oc);
+        const int rc = render_once(c, cam, o, d_out, d_depth, d_opacity, st, stats, &oc, background);
         if (rc) return rc;
         bool again = false;
         std::string why;
@@ -886,6 +888,61 @@ int nerfint::render_device(nerf_ctx *c, const nerf_camera *cam, const nerf_rende
             return fail(c, NERF_ERR_STATE, msg);
         }
     }
+}
+
+int nerfint::output_window(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *opts, size_t *w_out, size_t *h_out) {
+    int rc;
+    if ((rc = check_camera(c, cam))) return rc;
+    if (!opts) return fail(c, NERF_ERR_INVALID, "opts is NULL");
+    const bool crop = opts->crop_w > 0 || opts->crop_h > 0;
+    const long long w = crop ? opts->crop_w : cam->nx;
+    long long h = crop ? opts->crop_h : cam->ny;
+    if (w <= 0 || h <= 0) return fail(c, NERF_ERR_INVALID, "crop window outside the frame");
+    if (opts->band_count > 1) {
+        if (opts->band_index < 0 || opts->band_index >= opts->band_count || opts->band_stripe_rows < 0) return fail(c, NERF_ERR_INVALID, "band_index / band_count / band_stripe_rows out of range");
+        h = band_rows((int)h, opts->band_index, opts->band_count, opts->band_stripe_rows);
+        if (h <= 0) return fail(c, NERF_ERR_INVALID, "this band has no rows (more bands than rows)");
+    }
+    *w_out = (size_t)w; *h_out = (size_t)h;
+    return NERF_OK;
+}
+
+namespace {
+
+// what the three alpha modes ask of the compositing kernel: the background it adds (NULL: the reference's white) and whether the pack
+// kernel needs the opacity plane
+int check_rgba8(nerf_ctx *c, const float *background, int alpha_mode, const void *out, const float **bg_composite) {
+    static const float kBlack[3] = {0.0f, 0.0f, 0.0f};
+    if (alpha_mode != NERF_ALPHA_OPAQUE && alpha_mode != NERF_ALPHA_PREMULTIPLIED && alpha_mode != NERF_ALPHA_STRAIGHT)
+        return fail(c, NERF_ERR_INVALID, "alpha_mode must be NERF_ALPHA_OPAQUE, NERF_ALPHA_PREMULTIPLIED or NERF_ALPHA_STRAIGHT");
+    if (background && !(std::isfinite(background[0]) && std::isfinite(background[1]) && std::isfinite(background[2])))
+        return fail(c, NERF_ERR_INVALID, "background components must be finite");
+    if (!out) return fail(c, NERF_ERR_INVALID, "output pointer is NULL");
+    *bg_composite = alpha_mode == NERF_ALPHA_OPAQUE ? background : kBlack; // premultiplied / straight: C + 0 * (1 - A) = C
+    return NERF_OK;
+}
+
+size_t align4(size_t n) { return (n + 3) & ~(size_t)3; }
+
+} // namespace
+
+// The f32 frame (and the opacity plane of the two alpha modes) live in the context's own workspace, grown on demand: a warm call
+// allocates nothing.  Conversion and quantisation run once per pixel, on the frame that stands (behind the box filter and behind
+// certify_zero's retry loop, both inside render_device).
+int nerfint::render_rgba8_device(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *o, const float *background, int alpha_mode,
+                                 uint8_t *d_rgba, hipStream_t st, nerf_stats *stats) {
+    int rc;
+    const float *bg = nullptr;
+    if ((rc = check_rgba8(c, background, alpha_mode, d_rgba, &bg))) return rc;
+    size_t w = 0, h = 0;
+    if ((rc = output_window(c, cam, o, &w, &h))) return rc;
+    const size_t px = w * h, op_at = align4(3 * px);
+    if ((rc = ensure_bytes(c, (void **)&c->d_pack, &c->pack_bytes, (op_at + px) * sizeof(float)))) return rc;
+    float *d_rgb = c->d_pack, *d_opacity = alpha_mode == NERF_ALPHA_OPAQUE ? nullptr : c->d_pack + op_at;
+    if ((rc = render_device(c, cam, o, d_rgb, nullptr, d_opacity, st, stats, bg))) return rc;
+    HIP_TRY(c, launch_pack_rgba8(d_rgb, d_opacity, (uint32_t *)d_rgba, px, alpha_mode, st));
+    if (stats) HIP_TRY(c, hipStreamSynchronize(st)); // as the float variant: with stats the output is complete on return
+    return NERF_OK;
 }
 
 // ================================================================================================
@@ -996,7 +1053,7 @@ void nerf_destroy(nerf_ctx *c) {
     DeviceGuard dg(c->device);
     (void)hipDeviceSynchronize();
     for (auto &n : c->net) { if (n.wstream) (void)hipFree(n.wstream); if (n.small) (void)hipFree(n.small); if (n.wstream_bf16v2) (void)hipFree(n.wstream_bf16v2); if (n.wstream_bf16v3) (void)hipFree(n.wstream_bf16v3); if (n.wstream_x3) (void)hipFree(n.wstream_x3); if (n.wstream_x2) (void)hipFree(n.wstream_x2); if (n.wstream_f16v2) (void)hipFree(n.wstream_f16v2); }
-    float *ptrs[] = {c->d_dirs, c->d_tc, c->d_sc, c->d_rgbc, c->d_tf, c->d_sf, c->d_rgbf, c->d_rayfb, c->d_rayaux, c->d_out};
+    float *ptrs[] = {c->d_dirs, c->d_tc, c->d_sc, c->d_rgbc, c->d_tf, c->d_sf, c->d_rgbf, c->d_rayfb, c->d_rayaux, c->d_out, c->d_pack};
     for (float *p : ptrs) if (p) (void)hipFree(p);
     if (c->d_scratch) (void)hipFree(c->d_scratch);
     if (c->d_clock) (void)hipFree(c->d_clock);
@@ -1154,20 +1211,11 @@ int nerf_render_image_aux(nerf_ctx *c, const nerf_camera *cam, const nerf_render
     if (!c) return fail(nullptr, NERF_ERR_INVALID, "ctx is NULL");
     if (!rgb_out) return fail(c, NERF_ERR_INVALID, "output pointer is NULL");
     int rc;
-    if ((rc = check_camera(c, cam))) return rc;
-    if (!opts) return fail(c, NERF_ERR_INVALID, "opts is NULL");
+    size_t w = 0, h = 0;
+    if ((rc = output_window(c, cam, opts, &w, &h))) return rc;
     DeviceGuard dg(c->device);
-    const bool crop = opts->crop_w > 0 || opts->crop_h > 0;
-    const long long w = crop ? opts->crop_w : cam->nx;
-    long long h = crop ? opts->crop_h : cam->ny;
-    if (w <= 0 || h <= 0) return fail(c, NERF_ERR_INVALID, "crop window outside the frame");
-    if (opts->band_count > 1) {
-        if (opts->band_index < 0 || opts->band_index >= opts->band_count || opts->band_stripe_rows < 0) return fail(c, NERF_ERR_INVALID, "band_index / band_count / band_stripe_rows out of range");
-        h = band_rows((int)h, opts->band_index, opts->band_count, opts->band_stripe_rows);
-        if (h <= 0) return fail(c, NERF_ERR_INVALID, "this band has no rows (more bands than rows)");
-    }
     // staging: the colour, then each requested map (w x h floats)
-    const size_t px = (size_t)w * h, bytes = px * 3 * sizeof(float);
+    const size_t px = w * h, bytes = px * 3 * sizeof(float);
     const size_t maps = (depth_out ? 1 : 0) + (opacity_out ? 1 : 0);
     if ((rc = ensure_bytes(c, (void **)&c->d_out, &c->out_floats, bytes + maps * px * sizeof(float)))) return rc;
     float *d_depth = depth_out ? c->d_out + 3 * px : nullptr;
@@ -1184,6 +1232,31 @@ int nerf_render_image_aux(nerf_ctx *c, const nerf_camera *cam, const nerf_render
 int nerf_render_image(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *opts, float *rgb_out, nerf_stats *stats) {
     return nerf_render_image_aux(c, cam, opts, rgb_out, nullptr, nullptr, stats);
 }
+
+int nerf_render_image_rgba8_device(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *opts, const float background[3], int alpha_mode,
+                                   uint8_t *d_rgba_out, void *stream, nerf_stats *stats) try {
+    if (!c) return fail(nullptr, NERF_ERR_INVALID, "ctx is NULL");
+    DeviceGuard dg(c->device);
+    return render_rgba8_device(c, cam, opts, background, alpha_mode, d_rgba_out, (hipStream_t)stream, stats);
+} NERF_CATCH(c)
+
+int nerf_render_image_rgba8(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *opts, const float background[3], int alpha_mode,
+                            uint8_t *rgba_out, nerf_stats *stats) try {
+    if (!c) return fail(nullptr, NERF_ERR_INVALID, "ctx is NULL");
+    int rc;
+    const float *bg = nullptr;
+    if ((rc = check_rgba8(c, background, alpha_mode, rgba_out, &bg))) return rc;
+    size_t w = 0, h = 0;
+    if ((rc = output_window(c, cam, opts, &w, &h))) return rc;
+    DeviceGuard dg(c->device);
+    const size_t bytes = w * h * 4; // 4 bytes per pixel come back instead of 12 (16 with the opacity)
+    if ((rc = ensure_bytes(c, (void **)&c->d_out, &c->out_floats, bytes))) return rc;
+    nerf_stats local; // a synchronous render always reads its counters (see nerf_render_image_aux)
+    if ((rc = render_rgba8_device(c, cam, opts, background, alpha_mode, (uint8_t *)c->d_out, c->stream, stats ? stats : &local))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(rgba_out, c->d_out, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return NERF_OK;
+} NERF_CATCH(c)
 
 int nerf_band_rows(int window_rows, int band_index, int band_count, int band_stripe_rows) {
     if (window_rows < 0 || band_count < 0 || band_stripe_rows < 0 || (band_count > 1 && (band_index < 0 || band_index >= band_count)))
@@ -1350,6 +1423,35 @@ int nerf_stage_integrate(nerf_ctx *c, size_t n_rays, int n, float far_, const fl
     HIP_TRY(c, launch_composite(ca, c->stream));
     HIP_TRY(c, hipMemcpyAsync(rgb_out, d + o_o, 3 * R * 4, hipMemcpyDeviceToHost, c->stream));
     if (w_out) HIP_TRY(c, hipMemcpyAsync(w_out, d + o_w, R * N * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return NERF_OK;
+} NERF_CATCH(c)
+
+int nerf_stage_integrate_rgba8(nerf_ctx *c, size_t n_rays, int n, float far_, const float *rgb, const float *sigma, const float *t,
+                               const float background[3], int alpha_mode, uint8_t *rgba_out) try {
+    if (!c) return fail(nullptr, NERF_ERR_INVALID, "ctx is NULL");
+    int rc;
+    const float *bg = nullptr;
+    if ((rc = check_rgba8(c, background, alpha_mode, rgba_out, &bg))) return rc;
+    if (n_rays == 0) return NERF_OK;
+    if (n <= 0 || !rgb || !sigma || !t) return fail(c, NERF_ERR_INVALID, "bad argument");
+    if (composite_lds_bytes(n) > 160 * 1024 || n_rays > 0x7fffffff / (size_t)n) return fail(c, NERF_ERR_INVALID, "too many samples");
+    DeviceGuard dg(c->device);
+    const size_t R = n_rays, N = (size_t)n;
+    // scratch (floats): t, sigma, rgb, per-ray colour, per-ray opacity, packed words
+    const size_t o_t = 0, o_s = o_t + R * N, o_c = o_s + R * N, o_o = o_c + 3 * R * N, o_a = o_o + 3 * R, o_p = o_a + R, total = o_p + R;
+    if ((rc = ensure_bytes(c, &c->d_scratch, &c->scratch_bytes, total * sizeof(float)))) return rc;
+    float *d = (float *)c->d_scratch;
+    HIP_TRY(c, hipMemcpyAsync(d + o_t, t, R * N * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d + o_s, sigma, R * N * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d + o_c, rgb, 3 * R * N * 4, hipMemcpyHostToDevice, c->stream));
+    CompositeArgs ca{};
+    ca.n_rays = (int)R; ca.n = n; ca.far_ = far_; ca.t = d + o_t; ca.sigma = d + o_s; ca.rgb = d + o_c; ca.out = d + o_o;
+    ca.opacity = alpha_mode == NERF_ALPHA_OPAQUE ? nullptr : d + o_a;
+    if (bg) { ca.use_bg = 1; ca.bg[0] = bg[0]; ca.bg[1] = bg[1]; ca.bg[2] = bg[2]; }
+    HIP_TRY(c, launch_composite(ca, c->stream));
+    HIP_TRY(c, launch_pack_rgba8(ca.out, ca.opacity, (uint32_t *)(d + o_p), R, alpha_mode, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(rgba_out, d + o_p, R * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return NERF_OK;
 } NERF_CATCH(c)

@@ -5,6 +5,7 @@
 //
 // With no flags it reproduces the reference's run: 256x256, 64 coarse + 128 fine samples, ./output.ppm.
 // --depth / --opacity add the expected-depth and opacity maps (nerf_render_image_aux) as one-channel PFM files.
+// --rgba adds the display-ready frame (nerf_render_image_rgba8: packed on the device, over --background, with --alpha) as a PAM file.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -20,13 +21,17 @@ static void usage(const char *argv0) {
             "          [--coarse-only] [--crop X0,Y0,W,H] [--dtype f32|bf16|bf16x3|f16x2] [--skip-empty] [--skip-dead] [--hybrid-sampling] [--certify-zero]\n"
             "          [--device ID | --gpus N | --devices ID,ID,... [--gather host|peer|rccl]] [--frames K] [--out FILE.ppm]\n"
             "          [--depth FILE.pfm] [--opacity FILE.pfm]\n"
+            "          [--rgba FILE.pam [--background R,G,B] [--alpha opaque|premultiplied|straight]]\n"
             "defaults: --scene lego_rust --width 256 --height 256 --coarse 64 --fine 128 --out output.ppm\n",
             argv0);
 }
 
 int main(int argc, char **argv) {
     std::string scene = getenv("NERF_SCENE_DIR") ? getenv("NERF_SCENE_DIR") : "lego_rust";
-    std::string out = "output.ppm", depth_path, opacity_path;
+    std::string out = "output.ppm", depth_path, opacity_path, rgba_path;
+    float background[3] = {1.0f, 1.0f, 1.0f};
+    bool have_background = false;
+    int alpha_mode = NERF_ALPHA_OPAQUE;
     int width = 256, height = 256, device = 0, frames = 1, gpus = 1, gather = NERF_GATHER_HOST; // src/lib.rs:657-658
     std::vector<int> devices;
     nerf_render_opts opts;
@@ -60,6 +65,16 @@ int main(int argc, char **argv) {
         else if (a == "--out") out = next();
         else if (a == "--depth") depth_path = next();
         else if (a == "--opacity") opacity_path = next();
+        else if (a == "--rgba") rgba_path = next();
+        else if (a == "--background") {
+            if (sscanf(next(), "%f,%f,%f", &background[0], &background[1], &background[2]) != 3) { usage(argv[0]); return 2; }
+            have_background = true;
+        }
+        else if (a == "--alpha") {
+            const std::string m = next();
+            if (m == "opaque") alpha_mode = NERF_ALPHA_OPAQUE; else if (m == "premultiplied") alpha_mode = NERF_ALPHA_PREMULTIPLIED;
+            else if (m == "straight") alpha_mode = NERF_ALPHA_STRAIGHT; else { usage(argv[0]); return 2; }
+        }
         else if (a == "--crop") {
             if (sscanf(next(), "%d,%d,%d,%d", &opts.crop_x0, &opts.crop_y0, &opts.crop_w, &opts.crop_h) != 4) { usage(argv[0]); return 2; }
         } else { usage(argv[0]); return a == "--help" || a == "-h" ? 0 : 2; }
@@ -135,6 +150,16 @@ int main(int argc, char **argv) {
                (double)st.certify_margin[0], (double)st.certify_margin[1], (double)st.certify_headroom[0], (double)st.certify_headroom[1],
                (double)st.certify_max_error[0], (double)st.certify_max_error[1], st.n_certify_retries, st.n_certify_fallback_rays);
     if (nerf_save_ppm(out.c_str(), ow, oh, image.data())) { fprintf(stderr, "error: %s\n", nerf_last_error(nullptr)); return 1; } // :676
+    if (!rgba_path.empty()) { // the same frame once more, display-ready: packed on the device, 4 bytes per pixel come back
+        std::vector<uint8_t> rgba((size_t)ow * oh * 4);
+        const float *bg = have_background ? background : nullptr;
+        if (gpus == 1 ? nerf_render_image_rgba8(ctx, &cam, &opts, bg, alpha_mode, rgba.data(), nullptr)
+                      : nerf_render_image_multi_rgba8(ctxs.data(), gpus, &cam, &opts, gather, bg, alpha_mode, rgba.data(), nullptr)) {
+            fprintf(stderr, "error: %s\n", nerf_last_error(ctx));
+            return 1;
+        }
+        if (nerf_save_pam(rgba_path.c_str(), ow, oh, rgba.data())) { fprintf(stderr, "error: %s\n", nerf_last_error(nullptr)); return 1; }
+    }
     if ((d_map && nerf_save_pfm(depth_path.c_str(), ow, oh, d_map)) || (o_map && nerf_save_pfm(opacity_path.c_str(), ow, oh, o_map))) {
         fprintf(stderr, "error: %s\n", nerf_last_error(nullptr));
         return 1;

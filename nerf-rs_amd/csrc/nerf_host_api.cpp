@@ -170,6 +170,13 @@ int nerf_save_pfm(const char *path, int width, int height, const float *values) 
     return rc ? fail_noctx(rc, err) : NERF_OK;
 } NERF_HOST_CATCH
 
+int nerf_save_pam(const char *path, int width, int height, const uint8_t *rgba) try {
+    if (!path || !rgba) return fail_noctx(NERF_ERR_INVALID, "NULL argument");
+    std::string err;
+    const int rc = save_pam(path, width, height, rgba, err);
+    return rc ? fail_noctx(rc, err) : NERF_OK;
+} NERF_HOST_CATCH
+
 void nerf_quantize_rgb8(const float *rgb, size_t n_pixels, uint8_t *out) { quantize_rgb8(rgb, n_pixels, out); }
 
 void nerf_quantize_rgba8(const float *rgb, size_t n_pixels, uint8_t *out) {

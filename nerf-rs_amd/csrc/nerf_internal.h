@@ -58,6 +58,7 @@ struct nerf_ctx {
     float *d_rayfb = nullptr; size_t rayfb_floats = 0; // SSAA ray framebuffer
     float *d_rayaux = nullptr; size_t rayaux_bytes = 0; // SSAA ray-level depth + opacity maps (nerf_render_image_aux)
     float *d_out = nullptr; size_t out_floats = 0;       // host-pointer render output staging
+    float *d_pack = nullptr; size_t pack_bytes = 0;      // RGBA8 renders: the f32 frame [+ opacity plane] the pack kernel reads (a host-pointer call stages the packed words in d_out)
     // scratch for forward_batch / stage calls
     void *d_scratch = nullptr; size_t scratch_bytes = 0;
     // skip_dead: device queue/counters {u32 ray counter, u32 live count, u64 chunk count} per MLP launch of a render, the
@@ -132,7 +133,14 @@ inline int band_first_row(int h, int i, int n) { return i * (h / n) + std::min(i
 int ensure_bytes(nerf_ctx *c, void **p, size_t *cur, size_t need);
 // render_image on the context's device, asynchronous on `st` (synchronises only when stats != NULL); d_depth / d_opacity
 // (h x w floats each, like d_out's pixels) may be NULL (nerf_render_image_aux)
+// background: NULL = the reference's white (the float entry points); else 3 floats B, the colour is sum_i w_i c_i + B * (1 - opacity)
 int render_device(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *o, float *d_out, float *d_depth, float *d_opacity,
-                  hipStream_t st, nerf_stats *stats);
+                  hipStream_t st, nerf_stats *stats, const float *background = nullptr);
+// nerf_render_image_rgba8_device: render_device into the context's f32 workspace, then the pack kernel into d_rgba (h x w words);
+// validates background / alpha_mode / d_rgba.  Asynchronous on `st` unless stats != NULL or certify_zero.
+int render_rgba8_device(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *o, const float *background, int alpha_mode,
+                        uint8_t *d_rgba, hipStream_t st, nerf_stats *stats);
+// width and rows of what a render with these options writes (the window, or one band of it); fails like the render would
+int output_window(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *o, size_t *w, size_t *h);
 
 } // namespace nerfint

@@ -77,17 +77,30 @@ struct Job {
     int b0 = 0;          // first row of the band inside the frame (contiguous bands)
     int rows = 0;        // rows of the band
     nerf_stats *stats;
+    nerf_stats local;    // RGBA8 frames always read their counters (n_nonfinite_points), also when the caller wants no stats
     int rc = NERF_OK;
 };
 
 // The colour and each requested map (nerf_render_image_multi_aux) travel as PLANES of one buffer: a buffer (band, slot or frame) of
 // R rows holds plane p at float offset w * R * off, rows packed (w * nch floats each).  Colour alone: one plane, the layout of
 // nerf_render_image_multi.  A slot of the all-gather holds every plane of its band: still ONE collective per frame.
+// An RGBA8 frame (nerf_render_image_multi_rgba8) is ONE such plane of one opaque 32-bit word per pixel: each context packs its own
+// band, and from there on the words are only copied (hipMemcpy*, the integer copy kernel, an all-gather of ncclUint32).
 struct Plane {
     float *host; // the caller's h x w x nch buffer
     int nch;     // floats per pixel
     int off;     // floats per pixel of the planes in front of it
 };
+
+// RGBA8 output of a multi render: NULL out = a float render
+struct Rgba8 {
+    const float *background;
+    int alpha_mode;
+    uint8_t *out;
+};
+
+int render_multi(nerf_ctx *const *ctxs, int n, const nerf_camera *cam, const nerf_render_opts *opts, int gather,
+                 float *rgb_out, float *depth_out, float *opacity_out, nerf_stats *per_ctx, const Rgba8 *rgba);
 
 } // namespace
 
@@ -114,7 +127,27 @@ void nerf_multi_release(void) {
 }
 
 int nerf_render_image_multi_aux(nerf_ctx *const *ctxs, int n, const nerf_camera *cam, const nerf_render_opts *opts, int gather,
-                                float *rgb_out, float *depth_out, float *opacity_out, nerf_stats *per_ctx) try {
+                                float *rgb_out, float *depth_out, float *opacity_out, nerf_stats *per_ctx) {
+    return render_multi(ctxs, n, cam, opts, gather, rgb_out, depth_out, opacity_out, per_ctx, nullptr);
+}
+
+int nerf_render_image_multi_rgba8(nerf_ctx *const *ctxs, int n, const nerf_camera *cam, const nerf_render_opts *opts, int gather,
+                                  const float background[3], int alpha_mode, uint8_t *rgba_out, nerf_stats *per_ctx) {
+    const Rgba8 rgba{background, alpha_mode, rgba_out};
+    return render_multi(ctxs, n, cam, opts, gather, nullptr, nullptr, nullptr, per_ctx, &rgba);
+}
+
+int nerf_render_image_multi(nerf_ctx *const *ctxs, int n, const nerf_camera *cam, const nerf_render_opts *opts, int gather,
+                            float *rgb_out, nerf_stats *per_ctx) {
+    return nerf_render_image_multi_aux(ctxs, n, cam, opts, gather, rgb_out, nullptr, nullptr, per_ctx);
+}
+
+} // extern "C"
+
+namespace {
+
+int render_multi(nerf_ctx *const *ctxs, int n, const nerf_camera *cam, const nerf_render_opts *opts, int gather,
+                 float *rgb_out, float *depth_out, float *opacity_out, nerf_stats *per_ctx, const Rgba8 *rgba) try {
     if (!ctxs || n <= 0) return fail(nullptr, NERF_ERR_INVALID, "nerf_render_image_multi: no contexts");
     std::set<const nerf_ctx *> seen;
     for (int i = 0; i < n; ++i) {
@@ -124,7 +157,7 @@ int nerf_render_image_multi_aux(nerf_ctx *const *ctxs, int n, const nerf_camera 
     nerf_ctx *c0 = ctxs[0];
     if (!cam || cam->nx <= 0 || cam->ny <= 0) return fail(c0, NERF_ERR_INVALID, "width and height must be greater than zero");
     if (!opts) return fail(c0, NERF_ERR_INVALID, "opts is NULL");
-    if (!rgb_out) return fail(c0, NERF_ERR_INVALID, "output pointer is NULL");
+    if (rgba ? !rgba->out : !rgb_out) return fail(c0, NERF_ERR_INVALID, "output pointer is NULL");
     if (gather != NERF_GATHER_HOST && gather != NERF_GATHER_PEER && gather != NERF_GATHER_RCCL)
         return fail(c0, NERF_ERR_INVALID, "gather must be NERF_GATHER_HOST, NERF_GATHER_PEER or NERF_GATHER_RCCL");
     int x0 = 0, y0 = 0, cw = cam->nx, ch = cam->ny;
@@ -133,7 +166,8 @@ int nerf_render_image_multi_aux(nerf_ctx *const *ctxs, int n, const nerf_camera 
         return fail(c0, NERF_ERR_INVALID, "crop window outside the frame");
     Plane planes[3];
     int np = 0, unit = 0;
-    for (const Plane q : {Plane{rgb_out, 3, 0}, Plane{depth_out, 1, 0}, Plane{opacity_out, 1, 0}})
+    // (an RGBA8 frame: the caller's bytes are addressed as words for the copies' offsets only -- nothing dereferences them as floats)
+    for (const Plane q : {Plane{rgba ? (float *)rgba->out : rgb_out, rgba ? 1 : 3, 0}, Plane{depth_out, 1, 0}, Plane{opacity_out, 1, 0}})
         if (q.host) { planes[np] = q; planes[np++].off = unit; unit += q.nch; }
     auto at = [&](float *base, int rows, int p) { return base + (size_t)cw * rows * planes[p].off; }; // plane p of a buffer of `rows` rows
     const size_t row_floats = (size_t)cw * unit, frame_floats = row_floats * ch; // every plane
@@ -189,7 +223,7 @@ int nerf_render_image_multi_aux(nerf_ctx *const *ctxs, int n, const nerf_camera 
         J.d_band = c->d_out; J.cap = rows;
         if (gather == NERF_GATHER_PEER && i == 0) J.cap = stripe ? max_rows : ch; // b0 == 0: the frame (contiguous) or slot 0 (striped)
         if (gather == NERF_GATHER_RCCL) { J.d_band = c->d_out + slot_floats * i; J.cap = max_rows; }
-        J.stats = per_ctx ? &per_ctx[i] : nullptr;
+        J.stats = per_ctx ? &per_ctx[i] : rgba ? &J.local : nullptr;
         if (per_ctx) memset(&per_ctx[i], 0, sizeof(nerf_stats));
     }
 
@@ -203,7 +237,8 @@ int nerf_render_image_multi_aux(nerf_ctx *const *ctxs, int n, const nerf_camera 
         if (hipSetDevice(c->device) != hipSuccess) { J.rc = fail(c, NERF_ERR_HIP, "hipSetDevice failed"); return; }
         if (J.rows > 0) {
             float *d_depth = depth_out ? at(J.d_band, J.cap, 1) : nullptr, *d_opacity = opacity_out ? at(J.d_band, J.cap, np - 1) : nullptr;
-            J.rc = render_device(c, cam, &J.o, J.d_band, d_depth, d_opacity, c->stream, J.stats);
+            J.rc = rgba ? render_rgba8_device(c, cam, &J.o, rgba->background, rgba->alpha_mode, (uint8_t *)J.d_band, c->stream, J.stats)
+                        : render_device(c, cam, &J.o, J.d_band, d_depth, d_opacity, c->stream, J.stats);
             if (J.rc) return;
         }
         hipError_t e = hipSuccess;
@@ -300,7 +335,7 @@ int nerf_render_image_multi_aux(nerf_ctx *const *ctxs, int n, const nerf_camera 
         } else {
             ncclResult_t r = g_rccl.GroupStart();
             for (int i = 0; i < n && r == ncclSuccess; ++i)
-                r = g_rccl.AllGather(jobs[i].d_band, ctxs[i]->d_out, slot_floats, ncclFloat, comms[i], ctxs[i]->stream);
+                r = g_rccl.AllGather(jobs[i].d_band, ctxs[i]->d_out, slot_floats, rgba ? ncclUint32 : ncclFloat, comms[i], ctxs[i]->stream);
             const ncclResult_t r2 = g_rccl.GroupEnd();
             if (r == ncclSuccess) r = r2;
             if (r != ncclSuccess) { rc_first = NERF_ERR_HIP; err_first = std::string("ncclAllGather: ") + g_rccl.GetErrorString(r); }
@@ -350,9 +385,4 @@ int nerf_render_image_multi_aux(nerf_ctx *const *ctxs, int n, const nerf_camera 
     return fail(ctxs && n > 0 ? ctxs[0] : nullptr, NERF_ERR_INVALID, std::string("nerf_render_image_multi: ") + e.what());
 }
 
-int nerf_render_image_multi(nerf_ctx *const *ctxs, int n, const nerf_camera *cam, const nerf_render_opts *opts, int gather,
-                            float *rgb_out, nerf_stats *per_ctx) {
-    return nerf_render_image_multi_aux(ctxs, n, cam, opts, gather, rgb_out, nullptr, nullptr, per_ctx);
-}
-
-} // extern "C"
+} // namespace

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/nerf_mi355x.h"
+
 // A pass renders the rectangle [ry0, ry0+rh) x [rx0, rx0+rw) of the (rny x rnx) ray grid; ray r of the pass is
 // (ry0 + r / rw, rx0 + r % rw); its RNG pixel index is row * rnx + col.
 struct RayGenArgs {
@@ -53,6 +55,10 @@ struct CompositeArgs {
     float *w_out;       // optional n_rays x n
     float *depth;       // optional n_rays: sum_i (t_i * w_i) (nerf_render_image_aux)
     float *opacity;     // optional n_rays: sum_i w_i
+    // the RGBA8 entry points (appended: the fields above keep their offsets): use_bg != 0 => out = sum_i w_i c_i + bg * (1 - opacity)
+    // instead of the reference's white
+    int use_bg;
+    float bg[3];
 };
 
 hipError_t sampling_init(void);
@@ -63,6 +69,8 @@ hipError_t launch_resample(const ResampleArgs &a, hipStream_t st);
 hipError_t launch_composite(const CompositeArgs &a, hipStream_t st);
 // nch floats per pixel (3: colour, 1: a depth or opacity map)
 hipError_t launch_box_downsample(const float *rays, float *out, int w, int h, int s, int nch, hipStream_t st);
+// pixel-level f32 colour (n x 3) [+ opacity (n) for the two alpha modes] -> n words R | G << 8 | B << 16 | A << 24 (NERF_ALPHA_*)
+hipError_t launch_pack_rgba8(const float *rgb, const float *opacity, uint32_t *out, size_t n_pixels, int alpha_mode, hipStream_t st);
 // multi-GPU: n gathered bands (slot_floats apart, rows packed) -> the h x w x nch frame; stripe = 0: contiguous bands
 hipError_t launch_bands_to_frame(const float *slots, float *frame, int w, int h, int n, int stripe, size_t slot_floats, int nch, hipStream_t st);
 size_t resample_lds_bytes(int nc, int nf);

@@ -308,11 +308,13 @@ __global__ __launch_bounds__(256) void k_resample(ResampleArgs a) {
 // kAux (nerf_render_image_aux): the same walk also sums the expected depth sum_i (t_i * w_i) and writes it with the opacity
 // (acc = sum_i w_i) -- two more registers and two 4-B stores per ray; the colour arithmetic is the same either way.  The
 // colour-only instance is the one compiled without it.
+// kBg (the RGBA8 entry points): the background is CompositeArgs::bg instead of the reference's constant 1.  The two instances without it
+// keep the reference's expression, so they stay the code they were before the flag existed.
 constexpr int kCompChunk = 16;
 constexpr int kCompTS = kCompChunk + 1;     // row strides (floats)
 constexpr int kCompCS = 3 * kCompChunk + 1;
 
-template <bool kAux>
+template <bool kAux, bool kBg>
 __global__ __launch_bounds__(64) void k_composite(CompositeArgs a) {
     __shared__ float s_t[64 * kCompTS], s_sg[64 * kCompTS], s_col[64 * kCompCS];
     const int lane = threadIdx.x;
@@ -380,9 +382,14 @@ __global__ __launch_bounds__(64) void k_composite(CompositeArgs a) {
         __syncthreads();
     }
     if (live) {
-        const float bg = 1.0f * (1.0f - acc);
         float *o = a.out + 3 * (size_t)my_ray;
-        o[0] = r + bg; o[1] = g + bg; o[2] = b + bg;
+        if constexpr (kBg) { // C + B * (1 - A): multiply and add rounded separately; B = 1 gives the line below, B = 0 gives C
+            const float rest = 1.0f - acc;
+            o[0] = r + a.bg[0] * rest; o[1] = g + a.bg[1] * rest; o[2] = b + a.bg[2] * rest;
+        } else {
+            const float bg = 1.0f * (1.0f - acc);
+            o[0] = r + bg; o[1] = g + bg; o[2] = b + bg;
+        }
         if constexpr (kAux) {
             if (a.depth) a.depth[my_ray] = dep;
             if (a.opacity) a.opacity[my_ray] = acc;
@@ -401,6 +408,42 @@ __global__ void k_box_downsample(const float *__restrict__ rays, float *__restri
     for (int di = 0; di < s; ++di)
         for (int dj = 0; dj < s; ++dj) acc += rays[nch * ((size_t)(i * s + di) * RW + (j * s + dj)) + c];
     out[idx] = acc * (1.0f / (float)(s * s));
+}
+
+// ---- display output: f32 pixels -> one R,G,B,A word per pixel (nerf_render_image_rgba8) --------------------------------
+// Runs once per PIXEL, behind the box filter.  The quantiser is quantize_rgb8 of host_util.cpp operation for operation: clamp to [0, 1],
+// * 255, + 0.5 (separate roundings: -ffp-contract=off), truncate; NaN -> 0 by an explicit test.
+// One pixel per lane: a wave reads 768 contiguous bytes of colour (three dword loads per lane, every cache line used whole), 256 of
+// opacity, and stores 256 contiguous bytes.  20 B per pixel -- 12.8 MB for an 800 x 800 frame, microseconds at HBM speed: the kernel is
+// launch-bound at frame sizes, wider accesses per lane would buy nothing that can be measured (and would need 16-byte-aligned bands).
+__device__ __forceinline__ unsigned quantize8(float v) {
+    v = v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v);
+    const float q = v * 255.0f + 0.5f;
+    return (q != q) ? 0u : (unsigned)q;
+}
+
+__global__ __launch_bounds__(256) void k_pack_rgba8(const float *__restrict__ rgb, const float *__restrict__ opacity,
+                                                    uint32_t *__restrict__ out, size_t n_pixels, int alpha_mode) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_pixels) return;
+    float r = rgb[3 * i], g = rgb[3 * i + 1], b = rgb[3 * i + 2];
+    unsigned alpha = 255u;
+    if (alpha_mode != NERF_ALPHA_OPAQUE) { // wave-uniform
+        const float acc = opacity[i];
+        if (alpha_mode == NERF_ALPHA_STRAIGHT) { // correctly rounded IEEE division
+            const bool some = acc > 0.0f;
+            r = some ? __fdiv_rn(r, acc) : 0.0f; g = some ? __fdiv_rn(g, acc) : 0.0f; b = some ? __fdiv_rn(b, acc) : 0.0f;
+        }
+        alpha = quantize8(acc);
+    }
+    out[i] = quantize8(r) | quantize8(g) << 8 | quantize8(b) << 16 | alpha << 24;
+}
+
+hipError_t launch_pack_rgba8(const float *rgb, const float *opacity, uint32_t *out, size_t n_pixels, int alpha_mode, hipStream_t st) {
+    if (n_pixels == 0) return hipSuccess;
+    if (alpha_mode < NERF_ALPHA_OPAQUE || alpha_mode > NERF_ALPHA_STRAIGHT || (alpha_mode != NERF_ALPHA_OPAQUE && !opacity)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_pack_rgba8, dim3((unsigned)((n_pixels + 255) / 256)), dim3(256), 0, st, rgb, opacity, out, n_pixels, alpha_mode);
+    return hipGetLastError();
 }
 
 // ---- zero certification (nerf_render_opts.certify_zero): which samples does the exact kernel have to look at? ------------
@@ -644,8 +687,9 @@ hipError_t launch_cert_audit(const unsigned *aux, const unsigned *aux_count, uns
 // ---- multi-GPU: bands -> frame ---------------------------------------------------------------------------------------------------
 // `slots` = n bands of slot_floats floats each (band b's rows packed at its start); band b holds the rows of the stripes b, b + n, ... of
 // the frame (stripe = `stripe` rows; stripe == 0: contiguous bands, the first h % n bands one row longer).  One thread per float4-less float:
-// the frame is 7.7 MB -- a copy kernel, HBM-bound.  nch floats per pixel: 3 for colour, 1 for a depth or opacity plane.
-__global__ void k_bands_to_frame(const float *__restrict__ slots, float *__restrict__ frame, int w, int h, int n, int stripe, size_t slot_floats, int nch) {
+// the frame is 7.7 MB -- a copy kernel, HBM-bound.  nch floats per pixel: 3 for colour, 1 for a depth or opacity plane -- or for a band of
+// packed RGBA8 pixels (nerf_render_image_multi_rgba8), which is why the words are moved as integers: nothing here may read them as floats.
+__global__ void k_bands_to_frame(const uint32_t *__restrict__ slots, uint32_t *__restrict__ frame, int w, int h, int n, int stripe, size_t slot_floats, int nch) {
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t row_floats = (size_t)w * nch;
     if (idx >= row_floats * h) return;
@@ -663,7 +707,7 @@ __global__ void k_bands_to_frame(const float *__restrict__ slots, float *__restr
 hipError_t launch_bands_to_frame(const float *slots, float *frame, int w, int h, int n, int stripe, size_t slot_floats, int nch, hipStream_t st) {
     const size_t total = (size_t)w * nch * h;
     if (total == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_bands_to_frame, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, slots, frame, w, h, n, stripe, slot_floats, nch);
+    hipLaunchKernelGGL(k_bands_to_frame, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const uint32_t *)slots, (uint32_t *)frame, w, h, n, stripe, slot_floats, nch);
     return hipGetLastError();
 }
 
@@ -704,8 +748,13 @@ hipError_t launch_resample(const ResampleArgs &a, hipStream_t st) {
 
 hipError_t launch_composite(const CompositeArgs &a, hipStream_t st) {
     if (a.n_rays <= 0) return hipSuccess;
-    if (a.depth || a.opacity) hipLaunchKernelGGL(k_composite<true>, dim3((a.n_rays + 63) / 64), dim3(64), 0, st, a);
-    else hipLaunchKernelGGL(k_composite<false>, dim3((a.n_rays + 63) / 64), dim3(64), 0, st, a);
+    const dim3 grid((a.n_rays + 63) / 64), block(64);
+    const bool aux = a.depth || a.opacity;
+    if (a.use_bg) { // the RGBA8 entry points
+        if (aux) hipLaunchKernelGGL((k_composite<true, true>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((k_composite<false, true>), grid, block, 0, st, a);
+    } else if (aux) hipLaunchKernelGGL((k_composite<true, false>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((k_composite<false, false>), grid, block, 0, st, a);
     return hipGetLastError();
 }
 
