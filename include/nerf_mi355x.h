@@ -77,8 +77,9 @@ typedef struct {
                            * Range: f16 overflows at 65 504 -- activations must stay below it (true for the lego networks inside
                            * the scene and well beyond: validated for |p| <= 16; bf16x3 has no such limit); a network with a
                            * weight beyond the f16 range makes this mode unavailable (NERF_ERR_STATE). */
-    int32_t skip_empty;   /* ext: 1 = skip the colour head (bottleneck + viewdirs + rgb, 17 % of a full MLP
-                           * evaluation) for every workgroup tile (128 samples in f32, 256 in bf16) whose densities are all 0.
+    int32_t skip_empty;   /* ext: 1 = skip the colour head (bottleneck + viewdirs + rgb: 17 % of a full MLP
+                           * evaluation in the 16-bit arithmetics, 6.9 % in F32, whose kernels run the bottleneck folded into
+                           * viewdirs) for every workgroup tile (128 samples in f32, 256 in bf16) whose densities are all 0.
                            * EXACT: such samples have alpha = 0 and weight 0, the image is bit-identical; only the work
                            * changes.  Default 0 so that timings are plain executed-FLOP figures. */
     int32_t skip_dead;    /* ext (the rest of it; every mlp_dtype): 1 = evaluate only what can reach a pixel.
@@ -147,7 +148,8 @@ typedef struct {
     /* MLP evaluations actually executed (equal to the point counts above unless skip_empty / skip_dead removed work): */
     uint64_t n_exec_coarse_trunk;  /* coarse network, dense0..7 + alpha */
     uint64_t n_exec_fine_trunk;    /* fine network, dense0..7 + alpha */
-    uint64_t n_exec_colour;        /* bottleneck + viewdirs + rgb (fine network, or the coarse one when coarse_only) */
+    uint64_t n_exec_colour;        /* colour heads executed (fine network, or the coarse one when coarse_only): bottleneck + viewdirs + rgb; in F32
+                                    * the bottleneck is folded into viewdirs at load time, a head is then viewdirs' + rgb */
     uint64_t n_hybrid_rays;        /* hybrid_sampling: rays whose coarse pass was redone in f32 (counted in n_exec_coarse_trunk too) */
     uint64_t n_nonfinite_points;   /* split arithmetics: evaluations in which an operand left the arithmetic's range (NERF_MLP_F16X2: an
                                     * activation beyond 65 504 -- every value is watched as it is split, one v_max3 per pair) or whose density
@@ -194,6 +196,12 @@ int nerf_check_network_blob(const char *blob_path);
 /* Diagnostic: the packed device images of a weight directory (layout: nerf-rs_amd/csrc/mlp_layout.h).  Pass NULL
  * buffers to query the lengths (in floats).  Host-only. */
 int nerf_debug_pack_network_dir(const char *dir, float *wstream, size_t wstream_cap, float *small, size_t small_cap,
+                                size_t *wstream_len, size_t *small_len);
+/* Diagnostic: the image the NERF_MLP_F32 kernels read, formed from the packed one at load time (directory and blob loaders alike):
+ * the bottleneck layer has no activation and feeds only the viewdirs layer, so the two are one linear map W' = W_b . W_v[0:256],
+ * b' = b_v + b_b^T . W_v[0:256] (fp64 accumulation, rounded once to f32).  129 chunks instead of 145 (mlp_layout.h
+ * kChunksFullFolded); the small block differs in the viewdirs bias only.  Same calling convention as above.  Host-only. */
+int nerf_debug_fold_network_dir(const char *dir, float *wstream, size_t wstream_cap, float *small, size_t small_cap,
                                 size_t *wstream_len, size_t *small_len);
 /* Diagnostic: the three bf16 parts (raw bit patterns) the NERF_MLP_BF16X3 packer stores for each of n f32 weights:
  * parts[3 i + k], k = 0..2, with v = p0 + p1 + p2 up to 2^-27 |v|.  Host-only. */

@@ -64,6 +64,8 @@ PROTOTYPES = {
     "nerf_check_network_blob": (C.c_int, [C.c_char_p]),
     "nerf_debug_pack_network_dir": (C.c_int, [C.c_char_p, f32p, C.c_size_t, f32p, C.c_size_t, C.POINTER(C.c_size_t),
                                               C.POINTER(C.c_size_t)]),
+    "nerf_debug_fold_network_dir": (C.c_int, [C.c_char_p, f32p, C.c_size_t, f32p, C.c_size_t, C.POINTER(C.c_size_t),
+                                              C.POINTER(C.c_size_t)]),
     "nerf_debug_split_bf16x3": (C.c_int, [f32p, C.c_size_t, C.POINTER(C.c_uint16)]),
     "nerf_debug_split_f16x2": (C.c_int, [f32p, C.c_size_t, C.POINTER(C.c_uint16)]),
     "nerf_debug_certify_policy": (C.c_int, [C.c_float, C.c_uint64, C.c_uint64, C.c_float, C.c_float, f32p]),

@@ -3,7 +3,7 @@
 // touches the device).  tests/test_host_asan.py feeds it valid, truncated, oversized and malformed weight directories, blobs and
 // camera JSON files: every call must come back with a status code and a message -- a sanitizer report aborts with a non-zero exit.
 //   host_asan_driver check_dir <dir> | pack_dir <dir> <blob> | check_blob <blob> | camera_json <json> <w> <h> |
-//                    debug_pack <dir> | quantize | save_ppm <path> <w> <h> | save_pfm <path> <w> <h> | save_pam <path> <w> <h> | split
+//                    debug_pack <dir> | debug_fold <dir> | quantize | save_ppm <path> <w> <h> | save_pfm <path> <w> <h> | save_pam <path> <w> <h> | split
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -44,6 +44,18 @@ int main(int argc, char **argv) {
             printf("packed %zu + %zu floats, sum %.6f\n", nw, ns, s);
         }
         return report("debug_pack", rc);
+    }
+    if (cmd == "debug_fold" && argc == 3) { // the folded image of the f32 kernels (host_util.cpp fold_network)
+        size_t nw = 0, ns = 0;
+        int rc = nerf_debug_fold_network_dir(argv[2], nullptr, 0, nullptr, 0, &nw, &ns);
+        if (!rc) {
+            std::vector<float> ws(nw), sm(ns);
+            rc = nerf_debug_fold_network_dir(argv[2], ws.data(), ws.size(), sm.data(), sm.size(), &nw, &ns);
+            if (!rc) rc = nerf_debug_fold_network_dir(argv[2], ws.data(), ws.size(), sm.data(), sm.size() - 1, &nw, &ns) == NERF_ERR_INVALID ? 0 : 99; // short buffer refused
+            double s = 0; for (float v : ws) s += v; for (float v : sm) s += v;
+            printf("folded %zu + %zu floats, sum %.6f\n", nw, ns, s);
+        }
+        return report("debug_fold", rc);
     }
     if (cmd == "quantize") { // clamp + NaN/inf through the quantisers (src/lib.rs:573-577, :582-592)
         const float v[] = {-1.f, 0.f, 0.5f, 1.f, 2.f, NAN, INFINITY, -INFINITY, 1e-9f, 0.999999f, 0.25f, 0.75f};

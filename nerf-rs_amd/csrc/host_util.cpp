@@ -164,6 +164,61 @@ void pack_network(const HostNet &net, std::vector<float> &ws, std::vector<float>
     for (int c = 0; c < 3; ++c) sm[kMiscOff + 1 + c] = net.rgb.b[c];
 }
 
+// ---- folded image of the f32 kernels ------------------------------------------------------------
+// The bottleneck (256 -> 256, no activation, src/network.rs:218) feeds only the viewdirs layer, which is linear up to its own
+// ReLU: W' = W_b . W_v[0:256], b' = b_v + b_b^T . W_v[0:256].  Works on the PACKED image (so the directory loader and the
+// blob loader share it): un-permutes the two layers' pieces, multiplies with fp64 accumulation (every f32 x f32 product is
+// exact in fp64), rounds once to f32 and packs W' as a 4-output-tile layer whose input rows follow the bottleneck's.
+bool fold_network(const std::vector<float> &ws, const std::vector<float> &sm, std::vector<float> &fws, std::vector<float> &fsm) {
+    if (ws.size() != (size_t)kChunksFull * kChunkFloats || sm.size() != (size_t)kSmallFloats) return false;
+    const size_t bott = (size_t)kChunksSigma * kChunkFloats;              // bottleneck: k-step st, group g -> piece (st * 2 + g)
+    const size_t view = bott + (size_t)chunksOf(kStepsHid, 8) * kChunkFloats; // viewdirs: k-step st -> piece st
+    std::vector<double> Wb(256 * 256), Wv(256 * 128), bb(256), bv(128);
+    for (int st = 0; st < kStepsHid; ++st)
+        for (int l = 0; l < 64; ++l) {
+            const int row = hidden_row(st, l >> 5);
+            for (int g = 0; g < 2; ++g)
+                for (int q = 0; q < 4; ++q)
+                    Wb[(size_t)row * 256 + 32 * (4 * g + q) + (l & 31)] = ws[bott + ((size_t)st * 2 + g) * 256 + l * 4 + q];
+            for (int q = 0; q < 4; ++q) Wv[(size_t)row * 128 + 32 * q + (l & 31)] = ws[view + (size_t)st * 256 + l * 4 + q];
+        }
+    for (int nt = 0; nt < 8; ++nt)
+        for (int h = 0; h < 2; ++h)
+            for (int r = 0; r < 16; ++r) {
+                bb[32 * nt + regFeature(r, h)] = sm[kBiasOff + 8 * 256 + (nt * 2 + h) * 16 + r];
+                if (nt < 4) bv[32 * nt + regFeature(r, h)] = sm[kBiasViewOff + (nt * 2 + h) * 16 + r];
+            }
+    std::vector<float> Wf(256 * 128);
+    std::vector<double> acc(128);
+    for (int i = 0; i < 256; ++i) {
+        std::fill(acc.begin(), acc.end(), 0.0);
+        for (int j = 0; j < 256; ++j) {
+            const double a = Wb[(size_t)i * 256 + j];
+            for (int n = 0; n < 128; ++n) acc[n] += a * Wv[(size_t)j * 128 + n];
+        }
+        for (int n = 0; n < 128; ++n) Wf[(size_t)i * 128 + n] = (float)acc[n];
+    }
+    for (int n = 0; n < 128; ++n) acc[n] = 0.0;
+    for (int j = 0; j < 256; ++j)
+        for (int n = 0; n < 128; ++n) acc[n] += bb[j] * Wv[(size_t)j * 128 + n];
+
+    fws.clear();
+    fws.reserve((size_t)kChunksFullFolded * kChunkFloats);
+    fws.insert(fws.end(), ws.begin(), ws.begin() + bott);
+    for (int st = 0; st < kStepsHid; ++st)
+        for (int l = 0; l < 64; ++l)
+            for (int q = 0; q < 4; ++q) fws.push_back(Wf[(size_t)hidden_row(st, l >> 5) * 128 + 32 * q + (l & 31)]);
+    fws.insert(fws.end(), ws.begin() + (size_t)kFoldDirChunk * kChunkFloats, ws.end());
+    fsm = sm;
+    for (int nt = 0; nt < 4; ++nt)
+        for (int h = 0; h < 2; ++h)
+            for (int r = 0; r < 16; ++r) {
+                const int n = 32 * nt + regFeature(r, h);
+                fsm[kBiasViewOff + (nt * 2 + h) * 16 + r] = (float)(bv[n] + acc[n]);
+            }
+    return fws.size() == (size_t)kChunksFullFolded * kChunkFloats;
+}
+
 // ---- bf16 stream -------------------------------------------------------------------------------
 uint16_t f32_to_bf16_rne(float v) {
     uint32_t u;

@@ -32,6 +32,10 @@ int assemble_net(std::map<std::string, Tensor> &params, HostNet &net, std::strin
 
 // Packed device images (mlp_layout.h).
 void pack_network(const HostNet &net, std::vector<float> &wstream, std::vector<float> &small);
+// The image the f32 kernels read (mlp_layout.h kChunksFullFolded): the activation-free bottleneck folded into the viewdirs layer,
+// formed from pack_network's output with fp64 accumulation.  false if the input does not have the packed image's sizes.
+bool fold_network(const std::vector<float> &wstream, const std::vector<float> &small, std::vector<float> &folded_wstream,
+                  std::vector<float> &folded_small);
 // bf16 weight stream of mlp_kernel_bf16.hip (round-to-nearest-even); the small-parameter block is shared with fp32.
 void pack_network_bf16(const HostNet &net, std::vector<uint16_t> &wstream);
 uint16_t f32_to_bf16_rne(float v);

@@ -5,8 +5,8 @@
 enum { MLP_MODE_POINTS = 0, MLP_MODE_RAYS = 1, MLP_MODE_LIST = 2 }; // LIST (f32 and split kernels): ray mode over a device-side list of sample indices (bit 31 of an entry: audited certificate)
 
 struct MlpArgs {
-    const float *wstream;      // packed weight stream (mlp_layout.h), device
-    const float *small_params; // biases + head weights, kSmallFloats floats, device
+    const float *wstream;      // weight stream of the launched arithmetic (mlp_layout.h), device; f32 kernels: the FOLDED image (kChunksFullFolded)
+    const float *small_params; // biases + head weights, kSmallFloats floats, device; f32 kernels: the folded image's (viewdirs bias = b')
     int n_points;
     int mode;
     // MLP_MODE_POINTS: forward_batch layouts (src/network.rs:197): points 3 x n SoA, dirs n x 3 AoS

@@ -14,7 +14,9 @@
 //     in 16-KiB chunks into a 3-slot ring shared by the 4 waves; one s_barrier per chunk, placed in the
 //     middle of the chunk so the next chunk's first operands can be fetched before they are needed;
 //   * alpha (N=1) and rgb (N=3) heads run on the VALU from the register-resident activations.
-// Per 32-point wave tile: 9280 MFMAs (full) / 7680 (sigma only) x 64 cycles.
+//   * the bottleneck layer (no activation, src/network.rs:218) is folded into the viewdirs layer on the host, once per loaded
+//     network (host_util.cpp fold_network): the colour head is relu(h7) -> viewdirs' -> rgb.
+// Per 32-point wave tile: 8256 MFMAs (full; 9280 before the fold) / 7680 (sigma only) x 64 cycles.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -51,7 +53,7 @@ __global__ __launch_bounds__(256, 1) void nerf_mlp_kernel(const MlpArgs A) {
     P.ring_addr = (uint32_t)(uintptr_t)lds + wave * 4096;
     P.wr_slot_off = 0;
     P.next_off = 0;
-    P.stream_bytes = (FULL ? kChunksFull : kChunksSigma) * kChunkBytes;
+    P.stream_bytes = (FULL ? kChunksFullFolded : kChunksSigma) * kChunkBytes;
     P.gbase = (const char *)A.wstream + wave * 4096;
     __syncthreads();
 #pragma unroll
@@ -120,7 +122,7 @@ __global__ __launch_bounds__(256, 1) void nerf_mlp_kernel(const MlpArgs A) {
         if (FULL && A.skip_empty) {
             // Empty-tile skip (exact): if sigma == 0 for all 128 points of this workgroup's tile, then
             // alpha = 1 - exp(-0 * delta) = 0 and w = T * 0 = 0 exactly for each of them (src/lib.rs:271-272), so their
-            // colours never reach a pixel: skip bottleneck + viewdirs + rgb (17 % of a full evaluation), write rgb = 0.
+            // colours never reach a pixel: skip viewdirs' + rgb (6.9 % of a full evaluation), write rgb = 0.
             LDS_AS int *vote = (LDS_AS int *)(lds + kRingSlots * kChunkBytes) + kMiscOff + 8;
             const bool any_wg = tile_has_density(vote, valid && sigma > 0.0f, wave, lane);
             if (!any_wg) {
@@ -132,16 +134,15 @@ __global__ __launch_bounds__(256, 1) void nerf_mlp_kernel(const MlpArgs A) {
                 continue;
             }
         }
-        if (FULL) hidden_layer<true>(Y, X, small + kBiasOff + 8 * 256, P, h); // bottleneck (no activation, :218)
-
         if (FULL) {
             f32x16 D;
             encode_dir<NERF_FAST_SINCOS != 0>(dx, dy, dz, h, D);
-            // viewdirs: [bottleneck ; dir encoding] -> 128 (src/network.rs:219-222)
+            // viewdirs': [relu(h7) ; dir encoding] -> 128 = bottleneck (no activation, :218) folded into viewdirs (:219-222);
+            // W' and b' come from the host (mlp_layout.h kChunksFullFolded)
             f32x16 V[4];
             load_bias<4>(V, small + kBiasViewOff, h);
 #pragma unroll
-            for (int t = 0; t < 8; ++t) tile_steps<4, false>(X[t], V, P);
+            for (int t = 0; t < 8; ++t) tile_steps<4, true>(Y[t], V, P);
             tile_steps<4, false>(D, V, P);
             float c[3];
             rgb_head(V, small, h, c);

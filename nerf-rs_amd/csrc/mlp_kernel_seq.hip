@@ -4,7 +4,8 @@
 //   (A) once the transmittance T falls below 1e-4 every later weight of the ray is exactly 0 (:276-279): neither the
 //       density nor the colour of those samples can reach the pixel;
 //   (B) a sample with weight w = T * alpha == 0 (sigma == 0, or delta == 0) contributes 0 * rgb = 0: its colour head
-//       (bottleneck + viewdirs + rgb, 17 % of an evaluation) is dead, its density is not (it decides the weights).
+//       (viewdirs' + rgb, 6.9 % of an evaluation: the bottleneck is folded into viewdirs on the host, mlp_layout.h) is dead, its
+//       density is not (it decides the weights).
 // The fused kernel (mlp_kernel.hip) evaluates everything.  Here ONE kernel does only the live work:
 //
 //   RAY-SEQUENTIAL trunk (dense0..7 + alpha -> sigma).  A wave owns one ray at a time and walks its samples in chunks of 32
@@ -16,8 +17,8 @@
 //       trunk outputs h8 of the samples with w > 0 are COMPACTED IN LDS: a staging ring of 3 x 32 columns x 1 KiB beside the
 //       weight ring; whenever 64 columns are staged the four waves of the workgroup run the colour head on them together,
 //       N-SPLIT: every wave takes all 64 columns (two interleaved groups of 32; B operands re-read from the staging tiles) and a
-//       quarter of the output features (bottleneck: 2 of 8 output tiles, viewdirs: 1 of 4), intermediate activations return to
-//       the same staging tiles.  The weight ring switches to the colour part of the stream for the pass and prefetches the
+//       quarter of the output features (1 of viewdirs' 4 output tiles), the viewdirs outputs return to the same staging tiles
+//       for the rgb head.  The weight ring switches to the colour part of the stream for the pass and prefetches the
 //       trunk's first chunks at its end.
 //
 // Every value that reaches a pixel is produced by the same instruction sequence on the same operands as in the fused kernel
@@ -68,7 +69,7 @@ __device__ __forceinline__ void pipe_start(Pipe &P, const LDS_AS char *lds, int 
 #ifndef NERF_SEQ_DIAG_STAMP
 #define NERF_SEQ_DIAG_STAMP 0 // k > 0: wave 0 of every workgroup accumulates s_memtime cycles of phase k of the colour passes into the NEXT launch
                               // slot's counters (read back as nerf_stats.n_hybrid_rays = passes, n_exec_coarse_trunk += cycles): 1 whole pass,
-                              // 2 bottleneck loop, 3 viewdirs loop, 4 tail (rgb head), 5 from the vote barrier to the first pass, 6 between the two loops
+                              // 3 viewdirs loop, 4 tail (rgb head), 5 from the vote barrier to the first pass
 #endif
 #ifndef NERF_SEQ_DIAG_NO_STAGE
 #define NERF_SEQ_DIAG_NO_STAGE 0 // 1: no staging either (the trunk alone, with the scan)
@@ -84,7 +85,7 @@ constexpr int kStageMetaOff = kStageOff + kStageTiles * kStageTileBytes;
 constexpr int kStageVoteOff = kStageMetaOff + kStageCols * 16;
 constexpr int kSeqLdsBytes = kStageVoteOff + 16;
 static_assert(kSeqLdsBytes <= 160 * 1024, "LDS");
-constexpr int kColourChunks = kChunksFull - kChunksSigma; // 16 (bottleneck) + 9 (viewdirs)
+constexpr int kColourChunks = kChunksColourFolded; // 8 (W': bottleneck folded into viewdirs) + 1 (dir encoding)
 static_assert(kRingSlots == 3, "the colour passes keep all three ring slots in flight");
 
 namespace {
@@ -126,7 +127,7 @@ __device__ __forceinline__ void ring_advance(Pipe &P) {
 // mid-chunk sync of a colour pass; returns whether a chunk was selected for refill (its four pieces follow behind the next MFMAs)
 __device__ __forceinline__ bool colour_sync(Pipe &P, int chunk, bool last_pass, const char *trunk_gbase) {
     if (last_pass && chunk == kColourChunks - 3) { P.gbase = trunk_gbase; P.stream_bytes = kChunksSigma * kChunkBytes; P.next_off = 0; }
-    asm volatile("s_waitcnt vmcnt(4)\n\ts_barrier" ::: "memory");
+    asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory"); // lgkmcnt: this wave's operand reads of chunk c (half a chunk old) are done before its slot is refilled
     const bool refill = !(last_pass && chunk == kColourChunks - 1);
     if (refill) pipe_next_chunk(P);
     return refill;
@@ -159,9 +160,10 @@ __device__ __forceinline__ void store_tile(LDS_AS char *tile, int lane, int slot
     }
 }
 
-// One colour pass: bottleneck + viewdirs + rgb (src/network.rs:218-223) on up to 64 staged columns = two GROUPS of 32 (tiles
+// One colour pass: viewdirs' (bottleneck folded in) + rgb (src/network.rs:218-223) on up to 64 staged columns = two GROUPS of 32 (tiles
 // S.head and S.head + 1 of the staging ring; `n_cols` of them are real, the rest is stale LDS whose results are never stored).
-// All four waves; wave w computes output tiles 2w, 2w+1 of the bottleneck and output tile w of viewdirs for ALL columns, the
+// All four waves; wave w computes output tile w of viewdirs for ALL columns, in the fused kernel's order per output (bias, then k
+// ascending over the 8 tiles of relu(h8), then the dir tile), the
 // two groups interleaved: every A operand feeds both, which doubles the MFMAs per chunk -- a chunk carries ~300-500 cycles of fixed
 // cost (mid-chunk wait + barrier, four DMA pieces per wave, operand reads): single-group passes ran at 92 cycles per MFMA, two groups at
 // 73-80 (profiles/r03_seq_colour_pass.md; a dependent MFMA itself issues at 64.00: tools/probes/mfma_chain_probe.hip).
@@ -176,96 +178,37 @@ __device__ __forceinline__ void colour_pass(Pipe &P, const Stage &S, int n_cols,
     const LDS_AS char *tl0 = tile0 + lane * 16, *tl1 = tile1 + lane * 16;
     const f32x4 m0 = S.meta[t0 * 32 + p], m1 = S.meta[t1 * 32 + p]; // {sample index, direction}
 
-    // ---- bottleneck: 128 k-steps, 2 KiB of the stream each (8 output tiles), chunk = 8 k-steps; this wave: tiles 2w, 2w+1 =
-    // elements {2 (w & 1), 2 (w & 1) + 1} of piece g = w >> 1
-    const int a_off = (wave >> 1) * 1024 + (wave & 1) * 8;
-    f32x2 a_cur[8], a_nxt[8];
+    // ---- viewdirs' (the bottleneck folded into viewdirs on the host, mlp_layout.h kChunksFullFolded): 144 k-steps, 1 KiB of the
+    // stream each (4 output tiles), chunk = 16 k-steps = one input tile; this wave: output tile w = element w of every piece
+    const int v_off = wave * 4;
+    float c_cur[16], c_nxt[16];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) a_cur[j] = *(const LDS_AS f32x2 *)(P.rd_base + j * 2048 + a_off);
+    for (int j = 0; j < 16; ++j) c_cur[j] = *(const LDS_AS float *)(P.rd_base + j * 1024 + v_off);
     f32x4 bn0[4], bn1[4];
     load_b_tile(bn0, tl0, 0);
     load_b_tile(bn1, tl1, 0);
-    f32x16 acc00, acc01, acc10, acc11; // [group][tile 2w + k]
-    bias_tile(acc00, small + kBiasOff + 8 * 256 + ((2 * wave) * 2 + h) * 16);
-    bias_tile(acc01, small + kBiasOff + 8 * 256 + ((2 * wave + 1) * 2 + h) * 16);
-    acc10 = acc00; acc11 = acc01;
-    int chunk = 0;
-#if NERF_SEQ_DIAG_STAMP == 2
-    const unsigned long long ts0 = __builtin_amdgcn_s_memtime();
-#endif
-    for (int tt = 0; tt < 8; ++tt) {
-        float bq0[16], bq1[16]; // B operands of this input tile: relu(h8) (the bottleneck reads the ReLU'd dense7 output, :218), one VALU burst
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { bq0[4 * q + e] = relu(bn0[q][e]); bq1[4 * q + e] = relu(bn1[q][e]); }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int half = 0; half < 2; ++half, ++chunk) {
-            bool refill = false;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                if (j == 4) {
-                    refill = colour_sync(P, chunk, last_pass, trunk_gbase);
-                    ring_advance(P);
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) a_nxt[k] = *(const LDS_AS f32x2 *)(P.rd_base + k * 2048 + a_off);
-                    if (half == 1 && tt < 7) { load_b_tile(bn0, tl0, tt + 1); load_b_tile(bn1, tl1, tt + 1); } // next input tile, half a chunk ahead
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                const float b0 = bq0[8 * half + j], b1 = bq1[8 * half + j];
-                acc00 = MFMA(a_cur[j][0], b0, acc00);
-                if (j >= 4) { __builtin_amdgcn_sched_barrier(0); if (refill) pipe_issue_piece(P, j - 4); __builtin_amdgcn_sched_barrier(0); }
-                acc10 = MFMA(a_cur[j][0], b1, acc10);
-                acc01 = MFMA(a_cur[j][1], b0, acc01);
-                acc11 = MFMA(a_cur[j][1], b1, acc11);
-            }
-#pragma unroll
-            for (int k = 0; k < 8; ++k) a_cur[k] = a_nxt[k];
-        }
-    }
-#if NERF_SEQ_DIAG_STAMP == 2
-    diag += __builtin_amdgcn_s_memtime() - ts0;
-#endif
-#if NERF_SEQ_DIAG_STAMP == 6
-    const unsigned long long ts0 = __builtin_amdgcn_s_memtime();
-#endif
-    // bottleneck outputs (no activation) -> the staging tiles, as input tiles 2w, 2w+1 of viewdirs
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); // every wave has read its last h8 operands
-    store_tile(tile0, lane, 2 * wave, acc00); store_tile(tile0, lane, 2 * wave + 1, acc01);
-    store_tile(tile1, lane, 2 * wave, acc10); store_tile(tile1, lane, 2 * wave + 1, acc11);
-    // ---- viewdirs: 144 k-steps, 1 KiB of the stream each (4 output tiles), chunk = 16 k-steps = one input tile; this wave: tile w
-    const int v_off = wave * 4;
-    float c_cur[16], c_nxt[16];
-    // a_cur holds this chunk's operands in the bottleneck's addressing (fetched at the last mid-chunk sync): fetch viewdirs' own
-#pragma unroll
-    for (int j = 0; j < 16; ++j) c_cur[j] = *(const LDS_AS float *)(P.rd_base + j * 1024 + v_off);
     f32x16 V0, V1;
     bias_tile(V0, small + kBiasViewOff + (wave * 2 + h) * 16);
     V1 = V0;
     f32x16 D0, D1; // the ninth input tile: the columns' direction encodings (every wave needs them for its output tile)
     encode_dir<NERF_FAST_SINCOS != 0>(m0[1], m0[2], m0[3], h, D0);
     encode_dir<NERF_FAST_SINCOS != 0>(m1[1], m1[2], m1[3], h, D1);
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); // bottleneck outputs visible
-    load_b_tile(bn0, tl0, 0);
-    load_b_tile(bn1, tl1, 0);
-#if NERF_SEQ_DIAG_STAMP == 6
-    diag += __builtin_amdgcn_s_memtime() - ts0;
-#endif
+    int chunk = 0;
 #if NERF_SEQ_DIAG_STAMP == 3
     const unsigned long long ts0 = __builtin_amdgcn_s_memtime();
 #endif
-    for (int tt = 0; tt < 9; ++tt, ++chunk) { // input tiles 0..7: the bottleneck outputs (no activation); 8: the direction encoding (:219-220)
-        float bq0[16], bq1[16];
+    for (int tt = 0; tt < 9; ++tt, ++chunk) { // input tiles 0..7: relu(h8), the staged trunk outputs (the fused kernel's order: k ascending); 8: the direction encoding (:219-220)
+        float bq0[16], bq1[16]; // B operands of this input tile, one VALU burst
         if (tt < 8) {
 #pragma unroll
             for (int q = 0; q < 4; ++q)
 #pragma unroll
-                for (int e = 0; e < 4; ++e) { bq0[4 * q + e] = bn0[q][e]; bq1[4 * q + e] = bn1[q][e]; }
+                for (int e = 0; e < 4; ++e) { bq0[4 * q + e] = relu(bn0[q][e]); bq1[4 * q + e] = relu(bn1[q][e]); }
         } else {
 #pragma unroll
             for (int r = 0; r < 16; ++r) { bq0[r] = D0[r]; bq1[r] = D1[r]; }
         }
+        __builtin_amdgcn_sched_barrier(0);
         bool refill = false;
 #pragma unroll
         for (int j = 0; j < 16; ++j) {

@@ -40,6 +40,15 @@ constexpr int kChunksSigma = chunksOf(kStepsL0, 8) + 4 * chunksOf(kStepsHid, 8) 
                              2 * chunksOf(kStepsHid, 8);                                  // 120
 constexpr int kChunksFull = kChunksSigma + chunksOf(kStepsHid, 8) + chunksOf(kStepsView, 4); // 145
 
+// The f32 kernels read a FOLDED image of that stream (host_util.cpp fold_network): the bottleneck has no activation and the
+// viewdirs layer is its only consumer, so W' = W_b . W_v[0:256] (256 x 128) and b' = b_v + b_b^T . W_v[0:256] replace the two
+// layers.  Stream: the sigma part unchanged, W' as a 4-output-tile layer over relu(h7) (rows permuted like the bottleneck's),
+// the dir-encoding chunk of viewdirs unchanged.  Small block: b' in the viewdirs bias slot, the rest unchanged.
+constexpr int kStepsViewFolded = kStepsHid + 16;                                         // 256 + 32 dir slots: the same 144 k-steps
+constexpr int kChunksColourFolded = chunksOf(kStepsViewFolded, 4);                       // 8 (W') + 1 (dir encoding) = 9
+constexpr int kChunksFullFolded = kChunksSigma + kChunksColourFolded;                    // 129
+constexpr int kFoldDirChunk = kChunksFull - 1;                                           // chunk of the packed stream that moves to the end of the folded one
+
 // small parameters kept resident in LDS (floats)
 constexpr int kBiasOff = 0;                     // 9 layers x [8 nt][2 h][16]  (dense0..7, bottleneck)
 constexpr int kBiasViewOff = kBiasOff + 9 * 256; // [4 nt][2 h][16]

@@ -113,6 +113,8 @@ static const float *stream_of(const DevNet &n, int dtype) {
     if (dtype == NERF_MLP_F32) return n.wstream;
     return g_bf16_v2 ? (const float *)n.wstream_bf16v2 : (const float *)n.wstream_bf16v3;
 }
+// the small block that goes with stream_of: the f32 kernels read the folded image, every other arithmetic the packed one
+static const float *small_of(const DevNet &n, int dtype) { return dtype == NERF_MLP_F32 ? n.small_f32 : n.small; }
 // NERF_V2_F16_FULL (experiment, variant builds): NERF_MLP_BF16 renders run the f16 twin of the bf16 kernel (fused ray-mode launches only)
 static hipError_t launch_mlp(const nerf_ctx *c, int dtype, const MlpArgs &a, bool full, hipStream_t st) {
 #ifdef NERF_V2_F16_FULL
@@ -304,11 +306,17 @@ int bf16_from_f32_stream(nerf_ctx *c, int which, const std::vector<float> &ws) {
 int upload_packed(nerf_ctx *c, int which, const std::vector<float> &ws, const std::vector<float> &sm) {
     if (ws.size() != (size_t)nerfmlp::kChunksFull * nerfmlp::kChunkFloats || sm.size() != (size_t)nerfmlp::kSmallFloats)
         return fail(c, NERF_ERR_SHAPE, "packed network image has the wrong size for this library build");
+    // the f32 kernels run the bottleneck folded into viewdirs (once per loaded network); the 16-bit arithmetics keep the packed
+    // image's small block (their streams come from upload_bf16_family)
+    std::vector<float> fws, fsm;
+    if (!fold_network(ws, sm, fws, fsm)) return fail(c, NERF_ERR_SHAPE, "internal: folded network image has the wrong size");
     DevNet &d = c->net[which];
-    if (!d.wstream) HIP_TRY(c, hipMalloc((void **)&d.wstream, ws.size() * sizeof(float)));
+    if (!d.wstream) HIP_TRY(c, hipMalloc((void **)&d.wstream, fws.size() * sizeof(float)));
     if (!d.small) HIP_TRY(c, hipMalloc((void **)&d.small, sm.size() * sizeof(float)));
-    HIP_TRY(c, hipMemcpy(d.wstream, ws.data(), ws.size() * sizeof(float), hipMemcpyHostToDevice));
+    if (!d.small_f32) HIP_TRY(c, hipMalloc((void **)&d.small_f32, fsm.size() * sizeof(float)));
+    HIP_TRY(c, hipMemcpy(d.wstream, fws.data(), fws.size() * sizeof(float), hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemcpy(d.small, sm.data(), sm.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(d.small_f32, fsm.data(), fsm.size() * sizeof(float), hipMemcpyHostToDevice));
     d.loaded = true;
     c->cert_margin[which] = c->cert_margin_floor[which]; // certify_zero calibrates itself per network (upload_bf16_family, which follows, decides the pre-filter)
     return NERF_OK;
@@ -545,7 +553,7 @@ int render_once(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *o, 
             HIP_TRY(c, hipMemsetAsync(sigma_out, 0, (size_t)n_rays * spr * sizeof(float), st)); // samples behind the cut stay 0
             if (rgb_out) HIP_TRY(c, hipMemsetAsync(rgb_out, 0, (size_t)n_rays * spr * 3 * sizeof(float), st)); // weight-0 samples: 0 * 0
             SeqArgs q{};
-            q.wstream = stream_of(net, dt); q.small_params = net.small; q.n_rays = n_rays; q.samples_per_ray = spr;
+            q.wstream = stream_of(net, dt); q.small_params = small_of(net, dt); q.n_rays = n_rays; q.samples_per_ray = spr;
             q.ray_dirs = c->d_dirs; q.t = t_in; q.far_ = cam->far_;
             q.origin[0] = cam->pos[0]; q.origin[1] = cam->pos[1]; q.origin[2] = cam->pos[2];
             q.sigma_out = sigma_out; q.ray_counter = ctr; q.live_count = ctr + 1; q.h8 = c->d_h8; q.slot_point = c->d_slot_point;
@@ -620,7 +628,7 @@ int render_once(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *o, 
                 t.done(c->last_render);
             }
             MlpArgs l = b;
-            l.wstream = stream_of(net, dt); l.raw_pre = 0; l.mode = MLP_MODE_LIST; l.rgb_out = rgb_out; l.n_points = (int)cap;
+            l.wstream = stream_of(net, dt); l.small_params = small_of(net, dt); l.raw_pre = 0; l.mode = MLP_MODE_LIST; l.rgb_out = rgb_out; l.n_points = (int)cap;
             l.point_list = c->d_point_list; l.point_list_count = slots;
             if (rgb_out && c->cert_zero_tiles) { l.point_list_count_back = slots + 9; l.skip_empty = 1; l.skip_counter = c->d_skip; }
             l.nonfinite = split_dtype(dt) ? c->d_nonfinite : nullptr;
@@ -642,7 +650,7 @@ int render_once(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *o, 
             return NERF_OK;
         };
         // coarse network: sigma only unless its colours are composited (reference discards them, src/lib.rs:404)
-        a.wstream = stream_of(NC, dtype_coarse); a.small_params = NC.small;
+        a.wstream = stream_of(NC, dtype_coarse); a.small_params = small_of(NC, dtype_coarse);
         a.n_points = n_rays * nc; a.samples_per_ray = nc; a.t = c->d_tc;
         a.sigma_out = c->d_sc; a.rgb_out = o->coarse_only ? c->d_rgbc : nullptr; // sigma-only launch otherwise
         a.skip_empty = o->skip_empty; a.skip_counter = o->skip_empty ? c->d_skip : nullptr; // only full kernels look at it
@@ -686,7 +694,7 @@ int render_once(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *o, 
                 // The coarse densities came from the split arithmetic.  Redo, in exact f32, the rays with a draw in a light CDF
                 // bin (their sample positions are the ill-conditioned ones) and resample just those: same positions as the f32 path.
                 SeqArgs q{};
-                q.wstream = NC.wstream; q.small_params = NC.small; q.n_rays = n_rays; q.samples_per_ray = nc;
+                q.wstream = NC.wstream; q.small_params = NC.small_f32; q.n_rays = n_rays; q.samples_per_ray = nc;
                 q.ray_dirs = c->d_dirs; q.t = c->d_tc; q.far_ = cam->far_;
                 q.origin[0] = cam->pos[0]; q.origin[1] = cam->pos[1]; q.origin[2] = cam->pos[2];
                 q.sigma_out = c->d_sc; q.ray_counter = hctr; q.stats = (unsigned long long *)(hctr + 2);
@@ -706,7 +714,7 @@ int render_once(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *o, 
             }
             t_fine = c->d_tf;
         }
-        a.wstream = stream_of(NF, dtype); a.small_params = NF.small;
+        a.wstream = stream_of(NF, dtype); a.small_params = small_of(NF, dtype);
         a.n_points = n_rays * M; a.samples_per_ray = M; a.t = t_fine;
         a.sigma_out = c->d_sf; a.rgb_out = c->d_rgbf;
         a.clock_out = c->d_clock; // NULL unless NERF_DEBUG_CLOCK=1
@@ -1052,7 +1060,7 @@ void nerf_destroy(nerf_ctx *c) {
     if (!c) return;
     DeviceGuard dg(c->device);
     (void)hipDeviceSynchronize();
-    for (auto &n : c->net) { if (n.wstream) (void)hipFree(n.wstream); if (n.small) (void)hipFree(n.small); if (n.wstream_bf16v2) (void)hipFree(n.wstream_bf16v2); if (n.wstream_bf16v3) (void)hipFree(n.wstream_bf16v3); if (n.wstream_x3) (void)hipFree(n.wstream_x3); if (n.wstream_x2) (void)hipFree(n.wstream_x2); if (n.wstream_f16v2) (void)hipFree(n.wstream_f16v2); }
+    for (auto &n : c->net) { if (n.wstream) (void)hipFree(n.wstream); if (n.small) (void)hipFree(n.small); if (n.small_f32) (void)hipFree(n.small_f32); if (n.wstream_bf16v2) (void)hipFree(n.wstream_bf16v2); if (n.wstream_bf16v3) (void)hipFree(n.wstream_bf16v3); if (n.wstream_x3) (void)hipFree(n.wstream_x3); if (n.wstream_x2) (void)hipFree(n.wstream_x2); if (n.wstream_f16v2) (void)hipFree(n.wstream_f16v2); }
     float *ptrs[] = {c->d_dirs, c->d_tc, c->d_sc, c->d_rgbc, c->d_tf, c->d_sf, c->d_rgbf, c->d_rayfb, c->d_rayaux, c->d_out, c->d_pack};
     for (float *p : ptrs) if (p) (void)hipFree(p);
     if (c->d_scratch) (void)hipFree(c->d_scratch);
@@ -1156,7 +1164,7 @@ static int forward_device(nerf_ctx *c, int which, int dtype, const float *d_pts,
     a.mode = MLP_MODE_POINTS;
     if (!valid_dtype(dtype)) return fail(c, NERF_ERR_INVALID, "mlp_dtype must be NERF_MLP_F32, NERF_MLP_BF16, NERF_MLP_BF16X3 or NERF_MLP_F16X2");
     if (dtype == NERF_MLP_F16X2 && !c->net[which].wstream_x2) return fail(c, NERF_ERR_STATE, "NERF_MLP_F16X2 is unavailable for this network: a weight exceeds the f16 range");
-    a.wstream = stream_of(c->net[which], dtype); a.small_params = c->net[which].small;
+    a.wstream = stream_of(c->net[which], dtype); a.small_params = small_of(c->net[which], dtype);
     a.n_points = (int)n; a.pts_soa = d_pts; a.dirs_aos = d_dirs; a.sigma_out = d_sigma; a.rgb_out = d_rgb;
     a.nonfinite = split_dtype(dtype) ? c->d_nonfinite : nullptr;
     HIP_TRY(c, launch_mlp(c, dtype, a, true, (hipStream_t)stream));

@@ -132,8 +132,12 @@ int main(int argc, char **argv) {
     }
     int n_cus = 0; char arch[64] = {0};
     nerf_device_info(ctx, &n_cus, arch, sizeof arch);
-    const double flop_ray = opts.coarse_only ? opts.n_coarse * 1186816.0
-                                             : opts.n_coarse * 982528.0 + (double)(opts.n_coarse + opts.n_fine) * 1186816.0;
+    // FLOPs per point as EXECUTED by the f32 kernels (bottleneck folded into viewdirs at load time: 2 x 256 x 256 fewer than the
+    // reference's graph).  The 16-bit arithmetics still execute the unfolded head: their full evaluations are priced 11 % low.
+    const double kFlopPerPointFull = 1055744.0, kFlopPerPointFullReferenceGraph = 1186816.0, kFlopPerPointSigma = 982528.0;
+    (void)kFlopPerPointFullReferenceGraph;
+    const double flop_ray = opts.coarse_only ? opts.n_coarse * kFlopPerPointFull
+                                             : opts.n_coarse * kFlopPerPointSigma + (double)(opts.n_coarse + opts.n_fine) * kFlopPerPointFull;
     const bool bf16 = opts.mlp_dtype != NERF_MLP_F32;
     const double mfma_flops = opts.mlp_dtype == NERF_MLP_BF16X3 ? 6.0 : opts.mlp_dtype == NERF_MLP_F16X2 ? 3.0 : 1.0; // executed bf16 MFMA flops per algorithmic f32 flop
     if (gpus > 1) printf("%d GPUs, %s gathered by %s\n", gpus, (opts.skip_dead || opts.skip_empty || opts.certify_zero) ? "rows dealt out round-robin," : "contiguous row bands", gather == NERF_GATHER_PEER ? "xGMI peer copies" : gather == NERF_GATHER_RCCL ? "one RCCL all-gather" : "direct D2H");

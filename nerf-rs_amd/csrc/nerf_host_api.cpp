@@ -123,8 +123,8 @@ int nerf_debug_split_f16x2(const float *values, size_t n, uint16_t *parts) try {
     return NERF_OK;
 } NERF_HOST_CATCH
 
-int nerf_debug_pack_network_dir(const char *dir, float *wstream, size_t wstream_cap, float *small, size_t small_cap,
-                                size_t *wstream_len, size_t *small_len) try {
+static int debug_pack(const char *dir, bool folded, float *wstream, size_t wstream_cap, float *small, size_t small_cap,
+                      size_t *wstream_len, size_t *small_len) {
     if (!dir) return fail_noctx(NERF_ERR_INVALID, "dir is NULL");
     std::map<std::string, Tensor> params;
     std::string err;
@@ -135,11 +135,26 @@ int nerf_debug_pack_network_dir(const char *dir, float *wstream, size_t wstream_
     if (rc) return fail_noctx(rc, err);
     std::vector<float> ws, sm;
     pack_network(hn, ws, sm);
+    if (folded) {
+        std::vector<float> fws, fsm;
+        if (!fold_network(ws, sm, fws, fsm)) return fail_noctx(NERF_ERR_SHAPE, "internal: packed image has the wrong size");
+        ws.swap(fws); sm.swap(fsm);
+    }
     if (wstream_len) *wstream_len = ws.size();
     if (small_len) *small_len = sm.size();
     if (wstream) { if (wstream_cap < ws.size()) return fail_noctx(NERF_ERR_INVALID, "wstream buffer too small"); memcpy(wstream, ws.data(), ws.size() * sizeof(float)); }
     if (small) { if (small_cap < sm.size()) return fail_noctx(NERF_ERR_INVALID, "small buffer too small"); memcpy(small, sm.data(), sm.size() * sizeof(float)); }
     return NERF_OK;
+}
+
+int nerf_debug_pack_network_dir(const char *dir, float *wstream, size_t wstream_cap, float *small, size_t small_cap,
+                                size_t *wstream_len, size_t *small_len) try {
+    return debug_pack(dir, false, wstream, wstream_cap, small, small_cap, wstream_len, small_len);
+} NERF_HOST_CATCH
+
+int nerf_debug_fold_network_dir(const char *dir, float *wstream, size_t wstream_cap, float *small, size_t small_cap,
+                                size_t *wstream_len, size_t *small_len) try {
+    return debug_pack(dir, true, wstream, wstream_cap, small, small_cap, wstream_len, small_len);
 } NERF_HOST_CATCH
 
 int nerf_camera_from_json(const char *path, int width, int height, nerf_camera *out) try {

@@ -13,7 +13,9 @@
 namespace nerfint {
 
 struct DevNet {
-    float *wstream = nullptr, *small = nullptr;
+    float *wstream = nullptr;   // the f32 kernels' stream: the FOLDED image (mlp_layout.h kChunksFullFolded; host_util.h fold_network)
+    float *small = nullptr;     // small block of the packed image: the 16-bit arithmetics, which run the unfolded head
+    float *small_f32 = nullptr; // small block of the folded image (viewdirs bias = b'): the f32 kernels
     uint16_t *wstream_bf16v2 = nullptr; // bf16 pieces in output-tile-major order (mlp_kernel_bf16v2.hip)
     uint16_t *wstream_bf16v3 = nullptr; // bf16 pieces for the 16x16x32 kernel (mlp_kernel_bf16v3.hip)
     uint16_t *wstream_x3 = nullptr;     // three bf16 parts per weight (mlp_kernel_bf16x3.hip)

@@ -30,8 +30,8 @@ with N.Renderer(0) as r:
         msg += f" clock {mhz.value:.0f} MHz"
     peak = 2500.0 if dtype in ("bf16", "bf16x3", "f16x2") else 157.3
     ex = 6.0 if dtype == "bf16x3" else 3.0 if dtype == "f16x2" else 1.0  # executed 16-bit MFMA flops per algorithmic f32 flop
-    fl = ex * best.n_fine_points * 1186816 / (best.ms_fine_mlp * 1e-3) / 1e12
-    cl = ex * best.n_coarse_points * 982528 / (best.ms_coarse_mlp * 1e-3) / 1e12
+    fl = ex * best.n_fine_points * N.FLOP_PER_POINT_FULL / (best.ms_fine_mlp * 1e-3) / 1e12
+    cl = ex * best.n_coarse_points * N.FLOP_PER_POINT_SIGMA / (best.ms_coarse_mlp * 1e-3) / 1e12
     print(f"{os.path.basename(N.lib_path()):34s} total {best.ms_total:8.2f} ms  coarse {best.ms_coarse_mlp:7.2f} ({cl:6.2f} TF)  "
           f"fine {best.ms_fine_mlp:8.2f} ({fl:6.2f} TF = {100 * fl / peak:5.2f}%)  other {best.ms_other:5.2f}  "
           f"rays/s {best.n_rays / best.ms_total * 1e3:9.0f}{msg}", flush=True)
