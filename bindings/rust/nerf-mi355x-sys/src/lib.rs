@@ -130,6 +130,17 @@ extern "C" {
                                  n: usize, rgb_aos: *mut f32, sigma: *mut f32) -> c_int;
     pub fn nerf_forward_batch_device(ctx: *mut nerf_ctx, which: c_int, d_pts_soa: *const f32, d_dirs_aos: *const f32,
                                      n: usize, d_rgb_aos: *mut f32, d_sigma: *mut f32, stream: *mut c_void) -> c_int;
+    /// sigma alone at n points (3 x n SoA): the bits nerf_forward_batch returns as sigma, without directions or the colour head.
+    pub fn nerf_density_batch(ctx: *mut nerf_ctx, which: c_int, pts_soa: *const f32, n: usize, sigma: *mut f32) -> c_int;
+    pub fn nerf_density_batch_device(ctx: *mut nerf_ctx, which: c_int, d_pts_soa: *const f32, n: usize, d_sigma: *mut f32,
+                                     stream: *mut c_void) -> c_int;
+    /// sigma on the lattice lo + step * (ix, iy, iz) generated inside the kernel: `sigma_out` dims[2] x dims[1] x dims[0] (x fastest) or null;
+    /// `occ_bits` ceil(N / 32) words (bit b of word w = sigma of cell 32 w + b > threshold) or null; `n_occupied` / `bounds` (6) optional.
+    pub fn nerf_density_grid(ctx: *mut nerf_ctx, which: c_int, lo: *const f32, step: *const f32, dims: *const i32, sigma_out: *mut f32,
+                             threshold: f32, occ_bits: *mut u32, n_occupied: *mut u64, bounds: *mut i32) -> c_int;
+    pub fn nerf_density_grid_device(ctx: *mut nerf_ctx, which: c_int, lo: *const f32, step: *const f32, dims: *const i32,
+                                    d_sigma_out: *mut f32, threshold: f32, d_occ_bits: *mut u32, n_occupied: *mut u64, bounds: *mut i32,
+                                    stream: *mut c_void) -> c_int;
     pub fn nerf_render_image(ctx: *mut nerf_ctx, cam: *const nerf_camera, opts: *const nerf_render_opts,
                              rgb_out: *mut f32, stats: *mut nerf_stats) -> c_int;
     pub fn nerf_render_image_device(ctx: *mut nerf_ctx, cam: *const nerf_camera, opts: *const nerf_render_opts,

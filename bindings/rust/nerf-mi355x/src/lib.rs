@@ -109,6 +109,35 @@ impl Gpu {
         Ok((rgb, sigma))
     }
 
+    /// sigma alone at points (3 x B SoA): the bits `forward_batch` returns as sigma, without directions or the colour head.
+    pub fn density(&self, fine: bool, points: &[f32]) -> Result<Vec<f32>, Error> {
+        assert_eq!(points.len() % 3, 0);
+        let n = points.len() / 3;
+        let mut sigma = vec![0f32; n];
+        let which = if fine { sys::NERF_NET_FINE } else { sys::NERF_NET_COARSE };
+        check(self.ctx, unsafe { sys::nerf_density_batch(self.ctx, which, points.as_ptr(), n, sigma.as_mut_ptr()) })?;
+        Ok(sigma)
+    }
+
+    /// The density field on the lattice `lo + step * (ix, iy, iz)`, `0 <= i* < dims`, generated inside the kernel (nerf_density_grid):
+    /// sigma (x fastest) if `want_sigma`, and with a `threshold` the occupancy words (bit b of word w = cell 32 w + b), the number of
+    /// occupied cells and their inclusive index bounds `[ix_min, iy_min, iz_min, ix_max, iy_max, iz_max]` (none: mins = dims, maxs = -1).
+    #[allow(clippy::type_complexity)]
+    pub fn density_grid(&self, fine: bool, lo: [f32; 3], step: [f32; 3], dims: [i32; 3], threshold: Option<f32>, want_sigma: bool)
+                        -> Result<(Option<Vec<f32>>, Option<(Vec<u32>, u64, [i32; 6])>), Error> {
+        let n = dims.iter().map(|&d| d.max(0) as usize).product::<usize>(); // a dim <= 0: the library refuses the call
+        let mut sigma = if want_sigma { Some(vec![0f32; n]) } else { None };
+        let mut occ = threshold.map(|_| (vec![0u32; (n + 31) / 32], 0u64, [0i32; 6]));
+        let which = if fine { sys::NERF_NET_FINE } else { sys::NERF_NET_COARSE };
+        let sp = sigma.as_mut().map_or(std::ptr::null_mut(), |v| v.as_mut_ptr());
+        let (bp, cp, rp) = occ.as_mut().map_or((std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut()),
+                                               |o| (o.0.as_mut_ptr(), &mut o.1 as *mut u64, o.2.as_mut_ptr()));
+        check(self.ctx, unsafe {
+            sys::nerf_density_grid(self.ctx, which, lo.as_ptr(), step.as_ptr(), dims.as_ptr(), sp, threshold.unwrap_or(0.0), bp, cp, rp)
+        })?;
+        Ok((sigma, occ))
+    }
+
     /// Linear RGB, pixel (i, j) at `(i * w + j) * 3` (image[i * nx + j], src/lib.rs:552-557); `opts.n_coarse` = camera.samples_per_ray.
     pub fn render_image(&self, cam: &Camera, opts: &RenderOpts) -> Result<(Vec<f32>, Stats), Error> {
         let (w, h) = if opts.crop_w > 0 || opts.crop_h > 0 { (opts.crop_w, opts.crop_h) } else { (cam.nx, cam.ny) };

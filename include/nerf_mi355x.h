@@ -231,6 +231,33 @@ int nerf_forward_batch_ex(nerf_ctx *ctx, int which, int mlp_dtype, const float *
 int nerf_forward_batch_device(nerf_ctx *ctx, int which, const float *d_pts_soa, const float *d_dirs_aos, size_t n,
                               float *d_rgb_aos, float *d_sigma, void *stream);
 
+/* ---- density queries: sigma alone, at caller points or on a lattice the kernel generates itself ------------------------------ */
+/* sigma of network `which` at n points (3 x n SoA as nerf_forward_batch): the same bits nerf_forward_batch returns as sigma (density does
+ * not depend on the view direction, src/network.rs:197-237: it is read off dense7 before the direction is concatenated), without a
+ * direction per point and without the colour head.  f32 arithmetic only.  Host pointers, synchronous; n == 0 is a no-op.  Input domain
+ * and largest n: as nerf_forward_batch (|p| <= 2048 per coordinate for full accuracy; beyond that the accuracy degrades, nothing faults). */
+int nerf_density_batch(nerf_ctx *ctx, int which, const float *pts_soa /*3 x n*/, size_t n, float *sigma /*n*/);
+/* device pointers, asynchronous on `stream` */
+int nerf_density_batch_device(nerf_ctx *ctx, int which, const float *d_pts_soa, size_t n, float *d_sigma, void *stream);
+/* sigma on the lattice p = lo + step * (ix, iy, iz), 0 <= i* < dims[*]: per coordinate the f32 product step * (float)i, then the f32 sum
+ * with lo, each rounded once -- a host that builds the points the same way gets the bits of nerf_density_batch.  The points are made
+ * inside the kernel: nothing but the weights is read.  step may be 0 or negative.  N = dims[0] dims[1] dims[2] is one launch: at most the
+ * largest n of nerf_forward_batch.  The lattice should stay inside nerf_forward_batch's input domain.
+ *   sigma_out  dims[2] x dims[1] x dims[0] floats, x fastest (linear cell ix + dims[0] (iy + dims[1] iz)), or NULL
+ *   occ_bits   ceil(N / 32) uint32 words, bit b of word w = (sigma of linear cell 32 w + b) > threshold (a NaN sigma is not occupied;
+ *              the bits behind cell N - 1 are 0), or NULL; threshold must be >= 0 (not NaN) when occ_bits is given.  An occupancy-only
+ *              query never materialises sigma: N / 8 bytes instead of 4 N
+ *   n_occupied number of set bits; bounds = {ix_min, iy_min, iz_min, ix_max, iy_max, iz_max} of the set cells, inclusive (no set cell:
+ *              mins = dims, maxs = -1).  Both optional, only with occ_bits.
+ * At least one of sigma_out, occ_bits.  f32 arithmetic only.  Host pointers, synchronous. */
+int nerf_density_grid(nerf_ctx *ctx, int which, const float lo[3], const float step[3], const int32_t dims[3], float *sigma_out,
+                      float threshold, uint32_t *occ_bits, uint64_t *n_occupied, int32_t bounds[6]);
+/* d_sigma_out / d_occ_bits: device pointers; n_occupied / bounds: HOST pointers.  Asynchronous on `stream` unless n_occupied or bounds
+ * is given: then the call synchronises the stream before it returns. */
+int nerf_density_grid_device(nerf_ctx *ctx, int which, const float lo[3], const float step[3], const int32_t dims[3],
+                             float *d_sigma_out, float threshold, uint32_t *d_occ_bits, uint64_t *n_occupied, int32_t bounds[6],
+                             void *stream);
+
 /* ---- S3: render_image (src/lib.rs:474-565) ----------------------------------------------------------------- */
 /* rgb_out: crop_h x crop_w x 3 (or ny x nx x 3) linear RGB f32, row-major, index (i*w + j)*3 as image[i*nx+j]
  * (src/lib.rs:552-557).  Unlike the reference (src/lib.rs:491-501) nx, ny need not be multiples of 8. */
@@ -388,7 +415,8 @@ const char *nerf_build_variant(void);
  * n_certify_* / certify_margin / certify_headroom / certify_max_error, renders fail on n_nonfinite_points != 0,
  * nerf_render_opts.band_*, nerf_band_rows, nerf_debug_certify_policy; additive: nerf_render_image_aux, nerf_render_image_aux_device,
  * nerf_render_image_multi_aux, nerf_save_pfm, nerf_render_image_rgba8, nerf_render_image_rgba8_device, nerf_render_image_multi_rgba8,
- * nerf_stage_integrate_rgba8, nerf_save_pam, NERF_ALPHA_*). */
+ * nerf_stage_integrate_rgba8, nerf_save_pam, NERF_ALPHA_*, nerf_density_batch, nerf_density_batch_device, nerf_density_grid,
+ * nerf_density_grid_device). */
 int nerf_abi_version(void);
 /* sizeof(nerf_camera), sizeof(nerf_render_opts), sizeof(nerf_stats) as this library was built: lets a binding written in
  * another language (the Rust `-sys` crate, ctypes) check its struct mirrors at start-up. */

@@ -9,6 +9,7 @@ _LIB = None
 f32p = C.POINTER(C.c_float)
 u8p = C.POINTER(C.c_uint8)
 u32p = C.POINTER(C.c_uint32)
+i32p = C.POINTER(C.c_int32)
 
 
 class NerfError(RuntimeError):
@@ -73,6 +74,11 @@ PROTOTYPES = {
     "nerf_forward_batch_ex": (C.c_int, [C.c_void_p, C.c_int, C.c_int, f32p, f32p, C.c_size_t, f32p, f32p]),
     "nerf_forward_batch_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                                             C.c_void_p, C.c_void_p]),
+    "nerf_density_batch": (C.c_int, [C.c_void_p, C.c_int, f32p, C.c_size_t, f32p]),
+    "nerf_density_batch_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "nerf_density_grid": (C.c_int, [C.c_void_p, C.c_int, f32p, f32p, i32p, f32p, C.c_float, u32p, C.POINTER(C.c_uint64), i32p]),
+    "nerf_density_grid_device": (C.c_int, [C.c_void_p, C.c_int, f32p, f32p, i32p, C.c_void_p, C.c_float, C.c_void_p,
+                                           C.POINTER(C.c_uint64), i32p, C.c_void_p]),
     "nerf_render_image": (C.c_int, [C.c_void_p, C.POINTER(CCamera), C.POINTER(COpts), f32p, C.POINTER(CStats)]),
     "nerf_render_image_device": (C.c_int, [C.c_void_p, C.POINTER(CCamera), C.POINTER(COpts), C.c_void_p, C.c_void_p,
                                            C.POINTER(CStats)]),

@@ -14,7 +14,7 @@ import json
 import numpy as np
 
 from . import _lib
-from ._lib import CCamera, COpts, CStats, NerfError, check, f32p, u8p, u32p
+from ._lib import CCamera, COpts, CStats, NerfError, check, f32p, i32p, u8p, u32p
 
 NET_COARSE, NET_FINE = 0, 1
 MLP_F32, MLP_BF16 = 0, 1
@@ -186,6 +186,77 @@ class Network:
         """Raw device pointers (ints), asynchronous on `stream`."""
         R = self.renderer
         check(R._L.nerf_forward_batch_device(R.handle, self.which, d_points, d_view_dirs, n, d_rgb, d_sigma, stream), R.handle)
+
+    def density(self, points):
+        """sigma alone at points (3, B) f32 SoA -> (B,): the bits forward_batch returns as sigma, without directions and without the
+        colour head (nerf_density_batch; f32 arithmetic).  B == 0 returns an empty array."""
+        pts = _f32(points)
+        if pts.ndim != 2 or pts.shape[0] != 3:
+            raise NerfError(-1, "points must be a 3 x B matrix")
+        n = pts.shape[1]
+        sig = np.empty((n,), np.float32)
+        if n:
+            R = self.renderer
+            check(R._L.nerf_density_batch(R.handle, self.which, _p(pts), n, _p(sig)), R.handle)
+        return sig
+
+    def density_device(self, d_points, d_sigma, n, stream=0):
+        """Raw device pointers (ints), asynchronous on `stream`."""
+        R = self.renderer
+        check(R._L.nerf_density_batch_device(R.handle, self.which, d_points, n, d_sigma, stream), R.handle)
+
+    def density_grid(self, lo, step, dims, threshold=None, want_sigma=True):
+        """sigma on the lattice lo + step * (ix, iy, iz), 0 <= i* < dims = (nx, ny, nz), generated inside the kernel (nerf_density_grid)
+        -> (sigma, bits, count, bounds): sigma (nz, ny, nx) f32 or None (want_sigma=False); with a threshold (>= 0) bits = ceil(N / 32)
+        uint32 words, bit b of word w = sigma of linear cell 32 w + b > threshold (see unpack_occupancy), count = number of occupied cells,
+        bounds = (ix_min, iy_min, iz_min, ix_max, iy_max, iz_max), inclusive -- dims and (-1, -1, -1) if no cell is occupied; without a
+        threshold bits, count and bounds are None."""
+        lo_c, step_c, dims_c, n = _grid_args(lo, step, dims)
+        nx, ny, nz = (int(v) for v in dims_c)
+        sig = np.empty((nz, ny, nx), np.float32) if want_sigma and n > 0 else None
+        bits = np.empty(((n + 31) // 32,), np.uint32) if threshold is not None and n > 0 else None
+        cnt, bounds = C.c_uint64(0), np.zeros(6, np.int32)
+        R = self.renderer
+        check(R._L.nerf_density_grid(R.handle, self.which, _p(lo_c), _p(step_c), dims_c.ctypes.data_as(i32p),
+                                     None if sig is None else _p(sig), 0.0 if threshold is None else float(threshold),
+                                     None if bits is None else bits.ctypes.data_as(u32p),
+                                     None if bits is None else C.byref(cnt), None if bits is None else bounds.ctypes.data_as(i32p)), R.handle)
+        if bits is None:
+            return sig, None, None, None
+        return sig, bits, int(cnt.value), tuple(int(v) for v in bounds)
+
+    def density_grid_device(self, lo, step, dims, d_sigma=None, threshold=0.0, d_bits=None, want_stats=False, stream=0):
+        """Raw device pointers (ints; either may be None): d_sigma nz * ny * nx floats, d_bits ceil(N / 32) words.  Asynchronous on `stream`;
+        want_stats (needs d_bits) synchronises it and returns (count, bounds), else None."""
+        lo_c, step_c, dims_c, _ = _grid_args(lo, step, dims)
+        cnt, bounds = C.c_uint64(0), np.zeros(6, np.int32)
+        R = self.renderer
+        check(R._L.nerf_density_grid_device(R.handle, self.which, _p(lo_c), _p(step_c), dims_c.ctypes.data_as(i32p), d_sigma, float(threshold),
+                                            d_bits, C.byref(cnt) if want_stats else None,
+                                            bounds.ctypes.data_as(i32p) if want_stats else None, stream), R.handle)
+        return (int(cnt.value), tuple(int(v) for v in bounds)) if want_stats else None
+
+
+def _grid_args(lo, step, dims):
+    lo_c, step_c = _f32(lo).reshape(-1), _f32(step).reshape(-1)
+    d = np.asarray(dims)
+    if lo_c.size != 3 or step_c.size != 3 or d.size != 3:
+        raise NerfError(-1, "lo, step and dims must have three entries each")
+    if np.any(d != np.floor(d)) or np.any(np.abs(d) >= 2 ** 31):
+        raise NerfError(-1, "dims must be integers")
+    dims_c = np.ascontiguousarray(d.reshape(-1), dtype=np.int32)
+    n = int(np.prod(dims_c.astype(np.int64))) if np.all(dims_c > 0) else 0     # a dim <= 0: the library refuses the call
+    return lo_c, step_c, dims_c, n
+
+
+def unpack_occupancy(bits, dims):
+    """The occupancy words of density_grid -> bool (nz, ny, nx): bit b of word w is linear cell 32 w + b, x fastest."""
+    nx, ny, nz = (int(v) for v in dims)
+    n = nx * ny * nz
+    words = np.ascontiguousarray(bits, dtype="<u4").reshape(-1)
+    if nx <= 0 or ny <= 0 or nz <= 0 or words.size != (n + 31) // 32:
+        raise NerfError(-1, "bits must hold ceil(nx * ny * nz / 32) words")
+    return np.unpackbits(words.view(np.uint8), bitorder="little")[:n].astype(bool).reshape(nz, ny, nx)
 
 
 def load_network_from_dir(renderer, which, directory):

@@ -190,7 +190,8 @@ __device__ __forceinline__ void rgb_head(const Tiles &V, const LDS_AS float *sma
 // Raw per-point inputs: 6 floats.  MODE_POINTS: position + direction as given (src/network.rs:197).  MODE_RAYS:
 // (t, unused, unused) + the ray's unit direction; p = origin + dir_hat * t is formed at use with the multiply and the
 // add rounded separately (src/lib.rs:396 / :436).  The index is clamped: padding lanes of the last tile and the
-// look-ahead tile read the last point.
+// look-ahead tile read the last point.  MODE 3 (MLP_MODE_GRID) and 4 (MLP_MODE_POINTS without directions) belong to the f32
+// sigma-only kernel (mlp_kernel.hip) alone.
 struct RawIn { float a, b, c, dx, dy, dz; };
 
 // MLP_MODE_LIST: the list's length lives on the device; n_points is its CAPACITY (entries beyond it were counted, not stored: the host
@@ -230,6 +231,18 @@ __device__ __forceinline__ RawIn load_raw(const Args &A, int tile_idx, int wave,
         return r;
     }
     i = i < A.n_points ? i : A.n_points - 1;
+    if (MODE == 3) { // MLP_MODE_GRID: the cell's lattice indices as floats (x fastest); nothing is loaded.  Padding lanes take the last cell.
+        const unsigned nx = (unsigned)A.grid_n[0], ny = (unsigned)A.grid_n[1];
+        const unsigned row = (unsigned)i / nx;
+        r.a = (float)((unsigned)i - row * nx); r.b = (float)(row % ny); r.c = (float)(row / ny);
+        r.dx = 0.f; r.dy = 0.f; r.dz = 0.f;
+        return r;
+    }
+    if (MODE == 4) { // sigma-only MLP_MODE_POINTS (nerf_density_batch): the position alone, dirs_aos is NULL
+        r.a = A.pts_soa[i]; r.b = A.pts_soa[(size_t)A.n_points + i]; r.c = A.pts_soa[2 * (size_t)A.n_points + i];
+        r.dx = 0.f; r.dy = 0.f; r.dz = 0.f;
+        return r;
+    }
     if (MODE == 0) {
         r.a = A.pts_soa[i]; r.b = A.pts_soa[(size_t)A.n_points + i]; r.c = A.pts_soa[2 * (size_t)A.n_points + i];
         r.dx = A.dirs_aos[3 * (size_t)i]; r.dy = A.dirs_aos[3 * (size_t)i + 1]; r.dz = A.dirs_aos[3 * (size_t)i + 2];
@@ -245,6 +258,10 @@ template <int MODE, class Args>
 __device__ __forceinline__ void point_of(const Args &A, const RawIn &in, float &px, float &py, float &pz) {
     if (MODE == 0) {
         px = in.a; py = in.b; pz = in.c;
+    } else if (MODE == 3) { // MLP_MODE_GRID: lo + step * index, rounded like the ray points below
+        px = __fadd_rn(A.grid_lo[0], __fmul_rn(A.grid_step[0], in.a));
+        py = __fadd_rn(A.grid_lo[1], __fmul_rn(A.grid_step[1], in.b));
+        pz = __fadd_rn(A.grid_lo[2], __fmul_rn(A.grid_step[2], in.c));
     } else {
         px = __fadd_rn(A.origin[0], __fmul_rn(in.dx, in.a));
         py = __fadd_rn(A.origin[1], __fmul_rn(in.dy, in.a));

@@ -2,7 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-enum { MLP_MODE_POINTS = 0, MLP_MODE_RAYS = 1, MLP_MODE_LIST = 2 }; // LIST (f32 and split kernels): ray mode over a device-side list of sample indices (bit 31 of an entry: audited certificate)
+enum { MLP_MODE_POINTS = 0, MLP_MODE_RAYS = 1, MLP_MODE_LIST = 2, MLP_MODE_GRID = 3 }; // LIST (f32 and split kernels): ray mode over a device-side list of sample indices (bit 31 of an entry: audited certificate)
+// GRID (f32 sigma-only kernel, nerf_density_grid): the kernel makes its own points, slot i = cell (i % nx, (i / nx) % ny, i / (nx ny)) of a lattice
 
 struct MlpArgs {
     const float *wstream;      // weight stream of the launched arithmetic (mlp_layout.h), device; f32 kernels: the FOLDED image (kChunksFullFolded)
@@ -34,11 +35,20 @@ struct MlpArgs {
     // listed samples that are probably zeros there (and the audited certificates), so that their tiles are all-zero and skip_empty skips
     // their colour heads.  Slots [0, front) map to entries [0, front), slots [front, front + back) to the last `back` entries.
     const unsigned int *point_list_count_back;
+    // MLP_MODE_GRID (appended: the fields above keep their kernarg offsets): p = grid_lo + grid_step * (float)cell index, the multiply and
+    // the add rounded separately (a host can restate the points bit for bit); n_points = nx * ny * nz.  sigma_out may be NULL.
+    float grid_lo[3], grid_step[3];
+    int grid_n[3];
+    // fused occupancy (optional): word w = bit b set iff sigma of cell 32 w + b > occ_threshold (NaN: not occupied); ceil(n_points / 32) words,
+    // every one of them written by the launch, the bits behind the last cell 0
+    float occ_threshold;
+    unsigned int *occ_bits;
 };
 
 // Sets the dynamic-LDS attribute of every kernel instantiation on the current device.
 hipError_t nerf_mlp_init();
-// full=false evaluates dense0..7 + alpha only (sigma); n_blocks = persistent workgroups (<= #CUs).
+// full=false evaluates dense0..7 + alpha only (sigma); n_blocks = persistent workgroups (<= #CUs).  Sigma-only MLP_MODE_POINTS
+// (nerf_density_batch) never reads dirs_aos; MLP_MODE_GRID exists sigma-only.
 hipError_t nerf_mlp_launch(const MlpArgs &a, bool full, int n_blocks, hipStream_t stream);
 // bf16-operand variant (mlp_kernel_bf16v2.hip): a.wstream is the output-tile-major stream (mlp_layout.h kChunks*Bf16V2)
 hipError_t nerf_mlp_bf16v2_init();

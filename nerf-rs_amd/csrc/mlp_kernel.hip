@@ -71,17 +71,19 @@ __global__ __launch_bounds__(256, 1) void nerf_mlp_kernel(const MlpArgs A) {
 
     const int n_points = MODE == MLP_MODE_LIST ? list_length(A) : A.n_points; // list mode: the length lives on the device
     const int n_tiles = (n_points + kPointsPerBlock - 1) / kPointsPerBlock;
+    // what load_raw fetches: the sigma-only point instance (nerf_density_batch) has no directions to read
+    constexpr int LOAD = (!FULL && MODE == MLP_MODE_POINTS) ? 4 : MODE;
 #if NERF_PREFETCH_INPUTS
-    RawIn nxt = load_raw<MODE>(A, blockIdx.x, wave, p);
+    RawIn nxt = load_raw<LOAD>(A, blockIdx.x, wave, p);
 #endif
     for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const int slot = tile * kPointsPerBlock + wave * kPointsPerWave + p;
         const bool valid = slot < n_points;
 #if NERF_PREFETCH_INPUTS
         const RawIn in = nxt;
-        nxt = load_raw<MODE>(A, tile + gridDim.x, wave, p); // consumed one tile (~250 us) later
+        nxt = load_raw<LOAD>(A, tile + gridDim.x, wave, p); // consumed one tile (~250 us) later
 #else
-        const RawIn in = load_raw<MODE>(A, tile, wave, p);
+        const RawIn in = load_raw<LOAD>(A, tile, wave, p);
 #endif
         float px, py, pz;
         point_of<MODE>(A, in, px, py, pz);
@@ -118,6 +120,14 @@ __global__ __launch_bounds__(256, 1) void nerf_mlp_kernel(const MlpArgs A) {
         hidden_layer<true>(X, Y, small + kBiasOff + 7 * 256, P, h);
         const float pre = alpha_pre(Y, small, h);
         sigma = fmaxf(pre, 0.f);
+        if (MODE == MLP_MODE_GRID) {
+            if (valid && h == 0 && A.sigma_out) A.sigma_out[i] = sigma;
+            if (A.occ_bits) { // fused occupancy: one word per 32-point wave tile, bit = lane (NaN > threshold is false)
+                const unsigned word = (unsigned)__ballot(valid && h == 0 && sigma > A.occ_threshold);
+                const int slot0 = tile * kPointsPerBlock + wave * kPointsPerWave;
+                if (lane == 0 && slot0 < n_points) A.occ_bits[slot0 >> 5] = word;
+            }
+        } else
         if (valid && h == 0) A.sigma_out[i] = audit ? pre : sigma;
         if (FULL && A.skip_empty) {
             // Empty-tile skip (exact): if sigma == 0 for all 128 points of this workgroup's tile, then
@@ -168,11 +178,12 @@ static hipError_t launch_t(const MlpArgs &a, int n_blocks, hipStream_t stream) {
 }
 
 hipError_t nerf_mlp_init() {
-    // forward_batch always evaluates the full head, so the sigma-only kernel exists in ray mode only
-    const void *ks[5] = {(const void *)nerf_mlp_kernel<true, MLP_MODE_POINTS>, (const void *)nerf_mlp_kernel<true, MLP_MODE_RAYS>,
+    // sigma-only in point mode is nerf_density_batch, in grid mode nerf_density_grid (no colour on a lattice)
+    const void *ks[7] = {(const void *)nerf_mlp_kernel<true, MLP_MODE_POINTS>, (const void *)nerf_mlp_kernel<true, MLP_MODE_RAYS>,
                          (const void *)nerf_mlp_kernel<false, MLP_MODE_RAYS>, (const void *)nerf_mlp_kernel<true, MLP_MODE_LIST>,
-                         (const void *)nerf_mlp_kernel<false, MLP_MODE_LIST>};
-    for (int i = 0; i < 5; ++i) {
+                         (const void *)nerf_mlp_kernel<false, MLP_MODE_LIST>, (const void *)nerf_mlp_kernel<false, MLP_MODE_POINTS>,
+                         (const void *)nerf_mlp_kernel<false, MLP_MODE_GRID>};
+    for (int i = 0; i < 7; ++i) {
         hipError_t e = hipFuncSetAttribute(ks[i], hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
         if (e != hipSuccess) return e;
     }
@@ -188,7 +199,13 @@ hipError_t nerf_mlp_launch(const MlpArgs &a, bool full, int n_blocks, hipStream_
         if (!a.point_list || !a.point_list_count) return hipErrorInvalidValue;
         return full ? launch_t<true, MLP_MODE_LIST>(a, n_blocks, stream) : launch_t<false, MLP_MODE_LIST>(a, n_blocks, stream);
     }
+    if (a.mode == MLP_MODE_GRID) {
+        if (full || a.grid_n[0] <= 0 || a.grid_n[1] <= 0 || a.grid_n[2] <= 0 || (!a.sigma_out && !a.occ_bits)) return hipErrorInvalidValue;
+        const unsigned long long plane = (unsigned long long)a.grid_n[0] * (unsigned long long)a.grid_n[1];
+        if (plane > (unsigned long long)a.n_points || plane * (unsigned long long)a.grid_n[2] != (unsigned long long)a.n_points) return hipErrorInvalidValue;
+        return launch_t<false, MLP_MODE_GRID>(a, n_blocks, stream);
+    }
     if (a.mode == MLP_MODE_POINTS)
-        return full ? launch_t<true, MLP_MODE_POINTS>(a, n_blocks, stream) : hipErrorInvalidValue; // no sigma-only forward_batch
+        return full ? launch_t<true, MLP_MODE_POINTS>(a, n_blocks, stream) : launch_t<false, MLP_MODE_POINTS>(a, n_blocks, stream);
     return full ? launch_t<true, MLP_MODE_RAYS>(a, n_blocks, stream) : launch_t<false, MLP_MODE_RAYS>(a, n_blocks, stream);
 }

@@ -1202,6 +1202,131 @@ int nerf_forward_batch_ex(nerf_ctx *c, int which, int dtype, const float *pts, c
     return NERF_OK;
 } NERF_CATCH(c)
 
+// ---- density queries (f32 sigma-only kernel: MLP_MODE_POINTS without directions, MLP_MODE_GRID) -----------------------------------
+// Argument checks come before anything that needs the context or the device, so that a host without a GPU gets the same answers.
+static int density_batch_device(nerf_ctx *c, int which, const float *d_pts, size_t n, float *d_sigma, hipStream_t st) {
+    if (which != NERF_NET_COARSE && which != NERF_NET_FINE) return fail(c, NERF_ERR_INVALID, "which must be NERF_NET_COARSE or NERF_NET_FINE");
+    if (!c) return fail(nullptr, NERF_ERR_INVALID, "ctx is NULL");
+    if (n == 0) return NERF_OK;
+    if (!d_pts || !d_sigma) return fail(c, NERF_ERR_INVALID, "NULL buffer");
+    if (n > max_batch_points(c->n_cus)) return fail(c, NERF_ERR_INVALID, "batch too large (n plus one grid stride of tiles must fit in int32)");
+    if (!c->net[which].loaded) return fail(c, NERF_ERR_STATE, "network not loaded");
+    DeviceGuard dg(c->device);
+    MlpArgs a{};
+    a.mode = MLP_MODE_POINTS;
+    a.wstream = c->net[which].wstream; a.small_params = c->net[which].small_f32;
+    a.n_points = (int)n; a.pts_soa = d_pts; a.sigma_out = d_sigma;
+    HIP_TRY(c, nerf_mlp_launch(a, false, c->n_cus, st));
+    return NERF_OK;
+}
+
+int nerf_density_batch_device(nerf_ctx *c, int which, const float *d_pts, size_t n, float *d_sigma, void *stream) try {
+    return density_batch_device(c, which, d_pts, n, d_sigma, (hipStream_t)stream);
+} NERF_CATCH(c)
+
+int nerf_density_batch(nerf_ctx *c, int which, const float *pts, size_t n, float *sigma) try {
+    if (which != NERF_NET_COARSE && which != NERF_NET_FINE) return fail(c, NERF_ERR_INVALID, "which must be NERF_NET_COARSE or NERF_NET_FINE");
+    if (!c) return fail(nullptr, NERF_ERR_INVALID, "ctx is NULL");
+    if (n == 0) return NERF_OK;
+    if (!pts || !sigma) return fail(c, NERF_ERR_INVALID, "NULL buffer");
+    if (n > max_batch_points(c->n_cus)) return fail(c, NERF_ERR_INVALID, "batch too large (n plus one grid stride of tiles must fit in int32)");
+    if (!c->net[which].loaded) return fail(c, NERF_ERR_STATE, "network not loaded");
+    DeviceGuard dg(c->device);
+    int rc;
+    if ((rc = ensure_bytes(c, &c->d_scratch, &c->scratch_bytes, n * 4 * sizeof(float)))) return rc;
+    float *d_pts = (float *)c->d_scratch, *d_sig = d_pts + 3 * n;
+    HIP_TRY(c, hipMemcpyAsync(d_pts, pts, 3 * n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if ((rc = density_batch_device(c, which, d_pts, n, d_sig, c->stream))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(sigma, d_sig, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return NERF_OK;
+} NERF_CATCH(c)
+
+// everything nerf_density_grid* can refuse without a device; *n_cells = dims[0] dims[1] dims[2]
+static int density_grid_check(nerf_ctx *c, int which, const float *lo, const float *step, const int32_t *dims, const void *sigma_out,
+                              float threshold, const void *occ_bits, const void *n_occupied, const void *bounds, size_t *n_cells) {
+    if (which != NERF_NET_COARSE && which != NERF_NET_FINE) return fail(c, NERF_ERR_INVALID, "which must be NERF_NET_COARSE or NERF_NET_FINE");
+    if (!lo || !step || !dims) return fail(c, NERF_ERR_INVALID, "lo, step and dims must not be NULL");
+    for (int k = 0; k < 3; ++k) {
+        if (dims[k] <= 0) return fail(c, NERF_ERR_INVALID, "dims must be positive");
+        if (!std::isfinite(lo[k]) || !std::isfinite(step[k])) return fail(c, NERF_ERR_INVALID, "lo and step must be finite");
+    }
+    if (!sigma_out && !occ_bits) return fail(c, NERF_ERR_INVALID, "at least one of sigma_out and occ_bits must be given");
+    if (occ_bits && !(threshold >= 0.0f)) return fail(c, NERF_ERR_INVALID, "threshold must be >= 0 (and not NaN) when occ_bits is given");
+    if (!occ_bits && (n_occupied || bounds)) return fail(c, NERF_ERR_INVALID, "n_occupied and bounds need occ_bits");
+    // one launch, no slabs: N within the largest batch (the tighter, device-dependent limit follows once the context is known)
+    const size_t limit = c ? max_batch_points(c->n_cus) : max_batch_points(0);
+    const unsigned long long plane = (unsigned long long)dims[0] * (unsigned long long)dims[1];
+    if (plane > limit || plane * (unsigned long long)dims[2] > limit)
+        return fail(c, NERF_ERR_INVALID, "grid too large: dims[0] * dims[1] * dims[2] must fit in one launch (as nerf_forward_batch's n)");
+    *n_cells = (size_t)(plane * (unsigned long long)dims[2]);
+    if (!c) return fail(nullptr, NERF_ERR_INVALID, "ctx is NULL");
+    if (!c->net[which].loaded) return fail(c, NERF_ERR_STATE, "network not loaded");
+    return NERF_OK;
+}
+
+// the MLP launch in grid mode and, with d_stats (8 ints, device), the statistics of its occupancy words; arguments already checked
+static int density_grid_launch(nerf_ctx *c, int which, const float *lo, const float *step, const int32_t *dims, size_t n_cells,
+                               float *d_sigma, float threshold, uint32_t *d_bits, int *d_stats, hipStream_t st) {
+    MlpArgs a{};
+    a.mode = MLP_MODE_GRID;
+    a.wstream = c->net[which].wstream; a.small_params = c->net[which].small_f32;
+    a.n_points = (int)n_cells; a.sigma_out = d_sigma;
+    for (int k = 0; k < 3; ++k) { a.grid_lo[k] = lo[k]; a.grid_step[k] = step[k]; a.grid_n[k] = dims[k]; }
+    a.occ_threshold = threshold; a.occ_bits = d_bits;
+    HIP_TRY(c, nerf_mlp_launch(a, false, c->n_cus, st));
+    if (d_stats) HIP_TRY(c, launch_occupancy_stats(d_bits, n_cells, dims[0], dims[1], dims[2], d_stats, st));
+    return NERF_OK;
+}
+
+static void density_grid_stats_out(const int *h, uint64_t *n_occupied, int32_t *bounds) {
+    if (n_occupied) *n_occupied = (uint64_t)(uint32_t)h[0] | ((uint64_t)(uint32_t)h[1] << 32);
+    if (bounds) for (int k = 0; k < 6; ++k) bounds[k] = h[2 + k];
+}
+
+int nerf_density_grid_device(nerf_ctx *c, int which, const float lo[3], const float step[3], const int32_t dims[3], float *d_sigma_out,
+                             float threshold, uint32_t *d_occ_bits, uint64_t *n_occupied, int32_t bounds[6], void *stream) try {
+    size_t n_cells = 0;
+    int rc;
+    if ((rc = density_grid_check(c, which, lo, step, dims, d_sigma_out, threshold, d_occ_bits, n_occupied, bounds, &n_cells))) return rc;
+    DeviceGuard dg(c->device);
+    const bool stats = n_occupied || bounds;
+    if (stats && (rc = ensure_bytes(c, &c->d_scratch, &c->scratch_bytes, 8 * sizeof(int)))) return rc;
+    int *d_stats = stats ? (int *)c->d_scratch : nullptr;
+    if ((rc = density_grid_launch(c, which, lo, step, dims, n_cells, d_sigma_out, threshold, d_occ_bits, d_stats, (hipStream_t)stream))) return rc;
+    if (stats) {
+        int h[8];
+        HIP_TRY(c, hipMemcpyAsync(h, d_stats, sizeof h, hipMemcpyDeviceToHost, (hipStream_t)stream));
+        HIP_TRY(c, hipStreamSynchronize((hipStream_t)stream));
+        density_grid_stats_out(h, n_occupied, bounds);
+    }
+    return NERF_OK;
+} NERF_CATCH(c)
+
+int nerf_density_grid(nerf_ctx *c, int which, const float lo[3], const float step[3], const int32_t dims[3], float *sigma_out,
+                      float threshold, uint32_t *occ_bits, uint64_t *n_occupied, int32_t bounds[6]) try {
+    size_t n_cells = 0;
+    int rc;
+    if ((rc = density_grid_check(c, which, lo, step, dims, sigma_out, threshold, occ_bits, n_occupied, bounds, &n_cells))) return rc;
+    DeviceGuard dg(c->device);
+    // staging: [8 ints of statistics][occupancy words][sigma], each only if asked for
+    const bool stats = n_occupied || bounds;
+    const size_t n_words = occ_bits ? (n_cells + 31) / 32 : 0;
+    const size_t bytes = 8 * sizeof(int) + n_words * sizeof(uint32_t) + (sigma_out ? n_cells * sizeof(float) : 0);
+    if ((rc = ensure_bytes(c, &c->d_scratch, &c->scratch_bytes, bytes))) return rc;
+    int *d_stats = (int *)c->d_scratch;
+    uint32_t *d_bits = occ_bits ? (uint32_t *)(d_stats + 8) : nullptr;
+    float *d_sigma = sigma_out ? (float *)(d_stats + 8) + n_words : nullptr;
+    if ((rc = density_grid_launch(c, which, lo, step, dims, n_cells, d_sigma, threshold, d_bits, stats ? d_stats : nullptr, c->stream))) return rc;
+    int h[8];
+    if (sigma_out) HIP_TRY(c, hipMemcpyAsync(sigma_out, d_sigma, n_cells * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (occ_bits) HIP_TRY(c, hipMemcpyAsync(occ_bits, d_bits, n_words * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (stats) HIP_TRY(c, hipMemcpyAsync(h, d_stats, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (stats) density_grid_stats_out(h, n_occupied, bounds);
+    return NERF_OK;
+} NERF_CATCH(c)
+
 int nerf_render_image_aux_device(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *opts, float *d_rgb_out,
                                  float *d_depth_out, float *d_opacity_out, void *stream, nerf_stats *stats) try {
     if (!c) return fail(nullptr, NERF_ERR_INVALID, "ctx is NULL");

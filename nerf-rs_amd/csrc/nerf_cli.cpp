@@ -6,6 +6,8 @@
 // With no flags it reproduces the reference's run: 256x256, 64 coarse + 128 fine samples, ./output.ppm.
 // --depth / --opacity add the expected-depth and opacity maps (nerf_render_image_aux) as one-channel PFM files.
 // --rgba adds the display-ready frame (nerf_render_image_rgba8: packed on the device, over --background, with --alpha) as a PAM file.
+// --density-grid writes the density field on a lattice (nerf_density_grid): raw little-endian f32, x fastest, and / or the occupancy words;
+// with no image output asked for beside it (--out, --depth, --opacity, --rgba) the render is skipped.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -22,6 +24,8 @@ static void usage(const char *argv0) {
             "          [--device ID | --gpus N | --devices ID,ID,... [--gather host|peer|rccl]] [--frames K] [--out FILE.ppm]\n"
             "          [--depth FILE.pfm] [--opacity FILE.pfm]\n"
             "          [--rgba FILE.pam [--background R,G,B] [--alpha opaque|premultiplied|straight]]\n"
+            "          [--density-grid NX,NY,NZ --grid-lo X,Y,Z --grid-step SX,SY,SZ [--grid-net coarse|fine] [--grid-threshold T]\n"
+            "           [--grid-out FILE.raw] [--grid-occupancy FILE.bits]]   (at least one of the two files; no image flag: no render)\n"
             "defaults: --scene lego_rust --width 256 --height 256 --coarse 64 --fine 128 --out output.ppm\n",
             argv0);
 }
@@ -29,6 +33,11 @@ static void usage(const char *argv0) {
 int main(int argc, char **argv) {
     std::string scene = getenv("NERF_SCENE_DIR") ? getenv("NERF_SCENE_DIR") : "lego_rust";
     std::string out = "output.ppm", depth_path, opacity_path, rgba_path;
+    std::string grid_out, grid_bits_path;
+    int32_t grid_dims[3] = {0, 0, 0};
+    float grid_lo[3] = {0.f, 0.f, 0.f}, grid_step[3] = {0.f, 0.f, 0.f}, grid_threshold = 0.0f;
+    int grid_net = NERF_NET_FINE;
+    bool want_grid = false, have_grid_lo = false, have_grid_step = false, want_image = false;
     float background[3] = {1.0f, 1.0f, 1.0f};
     bool have_background = false;
     int alpha_mode = NERF_ALPHA_OPAQUE;
@@ -62,10 +71,20 @@ int main(int argc, char **argv) {
         else if (a == "--gather") { const std::string g = next(); gather = g == "peer" ? NERF_GATHER_PEER : g == "rccl" ? NERF_GATHER_RCCL : NERF_GATHER_HOST; }
         else if (a == "--device") device = atoi(next());
         else if (a == "--frames") frames = atoi(next());
-        else if (a == "--out") out = next();
-        else if (a == "--depth") depth_path = next();
-        else if (a == "--opacity") opacity_path = next();
-        else if (a == "--rgba") rgba_path = next();
+        else if (a == "--out") { out = next(); want_image = true; }
+        else if (a == "--depth") { depth_path = next(); want_image = true; }
+        else if (a == "--opacity") { opacity_path = next(); want_image = true; }
+        else if (a == "--rgba") { rgba_path = next(); want_image = true; }
+        else if (a == "--density-grid") {
+            if (sscanf(next(), "%d,%d,%d", &grid_dims[0], &grid_dims[1], &grid_dims[2]) != 3) { usage(argv[0]); return 2; }
+            want_grid = true;
+        }
+        else if (a == "--grid-lo") { if (sscanf(next(), "%f,%f,%f", &grid_lo[0], &grid_lo[1], &grid_lo[2]) != 3) { usage(argv[0]); return 2; } have_grid_lo = true; }
+        else if (a == "--grid-step") { if (sscanf(next(), "%f,%f,%f", &grid_step[0], &grid_step[1], &grid_step[2]) != 3) { usage(argv[0]); return 2; } have_grid_step = true; }
+        else if (a == "--grid-net") { const std::string n = next(); if (n == "coarse") grid_net = NERF_NET_COARSE; else if (n == "fine") grid_net = NERF_NET_FINE; else { usage(argv[0]); return 2; } }
+        else if (a == "--grid-threshold") grid_threshold = strtof(next(), nullptr);
+        else if (a == "--grid-out") grid_out = next();
+        else if (a == "--grid-occupancy") grid_bits_path = next();
         else if (a == "--background") {
             if (sscanf(next(), "%f,%f,%f", &background[0], &background[1], &background[2]) != 3) { usage(argv[0]); return 2; }
             have_background = true;
@@ -80,6 +99,9 @@ int main(int argc, char **argv) {
         } else { usage(argv[0]); return a == "--help" || a == "-h" ? 0 : 2; }
     }
 
+    if (want_grid && (!have_grid_lo || !have_grid_step || (grid_out.empty() && grid_bits_path.empty()))) { usage(argv[0]); return 2; }
+    if (!want_grid && (have_grid_lo || have_grid_step || !grid_out.empty() || !grid_bits_path.empty())) { usage(argv[0]); return 2; }
+
     // one context per GPU (--gpus N: devices 0..N-1, the rayon fan-out of src/lib.rs:533-550 becomes a fan-out over devices)
     if (gpus < 1) { usage(argv[0]); return 2; }
     std::vector<nerf_ctx *> ctxs(gpus, nullptr);
@@ -91,6 +113,40 @@ int main(int argc, char **argv) {
             fprintf(stderr, "error: %s\n", nerf_last_error(c));
             return 1;
         }
+    if (want_grid) { // the density field on the first context (one launch, one GPU)
+        const bool ok_dims = grid_dims[0] > 0 && grid_dims[1] > 0 && grid_dims[2] > 0;
+        const size_t cells = ok_dims ? (size_t)grid_dims[0] * (size_t)grid_dims[1] * (size_t)grid_dims[2] : 0; // the library refuses bad dims and sizes beyond one launch
+        std::vector<float> sigma;
+        std::vector<uint32_t> bits;
+        if (ok_dims && cells < ((size_t)1 << 31)) {
+            if (!grid_out.empty()) sigma.resize(cells);
+            if (!grid_bits_path.empty()) bits.resize((cells + 31) / 32);
+        }
+        uint64_t occupied = 0;
+        int32_t bounds[6] = {0, 0, 0, 0, 0, 0};
+        if (nerf_density_grid(ctx, grid_net, grid_lo, grid_step, grid_dims, sigma.empty() ? nullptr : sigma.data(), grid_threshold,
+                              bits.empty() ? nullptr : bits.data(), bits.empty() ? nullptr : &occupied, bits.empty() ? nullptr : bounds)) {
+            fprintf(stderr, "error: %s\n", nerf_last_error(ctx));
+            return 1;
+        }
+        auto dump = [](const std::string &path, const void *data, size_t bytes) { // the host is little-endian: the bytes as they are
+            FILE *f = fopen(path.c_str(), "wb");
+            const bool ok = f && fwrite(data, 1, bytes, f) == bytes;
+            if (f && fclose(f)) return false;
+            return ok;
+        };
+        if (!sigma.empty() && !dump(grid_out, sigma.data(), sigma.size() * sizeof(float))) { fprintf(stderr, "error: cannot write %s\n", grid_out.c_str()); return 1; }
+        if (!bits.empty() && !dump(grid_bits_path, bits.data(), bits.size() * sizeof(uint32_t))) { fprintf(stderr, "error: cannot write %s\n", grid_bits_path.c_str()); return 1; }
+        printf("density grid %d x %d x %d (%s network): %zu cells", grid_dims[0], grid_dims[1], grid_dims[2], grid_net == NERF_NET_FINE ? "fine" : "coarse", cells);
+        if (!bits.empty())
+            printf(", %llu with sigma > %g, index bounds x %d..%d y %d..%d z %d..%d", (unsigned long long)occupied, (double)grid_threshold,
+                   bounds[0], bounds[3], bounds[1], bounds[4], bounds[2], bounds[5]);
+        printf("\n");
+        if (!want_image) {
+            for (nerf_ctx *c : ctxs) nerf_destroy(c);
+            return 0;
+        }
+    }
     nerf_camera cam;
     if (nerf_camera_from_json((scene + "/tf_reference_samples.json").c_str(), width, height, &cam)) {
         fprintf(stderr, "error: %s\n", nerf_last_error(nullptr));

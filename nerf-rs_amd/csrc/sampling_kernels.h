@@ -73,6 +73,9 @@ hipError_t launch_box_downsample(const float *rays, float *out, int w, int h, in
 hipError_t launch_pack_rgba8(const float *rgb, const float *opacity, uint32_t *out, size_t n_pixels, int alpha_mode, hipStream_t st);
 // multi-GPU: n gathered bands (slot_floats apart, rows packed) -> the h x w x nch frame; stripe = 0: contiguous bands
 hipError_t launch_bands_to_frame(const float *slots, float *frame, int w, int h, int n, int stripe, size_t slot_floats, int nch, hipStream_t st);
+// nerf_density_grid: count and index bounds of the set bits of an occupancy word array (ceil(n_cells / 32) words, x fastest);
+// out8 (device, 8 ints) = {count low, count high, ix_min, iy_min, iz_min, ix_max, iy_max, iz_max}; empty: mins = dims, maxs = -1
+hipError_t launch_occupancy_stats(const uint32_t *words, size_t n_cells, int nx, int ny, int nz, int *out8, hipStream_t st);
 size_t resample_lds_bytes(int nc, int nf);
 size_t composite_lds_bytes(int n);
 // ---- zero certification (nerf_render_opts.certify_zero; kernels and protocol: sampling_kernels.hip) ------------------------------------

@@ -711,6 +711,61 @@ hipError_t launch_bands_to_frame(const float *slots, float *frame, int w, int h,
     return hipGetLastError();
 }
 
+// ---- density grids: what the occupancy words of nerf_density_grid hold --------------------------------------------------------
+// words: ceil(N / 32) words of the MLP kernel's grid mode, bit b of word w = linear cell 32 w + b, x fastest (N = nx ny nz; the bits behind
+// cell N - 1 are 0).  out[0..1] = number of set bits (one 64-bit count), out[2..4] = smallest ix, iy, iz of a set cell, out[5..7] = largest;
+// no set bit: mins = dims, maxs = -1.  ONE workgroup, no atomics, no initialised output: the input is N / 8 bytes (2 MiB for 256^3) behind an
+// MLP launch that took ~1e5 x longer, so the plain form is the right one.  A thread divides once per word and then walks the
+// word's set bits upwards, carrying (ix, iy, iz).
+__global__ __launch_bounds__(1024) void k_occupancy_stats(const uint32_t *__restrict__ words, size_t n_words, int nx, int ny, int nz, int *__restrict__ out) {
+    __shared__ unsigned long long s_cnt[16];
+    __shared__ int s_b[16][6];
+    unsigned long long cnt = 0;
+    int lo[3] = {nx, ny, nz}, hi[3] = {-1, -1, -1};
+    for (size_t w = threadIdx.x; w < n_words; w += blockDim.x) {
+        uint32_t bits = words[w];
+        if (!bits) continue;
+        cnt += (unsigned)__popc(bits);
+        const size_t row = (w * 32) / (size_t)nx;
+        int ix = (int)((w * 32) - row * (size_t)nx), iy = (int)(row % (size_t)ny), iz = (int)(row / (size_t)ny);
+        int at = 0;
+        while (bits) {
+            const int b = __ffs(bits) - 1;
+            bits &= bits - 1;
+            ix += b - at; at = b;
+            while (ix >= nx) { ix -= nx; if (++iy == ny) { iy = 0; ++iz; } }
+            lo[0] = min(lo[0], ix); lo[1] = min(lo[1], iy); lo[2] = min(lo[2], iz);
+            hi[0] = max(hi[0], ix); hi[1] = max(hi[1], iy); hi[2] = max(hi[2], iz);
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        cnt += __shfl_xor(cnt, off, 64);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { lo[k] = min(lo[k], __shfl_xor(lo[k], off, 64)); hi[k] = max(hi[k], __shfl_xor(hi[k], off, 64)); }
+    }
+    const int wave = threadIdx.x >> 6, n_waves = (blockDim.x + 63) >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        s_cnt[wave] = cnt;
+        for (int k = 0; k < 3; ++k) { s_b[wave][k] = lo[k]; s_b[wave][3 + k] = hi[k]; }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int v = 1; v < n_waves; ++v) {
+            cnt += s_cnt[v];
+            for (int k = 0; k < 3; ++k) { lo[k] = min(lo[k], s_b[v][k]); hi[k] = max(hi[k], s_b[v][3 + k]); }
+        }
+        out[0] = (int)(unsigned)(cnt & 0xffffffffull); out[1] = (int)(unsigned)(cnt >> 32);
+        for (int k = 0; k < 3; ++k) { out[2 + k] = lo[k]; out[5 + k] = hi[k]; }
+    }
+}
+
+hipError_t launch_occupancy_stats(const uint32_t *words, size_t n_cells, int nx, int ny, int nz, int *out8, hipStream_t st) {
+    if (n_cells == 0 || nx <= 0 || ny <= 0 || nz <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_occupancy_stats, dim3(1), dim3(1024), 0, st, words, (n_cells + 31) / 32, nx, ny, nz, out8);
+    return hipGetLastError();
+}
+
 // ---- launchers -----------------------------------------------------------------------------------------
 hipError_t launch_ray_dirs(const RayGenArgs &a, float *dirs, hipStream_t st) {
     if (a.n_rays <= 0) return hipSuccess;
