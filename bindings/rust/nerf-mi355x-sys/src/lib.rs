@@ -141,6 +141,19 @@ extern "C" {
     pub fn nerf_density_grid_device(ctx: *mut nerf_ctx, which: c_int, lo: *const f32, step: *const f32, dims: *const i32,
                                     d_sigma_out: *mut f32, threshold: f32, d_occ_bits: *mut u32, n_occupied: *mut u64, bounds: *mut i32,
                                     stream: *mut c_void) -> c_int;
+    /// The level set sigma = iso of a caller's lattice (host, dims[2] x dims[1] x dims[0], x fastest) as an indexed triangle mesh, marching
+    /// tetrahedra on the device.  Arrays may be null; both counts are always returned; the arrays are written only if both counts fit the
+    /// capacities (all null / 0: the size query).  Conventions: include/nerf_mi355x.h, "isosurface meshes".
+    pub fn nerf_isosurface_grid(ctx: *mut nerf_ctx, sigma: *const f32, lo: *const f32, step: *const f32, dims: *const i32, iso: f32,
+                                vertices: *mut f32, normals: *mut f32, cap_vertices: usize, triangles: *mut u32, cap_triangles: usize,
+                                n_vertices: *mut u64, n_triangles: *mut u64) -> c_int;
+    /// The same on the sigma lattice of network `which`, evaluated on the device and never sent to the host; `rgb` = vertex colours.
+    pub fn nerf_extract_mesh(ctx: *mut nerf_ctx, which: c_int, lo: *const f32, step: *const f32, dims: *const i32, iso: f32,
+                             vertices: *mut f32, normals: *mut f32, rgb: *mut f32, cap_vertices: usize, triangles: *mut u32,
+                             cap_triangles: usize, n_vertices: *mut u64, n_triangles: *mut u64) -> c_int;
+    pub fn nerf_extract_mesh_device(ctx: *mut nerf_ctx, which: c_int, lo: *const f32, step: *const f32, dims: *const i32, iso: f32,
+                                    d_vertices: *mut f32, d_normals: *mut f32, d_rgb: *mut f32, cap_vertices: usize, d_triangles: *mut u32,
+                                    cap_triangles: usize, n_vertices: *mut u64, n_triangles: *mut u64, stream: *mut c_void) -> c_int;
     pub fn nerf_render_image(ctx: *mut nerf_ctx, cam: *const nerf_camera, opts: *const nerf_render_opts,
                              rgb_out: *mut f32, stats: *mut nerf_stats) -> c_int;
     pub fn nerf_render_image_device(ctx: *mut nerf_ctx, cam: *const nerf_camera, opts: *const nerf_render_opts,
@@ -182,6 +195,9 @@ extern "C" {
     pub fn nerf_save_pfm(path: *const c_char, width: c_int, height: c_int, values: *const f32) -> c_int;
     /// PAM ("P7", RGB_ALPHA, MAXVAL 255) of height x width x 4 bytes
     pub fn nerf_save_pam(path: *const c_char, width: c_int, height: c_int, rgba: *const u8) -> c_int;
+    /// Binary little-endian PLY of an indexed triangle mesh; `normals` / `rgb` (written as uchar) may be null.  Host-only.
+    pub fn nerf_save_ply(path: *const c_char, n_vertices: usize, vertices: *const f32, normals: *const f32, rgb: *const f32,
+                         n_triangles: usize, triangles: *const u32) -> c_int;
     pub fn nerf_quantize_rgb8(rgb: *const f32, n_pixels: usize, out: *mut u8);
     pub fn nerf_quantize_rgba8(rgb: *const f32, n_pixels: usize, out: *mut u8);
     pub fn nerf_stage_ray_dirs(ctx: *mut nerf_ctx, cam: *const nerf_camera, x0: c_int, y0: c_int, w: c_int, h: c_int,

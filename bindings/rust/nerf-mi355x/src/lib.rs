@@ -69,6 +69,23 @@ pub fn save_ppm(path: &Path, width: i32, height: i32, rgb: &[f32]) -> Result<(),
     check(std::ptr::null(), unsafe { sys::nerf_save_ppm(cpath(path)?.as_ptr(), width, height, rgb.as_ptr()) })
 }
 
+/// An indexed triangle mesh (`Gpu::extract_mesh`): `vertices`, `normals`, `colours` are V x 3, `triangles` T x 3 vertex ids.
+#[derive(Debug, Clone, Default)]
+pub struct Mesh {
+    pub vertices: Vec<f32>,
+    pub normals: Option<Vec<f32>>,
+    pub colours: Option<Vec<f32>>,
+    pub triangles: Vec<u32>,
+}
+
+/// A mesh as a binary little-endian PLY (nerf_save_ply); colours are written as uchar red / green / blue.
+pub fn save_ply(path: &Path, mesh: &Mesh) -> Result<(), Error> {
+    let (nv, nt) = (mesh.vertices.len() / 3, mesh.triangles.len() / 3);
+    let np = mesh.normals.as_ref().map_or(std::ptr::null(), |v| v.as_ptr());
+    let cp = mesh.colours.as_ref().map_or(std::ptr::null(), |v| v.as_ptr());
+    check(std::ptr::null(), unsafe { sys::nerf_save_ply(cpath(path)?.as_ptr(), nv, mesh.vertices.as_ptr(), np, cp, nt, mesh.triangles.as_ptr()) })
+}
+
 /// A depth or opacity map of `Gpu::render_image_aux` as a one-channel PFM (little-endian, rows bottom-up).
 pub fn save_pfm(path: &Path, width: i32, height: i32, values: &[f32]) -> Result<(), Error> {
     assert_eq!(values.len(), (width * height) as usize, "values.len() != width * height");
@@ -136,6 +153,48 @@ impl Gpu {
             sys::nerf_density_grid(self.ctx, which, lo.as_ptr(), step.as_ptr(), dims.as_ptr(), sp, threshold.unwrap_or(0.0), bp, cp, rp)
         })?;
         Ok((sigma, occ))
+    }
+
+    /// The level set sigma = `iso` of a network on the lattice of `density_grid` (every dim >= 2, no zero step) as a welded, indexed
+    /// triangle mesh, extracted on the device by marching tetrahedra (nerf_extract_mesh; conventions in include/nerf_mi355x.h).  The
+    /// sigma lattice never reaches the host.  A size query is followed by the fill: the lattice is evaluated twice.
+    pub fn extract_mesh(&self, fine: bool, lo: [f32; 3], step: [f32; 3], dims: [i32; 3], iso: f32, normals: bool, colours: bool) -> Result<Mesh, Error> {
+        let which = if fine { sys::NERF_NET_FINE } else { sys::NERF_NET_COARSE };
+        let (mut nv, mut nt) = (0u64, 0u64);
+        let null = std::ptr::null_mut::<f32>();
+        check(self.ctx, unsafe {
+            sys::nerf_extract_mesh(self.ctx, which, lo.as_ptr(), step.as_ptr(), dims.as_ptr(), iso, null, null, null, 0, std::ptr::null_mut(), 0, &mut nv, &mut nt)
+        })?;
+        let (cap_v, cap_t) = (nv as usize, nt as usize);
+        let mut mesh = Mesh { vertices: vec![0f32; 3 * cap_v], normals: if normals { Some(vec![0f32; 3 * cap_v]) } else { None },
+                              colours: if colours { Some(vec![0f32; 3 * cap_v]) } else { None }, triangles: vec![0u32; 3 * cap_t] };
+        let np = mesh.normals.as_mut().map_or(null, |v| v.as_mut_ptr());
+        let cp = mesh.colours.as_mut().map_or(null, |v| v.as_mut_ptr());
+        check(self.ctx, unsafe {
+            sys::nerf_extract_mesh(self.ctx, which, lo.as_ptr(), step.as_ptr(), dims.as_ptr(), iso, mesh.vertices.as_mut_ptr(), np, cp, cap_v,
+                                   mesh.triangles.as_mut_ptr(), cap_t, &mut nv, &mut nt)
+        })?;
+        assert!(nv as usize == cap_v && nt as usize == cap_t, "the mesh changed between the size query and the fill");
+        Ok(mesh)
+    }
+
+    /// The same for a caller's sigma lattice (`sigma.len() == dims[0] * dims[1] * dims[2]`, x fastest): nerf_isosurface_grid; no network needed.
+    pub fn isosurface(&self, sigma: &[f32], lo: [f32; 3], step: [f32; 3], dims: [i32; 3], iso: f32, normals: bool) -> Result<Mesh, Error> {
+        assert_eq!(sigma.len(), dims.iter().map(|&d| d.max(0) as usize).product::<usize>(), "one sigma per lattice point");
+        let (mut nv, mut nt) = (0u64, 0u64);
+        let null = std::ptr::null_mut::<f32>();
+        check(self.ctx, unsafe {
+            sys::nerf_isosurface_grid(self.ctx, sigma.as_ptr(), lo.as_ptr(), step.as_ptr(), dims.as_ptr(), iso, null, null, 0, std::ptr::null_mut(), 0, &mut nv, &mut nt)
+        })?;
+        let (cap_v, cap_t) = (nv as usize, nt as usize);
+        let mut mesh = Mesh { vertices: vec![0f32; 3 * cap_v], normals: if normals { Some(vec![0f32; 3 * cap_v]) } else { None }, colours: None,
+                              triangles: vec![0u32; 3 * cap_t] };
+        let np = mesh.normals.as_mut().map_or(null, |v| v.as_mut_ptr());
+        check(self.ctx, unsafe {
+            sys::nerf_isosurface_grid(self.ctx, sigma.as_ptr(), lo.as_ptr(), step.as_ptr(), dims.as_ptr(), iso, mesh.vertices.as_mut_ptr(), np, cap_v,
+                                      mesh.triangles.as_mut_ptr(), cap_t, &mut nv, &mut nt)
+        })?;
+        Ok(mesh)
     }
 
     /// Linear RGB, pixel (i, j) at `(i * w + j) * 3` (image[i * nx + j], src/lib.rs:552-557); `opts.n_coarse` = camera.samples_per_ray.

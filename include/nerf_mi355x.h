@@ -258,6 +258,59 @@ int nerf_density_grid_device(nerf_ctx *ctx, int which, const float lo[3], const 
                              float *d_sigma_out, float threshold, uint32_t *d_occ_bits, uint64_t *n_occupied, int32_t bounds[6],
                              void *stream);
 
+/* ---- isosurface meshes: the level set sigma = iso of a density lattice as a deterministic, welded, indexed triangle mesh ----------------
+ * Marching tetrahedra on the Kuhn split of every lattice cell, on the device (nerf-rs_amd/csrc/isosurface_kernels.hip).  The split uses
+ * the same face diagonal on both sides of every cell face: the surface is watertight by construction and no case is ambiguous.  Every
+ * output position is fixed by prefix sums (no atomics): the same input gives the same bits in every run.  A host can restate the output
+ * bit for bit from the following conventions (tests/helpers/marching_tets.py does).
+ * LATTICE   the points of nerf_density_grid: p = lo + step * index, per coordinate the f32 product step * (float)i, then the f32 sum with lo,
+ *           each rounded once; sigma is dims[2] x dims[1] x dims[0] floats, x fastest (linear index A = ix + dims[0] (iy + dims[1] iz)).
+ *           Every dims[k] >= 2, every step[k] != 0; lo, step and iso finite; N = dims[0] dims[1] dims[2] at most the smaller of 2^28 and
+ *           nerf_forward_batch's largest n (every count then fits 32 bits) -- anything else is NERF_ERR_INVALID, checked before the context or
+ *           the device is needed.  step may be negative.
+ * INSIDE    sigma > iso, the occupancy predicate; a NaN is not inside.
+ * VERTICES  each lattice point A owns up to 7 edges, to A + d for d = (dx, dy, dz) in {0,1}^3 \ {0} where A + d lies on the lattice (3 axis
+ *           edges, 3 face diagonals, the body diagonal: the edges of the Kuhn tetrahedra).  An edge carries one vertex iff both end sigma
+ *           are finite and exactly one end is inside.  Vertex ids ascend with A, within A with dx + 2 dy + 4 dz.  With B = A + d:
+ *             t = (iso - sigma_A) / (sigma_B - sigma_A)      two f32 subtractions, one correctly rounded f32 division
+ *             p = p_A + t * (p_B - p_A) per coordinate       subtract, multiply, add, each rounded once
+ *           always evaluated from A to B, so that every cell sharing the edge sees the same bits.
+ * TRIANGLES cells ascend in linear index ix + (dims[0] - 1) (iy + (dims[1] - 1) iz); a cell with a non-finite corner emits nothing.
+ *           Within a cell with low corner c the six tetrahedra (c, c + e_a, c + e_a + e_b, c + (1,1,1)) follow in the axis orders
+ *           (a, b, .) = xyz, xzy, yxz, yzx, zxy, zyx.  A tetrahedron with one corner inside, or one corner outside, gives one triangle; two
+ *           corners inside give a quad, stored as two triangles.  Winding: counter-clockwise seen from the outside (sigma <= iso) IN
+ *           LATTICE INDEX SPACE -- independent of lo and step; a lattice with an odd number of negative steps is therefore wound INWARDS
+ *           in world space (flip the triangles, or mirror the lattice, if that matters).  Canonical form: a triangle starts with its
+ *           smallest vertex id; a quad's four vertices are taken in their cyclic order under that winding starting at the smallest id m
+ *           and split along the diagonal through m: (m, q1, q2), then (m, q2, q3).  Indices are uint32, three per triangle.
+ * NORMALS   per lattice point P and axis k: g_k = (sigma(P + e_k) - sigma(P - e_k)) / (x_k(P + e_k) - x_k(P - e_k)), indices clamped to the
+ *           lattice (one-sided at the borders), x_k the lattice coordinates above; at a vertex g = g_A + t * (g_B - g_A) with the arithmetic
+ *           of the position; len = sqrt((g_x^2 + g_y^2) + g_z^2), every operation rounded once, sqrt and division correctly rounded;
+ *           n = (-g) / len, the unit normal towards lower density; n = (0, 0, 0) where len is 0 or not finite.
+ * COLOURS   (network entry points) the rgb nerf_forward_batch of the same network returns at the vertex positions with dirs = -n (the
+ *           surface seen head-on; where n is zero the zero vector, negated, is passed); f32, n_vertices x 3.
+ * OUTPUT    vertices, normals, rgb: n_vertices x 3 floats; triangles: n_triangles x 3 uint32; each may be NULL.  n_vertices and
+ *           n_triangles are required and always returned.  The arrays are written only when BOTH counts fit their capacities
+ *           (cap_vertices vertices, cap_triangles triangles); otherwise nothing is written and the call still returns NERF_OK: all-NULL
+ *           arrays with zero capacities is the size query (a query followed by a fill runs everything twice, the network's lattice
+ *           evaluation included).
+ * Workspace: 16 bytes per lattice point in the context (sigma, one classification word, two prefix sums: 268 MB for 256^3), grown on
+ * demand -- a warm call allocates nothing; the sigma lattice of nerf_extract_mesh lives there and never reaches the host. */
+/* the caller's sigma lattice (host); needs a context, not a network */
+int nerf_isosurface_grid(nerf_ctx *ctx, const float *sigma, const float lo[3], const float step[3], const int32_t dims[3], float iso,
+                         float *vertices, float *normals, size_t cap_vertices, uint32_t *triangles, size_t cap_triangles,
+                         uint64_t *n_vertices, uint64_t *n_triangles);
+/* sigma of network `which` evaluated in grid mode (nerf_density_grid's launch) into the workspace, then the same kernels (+ colours).
+ * Host pointers, synchronous.  NERF_ERR_STATE: network not loaded. */
+int nerf_extract_mesh(nerf_ctx *ctx, int which, const float lo[3], const float step[3], const int32_t dims[3], float iso,
+                      float *vertices, float *normals, float *rgb, size_t cap_vertices, uint32_t *triangles, size_t cap_triangles,
+                      uint64_t *n_vertices, uint64_t *n_triangles);
+/* device output pointers, on `stream`; n_vertices / n_triangles are HOST pointers: the call synchronises the stream to read the counts,
+ * the emitting kernels that follow are asynchronous */
+int nerf_extract_mesh_device(nerf_ctx *ctx, int which, const float lo[3], const float step[3], const int32_t dims[3], float iso,
+                             float *d_vertices, float *d_normals, float *d_rgb, size_t cap_vertices, uint32_t *d_triangles,
+                             size_t cap_triangles, uint64_t *n_vertices, uint64_t *n_triangles, void *stream);
+
 /* ---- S3: render_image (src/lib.rs:474-565) ----------------------------------------------------------------- */
 /* rgb_out: crop_h x crop_w x 3 (or ny x nx x 3) linear RGB f32, row-major, index (i*w + j)*3 as image[i*nx+j]
  * (src/lib.rs:552-557).  Unlike the reference (src/lib.rs:491-501) nx, ny need not be multiples of 8. */
@@ -378,6 +431,12 @@ int nerf_save_pfm(const char *path, int width, int height, const float *values);
  * nerf_render_image_rgba8 writes them.  Host-only. */
 int nerf_save_pam(const char *path, int width, int height, const uint8_t *rgba);
 
+/* Binary little-endian PLY of an indexed triangle mesh: per vertex float x y z [float nx ny nz] [uchar red green blue, quantised like
+ * nerf_quantize_rgb8], per face "property list uchar uint vertex_indices" with three indices.  normals / rgb may be NULL; zero vertices or
+ * triangles are allowed.  NERF_ERR_INVALID: a missing array, or an index >= n_vertices.  Host-only. */
+int nerf_save_ply(const char *path, size_t n_vertices, const float *vertices, const float *normals, const float *rgb, size_t n_triangles,
+                  const uint32_t *triangles);
+
 /* ---- stage entry points (device execution, host buffers): the individual functions of render_block, exposed so
  * that a host that owns ray setup can call them and so that each stage has its own parity test ------------- */
 /* Camera::get_ray_dir (src/lib.rs:213-231) for the rectangle [y0,y0+h) x [x0,x0+w); normalize != 0 applies
@@ -416,7 +475,7 @@ const char *nerf_build_variant(void);
  * nerf_render_opts.band_*, nerf_band_rows, nerf_debug_certify_policy; additive: nerf_render_image_aux, nerf_render_image_aux_device,
  * nerf_render_image_multi_aux, nerf_save_pfm, nerf_render_image_rgba8, nerf_render_image_rgba8_device, nerf_render_image_multi_rgba8,
  * nerf_stage_integrate_rgba8, nerf_save_pam, NERF_ALPHA_*, nerf_density_batch, nerf_density_batch_device, nerf_density_grid,
- * nerf_density_grid_device). */
+ * nerf_density_grid_device, nerf_isosurface_grid, nerf_extract_mesh, nerf_extract_mesh_device, nerf_save_ply). */
 int nerf_abi_version(void);
 /* sizeof(nerf_camera), sizeof(nerf_render_opts), sizeof(nerf_stats) as this library was built: lets a binding written in
  * another language (the Rust `-sys` crate, ctypes) check its struct mirrors at start-up. */

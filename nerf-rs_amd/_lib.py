@@ -79,6 +79,13 @@ PROTOTYPES = {
     "nerf_density_grid": (C.c_int, [C.c_void_p, C.c_int, f32p, f32p, i32p, f32p, C.c_float, u32p, C.POINTER(C.c_uint64), i32p]),
     "nerf_density_grid_device": (C.c_int, [C.c_void_p, C.c_int, f32p, f32p, i32p, C.c_void_p, C.c_float, C.c_void_p,
                                            C.POINTER(C.c_uint64), i32p, C.c_void_p]),
+    "nerf_isosurface_grid": (C.c_int, [C.c_void_p, f32p, f32p, f32p, i32p, C.c_float, f32p, f32p, C.c_size_t, u32p, C.c_size_t,
+                                       C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "nerf_extract_mesh": (C.c_int, [C.c_void_p, C.c_int, f32p, f32p, i32p, C.c_float, f32p, f32p, f32p, C.c_size_t, u32p, C.c_size_t,
+                                    C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "nerf_extract_mesh_device": (C.c_int, [C.c_void_p, C.c_int, f32p, f32p, i32p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                           C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]),
+    "nerf_save_ply": (C.c_int, [C.c_char_p, C.c_size_t, f32p, f32p, f32p, C.c_size_t, u32p]),
     "nerf_render_image": (C.c_int, [C.c_void_p, C.POINTER(CCamera), C.POINTER(COpts), f32p, C.POINTER(CStats)]),
     "nerf_render_image_device": (C.c_int, [C.c_void_p, C.POINTER(CCamera), C.POINTER(COpts), C.c_void_p, C.c_void_p,
                                            C.POINTER(CStats)]),

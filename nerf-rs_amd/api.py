@@ -8,6 +8,7 @@ Reference names kept (elisabeth96/nerf-rs):
   save_ppm                src/lib.rs:567-580
 Errors the reference raises as panics surface as NerfError with the same message text.
 """
+import collections
 import ctypes as C
 import json
 
@@ -235,6 +236,70 @@ class Network:
                                             d_bits, C.byref(cnt) if want_stats else None,
                                             bounds.ctypes.data_as(i32p) if want_stats else None, stream), R.handle)
         return (int(cnt.value), tuple(int(v) for v in bounds)) if want_stats else None
+
+
+    def extract_mesh(self, lo, step, dims, iso, normals=False, colours=False, capacity=None):
+        """The level set sigma = iso of this network on the lattice lo + step * index (density_grid's lattice, every dims >= 2, no zero
+        step), extracted on the device by marching tetrahedra (nerf_extract_mesh; conventions: include/nerf_mi355x.h) -> Mesh(vertices
+        (V, 3) f32, normals (V, 3) f32 or None, colours (V, 3) f32 or None, triangles (T, 3) uint32).  The sigma lattice never reaches
+        the host.  normals: unit vectors towards lower density; colours: the network's rgb at the vertices seen head-on (dirs = -normal).
+
+        capacity=None asks the library for the counts first and then calls it again with arrays of that size: A QUERY FOLLOWED BY A FILL
+        EVALUATES THE LATTICE TWICE (the network launch included).  capacity=(max_vertices, max_triangles) is one call; a mesh that
+        does not fit raises NerfError with the counts in the message (nothing was written)."""
+        lo_c, step_c, dims_c, _ = _grid_args(lo, step, dims)
+        R = self.renderer
+        call = lambda v, n, c, cv, t, ct, nv, nt: R._L.nerf_extract_mesh(R.handle, self.which, _p(lo_c), _p(step_c), dims_c.ctypes.data_as(i32p), float(iso),
+                                                                         v, n, c, cv, t, ct, nv, nt)
+        return _mesh_call(call, R.handle, bool(normals), bool(colours), capacity)
+
+    def extract_mesh_device(self, lo, step, dims, iso, d_vertices, d_normals, d_colours, cap_vertices, d_triangles, cap_triangles, stream=0):
+        """Raw device pointers (ints; each may be None) -> (n_vertices, n_triangles).  Synchronises `stream` to read the counts; the arrays are
+        written (asynchronously) only if both counts fit the capacities."""
+        lo_c, step_c, dims_c, _ = _grid_args(lo, step, dims)
+        nv, nt = C.c_uint64(0), C.c_uint64(0)
+        R = self.renderer
+        check(R._L.nerf_extract_mesh_device(R.handle, self.which, _p(lo_c), _p(step_c), dims_c.ctypes.data_as(i32p), float(iso), d_vertices, d_normals,
+                                            d_colours, int(cap_vertices), d_triangles, int(cap_triangles), C.byref(nv), C.byref(nt), stream), R.handle)
+        return int(nv.value), int(nt.value)
+
+
+Mesh = collections.namedtuple("Mesh", "vertices normals colours triangles")
+
+
+def _mesh_call(call, handle, normals, colours, capacity):
+    """Size query + fill (capacity None) or one call with the given capacity, around `call(vertices, normals, colours, cap_v, triangles, cap_t,
+    n_vertices, n_triangles)`."""
+    nv, nt = C.c_uint64(0), C.c_uint64(0)
+    if capacity is None:
+        check(call(None, None, None, 0, None, 0, C.byref(nv), C.byref(nt)), handle)
+        cap_v, cap_t = int(nv.value), int(nt.value)
+    else:
+        cap_v, cap_t = (int(v) for v in capacity)
+        if cap_v < 0 or cap_t < 0:
+            raise NerfError(-1, "capacity must be (max_vertices, max_triangles), both >= 0")
+    v = np.empty((cap_v, 3), np.float32)
+    n = np.empty((cap_v, 3), np.float32) if normals else None
+    c = np.empty((cap_v, 3), np.float32) if colours else None
+    t = np.empty((cap_t, 3), np.uint32)
+    check(call(_p(v), None if n is None else _p(n), None if c is None else _p(c), cap_v, t.ctypes.data_as(u32p), cap_t, C.byref(nv), C.byref(nt)), handle)
+    n_v, n_t = int(nv.value), int(nt.value)
+    if n_v > cap_v or n_t > cap_t:
+        raise NerfError(-1, f"capacity too small: the mesh has {n_v} vertices and {n_t} triangles")
+    return Mesh(v[:n_v], None if n is None else n[:n_v], None if c is None else c[:n_v], t[:n_t])
+
+
+def isosurface(renderer, sigma, lo, step, iso, normals=False, capacity=None):
+    """The level set sigma = iso of a caller-supplied lattice sigma[iz, iy, ix] (shape (nz, ny, nx), x fastest, at the points lo + step * index)
+    by marching tetrahedra on the device (nerf_isosurface_grid; needs a Renderer, no network) -> Mesh(vertices, normals or None, None,
+    triangles).  capacity as in Network.extract_mesh (None: a size query, then the fill -- the lattice is uploaded and classified twice)."""
+    sig = _f32(sigma)
+    if sig.ndim != 3:
+        raise NerfError(-1, "sigma must be a (nz, ny, nx) array")
+    lo_c, step_c, dims_c, _ = _grid_args(lo, step, sig.shape[::-1])
+    call = lambda v, n, c, cv, t, ct, nv, nt: renderer._L.nerf_isosurface_grid(renderer.handle, _p(sig), _p(lo_c), _p(step_c), dims_c.ctypes.data_as(i32p),
+                                                                               float(iso), v, n, cv, t, ct, nv, nt)
+    return _mesh_call(call, renderer.handle, bool(normals), False, capacity)
 
 
 def _grid_args(lo, step, dims):
@@ -531,6 +596,19 @@ def save_pam(path, width, height, rgba):
     if a.size != width * height * 4:
         raise NerfError(-1, "rgba.len() != width * height * 4")
     check(_lib.load_library().nerf_save_pam(str(path).encode(), width, height, a.ctypes.data_as(u8p)))
+
+
+def save_ply(path, vertices, triangles, normals=None, colours=None):
+    """An indexed triangle mesh as a binary little-endian PLY (nerf_save_ply): vertices (V, 3) f32, triangles (T, 3) uint32, optional normals
+    (V, 3) f32 and colours (V, 3) f32 (written as uchar red / green / blue through quantize_rgb8)."""
+    v = _f32(vertices).reshape(-1, 3)
+    t = np.ascontiguousarray(triangles, dtype=np.uint32).reshape(-1, 3)
+    n = None if normals is None else _f32(normals).reshape(-1, 3)
+    c = None if colours is None else _f32(colours).reshape(-1, 3)
+    if (n is not None and n.shape != v.shape) or (c is not None and c.shape != v.shape):
+        raise NerfError(-1, "normals and colours must have one row per vertex")
+    check(_lib.load_library().nerf_save_ply(str(path).encode(), v.shape[0], _p(v), None if n is None else _p(n), None if c is None else _p(c),
+                                            t.shape[0], t.ctypes.data_as(u32p)))
 
 
 def load_tf_samples(path):

@@ -3,7 +3,8 @@
 // touches the device).  tests/test_host_asan.py feeds it valid, truncated, oversized and malformed weight directories, blobs and
 // camera JSON files: every call must come back with a status code and a message -- a sanitizer report aborts with a non-zero exit.
 //   host_asan_driver check_dir <dir> | pack_dir <dir> <blob> | check_blob <blob> | camera_json <json> <w> <h> |
-//                    debug_pack <dir> | debug_fold <dir> | quantize | save_ppm <path> <w> <h> | save_pfm <path> <w> <h> | save_pam <path> <w> <h> | split
+//                    debug_pack <dir> | debug_fold <dir> | quantize | save_ppm <path> <w> <h> | save_pfm <path> <w> <h> | save_pam <path> <w> <h> | split |
+//                    ply <path> <n_vertices> <n_triangles> <normals 0|1> <colours 0|1>
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -95,6 +96,40 @@ int main(int argc, char **argv) {
             if (n != hdr.size() + px.size() || memcmp(got.data(), hdr.data(), hdr.size()) || memcmp(got.data() + hdr.size(), px.data(), px.size())) rc = 99;
         }
         return report("save_pam", rc);
+    }
+    if (cmd == "ply" && argc == 7) { // the arrays are exactly as long as the counts say: an over-read is a report (zero counts included)
+        const long long nv = atoll(argv[3]), nt = atoll(argv[4]);
+        const bool with_n = atoi(argv[5]) != 0, with_c = atoi(argv[6]) != 0;
+        if (nv < 0 || nt < 0 || nv > 1000000 || nt > 1000000) return 2;
+        std::vector<float> v(3 * (size_t)nv), n(with_n ? (nv ? 3 * (size_t)nv : 1) : 0), c(with_c ? (nv ? 3 * (size_t)nv : 1) : 0); // non-NULL also for no vertices
+        std::vector<uint32_t> t(3 * (size_t)nt);
+        for (size_t i = 0; i < v.size(); ++i) v[i] = (float)(i % 101) * 0.03125f - 1.5f;
+        for (size_t i = 0; i < n.size(); ++i) n[i] = (float)(i % 7) - 3.0f;
+        for (size_t i = 0; i < c.size(); ++i) c[i] = i % 13 == 0 ? NAN : (float)(i % 19) / 16.f - 0.1f; // below 0, above 1 and NaN go through the quantiser
+        for (size_t i = 0; i < t.size(); ++i) t[i] = nv ? (uint32_t)((i * 7u + 3u) % (size_t)nv) : 0u;
+        int rc = nerf_save_ply(argv[2], (size_t)nv, nv ? v.data() : nullptr, with_n ? n.data() : nullptr, with_c ? c.data() : nullptr, (size_t)nt,
+                               nt ? t.data() : nullptr);
+        if (!rc) { // read it back: header + records, nothing more
+            std::string hdr = "ply\nformat binary_little_endian 1.0\nelement vertex " + std::to_string(nv) + "\nproperty float x\nproperty float y\nproperty float z\n";
+            if (with_n) hdr += "property float nx\nproperty float ny\nproperty float nz\n";
+            if (with_c) hdr += "property uchar red\nproperty uchar green\nproperty uchar blue\n";
+            hdr += "element face " + std::to_string(nt) + "\nproperty list uchar uint vertex_indices\nend_header\n";
+            const size_t vrec = 12 + (with_n ? 12 : 0) + (with_c ? 3 : 0), body = (size_t)nv * vrec + (size_t)nt * 13;
+            std::vector<char> got(hdr.size() + body + 1);
+            FILE *f = fopen(argv[2], "rb");
+            const size_t m = f ? fread(got.data(), 1, got.size(), f) : 0;
+            if (f) fclose(f);
+            if (m != hdr.size() + body || memcmp(got.data(), hdr.data(), hdr.size())) rc = 99;
+            if (!rc && nv && memcmp(got.data() + hdr.size(), v.data(), 12)) rc = 98;
+            if (!rc && nt && (got[hdr.size() + (size_t)nv * vrec] != 3 || memcmp(got.data() + hdr.size() + (size_t)nv * vrec + 1, t.data(), 12))) rc = 97;
+        }
+        if (!rc && nv && nt) { // an index beyond the vertices, a missing array: refused, nothing crashes
+            t[t.size() - 1] = (uint32_t)nv;
+            if (nerf_save_ply(argv[2], (size_t)nv, v.data(), nullptr, nullptr, (size_t)nt, t.data()) != NERF_ERR_INVALID) rc = 96;
+            if (nerf_save_ply(argv[2], (size_t)nv, nullptr, nullptr, nullptr, 0, nullptr) != NERF_ERR_INVALID) rc = 95;
+            if (nerf_save_ply(nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr) != NERF_ERR_INVALID) rc = 94;
+        }
+        return report("ply", rc);
     }
     if (cmd == "split") {
         const float v[] = {0.f, -0.f, 1.f, -3.14159274f, 65504.f, 7e4f, 1e-8f, 6e-8f, 1e30f, -1e-30f, NAN, INFINITY};

@@ -540,6 +540,44 @@ int save_pam(const std::string &path, int width, int height, const uint8_t *rgba
     return NERF_OK;
 }
 
+// Binary little-endian PLY: per vertex x y z [nx ny nz] [red green blue], per face the list length 3 (uchar) and three uint indices.  The records are
+// assembled in a bounded buffer (the host is little-endian, like every raw dump of this library).
+int save_ply(const std::string &path, size_t n_vertices, const float *vertices, const float *normals, const float *rgb, size_t n_triangles,
+             const uint32_t *triangles, std::string &err) {
+    if ((n_vertices && !vertices) || (n_triangles && !triangles)) { err = "save_ply: NULL array"; return NERF_ERR_INVALID; }
+    if (n_vertices > 0xffffffffull || n_triangles > 0xffffffffull) { err = "save_ply: more than 2^32 - 1 elements"; return NERF_ERR_INVALID; }
+    for (size_t i = 0; i < 3 * n_triangles; ++i)
+        if (triangles[i] >= n_vertices) { err = "save_ply: a triangle names a vertex beyond n_vertices"; return NERF_ERR_INVALID; }
+    FILE *f = fopen(path.c_str(), "wb");
+    if (!f) { err = "save_ply: cannot create " + path; return NERF_ERR_IO; }
+    fprintf(f, "ply\nformat binary_little_endian 1.0\nelement vertex %zu\nproperty float x\nproperty float y\nproperty float z\n", n_vertices);
+    if (normals) fprintf(f, "property float nx\nproperty float ny\nproperty float nz\n");
+    if (rgb) fprintf(f, "property uchar red\nproperty uchar green\nproperty uchar blue\n");
+    fprintf(f, "element face %zu\nproperty list uchar uint vertex_indices\nend_header\n", n_triangles);
+    const size_t vrec = 12 + (normals ? 12 : 0) + (rgb ? 3 : 0), trec = 13, chunk = 4096;
+    std::vector<uint8_t> buf(chunk * std::max(vrec, trec));
+    bool ok = true;
+    for (size_t at = 0; at < n_vertices && ok; at += chunk) {
+        const size_t m = std::min(chunk, n_vertices - at);
+        uint8_t *p = buf.data();
+        for (size_t i = at; i < at + m; ++i) {
+            memcpy(p, vertices + 3 * i, 12); p += 12;
+            if (normals) { memcpy(p, normals + 3 * i, 12); p += 12; }
+            if (rgb) { quantize_rgb8(rgb + 3 * i, 1, p); p += 3; }
+        }
+        ok = fwrite(buf.data(), 1, m * vrec, f) == m * vrec;
+    }
+    for (size_t at = 0; at < n_triangles && ok; at += chunk) {
+        const size_t m = std::min(chunk, n_triangles - at);
+        uint8_t *p = buf.data();
+        for (size_t i = at; i < at + m; ++i) { *p++ = 3; memcpy(p, triangles + 3 * i, 12); p += 12; }
+        ok = fwrite(buf.data(), 1, m * trec, f) == m * trec;
+    }
+    if (fclose(f) != 0) ok = false;
+    if (!ok) { err = "save_ply: short write " + path; return NERF_ERR_IO; }
+    return NERF_OK;
+}
+
 int certify_policy(float margin, uint64_t audited, uint64_t violations, float headroom, float max_error, float *new_margin) {
     if (new_margin) *new_margin = margin;
     if (!audited) return 0; // nothing was certified in front of a predicted cut: nothing to judge

@@ -68,6 +68,9 @@ int save_ppm(const std::string &path, int width, int height, const float *rgb, s
 int save_pfm(const std::string &path, int width, int height, const float *values, std::string &err);
 // PAM (P7, RGB_ALPHA, MAXVAL 255) of height x width x 4 bytes
 int save_pam(const std::string &path, int width, int height, const uint8_t *rgba, std::string &err);
+// binary little-endian PLY of an indexed triangle mesh; normals / rgb (written as uchar through quantize_rgb8) may be NULL
+int save_ply(const std::string &path, size_t n_vertices, const float *vertices, const float *normals, const float *rgb, size_t n_triangles,
+             const uint32_t *triangles, std::string &err);
 
 // certify_zero's audit policy (nerf_api.cpp render_device; exposed host-only as nerf_debug_certify_policy so that it is tested without a
 // GPU).  Given what the audit of one network found in one frame, decide whether the frame stands and, if not, the widened margin:

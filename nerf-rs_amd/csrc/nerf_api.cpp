@@ -20,6 +20,7 @@
 
 #include "../../include/nerf_mi355x.h"
 #include "host_util.h"
+#include "isosurface_kernels.h"
 #include "mlp_kernel.h"
 #include "mlp_layout.h"
 #include "sampling_kernels.h"
@@ -1064,6 +1065,7 @@ void nerf_destroy(nerf_ctx *c) {
     float *ptrs[] = {c->d_dirs, c->d_tc, c->d_sc, c->d_rgbc, c->d_tf, c->d_sf, c->d_rgbf, c->d_rayfb, c->d_rayaux, c->d_out, c->d_pack};
     for (float *p : ptrs) if (p) (void)hipFree(p);
     if (c->d_scratch) (void)hipFree(c->d_scratch);
+    if (c->d_mesh) (void)hipFree(c->d_mesh);
     if (c->d_clock) (void)hipFree(c->d_clock);
     if (c->d_skip) (void)hipFree(c->d_skip);
     if (c->d_nonfinite) (void)hipFree(c->d_nonfinite);
@@ -1325,6 +1327,119 @@ int nerf_density_grid(nerf_ctx *c, int which, const float lo[3], const float ste
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (stats) density_grid_stats_out(h, n_occupied, bounds);
     return NERF_OK;
+} NERF_CATCH(c)
+
+// ---- isosurface meshes (isosurface_kernels.hip): marching tetrahedra on a sigma lattice -------------------------------------------------
+// everything the mesh entry points can refuse without a device, in the order of density_grid_check; *n_points = dims[0] dims[1] dims[2]
+static int mesh_check(nerf_ctx *c, bool from_network, int which, const void *sigma, const float *lo, const float *step, const int32_t *dims, float iso,
+                      const uint64_t *n_vertices, const uint64_t *n_triangles, size_t *n_points) {
+    if (from_network && which != NERF_NET_COARSE && which != NERF_NET_FINE) return fail(c, NERF_ERR_INVALID, "which must be NERF_NET_COARSE or NERF_NET_FINE");
+    if (!lo || !step || !dims) return fail(c, NERF_ERR_INVALID, "lo, step and dims must not be NULL");
+    if (!from_network && !sigma) return fail(c, NERF_ERR_INVALID, "sigma must not be NULL");
+    if (!n_vertices || !n_triangles) return fail(c, NERF_ERR_INVALID, "n_vertices and n_triangles are required");
+    for (int k = 0; k < 3; ++k) {
+        if (dims[k] < 2) return fail(c, NERF_ERR_INVALID, "dims must be at least 2 (a lattice of cells)");
+        if (!std::isfinite(lo[k]) || !std::isfinite(step[k])) return fail(c, NERF_ERR_INVALID, "lo, step and iso must be finite");
+        if (step[k] == 0.0f) return fail(c, NERF_ERR_INVALID, "step must not be 0");
+    }
+    if (!std::isfinite(iso)) return fail(c, NERF_ERR_INVALID, "lo, step and iso must be finite");
+    // every count (at most 7 vertices and 12 triangles per point) fits 32 bits, and the lattice fits one launch of the grid kernel
+    const size_t limit = std::min((size_t)1 << 28, c ? max_batch_points(c->n_cus) : max_batch_points(0));
+    const unsigned long long plane = (unsigned long long)dims[0] * (unsigned long long)dims[1];
+    if (plane > limit || plane * (unsigned long long)dims[2] > limit)
+        return fail(c, NERF_ERR_INVALID, "lattice too large: dims[0] * dims[1] * dims[2] must be at most 2^28 (and nerf_forward_batch's largest n)");
+    *n_points = (size_t)(plane * (unsigned long long)dims[2]);
+    if (!c) return fail(nullptr, NERF_ERR_INVALID, "ctx is NULL");
+    if (from_network && !c->net[which].loaded) return fail(c, NERF_ERR_STATE, "network not loaded");
+    return NERF_OK;
+}
+
+static MeshLattice mesh_lattice(const float *lo, const float *step, const int32_t *dims, float iso) {
+    MeshLattice g;
+    g.nx = dims[0]; g.ny = dims[1]; g.nz = dims[2];
+    for (int k = 0; k < 3; ++k) { g.lo[k] = lo[k]; g.step[k] = step[k]; }
+    g.iso = iso;
+    return g;
+}
+
+struct MeshOut { // the caller's arrays (all host or all device pointers), each optional
+    float *vertices, *normals, *rgb;
+    uint32_t *triangles;
+    size_t cap_vertices, cap_triangles;
+};
+
+// sigma lies in the workspace: count, report both counts, and -- if an array is asked for and both counts fit -- emit.  host_out: the arrays are
+// host memory (staged in the context's scratch and copied back; synchronises).  The colours are nerf_forward_batch of network colour_net at the
+// vertices with dirs = -normal, run on the SoA copy the vertex kernel writes.
+static int mesh_extract(nerf_ctx *c, int colour_net, const MeshLattice &g, const MeshWorkspace &w, const MeshOut &o, bool host_out, uint64_t *n_vertices,
+                        uint64_t *n_triangles, hipStream_t st) {
+    HIP_TRY(c, launch_mesh_count(g, w, st));
+    uint32_t totals[2] = {0, 0};
+    HIP_TRY(c, hipMemcpyAsync(totals, w.totals, sizeof totals, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    const size_t nv = totals[0], nt = totals[1];
+    *n_vertices = nv; *n_triangles = nt;
+    if (!(o.vertices || o.normals || o.rgb || o.triangles) || nv > o.cap_vertices || nt > o.cap_triangles || nv == 0) return NERF_OK;
+    // staging in the scratch, in 256-byte slots: what the caller cannot receive directly, and the inputs / sigma output of the colour launch
+    size_t words = 0;
+    auto slot = [&](bool wanted, size_t n) { const size_t at = words; if (wanted) words += (n + 63) / 64 * 64; return at; };
+    const size_t v_at = slot(host_out && o.vertices, 3 * nv), n_at = slot(host_out && o.normals, 3 * nv), c_at = slot(host_out && o.rgb, 3 * nv),
+                 t_at = slot(host_out && o.triangles, 3 * nt), soa_at = slot(o.rgb, 3 * nv), dir_at = slot(o.rgb, 3 * nv), sig_at = slot(o.rgb, nv);
+    int rc;
+    if (words && (rc = ensure_bytes(c, &c->d_scratch, &c->scratch_bytes, words * sizeof(float)))) return rc;
+    float *s = (float *)c->d_scratch;
+    float *d_v = !o.vertices ? nullptr : host_out ? s + v_at : o.vertices, *d_n = !o.normals ? nullptr : host_out ? s + n_at : o.normals;
+    float *d_c = !o.rgb ? nullptr : host_out ? s + c_at : o.rgb;
+    uint32_t *d_t = !o.triangles ? nullptr : host_out ? (uint32_t *)(s + t_at) : o.triangles;
+    HIP_TRY(c, launch_mesh_emit(g, w, (uint32_t)nv, d_v, d_n, o.rgb ? s + soa_at : nullptr, o.rgb ? s + dir_at : nullptr, (uint32_t)nt, d_t, st));
+    if (o.rgb && (rc = forward_device(c, colour_net, NERF_MLP_F32, s + soa_at, s + dir_at, nv, d_c, s + sig_at, st))) return rc;
+    if (host_out) {
+        if (o.vertices) HIP_TRY(c, hipMemcpyAsync(o.vertices, d_v, 3 * nv * sizeof(float), hipMemcpyDeviceToHost, st));
+        if (o.normals) HIP_TRY(c, hipMemcpyAsync(o.normals, d_n, 3 * nv * sizeof(float), hipMemcpyDeviceToHost, st));
+        if (o.rgb) HIP_TRY(c, hipMemcpyAsync(o.rgb, d_c, 3 * nv * sizeof(float), hipMemcpyDeviceToHost, st));
+        if (o.triangles && nt) HIP_TRY(c, hipMemcpyAsync(o.triangles, d_t, 3 * nt * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipStreamSynchronize(st));
+    }
+    return NERF_OK;
+}
+
+int nerf_isosurface_grid(nerf_ctx *c, const float *sigma, const float lo[3], const float step[3], const int32_t dims[3], float iso, float *vertices,
+                         float *normals, size_t cap_vertices, uint32_t *triangles, size_t cap_triangles, uint64_t *n_vertices, uint64_t *n_triangles) try {
+    size_t n = 0;
+    int rc;
+    if ((rc = mesh_check(c, false, 0, sigma, lo, step, dims, iso, n_vertices, n_triangles, &n))) return rc;
+    DeviceGuard dg(c->device);
+    if ((rc = ensure_bytes(c, &c->d_mesh, &c->mesh_bytes, mesh_workspace_bytes(n)))) return rc;
+    const MeshWorkspace w = mesh_workspace_carve(c->d_mesh, n);
+    HIP_TRY(c, hipMemcpyAsync(w.sigma, sigma, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    const MeshOut o{vertices, normals, nullptr, triangles, cap_vertices, cap_triangles};
+    return mesh_extract(c, -1, mesh_lattice(lo, step, dims, iso), w, o, true, n_vertices, n_triangles, c->stream);
+} NERF_CATCH(c)
+
+// sigma of network `which` in grid mode into the workspace, then the kernels of nerf_isosurface_grid
+static int extract_mesh(nerf_ctx *c, int which, const float *lo, const float *step, const int32_t *dims, float iso, const MeshOut &o, bool host_out,
+                        uint64_t *n_vertices, uint64_t *n_triangles, hipStream_t st) {
+    size_t n = 0;
+    int rc;
+    if ((rc = mesh_check(c, true, which, nullptr, lo, step, dims, iso, n_vertices, n_triangles, &n))) return rc;
+    DeviceGuard dg(c->device);
+    if ((rc = ensure_bytes(c, &c->d_mesh, &c->mesh_bytes, mesh_workspace_bytes(n)))) return rc;
+    const MeshWorkspace w = mesh_workspace_carve(c->d_mesh, n);
+    if ((rc = density_grid_launch(c, which, lo, step, dims, n, w.sigma, 0.0f, nullptr, nullptr, st))) return rc;
+    return mesh_extract(c, which, mesh_lattice(lo, step, dims, iso), w, o, host_out, n_vertices, n_triangles, st);
+}
+
+int nerf_extract_mesh(nerf_ctx *c, int which, const float lo[3], const float step[3], const int32_t dims[3], float iso, float *vertices, float *normals,
+                      float *rgb, size_t cap_vertices, uint32_t *triangles, size_t cap_triangles, uint64_t *n_vertices, uint64_t *n_triangles) try {
+    const MeshOut o{vertices, normals, rgb, triangles, cap_vertices, cap_triangles};
+    return extract_mesh(c, which, lo, step, dims, iso, o, true, n_vertices, n_triangles, c ? c->stream : nullptr);
+} NERF_CATCH(c)
+
+int nerf_extract_mesh_device(nerf_ctx *c, int which, const float lo[3], const float step[3], const int32_t dims[3], float iso, float *d_vertices,
+                             float *d_normals, float *d_rgb, size_t cap_vertices, uint32_t *d_triangles, size_t cap_triangles, uint64_t *n_vertices,
+                             uint64_t *n_triangles, void *stream) try {
+    const MeshOut o{d_vertices, d_normals, d_rgb, d_triangles, cap_vertices, cap_triangles};
+    return extract_mesh(c, which, lo, step, dims, iso, o, false, n_vertices, n_triangles, (hipStream_t)stream);
 } NERF_CATCH(c)
 
 int nerf_render_image_aux_device(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *opts, float *d_rgb_out,

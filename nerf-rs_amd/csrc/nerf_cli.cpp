@@ -8,6 +8,8 @@
 // --rgba adds the display-ready frame (nerf_render_image_rgba8: packed on the device, over --background, with --alpha) as a PAM file.
 // --density-grid writes the density field on a lattice (nerf_density_grid): raw little-endian f32, x fastest, and / or the occupancy words;
 // with no image output asked for beside it (--out, --depth, --opacity, --rgba) the render is skipped.
+// --mesh writes the level set sigma = --mesh-iso of the same lattice (--density-grid / --grid-lo / --grid-step / --grid-net) as a binary PLY with
+// vertex normals (nerf_extract_mesh: marching tetrahedra on the device, the lattice never reaches the host), --mesh-colour adds vertex colours.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -25,15 +27,18 @@ static void usage(const char *argv0) {
             "          [--depth FILE.pfm] [--opacity FILE.pfm]\n"
             "          [--rgba FILE.pam [--background R,G,B] [--alpha opaque|premultiplied|straight]]\n"
             "          [--density-grid NX,NY,NZ --grid-lo X,Y,Z --grid-step SX,SY,SZ [--grid-net coarse|fine] [--grid-threshold T]\n"
-            "           [--grid-out FILE.raw] [--grid-occupancy FILE.bits]]   (at least one of the two files; no image flag: no render)\n"
-            "defaults: --scene lego_rust --width 256 --height 256 --coarse 64 --fine 128 --out output.ppm\n",
+            "           [--grid-out FILE.raw] [--grid-occupancy FILE.bits] [--mesh FILE.ply [--mesh-iso V] [--mesh-colour]]]\n"
+            "           (at least one of the three files; no image flag: no render)\n"
+            "defaults: --scene lego_rust --width 256 --height 256 --coarse 64 --fine 128 --out output.ppm --mesh-iso 10\n",
             argv0);
 }
 
 int main(int argc, char **argv) {
     std::string scene = getenv("NERF_SCENE_DIR") ? getenv("NERF_SCENE_DIR") : "lego_rust";
     std::string out = "output.ppm", depth_path, opacity_path, rgba_path;
-    std::string grid_out, grid_bits_path;
+    std::string grid_out, grid_bits_path, mesh_path;
+    float mesh_iso = 10.0f;
+    bool mesh_colour = false, have_mesh_opt = false;
     int32_t grid_dims[3] = {0, 0, 0};
     float grid_lo[3] = {0.f, 0.f, 0.f}, grid_step[3] = {0.f, 0.f, 0.f}, grid_threshold = 0.0f;
     int grid_net = NERF_NET_FINE;
@@ -85,6 +90,9 @@ int main(int argc, char **argv) {
         else if (a == "--grid-threshold") grid_threshold = strtof(next(), nullptr);
         else if (a == "--grid-out") grid_out = next();
         else if (a == "--grid-occupancy") grid_bits_path = next();
+        else if (a == "--mesh") mesh_path = next();
+        else if (a == "--mesh-iso") { mesh_iso = strtof(next(), nullptr); have_mesh_opt = true; }
+        else if (a == "--mesh-colour") { mesh_colour = true; have_mesh_opt = true; }
         else if (a == "--background") {
             if (sscanf(next(), "%f,%f,%f", &background[0], &background[1], &background[2]) != 3) { usage(argv[0]); return 2; }
             have_background = true;
@@ -99,8 +107,9 @@ int main(int argc, char **argv) {
         } else { usage(argv[0]); return a == "--help" || a == "-h" ? 0 : 2; }
     }
 
-    if (want_grid && (!have_grid_lo || !have_grid_step || (grid_out.empty() && grid_bits_path.empty()))) { usage(argv[0]); return 2; }
-    if (!want_grid && (have_grid_lo || have_grid_step || !grid_out.empty() || !grid_bits_path.empty())) { usage(argv[0]); return 2; }
+    if (want_grid && (!have_grid_lo || !have_grid_step || (grid_out.empty() && grid_bits_path.empty() && mesh_path.empty()))) { usage(argv[0]); return 2; }
+    if (!want_grid && (have_grid_lo || have_grid_step || !grid_out.empty() || !grid_bits_path.empty() || !mesh_path.empty())) { usage(argv[0]); return 2; }
+    if (mesh_path.empty() && have_mesh_opt) { usage(argv[0]); return 2; }
 
     // one context per GPU (--gpus N: devices 0..N-1, the rayon fan-out of src/lib.rs:533-550 becomes a fan-out over devices)
     if (gpus < 1) { usage(argv[0]); return 2; }
@@ -113,6 +122,33 @@ int main(int argc, char **argv) {
             fprintf(stderr, "error: %s\n", nerf_last_error(c));
             return 1;
         }
+    if (want_grid && !mesh_path.empty()) { // the level set of the lattice as a mesh: size query, then the fill (the lattice is evaluated twice)
+        uint64_t nv = 0, nt = 0;
+        if (nerf_extract_mesh(ctx, grid_net, grid_lo, grid_step, grid_dims, mesh_iso, nullptr, nullptr, nullptr, 0, nullptr, 0, &nv, &nt)) {
+            fprintf(stderr, "error: %s\n", nerf_last_error(ctx));
+            return 1;
+        }
+        std::vector<float> verts(3 * (size_t)nv), normals(3 * (size_t)nv), colours(mesh_colour ? 3 * (size_t)nv : 0);
+        std::vector<uint32_t> tris(3 * (size_t)nt);
+        if (nv && nerf_extract_mesh(ctx, grid_net, grid_lo, grid_step, grid_dims, mesh_iso, verts.data(), normals.data(), mesh_colour ? colours.data() : nullptr,
+                                    (size_t)nv, tris.data(), (size_t)nt, &nv, &nt)) {
+            fprintf(stderr, "error: %s\n", nerf_last_error(ctx));
+            return 1;
+        }
+        if (nerf_save_ply(mesh_path.c_str(), (size_t)nv, verts.data(), normals.data(), mesh_colour ? colours.data() : nullptr, (size_t)nt, tris.data())) {
+            fprintf(stderr, "error: %s\n", nerf_last_error(nullptr));
+            return 1;
+        }
+        printf("mesh sigma = %g on %d x %d x %d (%s network): %llu vertices, %llu triangles\n", (double)mesh_iso, grid_dims[0], grid_dims[1], grid_dims[2],
+               grid_net == NERF_NET_FINE ? "fine" : "coarse", (unsigned long long)nv, (unsigned long long)nt);
+        if (grid_out.empty() && grid_bits_path.empty()) {
+            if (!want_image) {
+                for (nerf_ctx *c : ctxs) nerf_destroy(c);
+                return 0;
+            }
+            want_grid = false;
+        }
+    }
     if (want_grid) { // the density field on the first context (one launch, one GPU)
         const bool ok_dims = grid_dims[0] > 0 && grid_dims[1] > 0 && grid_dims[2] > 0;
         const size_t cells = ok_dims ? (size_t)grid_dims[0] * (size_t)grid_dims[1] * (size_t)grid_dims[2] : 0; // the library refuses bad dims and sizes beyond one launch

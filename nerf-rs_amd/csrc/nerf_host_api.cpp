@@ -1,6 +1,6 @@
 // nerf_host_api.cpp -- the HOST-ONLY entry points of the C ABI (include/nerf_mi355x.h): everything that parses files from disk or
 // converts host buffers and never touches the device -- weight-directory validation and packing, the packed-blob reader, camera
-// construction (incl. the hand-written JSON reader), PPM writer, quantisers, the split diagnostics.  No HIP header is included,
+// construction (incl. the hand-written JSON reader), PPM / PFM / PAM / PLY writers, quantisers, the split diagnostics.  No HIP header is included,
 // so this file and host_util.cpp also build with plain g++ under AddressSanitizer + UBSan (`make host-asan`; driven by
 // tests/test_host_asan.py on the CPU box with truncated / oversized / malformed inputs).
 #include <math.h>
@@ -189,6 +189,14 @@ int nerf_save_pam(const char *path, int width, int height, const uint8_t *rgba) 
     if (!path || !rgba) return fail_noctx(NERF_ERR_INVALID, "NULL argument");
     std::string err;
     const int rc = save_pam(path, width, height, rgba, err);
+    return rc ? fail_noctx(rc, err) : NERF_OK;
+} NERF_HOST_CATCH
+
+int nerf_save_ply(const char *path, size_t n_vertices, const float *vertices, const float *normals, const float *rgb, size_t n_triangles,
+                  const uint32_t *triangles) try {
+    if (!path) return fail_noctx(NERF_ERR_INVALID, "NULL argument");
+    std::string err;
+    const int rc = save_ply(path, n_vertices, vertices, normals, rgb, n_triangles, triangles, err);
     return rc ? fail_noctx(rc, err) : NERF_OK;
 } NERF_HOST_CATCH
 

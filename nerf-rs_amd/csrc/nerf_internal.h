@@ -63,6 +63,8 @@ struct nerf_ctx {
     float *d_pack = nullptr; size_t pack_bytes = 0;      // RGBA8 renders: the f32 frame [+ opacity plane] the pack kernel reads (a host-pointer call stages the packed words in d_out)
     // scratch for forward_batch / stage calls
     void *d_scratch = nullptr; size_t scratch_bytes = 0;
+    // isosurface extraction (isosurface_kernels.h): the per-lattice-point workspace; the mesh itself is staged in d_scratch
+    void *d_mesh = nullptr; size_t mesh_bytes = 0;
     // skip_dead: device queue/counters {u32 ray counter, u32 live count, u64 chunk count} per MLP launch of a render, the
     // compacted trunk outputs of the live samples and their sample indices
     unsigned int *d_seq = nullptr; size_t seq_slots = 0;
