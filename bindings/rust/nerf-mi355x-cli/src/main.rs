@@ -27,6 +27,48 @@ fn main() {
     check(ctx, unsafe { sys::nerf_load_network_dir(ctx, sys::NERF_NET_COARSE, cstr(&root.join("coarse")).as_ptr()) });
     check(ctx, unsafe { sys::nerf_load_network_dir(ctx, sys::NERF_NET_FINE, cstr(&root.join("fine")).as_ptr()) });
 
+    // beyond the reference, with the flags and meanings of nerf_cli (nerf-rs_amd/csrc/nerf_cli.cpp):
+    //   --density-grid NX,NY,NZ --grid-lo X,Y,Z --grid-step SX,SY,SZ [--grid-net coarse|fine] --mesh FILE.ply [--mesh-iso V]
+    //   [--mesh-keep-largest K] [--mesh-min-points M]
+    // writes the sigma = V surface (default 10) of the lattice instead of rendering; K / M keep only the K largest connected components of the
+    // inside points / those of at least M lattice points (nerf_extract_mesh_filtered).  The three lattice flags are required with --mesh.
+    let args: Vec<String> = std::env::args().collect();
+    let value = |flag: &str| args.iter().position(|a| a == flag).and_then(|i| args.get(i + 1)).cloned();
+    fn triple<T: std::str::FromStr + Copy>(flag: &str, text: Option<String>) -> [T; 3] {
+        let text = text.unwrap_or_else(|| panic!("--mesh needs {flag} A,B,C"));
+        let v: Vec<T> = text.split(',').map(|x| x.trim().parse().unwrap_or_else(|_| panic!("{flag} A,B,C"))).collect();
+        assert!(v.len() == 3, "{flag} A,B,C");
+        [v[0], v[1], v[2]]
+    }
+    if let Some(path) = value("--mesh") {
+        let iso: f32 = value("--mesh-iso").map_or(10.0, |v| v.parse().expect("--mesh-iso V"));
+        let filter = sys::nerf_component_filter { keep_largest: value("--mesh-keep-largest").map_or(0, |v| v.parse().expect("--mesh-keep-largest K")),
+                                                  min_points: value("--mesh-min-points").map_or(0, |v| v.parse().expect("--mesh-min-points M")) };
+        let dims: [i32; 3] = triple("--density-grid", value("--density-grid"));
+        let lo: [f32; 3] = triple("--grid-lo", value("--grid-lo"));
+        let step: [f32; 3] = triple("--grid-step", value("--grid-step"));
+        let which = match value("--grid-net").as_deref() { None | Some("fine") => sys::NERF_NET_FINE, Some("coarse") => sys::NERF_NET_COARSE,
+                                                           Some(other) => panic!("--grid-net coarse|fine, not {other}") };
+        let fp = &filter as *const sys::nerf_component_filter as *const std::ffi::c_void;
+        let (mut nv, mut nt, mut nc, mut nk) = (0u64, 0u64, 0u64, 0u64);
+        let null = std::ptr::null_mut::<f32>();
+        check(ctx, unsafe {
+            sys::nerf_extract_mesh_filtered(ctx, which, lo.as_ptr(), step.as_ptr(), dims.as_ptr(), iso, fp, null, null, null, 0,
+                                            std::ptr::null_mut(), 0, &mut nv, &mut nt, &mut nc, &mut nk)
+        });
+        let (mut v, mut n, mut t) = (vec![0f32; 3 * nv as usize], vec![0f32; 3 * nv as usize], vec![0u32; 3 * nt as usize]);
+        check(ctx, unsafe {
+            sys::nerf_extract_mesh_filtered(ctx, which, lo.as_ptr(), step.as_ptr(), dims.as_ptr(), iso, fp, v.as_mut_ptr(), n.as_mut_ptr(), null,
+                                            nv as usize, t.as_mut_ptr(), nt as usize, &mut nv, &mut nt, std::ptr::null_mut(), std::ptr::null_mut())
+        });
+        check(std::ptr::null(), unsafe {
+            sys::nerf_save_ply(CString::new(path).unwrap().as_ptr(), nv as usize, v.as_ptr(), n.as_ptr(), std::ptr::null(), nt as usize, t.as_ptr())
+        });
+        println!("mesh sigma = {iso}: {nv} vertices, {nt} triangles; {nc} components, {nk} kept");
+        unsafe { sys::nerf_destroy(ctx) };
+        return;
+    }
+
     let (coarse_samples_per_ray, fine_samples_per_ray) = (64, 128); // default_sample_counts, src/lib.rs:603-612
     let (width, height) = (256, 256);                                // src/lib.rs:657-658
     println!("Rendering with {} coarse samples and {} fine samples per ray", coarse_samples_per_ray, fine_samples_per_ray);

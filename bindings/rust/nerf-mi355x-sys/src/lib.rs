@@ -80,6 +80,25 @@ pub struct nerf_stats {
     pub certify_max_error: [f32; 2],
 }
 
+/// `filter` of the `*_filtered` mesh entry points ("lattice components" in include/nerf_mi355x.h): a component of the inside points is kept
+/// iff `n_points >= min_points` and (`keep_largest == 0` or its rank < `keep_largest`); `keep_largest` <= 64.  Passed as `*const c_void`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct nerf_component_filter {
+    pub keep_largest: u32,
+    pub min_points: u32,
+}
+
+/// One entry of `nerf_lattice_components`' table (passed as `*mut c_void`): `label` = the smallest linear index of the component,
+/// `bounds` = inclusive {ix_min, iy_min, iz_min, ix_max, iy_max, iz_max}.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct nerf_component {
+    pub label: u32,
+    pub n_points: u32,
+    pub bounds: [i32; 6],
+}
+
 /// `gather` of `nerf_render_image_multi`
 pub const NERF_GATHER_HOST: c_int = 0;
 pub const NERF_GATHER_PEER: c_int = 1;
@@ -154,6 +173,28 @@ extern "C" {
     pub fn nerf_extract_mesh_device(ctx: *mut nerf_ctx, which: c_int, lo: *const f32, step: *const f32, dims: *const i32, iso: f32,
                                     d_vertices: *mut f32, d_normals: *mut f32, d_rgb: *mut f32, cap_vertices: usize, d_triangles: *mut u32,
                                     cap_triangles: usize, n_vertices: *mut u64, n_triangles: *mut u64, stream: *mut c_void) -> c_int;
+    /// Connected components of the inside points (sigma > iso, 14-neighbour Kuhn connectivity) of a caller's lattice: `labels_out` N u32 or null
+    /// (a component's label = its smallest linear index, 0xFFFFFFFF where not inside), `table` = `*mut nerf_component` with `cap_table` <= 64
+    /// entries or null (the largest components first, ties by label), `n_components` required.
+    pub fn nerf_lattice_components(ctx: *mut nerf_ctx, sigma: *const f32, dims: *const i32, iso: f32, labels_out: *mut u32, table: *mut c_void,
+                                   cap_table: usize, n_components: *mut u64) -> c_int;
+    /// `d_sigma` / `d_labels_out` on the device (e.g. nerf_density_grid_device's output); `table` / `n_components` on the host: synchronises `stream`.
+    pub fn nerf_lattice_components_device(ctx: *mut nerf_ctx, d_sigma: *const f32, dims: *const i32, iso: f32, d_labels_out: *mut u32,
+                                          table: *mut c_void, cap_table: usize, n_components: *mut u64, stream: *mut c_void) -> c_int;
+    /// The mesh entry points restricted to the components `filter` (`*const nerf_component_filter` or null = everything) keeps;
+    /// `n_components` / `n_kept` optional.
+    pub fn nerf_isosurface_grid_filtered(ctx: *mut nerf_ctx, sigma: *const f32, lo: *const f32, step: *const f32, dims: *const i32, iso: f32,
+                                         filter: *const c_void, vertices: *mut f32, normals: *mut f32, cap_vertices: usize, triangles: *mut u32,
+                                         cap_triangles: usize, n_vertices: *mut u64, n_triangles: *mut u64, n_components: *mut u64,
+                                         n_kept: *mut u64) -> c_int;
+    pub fn nerf_extract_mesh_filtered(ctx: *mut nerf_ctx, which: c_int, lo: *const f32, step: *const f32, dims: *const i32, iso: f32,
+                                      filter: *const c_void, vertices: *mut f32, normals: *mut f32, rgb: *mut f32, cap_vertices: usize,
+                                      triangles: *mut u32, cap_triangles: usize, n_vertices: *mut u64, n_triangles: *mut u64,
+                                      n_components: *mut u64, n_kept: *mut u64) -> c_int;
+    pub fn nerf_extract_mesh_filtered_device(ctx: *mut nerf_ctx, which: c_int, lo: *const f32, step: *const f32, dims: *const i32, iso: f32,
+                                             filter: *const c_void, d_vertices: *mut f32, d_normals: *mut f32, d_rgb: *mut f32,
+                                             cap_vertices: usize, d_triangles: *mut u32, cap_triangles: usize, n_vertices: *mut u64,
+                                             n_triangles: *mut u64, n_components: *mut u64, n_kept: *mut u64, stream: *mut c_void) -> c_int;
     pub fn nerf_render_image(ctx: *mut nerf_ctx, cam: *const nerf_camera, opts: *const nerf_render_opts,
                              rgb_out: *mut f32, stats: *mut nerf_stats) -> c_int;
     pub fn nerf_render_image_device(ctx: *mut nerf_ctx, cam: *const nerf_camera, opts: *const nerf_render_opts,
@@ -222,7 +263,9 @@ pub fn check_layouts() -> Result<(), String> {
     let (mut a, mut b, mut c) = (0usize, 0usize, 0usize);
     unsafe { nerf_abi_struct_sizes(&mut a, &mut b, &mut c) };
     let mine = (std::mem::size_of::<nerf_camera>(), std::mem::size_of::<nerf_render_opts>(), std::mem::size_of::<nerf_stats>());
-    if (a, b, c) == mine && unsafe { nerf_abi_version() } == 5 {
+    // the two component structs have fixed sizes (8 and 32 bytes, stated in the header)
+    let components = std::mem::size_of::<nerf_component_filter>() == 8 && std::mem::size_of::<nerf_component>() == 32;
+    if (a, b, c) == mine && components && unsafe { nerf_abi_version() } == 5 {
         Ok(())
     } else {
         Err(format!("libnerf_mi355x: ABI {} with struct sizes {:?}, this crate expects ABI 5 with {:?}", unsafe { nerf_abi_version() }, (a, b, c), mine))

@@ -69,6 +69,11 @@ pub fn save_ppm(path: &Path, width: i32, height: i32, rgb: &[f32]) -> Result<(),
     check(std::ptr::null(), unsafe { sys::nerf_save_ppm(cpath(path)?.as_ptr(), width, height, rgb.as_ptr()) })
 }
 
+/// Which connected components of the inside points a filtered mesh keeps (`nerf_component_filter`).
+pub type ComponentFilter = sys::nerf_component_filter;
+/// One connected component: label, number of lattice points, inclusive index bounds (`nerf_component`).
+pub type Component = sys::nerf_component;
+
 /// An indexed triangle mesh (`Gpu::extract_mesh`): `vertices`, `normals`, `colours` are V x 3, `triangles` T x 3 vertex ids.
 #[derive(Debug, Clone, Default)]
 pub struct Mesh {
@@ -195,6 +200,46 @@ impl Gpu {
                                       mesh.triangles.as_mut_ptr(), cap_t, &mut nv, &mut nt)
         })?;
         Ok(mesh)
+    }
+
+    /// `extract_mesh` restricted to the components `filter` keeps (nerf_extract_mesh_filtered; "lattice components" in the header): the
+    /// inside points (sigma > iso) are split into connected pieces under the 14-neighbour Kuhn connectivity, ranked by size (ties: smaller
+    /// label first); `keep_largest: 1` drops every floater.  Returns the mesh, the number of components and the number kept.
+    pub fn extract_mesh_filtered(&self, fine: bool, lo: [f32; 3], step: [f32; 3], dims: [i32; 3], iso: f32, filter: ComponentFilter, normals: bool,
+                                 colours: bool) -> Result<(Mesh, u64, u64), Error> {
+        let which = if fine { sys::NERF_NET_FINE } else { sys::NERF_NET_COARSE };
+        let (mut nv, mut nt, mut nc, mut nk) = (0u64, 0u64, 0u64, 0u64);
+        let null = std::ptr::null_mut::<f32>();
+        let fp = &filter as *const ComponentFilter as *const std::ffi::c_void;
+        check(self.ctx, unsafe {
+            sys::nerf_extract_mesh_filtered(self.ctx, which, lo.as_ptr(), step.as_ptr(), dims.as_ptr(), iso, fp, null, null, null, 0, std::ptr::null_mut(), 0,
+                                            &mut nv, &mut nt, &mut nc, &mut nk)
+        })?;
+        let (cap_v, cap_t) = (nv as usize, nt as usize);
+        let mut mesh = Mesh { vertices: vec![0f32; 3 * cap_v], normals: if normals { Some(vec![0f32; 3 * cap_v]) } else { None },
+                              colours: if colours { Some(vec![0f32; 3 * cap_v]) } else { None }, triangles: vec![0u32; 3 * cap_t] };
+        let np = mesh.normals.as_mut().map_or(null, |v| v.as_mut_ptr());
+        let cp = mesh.colours.as_mut().map_or(null, |v| v.as_mut_ptr());
+        check(self.ctx, unsafe {
+            sys::nerf_extract_mesh_filtered(self.ctx, which, lo.as_ptr(), step.as_ptr(), dims.as_ptr(), iso, fp, mesh.vertices.as_mut_ptr(), np, cp, cap_v,
+                                            mesh.triangles.as_mut_ptr(), cap_t, &mut nv, &mut nt, std::ptr::null_mut(), std::ptr::null_mut())
+        })?;
+        assert!(nv as usize == cap_v && nt as usize == cap_t, "the mesh changed between the size query and the fill");
+        Ok((mesh, nc, nk))
+    }
+
+    /// The connected components of the inside points of a caller's sigma lattice (nerf_lattice_components): per point its component's label
+    /// (the smallest linear index of the component; 0xFFFFFFFF where not inside), the `table` (<= 64) largest components in rank order, and
+    /// the number of components.
+    pub fn lattice_components(&self, sigma: &[f32], dims: [i32; 3], iso: f32, table: usize) -> Result<(Vec<u32>, Vec<Component>, u64), Error> {
+        assert_eq!(sigma.len(), dims.iter().map(|&d| d.max(0) as usize).product::<usize>(), "one sigma per lattice point");
+        let mut labels = vec![0u32; sigma.len()];
+        let mut entries = vec![Component::default(); table];
+        let mut n = 0u64;
+        let tp = if table > 0 { entries.as_mut_ptr() as *mut std::ffi::c_void } else { std::ptr::null_mut() };
+        check(self.ctx, unsafe { sys::nerf_lattice_components(self.ctx, sigma.as_ptr(), dims.as_ptr(), iso, labels.as_mut_ptr(), tp, table, &mut n) })?;
+        entries.truncate((n as usize).min(table));
+        Ok((labels, entries, n))
     }
 
     /// Linear RGB, pixel (i, j) at `(i * w + j) * 3` (image[i * nx + j], src/lib.rs:552-557); `opts.n_coarse` = camera.samples_per_ray.

@@ -311,6 +311,59 @@ int nerf_extract_mesh_device(nerf_ctx *ctx, int which, const float lo[3], const 
                              float *d_vertices, float *d_normals, float *d_rgb, size_t cap_vertices, uint32_t *d_triangles,
                              size_t cap_triangles, uint64_t *n_vertices, uint64_t *n_triangles, void *stream);
 
+/* ---- lattice components: the connected pieces of the inside points of a density lattice, and meshes of the largest pieces only ---------------
+ * A NeRF density has floaters: specks of sigma > iso detached from the object.  These entry points label the pieces on the device
+ * (nerf-rs_amd/csrc/components_kernels.hip), rank them by size, and let the mesh entry points drop all but the kept ones, without the lattice
+ * or the mesh visiting the host.  A host can restate every output bit for bit from the following (tests/helpers/lattice_components.py does).
+ * LATTICE       as above (x fastest, linear index A = ix + dims[0] (iy + dims[1] iz)); nerf_lattice_components needs no lo / step and accepts
+ *               every dims[k] >= 1; N as for the meshes (at most 2^28 and nerf_forward_batch's largest n); iso finite.
+ * INSIDE        sigma > iso, the predicate of the meshes: a NaN is not inside, +inf is.
+ * CONNECTIVITY  two inside points are adjacent iff they are the two ends of a Kuhn edge: they differ by +d or -d for one d in {0,1}^3 \ {0} --
+ *               the 7 edges a point owns and the 7 it is the far end of, 14 neighbours.  (0,0,0)-(1,1,1) are adjacent, (1,0,0)-(0,1,0) are not.
+ *               This is the connectivity of the piecewise-linear level set the mesh triangulates (sigma is linear along an edge of a
+ *               tetrahedron, so two inside ends are joined inside); 6, 18 or 26 neighbours would disagree with the mesh.
+ * LABEL         of a component: the smallest linear index among its points; of a point that is not inside: 0xFFFFFFFF.
+ * SIZE, RANK    n_points = number of lattice points of the component; components are ordered by n_points descending, ties by label ascending.
+ * FILTER        nerf_component_filter {keep_largest, min_points}: a component is KEPT iff n_points >= min_points and (keep_largest == 0 or its
+ *               rank < keep_largest).  keep_largest > 64 is NERF_ERR_INVALID.  A NULL filter or {0, 0} keeps everything.
+ * FILTERED MESH a point of a discarded component counts as NOT INSIDE when edges and cells are classified; nothing else changes: t, positions
+ *               and normals come from the true sigma with the arithmetic above.  The four corners of a tetrahedron are pairwise Kuhn-adjacent,
+ *               so its inside corners are all kept or all discarded.  The filtered mesh is therefore exactly the unfiltered mesh minus the
+ *               triangles of discarded components, minus the vertices whose inside end belongs to a discarded component, the remaining vertex
+ *               ids renumbered in their old order: vertex bits and triangle order are unchanged.  With a NULL or {0, 0} filter the output is
+ *               that of the unfiltered entry point, bit for bit.  The capacity protocol is the existing one, applied to the filtered counts.
+ * The labels are the same bits in every run (the root of a component is its smallest index whatever order the device's atomics land in);
+ * sizes, counts and bounds are integer sums, minima and maxima.  No kernel waits for another workgroup.
+ * Workspace: 8 bytes per lattice point (label; size + keep flag) on top of the meshes' 16, in the context, grown on demand, and only when a
+ * filter, a count or a component query is asked for -- a warm call allocates nothing.
+ * The struct arguments are declared `const void *` / `void *` below so that bindings generated from the scalar types alone keep working;
+ * they point to the two structs defined here.  This gives up type checking for C and C++ callers: to be revisited (typed pointers, an
+ * ABI-compatible change) once the textual check of the bindings against this header knows the two struct names. */
+typedef struct { uint32_t keep_largest, min_points; } nerf_component_filter;           /* 8 bytes */
+typedef struct { uint32_t label, n_points; int32_t bounds[6]; } nerf_component;        /* 32 bytes; bounds as nerf_density_grid: inclusive
+                                                                                        * {ix_min, iy_min, iz_min, ix_max, iy_max, iz_max} */
+/* Labels every point of the caller's lattice (host, dims[2] x dims[1] x dims[0] floats).  labels_out (N uint32) and table (nerf_component
+ * [cap_table]; receives the first min(cap_table, n_components) components in rank order, nothing beyond) are optional; n_components is
+ * required.  cap_table <= 64; a table with cap_table == 0 is NERF_ERR_INVALID.  Needs a context, not a network.  Synchronous. */
+int nerf_lattice_components(nerf_ctx *ctx, const float *sigma, const int32_t dims[3], float iso, uint32_t *labels_out, void *table,
+                            size_t cap_table, uint64_t *n_components);
+/* d_sigma / d_labels_out: device pointers; table and n_components: HOST pointers -- the call synchronises the stream to return them.  After
+ * nerf_density_grid_device on the same stream sigma never reaches the host. */
+int nerf_lattice_components_device(nerf_ctx *ctx, const float *d_sigma, const int32_t dims[3], float iso, uint32_t *d_labels_out, void *table,
+                                   size_t cap_table, uint64_t *n_components, void *stream);
+/* nerf_isosurface_grid / nerf_extract_mesh / nerf_extract_mesh_device restricted to the kept components.  filter: const nerf_component_filter *
+ * or NULL.  n_components (all components of the lattice) and n_kept (those that pass the filter) are optional HOST pointers. */
+int nerf_isosurface_grid_filtered(nerf_ctx *ctx, const float *sigma, const float lo[3], const float step[3], const int32_t dims[3], float iso,
+                                  const void *filter, float *vertices, float *normals, size_t cap_vertices, uint32_t *triangles,
+                                  size_t cap_triangles, uint64_t *n_vertices, uint64_t *n_triangles, uint64_t *n_components, uint64_t *n_kept);
+int nerf_extract_mesh_filtered(nerf_ctx *ctx, int which, const float lo[3], const float step[3], const int32_t dims[3], float iso,
+                               const void *filter, float *vertices, float *normals, float *rgb, size_t cap_vertices, uint32_t *triangles,
+                               size_t cap_triangles, uint64_t *n_vertices, uint64_t *n_triangles, uint64_t *n_components, uint64_t *n_kept);
+int nerf_extract_mesh_filtered_device(nerf_ctx *ctx, int which, const float lo[3], const float step[3], const int32_t dims[3], float iso,
+                                      const void *filter, float *d_vertices, float *d_normals, float *d_rgb, size_t cap_vertices,
+                                      uint32_t *d_triangles, size_t cap_triangles, uint64_t *n_vertices, uint64_t *n_triangles,
+                                      uint64_t *n_components, uint64_t *n_kept, void *stream);
+
 /* ---- S3: render_image (src/lib.rs:474-565) ----------------------------------------------------------------- */
 /* rgb_out: crop_h x crop_w x 3 (or ny x nx x 3) linear RGB f32, row-major, index (i*w + j)*3 as image[i*nx+j]
  * (src/lib.rs:552-557).  Unlike the reference (src/lib.rs:491-501) nx, ny need not be multiples of 8. */
@@ -475,7 +528,9 @@ const char *nerf_build_variant(void);
  * nerf_render_opts.band_*, nerf_band_rows, nerf_debug_certify_policy; additive: nerf_render_image_aux, nerf_render_image_aux_device,
  * nerf_render_image_multi_aux, nerf_save_pfm, nerf_render_image_rgba8, nerf_render_image_rgba8_device, nerf_render_image_multi_rgba8,
  * nerf_stage_integrate_rgba8, nerf_save_pam, NERF_ALPHA_*, nerf_density_batch, nerf_density_batch_device, nerf_density_grid,
- * nerf_density_grid_device, nerf_isosurface_grid, nerf_extract_mesh, nerf_extract_mesh_device, nerf_save_ply). */
+ * nerf_density_grid_device, nerf_isosurface_grid, nerf_extract_mesh, nerf_extract_mesh_device, nerf_save_ply, nerf_component_filter,
+ * nerf_component, nerf_lattice_components, nerf_lattice_components_device, nerf_isosurface_grid_filtered, nerf_extract_mesh_filtered,
+ * nerf_extract_mesh_filtered_device). */
 int nerf_abi_version(void);
 /* sizeof(nerf_camera), sizeof(nerf_render_opts), sizeof(nerf_stats) as this library was built: lets a binding written in
  * another language (the Rust `-sys` crate, ctypes) check its struct mirrors at start-up. */

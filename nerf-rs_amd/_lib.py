@@ -45,6 +45,16 @@ class CStats(C.Structure):
                 ("certify_max_error", C.c_float * 2)]
 
 
+class CComponentFilter(C.Structure):
+    """nerf_component_filter: a component is kept iff n_points >= min_points and (keep_largest == 0 or its rank < keep_largest)."""
+    _fields_ = [("keep_largest", C.c_uint32), ("min_points", C.c_uint32)]
+
+
+class CComponent(C.Structure):
+    """nerf_component: label = smallest linear index, bounds = inclusive (ix_min, iy_min, iz_min, ix_max, iy_max, iz_max)."""
+    _fields_ = [("label", C.c_uint32), ("n_points", C.c_uint32), ("bounds", C.c_int32 * 6)]
+
+
 # name -> (restype, argtypes); kept in sync with include/nerf_mi355x.h (tests/test_host_logic.py::test_abi_exports_every_declared_symbol checks the header)
 PROTOTYPES = {
     "nerf_abi_version": (C.c_int, []),
@@ -85,6 +95,16 @@ PROTOTYPES = {
                                     C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "nerf_extract_mesh_device": (C.c_int, [C.c_void_p, C.c_int, f32p, f32p, i32p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                            C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]),
+    "nerf_lattice_components": (C.c_int, [C.c_void_p, f32p, i32p, C.c_float, u32p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]),
+    "nerf_lattice_components_device": (C.c_int, [C.c_void_p, C.c_void_p, i32p, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64),
+                                                 C.c_void_p]),
+    "nerf_isosurface_grid_filtered": (C.c_int, [C.c_void_p, f32p, f32p, f32p, i32p, C.c_float, C.c_void_p, f32p, f32p, C.c_size_t, u32p, C.c_size_t,
+                                                C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "nerf_extract_mesh_filtered": (C.c_int, [C.c_void_p, C.c_int, f32p, f32p, i32p, C.c_float, C.c_void_p, f32p, f32p, f32p, C.c_size_t, u32p, C.c_size_t,
+                                             C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "nerf_extract_mesh_filtered_device": (C.c_int, [C.c_void_p, C.c_int, f32p, f32p, i32p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                                    C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]),
     "nerf_save_ply": (C.c_int, [C.c_char_p, C.c_size_t, f32p, f32p, f32p, C.c_size_t, u32p]),
     "nerf_render_image": (C.c_int, [C.c_void_p, C.POINTER(CCamera), C.POINTER(COpts), f32p, C.POINTER(CStats)]),
     "nerf_render_image_device": (C.c_int, [C.c_void_p, C.POINTER(CCamera), C.POINTER(COpts), C.c_void_p, C.c_void_p,

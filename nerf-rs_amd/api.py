@@ -15,7 +15,7 @@ import json
 import numpy as np
 
 from . import _lib
-from ._lib import CCamera, COpts, CStats, NerfError, check, f32p, i32p, u8p, u32p
+from ._lib import CCamera, CComponent, CComponentFilter, COpts, CStats, NerfError, check, f32p, i32p, u8p, u32p
 
 NET_COARSE, NET_FINE = 0, 1
 MLP_F32, MLP_BF16 = 0, 1
@@ -238,7 +238,7 @@ class Network:
         return (int(cnt.value), tuple(int(v) for v in bounds)) if want_stats else None
 
 
-    def extract_mesh(self, lo, step, dims, iso, normals=False, colours=False, capacity=None):
+    def extract_mesh(self, lo, step, dims, iso, normals=False, colours=False, capacity=None, keep_largest=0, min_points=0, return_counts=False):
         """The level set sigma = iso of this network on the lattice lo + step * index (density_grid's lattice, every dims >= 2, no zero
         step), extracted on the device by marching tetrahedra (nerf_extract_mesh; conventions: include/nerf_mi355x.h) -> Mesh(vertices
         (V, 3) f32, normals (V, 3) f32 or None, colours (V, 3) f32 or None, triangles (T, 3) uint32).  The sigma lattice never reaches
@@ -246,22 +246,45 @@ class Network:
 
         capacity=None asks the library for the counts first and then calls it again with arrays of that size: A QUERY FOLLOWED BY A FILL
         EVALUATES THE LATTICE TWICE (the network launch included).  capacity=(max_vertices, max_triangles) is one call; a mesh that
-        does not fit raises NerfError with the counts in the message (nothing was written)."""
+        does not fit raises NerfError with the counts in the message (nothing was written).
+
+        keep_largest / min_points (nerf_extract_mesh_filtered; "lattice components" in the header): only the components of the inside points
+        (14-neighbour Kuhn connectivity) with at least min_points lattice points and, if keep_largest > 0, among the keep_largest largest
+        (ties: smaller label first) are meshed -- keep_largest=1 drops every floater.  Both 0 (the default): the unfiltered entry point.
+        return_counts=True -> (Mesh, n_components, n_kept)."""
         lo_c, step_c, dims_c, _ = _grid_args(lo, step, dims)
         R = self.renderer
-        call = lambda v, n, c, cv, t, ct, nv, nt: R._L.nerf_extract_mesh(R.handle, self.which, _p(lo_c), _p(step_c), dims_c.ctypes.data_as(i32p), float(iso),
-                                                                         v, n, c, cv, t, ct, nv, nt)
-        return _mesh_call(call, R.handle, bool(normals), bool(colours), capacity)
+        filt, nc, nk = _filter_args(keep_largest, min_points, return_counts)
+        if filt is None and not return_counts:
+            call = lambda v, n, c, cv, t, ct, nv, nt: R._L.nerf_extract_mesh(R.handle, self.which, _p(lo_c), _p(step_c), dims_c.ctypes.data_as(i32p), float(iso),
+                                                                             v, n, c, cv, t, ct, nv, nt)
+        else:
+            call = lambda v, n, c, cv, t, ct, nv, nt: R._L.nerf_extract_mesh_filtered(R.handle, self.which, _p(lo_c), _p(step_c), dims_c.ctypes.data_as(i32p),
+                                                                                      float(iso), None if filt is None else C.addressof(filt),
+                                                                                      v, n, c, cv, t, ct, nv, nt, C.byref(nc) if return_counts else None,
+                                                                                      C.byref(nk) if return_counts else None)
+        mesh = _mesh_call(call, R.handle, bool(normals), bool(colours), capacity)
+        return (mesh, int(nc.value), int(nk.value)) if return_counts else mesh
 
-    def extract_mesh_device(self, lo, step, dims, iso, d_vertices, d_normals, d_colours, cap_vertices, d_triangles, cap_triangles, stream=0):
+    def extract_mesh_device(self, lo, step, dims, iso, d_vertices, d_normals, d_colours, cap_vertices, d_triangles, cap_triangles, stream=0,
+                            keep_largest=0, min_points=0, return_counts=False):
         """Raw device pointers (ints; each may be None) -> (n_vertices, n_triangles).  Synchronises `stream` to read the counts; the arrays are
-        written (asynchronously) only if both counts fit the capacities."""
+        written (asynchronously) only if both counts fit the capacities.  keep_largest / min_points as in extract_mesh
+        (nerf_extract_mesh_filtered_device); return_counts=True -> (n_vertices, n_triangles, n_components, n_kept)."""
         lo_c, step_c, dims_c, _ = _grid_args(lo, step, dims)
         nv, nt = C.c_uint64(0), C.c_uint64(0)
         R = self.renderer
-        check(R._L.nerf_extract_mesh_device(R.handle, self.which, _p(lo_c), _p(step_c), dims_c.ctypes.data_as(i32p), float(iso), d_vertices, d_normals,
-                                            d_colours, int(cap_vertices), d_triangles, int(cap_triangles), C.byref(nv), C.byref(nt), stream), R.handle)
-        return int(nv.value), int(nt.value)
+        filt, nc, nk = _filter_args(keep_largest, min_points, return_counts)
+        if filt is None and not return_counts:
+            check(R._L.nerf_extract_mesh_device(R.handle, self.which, _p(lo_c), _p(step_c), dims_c.ctypes.data_as(i32p), float(iso), d_vertices, d_normals,
+                                                d_colours, int(cap_vertices), d_triangles, int(cap_triangles), C.byref(nv), C.byref(nt), stream), R.handle)
+            return int(nv.value), int(nt.value)
+        check(R._L.nerf_extract_mesh_filtered_device(R.handle, self.which, _p(lo_c), _p(step_c), dims_c.ctypes.data_as(i32p), float(iso),
+                                                     None if filt is None else C.addressof(filt), d_vertices, d_normals, d_colours, int(cap_vertices),
+                                                     d_triangles, int(cap_triangles), C.byref(nv), C.byref(nt), C.byref(nc) if return_counts else None,
+                                                     C.byref(nk) if return_counts else None, stream), R.handle)
+        out = (int(nv.value), int(nt.value))
+        return out + (int(nc.value), int(nk.value)) if return_counts else out
 
 
 Mesh = collections.namedtuple("Mesh", "vertices normals colours triangles")
@@ -289,17 +312,81 @@ def _mesh_call(call, handle, normals, colours, capacity):
     return Mesh(v[:n_v], None if n is None else n[:n_v], None if c is None else c[:n_v], t[:n_t])
 
 
-def isosurface(renderer, sigma, lo, step, iso, normals=False, capacity=None):
+def _filter_args(keep_largest, min_points, return_counts):
+    """(CComponentFilter or None for "keep everything", n_components, n_kept) of a filtered mesh call."""
+    k, m = int(keep_largest), int(min_points)
+    if not (0 <= k < 2 ** 32 and 0 <= m < 2 ** 32):
+        raise NerfError(-1, "keep_largest and min_points must be non-negative 32-bit integers")
+    return (CComponentFilter(k, m) if (k or m > 1) else None), C.c_uint64(0), C.c_uint64(0)     # every component has a point: min_points 1 discards nothing
+
+
+def isosurface(renderer, sigma, lo, step, iso, normals=False, capacity=None, keep_largest=0, min_points=0, return_counts=False):
     """The level set sigma = iso of a caller-supplied lattice sigma[iz, iy, ix] (shape (nz, ny, nx), x fastest, at the points lo + step * index)
     by marching tetrahedra on the device (nerf_isosurface_grid; needs a Renderer, no network) -> Mesh(vertices, normals or None, None,
-    triangles).  capacity as in Network.extract_mesh (None: a size query, then the fill -- the lattice is uploaded and classified twice)."""
+    triangles).  capacity as in Network.extract_mesh (None: a size query, then the fill -- the lattice is uploaded and classified twice).
+    keep_largest / min_points / return_counts as in Network.extract_mesh (nerf_isosurface_grid_filtered)."""
     sig = _f32(sigma)
     if sig.ndim != 3:
         raise NerfError(-1, "sigma must be a (nz, ny, nx) array")
     lo_c, step_c, dims_c, _ = _grid_args(lo, step, sig.shape[::-1])
-    call = lambda v, n, c, cv, t, ct, nv, nt: renderer._L.nerf_isosurface_grid(renderer.handle, _p(sig), _p(lo_c), _p(step_c), dims_c.ctypes.data_as(i32p),
-                                                                               float(iso), v, n, cv, t, ct, nv, nt)
-    return _mesh_call(call, renderer.handle, bool(normals), False, capacity)
+    filt, nc, nk = _filter_args(keep_largest, min_points, return_counts)
+    if filt is None and not return_counts:
+        call = lambda v, n, c, cv, t, ct, nv, nt: renderer._L.nerf_isosurface_grid(renderer.handle, _p(sig), _p(lo_c), _p(step_c), dims_c.ctypes.data_as(i32p),
+                                                                                   float(iso), v, n, cv, t, ct, nv, nt)
+    else:
+        call = lambda v, n, c, cv, t, ct, nv, nt: renderer._L.nerf_isosurface_grid_filtered(renderer.handle, _p(sig), _p(lo_c), _p(step_c),
+                                                                                            dims_c.ctypes.data_as(i32p), float(iso),
+                                                                                            None if filt is None else C.addressof(filt), v, n, cv, t, ct,
+                                                                                            nv, nt, C.byref(nc) if return_counts else None,
+                                                                                            C.byref(nk) if return_counts else None)
+    mesh = _mesh_call(call, renderer.handle, bool(normals), False, capacity)
+    return (mesh, int(nc.value), int(nk.value)) if return_counts else mesh
+
+
+Component = collections.namedtuple("Component", "label n_points bounds")
+
+
+def _components_out(table, n_components):
+    return [Component(int(e.label), int(e.n_points), tuple(int(v) for v in e.bounds)) for e in table[:min(len(table), n_components)]]
+
+
+def lattice_components(renderer, sigma, iso, table=16, want_labels=True):
+    """The connected components of the inside points (sigma > iso; 14-neighbour Kuhn connectivity, the mesh's) of a caller-supplied lattice
+    sigma[iz, iy, ix], labelled on the device (nerf_lattice_components; "lattice components" in the header) -> (labels, components,
+    n_components): labels (nz, ny, nx) uint32, a component's label = the smallest linear index ix + nx (iy + ny iz) among its points,
+    0xFFFFFFFF where not inside (None with want_labels=False); components = the first min(table, n_components) as Component(label, n_points,
+    bounds = inclusive (ix_min, iy_min, iz_min, ix_max, iy_max, iz_max)), largest first, ties by label; table <= 64."""
+    sig = _f32(sigma)
+    if sig.ndim != 3:
+        raise NerfError(-1, "sigma must be a (nz, ny, nx) array")
+    dims_c = np.ascontiguousarray(sig.shape[::-1], dtype=np.int32)
+    cap = int(table)
+    if cap < 0:
+        raise NerfError(-1, "table must be >= 0")
+    labels = np.empty(sig.shape, np.uint32) if want_labels else None
+    entries = (CComponent * max(cap, 1))()
+    n = C.c_uint64(0)
+    check(renderer._L.nerf_lattice_components(renderer.handle, _p(sig), dims_c.ctypes.data_as(i32p), float(iso),
+                                              None if labels is None else labels.ctypes.data_as(u32p), C.addressof(entries) if cap else None, cap,
+                                              C.byref(n)), renderer.handle)
+    return labels, _components_out(entries[:cap], int(n.value)), int(n.value)
+
+
+def lattice_components_device(renderer, d_sigma, dims, iso, d_labels=None, table=16, stream=0):
+    """The same on a lattice resident on the device (raw pointers as ints: d_sigma nz * ny * nx floats, e.g. density_grid_device's output;
+    d_labels N uint32 or None) -> (components, n_components).  Synchronises `stream` (nerf_lattice_components_device)."""
+    d = np.asarray(dims)
+    if d.size != 3 or np.any(d != np.floor(d)) or np.any(np.abs(d) >= 2 ** 31):
+        raise NerfError(-1, "dims must be three integers")
+    dims_c = np.ascontiguousarray(d.reshape(-1), dtype=np.int32)
+    cap = int(table)
+    if cap < 0:
+        raise NerfError(-1, "table must be >= 0")
+    entries = (CComponent * max(cap, 1))()
+    n = C.c_uint64(0)
+    check(renderer._L.nerf_lattice_components_device(renderer.handle, d_sigma, dims_c.ctypes.data_as(i32p), float(iso), d_labels,
+                                                     C.addressof(entries) if cap else None, cap, C.byref(n), stream), renderer.handle)
+    return _components_out(entries[:cap], int(n.value)), int(n.value)
 
 
 def _grid_args(lo, step, dims):

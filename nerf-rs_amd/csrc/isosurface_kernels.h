@@ -30,8 +30,9 @@ struct MeshWorkspace {
 size_t mesh_workspace_bytes(size_t n_points);
 MeshWorkspace mesh_workspace_carve(void *base, size_t n_points);
 
-// classify -> block sums -> scan of the block sums (one workgroup): w.totals holds both counts when these three launches have run
-hipError_t launch_mesh_count(const MeshLattice &g, const MeshWorkspace &w, hipStream_t st);
+// classify -> block sums -> scan of the block sums (one workgroup): w.totals holds both counts when these three launches have run.
+// label / size (both or neither; components_kernels.h): the filtered classification -- a point whose component lacks the keep bit is not inside.
+hipError_t launch_mesh_count(const MeshLattice &g, const MeshWorkspace &w, hipStream_t st, const uint32_t *label = nullptr, const uint32_t *size = nullptr);
 // add (vbase, tbase) -> vertices -> triangles.  Every output is optional (device pointers):
 //   vertices, normals  n_vertices x 3 floats;  pts_soa  3 x n_vertices floats (x row, y row, z row);  neg_normals  n_vertices x 3 floats (-normal:
 //   the view direction that looks at the surface head-on);  triangles  n_triangles x 3 vertex ids

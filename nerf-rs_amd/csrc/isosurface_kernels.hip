@@ -3,7 +3,8 @@
 //
 //   k_mesh_classify    one thread per lattice point A: which of the up to 7 edges A -> A + d, d in {0,1}^3 \ {0}, carry a vertex (both end
 //                      sigma finite, exactly one end inside = sigma > iso), the inside mask of the 8 corners of the cell whose low corner A
-//                      is, and that cell's triangle count (0 when a corner is missing or not finite)
+//                      is, and that cell's triangle count (0 when a corner is missing or not finite).  k_mesh_classify_filtered: the same with
+//                      "inside" = sigma > iso and the point's component kept (components_kernels.hip); every later kernel reads only the masks
 //   k_mesh_block_sums  per block of 256 points the number of vertices and of triangles (wave ballots + 64-bit popcounts)
 //   k_mesh_scan_sums   ONE workgroup: exclusive prefix sums of the block sums in place, 256 at a time with a carry; the totals
 //   k_mesh_scan_add    per block the exclusive prefix sums of its points' counts + the block's offset -> vbase, tbase
@@ -57,7 +58,11 @@ __device__ __forceinline__ uint32_t tet_triangle_count(uint32_t inm, uint32_t tm
     return k == 2 ? 2u : (k == 1 || k == 3) ? 1u : 0u;
 }
 
-__global__ __launch_bounds__(kB) void k_mesh_classify(const float *__restrict__ sigma, MeshLattice g, uint32_t n, uint32_t *__restrict__ info) {
+// FILTER: a point of a discarded component counts as not inside -- the inside bit is ANDed with the keep flag (bit 31 of size[label], components_kernels.h)
+// of the corner's component.  Without it this is the unfiltered classification, instruction for instruction.
+template <bool FILTER>
+__device__ __forceinline__ void classify_point(const float *__restrict__ sigma, const MeshLattice &g, uint32_t n, uint32_t *__restrict__ info,
+                                               const uint32_t *__restrict__ label, const uint32_t *__restrict__ size) {
     const uint32_t A = blockIdx.x * (uint32_t)kB + threadIdx.x;
     if (A >= n) return;
     const uint32_t nx = (uint32_t)g.nx, ny = (uint32_t)g.ny, nz = (uint32_t)g.nz;
@@ -68,9 +73,15 @@ __global__ __launch_bounds__(kB) void k_mesh_classify(const float *__restrict__ 
     for (int e = 0; e < 8; ++e) {
         const bool ok = (!(e & 1) || hx) && (!(e & 2) || hy) && (!(e & 4) || hz);
         if (ok) { // inside the lattice: A + offset < n
-            const float s = sigma[A + (uint32_t)(e & 1) + nx * ((uint32_t)((e >> 1) & 1) + ny * (uint32_t)(e >> 2))];
+            const uint32_t P = A + (uint32_t)(e & 1) + nx * ((uint32_t)((e >> 1) & 1) + ny * (uint32_t)(e >> 2));
+            const float s = sigma[P];
             fin |= (is_finite(s) ? 1u : 0u) << e;
-            inm |= (s > g.iso ? 1u : 0u) << e; // a NaN is not inside
+            bool in = s > g.iso; // a NaN is not inside
+            if (FILTER && in) {
+                const uint32_t l = label[P]; // the root of an inside point: an index < n
+                in = l < n && (size[l] >> 31) != 0u;
+            }
+            inm |= (in ? 1u : 0u) << e;
         }
     }
     uint32_t mask = 0;
@@ -83,6 +94,15 @@ __global__ __launch_bounds__(kB) void k_mesh_classify(const float *__restrict__ 
         tri = tet_triangle_count(inm, tet_mask(1, 2)) + tet_triangle_count(inm, tet_mask(1, 4)) + tet_triangle_count(inm, tet_mask(2, 1)) +
               tet_triangle_count(inm, tet_mask(2, 4)) + tet_triangle_count(inm, tet_mask(4, 1)) + tet_triangle_count(inm, tet_mask(4, 2));
     info[A] = mask | (inm << 8) | (tri << 16);
+}
+
+__global__ __launch_bounds__(kB) void k_mesh_classify(const float *__restrict__ sigma, MeshLattice g, uint32_t n, uint32_t *__restrict__ info) {
+    classify_point<false>(sigma, g, n, info, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(kB) void k_mesh_classify_filtered(const float *__restrict__ sigma, MeshLattice g, uint32_t n, uint32_t *__restrict__ info,
+                                                              const uint32_t *__restrict__ label, const uint32_t *__restrict__ size) {
+    classify_point<true>(sigma, g, n, info, label, size);
 }
 
 // number of set bits over the wave of bit `bit` of v: one ballot, one 64-bit popcount
@@ -325,9 +345,10 @@ MeshWorkspace mesh_workspace_carve(void *base, size_t n_points) {
     return w;
 }
 
-hipError_t launch_mesh_count(const MeshLattice &g, const MeshWorkspace &w, hipStream_t st) {
-    if (w.n_points == 0 || (size_t)g.nx * (size_t)g.ny * (size_t)g.nz != w.n_points || g.nx < 2 || g.ny < 2 || g.nz < 2) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_mesh_classify, dim3(w.n_blocks), dim3(kB), 0, st, w.sigma, g, w.n_points, w.info);
+hipError_t launch_mesh_count(const MeshLattice &g, const MeshWorkspace &w, hipStream_t st, const uint32_t *label, const uint32_t *size) {
+    if (w.n_points == 0 || (size_t)g.nx * (size_t)g.ny * (size_t)g.nz != w.n_points || g.nx < 2 || g.ny < 2 || g.nz < 2 || (!label != !size)) return hipErrorInvalidValue;
+    if (label) hipLaunchKernelGGL(k_mesh_classify_filtered, dim3(w.n_blocks), dim3(kB), 0, st, w.sigma, g, w.n_points, w.info, label, size);
+    else hipLaunchKernelGGL(k_mesh_classify, dim3(w.n_blocks), dim3(kB), 0, st, w.sigma, g, w.n_points, w.info);
     hipLaunchKernelGGL(k_mesh_block_sums, dim3(w.n_blocks), dim3(kB), 0, st, w.info, w.n_points, w.vsum, w.tsum);
     hipLaunchKernelGGL(k_mesh_scan_sums, dim3(1), dim3(kB), 0, st, w.vsum, w.tsum, w.n_blocks, w.totals);
     return hipGetLastError();

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../../include/nerf_mi355x.h"
+#include "components_kernels.h"
 #include "host_util.h"
 #include "isosurface_kernels.h"
 #include "mlp_kernel.h"
@@ -1066,6 +1067,7 @@ void nerf_destroy(nerf_ctx *c) {
     for (float *p : ptrs) if (p) (void)hipFree(p);
     if (c->d_scratch) (void)hipFree(c->d_scratch);
     if (c->d_mesh) (void)hipFree(c->d_mesh);
+    if (c->d_comp) (void)hipFree(c->d_comp);
     if (c->d_clock) (void)hipFree(c->d_clock);
     if (c->d_skip) (void)hipFree(c->d_skip);
     if (c->d_nonfinite) (void)hipFree(c->d_nonfinite);
@@ -1371,12 +1373,24 @@ struct MeshOut { // the caller's arrays (all host or all device pointers), each 
 // sigma lies in the workspace: count, report both counts, and -- if an array is asked for and both counts fit -- emit.  host_out: the arrays are
 // host memory (staged in the context's scratch and copied back; synchronises).  The colours are nerf_forward_batch of network colour_net at the
 // vertices with dirs = -normal, run on the SoA copy the vertex kernel writes.
+// Components (optional): what mesh_components prepared -- the classification then drops the points of discarded components (comp->filtered), and
+// both component counts are read with the mesh's.
+struct MeshComponents {
+    CompWorkspace w;
+    bool filtered;                    // the filter discards something in principle: classify through the keep flags
+    uint64_t *n_components, *n_kept;  // the caller's, optional
+};
+
 static int mesh_extract(nerf_ctx *c, int colour_net, const MeshLattice &g, const MeshWorkspace &w, const MeshOut &o, bool host_out, uint64_t *n_vertices,
-                        uint64_t *n_triangles, hipStream_t st) {
-    HIP_TRY(c, launch_mesh_count(g, w, st));
-    uint32_t totals[2] = {0, 0};
+                        uint64_t *n_triangles, hipStream_t st, const MeshComponents *comp = nullptr) {
+    if (comp && comp->filtered) HIP_TRY(c, launch_mesh_count(g, w, st, comp->w.label, comp->w.size));
+    else HIP_TRY(c, launch_mesh_count(g, w, st));
+    uint32_t totals[2] = {0, 0}, counts[2] = {0, 0};
     HIP_TRY(c, hipMemcpyAsync(totals, w.totals, sizeof totals, hipMemcpyDeviceToHost, st));
+    if (comp) HIP_TRY(c, hipMemcpyAsync(counts, comp->w.counts, sizeof counts, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
+    if (comp && comp->n_components) *comp->n_components = counts[0];
+    if (comp && comp->n_kept) *comp->n_kept = counts[1];
     const size_t nv = totals[0], nt = totals[1];
     *n_vertices = nv; *n_triangles = nt;
     if (!(o.vertices || o.normals || o.rgb || o.triangles) || nv > o.cap_vertices || nt > o.cap_triangles || nv == 0) return NERF_OK;
@@ -1403,31 +1417,154 @@ static int mesh_extract(nerf_ctx *c, int colour_net, const MeshLattice &g, const
     return NERF_OK;
 }
 
-int nerf_isosurface_grid(nerf_ctx *c, const float *sigma, const float lo[3], const float step[3], const int32_t dims[3], float iso, float *vertices,
-                         float *normals, size_t cap_vertices, uint32_t *triangles, size_t cap_triangles, uint64_t *n_vertices, uint64_t *n_triangles) try {
+// ---- lattice components (components_kernels.hip) -----------------------------------------------------------------------------------------------
+static int filter_check(nerf_ctx *c, const nerf_component_filter *f) {
+    if (f && f->keep_largest > (uint32_t)kCompMaxRank) return fail(c, NERF_ERR_INVALID, "filter: keep_largest must be at most 64");
+    return NERF_OK;
+}
+
+// the component workspace for n points (the root list and the rank map borrow the mesh workspace's prefix-sum arrays, idle at this point) and the
+// labelling launches on d_sigma; the mesh workspace must have been ensured by the caller (it may hold sigma already)
+static int components_launch(nerf_ctx *c, const float *d_sigma, const int32_t *dims, float iso, size_t n, uint32_t keep_largest, uint32_t min_points,
+                             uint32_t cap_table, CompWorkspace *out, hipStream_t st) {
+    int rc;
+    if ((rc = ensure_bytes(c, &c->d_comp, &c->comp_bytes, comp_workspace_bytes(n)))) return rc;
+    const MeshWorkspace mw = mesh_workspace_carve(c->d_mesh, n);
+    *out = comp_workspace_carve(c->d_comp, n, mw.vbase, mw.tbase);
+    HIP_TRY(c, launch_components(d_sigma, dims[0], dims[1], dims[2], iso, *out, keep_largest, min_points, cap_table, st));
+    return NERF_OK;
+}
+
+// a filtered mesh call: label the lattice in w.sigma when the filter can discard something or a count is asked for.  *use = whether anything ran.
+static int mesh_components(nerf_ctx *c, const MeshWorkspace &w, const int32_t *dims, float iso, size_t n, const nerf_component_filter *f,
+                           uint64_t *n_components, uint64_t *n_kept, MeshComponents *mc, bool *use, hipStream_t st) {
+    const uint32_t keep_largest = f ? f->keep_largest : 0u, min_points = f ? f->min_points : 0u;
+    mc->filtered = keep_largest != 0 || min_points > 1; // every component has at least one point
+    mc->n_components = n_components; mc->n_kept = n_kept;
+    *use = mc->filtered || n_components || n_kept;
+    if (!*use) return NERF_OK;
+    return components_launch(c, w.sigma, dims, iso, n, keep_largest, min_points, 0, &mc->w, st);
+}
+
+int nerf_isosurface_grid_filtered(nerf_ctx *c, const float *sigma, const float lo[3], const float step[3], const int32_t dims[3], float iso,
+                                  const void *filter, float *vertices, float *normals, size_t cap_vertices, uint32_t *triangles, size_t cap_triangles,
+                                  uint64_t *n_vertices, uint64_t *n_triangles, uint64_t *n_components, uint64_t *n_kept) try {
     size_t n = 0;
     int rc;
+    if ((rc = filter_check(c, (const nerf_component_filter *)filter))) return rc;
     if ((rc = mesh_check(c, false, 0, sigma, lo, step, dims, iso, n_vertices, n_triangles, &n))) return rc;
     DeviceGuard dg(c->device);
     if ((rc = ensure_bytes(c, &c->d_mesh, &c->mesh_bytes, mesh_workspace_bytes(n)))) return rc;
     const MeshWorkspace w = mesh_workspace_carve(c->d_mesh, n);
     HIP_TRY(c, hipMemcpyAsync(w.sigma, sigma, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    MeshComponents mc{};
+    bool use = false;
+    if ((rc = mesh_components(c, w, dims, iso, n, (const nerf_component_filter *)filter, n_components, n_kept, &mc, &use, c->stream))) return rc;
     const MeshOut o{vertices, normals, nullptr, triangles, cap_vertices, cap_triangles};
-    return mesh_extract(c, -1, mesh_lattice(lo, step, dims, iso), w, o, true, n_vertices, n_triangles, c->stream);
+    return mesh_extract(c, -1, mesh_lattice(lo, step, dims, iso), w, o, true, n_vertices, n_triangles, c->stream, use ? &mc : nullptr);
+} NERF_CATCH(c)
+
+int nerf_isosurface_grid(nerf_ctx *c, const float *sigma, const float lo[3], const float step[3], const int32_t dims[3], float iso, float *vertices,
+                         float *normals, size_t cap_vertices, uint32_t *triangles, size_t cap_triangles, uint64_t *n_vertices, uint64_t *n_triangles) {
+    return nerf_isosurface_grid_filtered(c, sigma, lo, step, dims, iso, nullptr, vertices, normals, cap_vertices, triangles, cap_triangles, n_vertices,
+                                         n_triangles, nullptr, nullptr);
+}
+
+// everything nerf_lattice_components* can refuse without a device; *n_points = dims[0] dims[1] dims[2]
+static int components_check(nerf_ctx *c, const void *sigma, const int32_t *dims, float iso, const void *table, size_t cap_table, const uint64_t *n_components,
+                            size_t *n_points) {
+    if (!sigma) return fail(c, NERF_ERR_INVALID, "sigma must not be NULL");
+    if (!dims) return fail(c, NERF_ERR_INVALID, "dims must not be NULL");
+    if (!n_components) return fail(c, NERF_ERR_INVALID, "n_components is required");
+    for (int k = 0; k < 3; ++k)
+        if (dims[k] < 1) return fail(c, NERF_ERR_INVALID, "dims must be positive");
+    if (!std::isfinite(iso)) return fail(c, NERF_ERR_INVALID, "iso must be finite");
+    if (cap_table > (size_t)kCompMaxRank) return fail(c, NERF_ERR_INVALID, "cap_table must be at most 64");
+    if (table && cap_table == 0) return fail(c, NERF_ERR_INVALID, "a table needs cap_table > 0");
+    const size_t limit = std::min((size_t)1 << 28, c ? max_batch_points(c->n_cus) : max_batch_points(0));
+    const unsigned long long plane = (unsigned long long)dims[0] * (unsigned long long)dims[1];
+    if (plane > limit || plane * (unsigned long long)dims[2] > limit)
+        return fail(c, NERF_ERR_INVALID, "lattice too large: dims[0] * dims[1] * dims[2] must be at most 2^28 (and nerf_forward_batch's largest n)");
+    *n_points = (size_t)(plane * (unsigned long long)dims[2]);
+    if (!c) return fail(nullptr, NERF_ERR_INVALID, "ctx is NULL");
+    return NERF_OK;
+}
+
+// labels of d_sigma; labels_out is host (staged through the workspace's own label array) or device memory.  Synchronises st.
+static int lattice_components(nerf_ctx *c, const float *d_sigma, const int32_t *dims, float iso, size_t n, uint32_t *labels_out, bool host_out,
+                              nerf_component *table, size_t cap_table, uint64_t *n_components, hipStream_t st) {
+    static_assert(sizeof(nerf_component) == sizeof(CompEntry) && sizeof(nerf_component) == 32 && sizeof(nerf_component_filter) == 8, "component structs");
+    int rc;
+    CompWorkspace w;
+    const uint32_t cap = table ? (uint32_t)cap_table : 0u;
+    if ((rc = components_launch(c, d_sigma, dims, iso, n, 0, 0, cap, &w, st))) return rc;
+    uint32_t counts[2] = {0, 0};
+    CompEntry entries[kCompMaxRank];
+    HIP_TRY(c, hipMemcpyAsync(counts, w.counts, sizeof counts, hipMemcpyDeviceToHost, st));
+    if (cap) HIP_TRY(c, hipMemcpyAsync(entries, w.table, cap * sizeof(CompEntry), hipMemcpyDeviceToHost, st));
+    if (labels_out) HIP_TRY(c, hipMemcpyAsync(labels_out, w.label, n * sizeof(uint32_t), host_out ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    *n_components = counts[0];
+    const size_t filled = std::min((size_t)cap, (size_t)counts[0]);
+    if (filled) memcpy(table, entries, filled * sizeof(CompEntry));
+    return NERF_OK;
+}
+
+int nerf_lattice_components(nerf_ctx *c, const float *sigma, const int32_t dims[3], float iso, uint32_t *labels_out, void *table, size_t cap_table,
+                            uint64_t *n_components) try {
+    size_t n = 0;
+    int rc;
+    if ((rc = components_check(c, sigma, dims, iso, table, cap_table, n_components, &n))) return rc;
+    DeviceGuard dg(c->device);
+    if ((rc = ensure_bytes(c, &c->d_mesh, &c->mesh_bytes, mesh_workspace_bytes(n)))) return rc;
+    const MeshWorkspace mw = mesh_workspace_carve(c->d_mesh, n);
+    HIP_TRY(c, hipMemcpyAsync(mw.sigma, sigma, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    return lattice_components(c, mw.sigma, dims, iso, n, labels_out, true, (nerf_component *)table, cap_table, n_components, c->stream);
+} NERF_CATCH(c)
+
+int nerf_lattice_components_device(nerf_ctx *c, const float *d_sigma, const int32_t dims[3], float iso, uint32_t *d_labels_out, void *table, size_t cap_table,
+                                   uint64_t *n_components, void *stream) try {
+    size_t n = 0;
+    int rc;
+    if ((rc = components_check(c, d_sigma, dims, iso, table, cap_table, n_components, &n))) return rc;
+    DeviceGuard dg(c->device);
+    if ((rc = ensure_bytes(c, &c->d_mesh, &c->mesh_bytes, mesh_workspace_bytes(n)))) return rc;
+    return lattice_components(c, d_sigma, dims, iso, n, d_labels_out, false, (nerf_component *)table, cap_table, n_components, (hipStream_t)stream);
 } NERF_CATCH(c)
 
 // sigma of network `which` in grid mode into the workspace, then the kernels of nerf_isosurface_grid
 static int extract_mesh(nerf_ctx *c, int which, const float *lo, const float *step, const int32_t *dims, float iso, const MeshOut &o, bool host_out,
-                        uint64_t *n_vertices, uint64_t *n_triangles, hipStream_t st) {
+                        uint64_t *n_vertices, uint64_t *n_triangles, hipStream_t st, const nerf_component_filter *filter = nullptr,
+                        uint64_t *n_components = nullptr, uint64_t *n_kept = nullptr) {
     size_t n = 0;
     int rc;
+    if ((rc = filter_check(c, filter))) return rc;
     if ((rc = mesh_check(c, true, which, nullptr, lo, step, dims, iso, n_vertices, n_triangles, &n))) return rc;
     DeviceGuard dg(c->device);
     if ((rc = ensure_bytes(c, &c->d_mesh, &c->mesh_bytes, mesh_workspace_bytes(n)))) return rc;
     const MeshWorkspace w = mesh_workspace_carve(c->d_mesh, n);
     if ((rc = density_grid_launch(c, which, lo, step, dims, n, w.sigma, 0.0f, nullptr, nullptr, st))) return rc;
-    return mesh_extract(c, which, mesh_lattice(lo, step, dims, iso), w, o, host_out, n_vertices, n_triangles, st);
+    MeshComponents mc{};
+    bool use = false;
+    if ((rc = mesh_components(c, w, dims, iso, n, filter, n_components, n_kept, &mc, &use, st))) return rc;
+    return mesh_extract(c, which, mesh_lattice(lo, step, dims, iso), w, o, host_out, n_vertices, n_triangles, st, use ? &mc : nullptr);
 }
+
+int nerf_extract_mesh_filtered(nerf_ctx *c, int which, const float lo[3], const float step[3], const int32_t dims[3], float iso, const void *filter,
+                               float *vertices, float *normals, float *rgb, size_t cap_vertices, uint32_t *triangles, size_t cap_triangles,
+                               uint64_t *n_vertices, uint64_t *n_triangles, uint64_t *n_components, uint64_t *n_kept) try {
+    const MeshOut o{vertices, normals, rgb, triangles, cap_vertices, cap_triangles};
+    return extract_mesh(c, which, lo, step, dims, iso, o, true, n_vertices, n_triangles, c ? c->stream : nullptr, (const nerf_component_filter *)filter,
+                        n_components, n_kept);
+} NERF_CATCH(c)
+
+int nerf_extract_mesh_filtered_device(nerf_ctx *c, int which, const float lo[3], const float step[3], const int32_t dims[3], float iso, const void *filter,
+                                      float *d_vertices, float *d_normals, float *d_rgb, size_t cap_vertices, uint32_t *d_triangles, size_t cap_triangles,
+                                      uint64_t *n_vertices, uint64_t *n_triangles, uint64_t *n_components, uint64_t *n_kept, void *stream) try {
+    const MeshOut o{d_vertices, d_normals, d_rgb, d_triangles, cap_vertices, cap_triangles};
+    return extract_mesh(c, which, lo, step, dims, iso, o, false, n_vertices, n_triangles, (hipStream_t)stream, (const nerf_component_filter *)filter,
+                        n_components, n_kept);
+} NERF_CATCH(c)
 
 int nerf_extract_mesh(nerf_ctx *c, int which, const float lo[3], const float step[3], const int32_t dims[3], float iso, float *vertices, float *normals,
                       float *rgb, size_t cap_vertices, uint32_t *triangles, size_t cap_triangles, uint64_t *n_vertices, uint64_t *n_triangles) try {

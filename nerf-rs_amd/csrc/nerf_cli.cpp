@@ -9,7 +9,8 @@
 // --density-grid writes the density field on a lattice (nerf_density_grid): raw little-endian f32, x fastest, and / or the occupancy words;
 // with no image output asked for beside it (--out, --depth, --opacity, --rgba) the render is skipped.
 // --mesh writes the level set sigma = --mesh-iso of the same lattice (--density-grid / --grid-lo / --grid-step / --grid-net) as a binary PLY with
-// vertex normals (nerf_extract_mesh: marching tetrahedra on the device, the lattice never reaches the host), --mesh-colour adds vertex colours.
+// vertex normals (nerf_extract_mesh: marching tetrahedra on the device, the lattice never reaches the host), --mesh-colour adds vertex colours,
+// --mesh-keep-largest K / --mesh-min-points M mesh only the K largest connected components of the inside points / those of at least M points.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -27,7 +28,8 @@ static void usage(const char *argv0) {
             "          [--depth FILE.pfm] [--opacity FILE.pfm]\n"
             "          [--rgba FILE.pam [--background R,G,B] [--alpha opaque|premultiplied|straight]]\n"
             "          [--density-grid NX,NY,NZ --grid-lo X,Y,Z --grid-step SX,SY,SZ [--grid-net coarse|fine] [--grid-threshold T]\n"
-            "           [--grid-out FILE.raw] [--grid-occupancy FILE.bits] [--mesh FILE.ply [--mesh-iso V] [--mesh-colour]]]\n"
+            "           [--grid-out FILE.raw] [--grid-occupancy FILE.bits] [--mesh FILE.ply [--mesh-iso V] [--mesh-colour]\n"
+            "            [--mesh-keep-largest K] [--mesh-min-points M]]]\n"
             "           (at least one of the three files; no image flag: no render)\n"
             "defaults: --scene lego_rust --width 256 --height 256 --coarse 64 --fine 128 --out output.ppm --mesh-iso 10\n",
             argv0);
@@ -39,6 +41,7 @@ int main(int argc, char **argv) {
     std::string grid_out, grid_bits_path, mesh_path;
     float mesh_iso = 10.0f;
     bool mesh_colour = false, have_mesh_opt = false;
+    nerf_component_filter mesh_filter = {0, 0}; // --mesh-keep-largest / --mesh-min-points: only the kept components of the inside points are meshed
     int32_t grid_dims[3] = {0, 0, 0};
     float grid_lo[3] = {0.f, 0.f, 0.f}, grid_step[3] = {0.f, 0.f, 0.f}, grid_threshold = 0.0f;
     int grid_net = NERF_NET_FINE;
@@ -93,6 +96,8 @@ int main(int argc, char **argv) {
         else if (a == "--mesh") mesh_path = next();
         else if (a == "--mesh-iso") { mesh_iso = strtof(next(), nullptr); have_mesh_opt = true; }
         else if (a == "--mesh-colour") { mesh_colour = true; have_mesh_opt = true; }
+        else if (a == "--mesh-keep-largest") { mesh_filter.keep_largest = (uint32_t)strtoul(next(), nullptr, 10); have_mesh_opt = true; }
+        else if (a == "--mesh-min-points") { mesh_filter.min_points = (uint32_t)strtoul(next(), nullptr, 10); have_mesh_opt = true; }
         else if (a == "--background") {
             if (sscanf(next(), "%f,%f,%f", &background[0], &background[1], &background[2]) != 3) { usage(argv[0]); return 2; }
             have_background = true;
@@ -123,15 +128,18 @@ int main(int argc, char **argv) {
             return 1;
         }
     if (want_grid && !mesh_path.empty()) { // the level set of the lattice as a mesh: size query, then the fill (the lattice is evaluated twice)
-        uint64_t nv = 0, nt = 0;
-        if (nerf_extract_mesh(ctx, grid_net, grid_lo, grid_step, grid_dims, mesh_iso, nullptr, nullptr, nullptr, 0, nullptr, 0, &nv, &nt)) {
+        uint64_t nv = 0, nt = 0, n_comp = 0, n_kept = 0;
+        const bool filtered = mesh_filter.keep_largest || mesh_filter.min_points;
+        const nerf_component_filter *filter = filtered ? &mesh_filter : nullptr; // no filter: the unfiltered path, no labelling
+        if (nerf_extract_mesh_filtered(ctx, grid_net, grid_lo, grid_step, grid_dims, mesh_iso, filter, nullptr, nullptr, nullptr, 0, nullptr, 0, &nv, &nt,
+                                       filtered ? &n_comp : nullptr, filtered ? &n_kept : nullptr)) {
             fprintf(stderr, "error: %s\n", nerf_last_error(ctx));
             return 1;
         }
         std::vector<float> verts(3 * (size_t)nv), normals(3 * (size_t)nv), colours(mesh_colour ? 3 * (size_t)nv : 0);
         std::vector<uint32_t> tris(3 * (size_t)nt);
-        if (nv && nerf_extract_mesh(ctx, grid_net, grid_lo, grid_step, grid_dims, mesh_iso, verts.data(), normals.data(), mesh_colour ? colours.data() : nullptr,
-                                    (size_t)nv, tris.data(), (size_t)nt, &nv, &nt)) {
+        if (nv && nerf_extract_mesh_filtered(ctx, grid_net, grid_lo, grid_step, grid_dims, mesh_iso, filter, verts.data(), normals.data(),
+                                             mesh_colour ? colours.data() : nullptr, (size_t)nv, tris.data(), (size_t)nt, &nv, &nt, nullptr, nullptr)) {
             fprintf(stderr, "error: %s\n", nerf_last_error(ctx));
             return 1;
         }
@@ -141,6 +149,9 @@ int main(int argc, char **argv) {
         }
         printf("mesh sigma = %g on %d x %d x %d (%s network): %llu vertices, %llu triangles\n", (double)mesh_iso, grid_dims[0], grid_dims[1], grid_dims[2],
                grid_net == NERF_NET_FINE ? "fine" : "coarse", (unsigned long long)nv, (unsigned long long)nt);
+        if (filtered)
+            printf("components of sigma > %g (keep largest %u, at least %u points): %llu components, %llu kept\n", (double)mesh_iso, mesh_filter.keep_largest,
+                   mesh_filter.min_points, (unsigned long long)n_comp, (unsigned long long)n_kept);
         if (grid_out.empty() && grid_bits_path.empty()) {
             if (!want_image) {
                 for (nerf_ctx *c : ctxs) nerf_destroy(c);

@@ -65,6 +65,8 @@ struct nerf_ctx {
     void *d_scratch = nullptr; size_t scratch_bytes = 0;
     // isosurface extraction (isosurface_kernels.h): the per-lattice-point workspace; the mesh itself is staged in d_scratch
     void *d_mesh = nullptr; size_t mesh_bytes = 0;
+    // lattice components (components_kernels.h): labels, sizes / keep flags; allocated only when a filter or a component query is asked for
+    void *d_comp = nullptr; size_t comp_bytes = 0;
     // skip_dead: device queue/counters {u32 ray counter, u32 live count, u64 chunk count} per MLP launch of a render, the
     // compacted trunk outputs of the live samples and their sample indices
     unsigned int *d_seq = nullptr; size_t seq_slots = 0;

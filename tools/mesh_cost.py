@@ -4,6 +4,11 @@ through nerf_extract_mesh_device, with and without vertex colours, beside nerf_d
 build and session.  Device events on the default stream, warm calls (one untimed call per form first: the workspace is allocated there).
 
     python tools/mesh_cost.py [--n 128] [--iso 10] [--launches 7] [--out profiles/mesh_cost.txt]
+    python tools/mesh_cost.py --components [--out profiles/components_cost.txt]     # + the component filter
+
+--components adds: the same extraction with keep_largest = 1 (labelling, ranking and the filtered classification in front of the mesh
+kernels), nerf_lattice_components_device alone on the resident lattice (labels + a table of 16), the component count, the largest
+component's share of the inside points and of the vertices, and the bytes returned.
 
 nerf_extract_mesh_device reads the two counts on the host between the counting and the emitting kernels (one stream synchronisation and an
 8-byte copy), so the interval between the events contains that round trip: it is the cost a caller sees, not a sum of kernel times.
@@ -26,6 +31,7 @@ def main():
     ap.add_argument("--iso", type=float, default=10.0)
     ap.add_argument("--launches", type=int, default=7, help="timed calls per form, after one warm-up (>= 5)")
     ap.add_argument("--out", default=None, help="also write the report to this file")
+    ap.add_argument("--components", action="store_true", help="also time the component filter and the component query")
     args = ap.parse_args()
     assert args.launches >= 5
     import nerf_rs_amd as N
@@ -70,6 +76,29 @@ def main():
         say(f"on top of the sigma launch: counting {t_count - t_grid:+.3f} ms, emitting positions + triangles {t_mesh - t_count:+.3f} ms, normals "
             f"{t_norm - t_mesh:+.3f} ms, colours ({nv} full evaluations of the network) {t_col - t_norm:+.3f} ms")
         say(f"ratio to the sigma launch alone: {t_mesh / t_grid:.4f} (positions + triangles), {t_norm / t_grid:.4f} (+ normals), {t_col / t_grid:.4f} (+ colours)")
+        if args.components:
+            fv, ft, n_comp, n_kept = r.fine.extract_mesh_device(lo, step, dims, args.iso, None, None, None, 0, None, 0, keep_largest=1, return_counts=True)
+            d_lab = hip.malloc(points * 4)
+            comps, n_comp2 = N.lattice_components_device(r, d_sig, dims, args.iso, d_labels=d_lab, table=16)      # d_sig: the timed grid launch's output
+            assert n_comp2 == n_comp and n_kept == min(1, n_comp)
+            inside = r.fine.density_grid_device(lo, step, dims, d_sigma=None, threshold=args.iso, d_bits=d_lab, want_stats=True)[0]
+            say(f"components of sigma > {args.iso:g}: {n_comp} components over {inside} inside points; sizes of the largest "
+                f"{[c.n_points for c in comps[:8]]}; the largest holds {100.0 * comps[0].n_points / max(inside, 1):.2f} % of the inside points, "
+                f"bounds {comps[0].bounds}")
+            say(f"filtered mesh (keep_largest = 1): {fv} vertices ({100.0 * fv / max(nv, 1):.2f} % of {nv}), {ft} triangles ({100.0 * ft / max(nt, 1):.2f} % "
+                f"of {nt}); bytes returned {12 * fv + 12 * ft} (positions + indices) against {12 * nv + 12 * nt} unfiltered; a component query "
+                f"returns 8 + 32 x table bytes (+ 4 N = {4 * points} only if the labels are asked for)")
+            t_filt = timed("nerf_extract_mesh_filtered_device, keep_largest = 1", lambda: r.fine.extract_mesh_device(lo, step, dims, args.iso, d_v, None, None, nv, d_t, nt,
+                                                                                                                   keep_largest=1))
+            t_again = timed("nerf_extract_mesh_device, positions + triangles (again)", lambda: r.fine.extract_mesh_device(lo, step, dims, args.iso, d_v, None, None, nv, d_t, nt))
+            t_cc = timed("nerf_lattice_components_device, table of 16, no labels", lambda: N.lattice_components_device(r, d_sig, dims, args.iso, table=16))
+            t_cc0 = timed("nerf_lattice_components_device, count only", lambda: N.lattice_components_device(r, d_sig, dims, args.iso, table=0))
+            t_cc64 = timed("nerf_lattice_components_device, table of 64, no labels", lambda: N.lattice_components_device(r, d_sig, dims, args.iso, table=64))
+            t_ccl = timed("nerf_lattice_components_device, table of 16 + labels", lambda: N.lattice_components_device(r, d_sig, dims, args.iso, d_labels=d_lab, table=16))
+            say(f"the filter on top of the unfiltered extraction: {t_filt - 0.5 * (t_mesh + t_again):+.3f} ms ({100.0 * (t_filt - 0.5 * (t_mesh + t_again)) / t_grid:.2f} % of the "
+                f"sigma launch); the component query alone: {t_cc:.3f} ms ({100.0 * t_cc / t_grid:.2f} % of the sigma launch), of which the 16 ranking passes, the table "
+                f"and its bounds {t_cc - t_cc0:+.3f} ms (64 passes: {t_cc64 - t_cc0:+.3f} ms); copying the labels {t_ccl - t_cc:+.3f} ms")
+            hip.L.hipFree(d_lab)
         for p in (d_sig, d_v, d_n, d_c, d_t):
             hip.L.hipFree(p)
     if args.out:
