@@ -16,9 +16,11 @@ def oracle_samples(samples, m):
     return dict(samples, camera_origin=list(m[:, 3]), camera_forward=list(-m[:, 2]), camera_up=list(m[:, 1]))
 
 
-def random_scene(root, seed, alpha_bias=(0.02, 0.03), alpha_scale=0.25):
+def random_scene(root, seed, alpha_bias=(0.02, 0.03), alpha_scale=0.25, view_gain=1.0):
     """Two random networks of the reference's architecture in its directory format (He-scaled weights; alpha bias > 0 so that
-    the density field is alive: a fog of varying density instead of a surface -- very different weight statistics from lego)."""
+    the density field is alive: a fog of varying density instead of a surface -- very different weight statistics from lego).
+    view_gain multiplies the rows of both viewdirs kernels that read the encoded direction (256..282): colour then follows the view
+    direction that much more strongly (the probe network of tests/helpers/render_restatement.py).  1.0 writes the files unchanged."""
     rng = np.random.default_rng(seed)
     shapes = [("dense0", 63, 256)] + [(f"dense{i}", 256, 256) for i in range(1, 5)] + [("dense5", 319, 256), ("dense6", 256, 256),
               ("dense7", 256, 256), ("bottleneck", 256, 256), ("viewdirs", 283, 128), ("rgb", 128, 3), ("alpha", 256, 1)]
@@ -32,6 +34,8 @@ def random_scene(root, seed, alpha_bias=(0.02, 0.03), alpha_scale=0.25):
             if name == "alpha":
                 w *= alpha_scale
                 b[:] = a_bias
+            if name == "viewdirs" and view_gain != 1.0:
+                w[256:283] *= np.float32(view_gain)
             w.tofile(d / f"{name}_kernel.bin"); b.tofile(d / f"{name}_bias.bin")
             lines += [f"{name}_kernel {k} {n}", f"{name}_bias {n}"]
         (d / "shapes.txt").write_text("\n".join(lines) + "\n")
