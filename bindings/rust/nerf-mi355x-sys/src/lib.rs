@@ -212,6 +212,17 @@ extern "C" {
     pub fn nerf_render_image_rgba8_device(ctx: *mut nerf_ctx, cam: *const nerf_camera, opts: *const nerf_render_opts,
                                           background: *const f32, alpha_mode: c_int, d_rgba_out: *mut u8, stream: *mut c_void,
                                           stats: *mut nerf_stats) -> c_int;
+    /// Render the caller's rays instead of a camera's: per-ray origins (`n_origins` = 1 or `n_rays`), directions, optional per-ray
+    /// {near, far} `bounds` and RNG indices.  A batch made of a camera's rays carries the bits of `nerf_render_image_aux`.
+    pub fn nerf_render_rays(ctx: *mut nerf_ctx, origins: *const f32, n_origins: usize, dirs: *const f32, n_rays: usize,
+                            normalize: c_int, near: f32, far: f32, bounds: *const f32, rng_index: *const u32,
+                            opts: *const nerf_render_opts, background: *const f32, rgb_out: *mut f32, depth_out: *mut f32,
+                            opacity_out: *mut f32, stats: *mut nerf_stats) -> c_int;
+    pub fn nerf_render_rays_device(ctx: *mut nerf_ctx, d_origins: *const f32, n_origins: usize, d_dirs: *const f32, n_rays: usize,
+                                   normalize: c_int, near: f32, far: f32, d_bounds: *const f32, d_rng_index: *const u32,
+                                   opts: *const nerf_render_opts, background: *const f32, d_rgb_out: *mut f32,
+                                   d_depth_out: *mut f32, d_opacity_out: *mut f32, stream: *mut c_void,
+                                   stats: *mut nerf_stats) -> c_int;
     /// render_image over several GPUs: `ctxs[i]` = one context per device, row bands on per-context host threads + streams,
     /// gathered into `rgb_out` by `gather` (NERF_GATHER_*).  The reference's counterpart is the rayon fan-out, src/lib.rs:533-557.
     pub fn nerf_render_image_multi(ctxs: *const *mut nerf_ctx, n: c_int, cam: *const nerf_camera, opts: *const nerf_render_opts,

@@ -274,6 +274,29 @@ impl Gpu {
         check(self.ctx, unsafe { sys::nerf_render_image_rgba8(self.ctx, cam, opts, bg, alpha as i32, rgba.as_mut_ptr(), &mut stats) })?;
         Ok((rgba, stats))
     }
+
+    /// The caller's rays instead of a camera's (nerf_render_rays): `origins` holds one origin (3 floats) for every ray or one per ray,
+    /// `dirs` n x 3 (normalised on the device when `normalize`), `bounds` optional n x 2 {near, far} (else `near`, `far` for every ray),
+    /// `rng_index` optional n (else ray r draws from index r).  `opts` as for an image, without the pixel-grid and skip options.
+    /// -> (rgb n x 3, depth n, opacity n, stats).
+    #[allow(clippy::too_many_arguments)]
+    pub fn render_rays(&self, origins: &[f32], dirs: &[f32], normalize: bool, near: f32, far: f32, bounds: Option<&[f32]>,
+                       rng_index: Option<&[u32]>, opts: &RenderOpts, background: Option<[f32; 3]>) -> Result<(Vec<f32>, Vec<f32>, Vec<f32>, Stats), Error> {
+        let n = dirs.len() / 3;
+        assert_eq!(dirs.len(), 3 * n, "dirs.len() must be 3 * n_rays");
+        assert!(origins.len() == 3 || origins.len() == 3 * n, "origins must hold one origin or one per ray");
+        assert!(bounds.map_or(true, |b| b.len() == 2 * n), "bounds.len() must be 2 * n_rays");
+        assert!(rng_index.map_or(true, |i| i.len() == n), "rng_index.len() must be n_rays");
+        let (mut rgb, mut depth, mut opacity) = (vec![0f32; 3 * n], vec![0f32; n], vec![0f32; n]);
+        let mut stats = Stats::default();
+        let bg = background.as_ref().map_or(std::ptr::null(), |b| b.as_ptr());
+        check(self.ctx, unsafe {
+            sys::nerf_render_rays(self.ctx, origins.as_ptr(), origins.len() / 3, dirs.as_ptr(), n, normalize as i32, near, far,
+                                  bounds.map_or(std::ptr::null(), |b| b.as_ptr()), rng_index.map_or(std::ptr::null(), |i| i.as_ptr()), opts, bg,
+                                  rgb.as_mut_ptr(), depth.as_mut_ptr(), opacity.as_mut_ptr(), &mut stats)
+        })?;
+        Ok((rgb, depth, opacity, stats))
+    }
 }
 
 impl Drop for Gpu {

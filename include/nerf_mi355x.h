@@ -415,6 +415,58 @@ int nerf_render_image_rgba8(nerf_ctx *ctx, const nerf_camera *cam, const nerf_re
 int nerf_render_image_rgba8_device(nerf_ctx *ctx, const nerf_camera *cam, const nerf_render_opts *opts, const float background[3],
                                    int alpha_mode, uint8_t *d_rgba_out, void *stream, nerf_stats *stats);
 
+/* ---- ray batches: render the caller's rays (per-ray origins, directions and bounds) ----------------------------------------------------
+ * Every other render entry point takes a nerf_camera, a pinhole camera on a pixel grid.  These take the rays themselves -- the `render_rays`
+ * of other NeRF code bases: another lens, rays clipped against the scene box, a picking ray, stereo pairs, a batch of pixels of many poses.
+ * Per ray r, every operation in f32, rounded once, never contracted:
+ *   DIRECTION  d = dirs[r] when normalize == 0 (the caller promises unit length), else dirs[r] / sqrtf(dx*dx + dy*dy + dz*dz), the sum in
+ *              that order, sqrt and division correctly rounded: Vec3::normalize as nerf_stage_ray_dirs applies it.
+ *   BOUNDS     [near_r, far_r] = bounds[r] = {near, far}, or [near_, far_] for every ray when bounds is NULL.
+ *   COARSE     stratified_samples (src/lib.rs:233-248) over [near_r, far_r] with opts->n_coarse samples, in nerf_stage_stratified's
+ *              arithmetic, from Philox stream 0 of (opts->seed, index_r); index_r = rng_index[r], or r when rng_index is NULL.
+ *   POINTS     fl(o_r + fl(d * t)) per coordinate; o_r = origins[r], or origins[0] when n_origins == 1.
+ *   NETWORKS   the coarse network at the coarse points; compute_weights + sample_importance (nerf_stage_resample) from Philox stream 1 of
+ *              the same index, the last interval being far_r - t_last; merge and sort; the fine network at the merged points with d as
+ *              view direction; integrate_ray (last interval: far_r - t_last) over `background` (NULL = white; the arithmetic of
+ *              nerf_render_image_rgba8's NERF_ALPHA_OPAQUE, which with white is nerf_render_image's).
+ *   BRANCHES   those of nerf_render_image: n_fine == 0 or n_coarse < 3 evaluates the fine network on the coarse samples; coarse_only is
+ *              honoured; mlp_dtype selects the arithmetic as there (BF16X3 / F16X2: the sampling pass stays in exact f32).
+ *   MAPS       depth_out[r], opacity_out[r]: exactly nerf_render_image_aux's sums.  Either may be NULL.
+ * CONSEQUENCE  a batch made of a camera's rays -- origins = cam.pos (n_origins = 1), dirs = nerf_stage_ray_dirs of a window, near_ / far_ the
+ *              camera's, rng_index = row * nx + col -- carries the bits of nerf_render_image_aux for that window.  The output of ray r
+ *              depends on ray r's inputs, opts and the weights alone: permuting a batch (rng_index along with it) permutes its outputs;
+ *              n_origins == n_rays with one origin repeated gives the bits of n_origins == 1.
+ * LIMITS       n_rays == 0 is a no-op; n_rays <= INT32_MAX.  The batch runs in passes of at most NERF_MAX_RAYS_PER_PASS rays with
+ *              rays * samples <= 0x3fffffff, like an image; the limit on samples per ray is the image renders'.  Per-ray origins cost a
+ *              workspace of 24 bytes per sample of a pass in the context, grown on demand: a warm call allocates nothing.
+ * FIRST VERSION: the options tied to the pixel grid or to the ray-sequential and list kernels are refused -- NERF_ERR_INVALID when any of
+ *              opts->crop_*, ssaa > 1, band_count > 1, skip_empty, skip_dead, hybrid_sampling, certify_zero is set.  Also NERF_ERR_INVALID:
+ *              a NULL origins / dirs / opts / rgb_out, n_origins outside {1, n_rays}, n_coarse <= 0, n_fine < 0, a bad mlp_dtype, near_ /
+ *              far_ not finite or far_ <= near_ when bounds is NULL, a non-finite background.  All of this is checked before the context
+ *              or the device is needed.
+ * PER-RAY CHECKS (host entry point only): a non-finite origin, direction or bound, a zero direction with normalize, far <= near --
+ *              NERF_ERR_INVALID, the message names the first offending ray ("ray 17: ...").  nerf_render_rays_device cannot look at the
+ *              rays: the outputs of such a ray are unspecified, no other ray is affected.  A ray that misses its volume (far <= near)
+ *              is the caller's to leave out.
+ * FAILURE      nerf_stats.n_nonfinite_points != 0 fails the call with NERF_ERR_STATE as for an image (the host entry point always reads
+ *              the counters, the device one with stats != NULL).  nerf_stats is filled as for an image (n_rays, point counts, ms_*,
+ *              n_passes, n_mlp_launches); nerf_kernel_time_query keeps counting image renders only.
+ * Host pointers, synchronous. */
+int nerf_render_rays(nerf_ctx *ctx, const float *origins /* n_origins x 3 */, size_t n_origins /* 1 or n_rays */,
+                     const float *dirs /* n_rays x 3 */, size_t n_rays, int normalize,
+                     float near_, float far_, const float *bounds /* n_rays x 2 {near, far}, or NULL: near_, far_ for every ray */,
+                     const uint32_t *rng_index /* n_rays, or NULL: ray r draws from index r */,
+                     const nerf_render_opts *opts, const float background[3] /* NULL = white */,
+                     float *rgb_out /* n_rays x 3 */, float *depth_out /* n_rays or NULL */, float *opacity_out /* n_rays or NULL */,
+                     nerf_stats *stats /* may be NULL */);
+/* origins, dirs, bounds, rng_index and the outputs are DEVICE pointers; asynchronous on `stream` (stats != NULL synchronises it before
+ * returning), except that with n_origins == 1 the origin -- which rides in the MLP kernels' arguments -- is read back first: 12 bytes and one
+ * stream synchronisation before the first launch. */
+int nerf_render_rays_device(nerf_ctx *ctx, const float *d_origins, size_t n_origins, const float *d_dirs, size_t n_rays, int normalize,
+                            float near_, float far_, const float *d_bounds, const uint32_t *d_rng_index,
+                            const nerf_render_opts *opts, const float background[3],
+                            float *d_rgb_out, float *d_depth_out, float *d_opacity_out, void *stream, nerf_stats *stats);
+
 /* ---- S3 over several GPUs of one node (reference: the rayon fan-out over blocks + scatter, src/lib.rs:533-557) ------
  * ctxs[i] is one context per device (nerf_create / nerf_create_multi), each with both networks loaded (weights are
  * replicated).  Context i renders band i of n of the output rows (nerf_render_opts.band_*, set here: the caller's values are
@@ -530,7 +582,7 @@ const char *nerf_build_variant(void);
  * nerf_stage_integrate_rgba8, nerf_save_pam, NERF_ALPHA_*, nerf_density_batch, nerf_density_batch_device, nerf_density_grid,
  * nerf_density_grid_device, nerf_isosurface_grid, nerf_extract_mesh, nerf_extract_mesh_device, nerf_save_ply, nerf_component_filter,
  * nerf_component, nerf_lattice_components, nerf_lattice_components_device, nerf_isosurface_grid_filtered, nerf_extract_mesh_filtered,
- * nerf_extract_mesh_filtered_device). */
+ * nerf_extract_mesh_filtered_device, nerf_render_rays, nerf_render_rays_device). */
 int nerf_abi_version(void);
 /* sizeof(nerf_camera), sizeof(nerf_render_opts), sizeof(nerf_stats) as this library was built: lets a binding written in
  * another language (the Rust `-sys` crate, ctypes) check its struct mirrors at start-up. */

@@ -121,6 +121,10 @@ PROTOTYPES = {
                                                  C.POINTER(CStats)]),
     "nerf_render_image_multi_rgba8": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(CCamera), C.POINTER(COpts), C.c_int, f32p, C.c_int,
                                                 u8p, C.POINTER(CStats)]),
+    "nerf_render_rays": (C.c_int, [C.c_void_p, f32p, C.c_size_t, f32p, C.c_size_t, C.c_int, C.c_float, C.c_float, f32p, u32p, C.POINTER(COpts),
+                                   f32p, f32p, f32p, f32p, C.POINTER(CStats)]),
+    "nerf_render_rays_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_float, C.c_void_p,
+                                          C.c_void_p, C.POINTER(COpts), f32p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CStats)]),
     "nerf_create_multi": (C.c_int, [C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p)]),
     "nerf_multi_release": (None, []),
     "nerf_band_rows": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),

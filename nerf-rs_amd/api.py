@@ -593,6 +593,68 @@ def render_image_rgba8(coarse, fine, camera, fine_samples_per_ray=128, *, backgr
     return (out, Stats(st)) if return_stats else out
 
 
+def _ray_opts(n_coarse, fine_samples_per_ray, seed, coarse_only, dtype):
+    return RenderOpts(n_coarse, fine_samples_per_ray, coarse_only, None, 1, seed, dtype).to_c()
+
+
+def render_rays(coarse, fine, origins, dirs, near, far, fine_samples_per_ray=128, *, n_coarse=64, bounds=None, normalize=True,
+                rng_index=None, seed=0, coarse_only=False, dtype="f32", background=None, aux=False, return_stats=False):
+    """The caller's rays instead of a camera's (nerf_render_rays) -> rgb (n, 3) float32.
+
+    origins: (3,) -- one origin for every ray -- or (n, 3); dirs: (n, 3), normalised on the device unless normalize=False (the caller
+    then promises unit length); near, far: the interval every ray samples, unless bounds (n, 2) = (near, far) per ray is given;
+    rng_index: (n,) uint32, the index ray r draws its samples from (None: r) -- a camera's rays with rng_index = row * nx + col give the
+    bits of render_image.  n_coarse + fine_samples_per_ray samples, seed, coarse_only, dtype as in render_image; background: None
+    (white) or (R, G, B).  aux=True: (rgb, depth (n,), opacity (n,)) as render_image(aux=True); the stats follow if return_stats.
+    The per-pixel options of render_image (crop, ssaa, bands, the skip modes) do not exist for rays."""
+    R = coarse.renderer
+    if fine is not None and fine.renderer is not R:
+        raise NerfError(-1, "coarse and fine networks must live in the same Renderer")
+    d = _f32(dirs)
+    if d.ndim != 2 or d.shape[1] != 3:
+        raise NerfError(-1, "dirs must be an (n, 3) array")
+    n = d.shape[0]
+    o = _f32(origins)
+    if o.shape not in ((3,), (n, 3)):
+        raise NerfError(-1, "origins must have shape (3,) or (n, 3)")
+    b = None if bounds is None else _f32(bounds)
+    if b is not None and b.shape != (n, 2):
+        raise NerfError(-1, "bounds must be an (n, 2) array of (near, far)")
+    idx = None if rng_index is None else np.ascontiguousarray(rng_index, dtype=np.uint32)
+    if idx is not None and idx.shape != (n,):
+        raise NerfError(-1, "rng_index must have one entry per ray")
+    opts = _ray_opts(n_coarse, fine_samples_per_ray, seed, coarse_only, dtype)
+    keep, bg = _background(background)
+    rgb = np.empty((n, 3), np.float32)
+    depth, opacity = (np.empty(n, np.float32), np.empty(n, np.float32)) if aux else (None, None)
+    st = CStats()
+    check(R._L.nerf_render_rays(R.handle, _p(o), 1 if o.ndim == 1 else n, _p(d), n, int(bool(normalize)), float(near), float(far),
+                                None if b is None else _p(b), None if idx is None else idx.ctypes.data_as(u32p), C.byref(opts), bg,
+                                _p(rgb), None if depth is None else _p(depth), None if opacity is None else _p(opacity), C.byref(st)), R.handle)
+    out = (rgb, depth, opacity) if aux else (rgb,)
+    if return_stats:
+        out += (Stats(st),)
+    return out if len(out) > 1 else out[0]
+
+
+def render_rays_device(coarse, fine, d_origins, n_origins, d_dirs, n_rays, near, far, fine_samples_per_ray, d_rgb, *, n_coarse=64,
+                       d_bounds=None, normalize=True, d_rng_index=None, seed=0, coarse_only=False, dtype="f32", background=None,
+                       d_depth=None, d_opacity=None, stream=0, return_stats=False):
+    """nerf_render_rays_device: raw device pointers (ints; d_bounds, d_rng_index, d_depth, d_opacity may be None), asynchronous on
+    `stream` (n_origins == 1 reads the origin back first and synchronises the stream once; return_stats synchronises it at the end).
+    n_origins is 1 or n_rays.  Returns None / the stats."""
+    R = coarse.renderer
+    if fine is not None and fine.renderer is not R:
+        raise NerfError(-1, "coarse and fine networks must live in the same Renderer")
+    opts = _ray_opts(n_coarse, fine_samples_per_ray, seed, coarse_only, dtype)
+    keep, bg = _background(background)
+    st = CStats()
+    check(R._L.nerf_render_rays_device(R.handle, d_origins, int(n_origins), d_dirs, int(n_rays), int(bool(normalize)), float(near), float(far),
+                                       d_bounds, d_rng_index, C.byref(opts), bg, d_rgb, d_depth, d_opacity, stream,
+                                       C.byref(st) if return_stats else None), R.handle)
+    return Stats(st) if return_stats else None
+
+
 GATHER_HOST, GATHER_PEER, GATHER_RCCL = 0, 1, 2
 _GATHERS = {"host": 0, "peer": 1, "rccl": 2, 0: 0, 1: 1, 2: 2}
 

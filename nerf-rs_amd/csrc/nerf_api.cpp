@@ -24,6 +24,7 @@
 #include "isosurface_kernels.h"
 #include "mlp_kernel.h"
 #include "mlp_layout.h"
+#include "ray_batch_kernels.h"
 #include "sampling_kernels.h"
 
 using namespace nerfhost;
@@ -844,6 +845,228 @@ int render_once(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *o, 
     return NERF_OK;
 }
 
+
+// ---- ray batches (nerf_render_rays) -------------------------------------------------------------------------------------
+// What the header's contract needs beside render_once: the rays are the caller's, so there is no camera, no window and none of the modes
+// tied to either.  Per pass of at most max_rays_per_pass rays (rays * samples <= 0x3fffffff, as above):
+//     k_batch_prepare -> coarse MLP (sigma) -> resample/sort -> fine MLP -> composite
+// A shared origin runs the image path's MLP_MODE_RAYS launches (the origin rides in the kernel arguments); per-ray origins expand every
+// pass's samples into points + per-sample directions (k_batch_points, 24 B per sample in c->d_batch) for MLP_MODE_POINTS, which forms
+// nothing itself and then runs the same per-column arithmetic: the two paths carry the same bits.
+struct RayBatch {
+    const float *h_origin;     // n_origins == 1: the shared origin (HOST, 3 floats); else NULL
+    const float *d_origins;    // n_origins == n_rays: n_rays x 3 (device); else NULL
+    const float *d_dirs;       // n_rays x 3 (device)
+    size_t n_rays;
+    int normalize;
+    float near_, far_;
+    const float *d_bounds;     // n_rays x 2 (device) or NULL
+    const uint32_t *d_rng;     // n_rays (device) or NULL
+};
+
+// everything nerf_render_rays* can refuse without a context or a device, in the header's order
+int check_ray_batch(nerf_ctx *c, const void *origins, size_t n_origins, const void *dirs, size_t n_rays, float near_, float far_, const void *bounds,
+                    const nerf_render_opts *o, const float *background, const void *rgb_out) {
+    if (!o) return fail(c, NERF_ERR_INVALID, "opts is NULL");
+    if (n_rays > (size_t)0x7fffffff) return fail(c, NERF_ERR_INVALID, "n_rays must be at most INT32_MAX");
+    if (n_rays > 0 && (!origins || !dirs || !rgb_out)) return fail(c, NERF_ERR_INVALID, "origins, dirs and rgb_out must not be NULL");
+    if (n_origins != 1 && n_origins != n_rays) return fail(c, NERF_ERR_INVALID, "n_origins must be 1 (one origin for every ray) or n_rays");
+    if (o->crop_x0 || o->crop_y0 || o->crop_w || o->crop_h) return fail(c, NERF_ERR_INVALID, "ray batches have no pixel grid: crop_* must be 0");
+    if (o->ssaa > 1) return fail(c, NERF_ERR_INVALID, "ray batches have no pixel grid: ssaa must be 0 or 1");
+    if (o->band_count > 1) return fail(c, NERF_ERR_INVALID, "ray batches have no rows: band_count must be 0 or 1");
+    if (o->skip_empty || o->skip_dead || o->hybrid_sampling || o->certify_zero)
+        return fail(c, NERF_ERR_INVALID, "skip_empty, skip_dead, hybrid_sampling and certify_zero are not available for ray batches (first version)");
+    if (o->n_coarse <= 0) return fail(c, NERF_ERR_INVALID, "coarse samples per ray must be greater than 0");
+    if (o->n_fine < 0) return fail(c, NERF_ERR_INVALID, "fine samples per ray must be >= 0");
+    if (!valid_dtype(o->mlp_dtype)) return fail(c, NERF_ERR_INVALID, "mlp_dtype must be NERF_MLP_F32, NERF_MLP_BF16, NERF_MLP_BF16X3 or NERF_MLP_F16X2");
+    if (!bounds) {
+        if (!std::isfinite(near_) || !std::isfinite(far_)) return fail(c, NERF_ERR_INVALID, "near_ and far_ must be finite when bounds is NULL");
+        if (!(far_ > near_)) return fail(c, NERF_ERR_INVALID, "far_ must be greater than near_ when bounds is NULL");
+    }
+    if (background && !(std::isfinite(background[0]) && std::isfinite(background[1]) && std::isfinite(background[2])))
+        return fail(c, NERF_ERR_INVALID, "background components must be finite");
+    const int nc = o->n_coarse, nf = (o->coarse_only || o->n_fine == 0 || nc < 3) ? 0 : o->n_fine;
+    if ((long long)nc + nf > 0x3fffffff || composite_lds_bytes(nc + nf) > 160 * 1024 || (nf > 0 && resample_lds_bytes(nc, nf) > 160 * 1024))
+        return fail(c, NERF_ERR_INVALID, "too many samples per ray for the sampling / compositing kernels (one ray per wave in LDS)");
+    return NERF_OK;
+}
+
+// the host entry point's per-ray checks: the first offending ray is named
+int check_ray_batch_rays(nerf_ctx *c, const float *origins, size_t n_origins, const float *dirs, size_t n_rays, int normalize, const float *bounds) {
+    char msg[160];
+    auto finite3 = [](const float *v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); };
+    for (size_t r = 0; r < n_rays; ++r) {
+        const char *what = nullptr;
+        const float *d = dirs + 3 * r;
+        if (r < n_origins && !finite3(origins + 3 * r)) what = "its origin is not finite";
+        else if (!finite3(d)) what = "its direction is not finite";
+        else if (normalize && d[0] == 0.0f && d[1] == 0.0f && d[2] == 0.0f) what = "its direction is zero and cannot be normalised";
+        else if (bounds && !(std::isfinite(bounds[2 * r]) && std::isfinite(bounds[2 * r + 1]))) what = "its bounds are not finite";
+        else if (bounds && !(bounds[2 * r + 1] > bounds[2 * r])) what = "its far is not greater than its near";
+        if (what) {
+            snprintf(msg, sizeof msg, "ray %zu: %s", r, what);
+            return fail(c, NERF_ERR_INVALID, msg);
+        }
+    }
+    return NERF_OK;
+}
+
+// arguments already checked (check_ray_batch); asynchronous on st unless stats != NULL
+int render_rays_device(nerf_ctx *c, const RayBatch &b, const nerf_render_opts *o, const float *background, float *d_out, float *d_depth,
+                       float *d_opacity, hipStream_t st, nerf_stats *stats) {
+    int rc;
+    const int dtype = o->mlp_dtype;
+    const int dtype_coarse = (split_dtype(dtype) && !o->coarse_only) ? NERF_MLP_F32 : dtype; // as render_once: the sampling pass stays in exact f32
+    if (!c->net[NERF_NET_COARSE].loaded) return fail(c, NERF_ERR_STATE, "coarse network not loaded");
+    if (!o->coarse_only && !c->net[NERF_NET_FINE].loaded) return fail(c, NERF_ERR_STATE, "fine network not loaded");
+    if (dtype == NERF_MLP_F16X2 && !c->net[o->coarse_only ? NERF_NET_COARSE : NERF_NET_FINE].wstream_x2)
+        return fail(c, NERF_ERR_STATE, "NERF_MLP_F16X2 is unavailable for this network: a weight exceeds the f16 range");
+    const int nc = o->n_coarse;
+    const int nf = (o->coarse_only || o->n_fine == 0 || nc < 3) ? 0 : o->n_fine; // the sample-count branches of render_once
+    const int M = nc + nf;
+    const size_t pass_cap = std::max<size_t>(1, std::min<size_t>(c->max_rays_per_pass, (size_t)0x3fffffff / (size_t)M));
+    const size_t pass_rays = std::min(b.n_rays, pass_cap);
+    if ((rc = ensure_workspace(c, pass_rays, nc, M, o->coarse_only != 0))) return rc;
+    // c->d_batch (floats): [far per ray, padded to 64][points 3 x n SoA][directions n x 3 AoS], n = the pass's rays x M
+    const bool expand = b.d_origins != nullptr;
+    const size_t far_floats = b.d_bounds ? (pass_rays + 63) / 64 * 64 : 0, n_max = pass_rays * (size_t)M;
+    float *d_far = nullptr, *d_pts = nullptr, *d_daos = nullptr;
+    if (far_floats || expand) {
+        if ((rc = ensure_bytes(c, &c->d_batch, &c->batch_bytes, (far_floats + (expand ? 6 * n_max : 0)) * sizeof(float)))) return rc;
+        d_far = b.d_bounds ? (float *)c->d_batch : nullptr;
+        d_pts = (float *)c->d_batch + far_floats; d_daos = d_pts + 3 * n_max;
+    }
+    // events: all owned by last_render (kind 5, not 1, for the colour-producing network: c->dominant and with it nerf_kernel_time_query
+    // belong to image renders)
+    recycle_render(c);
+    const bool watch_range = c->d_nonfinite && (split_dtype(dtype) || split_dtype(dtype_coarse));
+    if (watch_range) HIP_TRY(c, hipMemsetAsync(c->d_nonfinite, 0, sizeof(unsigned int), st));
+    const bool timing = true;
+    const DevNet &NC = c->net[NERF_NET_COARSE], &NF = c->net[NERF_NET_FINE];
+    uint32_t passes = 0;
+    for (size_t r0 = 0; r0 < b.n_rays; r0 += pass_cap, ++passes) {
+        const int n_rays = (int)std::min(pass_cap, b.n_rays - r0);
+        const float *far_per_ray = d_far;
+        const float *origins = expand ? b.d_origins + 3 * r0 : nullptr;
+        {
+            BatchPrepareArgs p{};
+            p.n_rays = n_rays; p.first_ray = (uint32_t)r0; p.dirs = b.d_dirs + 3 * r0; p.normalize = b.normalize;
+            p.bounds = b.d_bounds ? b.d_bounds + 2 * r0 : nullptr; p.rng_index = b.d_rng ? b.d_rng + r0 : nullptr;
+            p.near_ = b.near_; p.far_ = b.far_; p.count = nc; p.seed_lo = (uint32_t)o->seed; p.seed_hi = (uint32_t)(o->seed >> 32);
+            p.dirs_out = c->d_dirs; p.t_out = c->d_tc; p.far_out = d_far;
+            Timed t(c, st, 2, 0, timing);
+            HIP_TRY(c, launch_batch_prepare(p, st));
+            t.done(c->last_render);
+        }
+        MlpArgs a{};
+        a.ray_dirs = c->d_dirs;
+        if (expand) a.mode = MLP_MODE_POINTS;
+        else { a.mode = MLP_MODE_RAYS; a.origin[0] = b.h_origin[0]; a.origin[1] = b.h_origin[1]; a.origin[2] = b.h_origin[2]; }
+        // per-ray origins: the points and per-sample directions of the launch that follows (a.n_points, a.t, a.samples_per_ray are set)
+        auto expand_points = [&]() -> int {
+            if (!expand) return NERF_OK;
+            BatchPointsArgs q{};
+            q.n_rays = n_rays; q.spr = a.samples_per_ray; q.origins = origins; q.dirs = c->d_dirs; q.t = a.t;
+            q.pts_soa = d_pts; q.dirs_aos = d_daos;
+            a.pts_soa = d_pts; a.dirs_aos = d_daos;
+            Timed t(c, st, 2, 0, timing);
+            HIP_TRY(c, launch_batch_points(q, st));
+            t.done(c->last_render);
+            return NERF_OK;
+        };
+        a.wstream = stream_of(NC, dtype_coarse); a.small_params = small_of(NC, dtype_coarse);
+        a.n_points = n_rays * nc; a.samples_per_ray = nc; a.t = c->d_tc;
+        a.sigma_out = c->d_sc; a.rgb_out = o->coarse_only ? c->d_rgbc : nullptr;
+        a.nonfinite = split_dtype(dtype_coarse) ? c->d_nonfinite : nullptr;
+        // only the f32 kernel has a sigma-only points mode: a bf16 sampling pass over expanded points runs the full kernel (the same
+        // densities) and leaves its colours in the fine pass's buffer, which that pass overwrites
+        bool full_coarse = o->coarse_only != 0;
+        if (expand && !full_coarse && dtype_coarse != NERF_MLP_F32) { full_coarse = true; a.rgb_out = c->d_rgbf; }
+        if ((rc = expand_points())) return rc;
+        {
+            Timed t(c, st, o->coarse_only ? 5 : 0, (uint64_t)a.n_points, timing);
+            HIP_TRY(c, launch_mlp(c, dtype_coarse, a, full_coarse, st));
+            t.done(c->last_render);
+        }
+        CompositeArgs ca{};
+        ca.n_rays = n_rays; ca.far_ = b.far_; ca.far_per_ray = far_per_ray; ca.out = d_out + 3 * r0;
+        ca.depth = d_depth ? d_depth + r0 : nullptr; ca.opacity = d_opacity ? d_opacity + r0 : nullptr;
+        if (background) { ca.use_bg = 1; ca.bg[0] = background[0]; ca.bg[1] = background[1]; ca.bg[2] = background[2]; }
+        if (o->coarse_only) {
+            ca.n = nc; ca.t = c->d_tc; ca.sigma = c->d_sc; ca.rgb = c->d_rgbc;
+            Timed t(c, st, 2, 0, timing);
+            HIP_TRY(c, launch_composite(ca, st));
+            t.done(c->last_render);
+            continue;
+        }
+        const float *t_fine = c->d_tc;
+        if (nf > 0) {
+            ResampleArgs ra{};
+            ra.n_rays = n_rays; ra.nc = nc; ra.nf = nf; ra.far_ = b.far_; ra.far_per_ray = far_per_ray;
+            ra.seed_lo = (uint32_t)o->seed; ra.seed_hi = (uint32_t)(o->seed >> 32);
+            ra.t_coarse = c->d_tc; ra.sigma_coarse = c->d_sc; ra.t_fine = c->d_tf;
+            // the index of Philox stream 1: the caller's, or the ray's number in the batch -- a one-row rectangle that starts at column r0
+            ra.pixel_index = b.d_rng ? b.d_rng + r0 : nullptr;
+            ra.g.n_rays = n_rays; ra.g.rx0 = (int)r0; ra.g.ry0 = 0; ra.g.rw = n_rays; ra.g.rnx = n_rays; ra.g.rny = 1;
+            Timed t(c, st, 2, 0, timing);
+            HIP_TRY(c, launch_resample(ra, st));
+            t.done(c->last_render);
+            t_fine = c->d_tf;
+        }
+        a.wstream = stream_of(NF, dtype); a.small_params = small_of(NF, dtype);
+        a.n_points = n_rays * M; a.samples_per_ray = M; a.t = t_fine;
+        a.sigma_out = c->d_sf; a.rgb_out = c->d_rgbf;
+        a.nonfinite = split_dtype(dtype) ? c->d_nonfinite : nullptr;
+        if ((rc = expand_points())) return rc;
+        {
+            Timed t(c, st, 5, (uint64_t)a.n_points, timing);
+            HIP_TRY(c, launch_mlp(c, dtype, a, true, st));
+            t.done(c->last_render);
+        }
+        ca.n = M; ca.t = t_fine; ca.sigma = c->d_sf; ca.rgb = c->d_rgbf;
+        Timed t(c, st, 2, 0, timing);
+        HIP_TRY(c, launch_composite(ca, st));
+        t.done(c->last_render);
+    }
+    if (stats) {
+        HIP_TRY(c, hipStreamSynchronize(st));
+        memset(stats, 0, sizeof *stats);
+        stats->n_rays = b.n_rays;
+        stats->n_passes = passes;
+        stats->n_coarse_points = stats->n_rays * (uint64_t)nc;
+        stats->n_fine_points = o->coarse_only ? 0 : stats->n_rays * (uint64_t)M;
+        for (const auto &p : c->last_render) {
+            float ms = 0.f;
+            HIP_TRY(c, hipEventElapsedTime(&ms, p.a, p.b));
+            if (p.kind == 0) { stats->ms_coarse_mlp += ms; stats->n_mlp_launches++; }
+            else if (p.kind == 5) {
+                stats->n_mlp_launches++;
+                if (o->coarse_only) stats->ms_coarse_mlp += ms; else stats->ms_fine_mlp += ms;
+            } else stats->ms_other += ms;
+        }
+        if (!c->last_render.empty()) {
+            float ms = 0.f;
+            HIP_TRY(c, hipEventElapsedTime(&ms, c->last_render.front().a, c->last_render.back().b));
+            stats->ms_total = ms;
+        }
+        if (watch_range) {
+            unsigned int bad = 0;
+            HIP_TRY(c, hipMemcpy(&bad, c->d_nonfinite, sizeof bad, hipMemcpyDeviceToHost));
+            stats->n_nonfinite_points = bad;
+        }
+        stats->n_exec_coarse_trunk = stats->n_coarse_points;
+        stats->n_exec_fine_trunk = stats->n_fine_points;
+        stats->n_exec_colour = o->coarse_only ? stats->n_coarse_points : stats->n_fine_points;
+        if (stats->n_nonfinite_points) { // as an image render: never returned as a success
+            char msg[320];
+            snprintf(msg, sizeof msg, "%llu evaluations: an operand left the range of the split arithmetic (NERF_MLP_F16X2: |activation| <= 65504) or a "
+                     "density was not finite; the batch is not usable -- use NERF_MLP_BF16X3 or NERF_MLP_F32", (unsigned long long)stats->n_nonfinite_points);
+            return fail(c, NERF_ERR_STATE, msg);
+        }
+    }
+    return NERF_OK;
+}
+
 } // namespace
 
 // certify_zero frames are AUDITED (k_cert_audit: 1 in 16 of the samples certified by less than twice the margin and 1 in 128 of the others are evaluated exactly all the same).  A frame stands only if no
@@ -1067,6 +1290,7 @@ void nerf_destroy(nerf_ctx *c) {
     for (float *p : ptrs) if (p) (void)hipFree(p);
     if (c->d_scratch) (void)hipFree(c->d_scratch);
     if (c->d_mesh) (void)hipFree(c->d_mesh);
+    if (c->d_batch) (void)hipFree(c->d_batch);
     if (c->d_comp) (void)hipFree(c->d_comp);
     if (c->d_clock) (void)hipFree(c->d_clock);
     if (c->d_skip) (void)hipFree(c->d_skip);
@@ -1639,6 +1863,56 @@ int nerf_render_image_rgba8(nerf_ctx *c, const nerf_camera *cam, const nerf_rend
     nerf_stats local; // a synchronous render always reads its counters (see nerf_render_image_aux)
     if ((rc = render_rgba8_device(c, cam, opts, background, alpha_mode, (uint8_t *)c->d_out, c->stream, stats ? stats : &local))) return rc;
     HIP_TRY(c, hipMemcpyAsync(rgba_out, c->d_out, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return NERF_OK;
+} NERF_CATCH(c)
+
+// ---- ray batches ---------------------------------------------------------------------------------------------------------------------
+int nerf_render_rays_device(nerf_ctx *c, const float *d_origins, size_t n_origins, const float *d_dirs, size_t n_rays, int normalize, float near_,
+                            float far_, const float *d_bounds, const uint32_t *d_rng_index, const nerf_render_opts *opts, const float background[3],
+                            float *d_rgb_out, float *d_depth_out, float *d_opacity_out, void *stream, nerf_stats *stats) try {
+    int rc;
+    if ((rc = check_ray_batch(c, d_origins, n_origins, d_dirs, n_rays, near_, far_, d_bounds, opts, background, d_rgb_out))) return rc;
+    if (!c) return fail(nullptr, NERF_ERR_INVALID, "ctx is NULL");
+    if (n_rays == 0) return NERF_OK;
+    DeviceGuard dg(c->device);
+    const hipStream_t st = (hipStream_t)stream;
+    RayBatch b{nullptr, nullptr, d_dirs, n_rays, normalize ? 1 : 0, near_, far_, d_bounds, d_rng_index};
+    float origin[3];
+    if (n_origins == 1) { // the shared origin rides in the MLP kernels' arguments: 12 bytes come back first
+        HIP_TRY(c, hipMemcpyAsync(origin, d_origins, sizeof origin, hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipStreamSynchronize(st));
+        b.h_origin = origin;
+    } else b.d_origins = d_origins;
+    return render_rays_device(c, b, opts, background, d_rgb_out, d_depth_out, d_opacity_out, st, stats);
+} NERF_CATCH(c)
+
+int nerf_render_rays(nerf_ctx *c, const float *origins, size_t n_origins, const float *dirs, size_t n_rays, int normalize, float near_, float far_,
+                     const float *bounds, const uint32_t *rng_index, const nerf_render_opts *opts, const float background[3], float *rgb_out,
+                     float *depth_out, float *opacity_out, nerf_stats *stats) try {
+    int rc;
+    if ((rc = check_ray_batch(c, origins, n_origins, dirs, n_rays, near_, far_, bounds, opts, background, rgb_out))) return rc;
+    if ((rc = check_ray_batch_rays(c, origins, n_origins, dirs, n_rays, normalize, bounds))) return rc;
+    if (!c) return fail(nullptr, NERF_ERR_INVALID, "ctx is NULL");
+    if (n_rays == 0) return NERF_OK;
+    DeviceGuard dg(c->device);
+    // staging (floats): dirs, [origins], [bounds], [rng_index], rgb, [depth], [opacity]
+    const size_t R = n_rays, o_d = 0, o_o = o_d + 3 * R, o_b = o_o + (n_origins == 1 ? 0 : 3 * R), o_i = o_b + (bounds ? 2 * R : 0),
+                 o_c = o_i + (rng_index ? R : 0), o_z = o_c + 3 * R, o_a = o_z + (depth_out ? R : 0), total = o_a + (opacity_out ? R : 0);
+    if ((rc = ensure_bytes(c, (void **)&c->d_out, &c->out_floats, total * sizeof(float)))) return rc;
+    float *d = c->d_out;
+    HIP_TRY(c, hipMemcpyAsync(d + o_d, dirs, 3 * R * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (n_origins != 1) HIP_TRY(c, hipMemcpyAsync(d + o_o, origins, 3 * R * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (bounds) HIP_TRY(c, hipMemcpyAsync(d + o_b, bounds, 2 * R * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (rng_index) HIP_TRY(c, hipMemcpyAsync(d + o_i, rng_index, R * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    RayBatch b{n_origins == 1 ? origins : nullptr, n_origins == 1 ? nullptr : d + o_o, d + o_d, n_rays, normalize ? 1 : 0, near_, far_,
+               bounds ? d + o_b : nullptr, rng_index ? (const uint32_t *)(d + o_i) : nullptr};
+    nerf_stats local; // a synchronous render always reads its counters (see nerf_render_image_aux)
+    if ((rc = render_rays_device(c, b, opts, background, d + o_c, depth_out ? d + o_z : nullptr, opacity_out ? d + o_a : nullptr, c->stream,
+                                 stats ? stats : &local))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(rgb_out, d + o_c, 3 * R * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (depth_out) HIP_TRY(c, hipMemcpyAsync(depth_out, d + o_z, R * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (opacity_out) HIP_TRY(c, hipMemcpyAsync(opacity_out, d + o_a, R * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return NERF_OK;
 } NERF_CATCH(c)

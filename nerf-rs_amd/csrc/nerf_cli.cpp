@@ -11,6 +11,9 @@
 // --mesh writes the level set sigma = --mesh-iso of the same lattice (--density-grid / --grid-lo / --grid-step / --grid-net) as a binary PLY with
 // vertex normals (nerf_extract_mesh: marching tetrahedra on the device, the lattice never reaches the host), --mesh-colour adds vertex colours,
 // --mesh-keep-largest K / --mesh-min-points M mesh only the K largest connected components of the inside points / those of at least M points.
+// --rays FILE renders the caller's rays (nerf_render_rays): n x 6 little-endian f32 {origin, direction} (directions are normalised on the device),
+// near / far from the scene JSON unless --rays-bounds FILE gives n x 2 {near, far}; --rays-out FILE receives n x 3 f32 linear RGB (over --background).
+// --coarse / --fine / --seed / --dtype / --coarse-only apply; with no image flag beside it the render is skipped.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -31,6 +34,7 @@ static void usage(const char *argv0) {
             "           [--grid-out FILE.raw] [--grid-occupancy FILE.bits] [--mesh FILE.ply [--mesh-iso V] [--mesh-colour]\n"
             "            [--mesh-keep-largest K] [--mesh-min-points M]]]\n"
             "           (at least one of the three files; no image flag: no render)\n"
+            "          [--rays FILE.f32 --rays-out FILE.f32 [--rays-bounds FILE.f32]]   (n x 6 f32 in, n x 3 f32 out; no image flag: no render)\n"
             "defaults: --scene lego_rust --width 256 --height 256 --coarse 64 --fine 128 --out output.ppm --mesh-iso 10\n",
             argv0);
 }
@@ -38,7 +42,7 @@ static void usage(const char *argv0) {
 int main(int argc, char **argv) {
     std::string scene = getenv("NERF_SCENE_DIR") ? getenv("NERF_SCENE_DIR") : "lego_rust";
     std::string out = "output.ppm", depth_path, opacity_path, rgba_path;
-    std::string grid_out, grid_bits_path, mesh_path;
+    std::string grid_out, grid_bits_path, mesh_path, rays_path, rays_out_path, rays_bounds_path;
     float mesh_iso = 10.0f;
     bool mesh_colour = false, have_mesh_opt = false;
     nerf_component_filter mesh_filter = {0, 0}; // --mesh-keep-largest / --mesh-min-points: only the kept components of the inside points are meshed
@@ -94,6 +98,9 @@ int main(int argc, char **argv) {
         else if (a == "--grid-out") grid_out = next();
         else if (a == "--grid-occupancy") grid_bits_path = next();
         else if (a == "--mesh") mesh_path = next();
+        else if (a == "--rays") rays_path = next();
+        else if (a == "--rays-out") rays_out_path = next();
+        else if (a == "--rays-bounds") rays_bounds_path = next();
         else if (a == "--mesh-iso") { mesh_iso = strtof(next(), nullptr); have_mesh_opt = true; }
         else if (a == "--mesh-colour") { mesh_colour = true; have_mesh_opt = true; }
         else if (a == "--mesh-keep-largest") { mesh_filter.keep_largest = (uint32_t)strtoul(next(), nullptr, 10); have_mesh_opt = true; }
@@ -115,6 +122,7 @@ int main(int argc, char **argv) {
     if (want_grid && (!have_grid_lo || !have_grid_step || (grid_out.empty() && grid_bits_path.empty() && mesh_path.empty()))) { usage(argv[0]); return 2; }
     if (!want_grid && (have_grid_lo || have_grid_step || !grid_out.empty() || !grid_bits_path.empty() || !mesh_path.empty())) { usage(argv[0]); return 2; }
     if (mesh_path.empty() && have_mesh_opt) { usage(argv[0]); return 2; }
+    if (rays_path.empty() != rays_out_path.empty() || (rays_path.empty() && !rays_bounds_path.empty())) { usage(argv[0]); return 2; }
 
     // one context per GPU (--gpus N: devices 0..N-1, the rayon fan-out of src/lib.rs:533-550 becomes a fan-out over devices)
     if (gpus < 1) { usage(argv[0]); return 2; }
@@ -127,6 +135,45 @@ int main(int argc, char **argv) {
             fprintf(stderr, "error: %s\n", nerf_last_error(c));
             return 1;
         }
+    if (!rays_path.empty()) { // the caller's rays on the first context
+        auto slurp = [](const std::string &path, std::vector<float> &v) { // the host is little-endian: the bytes as they are
+            FILE *f = fopen(path.c_str(), "rb");
+            if (!f) return false;
+            bool ok = fseek(f, 0, SEEK_END) == 0;
+            const long bytes = ok ? ftell(f) : -1;
+            ok = ok && bytes >= 0 && bytes % (long)sizeof(float) == 0 && fseek(f, 0, SEEK_SET) == 0;
+            if (ok) { v.resize((size_t)bytes / sizeof(float)); ok = fread(v.data(), 1, (size_t)bytes, f) == (size_t)bytes; }
+            fclose(f);
+            return ok;
+        };
+        std::vector<float> rays, ray_bounds;
+        if (!slurp(rays_path, rays) || rays.size() % 6 != 0) { fprintf(stderr, "error: %s must hold n x 6 f32 (origin, direction)\n", rays_path.c_str()); return 1; }
+        const size_t n = rays.size() / 6;
+        if (!rays_bounds_path.empty() && (!slurp(rays_bounds_path, ray_bounds) || ray_bounds.size() != 2 * n)) {
+            fprintf(stderr, "error: %s must hold n x 2 f32 (near, far), one pair per ray of %s\n", rays_bounds_path.c_str(), rays_path.c_str());
+            return 1;
+        }
+        nerf_camera jc; // near and far of the scene
+        if (nerf_camera_from_json((scene + "/tf_reference_samples.json").c_str(), width, height, &jc)) { fprintf(stderr, "error: %s\n", nerf_last_error(nullptr)); return 1; }
+        std::vector<float> o(3 * n), d(3 * n), rgb(3 * n);
+        for (size_t r = 0; r < n; ++r)
+            for (int k = 0; k < 3; ++k) { o[3 * r + k] = rays[6 * r + k]; d[3 * r + k] = rays[6 * r + 3 + k]; }
+        nerf_stats rst;
+        if (nerf_render_rays(ctx, o.data(), n, d.data(), n, 1, jc.near_, jc.far_, ray_bounds.empty() ? nullptr : ray_bounds.data(), nullptr, &opts,
+                             have_background ? background : nullptr, rgb.data(), nullptr, nullptr, &rst)) {
+            fprintf(stderr, "error: %s\n", nerf_last_error(ctx));
+            return 1;
+        }
+        FILE *f = fopen(rays_out_path.c_str(), "wb");
+        const bool ok = f && fwrite(rgb.data(), sizeof(float), rgb.size(), f) == rgb.size();
+        if ((f && fclose(f)) || !ok) { fprintf(stderr, "error: cannot write %s\n", rays_out_path.c_str()); return 1; }
+        printf("%zu rays (%d coarse + %d fine samples): device %.2f ms in %u pass(es)\n", n, opts.n_coarse, opts.coarse_only ? 0 : opts.n_fine, n ? rst.ms_total : 0.0,
+               n ? rst.n_passes : 0u);
+        if (!want_image && !want_grid) {
+            for (nerf_ctx *c : ctxs) nerf_destroy(c);
+            return 0;
+        }
+    }
     if (want_grid && !mesh_path.empty()) { // the level set of the lattice as a mesh: size query, then the fill (the lattice is evaluated twice)
         uint64_t nv = 0, nt = 0, n_comp = 0, n_kept = 0;
         const bool filtered = mesh_filter.keep_largest || mesh_filter.min_points;

@@ -40,7 +40,7 @@ constexpr float kCertMarginCoarseF16 = 0.25f, kCertMarginFineF16 = 0.5f;
 
 struct EvPair {
     hipEvent_t a, b;
-    int kind; // 0 coarse mlp, 1 fine mlp (dominant), 2 other
+    int kind; // 0 coarse mlp, 1 fine mlp (dominant), 2 other, 4 colour head of skip_dead, 5 the colour-producing mlp of a ray batch (not in `dominant`)
     uint64_t points;
 };
 
@@ -61,6 +61,8 @@ struct nerf_ctx {
     float *d_rayaux = nullptr; size_t rayaux_bytes = 0; // SSAA ray-level depth + opacity maps (nerf_render_image_aux)
     float *d_out = nullptr; size_t out_floats = 0;       // host-pointer render output staging
     float *d_pack = nullptr; size_t pack_bytes = 0;      // RGBA8 renders: the f32 frame [+ opacity plane] the pack kernel reads (a host-pointer call stages the packed words in d_out)
+    // ray batches with per-ray origins / bounds (nerf_render_rays): per pass {far per ray, points 3 x n SoA, directions n x 3 AoS}
+    void *d_batch = nullptr; size_t batch_bytes = 0;
     // scratch for forward_batch / stage calls
     void *d_scratch = nullptr; size_t scratch_bytes = 0;
     // isosurface extraction (isosurface_kernels.h): the per-lattice-point workspace; the mesh itself is staged in d_scratch

@@ -43,6 +43,8 @@ struct ResampleArgs {
     // ... and, in a second launch, resample only the rays of a list (n_rays = capacity of the launch; the count lives on the device)
     const unsigned int *ray_list = nullptr;
     const unsigned int *ray_list_count = nullptr;
+    // ray batches (appended: the fields above keep their offsets): n_rays floats, ray r's last interval ends at far_per_ray[r]; NULL = far_
+    const float *far_per_ray = nullptr;
 };
 
 struct CompositeArgs {
@@ -59,6 +61,8 @@ struct CompositeArgs {
     // instead of the reference's white
     int use_bg;
     float bg[3];
+    // ray batches (appended likewise): n_rays floats, ray r's last interval ends at far_per_ray[r]; NULL = far_
+    const float *far_per_ray;
 };
 
 hipError_t sampling_init(void);

@@ -14,25 +14,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "philox.hip.h"
 #include "sampling_kernels.h"
 
 namespace {
-
-// Philox-4x32-10, key = seed, counter = (pixel_index, stream, k/4, 0); same stream as the CPU oracle.
-__device__ __forceinline__ void philox4x32(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, uint32_t c2,
-                                           uint32_t c3, uint32_t (&out)[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-        c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
-__device__ __forceinline__ float u01(uint32_t x) { return (float)(x >> 9) * (1.0f / 8388608.0f); }
 
 // Intra-wave LDS hand-off: LDS instructions of one wave execute in issue order, so a compiler-level fence
 // (no instruction at wavefront scope) plus a scheduling barrier is all that is needed.
@@ -137,10 +122,11 @@ __global__ __launch_bounds__(256) void k_resample(ResampleArgs a) {
     float *t = lds_f + (size_t)wv * (7 * nc + a.sort_pow2);
     float *sg = t + nc, *alpha = sg + nc, *w = alpha + nc, *cdf = w + nc, *bins = cdf + nc, *Tn = bins + nc, *mg = Tn + nc;
     const bool flagging = a.flag_list || a.flag_out; // hybrid sampling's first launch (and its stage hook): wave-uniform
+    const float far_ = a.far_per_ray ? a.far_per_ray[ray] : a.far_; // ray batches: every ray ends at its own far
 
     for (int i = lane; i < nc; i += 64) { t[i] = a.t_coarse[(size_t)ray * nc + i]; sg[i] = a.sigma_coarse[(size_t)ray * nc + i]; }
     wave_sync();
-    for (int i = lane; i < nc; i += 64) alpha[i] = sample_alpha(t, sg, i, nc, a.far_);
+    for (int i = lane; i < nc; i += 64) alpha[i] = sample_alpha(t, sg, i, nc, far_);
     wave_sync();
     const bool near_cut = weights_scan(alpha, w, nc, lane, flagging ? Tn : nullptr);
     wave_sync();
@@ -188,7 +174,7 @@ __global__ __launch_bounds__(256) void k_resample(ResampleArgs a) {
             const int i = base + lane;
             float v = 0.0f;
             if (i < nc) {
-                float delta = (i + 1 < nc) ? t[i + 1] - t[i] : a.far_ - t[i];
+                float delta = (i + 1 < nc) ? t[i + 1] - t[i] : far_ - t[i];
                 if (delta < 0.0f) delta = 0.0f;
                 const float s_i = sg[i];
                 const bool behind_cut = i > 0 && Tn[i - 1] < 1e-4f;
@@ -327,6 +313,8 @@ __global__ __launch_bounds__(64) void k_composite(CompositeArgs a) {
     float dep = 0.0f;                           // kAux only
     bool cut = false;                           // compute_weights' early break (src/lib.rs:273-279): later weights are 0
     float t_cur = 0.0f;
+    const int er = my_ray < a.n_rays ? my_ray : a.n_rays - 1;
+    const float far_ = a.far_per_ray ? a.far_per_ray[er] : a.far_; // ray batches: every ray ends at its own far
     for (int c0 = 0; c0 < n; c0 += kCompChunk) {
         const int cs = n - c0 < kCompChunk ? n - c0 : kCompChunk;
         // stage: t[c0 .. c0+cs] (one extra: the next sample's t closes the last interval), sigma, rgb.  All loads are issued
@@ -345,8 +333,7 @@ __global__ __launch_bounds__(64) void k_composite(CompositeArgs a) {
                 vc[k][q] = a.rgb[3 * base + (e < 3 * cs ? e : 3 * cs - 1)];
             }
         }
-        int er = my_ray < a.n_rays ? my_ray : a.n_rays - 1;
-        const float t_ext = (c0 + cs < n) ? a.t[(size_t)er * n + c0 + cs] : a.far_; // last interval ends at far (:180)
+        const float t_ext = (c0 + cs < n) ? a.t[(size_t)er * n + c0 + cs] : far_; // last interval ends at far (:180)
 #pragma unroll
         for (int k = 0; k < 16; ++k) {
             const int rr = 4 * k + rq;
