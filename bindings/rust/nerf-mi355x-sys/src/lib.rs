@@ -139,6 +139,7 @@ extern "C" {
                                        small_cap: usize, wstream_len: *mut usize, small_len: *mut usize) -> c_int;
     pub fn nerf_debug_fold_network_dir(dir: *const c_char, wstream: *mut f32, wstream_cap: usize, small: *mut f32,
                                        small_cap: usize, wstream_len: *mut usize, small_len: *mut usize) -> c_int;
+    pub fn nerf_debug_zero_skip_network_dir(dir: *const c_char, eligible: *mut c_int) -> c_int;
     pub fn nerf_debug_split_bf16x3(values: *const f32, n: usize, parts: *mut u16) -> c_int;
     pub fn nerf_debug_split_f16x2(values: *const f32, n: usize, parts: *mut u16) -> c_int;
     pub fn nerf_debug_certify_policy(margin: f32, audited: u64, violations: u64, headroom: f32, max_error: f32, new_margin: *mut f32) -> c_int;

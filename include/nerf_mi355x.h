@@ -168,6 +168,12 @@ typedef struct {
 } nerf_stats;
 
 /* ---- lifecycle ------------------------------------------------------------------------------------------ */
+/* Environment read by nerf_create (per context; networks loaded into it afterwards follow it):
+ *   NERF_ZERO_STEP_SKIP=0   the NERF_MLP_F32 kernels execute every MFMA k-step.  Default (unset or non-zero): a k-step of a 256-wide layer
+ *                           whose ReLU'd inputs are zero for all 32 points of a wave is skipped -- exactly fma(a, 0, c) = c, so every output
+ *                           keeps its bits; a network with a non-finite parameter runs with the skip off on its own.
+ *   NERF_DEBUG_ZSKIP=1      diagnostic: every f32 MLP launch synchronises and prints its executed / total ReLU k-steps to stderr.
+ *   NERF_DEBUG_CLOCK=1      diagnostic: nerf_debug_shader_clock_mhz. */
 int nerf_create(int device_id, nerf_ctx **out);
 void nerf_destroy(nerf_ctx *ctx);
 /* Message of the last failing call on ctx (or of the last failing context-free call when ctx == NULL). */
@@ -203,6 +209,10 @@ int nerf_debug_pack_network_dir(const char *dir, float *wstream, size_t wstream_
  * kChunksFullFolded); the small block differs in the viewdirs bias only.  Same calling convention as above.  Host-only. */
 int nerf_debug_fold_network_dir(const char *dir, float *wstream, size_t wstream_cap, float *small, size_t small_cap,
                                 size_t *wstream_len, size_t *small_len);
+/* Diagnostic: what the loaders decide for zero-step skipping of the NERF_MLP_F32 kernels (see NERF_ZERO_STEP_SKIP at nerf_create): *eligible = 1 iff
+ * every value of the folded image of this weight directory is finite.  Host-only: it reports the loaders' predicate, not a context; what a
+ * context did with a loaded network shows in NERF_DEBUG_ZSKIP's counters (executed == total: every k-step was executed). */
+int nerf_debug_zero_skip_network_dir(const char *dir, int *eligible);
 /* Diagnostic: the three bf16 parts (raw bit patterns) the NERF_MLP_BF16X3 packer stores for each of n f32 weights:
  * parts[3 i + k], k = 0..2, with v = p0 + p1 + p2 up to 2^-27 |v|.  Host-only. */
 int nerf_debug_split_bf16x3(const float *values, size_t n, uint16_t *parts /* 3 n */);

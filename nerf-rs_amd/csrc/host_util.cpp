@@ -219,6 +219,16 @@ bool fold_network(const std::vector<float> &ws, const std::vector<float> &sm, st
     return fws.size() == (size_t)kChunksFullFolded * kChunkFloats;
 }
 
+bool zero_skip_safe(const std::vector<float> &ws, const std::vector<float> &sm) {
+    for (const std::vector<float> *v : {&ws, &sm})
+        for (float x : *v) {
+            uint32_t u;
+            memcpy(&u, &x, 4);
+            if ((u & 0x7f800000u) == 0x7f800000u) return false; // inf or NaN
+        }
+    return true;
+}
+
 // ---- bf16 stream -------------------------------------------------------------------------------
 uint16_t f32_to_bf16_rne(float v) {
     uint32_t u;

@@ -36,6 +36,9 @@ void pack_network(const HostNet &net, std::vector<float> &wstream, std::vector<f
 // formed from pack_network's output with fp64 accumulation.  false if the input does not have the packed image's sizes.
 bool fold_network(const std::vector<float> &wstream, const std::vector<float> &small, std::vector<float> &folded_wstream,
                   std::vector<float> &folded_small);
+// true iff every value of an f32 device image (stream + small block) is finite: the condition under which the f32 kernels may skip
+// k-steps whose ReLU inputs are all zero (fma(a, 0, c) = c needs a finite a; a NaN bias must take the dense path's quieting too)
+bool zero_skip_safe(const std::vector<float> &wstream, const std::vector<float> &small);
 // bf16 weight stream of mlp_kernel_bf16.hip (round-to-nearest-even); the small-parameter block is shared with fp32.
 void pack_network_bf16(const HostNet &net, std::vector<uint16_t> &wstream);
 uint16_t f32_to_bf16_rne(float v);

@@ -67,7 +67,28 @@ struct Pipe {
     const char *cur_src;     // wave-uniform: this wave's quarter of the chunk being DMA'd
     uint32_t cur_dst;        // its LDS destination
     uint32_t lane16;
+    // zero-step skipping (tile_steps<*, true>): wave-uniform, all three live in SGPRs
+    uint64_t zs_off;         // ORed into every liveness mask: 0 = skip dead k-steps, all-ones = execute every k-step (MlpArgs.zero_skip == 0)
+    // Diagnostic counters (MlpArgs.zskip_stats).  They are ALWAYS kept, in timed runs too: one s_add per executed k-step (next to its
+    // 8 or 4 MFMAs) and one per tile_steps call, which is part of every measured figure; only the atomics at kernel exit are switched.
+    uint32_t zs_exec;        // ReLU k-steps this wave executed ...
+    uint32_t zs_total;       // ... of this many
 };
+
+__device__ __forceinline__ void pipe_zskip_init(Pipe &P, int zero_skip) {
+    P.zs_off = zero_skip ? 0ull : ~0ull;
+    P.zs_exec = 0;
+    P.zs_total = 0;
+}
+
+// one atomic pair per wave at kernel exit (stats = {executed, total} ReLU k-steps; NULL unless the diagnostic is switched on -- the
+// per-wave sums in Pipe are kept either way)
+__device__ __forceinline__ void pipe_zskip_report(const Pipe &P, unsigned long long *stats, int lane) {
+    if (stats && lane == 0) {
+        atomicAdd(stats, (unsigned long long)P.zs_exec);
+        atomicAdd(stats + 1, (unsigned long long)P.zs_total);
+    }
+}
 
 // Select the next chunk: its stream offset and ring slot (kept opaque so the 145 values are not constant-folded
 // into 145 live address registers).
@@ -186,6 +207,30 @@ __device__ __forceinline__ void pipe_advance(Pipe &P, int ms, f32x4 &a0, f32x4 &
 // ---- one input tile (16 k-steps) of a layer with NT output tiles --------------------------------
 // Every input tile starts on a chunk boundary (16 macro-steps for NT=8, 8 for NT=4), so the mid-chunk
 // sync lands on macro-step 4 of every chunk.
+//
+// Zero-step skipping (RELU tiles).  A k-step multiplies NT weight tiles by ONE B register: two hidden units (one per lane half) across
+// the wave's 32 points.  About three quarters of all ReLU outputs are zero; when all 64 lane values of the register are, the step
+// computes fma(a, +0, c) for every accumulator element, and a wave-uniform branch goes round its MFMAs.  The liveness masks are
+// ballots of `bits != 0` taken AFTER the integer-max ReLU in the same VALU burst that prepares the B operands (-0, negative values
+// and sign-bit NaNs are +0 there, as they are for the MFMA; +NaN and +inf are live); they stay in SGPRs, and a k-step pays one
+// scalar compare and one branch.  Only MFMAs are skipped: the LDS reads (pipe_advance), the DMA pieces (pipe_mid_step) and the
+// waitcnt + s_barrier (pipe_sync) run on both paths in the same order and number -- a wave that skips still reaches every barrier
+// and feeds its quarter of every chunk.
+// Exactness: fma(a, 0, c) = c for every FINITE a, except that c = -0 stays -0 where the dense path gives -0 + +0 = +0.  The host
+// switches the skip off for a network with a non-finite parameter (host_util.cpp zero_skip_safe), and every MFMA accumulator of
+// these kernels is consumed through the integer-max relu() alone, which maps both zeros to +0: the hidden layers' B operands
+// above, alpha_pre() (hence sigma AND the audited raw pre-activation of list mode), rgb_channel() for the V tiles, and the
+// ray-sequential kernel's staged h8 tiles (relu'd in colour_pass).  Results are bit-identical to the dense path.
+// Liveness of one ReLU'd B register: the lanes whose value is not +0, compared as an integer.  The empty asm pins the ReLU'd value in
+// its VGPR here, inside the B-operand burst: without it hipcc compares the raw value instead and sinks the v_max into the k-step's
+// branch, i.e. back between the MFMAs.
+__device__ __forceinline__ uint64_t relu_live(float &b) {
+    int bits = __builtin_bit_cast(int, b);
+    asm volatile("" : "+v"(bits));
+    b = __builtin_bit_cast(float, bits);
+    return __builtin_amdgcn_ballot_w64(bits != 0);
+}
+
 template <int NT, bool RELU>
 __device__ __forceinline__ void tile_steps(const f32x16 &in, f32x16 (&out)[NT], Pipe &P) {
     static_assert(NT == 8 || NT == 4, "NT");
@@ -193,7 +238,9 @@ __device__ __forceinline__ void tile_steps(const f32x16 &in, f32x16 (&out)[NT], 
     // the B operands of G consecutive k-steps are prepared in one burst (G more live VGPRs).
     constexpr int G = RELU ? NERF_RELU_GROUP : 1;
     float bq[G];
+    if constexpr (RELU) P.zs_total += 16;
     if constexpr (NT == 8) {
+        uint64_t live[G];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             f32x4 a0, a1;
@@ -202,18 +249,35 @@ __device__ __forceinline__ void tile_steps(const f32x16 &in, f32x16 (&out)[NT], 
             if (r % G == 0) {
 #pragma unroll
                 for (int g = 0; g < G; ++g) bq[g] = RELU ? relu(in[r + g]) : in[r + g];
+                if constexpr (RELU) {
+#pragma unroll
+                    for (int g = 0; g < G; ++g) live[g] = relu_live(bq[g]) | P.zs_off;
+                }
                 if (G > 1) __builtin_amdgcn_sched_barrier(0);
             }
             const float b = bq[r % G];
-            out[0] = MFMA(a0[0], b, out[0]); out[1] = MFMA(a0[1], b, out[1]);
-            pipe_mid_step(P, r & 7);
-            out[2] = MFMA(a0[2], b, out[2]); out[3] = MFMA(a0[3], b, out[3]);
-            out[4] = MFMA(a1[0], b, out[4]); out[5] = MFMA(a1[1], b, out[5]);
-            out[6] = MFMA(a1[2], b, out[6]); out[7] = MFMA(a1[3], b, out[7]);
+            if constexpr (RELU) {
+                // the DMA piece goes in front of the branch (behind the previous k-step's MFMAs), so that it is outside the skipped region
+                pipe_mid_step(P, r & 7);
+                if (live[r % G] != 0) {
+                    ++P.zs_exec;
+                    out[0] = MFMA(a0[0], b, out[0]); out[1] = MFMA(a0[1], b, out[1]);
+                    out[2] = MFMA(a0[2], b, out[2]); out[3] = MFMA(a0[3], b, out[3]);
+                    out[4] = MFMA(a1[0], b, out[4]); out[5] = MFMA(a1[1], b, out[5]);
+                    out[6] = MFMA(a1[2], b, out[6]); out[7] = MFMA(a1[3], b, out[7]);
+                }
+            } else {
+                out[0] = MFMA(a0[0], b, out[0]); out[1] = MFMA(a0[1], b, out[1]);
+                pipe_mid_step(P, r & 7);
+                out[2] = MFMA(a0[2], b, out[2]); out[3] = MFMA(a0[3], b, out[3]);
+                out[4] = MFMA(a1[0], b, out[4]); out[5] = MFMA(a1[1], b, out[5]);
+                out[6] = MFMA(a1[2], b, out[6]); out[7] = MFMA(a1[3], b, out[7]);
+            }
         }
     } else {
         constexpr int G2 = G < 2 ? 2 : G;
         float bq2[G2];
+        uint64_t live[G2];
 #pragma unroll
         for (int r = 0; r < 16; r += 2) {
             f32x4 a0, a1;
@@ -222,14 +286,25 @@ __device__ __forceinline__ void tile_steps(const f32x16 &in, f32x16 (&out)[NT], 
             if (r % G2 == 0) {
 #pragma unroll
                 for (int g = 0; g < G2; ++g) bq2[g] = RELU ? relu(in[r + g]) : in[r + g];
+                if constexpr (RELU) {
+#pragma unroll
+                    for (int g = 0; g < G2; ++g) live[g] = relu_live(bq2[g]) | P.zs_off;
+                }
                 if (G2 > 2) __builtin_amdgcn_sched_barrier(0);
             }
             const float b0 = bq2[r % G2], b1 = bq2[r % G2 + 1];
-            out[0] = MFMA(a0[0], b0, out[0]); out[1] = MFMA(a0[1], b0, out[1]);
+            // a macro-step of the 4-tile layer holds two k-steps: one branch each, the DMA piece between them on both paths
+            if (!RELU || live[r % G2] != 0) {
+                if constexpr (RELU) ++P.zs_exec;
+                out[0] = MFMA(a0[0], b0, out[0]); out[1] = MFMA(a0[1], b0, out[1]);
+                out[2] = MFMA(a0[2], b0, out[2]); out[3] = MFMA(a0[3], b0, out[3]);
+            }
             pipe_mid_step(P, r / 2);
-            out[2] = MFMA(a0[2], b0, out[2]); out[3] = MFMA(a0[3], b0, out[3]);
-            out[0] = MFMA(a1[0], b1, out[0]); out[1] = MFMA(a1[1], b1, out[1]);
-            out[2] = MFMA(a1[2], b1, out[2]); out[3] = MFMA(a1[3], b1, out[3]);
+            if (!RELU || live[r % G2 + 1] != 0) {
+                if constexpr (RELU) ++P.zs_exec;
+                out[0] = MFMA(a1[0], b1, out[0]); out[1] = MFMA(a1[1], b1, out[1]);
+                out[2] = MFMA(a1[2], b1, out[2]); out[3] = MFMA(a1[3], b1, out[3]);
+            }
         }
     }
 #if NERF_PIN_CHAINS

@@ -43,6 +43,10 @@ struct MlpArgs {
     // every one of them written by the launch, the bits behind the last cell 0
     float occ_threshold;
     unsigned int *occ_bits;
+    // f32 kernels (appended likewise): skip the MFMAs of k-steps whose ReLU'd B register is zero on all 64 lanes (mlp_f32_core.hip.h
+    // tile_steps; bit-identical for a network whose parameters are all finite -- DevNet.zero_skip).  0: every k-step is executed.
+    int zero_skip;
+    unsigned long long *zskip_stats; // optional diagnostic (NERF_DEBUG_ZSKIP): {executed, total} ReLU k-steps of the launch, printed to stderr
 };
 
 // Sets the dynamic-LDS attribute of every kernel instantiation on the current device.
@@ -50,6 +54,9 @@ hipError_t nerf_mlp_init();
 // full=false evaluates dense0..7 + alpha only (sigma); n_blocks = persistent workgroups (<= #CUs).  Sigma-only MLP_MODE_POINTS
 // (nerf_density_batch) never reads dirs_aos; MLP_MODE_GRID exists sigma-only.
 hipError_t nerf_mlp_launch(const MlpArgs &a, bool full, int n_blocks, hipStream_t stream);
+// the zero-step diagnostic around a launch of an f32 kernel (no-ops when stats == NULL): clear the counters / read, synchronise and print them
+hipError_t nerf_zskip_clear(unsigned long long *stats, hipStream_t stream);
+hipError_t nerf_zskip_print(const char *what, unsigned long long *stats, hipStream_t stream);
 // bf16-operand variant (mlp_kernel_bf16v2.hip): a.wstream is the output-tile-major stream (mlp_layout.h kChunks*Bf16V2)
 hipError_t nerf_mlp_bf16v2_init();
 hipError_t nerf_mlp_bf16v2_launch(const MlpArgs &a, bool full, int n_blocks, hipStream_t stream);
@@ -109,6 +116,8 @@ struct SeqArgs {
     // predicted cut always falls inside the evaluated samples).  The caller fills sigma_out with NaN (0xFF bytes): "not evaluated".
     int prefilter;
     float prefilter_cut_T;
+    int zero_skip;                   // f32 trunk: as MlpArgs.zero_skip (appended: the fields above keep their kernarg offsets)
+    unsigned long long *zskip_stats; // as MlpArgs.zskip_stats
 };
 struct ColourArgs {
     const float *wstream;      // the same stream (bottleneck + viewdirs part is used)

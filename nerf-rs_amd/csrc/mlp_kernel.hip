@@ -16,9 +16,12 @@
 //   * alpha (N=1) and rgb (N=3) heads run on the VALU from the register-resident activations.
 //   * the bottleneck layer (no activation, src/network.rs:218) is folded into the viewdirs layer on the host, once per loaded
 //     network (host_util.cpp fold_network): the colour head is relu(h7) -> viewdirs' -> rgb.
-// Per 32-point wave tile: 8256 MFMAs (full; 9280 before the fold) / 7680 (sigma only) x 64 cycles.
+//   * k-steps of the 256-wide layers whose ReLU'd B register is zero on all 64 lanes are skipped, exactly (mlp_f32_core.hip.h
+//     tile_steps; MlpArgs.zero_skip).
+// Per 32-point wave tile: at most 8256 MFMAs (full; 9280 before the fold) / 7680 (sigma only) x 64 cycles.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
 
 #include "mlp_f32_core.hip.h"
 #include "mlp_kernel.h"
@@ -55,6 +58,7 @@ __global__ __launch_bounds__(256, 1) void nerf_mlp_kernel(const MlpArgs A) {
     P.next_off = 0;
     P.stream_bytes = (FULL ? kChunksFullFolded : kChunksSigma) * kChunkBytes;
     P.gbase = (const char *)A.wstream + wave * 4096;
+    pipe_zskip_init(P, A.zero_skip);
     __syncthreads();
 #pragma unroll
     for (int c = 0; c < kRingSlots - 1; ++c) pipe_issue(P);
@@ -165,16 +169,39 @@ __global__ __launch_bounds__(256, 1) void nerf_mlp_kernel(const MlpArgs A) {
     }
     // drain the (unused) prefetches before the LDS allocation is released
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    pipe_zskip_report(P, A.zskip_stats, lane);
     if (A.clock_out && tid == 0) { // diagnostic: shader clock = d(memtime) / d(memrealtime) x 100 MHz
         A.clock_out[2 * blockIdx.x] = __builtin_amdgcn_s_memtime() - clk0;
         A.clock_out[2 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime() - rt0;
     }
 }
 
+// NERF_DEBUG_ZSKIP: the {executed, total} ReLU k-step counters of one launch.  Cleared in front of it, read (synchronising) and printed
+// behind it -- the clear, the atomics and the synchronising read are a diagnostic, never on in timed runs (the kernels keep their
+// per-wave sums in scalar registers regardless: mlp_f32_core.hip.h Pipe).
+hipError_t nerf_zskip_clear(unsigned long long *stats, hipStream_t stream) {
+    return stats ? hipMemsetAsync(stats, 0, 2 * sizeof(unsigned long long), stream) : hipSuccess;
+}
+hipError_t nerf_zskip_print(const char *what, unsigned long long *stats, hipStream_t stream) {
+    if (!stats) return hipSuccess;
+    unsigned long long h[2] = {0, 0};
+    hipError_t e = hipMemcpyAsync(h, stats, sizeof h, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e == hipSuccess) fprintf(stderr, "nerf zskip: %s relu_ksteps_executed=%llu relu_ksteps_total=%llu\n", what, h[0], h[1]);
+    return e;
+}
+
 template <bool FULL, int MODE>
 static hipError_t launch_t(const MlpArgs &a, int n_blocks, hipStream_t stream) {
+    hipError_t e = nerf_zskip_clear(a.zskip_stats, stream);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL((nerf_mlp_kernel<FULL, MODE>), dim3(n_blocks), dim3(256), kLdsBytes, stream, a);
-    return hipGetLastError();
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    static const char *const modes[4] = {"points", "rays", "list", "grid"};
+    char what[48];
+    snprintf(what, sizeof what, "nerf_mlp_kernel<%s,%s>", FULL ? "full" : "sigma", modes[MODE]);
+    return nerf_zskip_print(what, a.zskip_stats, stream);
 }
 
 hipError_t nerf_mlp_init() {

@@ -285,6 +285,7 @@ __global__ __launch_bounds__(256, 1) void nerf_trunk_seq_kernel(const SeqArgs A)
     const char *colour_gbase = trunk_gbase + (size_t)kChunksSigma * kChunkBytes;
     Pipe P;
     pipe_start(P, lds, lane * 16, wave, (const char *)A.wstream, kChunksSigma);
+    pipe_zskip_init(P, A.zero_skip); // the trunk's ReLU k-steps (tile_steps); the colour passes have their own loop and stay dense
 
     Stage S;
     S.tiles = (LDS_AS char *)smem + kStageOff;
@@ -415,6 +416,7 @@ __global__ __launch_bounds__(256, 1) void nerf_trunk_seq_kernel(const SeqArgs A)
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // drain the unused DMA prefetches before the LDS allocation is released
     work_done(W, A, lane);
+    pipe_zskip_report(P, A.zskip_stats, lane);
 #if NERF_SEQ_DIAG_STAMP
     if (EXPORT && A.stats && wave == 0 && lane == 0) { // the next launch slot's counters: {u32 head, u32 live = passes, u64 = cycles}
         atomicAdd(A.stats + 2, diag_cycles);
@@ -440,7 +442,11 @@ hipError_t nerf_trunk_seq_launch(const SeqArgs &a, bool export_live, int n_block
     if (a.n_rays <= 0 || a.samples_per_ray <= 0) return hipSuccess;
     n_blocks = trunk_blocks(a, n_blocks);
     if (export_live && !a.rgb_out) return hipErrorInvalidValue;
+    hipError_t e = nerf_zskip_clear(a.zskip_stats, stream);
+    if (e != hipSuccess) return e;
     if (export_live) hipLaunchKernelGGL(nerf_trunk_seq_kernel<true>, dim3(n_blocks), dim3(256), kSeqLdsBytes, stream, a);
     else hipLaunchKernelGGL(nerf_trunk_seq_kernel<false>, dim3(n_blocks), dim3(256), kLdsBytes, stream, a);
-    return hipGetLastError();
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return nerf_zskip_print(export_live ? "nerf_trunk_seq_kernel<export>" : "nerf_trunk_seq_kernel<sigma>", a.zskip_stats, stream);
 }

@@ -118,6 +118,9 @@ static const float *stream_of(const DevNet &n, int dtype) {
 }
 // the small block that goes with stream_of: the f32 kernels read the folded image, every other arithmetic the packed one
 static const float *small_of(const DevNet &n, int dtype) { return dtype == NERF_MLP_F32 ? n.small_f32 : n.small; }
+// zero-step skipping of the f32 kernels (MlpArgs / SeqArgs; the other arithmetics ignore the two fields): per network, decided at load
+template <class Args>
+static void zskip_of(const nerf_ctx *c, const DevNet &n, Args &a) { a.zero_skip = n.zero_skip ? 1 : 0; a.zskip_stats = c->d_zskip; }
 // NERF_V2_F16_FULL (experiment, variant builds): NERF_MLP_BF16 renders run the f16 twin of the bf16 kernel (fused ray-mode launches only)
 static hipError_t launch_mlp(const nerf_ctx *c, int dtype, const MlpArgs &a, bool full, hipStream_t st) {
 #ifdef NERF_V2_F16_FULL
@@ -321,6 +324,7 @@ int upload_packed(nerf_ctx *c, int which, const std::vector<float> &ws, const st
     HIP_TRY(c, hipMemcpy(d.small, sm.data(), sm.size() * sizeof(float), hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemcpy(d.small_f32, fsm.data(), fsm.size() * sizeof(float), hipMemcpyHostToDevice));
     d.loaded = true;
+    d.zero_skip = c->zero_step_skip && zero_skip_safe(fws, fsm); // exact only while every parameter is finite (mlp_f32_core.hip.h tile_steps)
     c->cert_margin[which] = c->cert_margin_floor[which]; // certify_zero calibrates itself per network (upload_bf16_family, which follows, decides the pre-filter)
     return NERF_OK;
 }
@@ -556,7 +560,7 @@ int render_once(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *o, 
             HIP_TRY(c, hipMemsetAsync(sigma_out, 0, (size_t)n_rays * spr * sizeof(float), st)); // samples behind the cut stay 0
             if (rgb_out) HIP_TRY(c, hipMemsetAsync(rgb_out, 0, (size_t)n_rays * spr * 3 * sizeof(float), st)); // weight-0 samples: 0 * 0
             SeqArgs q{};
-            q.wstream = stream_of(net, dt); q.small_params = small_of(net, dt); q.n_rays = n_rays; q.samples_per_ray = spr;
+            q.wstream = stream_of(net, dt); q.small_params = small_of(net, dt); zskip_of(c, net, q); q.n_rays = n_rays; q.samples_per_ray = spr;
             q.ray_dirs = c->d_dirs; q.t = t_in; q.far_ = cam->far_;
             q.origin[0] = cam->pos[0]; q.origin[1] = cam->pos[1]; q.origin[2] = cam->pos[2];
             q.sigma_out = sigma_out; q.ray_counter = ctr; q.live_count = ctr + 1; q.h8 = c->d_h8; q.slot_point = c->d_slot_point;
@@ -631,7 +635,7 @@ int render_once(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *o, 
                 t.done(c->last_render);
             }
             MlpArgs l = b;
-            l.wstream = stream_of(net, dt); l.small_params = small_of(net, dt); l.raw_pre = 0; l.mode = MLP_MODE_LIST; l.rgb_out = rgb_out; l.n_points = (int)cap;
+            l.wstream = stream_of(net, dt); l.small_params = small_of(net, dt); zskip_of(c, net, l); l.raw_pre = 0; l.mode = MLP_MODE_LIST; l.rgb_out = rgb_out; l.n_points = (int)cap;
             l.point_list = c->d_point_list; l.point_list_count = slots;
             if (rgb_out && c->cert_zero_tiles) { l.point_list_count_back = slots + 9; l.skip_empty = 1; l.skip_counter = c->d_skip; }
             l.nonfinite = split_dtype(dt) ? c->d_nonfinite : nullptr;
@@ -653,7 +657,7 @@ int render_once(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *o, 
             return NERF_OK;
         };
         // coarse network: sigma only unless its colours are composited (reference discards them, src/lib.rs:404)
-        a.wstream = stream_of(NC, dtype_coarse); a.small_params = small_of(NC, dtype_coarse);
+        a.wstream = stream_of(NC, dtype_coarse); a.small_params = small_of(NC, dtype_coarse); zskip_of(c, NC, a);
         a.n_points = n_rays * nc; a.samples_per_ray = nc; a.t = c->d_tc;
         a.sigma_out = c->d_sc; a.rgb_out = o->coarse_only ? c->d_rgbc : nullptr; // sigma-only launch otherwise
         a.skip_empty = o->skip_empty; a.skip_counter = o->skip_empty ? c->d_skip : nullptr; // only full kernels look at it
@@ -697,7 +701,7 @@ int render_once(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *o, 
                 // The coarse densities came from the split arithmetic.  Redo, in exact f32, the rays with a draw in a light CDF
                 // bin (their sample positions are the ill-conditioned ones) and resample just those: same positions as the f32 path.
                 SeqArgs q{};
-                q.wstream = NC.wstream; q.small_params = NC.small_f32; q.n_rays = n_rays; q.samples_per_ray = nc;
+                q.wstream = NC.wstream; q.small_params = NC.small_f32; zskip_of(c, NC, q); q.n_rays = n_rays; q.samples_per_ray = nc;
                 q.ray_dirs = c->d_dirs; q.t = c->d_tc; q.far_ = cam->far_;
                 q.origin[0] = cam->pos[0]; q.origin[1] = cam->pos[1]; q.origin[2] = cam->pos[2];
                 q.sigma_out = c->d_sc; q.ray_counter = hctr; q.stats = (unsigned long long *)(hctr + 2);
@@ -717,7 +721,7 @@ int render_once(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *o, 
             }
             t_fine = c->d_tf;
         }
-        a.wstream = stream_of(NF, dtype); a.small_params = small_of(NF, dtype);
+        a.wstream = stream_of(NF, dtype); a.small_params = small_of(NF, dtype); zskip_of(c, NF, a);
         a.n_points = n_rays * M; a.samples_per_ray = M; a.t = t_fine;
         a.sigma_out = c->d_sf; a.rgb_out = c->d_rgbf;
         a.clock_out = c->d_clock; // NULL unless NERF_DEBUG_CLOCK=1
@@ -974,7 +978,7 @@ int render_rays_device(nerf_ctx *c, const RayBatch &b, const nerf_render_opts *o
             t.done(c->last_render);
             return NERF_OK;
         };
-        a.wstream = stream_of(NC, dtype_coarse); a.small_params = small_of(NC, dtype_coarse);
+        a.wstream = stream_of(NC, dtype_coarse); a.small_params = small_of(NC, dtype_coarse); zskip_of(c, NC, a);
         a.n_points = n_rays * nc; a.samples_per_ray = nc; a.t = c->d_tc;
         a.sigma_out = c->d_sc; a.rgb_out = o->coarse_only ? c->d_rgbc : nullptr;
         a.nonfinite = split_dtype(dtype_coarse) ? c->d_nonfinite : nullptr;
@@ -1013,7 +1017,7 @@ int render_rays_device(nerf_ctx *c, const RayBatch &b, const nerf_render_opts *o
             t.done(c->last_render);
             t_fine = c->d_tf;
         }
-        a.wstream = stream_of(NF, dtype); a.small_params = small_of(NF, dtype);
+        a.wstream = stream_of(NF, dtype); a.small_params = small_of(NF, dtype); zskip_of(c, NF, a);
         a.n_points = n_rays * M; a.samples_per_ray = M; a.t = t_fine;
         a.sigma_out = c->d_sf; a.rgb_out = c->d_rgbf;
         a.nonfinite = split_dtype(dtype) ? c->d_nonfinite : nullptr;
@@ -1243,6 +1247,10 @@ int nerf_create(int device_id, nerf_ctx **out) try {
         if (sscanf(env, "%f,%f", &m0, &m1) == 2 && m0 > 0.f && m1 > 0.f) { c->cert_margin_floor[0] = m0; c->cert_margin_floor[1] = m1; c->cert_margin[0] = m0; c->cert_margin[1] = m1; }
     }
 #endif
+    if (const char *env = getenv("NERF_ZERO_STEP_SKIP")) c->zero_step_skip = atoi(env) != 0;
+    if (const char *env = getenv("NERF_DEBUG_ZSKIP")) {
+        if (atoi(env) > 0 && hipMalloc((void **)&c->d_zskip, 2 * sizeof(unsigned long long)) != hipSuccess) c->d_zskip = nullptr;
+    }
     if (const char *env = getenv("NERF_DEBUG_CLOCK")) {
         if (atoi(env) > 0 && hipMalloc((void **)&c->d_clock, (size_t)c->n_cus * 2 * sizeof(unsigned long long)) != hipSuccess) c->d_clock = nullptr;
     }
@@ -1293,6 +1301,7 @@ void nerf_destroy(nerf_ctx *c) {
     if (c->d_batch) (void)hipFree(c->d_batch);
     if (c->d_comp) (void)hipFree(c->d_comp);
     if (c->d_clock) (void)hipFree(c->d_clock);
+    if (c->d_zskip) (void)hipFree(c->d_zskip);
     if (c->d_skip) (void)hipFree(c->d_skip);
     if (c->d_nonfinite) (void)hipFree(c->d_nonfinite);
     if (c->d_seq) (void)hipFree(c->d_seq);
@@ -1392,7 +1401,7 @@ static int forward_device(nerf_ctx *c, int which, int dtype, const float *d_pts,
     a.mode = MLP_MODE_POINTS;
     if (!valid_dtype(dtype)) return fail(c, NERF_ERR_INVALID, "mlp_dtype must be NERF_MLP_F32, NERF_MLP_BF16, NERF_MLP_BF16X3 or NERF_MLP_F16X2");
     if (dtype == NERF_MLP_F16X2 && !c->net[which].wstream_x2) return fail(c, NERF_ERR_STATE, "NERF_MLP_F16X2 is unavailable for this network: a weight exceeds the f16 range");
-    a.wstream = stream_of(c->net[which], dtype); a.small_params = small_of(c->net[which], dtype);
+    a.wstream = stream_of(c->net[which], dtype); a.small_params = small_of(c->net[which], dtype); zskip_of(c, c->net[which], a);
     a.n_points = (int)n; a.pts_soa = d_pts; a.dirs_aos = d_dirs; a.sigma_out = d_sigma; a.rgb_out = d_rgb;
     a.nonfinite = split_dtype(dtype) ? c->d_nonfinite : nullptr;
     HIP_TRY(c, launch_mlp(c, dtype, a, true, (hipStream_t)stream));
@@ -1442,7 +1451,7 @@ static int density_batch_device(nerf_ctx *c, int which, const float *d_pts, size
     DeviceGuard dg(c->device);
     MlpArgs a{};
     a.mode = MLP_MODE_POINTS;
-    a.wstream = c->net[which].wstream; a.small_params = c->net[which].small_f32;
+    a.wstream = c->net[which].wstream; a.small_params = c->net[which].small_f32; zskip_of(c, c->net[which], a);
     a.n_points = (int)n; a.pts_soa = d_pts; a.sigma_out = d_sigma;
     HIP_TRY(c, nerf_mlp_launch(a, false, c->n_cus, st));
     return NERF_OK;
@@ -1498,7 +1507,7 @@ static int density_grid_launch(nerf_ctx *c, int which, const float *lo, const fl
                                float *d_sigma, float threshold, uint32_t *d_bits, int *d_stats, hipStream_t st) {
     MlpArgs a{};
     a.mode = MLP_MODE_GRID;
-    a.wstream = c->net[which].wstream; a.small_params = c->net[which].small_f32;
+    a.wstream = c->net[which].wstream; a.small_params = c->net[which].small_f32; zskip_of(c, c->net[which], a);
     a.n_points = (int)n_cells; a.sigma_out = d_sigma;
     for (int k = 0; k < 3; ++k) { a.grid_lo[k] = lo[k]; a.grid_step[k] = step[k]; a.grid_n[k] = dims[k]; }
     a.occ_threshold = threshold; a.occ_bits = d_bits;

@@ -157,6 +157,18 @@ int nerf_debug_fold_network_dir(const char *dir, float *wstream, size_t wstream_
     return debug_pack(dir, true, wstream, wstream_cap, small, small_cap, wstream_len, small_len);
 } NERF_HOST_CATCH
 
+int nerf_debug_zero_skip_network_dir(const char *dir, int *eligible) try {
+    if (!eligible) return fail_noctx(NERF_ERR_INVALID, "eligible is NULL");
+    size_t nw = 0, ns = 0;
+    int rc = debug_pack(dir, true, nullptr, 0, nullptr, 0, &nw, &ns);
+    if (rc) return rc;
+    std::vector<float> ws(nw), sm(ns);
+    rc = debug_pack(dir, true, ws.data(), nw, sm.data(), ns, nullptr, nullptr);
+    if (rc) return rc;
+    *eligible = zero_skip_safe(ws, sm) ? 1 : 0;
+    return NERF_OK;
+} NERF_HOST_CATCH
+
 int nerf_camera_from_json(const char *path, int width, int height, nerf_camera *out) try {
     if (!path || !out) return fail_noctx(NERF_ERR_INVALID, "NULL argument");
     std::string err;

@@ -22,6 +22,7 @@ struct DevNet {
     uint16_t *wstream_x2 = nullptr;     // two f16 parts per weight (mlp_kernel_f16x2.hip); NULL if a weight exceeds the f16 range
     uint16_t *wstream_f16v2 = nullptr;  // one f16 per weight in wstream_bf16v2's order (mlp_kernel_f16v2.hip: certify_zero's pre-filter); NULL likewise
     bool loaded = false;
+    bool zero_skip = false; // the f32 kernels may skip all-zero ReLU k-steps: the context allows it and every parameter of the folded image is finite
 };
 
 // certify_zero: a sample is a certain zero iff its 16-bit (pre-filter) density pre-activation is below -margin.  Floors per network WITH THE bf16
@@ -101,6 +102,8 @@ struct nerf_ctx {
     unsigned int *d_nonfinite = nullptr;   // device counter of non-finite density pre-activations (split arithmetics)
     unsigned long long *d_clock = nullptr; // diagnostic: per-workgroup {cycles, 100 MHz ticks} of the last fine-MLP launch
     bool clock_valid = false;
+    bool zero_step_skip = true;            // NERF_ZERO_STEP_SKIP=0 at nerf_create: the f32 kernels execute every k-step (networks loaded afterwards)
+    unsigned long long *d_zskip = nullptr; // diagnostic (NERF_DEBUG_ZSKIP=1): {executed, total} ReLU k-steps of the f32 launch under way
     size_t max_rays_per_pass = (size_t)1 << 20;
     std::vector<hipEvent_t> ev_pool;
     std::vector<nerfint::EvPair> last_render; // events of the last render
