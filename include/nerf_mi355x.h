@@ -171,7 +171,9 @@ typedef struct {
 /* Environment read by nerf_create (per context; networks loaded into it afterwards follow it):
  *   NERF_ZERO_STEP_SKIP=0   the NERF_MLP_F32 kernels execute every MFMA k-step.  Default (unset or non-zero): a k-step of a 256-wide layer
  *                           whose ReLU'd inputs are zero for all 32 points of a wave is skipped -- exactly fma(a, 0, c) = c, so every output
- *                           keeps its bits; a network with a non-finite parameter runs with the skip off on its own.
+ *                           keeps its bits; a network with a non-finite parameter runs with the skip off on its own.  Inputs and
+ *                           activations need not be finite for that: subnormal, NaN, infinite and overflowing values give the same bits
+ *                           with and without the skip (measured: profiles/zskip_counts.txt), whatever those bits are worth.
  *   NERF_DEBUG_ZSKIP=1      diagnostic: every f32 MLP launch synchronises and prints its executed / total ReLU k-steps to stderr.
  *   NERF_DEBUG_CLOCK=1      diagnostic: nerf_debug_shader_clock_mhz. */
 int nerf_create(int device_id, nerf_ctx **out);

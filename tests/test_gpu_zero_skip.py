@@ -9,12 +9,16 @@ consecutive skipped chunks than the LDS ring has slots (b), the four waves of a 
 import contextlib
 import os
 import re
+import sys
 
 import numpy as np
 import pytest
 
 from conftest import SCENE, psnr
 from fold_utils import write_random_net
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+from zero_skip_cases import DEAD, _copy_net, _edit, _make_case, _sign_points  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -121,62 +125,8 @@ def test_forward_batch_same_bits_on_and_off(scene_pair, random_pair, points, ora
 
 
 # ---- 2. engineered networks ------------------------------------------------------------------------------------------------------
-DEAD = -1.0e3  # a bias no pre-activation of these networks comes near: |w . x| stays below 1e2 on the test points
-
-
-def _edit(d, name, fn):
-    path = os.path.join(d, name + ".bin")
-    a = np.fromfile(path, dtype="<f4")
-    fn(a)
-    a.astype("<f4").tofile(path)
-
-
-def _copy_net(src, dst):
-    os.makedirs(dst)
-    for f in os.listdir(src):
-        with open(os.path.join(src, f), "rb") as i, open(os.path.join(dst, f), "wb") as o:
-            o.write(i.read())
-    return dst
-
-
-def _sign_points(rng):
-    """Case (c): x < 0 kills every unit of dense0, x > 0 keeps them.  First half: waves 0-1 of every 128-point workgroup tile dead and
-    waves 2-3 live; second half: alternating per 32 points (per wave).  The prefixes n = 128, 129 end inside / just behind a tile."""
-    pts = rng.uniform(-2.2, 2.2, size=(3, N_MAX)).astype(np.float32)
-    i = np.arange(N_MAX)
-    live = np.where(i < N_MAX // 2, (i // 64) % 2 == 1, (i // 32) % 2 == 1)
-    pts[0] = np.where(live, 1.0, -1.0) * np.maximum(np.abs(pts[0]), 0.05)
-    return pts.astype(np.float32), live
-
-
-def _make_case(case, base, tmp):
-    """-> (directory, twin directory, points or None): the twin differs only in weights the engineered zeros make irrelevant."""
-    d = _copy_net(base, str(tmp / case))
-    twin = str(tmp / (case + "_twin"))
-    if case == "a":       # dense2: all but two units dead -> dense3's k-steps skipped in long runs, whole chunks of them
-        keep = [37, 201]
-        def bias(b):
-            k = b[keep].copy(); b[:] = DEAD; b[keep] = k
-        _edit(d, "dense2_bias", bias)
-        _copy_net(d, twin)
-        def rows(w):
-            w = w.reshape(256, 256); k = w[keep].copy(); w[:] = 0; w[keep] = k
-        _edit(twin, "dense3_kernel", rows)
-    elif case == "b":     # dense3 entirely dead -> all 128 k-steps (16 chunks, the ring has 3 slots) of dense4 skipped
-        _edit(d, "dense3_bias", lambda b: b.__setitem__(slice(None), DEAD))
-        _copy_net(d, twin)
-        _edit(twin, "dense4_kernel", lambda w: w.__setitem__(slice(None), 0))
-    elif case == "c":     # dense0 = raw x on every unit (reference feature 0): relu(h0) = max(x, 0) for all 256 units
-        def kern(w):
-            w = w.reshape(63, 256); w[:] = 0; w[0] = 1.0
-        _edit(d, "dense0_kernel", kern)
-        _edit(d, "dense0_bias", lambda b: b.__setitem__(slice(None), 0))
-        _copy_net(d, twin)
-        _edit(twin, "dense1_kernel", lambda w: w.__setitem__(slice(None), 0))
-    elif case == "d":     # dense7 entirely dead: the alpha head and viewdirs' see zeros
-        _edit(d, "dense7_bias", lambda b: b.__setitem__(slice(None), DEAD))
-        twin = None
-    return d, twin
+# the networks and their points live in tests/helpers/zero_skip_cases.py (shared with test_gpu_zero_skip_kernels.py and the CPU proof of the
+# engineered conditions, test_zero_skip_cases_cpu.py)
 
 
 @pytest.fixture(scope="module")
