@@ -224,6 +224,22 @@ extern "C" {
                                    opts: *const nerf_render_opts, background: *const f32, d_rgb_out: *mut f32,
                                    d_depth_out: *mut f32, d_opacity_out: *mut f32, stream: *mut c_void,
                                    stats: *mut nerf_stats) -> c_int;
+    /// Central differences of sigma with step `h` at n points (3 x n SoA) -> `grad_soa` 3 x n: per axis (sigma(p + h e) - sigma(p - h e))
+    /// over the f32 difference of the two coordinates, 0 where that is 0.  Conventions: include/nerf_mi355x.h, "surface normals".
+    pub fn nerf_density_gradient_batch(ctx: *mut nerf_ctx, which: c_int, pts_soa: *const f32, n: usize, h: f32, grad_soa: *mut f32) -> c_int;
+    pub fn nerf_density_gradient_batch_device(ctx: *mut nerf_ctx, which: c_int, d_pts_soa: *const f32, n: usize, h: f32,
+                                              d_grad_soa: *mut f32, stream: *mut c_void) -> c_int;
+    /// `nerf_render_rays` + one normal per ray (`normals_out` n_rays x 3): minus the weighted sum of the density gradients (step `h`) at
+    /// the samples of weight > 0, normalised; zero for a ray without such a sample.  Colour, depth and opacity keep their bits.
+    pub fn nerf_render_rays_normals(ctx: *mut nerf_ctx, origins: *const f32, n_origins: usize, dirs: *const f32, n_rays: usize,
+                                    normalize: c_int, near: f32, far: f32, bounds: *const f32, rng_index: *const u32,
+                                    opts: *const nerf_render_opts, background: *const f32, rgb_out: *mut f32, depth_out: *mut f32,
+                                    opacity_out: *mut f32, h: f32, normals_out: *mut f32, stats: *mut nerf_stats) -> c_int;
+    pub fn nerf_render_rays_normals_device(ctx: *mut nerf_ctx, d_origins: *const f32, n_origins: usize, d_dirs: *const f32, n_rays: usize,
+                                           normalize: c_int, near: f32, far: f32, d_bounds: *const f32, d_rng_index: *const u32,
+                                           opts: *const nerf_render_opts, background: *const f32, d_rgb_out: *mut f32,
+                                           d_depth_out: *mut f32, d_opacity_out: *mut f32, h: f32, d_normals_out: *mut f32,
+                                           stream: *mut c_void, stats: *mut nerf_stats) -> c_int;
     /// render_image over several GPUs: `ctxs[i]` = one context per device, row bands on per-context host threads + streams,
     /// gathered into `rgb_out` by `gather` (NERF_GATHER_*).  The reference's counterpart is the rayon fan-out, src/lib.rs:533-557.
     pub fn nerf_render_image_multi(ctxs: *const *mut nerf_ctx, n: c_int, cam: *const nerf_camera, opts: *const nerf_render_opts,

@@ -141,6 +141,17 @@ impl Gpu {
         Ok(sigma)
     }
 
+    /// Central differences of sigma with step `h` (finite, > 0) at points (3 x B SoA) -> 3 x B, plane a = d sigma / d a
+    /// (nerf_density_gradient_batch; the sigmas are `density`'s bits).
+    pub fn density_gradient(&self, fine: bool, points: &[f32], h: f32) -> Result<Vec<f32>, Error> {
+        assert_eq!(points.len() % 3, 0);
+        let n = points.len() / 3;
+        let mut grad = vec![0f32; 3 * n];
+        let which = if fine { sys::NERF_NET_FINE } else { sys::NERF_NET_COARSE };
+        check(self.ctx, unsafe { sys::nerf_density_gradient_batch(self.ctx, which, points.as_ptr(), n, h, grad.as_mut_ptr()) })?;
+        Ok(grad)
+    }
+
     /// The density field on the lattice `lo + step * (ix, iy, iz)`, `0 <= i* < dims`, generated inside the kernel (nerf_density_grid):
     /// sigma (x fastest) if `want_sigma`, and with a `threshold` the occupancy words (bit b of word w = cell 32 w + b), the number of
     /// occupied cells and their inclusive index bounds `[ix_min, iy_min, iz_min, ix_max, iy_max, iz_max]` (none: mins = dims, maxs = -1).
@@ -296,6 +307,29 @@ impl Gpu {
                                   rgb.as_mut_ptr(), depth.as_mut_ptr(), opacity.as_mut_ptr(), &mut stats)
         })?;
         Ok((rgb, depth, opacity, stats))
+    }
+
+    /// `render_rays` with one normal per ray (nerf_render_rays_normals): minus the weighted sum of the density gradients, step `h`, at
+    /// the samples of weight > 0, normalised; (0, 0, 0) for a ray without such a sample.  -> (rgb, depth, opacity, normals n x 3, stats);
+    /// the first three are `render_rays`' bits.
+    #[allow(clippy::too_many_arguments, clippy::type_complexity)]
+    pub fn render_rays_normals(&self, origins: &[f32], dirs: &[f32], normalize: bool, near: f32, far: f32, bounds: Option<&[f32]>,
+                               rng_index: Option<&[u32]>, opts: &RenderOpts, background: Option<[f32; 3]>, h: f32)
+                               -> Result<(Vec<f32>, Vec<f32>, Vec<f32>, Vec<f32>, Stats), Error> {
+        let n = dirs.len() / 3;
+        assert_eq!(dirs.len(), 3 * n, "dirs.len() must be 3 * n_rays");
+        assert!(origins.len() == 3 || origins.len() == 3 * n, "origins must hold one origin or one per ray");
+        assert!(bounds.map_or(true, |b| b.len() == 2 * n), "bounds.len() must be 2 * n_rays");
+        assert!(rng_index.map_or(true, |i| i.len() == n), "rng_index.len() must be n_rays");
+        let (mut rgb, mut depth, mut opacity, mut normals) = (vec![0f32; 3 * n], vec![0f32; n], vec![0f32; n], vec![0f32; 3 * n]);
+        let mut stats = Stats::default();
+        let bg = background.as_ref().map_or(std::ptr::null(), |b| b.as_ptr());
+        check(self.ctx, unsafe {
+            sys::nerf_render_rays_normals(self.ctx, origins.as_ptr(), origins.len() / 3, dirs.as_ptr(), n, normalize as i32, near, far,
+                                          bounds.map_or(std::ptr::null(), |b| b.as_ptr()), rng_index.map_or(std::ptr::null(), |i| i.as_ptr()), opts,
+                                          bg, rgb.as_mut_ptr(), depth.as_mut_ptr(), opacity.as_mut_ptr(), h, normals.as_mut_ptr(), &mut stats)
+        })?;
+        Ok((rgb, depth, opacity, normals, stats))
     }
 }
 

@@ -479,6 +479,61 @@ int nerf_render_rays_device(nerf_ctx *ctx, const float *d_origins, size_t n_orig
                             const nerf_render_opts *opts, const float background[3],
                             float *d_rgb_out, float *d_depth_out, float *d_opacity_out, void *stream, nerf_stats *stats);
 
+/* ---- surface normals: the gradient of sigma at caller points, and one normal per ray of a batch -------------------------------------------
+ * The mesh normals above difference sigma over a whole lattice spacing.  These entry points difference the network itself, with a step h
+ * the caller chooses, on the device (nerf-rs_amd/csrc/normal_kernels.hip around the f32 sigma-only launch of nerf_density_batch).  All
+ * arithmetic is f32; every operation is rounded once and never contracted; division and sqrt are correctly rounded.  A host can restate
+ * every output bit for bit from nerf_density_batch and the stage calls (tests/helpers/normal_restatement.py does).
+ * GRADIENT   of sigma at a point p with step h (one scalar per call, finite and > 0).  For each axis a in {x, y, z}:
+ *              p+ = p with coordinate a replaced by fl(p_a + h), p- = p with coordinate a replaced by fl(p_a - h);
+ *              sigma+, sigma- = the bits nerf_density_batch returns at p+ and p- (always the f32 sigma-only kernel);
+ *              den = fl(p+_a - p-_a);  g_a = fl(fl(sigma+ - sigma-) / den), and g_a = 0 if den == 0 (h below half an ulp of p_a).
+ * RAY NORMAL added to the ray-batch pipeline exactly as nerf_render_rays specifies it, over the samples the final compositing integrates: the
+ *            fine pass's n_coarse + n_fine merged samples, or the coarse ones under coarse_only (and in nerf_render_rays' other branches).
+ *              w_i = the weight the compositing kernel computes for sample i: the bits of nerf_stage_integrate's w_out on that pass's
+ *                    t, sigma (in the render's own mlp_dtype) and far;
+ *              x_i = fl(o + fl(d * t_i)) per coordinate, d the direction the networks saw (normalised when normalize != 0);
+ *              a sample is LIVE iff w_i > 0 (a NaN weight is not); only live samples are evaluated, every other sample contributes
+ *                    nothing whatever its gradient would have been;
+ *              G_a = sum over the live i in ascending i of w_i g_a(x_i): acc = fl(acc + fl(w_i * g_a(x_i))), starting from +0;
+ *              len = sqrtf(fl(fl(G_x G_x + G_y G_y) + G_z G_z));  n = (-G) / len per component -- towards lower density, the mesh normals'
+ *                    convention; n = (0, 0, 0) when len is 0 or not finite, which includes a ray without a live sample.
+ *            The network differentiated is the one that was composited (fine, or coarse under coarse_only), always in f32 -- also when
+ *            mlp_dtype made the weights in another arithmetic.
+ * CONSEQUENCE nerf_render_rays' clauses extend to the normal: a ray's normal depends on that ray's inputs, opts, h and the weights alone;
+ *            permuting a batch permutes the normals; shared and repeated origins give the same bits; the pass size changes no bit; and
+ *            colour, depth and opacity of a call that also asks for normals are the bits of the same call without them.
+ * WORKSPACE  in the context, grown on demand (a warm call allocates nothing): 8 bytes per composited sample of a pass (weights, live
+ *            list) + 8 per ray, and 16 bytes per stencil point -- 96 per live sample of a pass.  nerf_density_gradient_batch* runs large n in
+ *            internal chunks of at most 2^20 points (NERF_GRADIENT_CHUNK, read by nerf_create, overrides it): its stencil workspace is
+ *            bounded by 96 MiB whatever n is, and no bit depends on the chunking.
+ * The live count of every pass comes back to the host (8 bytes, one stream synchronisation per pass): it sizes the launches that follow,
+ * so nerf_render_rays_normals_device is asynchronous only from its last pass's count on.  A pass without a live sample launches nothing
+ * further and writes zero normals.
+ * NERF_DEBUG_NORMALS=1 (read by nerf_create): a normals render that fills nerf_stats prints its live share and the device time of its own
+ * launches to stderr.  Those launches count into nerf_stats.ms_other and ms_total; n_mlp_launches stays the colour pipeline's. */
+/* grad_soa: 3 x n like pts_soa (plane a = dsigma/da).  Host pointers, synchronous; n == 0 is a no-op.  Input domain and largest n: as
+ * nerf_density_batch (the stencil points p +- h included).  NERF_ERR_INVALID (checked before the context or the device is needed, "ctx is
+ * NULL" last): a bad `which`, h not finite or <= 0, a NULL buffer with n > 0. */
+int nerf_density_gradient_batch(nerf_ctx *ctx, int which, const float *pts_soa /*3 x n*/, size_t n, float h, float *grad_soa /*3 x n*/);
+/* device pointers, asynchronous on `stream` */
+int nerf_density_gradient_batch_device(nerf_ctx *ctx, int which, const float *d_pts_soa, size_t n, float h, float *d_grad_soa, void *stream);
+/* nerf_render_rays + normals_out (n_rays x 3).  Every argument, refusal and per-ray check of nerf_render_rays applies unchanged; also
+ * NERF_ERR_INVALID, checked with the others before the context or the device is needed: h not finite or <= 0, normals_out NULL. */
+int nerf_render_rays_normals(nerf_ctx *ctx, const float *origins /* n_origins x 3 */, size_t n_origins /* 1 or n_rays */,
+                             const float *dirs /* n_rays x 3 */, size_t n_rays, int normalize,
+                             float near_, float far_, const float *bounds /* n_rays x 2 or NULL */,
+                             const uint32_t *rng_index /* n_rays or NULL */,
+                             const nerf_render_opts *opts, const float background[3] /* NULL = white */,
+                             float *rgb_out /* n_rays x 3 */, float *depth_out /* n_rays or NULL */, float *opacity_out /* n_rays or NULL */,
+                             float h, float *normals_out /* n_rays x 3 */, nerf_stats *stats /* may be NULL */);
+/* nerf_render_rays_device + d_normals_out (device, n_rays x 3); synchronises once per pass as described above */
+int nerf_render_rays_normals_device(nerf_ctx *ctx, const float *d_origins, size_t n_origins, const float *d_dirs, size_t n_rays, int normalize,
+                                    float near_, float far_, const float *d_bounds, const uint32_t *d_rng_index,
+                                    const nerf_render_opts *opts, const float background[3],
+                                    float *d_rgb_out, float *d_depth_out, float *d_opacity_out, float h, float *d_normals_out,
+                                    void *stream, nerf_stats *stats);
+
 /* ---- S3 over several GPUs of one node (reference: the rayon fan-out over blocks + scatter, src/lib.rs:533-557) ------
  * ctxs[i] is one context per device (nerf_create / nerf_create_multi), each with both networks loaded (weights are
  * replicated).  Context i renders band i of n of the output rows (nerf_render_opts.band_*, set here: the caller's values are
@@ -594,7 +649,8 @@ const char *nerf_build_variant(void);
  * nerf_stage_integrate_rgba8, nerf_save_pam, NERF_ALPHA_*, nerf_density_batch, nerf_density_batch_device, nerf_density_grid,
  * nerf_density_grid_device, nerf_isosurface_grid, nerf_extract_mesh, nerf_extract_mesh_device, nerf_save_ply, nerf_component_filter,
  * nerf_component, nerf_lattice_components, nerf_lattice_components_device, nerf_isosurface_grid_filtered, nerf_extract_mesh_filtered,
- * nerf_extract_mesh_filtered_device, nerf_render_rays, nerf_render_rays_device). */
+ * nerf_extract_mesh_filtered_device, nerf_render_rays, nerf_render_rays_device, nerf_density_gradient_batch,
+ * nerf_density_gradient_batch_device, nerf_render_rays_normals, nerf_render_rays_normals_device). */
 int nerf_abi_version(void);
 /* sizeof(nerf_camera), sizeof(nerf_render_opts), sizeof(nerf_stats) as this library was built: lets a binding written in
  * another language (the Rust `-sys` crate, ctypes) check its struct mirrors at start-up. */

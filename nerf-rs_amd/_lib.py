@@ -126,6 +126,13 @@ PROTOTYPES = {
                                    f32p, f32p, f32p, f32p, C.POINTER(CStats)]),
     "nerf_render_rays_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_float, C.c_void_p,
                                           C.c_void_p, C.POINTER(COpts), f32p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CStats)]),
+    "nerf_density_gradient_batch": (C.c_int, [C.c_void_p, C.c_int, f32p, C.c_size_t, C.c_float, f32p]),
+    "nerf_density_gradient_batch_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p]),
+    "nerf_render_rays_normals": (C.c_int, [C.c_void_p, f32p, C.c_size_t, f32p, C.c_size_t, C.c_int, C.c_float, C.c_float, f32p, u32p,
+                                           C.POINTER(COpts), f32p, f32p, f32p, f32p, C.c_float, f32p, C.POINTER(CStats)]),
+    "nerf_render_rays_normals_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_float,
+                                                  C.c_void_p, C.c_void_p, C.POINTER(COpts), f32p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
+                                                  C.c_void_p, C.c_void_p, C.POINTER(CStats)]),
     "nerf_create_multi": (C.c_int, [C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p)]),
     "nerf_multi_release": (None, []),
     "nerf_band_rows": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),

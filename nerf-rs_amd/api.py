@@ -206,6 +206,24 @@ class Network:
         R = self.renderer
         check(R._L.nerf_density_batch_device(R.handle, self.which, d_points, n, d_sigma, stream), R.handle)
 
+    def density_gradient(self, points, h):
+        """Central differences of sigma at points (3, B) f32 SoA with step h (finite, > 0) -> (3, B): per axis
+        (sigma(p + h e) - sigma(p - h e)) / (fl(p + h) - fl(p - h)) in f32, each operation rounded once, 0 where the denominator is 0
+        (nerf_density_gradient_batch; the sigmas are density()'s bits).  B == 0 returns an empty array."""
+        pts = _f32(points)
+        if pts.ndim != 2 or pts.shape[0] != 3:
+            raise NerfError(-1, "points must be a 3 x B matrix")
+        n = pts.shape[1]
+        grad = np.empty((3, n), np.float32)
+        R = self.renderer
+        check(R._L.nerf_density_gradient_batch(R.handle, self.which, _p(pts), n, float(h), _p(grad)), R.handle)
+        return grad
+
+    def density_gradient_device(self, d_points, d_grad, n, h, stream=0):
+        """Raw device pointers (ints), asynchronous on `stream`."""
+        R = self.renderer
+        check(R._L.nerf_density_gradient_batch_device(R.handle, self.which, d_points, n, float(h), d_grad, stream), R.handle)
+
     def density_grid(self, lo, step, dims, threshold=None, want_sigma=True):
         """sigma on the lattice lo + step * (ix, iy, iz), 0 <= i* < dims = (nx, ny, nz), generated inside the kernel (nerf_density_grid)
         -> (sigma, bits, count, bounds): sigma (nz, ny, nx) f32 or None (want_sigma=False); with a threshold (>= 0) bits = ceil(N / 32)
@@ -598,7 +616,7 @@ def _ray_opts(n_coarse, fine_samples_per_ray, seed, coarse_only, dtype):
 
 
 def render_rays(coarse, fine, origins, dirs, near, far, fine_samples_per_ray=128, *, n_coarse=64, bounds=None, normalize=True,
-                rng_index=None, seed=0, coarse_only=False, dtype="f32", background=None, aux=False, return_stats=False):
+                rng_index=None, seed=0, coarse_only=False, dtype="f32", background=None, aux=False, return_stats=False, normals_h=None):
     """The caller's rays instead of a camera's (nerf_render_rays) -> rgb (n, 3) float32.
 
     origins: (3,) -- one origin for every ray -- or (n, 3); dirs: (n, 3), normalised on the device unless normalize=False (the caller
@@ -606,6 +624,9 @@ def render_rays(coarse, fine, origins, dirs, near, far, fine_samples_per_ray=128
     rng_index: (n,) uint32, the index ray r draws its samples from (None: r) -- a camera's rays with rng_index = row * nx + col give the
     bits of render_image.  n_coarse + fine_samples_per_ray samples, seed, coarse_only, dtype as in render_image; background: None
     (white) or (R, G, B).  aux=True: (rgb, depth (n,), opacity (n,)) as render_image(aux=True); the stats follow if return_stats.
+    normals_h: a central-difference step h (finite, > 0) -> the per-ray normals (n, 3) follow the other arrays (the fourth array with
+    aux=True): minus the weighted sum of the density gradients at the live samples, normalised; zero for a ray without a live sample
+    (nerf_render_rays_normals).  Colour, depth and opacity keep their bits.
     The per-pixel options of render_image (crop, ssaa, bands, the skip modes) do not exist for rays."""
     R = coarse.renderer
     if fine is not None and fine.renderer is not R:
@@ -628,10 +649,17 @@ def render_rays(coarse, fine, origins, dirs, near, far, fine_samples_per_ray=128
     rgb = np.empty((n, 3), np.float32)
     depth, opacity = (np.empty(n, np.float32), np.empty(n, np.float32)) if aux else (None, None)
     st = CStats()
-    check(R._L.nerf_render_rays(R.handle, _p(o), 1 if o.ndim == 1 else n, _p(d), n, int(bool(normalize)), float(near), float(far),
-                                None if b is None else _p(b), None if idx is None else idx.ctypes.data_as(u32p), C.byref(opts), bg,
-                                _p(rgb), None if depth is None else _p(depth), None if opacity is None else _p(opacity), C.byref(st)), R.handle)
+    head = (R.handle, _p(o), 1 if o.ndim == 1 else n, _p(d), n, int(bool(normalize)), float(near), float(far),
+            None if b is None else _p(b), None if idx is None else idx.ctypes.data_as(u32p), C.byref(opts), bg,
+            _p(rgb), None if depth is None else _p(depth), None if opacity is None else _p(opacity))
+    if normals_h is None:
+        check(R._L.nerf_render_rays(*head, C.byref(st)), R.handle)
+    else:
+        normals = np.empty((n, 3), np.float32)
+        check(R._L.nerf_render_rays_normals(*head, float(normals_h), _p(normals), C.byref(st)), R.handle)
     out = (rgb, depth, opacity) if aux else (rgb,)
+    if normals_h is not None:
+        out += (normals,)
     if return_stats:
         out += (Stats(st),)
     return out if len(out) > 1 else out[0]
@@ -639,20 +667,51 @@ def render_rays(coarse, fine, origins, dirs, near, far, fine_samples_per_ray=128
 
 def render_rays_device(coarse, fine, d_origins, n_origins, d_dirs, n_rays, near, far, fine_samples_per_ray, d_rgb, *, n_coarse=64,
                        d_bounds=None, normalize=True, d_rng_index=None, seed=0, coarse_only=False, dtype="f32", background=None,
-                       d_depth=None, d_opacity=None, stream=0, return_stats=False):
+                       d_depth=None, d_opacity=None, stream=0, return_stats=False, d_normals=None, normals_h=None):
     """nerf_render_rays_device: raw device pointers (ints; d_bounds, d_rng_index, d_depth, d_opacity may be None), asynchronous on
     `stream` (n_origins == 1 reads the origin back first and synchronises the stream once; return_stats synchronises it at the end).
-    n_origins is 1 or n_rays.  Returns None / the stats."""
+    n_origins is 1 or n_rays.  d_normals (n_rays x 3 floats) together with normals_h: nerf_render_rays_normals_device, which
+    synchronises the stream once per pass to read that pass's live count.  Returns None / the stats."""
+    if (d_normals is None) != (normals_h is None):
+        raise NerfError(-1, "d_normals and normals_h go together")
     R = coarse.renderer
     if fine is not None and fine.renderer is not R:
         raise NerfError(-1, "coarse and fine networks must live in the same Renderer")
     opts = _ray_opts(n_coarse, fine_samples_per_ray, seed, coarse_only, dtype)
     keep, bg = _background(background)
     st = CStats()
-    check(R._L.nerf_render_rays_device(R.handle, d_origins, int(n_origins), d_dirs, int(n_rays), int(bool(normalize)), float(near), float(far),
-                                       d_bounds, d_rng_index, C.byref(opts), bg, d_rgb, d_depth, d_opacity, stream,
-                                       C.byref(st) if return_stats else None), R.handle)
+    head = (R.handle, d_origins, int(n_origins), d_dirs, int(n_rays), int(bool(normalize)), float(near), float(far),
+            d_bounds, d_rng_index, C.byref(opts), bg, d_rgb, d_depth, d_opacity)
+    if d_normals is None:
+        check(R._L.nerf_render_rays_device(*head, stream, C.byref(st) if return_stats else None), R.handle)
+    else:
+        check(R._L.nerf_render_rays_normals_device(*head, float(normals_h), d_normals, stream, C.byref(st) if return_stats else None), R.handle)
     return Stats(st) if return_stats else None
+
+
+def render_image_normals(coarse, fine, camera, fine_samples_per_ray=128, *, h, seed=0, coarse_only=False, crop=None, dtype="f32",
+                         background=None, return_stats=False):
+    """A camera's window with a normal map -> (rgb (h, w, 3), depth (h, w), opacity (h, w), normals (h, w, 3)) float32.
+
+    A convenience over the ray-batch path: the window's unit directions come from stage_ray_dirs, the origin is camera.pos, near / far
+    the camera's and rng_index = row * nx + col, then render_rays(aux=True, normals_h=h).  Colour, depth and opacity are therefore the
+    bits of render_image(aux=True) for the same window, seed, sample counts and dtype (with the default white background).  crop =
+    (x0, y0, w, h) or None for the whole frame; the per-pixel options of render_image that ray batches refuse (ssaa, bands, the skip
+    modes) are not offered.  The stats follow if return_stats."""
+    R = coarse.renderer
+    c = camera.c
+    x0, y0, w, hh = crop if crop else (0, 0, c.nx, c.ny)
+    if w <= 0 or hh <= 0 or x0 < 0 or y0 < 0 or x0 + w > c.nx or y0 + hh > c.ny:
+        raise NerfError(-1, "crop window outside the frame")
+    dirs = R.stage_ray_dirs(camera, x0, y0, w, hh, normalize=True).reshape(-1, 3)
+    rows, cols = np.meshgrid(np.arange(y0, y0 + hh), np.arange(x0, x0 + w), indexing="ij")
+    pix = (rows * c.nx + cols).reshape(-1).astype(np.uint32)
+    out = render_rays(coarse, fine, np.float32(list(c.pos)), dirs, c.near, c.far, fine_samples_per_ray, n_coarse=camera.samples_per_ray,
+                      normalize=False, rng_index=pix, seed=seed, coarse_only=coarse_only, dtype=dtype, background=background, aux=True,
+                      return_stats=return_stats, normals_h=h)
+    rgb, depth, opacity, normals = out[:4]
+    shaped = (rgb.reshape(hh, w, 3), depth.reshape(hh, w), opacity.reshape(hh, w), normals.reshape(hh, w, 3))
+    return shaped + (out[4],) if return_stats else shaped
 
 
 GATHER_HOST, GATHER_PEER, GATHER_RCCL = 0, 1, 2

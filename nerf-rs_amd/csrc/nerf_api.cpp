@@ -24,6 +24,7 @@
 #include "isosurface_kernels.h"
 #include "mlp_kernel.h"
 #include "mlp_layout.h"
+#include "normal_kernels.h"
 #include "ray_batch_kernels.h"
 #include "sampling_kernels.h"
 
@@ -915,9 +916,50 @@ int check_ray_batch_rays(nerf_ctx *c, const float *origins, size_t n_origins, co
     return NERF_OK;
 }
 
-// arguments already checked (check_ray_batch); asynchronous on st unless stats != NULL
+// what nerf_render_rays_normals* adds to check_ray_batch
+int check_normals(nerf_ctx *c, float h, const void *normals_out) {
+    if (!(std::isfinite(h) && h > 0.0f)) return fail(c, NERF_ERR_INVALID, "h (the central-difference step) must be finite and greater than 0");
+    if (!normals_out) return fail(c, NERF_ERR_INVALID, "normals_out must not be NULL");
+    return NERF_OK;
+}
+
+// largest batch of nerf_forward_batch*: INT32_MAX minus (persistent workgroups + 1) tiles of the widest kernel (256 points)
+size_t max_batch_points(int n_cus) { return (size_t)0x7fffffff - ((size_t)n_cus + 1) * 256; }
+
+// the f32 sigma-only MLP_MODE_POINTS launch (nerf_density_batch's) over n points
+hipError_t launch_sigma_points(const nerf_ctx *c, const DevNet &net, const float *d_pts, size_t n, float *d_sigma, hipStream_t st) {
+    MlpArgs a{};
+    a.mode = MLP_MODE_POINTS;
+    a.wstream = net.wstream; a.small_params = net.small_f32; zskip_of(c, net, a);
+    a.n_points = (int)n; a.pts_soa = d_pts; a.sigma_out = d_sigma;
+    return launch_mlp(c, NERF_MLP_F32, a, false, st);
+}
+
+// The pass workspace of a normals render in c->d_normal, every part 256-byte aligned.
+struct NormalWorkspace {
+    float *w; uint32_t *list, *count, *base, *bsum, *totals;
+    static size_t al(size_t bytes) { return (bytes + 255) / 256 * 256; }
+    static size_t blocks(size_t rays) { return (rays + kNormalBlock - 1) / kNormalBlock; }
+    static size_t bytes(size_t rays, size_t samples) { return 2 * al(4 * samples) + 2 * al(4 * rays) + al(4 * blocks(rays)) + 256; }
+    NormalWorkspace(void *p, size_t rays, size_t samples) {
+        char *q = (char *)p;
+        w = (float *)q; q += al(4 * samples);
+        list = (uint32_t *)q; q += al(4 * samples);
+        count = (uint32_t *)q; q += al(4 * rays);
+        base = (uint32_t *)q; q += al(4 * rays);
+        bsum = (uint32_t *)q; q += al(4 * blocks(rays));
+        totals = (uint32_t *)q;
+    }
+};
+
+// arguments already checked (check_ray_batch, check_normals); asynchronous on st unless stats != NULL.
+// d_normals != NULL (n_rays x 3): the compositing launch also hands out its weights, and per pass
+//     count + scan + list (3 launches) -> [8 bytes to the host] -> stencil -> sigma-only MLP over 6 L points -> reduce
+// follow.  The live total L of a pass goes back to the host -- ONE SMALL COPY AND ONE STREAM SYNCHRONISATION PER PASS, as mesh_extract reads
+// its counts: it sizes the stencil workspace (16 B per point, grown on demand) and the launches that follow; a pass with L = 0 launches
+// nothing further and writes zero normals.  The network differentiated is the one composited, always in f32.
 int render_rays_device(nerf_ctx *c, const RayBatch &b, const nerf_render_opts *o, const float *background, float *d_out, float *d_depth,
-                       float *d_opacity, hipStream_t st, nerf_stats *stats) {
+                       float *d_opacity, hipStream_t st, nerf_stats *stats, float h = 0.0f, float *d_normals = nullptr) {
     int rc;
     const int dtype = o->mlp_dtype;
     const int dtype_coarse = (split_dtype(dtype) && !o->coarse_only) ? NERF_MLP_F32 : dtype; // as render_once: the sampling pass stays in exact f32
@@ -928,9 +970,15 @@ int render_rays_device(nerf_ctx *c, const RayBatch &b, const nerf_render_opts *o
     const int nc = o->n_coarse;
     const int nf = (o->coarse_only || o->n_fine == 0 || nc < 3) ? 0 : o->n_fine; // the sample-count branches of render_once
     const int M = nc + nf;
-    const size_t pass_cap = std::max<size_t>(1, std::min<size_t>(c->max_rays_per_pass, (size_t)0x3fffffff / (size_t)M));
+    size_t pass_cap = std::max<size_t>(1, std::min<size_t>(c->max_rays_per_pass, (size_t)0x3fffffff / (size_t)M));
+    // normals: if every sample of a pass were live its 6 stencil points each must still fit one MLP launch
+    if (d_normals) pass_cap = std::max<size_t>(1, std::min<size_t>(pass_cap, max_batch_points(c->n_cus) / (6 * (size_t)M)));
     const size_t pass_rays = std::min(b.n_rays, pass_cap);
     if ((rc = ensure_workspace(c, pass_rays, nc, M, o->coarse_only != 0))) return rc;
+    const int n_comp = o->coarse_only ? nc : M; // samples per ray that the final compositing integrates
+    if (d_normals && (rc = ensure_bytes(c, &c->d_normal, &c->normal_bytes, NormalWorkspace::bytes(pass_rays, pass_rays * (size_t)n_comp)))) return rc;
+    const NormalWorkspace nw(c->d_normal, pass_rays, pass_rays * (size_t)n_comp);
+    c->normal_live = 0; c->normal_samples = 0;
     // c->d_batch (floats): [far per ray, padded to 64][points 3 x n SoA][directions n x 3 AoS], n = the pass's rays x M
     const bool expand = b.d_origins != nullptr;
     const size_t far_floats = b.d_bounds ? (pass_rays + 63) / 64 * 64 : 0, n_max = pass_rays * (size_t)M;
@@ -962,6 +1010,45 @@ int render_rays_device(nerf_ctx *c, const RayBatch &b, const nerf_render_opts *o
             HIP_TRY(c, launch_batch_prepare(p, st));
             t.done(c->last_render);
         }
+        // the normals of the pass, from the weights the compositing launch left in nw.w (t: the composited samples' positions)
+        auto normals_pass = [&](const DevNet &net, const float *t) -> int {
+            if (!d_normals) return NERF_OK;
+            NormalListArgs la{nw.w, n_rays, n_comp, nw.count, nw.base, nw.bsum, nw.totals, nw.list};
+            {
+                Timed tm(c, st, 7, 0, timing);
+                HIP_TRY(c, launch_normal_list(la, st));
+                tm.done(c->last_render);
+            }
+            uint32_t totals[2] = {0, 0};
+            HIP_TRY(c, hipMemcpyAsync(totals, nw.totals, sizeof totals, hipMemcpyDeviceToHost, st));
+            HIP_TRY(c, hipStreamSynchronize(st));
+            const size_t L = totals[0];
+            c->normal_live += L; c->normal_samples += (uint64_t)n_rays * (uint64_t)n_comp;
+            float *out = d_normals + 3 * r0;
+            if (L == 0) { HIP_TRY(c, hipMemsetAsync(out, 0, (size_t)n_rays * 3 * sizeof(float), st)); return NERF_OK; }
+            if (L > (size_t)n_rays * (size_t)n_comp) return fail(c, NERF_ERR_HIP, "normals: the live count exceeds the pass's samples");
+            int rc2;
+            if ((rc2 = ensure_bytes(c, &c->d_stencil, &c->stencil_bytes, 6 * L * 4 * sizeof(float)))) return rc2;
+            float *d_spts = (float *)c->d_stencil, *d_ssig = d_spts + 18 * L;
+            NormalStencilArgs sa{};
+            sa.n_live = (uint32_t)L; sa.h = h; sa.list = nw.list; sa.spr = n_comp; sa.origins = origins; sa.dirs = c->d_dirs; sa.t = t; sa.pts = d_spts;
+            if (!expand) { sa.origin[0] = b.h_origin[0]; sa.origin[1] = b.h_origin[1]; sa.origin[2] = b.h_origin[2]; }
+            {
+                Timed tm(c, st, 7, 0, timing);
+                HIP_TRY(c, launch_normal_stencil(sa, st));
+                tm.done(c->last_render);
+            }
+            {
+                Timed tm(c, st, 6, (uint64_t)(6 * L), timing);
+                HIP_TRY(c, launch_sigma_points(c, net, d_spts, 6 * L, d_ssig, st));
+                tm.done(c->last_render);
+            }
+            NormalReduceArgs ra{n_rays, (uint32_t)L, nw.count, nw.base, nw.list, nw.w, d_spts, d_ssig, out};
+            Timed tm(c, st, 7, 0, timing);
+            HIP_TRY(c, launch_normal_reduce(ra, st));
+            tm.done(c->last_render);
+            return NERF_OK;
+        };
         MlpArgs a{};
         a.ray_dirs = c->d_dirs;
         if (expand) a.mode = MLP_MODE_POINTS;
@@ -996,11 +1083,15 @@ int render_rays_device(nerf_ctx *c, const RayBatch &b, const nerf_render_opts *o
         ca.n_rays = n_rays; ca.far_ = b.far_; ca.far_per_ray = far_per_ray; ca.out = d_out + 3 * r0;
         ca.depth = d_depth ? d_depth + r0 : nullptr; ca.opacity = d_opacity ? d_opacity + r0 : nullptr;
         if (background) { ca.use_bg = 1; ca.bg[0] = background[0]; ca.bg[1] = background[1]; ca.bg[2] = background[2]; }
+        if (d_normals) ca.w_out = nw.w;
         if (o->coarse_only) {
             ca.n = nc; ca.t = c->d_tc; ca.sigma = c->d_sc; ca.rgb = c->d_rgbc;
-            Timed t(c, st, 2, 0, timing);
-            HIP_TRY(c, launch_composite(ca, st));
-            t.done(c->last_render);
+            {
+                Timed t(c, st, 2, 0, timing);
+                HIP_TRY(c, launch_composite(ca, st));
+                t.done(c->last_render);
+            }
+            if ((rc = normals_pass(NC, c->d_tc))) return rc;
             continue;
         }
         const float *t_fine = c->d_tc;
@@ -1028,9 +1119,12 @@ int render_rays_device(nerf_ctx *c, const RayBatch &b, const nerf_render_opts *o
             t.done(c->last_render);
         }
         ca.n = M; ca.t = t_fine; ca.sigma = c->d_sf; ca.rgb = c->d_rgbf;
-        Timed t(c, st, 2, 0, timing);
-        HIP_TRY(c, launch_composite(ca, st));
-        t.done(c->last_render);
+        {
+            Timed t(c, st, 2, 0, timing);
+            HIP_TRY(c, launch_composite(ca, st));
+            t.done(c->last_render);
+        }
+        if ((rc = normals_pass(NF, t_fine))) return rc;
     }
     if (stats) {
         HIP_TRY(c, hipStreamSynchronize(st));
@@ -1039,6 +1133,7 @@ int render_rays_device(nerf_ctx *c, const RayBatch &b, const nerf_render_opts *o
         stats->n_passes = passes;
         stats->n_coarse_points = stats->n_rays * (uint64_t)nc;
         stats->n_fine_points = o->coarse_only ? 0 : stats->n_rays * (uint64_t)M;
+        double ms_normal_sigma = 0.0, ms_normal_small = 0.0;
         for (const auto &p : c->last_render) {
             float ms = 0.f;
             HIP_TRY(c, hipEventElapsedTime(&ms, p.a, p.b));
@@ -1046,13 +1141,18 @@ int render_rays_device(nerf_ctx *c, const RayBatch &b, const nerf_render_opts *o
             else if (p.kind == 5) {
                 stats->n_mlp_launches++;
                 if (o->coarse_only) stats->ms_coarse_mlp += ms; else stats->ms_fine_mlp += ms;
-            } else stats->ms_other += ms;
+            } else stats->ms_other += ms; // kinds 6 and 7 too: a normals render's own launches are neither network pass of the colour
+            if (p.kind == 6) ms_normal_sigma += ms; else if (p.kind == 7) ms_normal_small += ms;
         }
         if (!c->last_render.empty()) {
             float ms = 0.f;
             HIP_TRY(c, hipEventElapsedTime(&ms, c->last_render.front().a, c->last_render.back().b));
             stats->ms_total = ms;
         }
+        if (d_normals && c->debug_normals)
+            fprintf(stderr, "nerf normals: %llu live of %llu composited samples, sigma launches %.3f ms over %llu points, other normal kernels %.3f ms\n",
+                    (unsigned long long)c->normal_live, (unsigned long long)c->normal_samples, ms_normal_sigma, (unsigned long long)(6 * c->normal_live),
+                    ms_normal_small);
         if (watch_range) {
             unsigned int bad = 0;
             HIP_TRY(c, hipMemcpy(&bad, c->d_nonfinite, sizeof bad, hipMemcpyDeviceToHost));
@@ -1247,6 +1347,11 @@ int nerf_create(int device_id, nerf_ctx **out) try {
         if (sscanf(env, "%f,%f", &m0, &m1) == 2 && m0 > 0.f && m1 > 0.f) { c->cert_margin_floor[0] = m0; c->cert_margin_floor[1] = m1; c->cert_margin[0] = m0; c->cert_margin[1] = m1; }
     }
 #endif
+    if (const char *env = getenv("NERF_GRADIENT_CHUNK")) {
+        const long long v = atoll(env);
+        if (v > 0) c->gradient_chunk = (size_t)v;
+    }
+    if (const char *env = getenv("NERF_DEBUG_NORMALS")) c->debug_normals = atoi(env) > 0;
     if (const char *env = getenv("NERF_ZERO_STEP_SKIP")) c->zero_step_skip = atoi(env) != 0;
     if (const char *env = getenv("NERF_DEBUG_ZSKIP")) {
         if (atoi(env) > 0 && hipMalloc((void **)&c->d_zskip, 2 * sizeof(unsigned long long)) != hipSuccess) c->d_zskip = nullptr;
@@ -1300,6 +1405,8 @@ void nerf_destroy(nerf_ctx *c) {
     if (c->d_mesh) (void)hipFree(c->d_mesh);
     if (c->d_batch) (void)hipFree(c->d_batch);
     if (c->d_comp) (void)hipFree(c->d_comp);
+    if (c->d_normal) (void)hipFree(c->d_normal);
+    if (c->d_stencil) (void)hipFree(c->d_stencil);
     if (c->d_clock) (void)hipFree(c->d_clock);
     if (c->d_zskip) (void)hipFree(c->d_zskip);
     if (c->d_skip) (void)hipFree(c->d_skip);
@@ -1379,8 +1486,6 @@ int nerf_load_network_blob(nerf_ctx *c, int which, const char *blob_path) try {
 
 static int forward_device(nerf_ctx *c, int which, int dtype, const float *d_pts, const float *d_dirs, size_t n, float *d_rgb,
                           float *d_sigma, void *stream);
-// largest batch of nerf_forward_batch*: INT32_MAX minus (persistent workgroups + 1) tiles of the widest kernel (256 points)
-static size_t max_batch_points(int n_cus) { return (size_t)0x7fffffff - ((size_t)n_cus + 1) * 256; }
 
 int nerf_forward_batch_device(nerf_ctx *c, int which, const float *d_pts, const float *d_dirs, size_t n, float *d_rgb,
                               float *d_sigma, void *stream) try {
@@ -1877,11 +1982,14 @@ int nerf_render_image_rgba8(nerf_ctx *c, const nerf_camera *cam, const nerf_rend
 } NERF_CATCH(c)
 
 // ---- ray batches ---------------------------------------------------------------------------------------------------------------------
-int nerf_render_rays_device(nerf_ctx *c, const float *d_origins, size_t n_origins, const float *d_dirs, size_t n_rays, int normalize, float near_,
-                            float far_, const float *d_bounds, const uint32_t *d_rng_index, const nerf_render_opts *opts, const float background[3],
-                            float *d_rgb_out, float *d_depth_out, float *d_opacity_out, void *stream, nerf_stats *stats) try {
+// nerf_render_rays_device and nerf_render_rays_normals_device (want_normals)
+static int rays_device(nerf_ctx *c, const float *d_origins, size_t n_origins, const float *d_dirs, size_t n_rays, int normalize, float near_,
+                       float far_, const float *d_bounds, const uint32_t *d_rng_index, const nerf_render_opts *opts, const float background[3],
+                       float *d_rgb_out, float *d_depth_out, float *d_opacity_out, bool want_normals, float h, float *d_normals_out, void *stream,
+                       nerf_stats *stats) {
     int rc;
     if ((rc = check_ray_batch(c, d_origins, n_origins, d_dirs, n_rays, near_, far_, d_bounds, opts, background, d_rgb_out))) return rc;
+    if (want_normals && (rc = check_normals(c, h, d_normals_out))) return rc;
     if (!c) return fail(nullptr, NERF_ERR_INVALID, "ctx is NULL");
     if (n_rays == 0) return NERF_OK;
     DeviceGuard dg(c->device);
@@ -1893,21 +2001,39 @@ int nerf_render_rays_device(nerf_ctx *c, const float *d_origins, size_t n_origin
         HIP_TRY(c, hipStreamSynchronize(st));
         b.h_origin = origin;
     } else b.d_origins = d_origins;
-    return render_rays_device(c, b, opts, background, d_rgb_out, d_depth_out, d_opacity_out, st, stats);
+    return render_rays_device(c, b, opts, background, d_rgb_out, d_depth_out, d_opacity_out, st, stats, h, want_normals ? d_normals_out : nullptr);
+}
+
+int nerf_render_rays_device(nerf_ctx *c, const float *d_origins, size_t n_origins, const float *d_dirs, size_t n_rays, int normalize, float near_,
+                            float far_, const float *d_bounds, const uint32_t *d_rng_index, const nerf_render_opts *opts, const float background[3],
+                            float *d_rgb_out, float *d_depth_out, float *d_opacity_out, void *stream, nerf_stats *stats) try {
+    return rays_device(c, d_origins, n_origins, d_dirs, n_rays, normalize, near_, far_, d_bounds, d_rng_index, opts, background, d_rgb_out, d_depth_out,
+                       d_opacity_out, false, 0.0f, nullptr, stream, stats);
 } NERF_CATCH(c)
 
-int nerf_render_rays(nerf_ctx *c, const float *origins, size_t n_origins, const float *dirs, size_t n_rays, int normalize, float near_, float far_,
+int nerf_render_rays_normals_device(nerf_ctx *c, const float *d_origins, size_t n_origins, const float *d_dirs, size_t n_rays, int normalize,
+                                    float near_, float far_, const float *d_bounds, const uint32_t *d_rng_index, const nerf_render_opts *opts,
+                                    const float background[3], float *d_rgb_out, float *d_depth_out, float *d_opacity_out, float h,
+                                    float *d_normals_out, void *stream, nerf_stats *stats) try {
+    return rays_device(c, d_origins, n_origins, d_dirs, n_rays, normalize, near_, far_, d_bounds, d_rng_index, opts, background, d_rgb_out, d_depth_out,
+                       d_opacity_out, true, h, d_normals_out, stream, stats);
+} NERF_CATCH(c)
+
+// nerf_render_rays and nerf_render_rays_normals (want_normals)
+static int rays_host(nerf_ctx *c, const float *origins, size_t n_origins, const float *dirs, size_t n_rays, int normalize, float near_, float far_,
                      const float *bounds, const uint32_t *rng_index, const nerf_render_opts *opts, const float background[3], float *rgb_out,
-                     float *depth_out, float *opacity_out, nerf_stats *stats) try {
+                     float *depth_out, float *opacity_out, bool want_normals, float h, float *normals_out, nerf_stats *stats) {
     int rc;
     if ((rc = check_ray_batch(c, origins, n_origins, dirs, n_rays, near_, far_, bounds, opts, background, rgb_out))) return rc;
+    if (want_normals && (rc = check_normals(c, h, normals_out))) return rc;
     if ((rc = check_ray_batch_rays(c, origins, n_origins, dirs, n_rays, normalize, bounds))) return rc;
     if (!c) return fail(nullptr, NERF_ERR_INVALID, "ctx is NULL");
     if (n_rays == 0) return NERF_OK;
     DeviceGuard dg(c->device);
-    // staging (floats): dirs, [origins], [bounds], [rng_index], rgb, [depth], [opacity]
+    // staging (floats): dirs, [origins], [bounds], [rng_index], rgb, [depth], [opacity], [normals]
     const size_t R = n_rays, o_d = 0, o_o = o_d + 3 * R, o_b = o_o + (n_origins == 1 ? 0 : 3 * R), o_i = o_b + (bounds ? 2 * R : 0),
-                 o_c = o_i + (rng_index ? R : 0), o_z = o_c + 3 * R, o_a = o_z + (depth_out ? R : 0), total = o_a + (opacity_out ? R : 0);
+                 o_c = o_i + (rng_index ? R : 0), o_z = o_c + 3 * R, o_a = o_z + (depth_out ? R : 0), o_n = o_a + (opacity_out ? R : 0),
+                 total = o_n + (want_normals ? 3 * R : 0);
     if ((rc = ensure_bytes(c, (void **)&c->d_out, &c->out_floats, total * sizeof(float)))) return rc;
     float *d = c->d_out;
     HIP_TRY(c, hipMemcpyAsync(d + o_d, dirs, 3 * R * sizeof(float), hipMemcpyHostToDevice, c->stream));
@@ -1918,10 +2044,77 @@ int nerf_render_rays(nerf_ctx *c, const float *origins, size_t n_origins, const 
                bounds ? d + o_b : nullptr, rng_index ? (const uint32_t *)(d + o_i) : nullptr};
     nerf_stats local; // a synchronous render always reads its counters (see nerf_render_image_aux)
     if ((rc = render_rays_device(c, b, opts, background, d + o_c, depth_out ? d + o_z : nullptr, opacity_out ? d + o_a : nullptr, c->stream,
-                                 stats ? stats : &local))) return rc;
+                                 stats ? stats : &local, h, want_normals ? d + o_n : nullptr))) return rc;
     HIP_TRY(c, hipMemcpyAsync(rgb_out, d + o_c, 3 * R * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (want_normals) HIP_TRY(c, hipMemcpyAsync(normals_out, d + o_n, 3 * R * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     if (depth_out) HIP_TRY(c, hipMemcpyAsync(depth_out, d + o_z, R * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     if (opacity_out) HIP_TRY(c, hipMemcpyAsync(opacity_out, d + o_a, R * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return NERF_OK;
+}
+
+int nerf_render_rays(nerf_ctx *c, const float *origins, size_t n_origins, const float *dirs, size_t n_rays, int normalize, float near_, float far_,
+                     const float *bounds, const uint32_t *rng_index, const nerf_render_opts *opts, const float background[3], float *rgb_out,
+                     float *depth_out, float *opacity_out, nerf_stats *stats) try {
+    return rays_host(c, origins, n_origins, dirs, n_rays, normalize, near_, far_, bounds, rng_index, opts, background, rgb_out, depth_out, opacity_out,
+                     false, 0.0f, nullptr, stats);
+} NERF_CATCH(c)
+
+int nerf_render_rays_normals(nerf_ctx *c, const float *origins, size_t n_origins, const float *dirs, size_t n_rays, int normalize, float near_,
+                             float far_, const float *bounds, const uint32_t *rng_index, const nerf_render_opts *opts, const float background[3],
+                             float *rgb_out, float *depth_out, float *opacity_out, float h, float *normals_out, nerf_stats *stats) try {
+    return rays_host(c, origins, n_origins, dirs, n_rays, normalize, near_, far_, bounds, rng_index, opts, background, rgb_out, depth_out, opacity_out,
+                     true, h, normals_out, stats);
+} NERF_CATCH(c)
+
+// ---- density gradients at caller points (normal_kernels.hip around the sigma-only launch) -----------------------------------------------
+// The points run in chunks of at most c->gradient_chunk (and of what one MLP launch takes for six stencil points each): per chunk
+// stencil -> sigma-only MLP over 6 m points -> combine, all on `st`, nothing comes back to the host.  A point's gradient depends on that
+// point alone (the sigma-only kernel's bits do not depend on the slot), so the chunking shows in no bit.
+static int density_gradient_device(nerf_ctx *c, int which, const float *d_pts, size_t n, float h, float *d_grad, hipStream_t st) {
+    if (which != NERF_NET_COARSE && which != NERF_NET_FINE) return fail(c, NERF_ERR_INVALID, "which must be NERF_NET_COARSE or NERF_NET_FINE");
+    if (!(std::isfinite(h) && h > 0.0f)) return fail(c, NERF_ERR_INVALID, "h (the central-difference step) must be finite and greater than 0");
+    if (n > 0 && (!d_pts || !d_grad)) return fail(c, NERF_ERR_INVALID, "NULL buffer");
+    if (!c) return fail(nullptr, NERF_ERR_INVALID, "ctx is NULL");
+    if (n == 0) return NERF_OK;
+    if (n > max_batch_points(c->n_cus)) return fail(c, NERF_ERR_INVALID, "batch too large (n plus one grid stride of tiles must fit in int32)");
+    if (!c->net[which].loaded) return fail(c, NERF_ERR_STATE, "network not loaded");
+    DeviceGuard dg(c->device);
+    const size_t chunk = std::max<size_t>(1, std::min({c->gradient_chunk, n, max_batch_points(c->n_cus) / 6}));
+    int rc;
+    if ((rc = ensure_bytes(c, &c->d_stencil, &c->stencil_bytes, 6 * chunk * 4 * sizeof(float)))) return rc;
+    for (size_t i0 = 0; i0 < n; i0 += chunk) {
+        const size_t m = std::min(chunk, n - i0);
+        float *d_spts = (float *)c->d_stencil, *d_ssig = d_spts + 18 * m;
+        NormalStencilArgs sa{};
+        sa.n_live = (uint32_t)m; sa.h = h; sa.src = d_pts + i0; sa.src_stride = n; sa.pts = d_spts;
+        HIP_TRY(c, launch_normal_stencil(sa, st));
+        HIP_TRY(c, launch_sigma_points(c, c->net[which], d_spts, 6 * m, d_ssig, st));
+        NormalCombineArgs ca{(uint32_t)m, d_spts, d_ssig, d_grad + i0, n};
+        HIP_TRY(c, launch_normal_combine(ca, st));
+    }
+    return NERF_OK;
+}
+
+int nerf_density_gradient_batch_device(nerf_ctx *c, int which, const float *d_pts, size_t n, float h, float *d_grad, void *stream) try {
+    return density_gradient_device(c, which, d_pts, n, h, d_grad, (hipStream_t)stream);
+} NERF_CATCH(c)
+
+int nerf_density_gradient_batch(nerf_ctx *c, int which, const float *pts, size_t n, float h, float *grad) try {
+    if (which != NERF_NET_COARSE && which != NERF_NET_FINE) return fail(c, NERF_ERR_INVALID, "which must be NERF_NET_COARSE or NERF_NET_FINE");
+    if (!(std::isfinite(h) && h > 0.0f)) return fail(c, NERF_ERR_INVALID, "h (the central-difference step) must be finite and greater than 0");
+    if (n > 0 && (!pts || !grad)) return fail(c, NERF_ERR_INVALID, "NULL buffer");
+    if (!c) return fail(nullptr, NERF_ERR_INVALID, "ctx is NULL");
+    if (n == 0) return NERF_OK;
+    if (n > max_batch_points(c->n_cus)) return fail(c, NERF_ERR_INVALID, "batch too large (n plus one grid stride of tiles must fit in int32)");
+    if (!c->net[which].loaded) return fail(c, NERF_ERR_STATE, "network not loaded");
+    DeviceGuard dg(c->device);
+    int rc;
+    if ((rc = ensure_bytes(c, &c->d_scratch, &c->scratch_bytes, n * 6 * sizeof(float)))) return rc;
+    float *d_pts = (float *)c->d_scratch, *d_grad = d_pts + 3 * n;
+    HIP_TRY(c, hipMemcpyAsync(d_pts, pts, 3 * n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if ((rc = density_gradient_device(c, which, d_pts, n, h, d_grad, c->stream))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(grad, d_grad, 3 * n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return NERF_OK;
 } NERF_CATCH(c)

@@ -14,6 +14,9 @@
 // --rays FILE renders the caller's rays (nerf_render_rays): n x 6 little-endian f32 {origin, direction} (directions are normalised on the device),
 // near / far from the scene JSON unless --rays-bounds FILE gives n x 2 {near, far}; --rays-out FILE receives n x 3 f32 linear RGB (over --background).
 // --coarse / --fine / --seed / --dtype / --coarse-only apply; with no image flag beside it the render is skipped.
+// --rays-normals FILE beside --rays-out adds n x 3 f32 per-ray normals (nerf_render_rays_normals; --normals-step H, default 1e-3, is the
+// central-difference step).  --normals FILE.ppm writes the normal map of the image run, encoded 0.5 n + 0.5 per component: the window's rays
+// (nerf_stage_ray_dirs, rng_index = row * nx + col) go through nerf_render_rays_normals once more on the first context.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -34,7 +37,9 @@ static void usage(const char *argv0) {
             "           [--grid-out FILE.raw] [--grid-occupancy FILE.bits] [--mesh FILE.ply [--mesh-iso V] [--mesh-colour]\n"
             "            [--mesh-keep-largest K] [--mesh-min-points M]]]\n"
             "           (at least one of the three files; no image flag: no render)\n"
-            "          [--rays FILE.f32 --rays-out FILE.f32 [--rays-bounds FILE.f32]]   (n x 6 f32 in, n x 3 f32 out; no image flag: no render)\n"
+            "          [--rays FILE.f32 --rays-out FILE.f32 [--rays-bounds FILE.f32] [--rays-normals FILE.f32]]\n"
+            "           (n x 6 f32 in, n x 3 f32 out; no image flag: no render)\n"
+            "          [--normals FILE.ppm] [--normals-step H]   (normal map of the image run, 0.5 n + 0.5; H: central-difference step, default 1e-3)\n"
             "defaults: --scene lego_rust --width 256 --height 256 --coarse 64 --fine 128 --out output.ppm --mesh-iso 10\n",
             argv0);
 }
@@ -42,7 +47,8 @@ static void usage(const char *argv0) {
 int main(int argc, char **argv) {
     std::string scene = getenv("NERF_SCENE_DIR") ? getenv("NERF_SCENE_DIR") : "lego_rust";
     std::string out = "output.ppm", depth_path, opacity_path, rgba_path;
-    std::string grid_out, grid_bits_path, mesh_path, rays_path, rays_out_path, rays_bounds_path;
+    std::string grid_out, grid_bits_path, mesh_path, rays_path, rays_out_path, rays_bounds_path, rays_normals_path, normals_path;
+    float normals_step = 1e-3f;
     float mesh_iso = 10.0f;
     bool mesh_colour = false, have_mesh_opt = false;
     nerf_component_filter mesh_filter = {0, 0}; // --mesh-keep-largest / --mesh-min-points: only the kept components of the inside points are meshed
@@ -101,6 +107,9 @@ int main(int argc, char **argv) {
         else if (a == "--rays") rays_path = next();
         else if (a == "--rays-out") rays_out_path = next();
         else if (a == "--rays-bounds") rays_bounds_path = next();
+        else if (a == "--rays-normals") rays_normals_path = next();
+        else if (a == "--normals") { normals_path = next(); want_image = true; }
+        else if (a == "--normals-step") normals_step = strtof(next(), nullptr);
         else if (a == "--mesh-iso") { mesh_iso = strtof(next(), nullptr); have_mesh_opt = true; }
         else if (a == "--mesh-colour") { mesh_colour = true; have_mesh_opt = true; }
         else if (a == "--mesh-keep-largest") { mesh_filter.keep_largest = (uint32_t)strtoul(next(), nullptr, 10); have_mesh_opt = true; }
@@ -122,7 +131,7 @@ int main(int argc, char **argv) {
     if (want_grid && (!have_grid_lo || !have_grid_step || (grid_out.empty() && grid_bits_path.empty() && mesh_path.empty()))) { usage(argv[0]); return 2; }
     if (!want_grid && (have_grid_lo || have_grid_step || !grid_out.empty() || !grid_bits_path.empty() || !mesh_path.empty())) { usage(argv[0]); return 2; }
     if (mesh_path.empty() && have_mesh_opt) { usage(argv[0]); return 2; }
-    if (rays_path.empty() != rays_out_path.empty() || (rays_path.empty() && !rays_bounds_path.empty())) { usage(argv[0]); return 2; }
+    if (rays_path.empty() != rays_out_path.empty() || (rays_path.empty() && !(rays_bounds_path.empty() && rays_normals_path.empty()))) { usage(argv[0]); return 2; }
 
     // one context per GPU (--gpus N: devices 0..N-1, the rayon fan-out of src/lib.rs:533-550 becomes a fan-out over devices)
     if (gpus < 1) { usage(argv[0]); return 2; }
@@ -155,18 +164,25 @@ int main(int argc, char **argv) {
         }
         nerf_camera jc; // near and far of the scene
         if (nerf_camera_from_json((scene + "/tf_reference_samples.json").c_str(), width, height, &jc)) { fprintf(stderr, "error: %s\n", nerf_last_error(nullptr)); return 1; }
-        std::vector<float> o(3 * n), d(3 * n), rgb(3 * n);
+        std::vector<float> o(3 * n), d(3 * n), rgb(3 * n), normals(rays_normals_path.empty() ? 0 : 3 * n + 1); // + 1: never a NULL pointer, also for n = 0
         for (size_t r = 0; r < n; ++r)
             for (int k = 0; k < 3; ++k) { o[3 * r + k] = rays[6 * r + k]; d[3 * r + k] = rays[6 * r + 3 + k]; }
         nerf_stats rst;
-        if (nerf_render_rays(ctx, o.data(), n, d.data(), n, 1, jc.near_, jc.far_, ray_bounds.empty() ? nullptr : ray_bounds.data(), nullptr, &opts,
-                             have_background ? background : nullptr, rgb.data(), nullptr, nullptr, &rst)) {
+        const float *rb = ray_bounds.empty() ? nullptr : ray_bounds.data(), *bg = have_background ? background : nullptr;
+        if (normals.empty() ? nerf_render_rays(ctx, o.data(), n, d.data(), n, 1, jc.near_, jc.far_, rb, nullptr, &opts, bg, rgb.data(), nullptr, nullptr, &rst)
+                            : nerf_render_rays_normals(ctx, o.data(), n, d.data(), n, 1, jc.near_, jc.far_, rb, nullptr, &opts, bg, rgb.data(), nullptr, nullptr,
+                                                       normals_step, normals.data(), &rst)) {
             fprintf(stderr, "error: %s\n", nerf_last_error(ctx));
             return 1;
         }
-        FILE *f = fopen(rays_out_path.c_str(), "wb");
-        const bool ok = f && fwrite(rgb.data(), sizeof(float), rgb.size(), f) == rgb.size();
-        if ((f && fclose(f)) || !ok) { fprintf(stderr, "error: cannot write %s\n", rays_out_path.c_str()); return 1; }
+        auto put = [](const std::string &path, const float *v, size_t count) {
+            FILE *f = fopen(path.c_str(), "wb");
+            const bool ok = f && fwrite(v, sizeof(float), count, f) == count;
+            if ((f && fclose(f)) || !ok) { fprintf(stderr, "error: cannot write %s\n", path.c_str()); return false; }
+            return true;
+        };
+        if (!put(rays_out_path, rgb.data(), rgb.size())) return 1;
+        if (!normals.empty() && !put(rays_normals_path, normals.data(), 3 * n)) return 1;
         printf("%zu rays (%d coarse + %d fine samples): device %.2f ms in %u pass(es)\n", n, opts.n_coarse, opts.coarse_only ? 0 : opts.n_fine, n ? rst.ms_total : 0.0,
                n ? rst.n_passes : 0u);
         if (!want_image && !want_grid) {
@@ -317,6 +333,24 @@ int main(int argc, char **argv) {
     if ((d_map && nerf_save_pfm(depth_path.c_str(), ow, oh, d_map)) || (o_map && nerf_save_pfm(opacity_path.c_str(), ow, oh, o_map))) {
         fprintf(stderr, "error: %s\n", nerf_last_error(nullptr));
         return 1;
+    }
+    if (!normals_path.empty()) { // the window's rays as a batch: colour as the frame above, plus the normals (there is no image entry point for them)
+        const int x0 = opts.crop_w > 0 ? opts.crop_x0 : 0, y0 = opts.crop_h > 0 ? opts.crop_y0 : 0;
+        const size_t n = (size_t)ow * oh;
+        std::vector<float> dirs(3 * n), rgb(3 * n), normals(3 * n);
+        std::vector<uint32_t> index(n);
+        for (int i = 0; i < oh; ++i)
+            for (int j = 0; j < ow; ++j) index[(size_t)i * ow + j] = (uint32_t)(y0 + i) * (uint32_t)width + (uint32_t)(x0 + j);
+        nerf_render_opts ro = opts; // ray batches have no pixel grid; what else they refuse (ssaa, the skip modes) is the library's error
+        ro.crop_x0 = ro.crop_y0 = ro.crop_w = ro.crop_h = 0;
+        if (nerf_stage_ray_dirs(ctx, &cam, x0, y0, ow, oh, 1, dirs.data()) ||
+            nerf_render_rays_normals(ctx, cam.pos, 1, dirs.data(), n, 0, cam.near_, cam.far_, nullptr, index.data(), &ro, nullptr, rgb.data(), nullptr, nullptr,
+                                     normals_step, normals.data(), nullptr)) {
+            fprintf(stderr, "error: %s\n", nerf_last_error(ctx));
+            return 1;
+        }
+        for (float &v : normals) v = 0.5f * v + 0.5f; // a zero normal (a ray that met nothing) becomes mid grey
+        if (nerf_save_ppm(normals_path.c_str(), ow, oh, normals.data())) { fprintf(stderr, "error: %s\n", nerf_last_error(nullptr)); return 1; }
     }
     for (nerf_ctx *c : ctxs) nerf_destroy(c);
     return 0;

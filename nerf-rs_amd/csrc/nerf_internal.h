@@ -41,7 +41,8 @@ constexpr float kCertMarginCoarseF16 = 0.25f, kCertMarginFineF16 = 0.5f;
 
 struct EvPair {
     hipEvent_t a, b;
-    int kind; // 0 coarse mlp, 1 fine mlp (dominant), 2 other, 4 colour head of skip_dead, 5 the colour-producing mlp of a ray batch (not in `dominant`)
+    int kind; // 0 coarse mlp, 1 fine mlp (dominant), 2 other, 4 colour head of skip_dead, 5 the colour-producing mlp of a ray batch (not in `dominant`),
+              // 6 the sigma-only stencil launch of a normals render, 7 its small kernels (neither in `dominant`)
     uint64_t points;
 };
 
@@ -70,6 +71,13 @@ struct nerf_ctx {
     void *d_mesh = nullptr; size_t mesh_bytes = 0;
     // lattice components (components_kernels.h): labels, sizes / keep flags; allocated only when a filter or a component query is asked for
     void *d_comp = nullptr; size_t comp_bytes = 0;
+    // surface normals (normal_kernels.h): per pass {weights, live list: 4 B per sample each; count, base per ray; block sums; total}, and
+    // per stencil point 16 B {3 coordinates, sigma}; the latter also serves nerf_density_gradient_batch, chunk by chunk
+    void *d_normal = nullptr; size_t normal_bytes = 0;
+    void *d_stencil = nullptr; size_t stencil_bytes = 0;
+    size_t gradient_chunk = (size_t)1 << 20;             // points per internal chunk of nerf_density_gradient_batch (NERF_GRADIENT_CHUNK)
+    bool debug_normals = false;                          // NERF_DEBUG_NORMALS=1: a normals render with stats prints its live share and kernel times
+    uint64_t normal_live = 0, normal_samples = 0;        // of the last normals render: live / composited samples
     // skip_dead: device queue/counters {u32 ray counter, u32 live count, u64 chunk count} per MLP launch of a render, the
     // compacted trunk outputs of the live samples and their sample indices
     unsigned int *d_seq = nullptr; size_t seq_slots = 0;
