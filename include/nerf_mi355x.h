@@ -174,6 +174,10 @@ typedef struct {
  *                           keeps its bits; a network with a non-finite parameter runs with the skip off on its own.  Inputs and
  *                           activations need not be finite for that: subnormal, NaN, infinite and overflowing values give the same bits
  *                           with and without the skip (measured: profiles/zskip_counts.txt), whatever those bits are worth.
+ *   NERF_RAY_GROUPING=0     ray-mode NERF_MLP_F32 launches give every 256-thread workgroup 128 consecutive samples.  Default: its four waves
+ *                           take the same 32-sample segment of four neighbouring rays (whenever the samples per ray are a multiple of 32
+ *                           and there are four rays), so that they skip alike and wait less for each other.  Which waves share a
+ *                           workgroup changes no value: every output keeps its bits (nerf_debug_ray_grouping shows the mapping).
  *   NERF_DEBUG_ZSKIP=1      diagnostic: every f32 MLP launch synchronises and prints its executed / total ReLU k-steps to stderr.
  *   NERF_DEBUG_CLOCK=1      diagnostic: nerf_debug_shader_clock_mhz. */
 int nerf_create(int device_id, nerf_ctx **out);
@@ -225,6 +229,12 @@ int nerf_debug_split_bf16x3(const float *values, size_t n, uint16_t *parts /* 3 
 int nerf_debug_certify_policy(float margin, uint64_t audited, uint64_t violations, float headroom, float max_error, float *new_margin);
 /* The same for the NERF_MLP_F16X2 packer: two f16 parts (IEEE binary16 bit patterns), v = p0 + p1 up to 2^-22 |v|.  Host-only. */
 int nerf_debug_split_f16x2(const float *values, size_t n, uint16_t *parts /* 2 n */);
+/* Diagnostic: which samples the waves of a ray-mode NERF_MLP_F32 launch of n_rays x samples_per_ray samples evaluate (see NERF_RAY_GROUPING at
+ * nerf_create; `enabled`: the context's switch).  For every workgroup tile T = 0 .. ceil(n_rays samples_per_ray / 128) - 1 and wave w = 0..3,
+ * first_slot_of_wave_tile[4 T + w] = first of the wave's 32 consecutive sample slots (slot = ray * samples_per_ray + sample), from the function
+ * the kernel calls.  Grouped (enabled, samples_per_ray a multiple of 32, n_rays >= 4): wave w of tile T = b S + j, S = samples_per_ray / 32,
+ * j < S, b < n_rays / 4, holds segment j of ray 4 b + w; the last n_rays % 4 rays and every other launch: slot 128 T + 32 w.  Host-only. */
+int nerf_debug_ray_grouping(int n_rays, int samples_per_ray, int enabled, int32_t *first_slot_of_wave_tile);
 
 /* ---- S2: Network::forward_batch (src/network.rs:197-237) -------------------------------------------------- */
 /* host pointers, synchronous.  n == 0 is a no-op (src/network.rs:199-201).

@@ -211,11 +211,11 @@ __device__ __forceinline__ int list_length(const Args &A) {
     return (int)(f + b);
 }
 
+// slot i of the launch (not yet clamped); the f32 kernel's ray mode forms it through the ray grouping (mlp_layout.h ray_group_first_slot)
 template <int MODE, class Args>
-__device__ __forceinline__ RawIn load_raw(const Args &A, int tile_idx, int wave, int p) {
+__device__ __forceinline__ RawIn load_raw_at(const Args &A, int i) {
     using namespace nerfmlp;
     RawIn r;
-    int i = tile_idx * kPointsPerBlock + wave * kPointsPerWave + p;
     if (MODE == 2) { // slot i of a device-side sample list: entry = sample index | (audited certificate ? 1 << 31 : 0)
         unsigned nfront, nback;
         list_parts(A, nfront, nback);
@@ -252,6 +252,11 @@ __device__ __forceinline__ RawIn load_raw(const Args &A, int tile_idx, int wave,
         r.dx = A.ray_dirs[3 * (size_t)ray]; r.dy = A.ray_dirs[3 * (size_t)ray + 1]; r.dz = A.ray_dirs[3 * (size_t)ray + 2];
     }
     return r;
+}
+// lane p of wave `wave` of workgroup tile `tile_idx`, 128 consecutive slots per tile
+template <int MODE, class Args>
+__device__ __forceinline__ RawIn load_raw(const Args &A, int tile_idx, int wave, int p) {
+    return load_raw_at<MODE>(A, tile_idx * nerfmlp::kPointsPerBlock + wave * nerfmlp::kPointsPerWave + p);
 }
 
 template <int MODE, class Args>

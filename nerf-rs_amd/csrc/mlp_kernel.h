@@ -47,6 +47,11 @@ struct MlpArgs {
     // tile_steps; bit-identical for a network whose parameters are all finite -- DevNet.zero_skip).  0: every k-step is executed.
     int zero_skip;
     unsigned long long *zskip_stats; // optional diagnostic (NERF_DEBUG_ZSKIP): {executed, total} ReLU k-steps of the launch, printed to stderr
+    // f32 kernels, MLP_MODE_RAYS (appended likewise): ray grouping (mlp_layout.h ray_group_first_slot).  The caller sets ray_grouping (the
+    // context's switch, NERF_RAY_GROUPING); nerf_mlp_launch derives the other two from the launch's shape, whatever the caller left in them.
+    int ray_grouping;   // 0: every workgroup tile is 128 consecutive samples
+    int group_segments; // S = samples_per_ray / 32 of a grouped launch, 0 = off
+    int group_tiles;    // workgroup tiles [0, group_tiles) are grouped
 };
 
 // Sets the dynamic-LDS attribute of every kernel instantiation on the current device.

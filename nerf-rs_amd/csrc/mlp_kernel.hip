@@ -18,6 +18,8 @@
 //     network (host_util.cpp fold_network): the colour head is relu(h7) -> viewdirs' -> rgb.
 //   * k-steps of the 256-wide layers whose ReLU'd B register is zero on all 64 lanes are skipped, exactly (mlp_f32_core.hip.h
 //     tile_steps; MlpArgs.zero_skip).
+//   * in ray mode the four waves of a workgroup take the same 32-sample segment of four neighbouring rays (mlp_layout.h ray grouping):
+//     they meet at every chunk's barrier, and rays of like depth have like numbers of dead k-steps.
 // Per 32-point wave tile: at most 8256 MFMAs (full; 9280 before the fold) / 7680 (sigma only) x 64 cycles.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -77,17 +79,24 @@ __global__ __launch_bounds__(256, 1) void nerf_mlp_kernel(const MlpArgs A) {
     const int n_tiles = (n_points + kPointsPerBlock - 1) / kPointsPerBlock;
     // what load_raw fetches: the sigma-only point instance (nerf_density_batch) has no directions to read
     constexpr int LOAD = (!FULL && MODE == MLP_MODE_POINTS) ? 4 : MODE;
+    // first slot of this wave's 32 points in workgroup tile T.  Ray mode: through the ray grouping (mlp_layout.h: the four waves take one
+    // segment of four neighbouring rays; MlpArgs.group_segments == 0: ungrouped); every other mode 128 consecutive slots per workgroup
+    auto first_slot = [&](int T) {
+        return MODE == MLP_MODE_RAYS ? ray_group_first_slot(T, wave, A.group_segments, A.group_tiles) : T * kPointsPerBlock + wave * kPointsPerWave;
+    };
+    int slot0_next = first_slot(blockIdx.x); // wave-uniform, formed once per tile: for the look-ahead, then carried over
 #if NERF_PREFETCH_INPUTS
-    RawIn nxt = load_raw<LOAD>(A, blockIdx.x, wave, p);
+    RawIn nxt = load_raw_at<LOAD>(A, slot0_next + p);
 #endif
     for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const int slot = tile * kPointsPerBlock + wave * kPointsPerWave + p;
+        const int slot = slot0_next + p;
         const bool valid = slot < n_points;
+        slot0_next = first_slot(tile + gridDim.x);
 #if NERF_PREFETCH_INPUTS
         const RawIn in = nxt;
-        nxt = load_raw<LOAD>(A, tile + gridDim.x, wave, p); // consumed one tile (~250 us) later
+        nxt = load_raw_at<LOAD>(A, slot0_next + p); // consumed one tile (~250 us) later
 #else
-        const RawIn in = load_raw<LOAD>(A, tile, wave, p);
+        const RawIn in = load_raw_at<LOAD>(A, slot);
 #endif
         float px, py, pz;
         point_of<MODE>(A, in, px, py, pz);
@@ -217,6 +226,16 @@ hipError_t nerf_mlp_init() {
     return hipSuccess;
 }
 
+// Every ray-mode launch comes through here (plain and skip_empty renders, shared-origin ray batches, coarse and fine passes): the ray
+// grouping of this launch, from its shape and the context's switch (MlpArgs.ray_grouping)
+static hipError_t launch_mlp_rays(const MlpArgs &a, bool full, int n_blocks, hipStream_t stream) {
+    MlpArgs g = a;
+    const RayGrouping rg = ray_grouping_of(a.n_points, a.samples_per_ray, a.ray_grouping != 0);
+    g.group_segments = rg.segments;
+    g.group_tiles = rg.group_tiles;
+    return full ? launch_t<true, MLP_MODE_RAYS>(g, n_blocks, stream) : launch_t<false, MLP_MODE_RAYS>(g, n_blocks, stream);
+}
+
 hipError_t nerf_mlp_launch(const MlpArgs &a, bool full, int n_blocks, hipStream_t stream) {
     if (a.n_points <= 0) return hipSuccess;
     const int n_tiles = (a.n_points + kPointsPerBlock - 1) / kPointsPerBlock;
@@ -234,5 +253,5 @@ hipError_t nerf_mlp_launch(const MlpArgs &a, bool full, int n_blocks, hipStream_
     }
     if (a.mode == MLP_MODE_POINTS)
         return full ? launch_t<true, MLP_MODE_POINTS>(a, n_blocks, stream) : launch_t<false, MLP_MODE_POINTS>(a, n_blocks, stream);
-    return full ? launch_t<true, MLP_MODE_RAYS>(a, n_blocks, stream) : launch_t<false, MLP_MODE_RAYS>(a, n_blocks, stream);
+    return launch_mlp_rays(a, full, n_blocks, stream);
 }

@@ -27,6 +27,43 @@ constexpr int kPointsPerWave = 32;
 constexpr int kWavesPerBlock = 4;
 constexpr int kPointsPerBlock = kPointsPerWave * kWavesPerBlock;
 
+// ---- ray grouping (f32 kernels, MLP_MODE_RAYS): which 32 consecutive sample slots a wave of a workgroup tile evaluates.
+// Ungrouped, wave w of workgroup tile T takes wave tile 4 T + w (slots 128 T + 32 w ...): 128 consecutive samples, most of one ray.  The
+// four waves meet at a barrier per weight chunk, so with zero-step skipping a chunk lasts as long as the wave with the fewest dead
+// k-steps -- and the wave at the surface has fewer than the three in empty space, for the whole tile.  Grouped, the four
+// waves take the SAME segment of four neighbouring rays, which are alike: with S = samples_per_ray / 32 segments per ray, rays go in
+// blocks of four, and wave w of workgroup tile T = b S + j (j < S) takes segment j of ray 4 b + w = wave tile 4 b S + w S + j.  The
+// last n_rays % 4 rays (workgroup tiles >= group_tiles) keep the ungrouped mapping.  A permutation of the wave tiles: every point is
+// evaluated alone, so no value changes.  The kernel and nerf_debug_ray_grouping (the tests) call the same two functions.
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define NERF_HOST_DEVICE __host__ __device__
+#else
+#define NERF_HOST_DEVICE
+#endif
+struct RayGrouping {
+    int segments;    // S; 0 = grouping off
+    int group_tiles; // (n_rays / 4) * S workgroup tiles are grouped
+};
+// on iff allowed, whole 32-sample segments per ray, and at least one block of four rays (S = 1 gives the ungrouped mapping again)
+NERF_HOST_DEVICE inline RayGrouping ray_grouping_of(int n_points, int samples_per_ray, bool allowed) {
+    RayGrouping g = {0, 0};
+    if (!allowed || samples_per_ray <= 0 || samples_per_ray % kPointsPerWave != 0 || n_points <= 0) return g;
+    const int n_rays = n_points / samples_per_ray;
+    if (n_rays < kWavesPerBlock) return g;
+    g.segments = samples_per_ray / kPointsPerWave;
+    g.group_tiles = (n_rays / kWavesPerBlock) * g.segments;
+    return g;
+}
+// first sample slot of wave `wave` of workgroup tile `tile` (one wave-uniform division per call)
+NERF_HOST_DEVICE inline int ray_group_first_slot(int tile, int wave, int segments, int group_tiles) {
+    int wave_tile = tile * kWavesPerBlock + wave;
+    if (segments > 0 && tile < group_tiles) {
+        const int b = (int)((unsigned)tile / (unsigned)segments), j = tile - b * segments;
+        wave_tile = (b * kWavesPerBlock + wave) * segments + j;
+    }
+    return wave_tile * kPointsPerWave;
+}
+
 // k-steps per layer (K padded to the 32-slot tiles) and output tiles
 constexpr int kStepsL0 = 32;    // 64 encoding slots (63 used)
 constexpr int kStepsHid = 128;  // 256

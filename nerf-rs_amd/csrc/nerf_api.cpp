@@ -120,8 +120,11 @@ static const float *stream_of(const DevNet &n, int dtype) {
 // the small block that goes with stream_of: the f32 kernels read the folded image, every other arithmetic the packed one
 static const float *small_of(const DevNet &n, int dtype) { return dtype == NERF_MLP_F32 ? n.small_f32 : n.small; }
 // zero-step skipping of the f32 kernels (MlpArgs / SeqArgs; the other arithmetics ignore the two fields): per network, decided at load
+// ... and the context's ray grouping (MlpArgs.ray_grouping: the ray-mode launcher of the f32 kernels reads it, nothing else does)
+static void grouping_of(const nerf_ctx *c, MlpArgs &a) { a.ray_grouping = c->ray_grouping ? 1 : 0; }
+static void grouping_of(const nerf_ctx *, SeqArgs &) {}
 template <class Args>
-static void zskip_of(const nerf_ctx *c, const DevNet &n, Args &a) { a.zero_skip = n.zero_skip ? 1 : 0; a.zskip_stats = c->d_zskip; }
+static void zskip_of(const nerf_ctx *c, const DevNet &n, Args &a) { a.zero_skip = n.zero_skip ? 1 : 0; a.zskip_stats = c->d_zskip; grouping_of(c, a); }
 // NERF_V2_F16_FULL (experiment, variant builds): NERF_MLP_BF16 renders run the f16 twin of the bf16 kernel (fused ray-mode launches only)
 static hipError_t launch_mlp(const nerf_ctx *c, int dtype, const MlpArgs &a, bool full, hipStream_t st) {
 #ifdef NERF_V2_F16_FULL
@@ -1353,6 +1356,7 @@ int nerf_create(int device_id, nerf_ctx **out) try {
     }
     if (const char *env = getenv("NERF_DEBUG_NORMALS")) c->debug_normals = atoi(env) > 0;
     if (const char *env = getenv("NERF_ZERO_STEP_SKIP")) c->zero_step_skip = atoi(env) != 0;
+    if (const char *env = getenv("NERF_RAY_GROUPING")) c->ray_grouping = atoi(env) != 0;
     if (const char *env = getenv("NERF_DEBUG_ZSKIP")) {
         if (atoi(env) > 0 && hipMalloc((void **)&c->d_zskip, 2 * sizeof(unsigned long long)) != hipSuccess) c->d_zskip = nullptr;
     }

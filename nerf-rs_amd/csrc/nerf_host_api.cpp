@@ -169,6 +169,19 @@ int nerf_debug_zero_skip_network_dir(const char *dir, int *eligible) try {
     return NERF_OK;
 } NERF_HOST_CATCH
 
+int nerf_debug_ray_grouping(int n_rays, int samples_per_ray, int enabled, int32_t *first_slot_of_wave_tile) try {
+    using namespace nerfmlp;
+    if (n_rays <= 0 || samples_per_ray <= 0 || !first_slot_of_wave_tile) return fail_noctx(NERF_ERR_INVALID, "n_rays and samples_per_ray must be > 0, the table not NULL");
+    const long long n_points = (long long)n_rays * samples_per_ray;
+    if (n_points > INT32_MAX - kPointsPerBlock) return fail_noctx(NERF_ERR_INVALID, "too many samples for one launch");
+    const int n_tiles = ((int)n_points + kPointsPerBlock - 1) / kPointsPerBlock;
+    const RayGrouping g = ray_grouping_of((int)n_points, samples_per_ray, enabled != 0); // as the ray-mode launcher of the f32 kernels (mlp_kernel.hip)
+    for (int tile = 0; tile < n_tiles; ++tile)
+        for (int wave = 0; wave < kWavesPerBlock; ++wave)
+            first_slot_of_wave_tile[tile * kWavesPerBlock + wave] = ray_group_first_slot(tile, wave, g.segments, g.group_tiles);
+    return NERF_OK;
+} NERF_HOST_CATCH
+
 int nerf_camera_from_json(const char *path, int width, int height, nerf_camera *out) try {
     if (!path || !out) return fail_noctx(NERF_ERR_INVALID, "NULL argument");
     std::string err;

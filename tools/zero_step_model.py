@@ -11,7 +11,10 @@ benchmark's own workload, and what does skipping its MFMAs buy while the four wa
   * a k-step = register r of input tile t = units 32 t + ROW_OF[r][0 / 1] (mlp_layout.h regFeature) over a wave's 32 points;
   * timing model: a chunk (8 macro-steps) takes as long as its slowest wave; an executed macro-step costs 1, a skipped one SKIP_COST
     (its LDS reads and DMA piece remain) -- an ASSUMPTION, bracketed by 0.10 and 0.25; the encoding tiles of dense0 / dense5 and the
-    direction tile are dense.
+    direction tile are dense;
+  * ray grouping (mlp_layout.h ray_group_first_slot): the same wave tiles, but the four waves of a workgroup tile hold the same 32-sample
+    segment of four adjacent rays instead of 128 consecutive samples -- the row "grouped: 4 adjacent rays x one segment", at the skip
+    cost the MI355X showed (0.28).
 
 Reads only oracle/ and lego_rust/.  Writes profiles/zskip_cpu_model.txt."""
 import os
@@ -27,6 +30,8 @@ SCENE = os.path.join(ROOT, "lego_rust")
 ROW_OF = np.array([[(r & 3) + 8 * (r >> 2) + 4 * h for h in (0, 1)] for r in range(16)])
 SKIP_COSTS = (0.10, 0.25)
 FRAME_MS, FINE_MS, COARSE_MS = 1149.0, 875.0, 271.0   # profiles/fold_summary.md
+SKIP_COST_MEASURED = 0.28                               # the cost that reproduces the measured fine kernel (0.8838 against 0.8835)
+ZSKIP_FRAME_MS, ZSKIP_FINE_MS, ZSKIP_COARSE_MS = 1026.0, 769.0, 254.0   # the frame with zero-step skipping, ungrouped
 
 
 def load(d):
@@ -84,6 +89,13 @@ def model_time(live_layers, dense_steps, nt4_last, skip_cost):
     return (total + n_wg * dense_steps) / (full + n_wg * dense_steps)
 
 
+def group_rays(live, segments):
+    """live[wave, 128] in ray-major wave order (wave tile g = ray * segments + segment) -> the same rows in the order the grouped launch
+    hands them to (workgroup tile, wave): tile b * segments + j, wave w = segment j of ray 4 b + w.  The ray count is a multiple of 4 here."""
+    g = np.arange(live.shape[0]).reshape(-1, 4, segments).transpose(0, 2, 1).reshape(-1)
+    return live[g]
+
+
 def main():
     oracle_py.build(); oracle_py.lib()
     nets = {"coarse": oracle_py.Net(os.path.join(SCENE, "coarse")), "fine": oracle_py.Net(os.path.join(SCENE, "fine"))}
@@ -103,7 +115,7 @@ def main():
                 pts[k].append((origin[None, :] + d["dir_hat"][None, :] * t[:, None]).astype(np.float32))
                 sig[k].append(s)
     lines = ["zero-step skipping: CPU measurement on 320 rays of the 800x800 view + chunk-coupled timing model (tools/zero_step_model.py)", ""]
-    ratios = {}
+    ratios, grouping = {}, {}
     for k in ("fine", "coarse"):
         P = np.concatenate(pts[k]); S = np.concatenate(sig[k])
         acts, s = trunk(W[k], P)
@@ -129,11 +141,19 @@ def main():
             ratios[(k, name)] = r
             ex = np.mean([l.mean() for l in live])
             lines.append(f"  {name:28s}: executed share of ReLU k-steps {ex:.3f}; kernel time x {r[0]:.3f} (skip cost {SKIP_COSTS[0]}) .. {r[1]:.3f} ({SKIP_COSTS[1]})")
+        # the same wave tiles handed out in groups: the 320 rays come in runs of 8 adjacent columns = two blocks of four
+        live = [step_live(acts[i]) for i in consumers]
+        segments = (192 if full else 64) // 32
+        grouping[k] = (model_time(live, dense_steps, full, SKIP_COST_MEASURED),
+                       model_time([group_rays(l, segments) for l in live], dense_steps, full, SKIP_COST_MEASURED))
+        lines.append(f"  skip cost {SKIP_COST_MEASURED} (MI355X): as packed x {grouping[k][0]:.4f}; grouped: 4 adjacent rays x one segment x {grouping[k][1]:.4f}")
         lines.append("")
     lines.append(f"frame (from {FRAME_MS:.0f} ms = {FINE_MS:.0f} fine + {COARSE_MS:.0f} coarse + 3):")
     for name in ("as packed", "sorted, same rays", "sorted, 4096 uniform points"):
         ms = [3.0 + FINE_MS * ratios[("fine", name)][i] + COARSE_MS * ratios[("coarse", name)][i] for i in range(2)]
         lines.append(f"  {name:28s}: {ms[0]:.0f} .. {ms[1]:.0f} ms")
+    ms = [3.0 + ZSKIP_FINE_MS * grouping["fine"][i] / grouping["fine"][0] + ZSKIP_COARSE_MS * grouping["coarse"][i] / grouping["coarse"][0] for i in range(2)]
+    lines.append(f"ray grouping at skip cost {SKIP_COST_MEASURED} (from {ZSKIP_FRAME_MS:.0f} ms = {ZSKIP_FINE_MS:.0f} fine + {ZSKIP_COARSE_MS:.0f} coarse + 3): as packed {ms[0]:.0f} ms, grouped {ms[1]:.0f} ms")
     out = os.path.join(ROOT, "profiles", "zskip_cpu_model.txt")
     open(out, "w").write("\n".join(lines) + "\n")
     print("\n".join(lines))
