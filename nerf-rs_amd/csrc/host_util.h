@@ -75,7 +75,7 @@ int save_pam(const std::string &path, int width, int height, const uint8_t *rgba
 int save_ply(const std::string &path, size_t n_vertices, const float *vertices, const float *normals, const float *rgb, size_t n_triangles,
              const uint32_t *triangles, std::string &err);
 
-// certify_zero's audit policy (nerf_api.cpp render_device; exposed host-only as nerf_debug_certify_policy so that it is tested without a
+// certify_zero's audit policy (nerf_render.cpp render_device; exposed host-only as nerf_debug_certify_policy so that it is tested without a
 // GPU).  Given what the audit of one network found in one frame, decide whether the frame stands and, if not, the widened margin:
 //   a violation (an audited certificate with a positive exact density)              -> max(4 m, 4 err)
 //   least headroom below m / 2 (an audited sample closer to a positive density)     -> max(2 m, 4 err)

@@ -195,7 +195,7 @@ __device__ __forceinline__ void rgb_head(const Tiles &V, const LDS_AS float *sma
 struct RawIn { float a, b, c, dx, dy, dz; };
 
 // MLP_MODE_LIST: the list's length lives on the device; n_points is its CAPACITY (entries beyond it were counted, not stored: the host
-// renders such a frame again with a larger list, nerf_api.cpp).  The list has a front part growing up from entry 0 and an optional back
+// renders such a frame again with a larger list, nerf_render.cpp render_device).  The list has a front part growing up from entry 0 and an optional back
 // part growing down from entry n_points - 1 (MlpArgs.point_list_count_back).
 template <class Args>
 __device__ __forceinline__ void list_parts(const Args &A, unsigned &front, unsigned &back) {

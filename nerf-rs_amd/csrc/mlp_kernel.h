@@ -25,7 +25,7 @@ struct MlpArgs {
     unsigned long long *skip_counter; // optional: number of skipped 128-point tiles (atomic)
     unsigned long long *clock_out; // optional diagnostic: per workgroup {shader cycles, 100 MHz ticks} of the tile loop
     unsigned int *nonfinite;       // optional (split arithmetics): += points whose density pre-activation is NaN / inf (f16 range overflow)
-    // zero certification (nerf_render_opts.certify_zero; nerf_api.cpp cert_pass): the bf16 kernel stores the density PRE-activation (no ReLU) in sigma_out ...
+    // zero certification (nerf_render_opts.certify_zero; nerf_render.cpp cert_pass): the bf16 kernel stores the density PRE-activation (no ReLU) in sigma_out ...
     int raw_pre;
     // ... and the f32 kernel evaluates only the listed samples (MLP_MODE_LIST: slot i -> sample point_list[i] = ray * samples_per_ray + k;
     // outputs are scattered to the sample's own position; n_points = capacity of the list, *point_list_count = its length)

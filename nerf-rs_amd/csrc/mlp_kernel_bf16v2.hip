@@ -578,7 +578,7 @@ __global__ __launch_bounds__(256, 1) void V2SYM(nerf_mlp_kernel_bf16v2, nerf_mlp
         trunk_layers<FULL>(E0, E1, X0, X1, Y0, Y1, C, small, H, P, h);
         const float pre0 = xhalf_sum(H.alpha[0]) + small[kMiscOff + 0], pre1 = xhalf_sum(H.alpha[1]) + small[kMiscOff + 0];
         if (range_left(pre0, pre1) && A.nonfinite && lane == 0) atomicAdd(A.nonfinite, 1u); // NERF_V2_F16 only: this wave's 64 points cannot be trusted
-        // raw_pre (zero certification, nerf_api.cpp): the pre-activation itself leaves the kernel -- how far below 0 it is decides
+        // raw_pre (zero certification, nerf_render.cpp cert_pass): the pre-activation itself leaves the kernel -- how far below 0 it is decides
         // whether the f32 kernel needs to look at the sample at all
         const float s0 = A.raw_pre ? pre0 : fmaxf(pre0, 0.f); // ReLU(alpha) (src/network.rs:216)
         const float s1 = A.raw_pre ? pre1 : fmaxf(pre1, 0.f);
@@ -848,7 +848,7 @@ hipError_t nerf_mlp_bf16v2_launch(const MlpArgs &a, bool full, int n_blocks, hip
         return full ? launch_t<true, MLP_MODE_POINTS>(a, n_blocks, stream) : hipErrorInvalidValue; // no sigma-only forward_batch
     return full ? launch_t<true, MLP_MODE_RAYS>(a, n_blocks, stream) : launch_t<false, MLP_MODE_RAYS>(a, n_blocks, stream);
 }
-#else // NERF_V2_F16: the pre-filter's two launches (sigma only; certify_zero, nerf_api.cpp cert_pass)
+#else // NERF_V2_F16: the pre-filter's two launches (sigma only; certify_zero, nerf_render.cpp cert_pass)
 hipError_t nerf_prefilter_f16v2_init() {
     const void *ks[2] = {(const void *)nerf_trunk_seq_kernel_f16v2<false>, (const void *)nerf_mlp_kernel_f16v2<false, MLP_MODE_RAYS>};
     for (int i = 0; i < 2; ++i) {

@@ -13,7 +13,7 @@
 //     two 1-KiB A pieces (one per half) feed eight MFMAs -- the same bytes per FLOP through LDS-DMA and ds_read as v2;
 //   * a finished output tile, ReLU'd and packed pairwise (v_cvt_pk_bf16_f32 + v_pk_max_i16), IS k-step nt of the next layer: k-slot
 //     (g, e) of a k-step holds feature 4 g + e (e < 4) or 16 + 4 g + e - 4 (e >= 4) of that tile -- the host permutes the weight
-//     rows accordingly (nerf_api.cpp bf16_v3_from_v1), so activations never leave registers;
+//     rows accordingly (nerf_networks.cpp bf16_v3_from_v1), so activations never leave registers;
 //   * encodings: lane L computes ALL features of point L (angle doubling from three base octaves), packs them to bf16 in the
 //     reference's feature order and transposes them into B fragments through 8 KiB of LDS per wave (wave-private, no barrier).
 // Stream: per layer, per output tile, per k-step, per half one 1-KiB piece; 16-KiB chunks; exactly v2's piece counts (dense0 32,

@@ -1,14 +1,22 @@
-// nerf_internal.h -- the context and the helpers shared by nerf_api.cpp (single-device entry points) and
-// nerf_multi.cpp (multi-GPU fan-out).  Internal to libnerf_mi355x.so; nothing here is part of the C ABI.
+// nerf_internal.h -- the context and what the host files of the device half of the ABI need from each other: nerf_context.cpp (context,
+// device memory, events), nerf_networks.cpp (weight upload, MLP launcher), nerf_render.cpp (pass pipeline, render entry points),
+// nerf_queries.cpp (point / grid / mesh / stage entry points) and nerf_multi.cpp (multi-GPU fan-out).  Internal to libnerf_mi355x.so;
+// nothing here is part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <algorithm>
+#include <exception>
+#include <new>
 #include <string>
 #include <vector>
 
 #include "../../include/nerf_mi355x.h"
+
+struct MlpArgs;    // mlp_kernel.h
+struct SeqArgs;
+struct RayGenArgs; // sampling_kernels.h
 
 namespace nerfint {
 
@@ -84,7 +92,7 @@ struct nerf_ctx {
     float *d_h8 = nullptr; size_t h8_bytes = 0;
     unsigned int *d_slot_point = nullptr; size_t slot_point_bytes = 0;
     unsigned int *d_flag_list = nullptr; size_t flag_list_bytes = 0; // hybrid sampling: rays whose coarse pass is redone in f32
-    // zero certification (nerf_render_opts.certify_zero; nerf_api.cpp cert_pass, sampling_kernels.hip k_cert_*)
+    // zero certification (nerf_render_opts.certify_zero; nerf_render.cpp cert_pass, sampling_kernels.hip k_cert_*)
     unsigned int *d_point_list = nullptr; size_t point_list_bytes = 0; // samples the exact kernel evaluates (one list, reused by every launch)
     unsigned int *d_cert = nullptr; size_t cert_bytes = 0;             // counters, 8 per (pass, network)
     int *d_jstar = nullptr; size_t jstar_bytes = 0;                    // per ray of a pass: first sample behind the predicted cut
@@ -150,7 +158,77 @@ inline int band_rows(int h, int i, int n, int stripe) {
 }
 inline int band_first_row(int h, int i, int n) { return i * (h / n) + std::min(i, h % n); } // contiguous bands only
 
+inline void copy3(float *dst, const float *src) { dst[0] = src[0]; dst[1] = src[1]; dst[2] = src[2]; } // an origin, a colour
+
+// No C++ exception may cross the C ABI (a Rust caller would abort): every entry point that can allocate is a function-try-block.
+#define NERF_CATCH(c)                                                                                              \
+    catch (const std::bad_alloc &) { return fail((c), NERF_ERR_IO, "out of host memory"); }                         \
+    catch (const std::exception &e) { return fail((c), NERF_ERR_INVALID, std::string("internal error: ") + e.what()); } \
+    catch (...) { return fail((c), NERF_ERR_INVALID, "internal error"); }
+
+// ---- nerf_context.cpp -------------------------------------------------------------------------------------------------------------
 int ensure_bytes(nerf_ctx *c, void **p, size_t *cur, size_t need);
+// the pass workspace (d_dirs .. d_rgbf) for `rays` rays of nc coarse and m fine-pass samples; d_rgbc only when need_rgbc
+int ensure_workspace(nerf_ctx *c, size_t rays, size_t nc, size_t m, bool need_rgbc);
+hipEvent_t get_event(nerf_ctx *c);
+// Event pairs of kind 1 (dominant MLP kernel) are owned by ctx->dominant once a render has finished; every other
+// pair is owned by ctx->last_render.
+void recycle_render(nerf_ctx *c);
+void recycle_dominant(nerf_ctx *c, size_t keep);
+
+// Record kernel(s) between two events of the given kind.  If done() is never reached (a launch failed and the caller
+// returned early) the destructor hands the events back to the pool.
+struct Timed {
+    nerf_ctx *c; hipStream_t st; EvPair p; bool on = true;
+    Timed(nerf_ctx *c_, hipStream_t st_, int kind, uint64_t points) : c(c_), st(st_) {
+        p.kind = kind; p.points = points; p.a = get_event(c); p.b = get_event(c);
+        if (!p.a || !p.b) on = false;
+        if (on) (void)hipEventRecord(p.a, st);
+    }
+    Timed(const Timed &) = delete;
+    Timed &operator=(const Timed &) = delete;
+    void done(std::vector<EvPair> &dst) {
+        if (on) { (void)hipEventRecord(p.b, st); dst.push_back(p); p.a = p.b = nullptr; }
+    }
+    ~Timed() {
+        if (p.a) c->ev_pool.push_back(p.a);
+        if (p.b) c->ev_pool.push_back(p.b);
+    }
+};
+// fn (-> int, a status) between two events of `kind` in c->last_render
+template <class F>
+int timed(nerf_ctx *c, hipStream_t st, int kind, uint64_t points, F &&fn) {
+    Timed t(c, st, kind, points);
+    const int rc = fn();
+    if (rc) return rc;
+    t.done(c->last_render);
+    return NERF_OK;
+}
+
+// ---- nerf_networks.cpp: weight stream + launcher of the selected arithmetic ---------------------------------------------------------
+bool bf16_is_v2(); // false only in a -DNERF_BF16_V3=1 variant build, where NERF_MLP_BF16 runs mlp_kernel_bf16v3.hip
+inline bool valid_dtype(int d) { return d == NERF_MLP_F32 || d == NERF_MLP_BF16 || d == NERF_MLP_BF16X3 || d == NERF_MLP_F16X2; }
+inline bool split_dtype(int d) { return d == NERF_MLP_BF16X3 || d == NERF_MLP_F16X2; } // f32-accurate operand-splitting arithmetics
+// where a launch in `dtype` counts the points that left its range: the split arithmetics only
+inline unsigned int *nonfinite_of(const nerf_ctx *c, int dtype) { return split_dtype(dtype) ? c->d_nonfinite : nullptr; }
+const float *stream_of(const DevNet &n, int dtype);
+const float *small_of(const DevNet &n, int dtype); // the f32 kernels read the folded image's small block, every other arithmetic the packed one
+// zero-step skipping of the f32 kernels (per network, decided at load) and, for MlpArgs, the context's ray grouping
+void zskip_of(const nerf_ctx *c, const DevNet &n, MlpArgs &a);
+void zskip_of(const nerf_ctx *c, const DevNet &n, SeqArgs &a);
+hipError_t init_mlp_kernels(); // the dynamic-LDS attributes of every MLP kernel of this build, on the current device
+hipError_t launch_mlp(const nerf_ctx *c, int dtype, const MlpArgs &a, bool full, hipStream_t st);
+// largest batch of nerf_forward_batch*: INT32_MAX minus (persistent workgroups + 1) tiles of the widest kernel (256 points)
+inline size_t max_batch_points(int n_cus) { return (size_t)0x7fffffff - ((size_t)n_cus + 1) * 256; }
+// the f32 sigma-only MLP_MODE_POINTS launch (nerf_density_batch's) over n points
+hipError_t launch_sigma_points(const nerf_ctx *c, const DevNet &net, const float *d_pts, size_t n, float *d_sigma, hipStream_t st);
+
+// ---- nerf_render.cpp ------------------------------------------------------------------------------------------------------------------
+RayGenArgs make_raygen(const nerf_camera &cam, int s);
+int check_camera(nerf_ctx *c, const nerf_camera *cam);
+// what the three alpha modes ask of the compositing kernel: the background it adds (NULL: the reference's white) and whether the pack
+// kernel needs the opacity plane
+int check_rgba8(nerf_ctx *c, const float *background, int alpha_mode, const void *out, const float **bg_composite);
 // render_image on the context's device, asynchronous on `st` (synchronises only when stats != NULL); d_depth / d_opacity
 // (h x w floats each, like d_out's pixels) may be NULL (nerf_render_image_aux)
 // background: NULL = the reference's white (the float entry points); else 3 floats B, the colour is sum_i w_i c_i + B * (1 - opacity)

@@ -1,0 +1,332 @@
+// nerf_networks.cpp -- the networks on the device: upload of a loaded network in every arithmetic's weight stream (the 16-bit streams are
+// re-packed here from one piece order), which stream and which kernel a dtype selects, and the nerf_load_network_* entry points.
+#include <hip/hip_runtime.h>
+
+#include <map>
+
+#include "../../include/nerf_mi355x.h"
+#include "host_util.h"
+#include "mlp_kernel.h"
+#include "mlp_layout.h"
+
+using namespace nerfhost;
+
+#include "nerf_internal.h"
+
+using namespace nerfint;
+
+// The bf16 kernel: mlp_kernel_bf16v2.hip (32x32x16).  A variant build with -DNERF_BF16_V3=1 (make variant; round-3 experiment, see
+// DESIGN 4.3) links mlp_kernel_bf16v3.hip (16x16x32) instead: same arithmetic, same results, measured 6 % slower on the full kernel.
+#ifndef NERF_BF16_V3
+#define NERF_BF16_V3 0
+#endif
+static constexpr bool g_bf16_v2 = !NERF_BF16_V3;
+
+namespace nerfint {
+
+bool bf16_is_v2() { return g_bf16_v2; }
+
+const float *stream_of(const DevNet &n, int dtype) {
+    if (dtype == NERF_MLP_BF16X3) return (const float *)n.wstream_x3;
+    if (dtype == NERF_MLP_F16X2) return (const float *)n.wstream_x2;
+    if (dtype == NERF_MLP_F32) return n.wstream;
+    return g_bf16_v2 ? (const float *)n.wstream_bf16v2 : (const float *)n.wstream_bf16v3;
+}
+const float *small_of(const DevNet &n, int dtype) { return dtype == NERF_MLP_F32 ? n.small_f32 : n.small; }
+// zero-step skipping of the f32 kernels (MlpArgs / SeqArgs; the other arithmetics ignore the two fields): per network, decided at load
+// ... and the context's ray grouping (MlpArgs.ray_grouping: the ray-mode launcher of the f32 kernels reads it, nothing else does)
+void zskip_of(const nerf_ctx *c, const DevNet &n, MlpArgs &a) { a.zero_skip = n.zero_skip ? 1 : 0; a.zskip_stats = c->d_zskip; a.ray_grouping = c->ray_grouping ? 1 : 0; }
+void zskip_of(const nerf_ctx *c, const DevNet &n, SeqArgs &a) { a.zero_skip = n.zero_skip ? 1 : 0; a.zskip_stats = c->d_zskip; }
+
+hipError_t init_mlp_kernels() {
+    hipError_t e1 = nerf_mlp_init();
+    if (e1 == hipSuccess) e1 = nerf_mlp_bf16v2_init();
+    if (e1 == hipSuccess) e1 = nerf_prefilter_f16v2_init();
+#if NERF_BF16_V3
+    if (e1 == hipSuccess) e1 = nerf_mlp_bf16v3_init();
+#endif
+    if (e1 == hipSuccess) e1 = nerf_mlp_bf16x3_init();
+    if (e1 == hipSuccess) e1 = nerf_seq_init();
+    if (e1 == hipSuccess) e1 = nerf_seq_bf16_init();
+    if (e1 == hipSuccess) e1 = nerf_seq_x3_init();
+    if (e1 == hipSuccess) e1 = nerf_mlp_f16x2_init();
+    if (e1 == hipSuccess) e1 = nerf_seq_f16x2_init();
+    return e1;
+}
+
+// NERF_V2_F16_FULL (experiment, variant builds): NERF_MLP_BF16 renders run the f16 twin of the bf16 kernel (fused ray-mode launches only)
+hipError_t launch_mlp(const nerf_ctx *c, int dtype, const MlpArgs &a, bool full, hipStream_t st) {
+#ifdef NERF_V2_F16_FULL
+    if (dtype == NERF_MLP_BF16 && a.mode == MLP_MODE_RAYS && !a.raw_pre) {
+        MlpArgs b = a;
+        for (const DevNet &n : c->net) if ((const void *)n.wstream_bf16v2 == (const void *)a.wstream && n.wstream_f16v2) b.wstream = (const float *)n.wstream_f16v2;
+        return full ? nerf_mlp_f16v2_full_launch(b, c->n_cus, st) : nerf_mlp_f16v2_launch(b, c->n_cus, st);
+    }
+#endif
+    if (dtype == NERF_MLP_F32) return nerf_mlp_launch(a, full, c->n_cus, st);
+    if (dtype == NERF_MLP_BF16X3) return nerf_mlp_bf16x3_launch(a, full, c->n_cus, st);
+    if (dtype == NERF_MLP_F16X2) return nerf_mlp_f16x2_launch(a, full, c->n_cus, st);
+#if NERF_BF16_V3
+    return nerf_mlp_bf16v3_launch(a, full, c->n_cus, st);
+#else
+    return nerf_mlp_bf16v2_launch(a, full, c->n_cus, st);
+#endif
+}
+
+hipError_t launch_sigma_points(const nerf_ctx *c, const DevNet &net, const float *d_pts, size_t n, float *d_sigma, hipStream_t st) {
+    MlpArgs a{};
+    a.mode = MLP_MODE_POINTS;
+    a.wstream = net.wstream; a.small_params = net.small_f32; zskip_of(c, net, a);
+    a.n_points = (int)n; a.pts_soa = d_pts; a.sigma_out = d_sigma;
+    return launch_mlp(c, NERF_MLP_F32, a, false, st);
+}
+
+} // namespace nerfint
+
+namespace {
+
+// v1 stream -> v2 stream: the 1-KiB pieces are identical (lane l, element j = W[row(tile, 8 ks + j, l >> 5)][32 nt + (l & 31)]);
+// v1 orders a layer's pieces (k-step, nt), v2 orders them (nt, k-step) and pads viewdirs' 72 pieces to 80.
+static void bf16_v2_from_v1(const std::vector<uint16_t> &v1, std::vector<uint16_t> &v2) {
+    using namespace nerfmlp;
+    v2.clear();
+    v2.reserve((size_t)kChunksFullBf16V2 * kChunkBytesBf16V2 / 2);
+    size_t base = 0; // uint16 elements
+    auto layer = [&](int KS, int NT) {
+        for (int nt = 0; nt < NT; ++nt)
+            for (int ks = 0; ks < KS; ++ks) {
+                const uint16_t *src = &v1[base + ((size_t)ks * NT + nt) * 512];
+                v2.insert(v2.end(), src, src + 512);
+            }
+        base += (size_t)KS * NT * 512;
+    };
+    layer(4, 8);
+    for (int i = 0; i < 4; ++i) layer(16, 8);
+    layer(20, 8);
+    for (int i = 0; i < 3; ++i) layer(16, 8);
+    layer(18, 4);
+    v2.resize((size_t)kChunksFullBf16V2 * kChunkBytesBf16V2 / 2, (uint16_t)0);
+}
+
+// v1 order (f32 values) -> the stream of mlp_kernel_bf16v3.hip (v_mfma_f32_16x16x32_bf16): per layer, per output tile nt, per k-step ks
+// (K = 32), per 16-feature half fh one 1-KiB piece: lane l = (i = l & 15, g = l >> 4), element e = W[row(ks, g, e)][32 nt + 16 fh + i].
+// Hidden k-steps: k-slot (g, e) = feature 4 g + e (e < 4) or 16 + 4 g + e - 4 of input tile ks (the C/D layout of two 16x16 output
+// halves packed pairwise); encoding k-steps: slot 32 ks + 8 g + e = the reference's feature index (src/network.rs:263-330).
+static void bf16_v3_from_v1(const std::vector<float> &v1f, std::vector<uint16_t> &v3) {
+    using namespace nerfmlp;
+    v3.clear();
+    v3.reserve((size_t)kChunksFullBf16V2 * kChunkBytesBf16V2 / 2);
+    int pos_inv[64][3], dir_inv[32][3]; // reference feature -> (input tile, register, lane-half) of the 32x32 layouts
+    for (auto &x : pos_inv) x[0] = -1;
+    for (auto &x : dir_inv) x[0] = -1;
+    for (int tt = 0; tt < 2; ++tt)
+        for (int r = 0; r < 16; ++r)
+            for (int h = 0; h < 2; ++h) {
+                const int f = posSlotFeature(16 * tt + r, h);
+                if (f >= 0) { pos_inv[f][0] = tt; pos_inv[f][1] = r; pos_inv[f][2] = h; }
+            }
+    for (int r = 0; r < 16; ++r)
+        for (int h = 0; h < 2; ++h) {
+            const int f = dirSlotFeature(r, h);
+            if (f >= 0) { dir_inv[f][0] = 0; dir_inv[f][1] = r; dir_inv[f][2] = h; }
+        }
+    size_t base = 0; // v1 pieces
+    // kind of k-step ks: 0 = activation tile `tile`, 1 = position-encoding slots 32 * tile .., 2 = direction-encoding slots
+    auto layer = [&](int n_tiles_v1, int NT, int KS, auto kind_of) {
+        for (int nt = 0; nt < NT; ++nt)
+            for (int ks = 0; ks < KS; ++ks)
+                for (int fh = 0; fh < 2; ++fh)
+                    for (int l = 0; l < 64; ++l)
+                        for (int e = 0; e < 8; ++e) {
+                            const int i = l & 15, g = l >> 4;
+                            int kind, tile;
+                            kind_of(ks, kind, tile);
+                            int tt = -1, r = 0, h = 0;
+                            if (kind == 0) {
+                                const int f = e < 4 ? 4 * g + e : 16 + 4 * g + (e - 4);
+                                tt = tile; h = (f >> 2) & 1; r = (f & 3) + 4 * (f >> 3);
+                            } else if (kind == 1) {
+                                const int s = 32 * tile + 8 * g + e;
+                                if (s < 63 && pos_inv[s][0] >= 0) { tt = pos_inv[s][0]; r = pos_inv[s][1]; h = pos_inv[s][2]; }
+                            } else {
+                                const int s = 8 * g + e;
+                                if (s < 27 && dir_inv[s][0] >= 0) { tt = n_tiles_v1 - 1; r = dir_inv[s][1]; h = dir_inv[s][2]; }
+                            }
+                            float v = 0.0f;
+                            if (tt >= 0) {
+                                const size_t piece = base + ((size_t)(tt * 2 + (r >> 3)) * NT + nt);
+                                v = v1f[(piece * 64 + (size_t)(16 * fh + i + 32 * h)) * 8 + (r & 7)];
+                            }
+                            v3.push_back(f32_to_bf16_rne(v));
+                        }
+        base += (size_t)n_tiles_v1 * 2 * NT;
+    };
+    layer(2, 8, 2, [](int ks, int &kind, int &tile) { kind = 1; tile = ks; });
+    for (int i = 0; i < 4; ++i) layer(8, 8, 8, [](int ks, int &kind, int &tile) { kind = 0; tile = ks; });
+    layer(10, 8, 10, [](int ks, int &kind, int &tile) { if (ks < 2) { kind = 1; tile = ks; } else { kind = 0; tile = ks; } });
+    for (int i = 0; i < 3; ++i) layer(8, 8, 8, [](int ks, int &kind, int &tile) { kind = 0; tile = ks; });
+    layer(9, 4, 9, [](int ks, int &kind, int &tile) { if (ks < 8) { kind = 0; tile = ks; } else { kind = 2; tile = 0; } });
+    v3.resize((size_t)kChunksFullBf16V2 * kChunkBytesBf16V2 / 2, (uint16_t)0);
+}
+
+int upload_packed(nerf_ctx *c, int which, const std::vector<float> &ws, const std::vector<float> &sm) {
+    if (ws.size() != (size_t)nerfmlp::kChunksFull * nerfmlp::kChunkFloats || sm.size() != (size_t)nerfmlp::kSmallFloats)
+        return fail(c, NERF_ERR_SHAPE, "packed network image has the wrong size for this library build");
+    // the f32 kernels run the bottleneck folded into viewdirs (once per loaded network); the 16-bit arithmetics keep the packed
+    // image's small block (their streams come from upload_bf16_family)
+    std::vector<float> fws, fsm;
+    if (!fold_network(ws, sm, fws, fsm)) return fail(c, NERF_ERR_SHAPE, "internal: folded network image has the wrong size");
+    DevNet &d = c->net[which];
+    if (!d.wstream) HIP_TRY(c, hipMalloc((void **)&d.wstream, fws.size() * sizeof(float)));
+    if (!d.small) HIP_TRY(c, hipMalloc((void **)&d.small, sm.size() * sizeof(float)));
+    if (!d.small_f32) HIP_TRY(c, hipMalloc((void **)&d.small_f32, fsm.size() * sizeof(float)));
+    HIP_TRY(c, hipMemcpy(d.wstream, fws.data(), fws.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(d.small, sm.data(), sm.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(d.small_f32, fsm.data(), fsm.size() * sizeof(float), hipMemcpyHostToDevice));
+    d.loaded = true;
+    d.zero_skip = c->zero_step_skip && zero_skip_safe(fws, fsm); // exact only while every parameter is finite (mlp_f32_core.hip.h tile_steps)
+    c->cert_margin[which] = c->cert_margin_floor[which]; // certify_zero calibrates itself per network (upload_bf16_family, which follows, decides the pre-filter)
+    return NERF_OK;
+}
+
+// All bf16-family streams come from one f32 array in the first bf16 design's piece order (host_util.h).
+int upload_bf16_family(nerf_ctx *c, int which, const std::vector<float> &v1f) {
+    if (v1f.size() != (size_t)nerfmlp::kPiecesV1 * 512) return fail(c, NERF_ERR_SHAPE, "internal: bf16 piece array has the wrong size");
+    DevNet &d = c->net[which];
+    std::vector<uint16_t> wb, v2, x3;
+    bf16_stream_from_v1order(v1f, wb);
+    bf16_v2_from_v1(wb, v2);
+    x3_stream_from_v1order(v1f, x3);
+    if (x3.size() != (size_t)nerfmlp::kChunksFullX3 * nerfmlp::kChunkBytesX3 / 2) return fail(c, NERF_ERR_SHAPE, "internal: bf16x3 stream size");
+    if (!d.wstream_bf16v2) HIP_TRY(c, hipMalloc((void **)&d.wstream_bf16v2, v2.size() * sizeof(uint16_t)));
+    HIP_TRY(c, hipMemcpy(d.wstream_bf16v2, v2.data(), v2.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+    if (!g_bf16_v2) {
+        std::vector<uint16_t> v3;
+        bf16_v3_from_v1(v1f, v3);
+        if (v3.size() != v2.size()) return fail(c, NERF_ERR_SHAPE, "internal: bf16 v3 stream size");
+        if (!d.wstream_bf16v3) HIP_TRY(c, hipMalloc((void **)&d.wstream_bf16v3, v3.size() * sizeof(uint16_t)));
+        HIP_TRY(c, hipMemcpy(d.wstream_bf16v3, v3.data(), v3.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+    }
+    if (!d.wstream_x3) HIP_TRY(c, hipMalloc((void **)&d.wstream_x3, x3.size() * sizeof(uint16_t)));
+    HIP_TRY(c, hipMemcpy(d.wstream_x3, x3.data(), x3.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+    {   // the f16 twin of the bf16 v2 stream (certify_zero's pre-filter): the same pieces in the same order, f16-rounded
+        std::vector<uint16_t> hb, h2;
+        const bool fits = f16_stream_from_v1order(v1f, hb);
+        if (fits) {
+            bf16_v2_from_v1(hb, h2); // a permutation of 16-bit elements: the element type does not matter
+            if (h2.size() != v2.size()) return fail(c, NERF_ERR_SHAPE, "internal: f16 v2 stream size");
+            if (!d.wstream_f16v2) HIP_TRY(c, hipMalloc((void **)&d.wstream_f16v2, h2.size() * sizeof(uint16_t)));
+            HIP_TRY(c, hipMemcpy(d.wstream_f16v2, h2.data(), h2.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+        } else if (d.wstream_f16v2) {
+            HIP_TRY(c, hipFree(d.wstream_f16v2));
+            d.wstream_f16v2 = nullptr;
+        }
+        // certify_zero calibrates itself per network: margins start at the floors of the pre-filter this network gets
+        c->cert_prefilter_f16[which] = g_bf16_v2 && c->cert_allow_f16 && d.wstream_f16v2 != nullptr;
+        c->cert_margin[which] = c->cert_prefilter_f16[which] ? c->cert_margin_floor_f16[which] : c->cert_margin_floor[which];
+    }
+    std::vector<uint16_t> x2;
+    if (x2_stream_from_v1order(v1f, x2)) { // every weight inside the f16 range (the lego networks: |w| <= 8.3)
+        if (x2.size() != (size_t)nerfmlp::kChunksFullF16X2 * nerfmlp::kChunkBytesF16X2 / 2) return fail(c, NERF_ERR_SHAPE, "internal: f16x2 stream size");
+        if (!d.wstream_x2) HIP_TRY(c, hipMalloc((void **)&d.wstream_x2, x2.size() * sizeof(uint16_t)));
+        HIP_TRY(c, hipMemcpy(d.wstream_x2, x2.data(), x2.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+    } else if (d.wstream_x2) { // a reload with out-of-range weights: NERF_MLP_F16X2 becomes unavailable for this network
+        HIP_TRY(c, hipFree(d.wstream_x2));
+        d.wstream_x2 = nullptr;
+    }
+    return NERF_OK;
+}
+
+int upload_net(nerf_ctx *c, int which, const HostNet &hn) {
+    std::vector<float> ws, sm;
+    pack_network(hn, ws, sm);
+    int rc = upload_packed(c, which, ws, sm);
+    if (rc) return rc;
+    std::vector<float> v1f;
+    pack_network_v1order_f32(hn, v1f);
+    return upload_bf16_family(c, which, v1f);
+}
+
+// The bf16-family streams hold the same weights in another order; for networks that arrive as a packed f32 blob they are
+// rebuilt from the f32 stream's pieces (piece (s, g): lane l, q -> W[row(s, l >> 5)][32 (4 g + q) + (l & 31)]).
+int bf16_from_f32_stream(nerf_ctx *c, int which, const std::vector<float> &ws) {
+    using namespace nerfmlp;
+    std::vector<float> v1f;
+    v1f.reserve((size_t)kPiecesV1 * 512);
+    size_t layer_base = 0; // floats
+    auto layer = [&](int n_tiles, int NT) {
+        for (int tt = 0; tt < n_tiles; ++tt)
+            for (int ks = 0; ks < 2; ++ks)
+                for (int nt = 0; nt < NT; ++nt)
+                    for (int l = 0; l < 64; ++l)
+                        for (int j = 0; j < 8; ++j) {
+                            const int st = 16 * tt + 8 * ks + j; // f32 k-step that holds register 8 ks + j of tile tt
+                            const size_t piece = layer_base + ((size_t)st * (NT / 4) + nt / 4) * 256;
+                            v1f.push_back(ws[piece + (size_t)l * 4 + (nt & 3)]);
+                        }
+        layer_base += (size_t)n_tiles * 16 * NT * 64;
+    };
+    layer(2, 8);
+    for (int i = 0; i < 4; ++i) layer(8, 8);
+    layer(10, 8);
+    for (int i = 0; i < 3; ++i) layer(8, 8);
+    layer(9, 4);
+    return upload_bf16_family(c, which, v1f);
+}
+
+} // namespace
+
+extern "C" {
+
+int nerf_load_network_dir(nerf_ctx *c, int which, const char *dir) try {
+    if (!c) return fail(nullptr, NERF_ERR_INVALID, "ctx is NULL");
+    if (which != NERF_NET_COARSE && which != NERF_NET_FINE) return fail(c, NERF_ERR_INVALID, "which must be NERF_NET_COARSE or NERF_NET_FINE");
+    if (!dir) return fail(c, NERF_ERR_INVALID, "dir is NULL");
+    DeviceGuard dg(c->device);
+    std::map<std::string, Tensor> params;
+    std::string err;
+    int rc = read_tensor_dir(dir, params, err);
+    if (rc) return fail(c, rc, err);
+    HostNet hn;
+    rc = assemble_net(params, hn, err);
+    if (rc) return fail(c, rc, err);
+    return upload_net(c, which, hn);
+} NERF_CATCH(c)
+
+int nerf_load_network_tensors(nerf_ctx *c, int which, int n, const char *const *names, const int64_t *dims,
+                              const float *const *data) try {
+    if (!c) return fail(nullptr, NERF_ERR_INVALID, "ctx is NULL");
+    if (which != NERF_NET_COARSE && which != NERF_NET_FINE) return fail(c, NERF_ERR_INVALID, "which must be NERF_NET_COARSE or NERF_NET_FINE");
+    if (n < 0 || (n > 0 && (!names || !dims || !data))) return fail(c, NERF_ERR_INVALID, "bad tensor table");
+    DeviceGuard dg(c->device);
+    std::map<std::string, Tensor> params;
+    for (int i = 0; i < n; ++i) {
+        if (!names[i] || !data[i] || dims[2 * i] < 0 || dims[2 * i + 1] < 0) return fail(c, NERF_ERR_INVALID, "bad tensor table entry");
+        Tensor t;
+        size_t cnt = (size_t)dims[2 * i];
+        t.dims.push_back(dims[2 * i]);
+        if (dims[2 * i + 1] > 0) { t.dims.push_back(dims[2 * i + 1]); cnt *= (size_t)dims[2 * i + 1]; }
+        t.data.assign(data[i], data[i] + cnt);
+        params[names[i]] = std::move(t);
+    }
+    HostNet hn;
+    std::string err;
+    const int rc = assemble_net(params, hn, err);
+    if (rc) return fail(c, rc, err);
+    return upload_net(c, which, hn);
+} NERF_CATCH(c)
+
+int nerf_load_network_blob(nerf_ctx *c, int which, const char *blob_path) try {
+    if (!c) return fail(nullptr, NERF_ERR_INVALID, "ctx is NULL");
+    if (which != NERF_NET_COARSE && which != NERF_NET_FINE) return fail(c, NERF_ERR_INVALID, "which must be NERF_NET_COARSE or NERF_NET_FINE");
+    if (!blob_path) return fail(c, NERF_ERR_INVALID, "blob_path is NULL");
+    DeviceGuard dg(c->device);
+    std::vector<float> ws, sm;
+    std::string err;
+    const int rrc = read_blob_file(blob_path, ws, sm, err);
+    if (rrc) return fail(c, rrc, err);
+    const int rc = upload_packed(c, which, ws, sm);
+    return rc ? rc : bf16_from_f32_stream(c, which, ws);
+} NERF_CATCH(c)
+
+} // extern "C"

@@ -1,0 +1,1093 @@
+// nerf_render.cpp -- the renders: the pass pipeline that image renders and ray batches share, their drivers, certify_zero's retry loop, and
+// the nerf_render_* entry points (include/nerf_mi355x.h).
+#include <hip/hip_runtime.h>
+#include <stdio.h>
+#include <string.h>
+
+#include <algorithm>
+#include <cmath>
+#include <mutex>
+#include <vector>
+
+#include "../../include/nerf_mi355x.h"
+#include "host_util.h"
+#include "mlp_kernel.h"
+#include "mlp_layout.h"
+#include "normal_kernels.h"
+#include "ray_batch_kernels.h"
+#include "sampling_kernels.h"
+
+using namespace nerfhost;
+
+#include "nerf_internal.h"
+
+using namespace nerfint;
+
+namespace nerfint {
+
+RayGenArgs make_raygen(const nerf_camera &cam, int s) {
+    RayGenArgs g{};
+    g.rnx = cam.nx * s; g.rny = cam.ny * s;
+    g.half = 0.5f; g.normalize = 1;
+    camera_basis(cam, g.r, g.u, g.f, &g.sx, &g.sy);
+    return g;
+}
+
+int check_camera(nerf_ctx *c, const nerf_camera *cam) {
+    if (!cam) return fail(c, NERF_ERR_INVALID, "camera is NULL");
+    if (cam->nx <= 0 || cam->ny <= 0) return fail(c, NERF_ERR_INVALID, "width and height must be greater than zero"); // src/lib.rs:705-709
+    return NERF_OK;
+}
+
+// what the three alpha modes ask of the compositing kernel: the background it adds (NULL: the reference's white) and whether the pack
+// kernel needs the opacity plane
+int check_rgba8(nerf_ctx *c, const float *background, int alpha_mode, const void *out, const float **bg_composite) {
+    static const float kBlack[3] = {0.0f, 0.0f, 0.0f};
+    if (alpha_mode != NERF_ALPHA_OPAQUE && alpha_mode != NERF_ALPHA_PREMULTIPLIED && alpha_mode != NERF_ALPHA_STRAIGHT)
+        return fail(c, NERF_ERR_INVALID, "alpha_mode must be NERF_ALPHA_OPAQUE, NERF_ALPHA_PREMULTIPLIED or NERF_ALPHA_STRAIGHT");
+    if (background && !(std::isfinite(background[0]) && std::isfinite(background[1]) && std::isfinite(background[2])))
+        return fail(c, NERF_ERR_INVALID, "background components must be finite");
+    if (!out) return fail(c, NERF_ERR_INVALID, "output pointer is NULL");
+    *bg_composite = alpha_mode == NERF_ALPHA_OPAQUE ? background : kBlack; // premultiplied / straight: C + 0 * (1 - A) = C
+    return NERF_OK;
+}
+
+} // namespace nerfint
+
+namespace {
+
+// The rays of a batch, already on the device (but for a shared origin).
+struct RayBatch {
+    const float *h_origin;     // n_origins == 1: the shared origin (HOST, 3 floats); else NULL
+    const float *d_origins;    // n_origins == n_rays: n_rays x 3 (device); else NULL
+    const float *d_dirs;       // n_rays x 3 (device)
+    size_t n_rays;
+    int normalize;
+    float near_, far_;
+    const float *d_bounds;     // n_rays x 2 (device) or NULL
+    const uint32_t *d_rng;     // n_rays (device) or NULL
+};
+
+// The pass workspace of a normals render in c->d_normal, every part 256-byte aligned.
+struct NormalWorkspace {
+    float *w = nullptr; uint32_t *list = nullptr, *count = nullptr, *base = nullptr, *bsum = nullptr, *totals = nullptr;
+    NormalWorkspace() = default;
+    static size_t al(size_t bytes) { return (bytes + 255) / 256 * 256; }
+    static size_t blocks(size_t rays) { return (rays + kNormalBlock - 1) / kNormalBlock; }
+    static size_t bytes(size_t rays, size_t samples) { return 2 * al(4 * samples) + 2 * al(4 * rays) + al(4 * blocks(rays)) + 256; }
+    NormalWorkspace(void *p, size_t rays, size_t samples) {
+        char *q = (char *)p;
+        w = (float *)q; q += al(4 * samples);
+        list = (uint32_t *)q; q += al(4 * samples);
+        count = (uint32_t *)q; q += al(4 * rays);
+        base = (uint32_t *)q; q += al(4 * rays);
+        bsum = (uint32_t *)q; q += al(4 * blocks(rays));
+        totals = (uint32_t *)q;
+    }
+};
+
+// ---- the pass pipeline ------------------------------------------------------------------------------------------------------------------
+// Host counterpart of render_image / render_block (reference src/lib.rs:353-565): where the reference cuts the frame in 8x8 blocks for rayon
+// workers, a render here is cut in "passes" of at most max_rays_per_pass rays (all resident in HBM), and per pass
+//     rays + coarse t -> coarse MLP (sigma) -> [composite, if coarse_only] -> resample/sort -> fine MLP -> composite
+// run as launches on one stream with no host round trip (a normals render has one per pass, normals_pass).  Image renders (render_once) and
+// ray batches (render_rays_device) validate their own arguments, fill a RenderJob and run the same loop, render_passes; they differ in
+// where a pass's rays come from (prepare_rays) and in how a network is evaluated over a pass's samples (eval_net).
+
+// per (pass, network) of a certify_zero render: {list 1 length, list 2 length, audited, violations, headroom code, max-error bits, fallback rays,
+//     audit-record count, pre-filter ray queue head, list 1 back-part length, u64 samples the pre-filter evaluated, f16 range exits, ...}
+constexpr int kCertSlots = 16;
+
+// What a render does, as plain data: filled by the two drivers after validation, read-only afterwards.
+struct RenderJob {
+    // the sample plan (plan_job)
+    int nc, nf, M;           // coarse samples, fine samples added by the resampler (0: none), samples of the fine pass
+    int dtype, dtype_coarse; // arithmetic of the colour-producing pass / of the sampling pass
+    bool coarse_only;
+    uint64_t seed;
+    float near_, far_;       // the shared bounds ...
+    float *d_far;            // ... or, for a batch with per-ray bounds, the far of each ray of the pass under way (k_batch_prepare writes it)
+    const float *background; // 3 floats, or NULL = the reference's white
+    // outputs, per ray: the pass that starts at ray r0 writes out + 3 r0, depth + r0, opacity + r0 (r0 = row x RW of an image)
+    float *out, *depth, *opacity;
+    size_t n_rays, pass_rays; // all rays, rays of a full pass
+    int kind_colour;          // event kind of the colour-producing launch: 1 for images (-> c->dominant), 5 for batches
+    const char *what;         // "frame" / "batch", for the non-finite error
+    hipStream_t st;
+    // modes (images only: ray batches refuse them)
+    int skip_empty;
+    bool seq, hybrid, certify; // skip_dead, hybrid_sampling with something to resample, certify_zero
+    size_t cert_cap, aux_cap;  // certify_zero: capacity of the sample list and of the audit records
+    unsigned long long *clock_out; // NERF_DEBUG_CLOCK: where the fine launch leaves its clocks
+    // the ray source: a camera window (g: everything but the pass's own n_rays and first row) or the caller's rays
+    const RayBatch *batch;
+    RayGenArgs g;
+    float origin[3];           // the shared origin (batches with per-ray origins: unused)
+    float *d_pts, *d_daos;     // per-ray origins: the points and per-sample directions of one launch (k_batch_points)
+    // normals (batches only): per-ray output, central-difference step, samples per ray the final compositing integrates, pass workspace
+    float *normals; float h; int n_comp; NormalWorkspace nw;
+};
+
+struct Pass {
+    uint32_t index;
+    size_t r0;             // first ray
+    int n_rays;
+    RayGenArgs g;          // what the resampler derives its Philox index from (unless rng is given): the image rectangle of the pass, or
+                           // for a batch the ray's number in it -- a one-row rectangle that starts at column r0
+    const uint32_t *rng;   // the caller's rng_index for the pass's rays, or NULL
+    const float *origins;  // per-ray origins of the pass, or NULL
+};
+
+bool watches_range(const nerf_ctx *c, const RenderJob &j) { return c->d_nonfinite && (split_dtype(j.dtype) || split_dtype(j.dtype_coarse)); }
+
+// sample_importance returns nothing for count == 0 or < 3 coarse samples (src/lib.rs:295-297): the fine net then runs on the coarse samples only
+int fine_samples(const nerf_render_opts *o) { return (o->coarse_only || o->n_fine == 0 || o->n_coarse < 3) ? 0 : o->n_fine; }
+
+// The sample plan's checks, shared by image renders and ray batches; each caller runs the three parts where its own order of refusals has them.
+enum PlanPart { PLAN_COUNTS, PLAN_NETWORKS, PLAN_LIMITS };
+int check_sample_plan(nerf_ctx *c, const nerf_render_opts *o, PlanPart part) {
+    if (part == PLAN_COUNTS) {
+        if (o->n_coarse <= 0) return fail(c, NERF_ERR_INVALID, "coarse samples per ray must be greater than 0"); // src/lib.rs:483-486
+        if (o->n_fine < 0) return fail(c, NERF_ERR_INVALID, "fine samples per ray must be >= 0");
+        if (!valid_dtype(o->mlp_dtype)) return fail(c, NERF_ERR_INVALID, "mlp_dtype must be NERF_MLP_F32, NERF_MLP_BF16, NERF_MLP_BF16X3 or NERF_MLP_F16X2");
+    } else if (part == PLAN_NETWORKS) {
+        if (!c->net[NERF_NET_COARSE].loaded) return fail(c, NERF_ERR_STATE, "coarse network not loaded");
+        if (!o->coarse_only && !c->net[NERF_NET_FINE].loaded) return fail(c, NERF_ERR_STATE, "fine network not loaded");
+        if (o->mlp_dtype == NERF_MLP_F16X2 && (!c->net[o->coarse_only ? NERF_NET_COARSE : NERF_NET_FINE].wstream_x2 ||
+                                               (o->hybrid_sampling && !c->net[NERF_NET_COARSE].wstream_x2)))
+            return fail(c, NERF_ERR_STATE, "NERF_MLP_F16X2 is unavailable for this network: a weight exceeds the f16 range");
+    } else {
+        const int nc = o->n_coarse, nf = fine_samples(o);
+        if ((long long)nc + nf > 0x3fffffff || composite_lds_bytes(nc + nf) > 160 * 1024 || (nf > 0 && resample_lds_bytes(nc, nf) > 160 * 1024))
+            return fail(c, NERF_ERR_INVALID, "too many samples per ray for the sampling / compositing kernels (one ray per wave in LDS)");
+    }
+    return NERF_OK;
+}
+
+// bf16x3 / f16x2: the sampling pass (coarse sigma -> CDF -> fine sample positions) stays on the exact-f32 MFMA kernel, so the fine
+// samples sit where the f32 path puts them bit for bit (a 1e-5 density difference can move a CDF entry across a fixed
+// uniform draw and relocate a sample -- a discontinuity, not an accuracy problem); only the colour-producing pass runs in
+// the three-way split arithmetic.
+// hybrid_sampling: the sampling pass itself runs in a split arithmetic (the render's own, or -- for an f32 render -- f16x2 where
+// the network fits the f16 range, else bf16x3) and only the ill-conditioned rays are redone in f32.
+void plan_job(const nerf_ctx *c, const nerf_render_opts *o, RenderJob &j) {
+    j.nc = o->n_coarse; j.nf = fine_samples(o); j.M = j.nc + j.nf;
+    j.coarse_only = o->coarse_only != 0;
+    j.seed = o->seed;
+    j.dtype = o->mlp_dtype;
+    j.dtype_coarse = o->hybrid_sampling ? (split_dtype(j.dtype) ? j.dtype : c->net[NERF_NET_COARSE].wstream_x2 ? NERF_MLP_F16X2 : NERF_MLP_BF16X3)
+                                        : (split_dtype(j.dtype) && !o->coarse_only) ? NERF_MLP_F32 : j.dtype;
+}
+
+// a pass must keep rays * samples within int32 (kernel indices) as well as within the configured budget
+size_t pass_capacity(const nerf_ctx *c, int M) { return std::max<size_t>(1, std::min<size_t>(c->max_rays_per_pass, (size_t)0x3fffffff / (size_t)M)); }
+
+// step 1: c->d_dirs and the coarse t in c->d_tc for the rays of pass p; fills what the later steps need to know about those rays
+int prepare_rays(nerf_ctx *c, const RenderJob &j, Pass &p) {
+    if (!j.batch) {
+        p.g = j.g; p.g.n_rays = p.n_rays; p.g.ry0 += (int)(p.r0 / (size_t)j.g.rw);
+        return timed(c, j.st, 2, 0, [&]() -> int {
+            HIP_TRY(c, launch_ray_dirs(p.g, c->d_dirs, j.st));
+            HIP_TRY(c, launch_stratified(p.g, j.nc, j.near_, j.far_, j.seed, c->d_tc, j.st));
+            return NERF_OK;
+        });
+    }
+    const RayBatch &b = *j.batch;
+    const size_t r0 = p.r0;
+    p.rng = b.d_rng ? b.d_rng + r0 : nullptr;
+    p.origins = b.d_origins ? b.d_origins + 3 * r0 : nullptr;
+    p.g.n_rays = p.n_rays; p.g.rx0 = (int)r0; p.g.ry0 = 0; p.g.rw = p.n_rays; p.g.rnx = p.n_rays; p.g.rny = 1;
+    BatchPrepareArgs q{};
+    q.n_rays = p.n_rays; q.first_ray = (uint32_t)r0; q.dirs = b.d_dirs + 3 * r0; q.normalize = b.normalize;
+    q.bounds = b.d_bounds ? b.d_bounds + 2 * r0 : nullptr; q.rng_index = p.rng;
+    q.near_ = b.near_; q.far_ = b.far_; q.count = j.nc; q.seed_lo = (uint32_t)j.seed; q.seed_hi = (uint32_t)(j.seed >> 32);
+    q.dirs_out = c->d_dirs; q.t_out = c->d_tc; q.far_out = j.d_far;
+    return timed(c, j.st, 2, 0, [&]() -> int { HIP_TRY(c, launch_batch_prepare(q, j.st)); return NERF_OK; });
+}
+
+// what every ray-sequential launch of a pass has in common: one network's trunk over the pass's rays from the shared origin
+SeqArgs seq_args(const nerf_ctx *c, const RenderJob &j, const Pass &p, const float *wstream, const float *small_params, int spr, const float *t,
+                 float *sigma_out) {
+    SeqArgs q{};
+    q.wstream = wstream; q.small_params = small_params; q.n_rays = p.n_rays; q.samples_per_ray = spr;
+    q.ray_dirs = c->d_dirs; q.t = t; q.far_ = j.far_;
+    copy3(q.origin, j.origin);
+    q.sigma_out = sigma_out;
+    return q;
+}
+
+// skip_dead: one network over the rays of the pass as ray-sequential trunk [+ colour head on the live samples]
+int seq_pass(nerf_ctx *c, const RenderJob &j, const Pass &p, const DevNet &net, int dt, int spr, const float *t_in, float *sigma_out, float *rgb_out,
+             int slot, int kind_trunk) {
+    const hipStream_t st = j.st;
+    unsigned int *ctr = c->d_seq + 4 * (size_t)slot;
+    HIP_TRY(c, hipMemsetAsync(sigma_out, 0, (size_t)p.n_rays * spr * sizeof(float), st)); // samples behind the cut stay 0
+    if (rgb_out) HIP_TRY(c, hipMemsetAsync(rgb_out, 0, (size_t)p.n_rays * spr * 3 * sizeof(float), st)); // weight-0 samples: 0 * 0
+    SeqArgs q = seq_args(c, j, p, stream_of(net, dt), small_of(net, dt), spr, t_in, sigma_out);
+    zskip_of(c, net, q);
+    q.ray_counter = ctr; q.live_count = ctr + 1; q.h8 = c->d_h8; q.slot_point = c->d_slot_point;
+    q.rgb_out = rgb_out; // f32: colour passes inside the trunk launch
+    q.stats = (unsigned long long *)(ctr + 2);
+    q.nonfinite = nonfinite_of(c, dt);
+    int rc = timed(c, st, kind_trunk, (uint64_t)p.n_rays * spr, [&]() -> int {
+        HIP_TRY(c, dt == NERF_MLP_BF16X3 ? nerf_trunk_seq_x3_launch(q, rgb_out != nullptr, c->n_cus, st)
+                   : dt == NERF_MLP_F16X2 ? nerf_trunk_seq_f16x2_launch(q, rgb_out != nullptr, c->n_cus, st)
+                   : dt == NERF_MLP_BF16  ? nerf_trunk_seq_bf16_launch(q, rgb_out != nullptr, c->n_cus, st)
+                                          : nerf_trunk_seq_launch(q, rgb_out != nullptr, c->n_cus, st));
+        return NERF_OK;
+    });
+    if (rc || !rgb_out || dt == NERF_MLP_F32) return rc;
+    ColourArgs k{};
+    k.wstream = stream_of(net, dt); k.small_params = net.small; k.live_count = ctr + 1; k.h8 = c->d_h8; k.slot_point = c->d_slot_point;
+    k.ray_dirs = c->d_dirs; k.samples_per_ray = spr; k.rgb_out = rgb_out; k.nonfinite = nonfinite_of(c, dt);
+    return timed(c, st, 4, 0, [&]() -> int {
+        HIP_TRY(c, dt == NERF_MLP_BF16X3 ? nerf_colour_x3_launch(k, c->n_cus, st)
+                   : dt == NERF_MLP_F16X2 ? nerf_colour_f16x2_launch(k, c->n_cus, st)
+                                          : nerf_colour_bf16_launch(k, c->n_cus, st));
+        return NERF_OK;
+    });
+}
+
+// Zero certification (nerf_render_opts.certify_zero; DESIGN 4.9, protocol: sampling_kernels.hip k_cert_*): a 16-bit pass (f16 or bf16 operands,
+// cert_prefilter_f16) over all samples finds (Z) the samples whose density pre-activation is so far below 0 (margin per network,
+// c->cert_margin: audited every frame and widened by render_device when the audit's headroom shrinks) that the exact network's density is
+// certainly 0 there too, and predicts (C) where each ray's transmittance falls below the reference's 1e-4 cut; the exact kernel evaluates only
+// the remaining samples in front of the predicted cut (a device-side list), the exact transmittance confirms the cut (or a second launch
+// evaluates the rest).  A certified sample has sigma = 0 => weight 0, a sample behind the cut has weight 0 whatever its density: the frame is
+// the plain frame, bit for bit, as long as no certificate is wrong.
+// Per network: 16-bit pre-activations of all samples -> plan (list 1, predicted cuts) -> exact kernel on list 1 -> audit -> exact
+// transmittance confirms the cuts (list 2 = what is left of the rays it does not) -> exact kernel on list 2.
+// a: the plain ray-mode launch of this network in arithmetic dt (eval_net), from which every launch here is derived.
+int cert_pass(nerf_ctx *c, const RenderJob &j, const Pass &p, const MlpArgs &a, const DevNet &net, int which, int dt, int kind) {
+    const hipStream_t st = j.st;
+    const int n_pts = a.n_points, spr = a.samples_per_ray;
+    const float *t_in = a.t;
+    float *sigma_out = a.sigma_out, *rgb_out = a.rgb_out;
+    unsigned int *slots = c->d_cert + kCertSlots * (2 * (size_t)p.index + which);
+    const unsigned cap = (unsigned)std::min<size_t>(j.cert_cap, (size_t)n_pts);
+    // the pre-filter's arithmetic: f16 where the network fits its range (8 x closer to the exact pre-activations: tighter margins, a shorter
+    // list), else bf16; a tile of the f16 pass that saw an activation leave the range counts in slots[12] and render_device goes back to bf16
+    const bool pf16 = c->cert_prefilter_f16[which];
+    const float *pf_stream = pf16 ? (const float *)net.wstream_f16v2 : stream_of(net, NERF_MLP_BF16);
+    MlpArgs b = a;
+    b.wstream = pf_stream; b.small_params = net.small;
+    b.rgb_out = nullptr; b.raw_pre = 1; b.skip_empty = 0; b.skip_counter = nullptr; b.nonfinite = pf16 ? slots + 12 : nullptr;
+    const int kind_side = which == 0 && !rgb_out ? 0 : 4;
+    int rc = timed(c, st, kind_side, 0, [&]() -> int {
+        if (c->cert_seq_prefilter) {
+            // the pre-filter walks each ray front to back and stops where its own (bf16) transmittance predicts the cut, a little
+            // later than k_cert_plan will (depth + 0.5): samples it never reaches stay NaN = "not evaluated" = uncertain
+            HIP_TRY(c, hipMemsetAsync(sigma_out, 0xFF, (size_t)n_pts * sizeof(float), st));
+            SeqArgs q = seq_args(c, j, p, pf_stream, net.small, spr, t_in, sigma_out);
+            q.ray_counter = slots + 8; q.stats = (unsigned long long *)(slots + 10);
+            q.prefilter = 1; q.prefilter_cut_T = expf(-(c->cert_depth_limit + 0.5f));
+            q.nonfinite = pf16 ? slots + 12 : nullptr;
+            HIP_TRY(c, pf16 ? nerf_trunk_seq_f16v2_launch(q, c->n_cus, st) : nerf_trunk_seq_bf16_launch(q, false, c->n_cus, st));
+        } else HIP_TRY(c, pf16 ? nerf_mlp_f16v2_launch(b, c->n_cus, st) : launch_mlp(c, NERF_MLP_BF16, b, false, st));
+        CertPlanArgs q{};
+        q.pre = sigma_out; q.t = t_in; q.n_rays = p.n_rays; q.spr = spr; q.far_ = j.far_;
+        q.margin = c->cert_margin[which]; q.depth_limit = c->cert_depth_limit;
+        q.audit_mask = c->cert_audit_mask; q.audit_mask_near = c->cert_audit_mask_near;
+        q.audit_salt = (unsigned)(j.seed * 0x9E3779B97F4A7C15ull >> 32) + 0x632BE5ABu * p.index + (unsigned)which;
+        q.list = c->d_point_list; q.count = slots; q.capacity = cap; q.jstar = c->d_jstar;
+        // full evaluations: probable zeros (pre-filter pre-activation below -margin x cert_zero_frac: several times the largest pre-filter error
+        // the lego audits see is not needed for a skip -- a positive density among them only keeps its tile's colour heads) and the audited
+        // certificates go to the back part of the list, whose all-zero tiles skip the colour head (exact: skip_empty)
+        if (rgb_out && c->cert_zero_tiles) { q.count_back = slots + 9; q.zero_threshold = c->cert_margin[which] * c->cert_zero_frac; }
+        q.aux = c->d_cert_aux; q.aux_count = slots + 7; q.aux_capacity = (unsigned)j.aux_cap;
+        HIP_TRY(c, launch_cert_plan(q, st));
+        if (rgb_out) HIP_TRY(c, hipMemsetAsync(rgb_out, 0, (size_t)n_pts * 3 * sizeof(float), st)); // weight 0 either way: 0 * 0
+        return NERF_OK;
+    });
+    if (rc) return rc;
+    MlpArgs l = b;
+    l.wstream = stream_of(net, dt); l.small_params = small_of(net, dt); zskip_of(c, net, l); l.raw_pre = 0; l.mode = MLP_MODE_LIST; l.rgb_out = rgb_out; l.n_points = (int)cap;
+    l.point_list = c->d_point_list; l.point_list_count = slots;
+    if (rgb_out && c->cert_zero_tiles) { l.point_list_count_back = slots + 9; l.skip_empty = 1; l.skip_counter = c->d_skip; }
+    l.nonfinite = nonfinite_of(c, dt);
+    // points = 0: the list's length is known on the device only (nerf_stats.n_exec_* report it after the frame)
+    if (cap > 0 && (rc = timed(c, st, kind, 0, [&]() -> int { HIP_TRY(c, launch_mlp(c, dt, l, rgb_out != nullptr, st)); return NERF_OK; }))) return rc;
+    return timed(c, st, kind_side, 0, [&]() -> int {
+        HIP_TRY(c, launch_cert_audit(c->d_cert_aux, slots + 7, (unsigned)j.aux_cap, sigma_out, slots + 2, c->n_cus, st));
+        CertVerifyArgs v{};
+        v.t = t_in; v.sigma = sigma_out; v.n_rays = p.n_rays; v.spr = spr; v.far_ = j.far_; v.jstar = c->d_jstar;
+        v.list = c->d_point_list; v.count = slots + 1; v.capacity = cap; v.fallback_rays = slots + 6;
+        HIP_TRY(c, launch_cert_verify(v, st));
+        l.point_list_count = slots + 1; l.point_list_count_back = nullptr;
+        if (cap > 0) HIP_TRY(c, launch_mlp(c, dt, l, rgb_out != nullptr, st)); // usually an empty list: the launch returns at once
+        return NERF_OK;
+    });
+}
+
+// steps 2 and 5: network `which` in arithmetic dt over the spr samples per ray at t of the pass's rays; rgb_out == NULL: densities only.
+// Four ways: ray-sequential (skip_dead), certified (certify_zero), or plainly -- in ray mode from the shared origin (the origin rides in the
+// kernel arguments), or for per-ray origins in points mode behind k_batch_points, which expands the samples into points + per-sample
+// directions; points mode forms nothing itself and then runs the same per-column arithmetic: the two plain paths carry the same bits.
+int eval_net(nerf_ctx *c, const RenderJob &j, const Pass &p, int which, int dt, int spr, const float *t, float *sigma_out, float *rgb_out, int kind) {
+    const DevNet &net = c->net[which];
+    if (j.seq) return seq_pass(c, j, p, net, dt, spr, t, sigma_out, rgb_out, 3 * (int)p.index + which, kind);
+    const hipStream_t st = j.st;
+    MlpArgs a{};
+    a.ray_dirs = c->d_dirs;
+    if (p.origins) a.mode = MLP_MODE_POINTS;
+    else { a.mode = MLP_MODE_RAYS; copy3(a.origin, j.origin); }
+    a.wstream = stream_of(net, dt); a.small_params = small_of(net, dt); zskip_of(c, net, a);
+    a.n_points = p.n_rays * spr; a.samples_per_ray = spr; a.t = t;
+    a.sigma_out = sigma_out; a.rgb_out = rgb_out; // the coarse network: sigma only unless its colours are composited (reference discards them, src/lib.rs:404)
+    a.skip_empty = j.skip_empty; a.skip_counter = j.skip_empty ? c->d_skip : nullptr; // only full kernels look at it
+    a.nonfinite = nonfinite_of(c, dt);
+    if (which == NERF_NET_FINE) a.clock_out = j.clock_out;
+    if (j.certify) return cert_pass(c, j, p, a, net, which, dt, kind);
+    bool full = rgb_out != nullptr;
+    if (p.origins) {
+        // only the f32 kernel has a sigma-only points mode: a bf16 sampling pass over expanded points runs the full kernel (the same
+        // densities) and leaves its colours in the fine pass's buffer, which that pass overwrites
+        if (!full && dt != NERF_MLP_F32) { full = true; a.rgb_out = c->d_rgbf; }
+        BatchPointsArgs q{};
+        q.n_rays = p.n_rays; q.spr = spr; q.origins = p.origins; q.dirs = c->d_dirs; q.t = t;
+        q.pts_soa = j.d_pts; q.dirs_aos = j.d_daos;
+        a.pts_soa = j.d_pts; a.dirs_aos = j.d_daos;
+        int rc;
+        if ((rc = timed(c, st, 2, 0, [&]() -> int { HIP_TRY(c, launch_batch_points(q, st)); return NERF_OK; }))) return rc;
+    }
+    return timed(c, st, kind, (uint64_t)a.n_points, [&]() -> int { HIP_TRY(c, launch_mlp(c, dt, a, full, st)); return NERF_OK; });
+}
+
+// hybrid_sampling, after the first resample ra: the coarse densities came from the split arithmetic.  Redo, in exact f32, the rays with a
+// draw in a light CDF bin (their sample positions are the ill-conditioned ones) and resample just those: same positions as the f32 path.
+// hctr: {queue head, flagged-ray count, u64 chunks}
+int hybrid_redo(nerf_ctx *c, const RenderJob &j, const Pass &p, const ResampleArgs &ra, unsigned int *hctr) {
+    const hipStream_t st = j.st;
+    const DevNet &NC = c->net[NERF_NET_COARSE];
+    SeqArgs q = seq_args(c, j, p, NC.wstream, NC.small_f32, j.nc, c->d_tc, c->d_sc);
+    zskip_of(c, NC, q);
+    q.ray_counter = hctr; q.stats = (unsigned long long *)(hctr + 2);
+    q.live_count = nullptr; // hctr[1] is the LENGTH of the ray list below: this launch never exports (no colour head)
+    q.ray_list = c->d_flag_list; q.ray_list_count = hctr + 1; q.zero_fill_after_cut = 1;
+    int rc;
+    if ((rc = timed(c, st, 0, 0, [&]() -> int { HIP_TRY(c, nerf_trunk_seq_launch(q, false, c->n_cus, st)); return NERF_OK; }))) return rc;
+    ResampleArgs rb = ra;
+    rb.flag_tau = 0.0f; rb.flag_count = nullptr; rb.flag_list = nullptr;
+    rb.ray_list = c->d_flag_list; rb.ray_list_count = hctr + 1;
+    return timed(c, st, 2, 0, [&]() -> int { HIP_TRY(c, launch_resample(rb, st)); return NERF_OK; });
+}
+
+// The normals of the pass (j.normals != NULL), from the weights the compositing launch left in nw.w (t: the composited samples' positions):
+//     count + scan + list (3 launches) -> [8 bytes to the host] -> stencil -> sigma-only MLP over 6 L points -> reduce
+// The live total L of a pass goes back to the host -- ONE SMALL COPY AND ONE STREAM SYNCHRONISATION PER PASS, as mesh_extract reads
+// its counts: it sizes the stencil workspace (16 B per point, grown on demand) and the launches that follow; a pass with L = 0 launches
+// nothing further and writes zero normals.  The network differentiated is the one composited, always in f32.
+int normals_pass(nerf_ctx *c, const RenderJob &j, const Pass &p, const DevNet &net, const float *t) {
+    if (!j.normals) return NERF_OK;
+    const hipStream_t st = j.st;
+    const NormalWorkspace &nw = j.nw;
+    const int n_rays = p.n_rays, n_comp = j.n_comp;
+    int rc;
+    NormalListArgs la{nw.w, n_rays, n_comp, nw.count, nw.base, nw.bsum, nw.totals, nw.list};
+    if ((rc = timed(c, st, 7, 0, [&]() -> int { HIP_TRY(c, launch_normal_list(la, st)); return NERF_OK; }))) return rc;
+    uint32_t totals[2] = {0, 0};
+    HIP_TRY(c, hipMemcpyAsync(totals, nw.totals, sizeof totals, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    const size_t L = totals[0];
+    c->normal_live += L; c->normal_samples += (uint64_t)n_rays * (uint64_t)n_comp;
+    float *out = j.normals + 3 * p.r0;
+    if (L == 0) { HIP_TRY(c, hipMemsetAsync(out, 0, (size_t)n_rays * 3 * sizeof(float), st)); return NERF_OK; }
+    if (L > (size_t)n_rays * (size_t)n_comp) return fail(c, NERF_ERR_HIP, "normals: the live count exceeds the pass's samples");
+    if ((rc = ensure_bytes(c, &c->d_stencil, &c->stencil_bytes, 6 * L * 4 * sizeof(float)))) return rc;
+    float *d_spts = (float *)c->d_stencil, *d_ssig = d_spts + 18 * L;
+    NormalStencilArgs sa{};
+    sa.n_live = (uint32_t)L; sa.h = j.h; sa.list = nw.list; sa.spr = n_comp; sa.origins = p.origins; sa.dirs = c->d_dirs; sa.t = t; sa.pts = d_spts;
+    if (!p.origins) copy3(sa.origin, j.origin);
+    if ((rc = timed(c, st, 7, 0, [&]() -> int { HIP_TRY(c, launch_normal_stencil(sa, st)); return NERF_OK; }))) return rc;
+    if ((rc = timed(c, st, 6, (uint64_t)(6 * L), [&]() -> int { HIP_TRY(c, launch_sigma_points(c, net, d_spts, 6 * L, d_ssig, st)); return NERF_OK; }))) return rc;
+    NormalReduceArgs ra{n_rays, (uint32_t)L, nw.count, nw.base, nw.list, nw.w, d_spts, d_ssig, out};
+    return timed(c, st, 7, 0, [&]() -> int { HIP_TRY(c, launch_normal_reduce(ra, st)); return NERF_OK; });
+}
+
+// The loop over passes: everything a render launches between its driver's allocations and its counters' read-back.
+int render_passes(nerf_ctx *c, const RenderJob &j, uint32_t *n_passes) {
+    const hipStream_t st = j.st;
+    int rc;
+    if ((j.skip_empty || j.certify) && c->d_skip) HIP_TRY(c, hipMemsetAsync(c->d_skip, 0, sizeof(unsigned long long), st));
+    if (watches_range(c, j)) HIP_TRY(c, hipMemsetAsync(c->d_nonfinite, 0, sizeof(unsigned int), st));
+    const DevNet &NC = c->net[NERF_NET_COARSE], &NF = c->net[NERF_NET_FINE];
+    uint32_t passes = 0;
+    for (size_t r0 = 0; r0 < j.n_rays; r0 += j.pass_rays, ++passes) {
+        Pass p{};
+        p.index = passes; p.r0 = r0; p.n_rays = (int)std::min(j.pass_rays, j.n_rays - r0);
+        if ((rc = prepare_rays(c, j, p))) return rc;
+        if ((rc = eval_net(c, j, p, NERF_NET_COARSE, j.dtype_coarse, j.nc, c->d_tc, c->d_sc, j.coarse_only ? c->d_rgbc : nullptr,
+                           j.coarse_only ? j.kind_colour : 0))) return rc;
+        CompositeArgs ca{};
+        ca.n_rays = p.n_rays; ca.far_ = j.far_; ca.far_per_ray = j.d_far; ca.out = j.out + 3 * r0;
+        ca.depth = j.depth ? j.depth + r0 : nullptr; ca.opacity = j.opacity ? j.opacity + r0 : nullptr;
+        if (j.background) { ca.use_bg = 1; copy3(ca.bg, j.background); }
+        if (j.normals) ca.w_out = j.nw.w;
+        if (j.coarse_only) {
+            ca.n = j.nc; ca.t = c->d_tc; ca.sigma = c->d_sc; ca.rgb = c->d_rgbc;
+            if ((rc = timed(c, st, 2, 0, [&]() -> int { HIP_TRY(c, launch_composite(ca, st)); return NERF_OK; }))) return rc;
+            if ((rc = normals_pass(c, j, p, NC, c->d_tc))) return rc;
+            continue;
+        }
+        const float *t_fine = c->d_tc;
+        if (j.nf > 0) {
+            ResampleArgs ra{};
+            ra.g = p.g; ra.n_rays = p.n_rays; ra.nc = j.nc; ra.nf = j.nf; ra.far_ = j.far_; ra.far_per_ray = j.d_far;
+            ra.seed_lo = (uint32_t)j.seed; ra.seed_hi = (uint32_t)(j.seed >> 32);
+            ra.t_coarse = c->d_tc; ra.sigma_coarse = c->d_sc; ra.t_fine = c->d_tf;
+            ra.pixel_index = p.rng;
+            unsigned int *hctr = j.seq ? c->d_seq + 4 * (size_t)(3 * passes + 2) : nullptr;
+            if (j.hybrid) { ra.flag_tau = c->hybrid_tau; ra.flag_count = hctr + 1; ra.flag_list = c->d_flag_list; }
+            if ((rc = timed(c, st, 2, 0, [&]() -> int { HIP_TRY(c, launch_resample(ra, st)); return NERF_OK; }))) return rc;
+            if (j.hybrid && (rc = hybrid_redo(c, j, p, ra, hctr))) return rc;
+            t_fine = c->d_tf;
+        }
+        if (j.clock_out) c->clock_valid = true;
+        if ((rc = eval_net(c, j, p, NERF_NET_FINE, j.dtype, j.M, t_fine, c->d_sf, c->d_rgbf, j.kind_colour))) return rc;
+        ca.n = j.M; ca.t = t_fine; ca.sigma = c->d_sf; ca.rgb = c->d_rgbf;
+        if ((rc = timed(c, st, 2, 0, [&]() -> int { HIP_TRY(c, launch_composite(ca, st)); return NERF_OK; }))) return rc;
+        if ((rc = normals_pass(c, j, p, NF, t_fine))) return rc;
+    }
+    *n_passes = passes;
+    return NERF_OK;
+}
+
+// What the audit of a certify_zero frame found (per network: 0 coarse, 1 fine), read from the device after the frame.
+struct CertOutcome {
+    uint64_t audited[2] = {0, 0}, violations[2] = {0, 0};
+    float headroom[2] = {INFINITY, INFINITY}; // min over the audited certificates of -(exact pre-activation)
+    float max_err[2] = {0.0f, 0.0f};          // max over them of |bf16 - exact pre-activation|
+    uint64_t listed[2] = {0, 0};      // samples the exact kernel evaluated (both launches, audited certificates included)
+    uint64_t fallback_rays = 0;       // rays whose predicted cut the exact transmittance did not confirm
+    uint64_t range_left[2] = {0, 0};  // f16 pre-filter: wave tiles in which an activation left the f16 range (the frame's certificates are void)
+    uint64_t list_need = 0;           // largest list any pass wanted ...
+    uint64_t list_capacity = 0;       // ... and what it had
+    uint64_t pass_samples = 0;        // samples of the largest network pass (the list's worst case)
+    bool used[2] = {false, false};
+};
+
+// the audit's outcome decides whether this frame stands (render_device): certify_zero renders synchronise the stream
+int read_cert_outcome(nerf_ctx *c, const RenderJob &j, uint32_t passes, CertOutcome *cert) {
+    HIP_TRY(c, hipStreamSynchronize(j.st));
+    std::vector<unsigned int> h((size_t)passes * 2 * kCertSlots);
+    HIP_TRY(c, hipMemcpy(h.data(), c->d_cert, h.size() * sizeof(unsigned int), hipMemcpyDeviceToHost));
+    for (uint32_t k = 0; k < passes * 2; ++k) {
+        const unsigned int *q = &h[(size_t)k * kCertSlots];
+        const int w = (int)(k & 1);
+        if (w == 1 && j.coarse_only) continue;
+        cert->used[w] = true;
+        cert->listed[w] += std::min<uint64_t>((uint64_t)q[0] + q[9], cert->list_capacity) + std::min<uint64_t>(q[1], cert->list_capacity);
+        cert->list_need = std::max<uint64_t>(cert->list_need, std::max<uint64_t>((uint64_t)q[0] + q[9], q[1]));
+        cert->audited[w] += q[2]; cert->violations[w] += q[3];
+        if (q[2]) {
+            const unsigned bits = 0x7f800000u - q[4];
+            float hr, er;
+            memcpy(&hr, &bits, sizeof hr); memcpy(&er, &q[5], sizeof er);
+            cert->headroom[w] = std::min(cert->headroom[w], hr); cert->max_err[w] = std::max(cert->max_err[w], er);
+        }
+        cert->fallback_rays += q[6];
+        cert->range_left[w] += q[12];
+    }
+    return NERF_OK;
+}
+
+// The stats of a finished render (stats != NULL: synchronises the stream): the part every render has, then what the job's modes counted.
+int finish_stats(nerf_ctx *c, const RenderJob &j, uint32_t passes, nerf_stats *stats, const CertOutcome *cert) {
+    if (!stats) return NERF_OK;
+    HIP_TRY(c, hipStreamSynchronize(j.st));
+    memset(stats, 0, sizeof *stats);
+    stats->n_rays = j.n_rays;
+    stats->n_passes = passes;
+    stats->n_coarse_points = stats->n_rays * (uint64_t)j.nc;                       // nominal: every sample of every ray
+    stats->n_fine_points = j.coarse_only ? 0 : stats->n_rays * (uint64_t)j.M;
+    double ms_normal_sigma = 0.0, ms_normal_small = 0.0;
+    for (const auto &p : c->last_render) {
+        float ms = 0.f;
+        HIP_TRY(c, hipEventElapsedTime(&ms, p.a, p.b));
+        if (p.kind == 0) { stats->ms_coarse_mlp += ms; stats->n_mlp_launches++; }
+        else if (p.kind == 1 || p.kind == 4 || p.kind == 5) { // the colour-producing launch; 4: colour head on the compacted live samples (skip_dead)
+            stats->n_mlp_launches++;
+            if (j.coarse_only) stats->ms_coarse_mlp += ms; else stats->ms_fine_mlp += ms;
+        } else stats->ms_other += ms; // kinds 6 and 7 too: a normals render's own launches are neither network pass of the colour
+        if (p.kind == 6) ms_normal_sigma += ms; else if (p.kind == 7) ms_normal_small += ms;
+    }
+    if (!c->last_render.empty()) {
+        float ms = 0.f;
+        HIP_TRY(c, hipEventElapsedTime(&ms, c->last_render.front().a, c->last_render.back().b));
+        stats->ms_total = ms;
+    }
+    if (j.normals && c->debug_normals)
+        fprintf(stderr, "nerf normals: %llu live of %llu composited samples, sigma launches %.3f ms over %llu points, other normal kernels %.3f ms\n",
+                (unsigned long long)c->normal_live, (unsigned long long)c->normal_samples, ms_normal_sigma, (unsigned long long)(6 * c->normal_live),
+                ms_normal_small);
+    if (watches_range(c, j)) {
+        unsigned int bad = 0;
+        HIP_TRY(c, hipMemcpy(&bad, c->d_nonfinite, sizeof bad, hipMemcpyDeviceToHost));
+        stats->n_nonfinite_points = bad;
+    }
+    if ((j.skip_empty || j.certify) && c->d_skip) { // certify_zero: all-zero tiles of the list's back part (probable zeros, audited certificates)
+        unsigned long long tiles = 0;
+        HIP_TRY(c, hipMemcpy(&tiles, c->d_skip, sizeof tiles, hipMemcpyDeviceToHost));
+        stats->n_colour_skipped_points = (uint64_t)tiles * nerfmlp::kPointsPerBlock;
+    }
+    // evaluations actually executed
+    const uint64_t n_colour = j.coarse_only ? stats->n_coarse_points : stats->n_fine_points;
+    stats->n_exec_coarse_trunk = stats->n_coarse_points;
+    stats->n_exec_fine_trunk = stats->n_fine_points;
+    stats->n_exec_colour = n_colour - stats->n_colour_skipped_points;
+    if (j.certify && cert) { // samples the exact kernel evaluated = the lengths of the lists (audited certificates included)
+        const uint64_t listed = j.coarse_only ? cert->listed[0] : cert->listed[1];
+        stats->n_exec_coarse_trunk = cert->listed[0];
+        stats->n_exec_fine_trunk = j.coarse_only ? 0 : cert->listed[1];
+        stats->n_exec_colour = listed - std::min<uint64_t>(stats->n_colour_skipped_points, listed);
+        stats->n_certify_audited = cert->audited[0] + cert->audited[1];
+        stats->n_certify_violations = cert->violations[0] + cert->violations[1];
+        stats->n_certify_fallback_rays = (uint32_t)std::min<uint64_t>(cert->fallback_rays, 0xffffffffu);
+        for (int w = 0; w < 2; ++w) { stats->certify_margin[w] = c->cert_margin[w]; stats->certify_headroom[w] = cert->headroom[w]; stats->certify_max_error[w] = cert->max_err[w]; }
+    }
+    if (j.seq) {
+        std::vector<unsigned int> h((size_t)passes * 3 * 4);
+        HIP_TRY(c, hipMemcpy(h.data(), c->d_seq, h.size() * sizeof(unsigned int), hipMemcpyDeviceToHost));
+        uint64_t evaluated[3] = {0, 0, 0}, live = 0; // samples the trunk launches evaluated (a ray's last chunk may be partial)
+        for (uint32_t k = 0; k < passes * 3; ++k) {
+            unsigned long long ch64;
+            memcpy(&ch64, &h[4 * (size_t)k + 2], sizeof ch64);
+            evaluated[k % 3] += ch64;
+            if (k % 3 == 2) stats->n_hybrid_rays += h[4 * (size_t)k + 1]; // flagged rays redone in f32
+            else live += h[4 * (size_t)k + 1];
+        }
+        stats->n_exec_coarse_trunk = evaluated[0] + evaluated[2];
+        stats->n_exec_fine_trunk = j.coarse_only ? 0 : evaluated[1];
+        stats->n_exec_colour = live;
+        stats->n_colour_skipped_points = n_colour - live;
+    }
+    if (stats->n_nonfinite_points) { // the result is WRONG there (f16 overflow yields finite garbage, not NaN): never return it as a success
+        char msg[320];
+        snprintf(msg, sizeof msg, "%llu evaluations: an operand left the range of the split arithmetic (NERF_MLP_F16X2: |activation| <= 65504) or a "
+                 "density was not finite; the %s is not usable -- use NERF_MLP_BF16X3 or NERF_MLP_F32", (unsigned long long)stats->n_nonfinite_points, j.what);
+        return fail(c, NERF_ERR_STATE, msg);
+    }
+    return NERF_OK;
+}
+
+// ---- image renders --------------------------------------------------------------------------------------------------------------------
+// the mode switches of an image render and the combinations the kernels exist for
+int check_image_modes(nerf_ctx *c, const nerf_render_opts *o) {
+    const int dtype = o->mlp_dtype;
+    if (o->skip_empty != 0 && o->skip_empty != 1) return fail(c, NERF_ERR_INVALID, "skip_empty must be 0 or 1");
+    if (o->skip_dead != 0 && o->skip_dead != 1) return fail(c, NERF_ERR_INVALID, "skip_dead must be 0 or 1");
+    const bool seq = o->skip_dead != 0;
+    if (seq && dtype == NERF_MLP_BF16 && !bf16_is_v2()) return fail(c, NERF_ERR_INVALID, "skip_dead with NERF_MLP_BF16 is not part of the NERF_BF16_V3 variant build");
+    if (o->hybrid_sampling != 0 && o->hybrid_sampling != 1) return fail(c, NERF_ERR_INVALID, "hybrid_sampling must be 0 or 1");
+    if (o->certify_zero != 0 && o->certify_zero != 1) return fail(c, NERF_ERR_INVALID, "certify_zero must be 0 or 1");
+    if (o->certify_zero && (dtype == NERF_MLP_BF16 || seq || o->skip_empty || !bf16_is_v2()))
+        return fail(c, NERF_ERR_INVALID, "certify_zero needs mlp_dtype F32, BF16X3 or F16X2 and neither skip_empty nor skip_dead");
+    if (o->hybrid_sampling && !(seq && !o->coarse_only && dtype != NERF_MLP_BF16)) // bf16 is its own arithmetic: there are no f32 sample positions to protect
+        return fail(c, NERF_ERR_INVALID, "hybrid_sampling needs skip_dead = 1, mlp_dtype F32, BF16X3 or F16X2, and a hierarchical render");
+    return NERF_OK;
+}
+
+// The pixels a render covers: the crop window, or one band of its rows (multi-GPU): contiguous bands are just a shorter window; striped
+// bands keep the window and map band-local rows to window rows in the ray generator (sampling_kernels.hip ray_row)
+struct Window { int s, x0, y0, cw, ch, stripe; };
+int image_window(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *o, Window *w) {
+    w->s = o->ssaa > 1 ? o->ssaa : 1;
+    w->x0 = 0; w->y0 = 0; w->cw = cam->nx; w->ch = cam->ny; w->stripe = 0;
+    if (o->crop_w > 0 || o->crop_h > 0) { w->x0 = o->crop_x0; w->y0 = o->crop_y0; w->cw = o->crop_w; w->ch = o->crop_h; }
+    if (w->cw <= 0 || w->ch <= 0 || w->x0 < 0 || w->y0 < 0 || w->x0 + w->cw > cam->nx || w->y0 + w->ch > cam->ny)
+        return fail(c, NERF_ERR_INVALID, "crop window outside the frame");
+    if (o->band_count > 1) {
+        if (o->band_index < 0 || o->band_index >= o->band_count || o->band_stripe_rows < 0) return fail(c, NERF_ERR_INVALID, "band_index / band_count / band_stripe_rows out of range");
+        const int rows = band_rows(w->ch, o->band_index, o->band_count, o->band_stripe_rows);
+        if (rows <= 0) return fail(c, NERF_ERR_INVALID, "this band has no rows (more bands than rows)");
+        if (o->band_stripe_rows == 0) w->y0 += band_first_row(w->ch, o->band_index, o->band_count);
+        else w->stripe = o->band_stripe_rows;
+        w->ch = rows;
+    } else if (o->band_count < 0) return fail(c, NERF_ERR_INVALID, "band_count must be >= 0");
+    return NERF_OK;
+}
+
+// skip_dead in a split arithmetic or in bf16 (two launches): the compacted trunk outputs are sized for the worst case (every sample
+// of a pass live; 1 KiB each as f32 tiles, 512 B as packed bf16).  The f32 kernel compacts in LDS and runs its colour passes in the
+// same launch: no buffer, no extra passes.
+bool exports_h8(const RenderJob &j) { return j.seq && (split_dtype(j.dtype) || j.dtype == NERF_MLP_BF16); }
+
+// the rays per pass that buffer's budget allows (called with the export mutex held)
+int export_budget(nerf_ctx *c, const RenderJob &j, int RW, size_t *pass_cap) {
+    const size_t h8_sample_bytes = j.dtype == NERF_MLP_BF16 ? 512 : 1024;
+    size_t budget = c->max_export_bytes, free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) // never more than half of what the device can still give (plus what we already hold)
+        budget = std::min(budget, (free_b + c->h8_bytes) / 2);
+    const size_t row_bytes = (size_t)RW * j.M * h8_sample_bytes;
+    if (row_bytes > budget) {
+        char msg[256];
+        snprintf(msg, sizeof msg, "skip_dead in this arithmetic exports %zu B per sample: one ray row of this render (%d rays x %d samples) needs "
+                 "%zu MiB, the budget is %zu MiB (NERF_MAX_EXPORT_BYTES, free device memory / 2); render a narrower crop or use NERF_MLP_F32",
+                 h8_sample_bytes, RW, j.M, row_bytes >> 20, budget >> 20);
+        return fail(c, NERF_ERR_INVALID, msg);
+    }
+    *pass_cap = std::min<size_t>(*pass_cap, budget / ((size_t)j.M * h8_sample_bytes));
+    return NERF_OK;
+}
+
+// skip_dead: the counters, per MLP launch {u32 ray queue head, u32 live-sample count, u64 evaluated samples}, cleared; the export buffer (which
+// releases h8_lock); the hybrid redo's ray list
+int reserve_seq(nerf_ctx *c, const RenderJob &j, size_t n_passes, std::unique_lock<std::mutex> &h8_lock) {
+    int rc;
+    const size_t slots = n_passes * 3; // per pass: coarse, fine, hybrid f32 redo of the coarse pass
+    if (slots > c->seq_slots) {
+        size_t bytes = c->seq_slots * 16;
+        if ((rc = ensure_bytes(c, (void **)&c->d_seq, &bytes, slots * 16))) return rc;
+        c->seq_slots = slots;
+    }
+    HIP_TRY(c, hipMemsetAsync(c->d_seq, 0, slots * 16, j.st));
+    const size_t pass_samples = j.pass_rays * (size_t)j.M;
+    if (exports_h8(j)) {
+        const size_t need = j.dtype == NERF_MLP_BF16 ? nerf_seq_h8_bytes_bf16(pass_samples) : nerf_seq_h8_bytes(pass_samples);
+        if (c->d_h8 && need < c->h8_bytes / 4) { // a much smaller render: give the big buffer back
+            HIP_TRY(c, hipDeviceSynchronize());
+            HIP_TRY(c, hipFree(c->d_h8));
+            c->d_h8 = nullptr; c->h8_bytes = 0;
+        }
+        if ((rc = ensure_bytes(c, (void **)&c->d_h8, &c->h8_bytes, need))) return rc;
+        if ((rc = ensure_bytes(c, (void **)&c->d_slot_point, &c->slot_point_bytes, (pass_samples + 256) * sizeof(unsigned int)))) return rc;
+        h8_lock.unlock();
+    }
+    if (j.hybrid && (rc = ensure_bytes(c, (void **)&c->d_flag_list, &c->flag_list_bytes, j.pass_rays * sizeof(unsigned int)))) return rc;
+    return NERF_OK;
+}
+
+// certify_zero: the sample list, the predicted cuts, the audit records and the counters (cleared); sets j.cert_cap and j.aux_cap
+int reserve_certify(nerf_ctx *c, RenderJob &j, size_t n_pass, CertOutcome *cert) {
+    int rc;
+    if (cert_plan_lds_bytes(j.M, nullptr) > 159 * 1024) return fail(c, NERF_ERR_INVALID, "certify_zero: too many samples per ray");
+    const size_t pass_samples = j.pass_rays * (size_t)j.M;
+    // the list is sized from what earlier frames needed (c->cert_list_frac of the samples, +25 %): if a pass wants more, the entries
+    // beyond the capacity are counted, not stored, and render_device renders the frame again with a list that fits
+    // (up to 64 MiB the list simply holds every sample: small renders -- a central crop lists 70 % of its samples -- never take that path)
+    j.cert_cap = pass_samples <= ((size_t)16 << 20) ? pass_samples : std::min<size_t>(pass_samples, (size_t)((double)pass_samples * c->cert_list_frac) + 4096);
+    if ((rc = ensure_bytes(c, (void **)&c->d_point_list, &c->point_list_bytes, j.cert_cap * sizeof(unsigned int)))) return rc;
+    j.cert_cap = std::min<size_t>(pass_samples, c->point_list_bytes / sizeof(unsigned int)); // an earlier, larger allocation is kept
+    if ((rc = ensure_bytes(c, (void **)&c->d_jstar, &c->jstar_bytes, j.pass_rays * sizeof(int)))) return rc;
+    j.aux_cap = 2 * (pass_samples / ((size_t)std::min(c->cert_audit_mask, c->cert_audit_mask_near) + 1)) + 4096; // more than the audit can select: a certificate that does not fit is not audited
+    if ((rc = ensure_bytes(c, (void **)&c->d_cert_aux, &c->cert_aux_bytes, j.aux_cap * 2 * sizeof(unsigned int)))) return rc;
+    if ((rc = ensure_bytes(c, (void **)&c->d_cert, &c->cert_bytes, kCertSlots * 2 * n_pass * sizeof(unsigned int)))) return rc;
+    HIP_TRY(c, hipMemsetAsync(c->d_cert, 0, kCertSlots * 2 * n_pass * sizeof(unsigned int), j.st));
+    if (cert) { cert->list_capacity = j.cert_cap; cert->pass_samples = pass_samples; }
+    return NERF_OK;
+}
+
+// One attempt at an image (render_device decides whether a certify_zero frame stands).  Passes are whole ray rows of the window.
+int render_once(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *o, float *d_out, float *d_depth, float *d_opacity, hipStream_t st,
+                nerf_stats *stats, CertOutcome *cert, const float *background) {
+    int rc;
+    if ((rc = check_camera(c, cam))) return rc;
+    if (!o) return fail(c, NERF_ERR_INVALID, "opts is NULL");
+    if (!d_out) return fail(c, NERF_ERR_INVALID, "output pointer is NULL");
+    if ((rc = check_sample_plan(c, o, PLAN_COUNTS))) return rc;
+    if ((rc = check_image_modes(c, o))) return rc;
+    if ((rc = check_sample_plan(c, o, PLAN_NETWORKS))) return rc;
+    Window w;
+    if ((rc = image_window(c, cam, o, &w))) return rc;
+    if ((rc = check_sample_plan(c, o, PLAN_LIMITS))) return rc;
+    RenderJob j{};
+    plan_job(c, o, j);
+    j.near_ = cam->near_; j.far_ = cam->far_; j.background = background;
+    j.kind_colour = 1; j.what = "frame"; j.st = st;
+    j.skip_empty = o->skip_empty; j.seq = o->skip_dead != 0; j.certify = o->certify_zero != 0;
+    j.hybrid = o->hybrid_sampling != 0 && j.nf > 0; // without resampling there is nothing to protect
+    j.clock_out = c->d_clock; // NULL unless NERF_DEBUG_CLOCK=1
+    copy3(j.origin, cam->pos);
+    const int s = w.s, RW = w.cw * s, RH = w.ch * s, RX0 = w.x0 * s, RY0 = w.y0 * s;
+    size_t pass_cap = pass_capacity(c, j.M);
+    // Budget and allocation of the export buffer are ONE critical section per process: contexts that share a device (nerf_render_image_multi's
+    // worker threads) would otherwise each claim half of the same free memory and fail in hipMalloc.  A context keeps its buffer while
+    // later renders fit; a render that needs less than a quarter of it gives it back (shrinks).
+    static std::mutex h8_mu;
+    std::unique_lock<std::mutex> h8_lock(h8_mu, std::defer_lock);
+    if (exports_h8(j)) {
+        h8_lock.lock();
+        if ((rc = export_budget(c, j, RW, &pass_cap))) return rc;
+    }
+    if ((size_t)RW > pass_cap && (size_t)RW * j.M > (size_t)0x3fffffff) return fail(c, NERF_ERR_INVALID, "ray row too wide for one pass");
+    const size_t rows_per_pass = std::max<size_t>(1, std::min<size_t>(RH, pass_cap / (size_t)RW));
+    j.n_rays = (size_t)RW * RH; j.pass_rays = rows_per_pass * RW;
+    if ((rc = ensure_workspace(c, j.pass_rays, j.nc, j.M, j.coarse_only))) return rc;
+    j.out = d_out; j.depth = d_depth; j.opacity = d_opacity;
+    if (s > 1) {
+        if ((rc = ensure_bytes(c, (void **)&c->d_rayfb, &c->rayfb_floats, (size_t)RW * RH * 3 * sizeof(float)))) return rc;
+        j.out = c->d_rayfb;
+        if (d_depth || d_opacity) { // ray-level maps, one plane each, box-filtered like the colour below
+            if ((rc = ensure_bytes(c, (void **)&c->d_rayaux, &c->rayaux_bytes, (size_t)RW * RH * 2 * sizeof(float)))) return rc;
+            j.depth = d_depth ? c->d_rayaux : nullptr;
+            j.opacity = d_opacity ? c->d_rayaux + (size_t)RW * RH : nullptr;
+        }
+    }
+    const size_t n_passes_total = ((size_t)RH + rows_per_pass - 1) / rows_per_pass;
+    if (j.seq && (rc = reserve_seq(c, j, n_passes_total, h8_lock))) return rc;
+    if (j.certify && (rc = reserve_certify(c, j, n_passes_total, cert))) return rc;
+    recycle_render(c);
+    recycle_dominant(c, 4096); // bound the backlog if the caller never queries
+    // If this render returns early (a launch failed), its dominant-kernel event pairs never reach c->dominant: hand them back
+    // to last_render's ownership so that the next recycle_render returns them to the pool.
+    struct RenderScope {
+        nerf_ctx *c; bool ok = false;
+        ~RenderScope() { if (!ok) for (auto &p : c->last_render) if (p.kind == 1) p.kind = 2; }
+    } scope{c};
+    j.g = make_raygen(*cam, s);
+    j.g.rx0 = RX0; j.g.rw = RW; j.g.ry0 = w.stripe > 0 ? 0 : RY0;
+    if (w.stripe > 0) { j.g.stripe = w.stripe * s; j.g.stripe_n = o->band_count; j.g.stripe_i = o->band_index; j.g.stripe_y0 = RY0; }
+    uint32_t passes = 0;
+    if ((rc = render_passes(c, j, &passes))) return rc;
+    if (s > 1 && (rc = timed(c, st, 2, 0, [&]() -> int {
+            HIP_TRY(c, launch_box_downsample(c->d_rayfb, d_out, w.cw, w.ch, s, 3, st));
+            if (d_depth) HIP_TRY(c, launch_box_downsample(j.depth, d_depth, w.cw, w.ch, s, 1, st));
+            if (d_opacity) HIP_TRY(c, launch_box_downsample(j.opacity, d_opacity, w.cw, w.ch, s, 1, st));
+            return NERF_OK;
+        }))) return rc;
+    // the dominant-kernel events also feed nerf_kernel_time_query (ownership: see recycle_render)
+    for (const auto &p : c->last_render)
+        if (p.kind == 1) c->dominant.push_back(p);
+    scope.ok = true;
+    if (cert && (rc = read_cert_outcome(c, j, passes, cert))) return rc;
+    return finish_stats(c, j, passes, stats, cert);
+}
+
+// ---- ray batches (nerf_render_rays) -------------------------------------------------------------------------------------
+// What the header's contract needs beside render_once: the rays are the caller's, so there is no camera, no window and none of the modes
+// tied to either; a pass is at most max_rays_per_pass rays (rays * samples <= 0x3fffffff, as above).
+// arguments already checked (check_ray_batch, check_normals); asynchronous on st unless stats != NULL or d_normals != NULL (n_rays x 3: the
+// compositing launch then also hands out its weights, and normals_pass follows it in every pass).
+int render_rays_device(nerf_ctx *c, const RayBatch &b, const nerf_render_opts *o, const float *background, float *d_out, float *d_depth,
+                       float *d_opacity, hipStream_t st, nerf_stats *stats, float h = 0.0f, float *d_normals = nullptr) {
+    int rc;
+    if ((rc = check_sample_plan(c, o, PLAN_NETWORKS))) return rc;
+    RenderJob j{};
+    plan_job(c, o, j);
+    j.near_ = b.near_; j.far_ = b.far_; j.background = background;
+    j.out = d_out; j.depth = d_depth; j.opacity = d_opacity;
+    // events: all owned by last_render (kind 5, not 1, for the colour-producing network: c->dominant and with it nerf_kernel_time_query
+    // belong to image renders)
+    j.kind_colour = 5; j.what = "batch"; j.st = st;
+    j.batch = &b; j.normals = d_normals; j.h = h;
+    size_t pass_cap = pass_capacity(c, j.M);
+    // normals: if every sample of a pass were live its 6 stencil points each must still fit one MLP launch
+    if (d_normals) pass_cap = std::max<size_t>(1, std::min<size_t>(pass_cap, max_batch_points(c->n_cus) / (6 * (size_t)j.M)));
+    j.n_rays = b.n_rays; j.pass_rays = std::min(b.n_rays, pass_cap);
+    if ((rc = ensure_workspace(c, j.pass_rays, j.nc, j.M, j.coarse_only))) return rc;
+    j.n_comp = j.coarse_only ? j.nc : j.M;
+    if (d_normals && (rc = ensure_bytes(c, &c->d_normal, &c->normal_bytes, NormalWorkspace::bytes(j.pass_rays, j.pass_rays * (size_t)j.n_comp)))) return rc;
+    j.nw = NormalWorkspace(c->d_normal, j.pass_rays, j.pass_rays * (size_t)j.n_comp);
+    c->normal_live = 0; c->normal_samples = 0;
+    // c->d_batch (floats): [far per ray, padded to 64][points 3 x n SoA][directions n x 3 AoS], n = the pass's rays x M
+    const bool expand = b.d_origins != nullptr;
+    const size_t far_floats = b.d_bounds ? (j.pass_rays + 63) / 64 * 64 : 0, n_max = j.pass_rays * (size_t)j.M;
+    if (far_floats || expand) {
+        if ((rc = ensure_bytes(c, &c->d_batch, &c->batch_bytes, (far_floats + (expand ? 6 * n_max : 0)) * sizeof(float)))) return rc;
+        j.d_far = b.d_bounds ? (float *)c->d_batch : nullptr;
+        j.d_pts = (float *)c->d_batch + far_floats; j.d_daos = j.d_pts + 3 * n_max;
+    }
+    if (!expand) copy3(j.origin, b.h_origin);
+    recycle_render(c);
+    uint32_t passes = 0;
+    if ((rc = render_passes(c, j, &passes))) return rc;
+    return finish_stats(c, j, passes, stats, nullptr);
+}
+
+// everything nerf_render_rays* can refuse without a context or a device, in the header's order
+int check_ray_batch(nerf_ctx *c, const void *origins, size_t n_origins, const void *dirs, size_t n_rays, float near_, float far_, const void *bounds,
+                    const nerf_render_opts *o, const float *background, const void *rgb_out) {
+    if (!o) return fail(c, NERF_ERR_INVALID, "opts is NULL");
+    if (n_rays > (size_t)0x7fffffff) return fail(c, NERF_ERR_INVALID, "n_rays must be at most INT32_MAX");
+    if (n_rays > 0 && (!origins || !dirs || !rgb_out)) return fail(c, NERF_ERR_INVALID, "origins, dirs and rgb_out must not be NULL");
+    if (n_origins != 1 && n_origins != n_rays) return fail(c, NERF_ERR_INVALID, "n_origins must be 1 (one origin for every ray) or n_rays");
+    if (o->crop_x0 || o->crop_y0 || o->crop_w || o->crop_h) return fail(c, NERF_ERR_INVALID, "ray batches have no pixel grid: crop_* must be 0");
+    if (o->ssaa > 1) return fail(c, NERF_ERR_INVALID, "ray batches have no pixel grid: ssaa must be 0 or 1");
+    if (o->band_count > 1) return fail(c, NERF_ERR_INVALID, "ray batches have no rows: band_count must be 0 or 1");
+    if (o->skip_empty || o->skip_dead || o->hybrid_sampling || o->certify_zero)
+        return fail(c, NERF_ERR_INVALID, "skip_empty, skip_dead, hybrid_sampling and certify_zero are not available for ray batches (first version)");
+    int rc;
+    if ((rc = check_sample_plan(c, o, PLAN_COUNTS))) return rc;
+    if (!bounds) {
+        if (!std::isfinite(near_) || !std::isfinite(far_)) return fail(c, NERF_ERR_INVALID, "near_ and far_ must be finite when bounds is NULL");
+        if (!(far_ > near_)) return fail(c, NERF_ERR_INVALID, "far_ must be greater than near_ when bounds is NULL");
+    }
+    if (background && !(std::isfinite(background[0]) && std::isfinite(background[1]) && std::isfinite(background[2])))
+        return fail(c, NERF_ERR_INVALID, "background components must be finite");
+    return check_sample_plan(c, o, PLAN_LIMITS);
+}
+
+// the host entry point's per-ray checks: the first offending ray is named
+int check_ray_batch_rays(nerf_ctx *c, const float *origins, size_t n_origins, const float *dirs, size_t n_rays, int normalize, const float *bounds) {
+    char msg[160];
+    auto finite3 = [](const float *v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); };
+    for (size_t r = 0; r < n_rays; ++r) {
+        const char *what = nullptr;
+        const float *d = dirs + 3 * r;
+        if (r < n_origins && !finite3(origins + 3 * r)) what = "its origin is not finite";
+        else if (!finite3(d)) what = "its direction is not finite";
+        else if (normalize && d[0] == 0.0f && d[1] == 0.0f && d[2] == 0.0f) what = "its direction is zero and cannot be normalised";
+        else if (bounds && !(std::isfinite(bounds[2 * r]) && std::isfinite(bounds[2 * r + 1]))) what = "its bounds are not finite";
+        else if (bounds && !(bounds[2 * r + 1] > bounds[2 * r])) what = "its far is not greater than its near";
+        if (what) {
+            snprintf(msg, sizeof msg, "ray %zu: %s", r, what);
+            return fail(c, NERF_ERR_INVALID, msg);
+        }
+    }
+    return NERF_OK;
+}
+
+// what nerf_render_rays_normals* adds to check_ray_batch
+int check_normals(nerf_ctx *c, float h, const void *normals_out) {
+    if (!(std::isfinite(h) && h > 0.0f)) return fail(c, NERF_ERR_INVALID, "h (the central-difference step) must be finite and greater than 0");
+    if (!normals_out) return fail(c, NERF_ERR_INVALID, "normals_out must not be NULL");
+    return NERF_OK;
+}
+
+} // namespace
+
+// certify_zero frames are AUDITED (k_cert_audit: 1 in 16 of the samples certified by less than twice the margin and 1 in 128 of the others are evaluated exactly all the same).  A frame stands only if no
+// audited certificate was wrong and the closest audited sample kept at least half the margin between itself and a positive density;
+// otherwise the network's margin is widened -- for good: c->cert_margin is per context and network, reset when a network is loaded --
+// and the frame is rendered again.  The same loop grows the sample list when a pass wanted more entries than it had.  Margins are
+// measurements, not proofs: what this buys is that a network on which bf16 is less accurate than on the lego scene
+// calibrates itself or fails loudly (NERF_ERR_STATE) instead of returning a silently different frame.
+// Every attempt writes the whole frame -- colour and the requested maps -- so the maps returned are those of the frame that stands.
+int nerfint::render_device(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *o, float *d_out, float *d_depth, float *d_opacity,
+                           hipStream_t st, nerf_stats *stats, const float *background) {
+    if (!o || !o->certify_zero) return render_once(c, cam, o, d_out, d_depth, d_opacity, st, stats, nullptr, background);
+    constexpr int kMaxRetries = 8;
+    uint64_t violations = 0;
+    for (int attempt = 0;; ++attempt) {
+        CertOutcome oc;
+        const int rc = render_once(c, cam, o, d_out, d_depth, d_opacity, st, stats, &oc, background);
+        if (rc) return rc;
+        bool again = false;
+        std::string why;
+        if (oc.list_need > oc.list_capacity) { // (entries beyond the capacity were counted, not stored)
+            c->cert_list_frac = std::min(1.0, 1.25 * (double)oc.list_need / (double)std::max<uint64_t>(oc.pass_samples, 1));
+            again = true;
+            why = "the sample list was too short";
+        }
+        for (int w = 0; w < 2; ++w)
+            if (oc.range_left[w]) { // the f16 pre-filter met an activation beyond 65 504: its pre-activations are void -- bf16 (f32's range) from now on
+                c->cert_prefilter_f16[w] = false;
+                c->cert_margin[w] = std::max(c->cert_margin[w], c->cert_margin_floor[w]);
+                again = true;
+                why = "an activation left the range of the f16 pre-filter";
+            }
+        const bool overflow = again; // an attempt whose list was too short evaluated only a part of it (or whose pre-filter left its range): its audit says nothing
+        if (!overflow) violations += oc.violations[0] + oc.violations[1];
+        for (int w = 0; w < 2 && !overflow; ++w) {
+            if (!oc.used[w] || !oc.audited[w]) continue;
+            // the rules live in host_util.cpp (certify_policy: tested on the CPU through nerf_debug_certify_policy)
+            float widened = c->cert_margin[w];
+            const int rule = certify_policy(c->cert_margin[w], oc.audited[w], oc.violations[w], oc.headroom[w], oc.max_err[w], &widened);
+            if (rule) {
+                c->cert_margin[w] = widened; again = true;
+                why = rule == 1 ? "an audited certificate was wrong" : rule == 2 ? "an audited certificate came closer to a positive density than half the margin"
+                                                                                 : "the 16-bit pass was off by more than half the margin on an audited certificate";
+            }
+        }
+        if (stats) { stats->n_certify_retries = (uint32_t)attempt; stats->n_certify_violations = violations; }
+        if (!again) return NERF_OK;
+        if (attempt == kMaxRetries) {
+            char msg[320];
+            snprintf(msg, sizeof msg, "certify_zero: %s after %d renders of this frame (margins now %g / %g): the 16-bit pass cannot certify this network's "
+                     "zero densities; render with certify_zero = 0", why.c_str(), attempt + 1, (double)c->cert_margin[0], (double)c->cert_margin[1]);
+            return fail(c, NERF_ERR_STATE, msg);
+        }
+    }
+}
+
+int nerfint::output_window(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *opts, size_t *w_out, size_t *h_out) {
+    int rc;
+    if ((rc = check_camera(c, cam))) return rc;
+    if (!opts) return fail(c, NERF_ERR_INVALID, "opts is NULL");
+    const bool crop = opts->crop_w > 0 || opts->crop_h > 0;
+    const long long w = crop ? opts->crop_w : cam->nx;
+    long long h = crop ? opts->crop_h : cam->ny;
+    if (w <= 0 || h <= 0) return fail(c, NERF_ERR_INVALID, "crop window outside the frame");
+    if (opts->band_count > 1) {
+        if (opts->band_index < 0 || opts->band_index >= opts->band_count || opts->band_stripe_rows < 0) return fail(c, NERF_ERR_INVALID, "band_index / band_count / band_stripe_rows out of range");
+        h = band_rows((int)h, opts->band_index, opts->band_count, opts->band_stripe_rows);
+        if (h <= 0) return fail(c, NERF_ERR_INVALID, "this band has no rows (more bands than rows)");
+    }
+    *w_out = (size_t)w; *h_out = (size_t)h;
+    return NERF_OK;
+}
+
+static size_t align4(size_t n) { return (n + 3) & ~(size_t)3; }
+
+// The f32 frame (and the opacity plane of the two alpha modes) live in the context's own workspace, grown on demand: a warm call
+// allocates nothing.  Conversion and quantisation run once per pixel, on the frame that stands (behind the box filter and behind
+// certify_zero's retry loop, both inside render_device).
+int nerfint::render_rgba8_device(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *o, const float *background, int alpha_mode,
+                                 uint8_t *d_rgba, hipStream_t st, nerf_stats *stats) {
+    int rc;
+    const float *bg = nullptr;
+    if ((rc = check_rgba8(c, background, alpha_mode, d_rgba, &bg))) return rc;
+    size_t w = 0, h = 0;
+    if ((rc = output_window(c, cam, o, &w, &h))) return rc;
+    const size_t px = w * h, op_at = align4(3 * px);
+    if ((rc = ensure_bytes(c, (void **)&c->d_pack, &c->pack_bytes, (op_at + px) * sizeof(float)))) return rc;
+    float *d_rgb = c->d_pack, *d_opacity = alpha_mode == NERF_ALPHA_OPAQUE ? nullptr : c->d_pack + op_at;
+    if ((rc = render_device(c, cam, o, d_rgb, nullptr, d_opacity, st, stats, bg))) return rc;
+    HIP_TRY(c, launch_pack_rgba8(d_rgb, d_opacity, (uint32_t *)d_rgba, px, alpha_mode, st));
+    if (stats) HIP_TRY(c, hipStreamSynchronize(st)); // as the float variant: with stats the output is complete on return
+    return NERF_OK;
+}
+
+extern "C" {
+
+int nerf_render_image_aux_device(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *opts, float *d_rgb_out,
+                                 float *d_depth_out, float *d_opacity_out, void *stream, nerf_stats *stats) try {
+    if (!c) return fail(nullptr, NERF_ERR_INVALID, "ctx is NULL");
+    DeviceGuard dg(c->device);
+    return render_device(c, cam, opts, d_rgb_out, d_depth_out, d_opacity_out, (hipStream_t)stream, stats);
+} NERF_CATCH(c)
+
+int nerf_render_image_device(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *opts, float *d_rgb_out,
+                             void *stream, nerf_stats *stats) {
+    return nerf_render_image_aux_device(c, cam, opts, d_rgb_out, nullptr, nullptr, stream, stats);
+}
+
+int nerf_render_image_aux(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *opts, float *rgb_out, float *depth_out,
+                          float *opacity_out, nerf_stats *stats) try {
+    if (!c) return fail(nullptr, NERF_ERR_INVALID, "ctx is NULL");
+    if (!rgb_out) return fail(c, NERF_ERR_INVALID, "output pointer is NULL");
+    int rc;
+    size_t w = 0, h = 0;
+    if ((rc = output_window(c, cam, opts, &w, &h))) return rc;
+    DeviceGuard dg(c->device);
+    // staging: the colour, then each requested map (w x h floats)
+    const size_t px = w * h, bytes = px * 3 * sizeof(float);
+    const size_t maps = (depth_out ? 1 : 0) + (opacity_out ? 1 : 0);
+    if ((rc = ensure_bytes(c, (void **)&c->d_out, &c->out_floats, bytes + maps * px * sizeof(float)))) return rc;
+    float *d_depth = depth_out ? c->d_out + 3 * px : nullptr;
+    float *d_opacity = opacity_out ? c->d_out + (3 + (depth_out ? 1 : 0)) * px : nullptr;
+    nerf_stats local; // a synchronous render always reads its counters: a frame computed outside a split arithmetic's range is an error
+    if ((rc = render_device(c, cam, opts, c->d_out, d_depth, d_opacity, c->stream, stats ? stats : &local))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(rgb_out, c->d_out, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (d_depth) HIP_TRY(c, hipMemcpyAsync(depth_out, d_depth, px * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (d_opacity) HIP_TRY(c, hipMemcpyAsync(opacity_out, d_opacity, px * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return NERF_OK;
+} NERF_CATCH(c)
+
+int nerf_render_image(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *opts, float *rgb_out, nerf_stats *stats) {
+    return nerf_render_image_aux(c, cam, opts, rgb_out, nullptr, nullptr, stats);
+}
+
+int nerf_render_image_rgba8_device(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *opts, const float background[3], int alpha_mode,
+                                   uint8_t *d_rgba_out, void *stream, nerf_stats *stats) try {
+    if (!c) return fail(nullptr, NERF_ERR_INVALID, "ctx is NULL");
+    DeviceGuard dg(c->device);
+    return render_rgba8_device(c, cam, opts, background, alpha_mode, d_rgba_out, (hipStream_t)stream, stats);
+} NERF_CATCH(c)
+
+int nerf_render_image_rgba8(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *opts, const float background[3], int alpha_mode,
+                            uint8_t *rgba_out, nerf_stats *stats) try {
+    if (!c) return fail(nullptr, NERF_ERR_INVALID, "ctx is NULL");
+    int rc;
+    const float *bg = nullptr;
+    if ((rc = check_rgba8(c, background, alpha_mode, rgba_out, &bg))) return rc;
+    size_t w = 0, h = 0;
+    if ((rc = output_window(c, cam, opts, &w, &h))) return rc;
+    DeviceGuard dg(c->device);
+    const size_t bytes = w * h * 4; // 4 bytes per pixel come back instead of 12 (16 with the opacity)
+    if ((rc = ensure_bytes(c, (void **)&c->d_out, &c->out_floats, bytes))) return rc;
+    nerf_stats local; // a synchronous render always reads its counters (see nerf_render_image_aux)
+    if ((rc = render_rgba8_device(c, cam, opts, background, alpha_mode, (uint8_t *)c->d_out, c->stream, stats ? stats : &local))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(rgba_out, c->d_out, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return NERF_OK;
+} NERF_CATCH(c)
+
+// ---- ray batches ---------------------------------------------------------------------------------------------------------------------
+// nerf_render_rays_device and nerf_render_rays_normals_device (want_normals)
+static int rays_device(nerf_ctx *c, const float *d_origins, size_t n_origins, const float *d_dirs, size_t n_rays, int normalize, float near_,
+                       float far_, const float *d_bounds, const uint32_t *d_rng_index, const nerf_render_opts *opts, const float background[3],
+                       float *d_rgb_out, float *d_depth_out, float *d_opacity_out, bool want_normals, float h, float *d_normals_out, void *stream,
+                       nerf_stats *stats) {
+    int rc;
+    if ((rc = check_ray_batch(c, d_origins, n_origins, d_dirs, n_rays, near_, far_, d_bounds, opts, background, d_rgb_out))) return rc;
+    if (want_normals && (rc = check_normals(c, h, d_normals_out))) return rc;
+    if (!c) return fail(nullptr, NERF_ERR_INVALID, "ctx is NULL");
+    if (n_rays == 0) return NERF_OK;
+    DeviceGuard dg(c->device);
+    const hipStream_t st = (hipStream_t)stream;
+    RayBatch b{nullptr, nullptr, d_dirs, n_rays, normalize ? 1 : 0, near_, far_, d_bounds, d_rng_index};
+    float origin[3];
+    if (n_origins == 1) { // the shared origin rides in the MLP kernels' arguments: 12 bytes come back first
+        HIP_TRY(c, hipMemcpyAsync(origin, d_origins, sizeof origin, hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipStreamSynchronize(st));
+        b.h_origin = origin;
+    } else b.d_origins = d_origins;
+    return render_rays_device(c, b, opts, background, d_rgb_out, d_depth_out, d_opacity_out, st, stats, h, want_normals ? d_normals_out : nullptr);
+}
+
+int nerf_render_rays_device(nerf_ctx *c, const float *d_origins, size_t n_origins, const float *d_dirs, size_t n_rays, int normalize, float near_,
+                            float far_, const float *d_bounds, const uint32_t *d_rng_index, const nerf_render_opts *opts, const float background[3],
+                            float *d_rgb_out, float *d_depth_out, float *d_opacity_out, void *stream, nerf_stats *stats) try {
+    return rays_device(c, d_origins, n_origins, d_dirs, n_rays, normalize, near_, far_, d_bounds, d_rng_index, opts, background, d_rgb_out, d_depth_out,
+                       d_opacity_out, false, 0.0f, nullptr, stream, stats);
+} NERF_CATCH(c)
+
+int nerf_render_rays_normals_device(nerf_ctx *c, const float *d_origins, size_t n_origins, const float *d_dirs, size_t n_rays, int normalize,
+                                    float near_, float far_, const float *d_bounds, const uint32_t *d_rng_index, const nerf_render_opts *opts,
+                                    const float background[3], float *d_rgb_out, float *d_depth_out, float *d_opacity_out, float h,
+                                    float *d_normals_out, void *stream, nerf_stats *stats) try {
+    return rays_device(c, d_origins, n_origins, d_dirs, n_rays, normalize, near_, far_, d_bounds, d_rng_index, opts, background, d_rgb_out, d_depth_out,
+                       d_opacity_out, true, h, d_normals_out, stream, stats);
+} NERF_CATCH(c)
+
+// nerf_render_rays and nerf_render_rays_normals (want_normals)
+static int rays_host(nerf_ctx *c, const float *origins, size_t n_origins, const float *dirs, size_t n_rays, int normalize, float near_, float far_,
+                     const float *bounds, const uint32_t *rng_index, const nerf_render_opts *opts, const float background[3], float *rgb_out,
+                     float *depth_out, float *opacity_out, bool want_normals, float h, float *normals_out, nerf_stats *stats) {
+    int rc;
+    if ((rc = check_ray_batch(c, origins, n_origins, dirs, n_rays, near_, far_, bounds, opts, background, rgb_out))) return rc;
+    if (want_normals && (rc = check_normals(c, h, normals_out))) return rc;
+    if ((rc = check_ray_batch_rays(c, origins, n_origins, dirs, n_rays, normalize, bounds))) return rc;
+    if (!c) return fail(nullptr, NERF_ERR_INVALID, "ctx is NULL");
+    if (n_rays == 0) return NERF_OK;
+    DeviceGuard dg(c->device);
+    // staging (floats): dirs, [origins], [bounds], [rng_index], rgb, [depth], [opacity], [normals]
+    const size_t R = n_rays, o_d = 0, o_o = o_d + 3 * R, o_b = o_o + (n_origins == 1 ? 0 : 3 * R), o_i = o_b + (bounds ? 2 * R : 0),
+                 o_c = o_i + (rng_index ? R : 0), o_z = o_c + 3 * R, o_a = o_z + (depth_out ? R : 0), o_n = o_a + (opacity_out ? R : 0),
+                 total = o_n + (want_normals ? 3 * R : 0);
+    if ((rc = ensure_bytes(c, (void **)&c->d_out, &c->out_floats, total * sizeof(float)))) return rc;
+    float *d = c->d_out;
+    HIP_TRY(c, hipMemcpyAsync(d + o_d, dirs, 3 * R * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (n_origins != 1) HIP_TRY(c, hipMemcpyAsync(d + o_o, origins, 3 * R * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (bounds) HIP_TRY(c, hipMemcpyAsync(d + o_b, bounds, 2 * R * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (rng_index) HIP_TRY(c, hipMemcpyAsync(d + o_i, rng_index, R * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    RayBatch b{n_origins == 1 ? origins : nullptr, n_origins == 1 ? nullptr : d + o_o, d + o_d, n_rays, normalize ? 1 : 0, near_, far_,
+               bounds ? d + o_b : nullptr, rng_index ? (const uint32_t *)(d + o_i) : nullptr};
+    nerf_stats local; // a synchronous render always reads its counters (see nerf_render_image_aux)
+    if ((rc = render_rays_device(c, b, opts, background, d + o_c, depth_out ? d + o_z : nullptr, opacity_out ? d + o_a : nullptr, c->stream,
+                                 stats ? stats : &local, h, want_normals ? d + o_n : nullptr))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(rgb_out, d + o_c, 3 * R * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (want_normals) HIP_TRY(c, hipMemcpyAsync(normals_out, d + o_n, 3 * R * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (depth_out) HIP_TRY(c, hipMemcpyAsync(depth_out, d + o_z, R * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (opacity_out) HIP_TRY(c, hipMemcpyAsync(opacity_out, d + o_a, R * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return NERF_OK;
+}
+
+int nerf_render_rays(nerf_ctx *c, const float *origins, size_t n_origins, const float *dirs, size_t n_rays, int normalize, float near_, float far_,
+                     const float *bounds, const uint32_t *rng_index, const nerf_render_opts *opts, const float background[3], float *rgb_out,
+                     float *depth_out, float *opacity_out, nerf_stats *stats) try {
+    return rays_host(c, origins, n_origins, dirs, n_rays, normalize, near_, far_, bounds, rng_index, opts, background, rgb_out, depth_out, opacity_out,
+                     false, 0.0f, nullptr, stats);
+} NERF_CATCH(c)
+
+int nerf_render_rays_normals(nerf_ctx *c, const float *origins, size_t n_origins, const float *dirs, size_t n_rays, int normalize, float near_,
+                             float far_, const float *bounds, const uint32_t *rng_index, const nerf_render_opts *opts, const float background[3],
+                             float *rgb_out, float *depth_out, float *opacity_out, float h, float *normals_out, nerf_stats *stats) try {
+    return rays_host(c, origins, n_origins, dirs, n_rays, normalize, near_, far_, bounds, rng_index, opts, background, rgb_out, depth_out, opacity_out,
+                     true, h, normals_out, stats);
+} NERF_CATCH(c)
+
+} // extern "C"

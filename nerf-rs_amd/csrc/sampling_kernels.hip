@@ -451,7 +451,7 @@ hipError_t launch_pack_rgba8(const float *rgb, const float *opacity, uint32_t *o
 //   * the buffer is zeroed otherwise: it becomes the exact pass's density buffer, whose listed entries the exact kernel overwrites.
 // List order is arbitrary (one atomic per workgroup and list part, entries staged in LDS); results do not depend on it.  The list has a
 // CAPACITY: entries beyond it are counted, not stored -- the host sees count > capacity after the frame, grows the list and renders the
-// frame again (nerf_api.cpp).
+// frame again (nerf_render.cpp render_device).
 constexpr float kCertMarker = -1.0f;
 constexpr int kCertPlanMaxLds = 159 * 1024; // dynamic LDS of k_cert_plan (its reservation counters are static LDS on top)
 constexpr int kPlanRays = 8; // rays per wave between two flushes of its LDS staging area

@@ -2,7 +2,7 @@
 
 render_image composes ray directions, stratified samples, the coarse network, resampling, the fine network and compositing inside
 one call; restate() makes the same image from the calls a host can make itself, one stage at a time, and hands back every per-ray
-intermediate.  The steps (reference: render_block, src/lib.rs:353-472; oracle/nerf_oracle.c render_rays; nerf_api.cpp render_once):
+intermediate.  The steps (reference: render_block, src/lib.rs:353-472; oracle/nerf_oracle.c render_rays; nerf_render.cpp render_passes):
 
   1. unit ray directions of the window's rays;
   2. stratified t, RNG pixel_index = (y0 + i) * W + x0 + j in the ray grid;
@@ -10,15 +10,15 @@ intermediate.  The steps (reference: render_block, src/lib.rs:353-472; oracle/ne
      forms ray-mode points with __fadd_rn(__fmul_rn(...)) for the same reason);
   4. the coarse network's densities at those points, the ray's direction repeated per sample;
   5. resample + merge + sort (skipped -- the fine network then runs on the coarse samples -- when n_fine == 0 or n_coarse < 3:
-     sample_importance returns nothing, src/lib.rs:295-297; nerf_api.cpp "const int nf = ...");
+     sample_importance returns nothing, src/lib.rs:295-297; nerf_render.cpp fine_samples);
   6. the fine network at the merged points;
   7. integrate_ray.
-coarse_only composites the coarse network's colours after step 4 (oracle/nerf_oracle.c "if (R->coarse_only)"; nerf_api.cpp
-"if (o->coarse_only)").  ssaa = S renders the window (S x0, S y0, S w, S h) of the camera with S times the pixels per side and
+coarse_only composites the coarse network's colours after step 4 (oracle/nerf_oracle.c "if (R->coarse_only)"; nerf_render.cpp
+render_passes "if (j.coarse_only)").  ssaa = S renders the window (S x0, S y0, S w, S h) of the camera with S times the pixels per side and
 reduces every S x S block of sub-rays by a row-major f32 sum followed by ONE multiply by 1 / S^2 (oracle_render_image "acc * inv";
 k_box_downsample).
 
-Which arithmetic runs which pass (nerf_api.cpp, dtype_coarse): f32 and bf16 renders run both networks in their own arithmetic;
+Which arithmetic runs which pass (nerf_render.cpp plan_job, dtype_coarse): f32 and bf16 renders run both networks in their own arithmetic;
 bf16x3 and f16x2 renders take their sample positions from the exact-f32 coarse pass and run only the colour-producing pass in the
 split arithmetic (so a coarse_only render runs the coarse network in the split arithmetic).
 
@@ -30,7 +30,7 @@ import numpy as np
 
 
 def pass_dtypes(dtype, coarse_only):
-    """(arithmetic of the coarse pass, arithmetic of the fine pass) of a render in `dtype` (nerf_api.cpp dtype_coarse)."""
+    """(arithmetic of the coarse pass, arithmetic of the fine pass) of a render in `dtype` (nerf_render.cpp plan_job, dtype_coarse)."""
     split = dtype in ("bf16x3", "f16x2")
     return ("f32" if split and not coarse_only else dtype), dtype
 

@@ -293,7 +293,7 @@ def test_ppm_of_full_frame(frame800, native, oracle, tmp_path):
 
 # ---- scheduler: passes, CLI ------------------------------------------------------------------------------------------
 def test_multi_pass_render_is_bit_identical(renderer, native, samples, monkeypatch):
-    """The pass scheduler (nerf_api.cpp) cuts the frame into row passes that fit NERF_MAX_RAYS_PER_PASS; with per-pixel
+    """The pass pipeline (nerf_render.cpp) cuts the frame into row passes that fit NERF_MAX_RAYS_PER_PASS; with per-pixel
     RNG and no cross-ray state the image must not depend on the pass size (incl. passes of one ragged row)."""
     cam = native.camera_from_samples(samples, 800, 800, 64)
     crop = (300, 380, 211, 37)

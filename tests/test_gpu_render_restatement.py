@@ -37,7 +37,7 @@ import render_restatement as RR  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 DTYPES = ("f32", "bf16x3", "f16x2", "bf16")
-# what the API allows next to each arithmetic (nerf_api.cpp render_once: certify_zero needs F32, BF16X3 or F16X2)
+# what the API allows next to each arithmetic (nerf_render.cpp check_image_modes: certify_zero needs F32, BF16X3 or F16X2)
 MODES = {"f32": ("skip_empty", "skip_dead", "certify_zero"), "bf16x3": ("skip_empty", "skip_dead", "certify_zero"),
          "f16x2": ("skip_empty", "skip_dead", "certify_zero"), "bf16": ("skip_empty", "skip_dead")}
 # (n_coarse, n_fine, coarse_only): samples per ray 8, 2, 70, 33, 192, 300, 64, 20 -- rays that end inside a 32-sample wave tile and
