@@ -60,24 +60,19 @@ __device__ __forceinline__ void unite(uint32_t *label, uint32_t a, uint32_t b) {
     }
 }
 
-// NERF_CC_PREMERGE (default 1; 0 only in A/B builds): an inside point starts under the first point of its run of consecutive inside points along x
+// Pre-merge: an inside point starts under the first point of its run of consecutive inside points along x
 // within its wave and row (one ballot) instead of under itself.  That is a valid starting forest -- the parent is a smaller index of the same
 // component -- so the result is the same; the union pass then starts from runs instead of points and its chains are shorter.
-#ifndef NERF_CC_PREMERGE
-#define NERF_CC_PREMERGE 1
-#endif
 
 __global__ __launch_bounds__(kB) void k_cc_init(const float *__restrict__ sigma, float iso, uint32_t nx, uint32_t n, uint32_t *__restrict__ label,
                                                 uint32_t *__restrict__ size) {
     const uint32_t A = blockIdx.x * (uint32_t)kB + threadIdx.x;
     const bool in = A < n && sigma[A] > iso; // a NaN is not inside; no early return: every lane takes part in the ballots
     uint32_t l = in ? A : kCompNone;
-#if NERF_CC_PREMERGE
     const int lane = threadIdx.x & 63; // a workgroup starts at a multiple of 256: A - lane is the wave's first point
     const unsigned long long m = __ballot(in);
     const unsigned long long starts = __ballot(in && (lane == 0 || A % nx == 0u || !((m >> (lane - 1)) & 1ull))); // first of the wave, of a row, or after a gap
     if (in) l = A - (uint32_t)(lane - (63 - __clzll((long long)(starts & (~0ull >> (63 - lane)))))); // the nearest start at or below this lane: it exists
-#endif
     if (A < n) { label[A] = l; size[A] = 0u; }
 }
 

@@ -39,7 +39,7 @@ bool fold_network(const std::vector<float> &wstream, const std::vector<float> &s
 // true iff every value of an f32 device image (stream + small block) is finite: the condition under which the f32 kernels may skip
 // k-steps whose ReLU inputs are all zero (fma(a, 0, c) = c needs a finite a; a NaN bias must take the dense path's quieting too)
 bool zero_skip_safe(const std::vector<float> &wstream, const std::vector<float> &small);
-// bf16 weight stream of mlp_kernel_bf16.hip (round-to-nearest-even); the small-parameter block is shared with fp32.
+// bf16 weight stream in the v1 piece order (round-to-nearest-even; the host's intermediate order that every 16-bit stream is re-packed from); the small-parameter block is shared with fp32.
 void pack_network_bf16(const HostNet &net, std::vector<uint16_t> &wstream);
 uint16_t f32_to_bf16_rne(float v);
 // the first bf16 design's piece order as f32 values, no padding (mlp_layout.h kPiecesV1 x 512): common source of all bf16 streams

@@ -1,4 +1,5 @@
-// mlp_common.hip.h -- device helpers shared by the f32 (mlp_kernel.hip) and bf16 (mlp_kernel_bf16.hip) MLP kernels.
+// mlp_common.hip.h -- device helpers shared by the f32 (mlp_kernel.hip, mlp_kernel_seq.hip) and the 16-bit (mlp_kernel_bf16v2.hip,
+// mlp_kernel_bf16x3.hip, mlp_kernel_f16x2.hip) MLP kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -32,9 +33,6 @@ __device__ __forceinline__ void glds_piece(uint32_t lane16, const char *gsrc, ui
 // four pieces addressed by the instruction offset, which advances the global AND the LDS address.  Beside MFMAs a piece costs its wave 25
 // cycles with M0 saved / written / restored around it, 17 with M0 written, 0 with M0 left alone (tools/probes/lds_dma_stagger_probe.hip).
 // hipcc uses M0 for nothing of its own in these kernels (no LDS-direct, no s_movrel, no sendmsg): tests/test_host_logic.py checks the ISA.
-#ifndef NERF_M0_PER_CHUNK
-#define NERF_M0_PER_CHUNK 1
-#endif
 __device__ __forceinline__ void dma_set_dst(uint32_t dst) { asm volatile("s_mov_b32 m0, %0\n\ts_nop 0" ::"s"(dst) : "memory"); }
 __device__ __forceinline__ void glds_piece_m0(uint32_t lane16, const char *gsrc, int i) {
     switch (i) { // i is a constant after unrolling
@@ -78,23 +76,16 @@ __device__ __forceinline__ void fast_sincos(float x, float *s_out, float *c_out)
     *c_out = __builtin_bit_cast(float, cb);
 }
 
-template <bool FAST>
-__device__ __forceinline__ void sincos_sel(float x, float *s, float *c) {
-    if constexpr (FAST) fast_sincos(x, s, c);
-    else sincosf(x, s, c);
-}
-
 // Positional encoding of a point: this lane-half's 32 slots (mlp_layout.h posSlotFeature; src/network.rs:263-292):
 // octaves 5h..5h+4 as idx 6*o + {sin xyz, cos xyz}, idx 30/31 = raw x,y (h = 0) or raw z, zero pad (h = 1).
-template <bool FAST>
 __device__ __forceinline__ void encode_point(float px, float py, float pz, int h, f32x16 (&E)[2]) {
     float f = h ? 32.0f : 1.0f;
 #pragma unroll
     for (int o = 0; o < 5; ++o) {
         float s, c;
-        sincos_sel<FAST>(f * px, &s, &c); E[(6 * o + 0) >> 4][(6 * o + 0) & 15] = s; E[(6 * o + 3) >> 4][(6 * o + 3) & 15] = c;
-        sincos_sel<FAST>(f * py, &s, &c); E[(6 * o + 1) >> 4][(6 * o + 1) & 15] = s; E[(6 * o + 4) >> 4][(6 * o + 4) & 15] = c;
-        sincos_sel<FAST>(f * pz, &s, &c); E[(6 * o + 2) >> 4][(6 * o + 2) & 15] = s; E[(6 * o + 5) >> 4][(6 * o + 5) & 15] = c;
+        fast_sincos(f * px, &s, &c); E[(6 * o + 0) >> 4][(6 * o + 0) & 15] = s; E[(6 * o + 3) >> 4][(6 * o + 3) & 15] = c;
+        fast_sincos(f * py, &s, &c); E[(6 * o + 1) >> 4][(6 * o + 1) & 15] = s; E[(6 * o + 4) >> 4][(6 * o + 4) & 15] = c;
+        fast_sincos(f * pz, &s, &c); E[(6 * o + 2) >> 4][(6 * o + 2) & 15] = s; E[(6 * o + 5) >> 4][(6 * o + 5) & 15] = c;
         f *= 2.0f;
     }
     E[1][14] = h ? pz : px;
@@ -103,15 +94,14 @@ __device__ __forceinline__ void encode_point(float px, float py, float pz, int h
 
 // Direction encoding: 16 slots per lane-half (mlp_layout.h dirSlotFeature; src/network.rs:294-330): octaves 2h, 2h+1,
 // raw x,y,z on h = 0, zero pads.
-template <bool FAST>
 __device__ __forceinline__ void encode_dir(float dx, float dy, float dz, int h, f32x16 &D) {
     float f = h ? 4.0f : 1.0f;
 #pragma unroll
     for (int o = 0; o < 2; ++o) {
         float s, c;
-        sincos_sel<FAST>(f * dx, &s, &c); D[6 * o + 0] = s; D[6 * o + 3] = c;
-        sincos_sel<FAST>(f * dy, &s, &c); D[6 * o + 1] = s; D[6 * o + 4] = c;
-        sincos_sel<FAST>(f * dz, &s, &c); D[6 * o + 2] = s; D[6 * o + 5] = c;
+        fast_sincos(f * dx, &s, &c); D[6 * o + 0] = s; D[6 * o + 3] = c;
+        fast_sincos(f * dy, &s, &c); D[6 * o + 1] = s; D[6 * o + 4] = c;
+        fast_sincos(f * dz, &s, &c); D[6 * o + 2] = s; D[6 * o + 5] = c;
         f *= 2.0f;
     }
     D[12] = h ? 0.f : dx; D[13] = h ? 0.f : dy; D[14] = h ? 0.f : dz; D[15] = 0.f;

@@ -9,13 +9,6 @@
 #include "mlp_common.hip.h"
 #include "mlp_layout.h"
 
-// Tuning switches (A/B-tested on MI355X).
-#ifndef NERF_DMA_SPREAD
-#define NERF_DMA_SPREAD 1 // 1: one LDS-DMA piece per macro-step behind an MFMA; 0: four pieces in a burst at the sync
-#endif
-#ifndef NERF_FAST_SINCOS
-#define NERF_FAST_SINCOS 1 // 1: branch-free Cody-Waite + minimax sincos (<= 1.6 ulp for |x| <= 2^11); 0: ocml sincosf
-#endif
 // Timing-only diagnostics (results are WRONG with any of these set; never shipped):
 #ifndef NERF_DIAG_NO_BARRIER
 #define NERF_DIAG_NO_BARRIER 0
@@ -26,29 +19,16 @@
 #ifndef NERF_DIAG_NO_LDS
 #define NERF_DIAG_NO_LDS 0
 #endif
-#define NERF_STR2(x) #x
-#define NERF_STR(x) NERF_STR2(x)
-// chunks allowed to stay in flight across the mid-chunk sync: kRingSlots - 3 (4 pieces each)
-#define NERF_SYNC_VMCNT ((NERF_RING_SLOTS - 3) * 4)
-#ifndef NERF_RELU_GROUP
-#define NERF_RELU_GROUP 16 // (1: 92.1 %, 2: 93.4 %, 4: 94.1 %, 8: 94.3 %, 16: 94.4 % of the fp32 MFMA roofline) B operands (AGPR read + ReLU) are prepared for this many k-steps in ONE contiguous VALU burst
-#endif
-#ifndef NERF_LDS_GROUP
-#define NERF_LDS_GROUP 1 // A operands are fetched from LDS for this many macro-steps per burst (1, 2 or 4)
-#endif
-#ifndef NERF_PIN_CHAINS
-#define NERF_PIN_CHAINS 0 // 1: zero-instruction asm touching all accumulators after every input tile (keeps MFMA chains in program order)
-#endif
-#ifndef NERF_PREFETCH_INPUTS
-#define NERF_PREFETCH_INPUTS 1 // 1: the next tile's t / direction are loaded one tile ahead
-#endif
-
-
 
 namespace mlpf32 {
 
 using namespace nerfmlp;
 using namespace mlpdev;
+
+// Tuning constants (A/B-tested on MI355X).
+// (1: 92.1 %, 2: 93.4 %, 4: 94.1 %, 8: 94.3 %, 16: 94.4 % of the fp32 MFMA roofline) B operands (AGPR read + ReLU) are prepared for this many k-steps in ONE contiguous VALU burst
+constexpr int kReluGroup = 16;
+constexpr int kLdsGroup = 1; // A operands are fetched from LDS for this many macro-steps per burst (1, 2 or 4)
 
 // ---- weight-stream pipeline -------------------------------------------------------------------
 // The stream is consumed in "macro-steps" of 2 KiB = the A operands of 8 MFMAs (one k-step of an
@@ -57,8 +37,8 @@ struct Pipe {
     const LDS_AS char *rd_base; // LDS address (incl. lane*16) of the chunk the NEXT macro-step to fetch lives in
     const LDS_AS char *ring_lane; // ring base + lane*16
     uint32_t rd_slot_off;       // wave-uniform byte offset of that chunk's slot
-    f32x4 nx[2 * NERF_LDS_GROUP]; // prefetched A operands of the next group of macro-steps
-    f32x4 cu[2 * NERF_LDS_GROUP]; // A operands of the current group
+    f32x4 nx[2 * kLdsGroup]; // prefetched A operands of the next group of macro-steps
+    f32x4 cu[2 * kLdsGroup]; // A operands of the current group
     uint32_t ring_addr;      // LDS byte address of the ring + wave*4 KiB (DMA destination base)
     uint32_t wr_slot_off;    // byte offset of the slot the next DMA chunk goes to
     uint32_t next_off;       // byte offset in the stream of the next chunk to DMA
@@ -101,16 +81,12 @@ __device__ __forceinline__ void pipe_next_chunk(Pipe &P) {
     P.next_off = (off == P.stream_bytes) ? 0u : off;
     slot += kChunkBytes;
     P.wr_slot_off = (slot == kRingSlots * kChunkBytes) ? 0u : slot;
-#if NERF_M0_PER_CHUNK
     dma_set_dst(P.cur_dst);
-#endif
 }
 
 __device__ __forceinline__ void pipe_issue_piece(Pipe &P, int i) {
-#if !NERF_DIAG_NO_DMA && NERF_M0_PER_CHUNK
+#if !NERF_DIAG_NO_DMA
     glds_piece_m0(P.lane16, P.cur_src, i);
-#elif !NERF_DIAG_NO_DMA
-    glds_piece(P.lane16, P.cur_src + i * 1024, P.cur_dst + i * 1024);
 #else
     (void)P; (void)i;
 #endif
@@ -123,31 +99,34 @@ __device__ __forceinline__ void pipe_issue(Pipe &P) {
 }
 
 // Middle of chunk c: chunk c+1 (issued one chunk ago) must have landed; every wave is past chunk c-1, so
-// its slot can be refilled with chunk c+2 (macro-steps 4..7 of chunk c issue one piece each, or all four here).
+// its slot can be refilled with chunk c+2 (macro-steps 4..7 of chunk c issue one piece each).
+// vmcnt: the chunks allowed to stay in flight across the sync, kRingSlots - 3 of 4 pieces each.
 __device__ __forceinline__ void pipe_sync(Pipe &P) {
 #if NERF_DIAG_NO_BARRIER
-    asm volatile("s_waitcnt vmcnt(" NERF_STR(NERF_SYNC_VMCNT) ")" ::: "memory");
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * (kRingSlots - 3)) : "memory");
 #else
-    asm volatile("s_waitcnt vmcnt(" NERF_STR(NERF_SYNC_VMCNT) ")\n\ts_barrier" ::: "memory");
+    asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(4 * (kRingSlots - 3)) : "memory");
 #endif
-#if NERF_DMA_SPREAD
     pipe_next_chunk(P);
-#else
-    pipe_issue(P);
-#endif
 }
 
-// Called between the MFMAs of macro-step `ms` (0..7 within its chunk).
+// Called between the MFMAs of macro-step `ms` (0..7 within its chunk): one LDS-DMA piece per macro-step behind an MFMA
+// (four pieces in a burst at the sync measured slower).
 __device__ __forceinline__ void pipe_mid_step(Pipe &P, int ms) {
-#if NERF_DMA_SPREAD
     if (ms >= 4) {
         __builtin_amdgcn_sched_barrier(0);
         pipe_issue_piece(P, ms - 4);
         __builtin_amdgcn_sched_barrier(0);
     }
-#else
-    (void)P; (void)ms;
-#endif
+}
+
+// Prime: fetch the operands of the first group of macro-steps of the chunk at rd_base.
+__device__ __forceinline__ void pipe_prime(Pipe &P) {
+#pragma unroll
+    for (int j = 0; j < kLdsGroup; ++j) {
+        P.nx[2 * j] = *(const LDS_AS f32x4 *)(P.rd_base + j * 2048);
+        P.nx[2 * j + 1] = *(const LDS_AS f32x4 *)(P.rd_base + j * 2048 + 1024);
+    }
 }
 
 // Abandon the rest of the current tile's weight stream and start over at chunk 0 (empty-tile skipping).  Every wave
@@ -162,18 +141,14 @@ __device__ __forceinline__ void pipe_restart(Pipe &P) {
     asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
     P.rd_slot_off = 0;
     P.rd_base = P.ring_lane;
-#pragma unroll
-    for (int j = 0; j < NERF_LDS_GROUP; ++j) {
-        P.nx[2 * j] = *(const LDS_AS f32x4 *)(P.rd_base + j * 2048);
-        P.nx[2 * j + 1] = *(const LDS_AS f32x4 *)(P.rd_base + j * 2048 + 1024);
-    }
+    pipe_prime(P);
 }
 
 // Take the prefetched operands of macro-step `ms` (0..7 within its chunk) and start fetching those of the next one.
 // All in-chunk addressing is a per-chunk base + immediate offset: VALU instructions are NOT free next to fp32 MFMAs
 // (they share the vector datapath), so the ring arithmetic is one v_add per chunk plus scalar ops.
 __device__ __forceinline__ void pipe_advance(Pipe &P, int ms, f32x4 &a0, f32x4 &a1) {
-    constexpr int LG = NERF_LDS_GROUP;
+    constexpr int LG = kLdsGroup;
     if (ms % LG == 0) {
 #pragma unroll
         for (int j = 0; j < 2 * LG; ++j) P.cu[j] = P.nx[j];
@@ -236,7 +211,7 @@ __device__ __forceinline__ void tile_steps(const f32x16 &in, f32x16 (&out)[NT], 
     static_assert(NT == 8 || NT == 4, "NT");
     // Every interruption of the fp32 MFMA stream by VALU work costs more than the VALU instructions themselves, so
     // the B operands of G consecutive k-steps are prepared in one burst (G more live VGPRs).
-    constexpr int G = RELU ? NERF_RELU_GROUP : 1;
+    constexpr int G = RELU ? kReluGroup : 1;
     float bq[G];
     if constexpr (RELU) P.zs_total += 16;
     if constexpr (NT == 8) {
@@ -307,12 +282,6 @@ __device__ __forceinline__ void tile_steps(const f32x16 &in, f32x16 (&out)[NT], 
             }
         }
     }
-#if NERF_PIN_CHAINS
-    if constexpr (NT == 8)
-        asm volatile("" : "+a"(out[0]), "+a"(out[1]), "+a"(out[2]), "+a"(out[3]), "+a"(out[4]), "+a"(out[5]), "+a"(out[6]), "+a"(out[7]));
-    else
-        asm volatile("" : "+a"(out[0]), "+a"(out[1]), "+a"(out[2]), "+a"(out[3]));
-#endif
 }
 
 template <int NT>

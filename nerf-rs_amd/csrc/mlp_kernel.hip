@@ -70,7 +70,7 @@ __global__ __launch_bounds__(256, 1) void nerf_mlp_kernel(const MlpArgs A) {
     P.rd_slot_off = 0;
     P.rd_base = P.ring_lane;
 #pragma unroll
-    for (int j = 0; j < NERF_LDS_GROUP; ++j) { // prime: operands of the first group of macro-steps
+    for (int j = 0; j < kLdsGroup; ++j) { // prime: operands of the first group of macro-steps (pipe_prime, written out: calling it here moves the scalar compares around the tile loop)
         P.nx[2 * j] = *(const LDS_AS f32x4 *)(P.rd_base + j * 2048);
         P.nx[2 * j + 1] = *(const LDS_AS f32x4 *)(P.rd_base + j * 2048 + 1024);
     }
@@ -85,19 +85,13 @@ __global__ __launch_bounds__(256, 1) void nerf_mlp_kernel(const MlpArgs A) {
         return MODE == MLP_MODE_RAYS ? ray_group_first_slot(T, wave, A.group_segments, A.group_tiles) : T * kPointsPerBlock + wave * kPointsPerWave;
     };
     int slot0_next = first_slot(blockIdx.x); // wave-uniform, formed once per tile: for the look-ahead, then carried over
-#if NERF_PREFETCH_INPUTS
-    RawIn nxt = load_raw_at<LOAD>(A, slot0_next + p);
-#endif
+    RawIn nxt = load_raw_at<LOAD>(A, slot0_next + p); // the next tile's t / direction are loaded one tile ahead
     for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const int slot = slot0_next + p;
         const bool valid = slot < n_points;
         slot0_next = first_slot(tile + gridDim.x);
-#if NERF_PREFETCH_INPUTS
         const RawIn in = nxt;
         nxt = load_raw_at<LOAD>(A, slot0_next + p); // consumed one tile (~250 us) later
-#else
-        const RawIn in = load_raw_at<LOAD>(A, slot);
-#endif
         float px, py, pz;
         point_of<MODE>(A, in, px, py, pz);
         const float dx = in.dx, dy = in.dy, dz = in.dz;
@@ -107,7 +101,7 @@ __global__ __launch_bounds__(256, 1) void nerf_mlp_kernel(const MlpArgs A) {
         const bool audit = MODE == MLP_MODE_LIST && (entry >> 31) != 0;
 
         f32x16 E[2];
-        encode_point<NERF_FAST_SINCOS != 0>(px, py, pz, h, E);
+        encode_point(px, py, pz, h, E);
 
         f32x16 X[8], Y[8];
 
@@ -159,7 +153,7 @@ __global__ __launch_bounds__(256, 1) void nerf_mlp_kernel(const MlpArgs A) {
         }
         if (FULL) {
             f32x16 D;
-            encode_dir<NERF_FAST_SINCOS != 0>(dx, dy, dz, h, D);
+            encode_dir(dx, dy, dz, h, D);
             // viewdirs': [relu(h7) ; dir encoding] -> 128 = bottleneck (no activation, :218) folded into viewdirs (:219-222);
             // W' and b' come from the host (mlp_layout.h kChunksFullFolded)
             f32x16 V[4];

@@ -48,48 +48,6 @@ typedef __bf16 h16x2 __attribute__((ext_vector_type(2)));
 typedef short s16x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-#ifndef NERF_BV2_SCHED_BARRIER
-#define NERF_BV2_SCHED_BARRIER 1 // keep the written interleave (A-operand prefetch distance, epilogue pairs between MFMA pairs)
-#endif
-#ifndef NERF_BV2_PREFETCH_INPUTS
-#define NERF_BV2_PREFETCH_INPUTS 1 // load the next tile's raw inputs one tile ahead
-#endif
-#ifndef NERF_BV2_DMA_INST_OFFSET
-#define NERF_BV2_DMA_INST_OFFSET 1 // one scalar base + M0 per chunk quarter, pieces addressed by the instruction offset
-#endif
-#ifndef NERF_BV2_DOUBLING
-#define NERF_BV2_DOUBLING 1 // encodings by angle doubling from each lane-half's base octave (mlp_common.hip.h)
-#endif
-#if NERF_BV2_DOUBLING
-#define ENCODE_POINT encode_point_doubling
-#define ENCODE_DIR encode_dir_doubling
-#else
-#define ENCODE_POINT encode_point<true>
-#define ENCODE_DIR encode_dir<true>
-#endif
-#ifndef NERF_BV2_M0_PER_CHUNK
-#define NERF_BV2_M0_PER_CHUNK 1 // M0 (the LDS destination of an LDS-DMA piece) is written ONCE per chunk, where the chunk is selected, and the four pieces
-#endif                          // of the wave's chunk quarter go out by instruction offset alone.  Round 4, tools/probes/lds_dma_stagger_probe.hip: beside MFMAs a
-                                // piece costs 25 cycles with M0 saved / written / restored around it, 17 with M0 written only, 0 with M0 left alone -- the
-                                // "price of an LDS-DMA instruction" of rounds 1-3 was the price of writing M0.  hipcc emits no M0 use of its own in these
-                                // kernels (no LDS-direct, no s_movrel, no sendmsg; tests/test_host_logic.py checks the generated ISA).
-#ifndef NERF_BV2_M0_NOSAVE
-#define NERF_BV2_M0_NOSAVE 0 // (NERF_BV2_M0_PER_CHUNK=0 only) 1: drop the M0 save/restore around each LDS-DMA piece (+0.3 %)
-#endif
-#ifndef NERF_BV2_PAIR_READS
-#define NERF_BV2_PAIR_READS 1 // A operands fetched two pieces at a time, one s_waitcnt per pair
-#endif
-#ifndef NERF_BV2_AHEAD
-#define NERF_BV2_AHEAD 4
-#endif
-#ifndef NERF_BV2_HALF_SYNC
-#define NERF_BV2_HALF_SYNC 0 // 1 (needs NERF_BV2_RING_SLOTS=5): one vmcnt + s_barrier per TWO chunks.  Three chunks are pre-loaded, chunk k + 3 is DMA'd
-#endif                       // during chunk k into the slot of chunk k - 2; the barrier in the middle of every even chunk c proves chunks <= c + 2 landed
-                             // (all issued before it) and every wave past chunk c - 1.  Round-4 experiment (profiles/r04_bf16_half_sync_ab.log):
-                             // same results, sigma-only kernel 26.1 ms against 26.0 -- the barrier is not what costs -- and the full kernel slower.
-#if NERF_BV2_HALF_SYNC
-static_assert(NERF_BV2_RING_SLOTS == 5, "NERF_BV2_HALF_SYNC needs a five-slot ring");
-#endif
 // timing-only diagnostics (results are garbage): which resource bounds the kernel
 #ifndef NERF_BV2_DIAG_NO_DMA
 #define NERF_BV2_DIAG_NO_DMA 0
@@ -107,7 +65,8 @@ static_assert(NERF_BV2_RING_SLOTS == 5, "NERF_BV2_HALF_SYNC needs a five-slot ri
 namespace {
 
 constexpr int kCB = kChunkBytesBf16V2, kRS = kRingSlotsBf16V2;
-constexpr int kAhead = NERF_BV2_AHEAD; // A-operand prefetch distance in pieces
+constexpr int kAhead = 4; // A-operand prefetch distance in pieces, fetched two at a time with one s_waitcnt per pair
+static_assert(kAhead % 2 == 0, "paired reads need an even prefetch distance");
 
 template <int I, int N, class F>
 __device__ __forceinline__ void static_for(F &&f) {
@@ -125,7 +84,6 @@ struct PipeV {
     uint32_t ring_addr, wr_slot_off, next_off, stream_bytes;
     const char *gbase, *cur_src;
     uint32_t cur_dst, lane16;
-    uint32_t sync_phase;          // NERF_BV2_HALF_SYNC: 0 = this chunk's middle carries the barrier
 };
 
 __device__ __forceinline__ void pipe_next_chunk(PipeV &P) {
@@ -137,22 +95,19 @@ __device__ __forceinline__ void pipe_next_chunk(PipeV &P) {
     P.next_off = (off == P.stream_bytes) ? 0u : off;
     slot += kCB;
     P.wr_slot_off = (slot == kRS * kCB) ? 0u : slot;
-#if NERF_BV2_M0_PER_CHUNK
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0" ::"s"(P.cur_dst) : "memory"); // the chunk quarter's LDS destination; its pieces add their instruction offset
-#endif
+    // M0 -- the LDS destination of an LDS-DMA piece -- is written ONCE per chunk quarter, here; the quarter's four pieces go out by instruction offset
+    // alone.  tools/probes/lds_dma_stagger_probe.hip: beside MFMAs a piece costs 25 cycles with M0 saved / written / restored around it, 17 with M0
+    // written only, 0 with M0 left alone.  hipcc emits no M0 use of its own in these kernels (no LDS-direct, no s_movrel, no sendmsg;
+    // tests/test_host_logic.py checks the generated ISA).
+    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0" ::"s"(P.cur_dst) : "memory");
 }
 
 // piece at byte offset `off` of the chunk quarter pipe_next_chunk selected (pipe_start's bursts)
-__device__ __forceinline__ void glds_piece_at(uint32_t lane16, const char *gsrc, uint32_t dst, int off) {
-#if NERF_BV2_M0_PER_CHUNK
-    (void)dst;
+__device__ __forceinline__ void glds_piece_at(uint32_t lane16, const char *gsrc, int off) {
     if (off == 0)         asm volatile("global_load_lds_dwordx4 %0, %1" ::"v"(lane16), "s"(gsrc) : "memory");
     else if (off == 1024) asm volatile("global_load_lds_dwordx4 %0, %1 offset:1024" ::"v"(lane16), "s"(gsrc) : "memory");
     else if (off == 2048) asm volatile("global_load_lds_dwordx4 %0, %1 offset:2048" ::"v"(lane16), "s"(gsrc) : "memory");
     else                  asm volatile("global_load_lds_dwordx4 %0, %1 offset:3072" ::"v"(lane16), "s"(gsrc) : "memory");
-#else
-    glds_piece(lane16, gsrc + off, dst + off);
-#endif
 }
 
 // (Re)start at chunk 0: chunks 0 .. kRS - 2 loaded and visible, the first kAhead A operands prefetched.  The caller guarantees
@@ -160,12 +115,11 @@ __device__ __forceinline__ void glds_piece_at(uint32_t lane16, const char *gsrc,
 __device__ __forceinline__ void pipe_start(PipeV &P) {
     P.next_off = 0;
     P.wr_slot_off = 0;
-    P.sync_phase = 0;
 #pragma unroll
-    for (int c = 0; c < (NERF_BV2_HALF_SYNC ? 3 : kRS - 1); ++c) {
+    for (int c = 0; c < kRS - 1; ++c) {
         pipe_next_chunk(P);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) glds_piece_at(P.lane16, P.cur_src, P.cur_dst, i * 1024);
+        for (int i = 0; i < 4; ++i) glds_piece_at(P.lane16, P.cur_src, i * 1024);
     }
     asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
     P.rd_slot_off = 0;
@@ -182,10 +136,7 @@ __device__ __forceinline__ h16x8 pipe_take(PipeV &P) {
     if constexpr (PH == 8) {
         // chunk c + 1 was issued kRS - 2 chunks ago; the 4 (kRS - 3) pieces of the chunks issued since may still be in
         // flight (VMEM returns in order; any compiler-issued access in between only makes this wait longer, never shorter)
-#if NERF_BV2_HALF_SYNC
-        if (P.sync_phase == 0) asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory"); // wave-uniform; every wave has consumed the same number of chunks
-        P.sync_phase ^= 1u;
-#elif NERF_BV2_DIAG_NO_BARRIER
+#if NERF_BV2_DIAG_NO_BARRIER
         asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * (kRS - 3)) : "memory");
 #else
         asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(4 * (kRS - 3)) : "memory");
@@ -195,8 +146,6 @@ __device__ __forceinline__ h16x8 pipe_take(PipeV &P) {
 #if NERF_BV2_DIAG_NO_LDS
     if constexpr (PH != 0) { u32x4 a = P.a[0]; asm volatile("" : "+v"(a)); return __builtin_bit_cast(h16x8, a); }
 #endif
-#if NERF_BV2_PAIR_READS
-    static_assert(kAhead % 2 == 0, "paired reads need an even prefetch distance");
     if constexpr ((PH & 1) == 0) {
         // both operands of this piece pair are "used" here, so hipcc waits for them with ONE s_waitcnt
         asm volatile("" : "+v"(P.a[PH % 8]), "+v"(P.a[(PH + 1) % 8]));
@@ -213,48 +162,13 @@ __device__ __forceinline__ h16x8 pipe_take(PipeV &P) {
     } else {
         return __builtin_bit_cast(h16x8, P.a[PH % 8]);
     }
-#else
-    const u32x4 a = P.a[PH % 8];
-    if constexpr (PH + kAhead == 16) { // the piece to prefetch is the first of the next chunk
-        uint32_t off = P.rd_slot_off + kCB;
-        off = (off == kRS * kCB) ? 0u : off;
-        P.rd_slot_off = off;
-        P.rd_base = P.ring_lane + off;
-    }
-    P.a[(PH + kAhead) % 8] = *(const LDS_AS u32x4 *)(P.rd_base + ((PH + kAhead) % 16) * 1024);
-    return __builtin_bit_cast(h16x8, a);
-#endif
 }
 
 // LDS-DMA piece whose instruction offset OFF advances the global AND the LDS address (both = base + OFF + lane * 16): the four
-// pieces of a wave's chunk quarter share one scalar base pair and one M0 value.
+// pieces of a wave's chunk quarter share one scalar base and the M0 value pipe_next_chunk wrote.
 template <int OFF>
-__device__ __forceinline__ void glds_piece_off(uint32_t lane16, const char *gsrc, uint32_t dst) {
-#if NERF_BV2_M0_PER_CHUNK
-    (void)dst; // M0 holds it since pipe_next_chunk
+__device__ __forceinline__ void glds_piece_off(uint32_t lane16, const char *gsrc) {
     asm volatile("global_load_lds_dwordx4 %0, %1 offset:%2" : : "v"(lane16), "s"(gsrc), "n"(OFF) : "memory");
-#elif NERF_BV2_DMA_INST_OFFSET && NERF_BV2_M0_NOSAVE
-    // M0 is written and read inside this one statement and not restored: hipcc emits no M0 use of its own in this kernel
-    // (no LDS-direct, no s_movrel, no sendmsg; checked on the generated ISA: every m0 reference is one of these statements)
-    asm volatile("s_mov_b32 m0, %2\n\t"
-                 "s_nop 0\n\t"
-                 "global_load_lds_dwordx4 %0, %1 offset:%3"
-                 :
-                 : "v"(lane16), "s"(gsrc), "s"(dst), "n"(OFF)
-                 : "memory");
-#elif NERF_BV2_DMA_INST_OFFSET
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\t"
-                 "s_mov_b32 m0, %3\n\t"
-                 "s_nop 0\n\t"
-                 "global_load_lds_dwordx4 %1, %2 offset:%4\n\t"
-                 "s_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(lane16), "s"(gsrc), "s"(dst), "n"(OFF)
-                 : "memory");
-#else
-    glds_piece(lane16, gsrc + OFF, dst + OFF);
-#endif
 }
 
 template <int PH>
@@ -262,7 +176,7 @@ __device__ __forceinline__ void pipe_dma(PipeV &P) {
 #if NERF_BV2_DIAG_NO_DMA
     return;
 #endif
-    if constexpr (PH >= 9 && (PH & 1) == 1) glds_piece_off<((PH - 9) / 2) * 1024>(P.lane16, P.cur_src, P.cur_dst);
+    if constexpr (PH >= 9 && (PH & 1) == 1) glds_piece_off<((PH - 9) / 2) * 1024>(P.lane16, P.cur_src);
 }
 
 #if NERF_V2_F16
@@ -357,11 +271,8 @@ template <int LAST>
 constexpr int pair_step(int pr) { return LAST == 15 ? (pr == 0 ? 1 : 2 * pr) // 16-piece tiles: even steps, the DMA pieces go out on odd ones
                                                     : 1 + pr * (LAST - 1) / 7; }
 
-#if NERF_BV2_SCHED_BARRIER
+// keeps the written interleave (A-operand prefetch distance, epilogue pairs between MFMA pairs)
 #define BV2_PIN() __builtin_amdgcn_sched_barrier(0)
-#else
-#define BV2_PIN() ((void)0)
-#endif
 
 struct Acc { f32x16 a0, a1, b0, b1; }; // two accumulator sets x two sub-tiles; even output tiles use set a, odd ones set b
 
@@ -476,8 +387,8 @@ __device__ __forceinline__ void colour_layers(u32x4 (&X0)[16], u32x4 (&X1)[16], 
     for (int k = 0; k < 16; ++k) { V0[k] = X0[k]; V1[k] = X1[k]; }
     {
         f32x16 D;
-        ENCODE_DIR(d0[0], d0[1], d0[2], h, D); pack_tile(D, V0[16], V0[17]);
-        ENCODE_DIR(d1[0], d1[1], d1[2], h, D); pack_tile(D, V1[16], V1[17]);
+        encode_dir_doubling(d0[0], d0[1], d0[2], h, D); pack_tile(D, V0[16], V0[17]);
+        encode_dir_doubling(d1[0], d1[1], d1[2], h, D); pack_tile(D, V1[16], V1[17]);
     }
     layer<18, 4, true, 3, true, false, 14, false>(V0, V1, Y0, Y1, C, small + kBiasViewOff, small, H, P, h); // viewdirs + rgb partial sums (:220-223)
     {   // viewdirs' 72 pieces end at phase 8; the stream carries 8 zero pieces up to the chunk end: step over them
@@ -542,19 +453,13 @@ __global__ __launch_bounds__(256, 1) void V2SYM(nerf_mlp_kernel_bf16v2, nerf_mlp
         }
         return r;
     };
-#if NERF_BV2_PREFETCH_INPUTS
-    RawIn nx0 = raw(blockIdx.x, 0), nx1 = raw(blockIdx.x, 1);
-#endif
+    RawIn nx0 = raw(blockIdx.x, 0), nx1 = raw(blockIdx.x, 1); // the next tile's raw inputs are loaded one tile ahead
     for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const int i0 = tile * kPointsPerBlockBf16V2 + wave * 64 + p, i1 = i0 + 32;
         const bool v0 = i0 < A.n_points, v1 = i1 < A.n_points;
-#if NERF_BV2_PREFETCH_INPUTS
         const RawIn in0 = nx0, in1 = nx1;
         const int nt_idx = tile + gridDim.x < n_tiles ? tile + gridDim.x : tile;
         nx0 = raw(nt_idx, 0); nx1 = raw(nt_idx, 1);
-#else
-        const RawIn in0 = raw(tile, 0), in1 = raw(tile, 1);
-#endif
 
         // position encodings -> 4 packed k-steps per sub-tile
         u32x4 E0[4], E1[4];
@@ -562,10 +467,10 @@ __global__ __launch_bounds__(256, 1) void V2SYM(nerf_mlp_kernel_bf16v2, nerf_mlp
             float px, py, pz;
             f32x16 E[2];
             point_of<MODE>(A, in0, px, py, pz);
-            ENCODE_POINT(px, py, pz, h, E);
+            encode_point_doubling(px, py, pz, h, E);
             pack_tile(E[0], E0[0], E0[1]); pack_tile(E[1], E0[2], E0[3]);
             point_of<MODE>(A, in1, px, py, pz);
-            ENCODE_POINT(px, py, pz, h, E);
+            encode_point_doubling(px, py, pz, h, E);
             pack_tile(E[0], E1[0], E1[1]); pack_tile(E[1], E1[2], E1[3]);
         }
         u32x4 X0[16], X1[16], Y0[16], Y1[16];
@@ -713,9 +618,9 @@ __global__ __launch_bounds__(256, 1) void V2SYM(nerf_trunk_seq_kernel_bf16, nerf
         u32x4 E0[4], E1[4];
         {
             f32x16 E[2];
-            ENCODE_POINT(c0.px, c0.py, c0.pz, h, E);
+            encode_point_doubling(c0.px, c0.py, c0.pz, h, E);
             pack_tile(E[0], E0[0], E0[1]); pack_tile(E[1], E0[2], E0[3]);
-            ENCODE_POINT(c1.px, c1.py, c1.pz, h, E);
+            encode_point_doubling(c1.px, c1.py, c1.pz, h, E);
             pack_tile(E[0], E1[0], E1[1]); pack_tile(E[1], E1[2], E1[3]);
         }
         u32x4 X0[16], X1[16], Y0[16], Y1[16];
@@ -877,17 +782,4 @@ hipError_t nerf_mlp_f16v2_launch(const MlpArgs &a, int n_blocks, hipStream_t str
     hipLaunchKernelGGL((nerf_mlp_kernel_f16v2<false, MLP_MODE_RAYS>), dim3(n_blocks), dim3(256), kLdsBytesBf16V2, stream, a);
     return hipGetLastError();
 }
-#ifdef NERF_V2_F16_FULL // experiment (variant builds): the full f16 kernel, to price an f16 twin of the bf16 mode
-hipError_t nerf_mlp_f16v2_full_launch(const MlpArgs &a, int n_blocks, hipStream_t stream) {
-    if (a.n_points <= 0) return hipSuccess;
-    if (a.mode != MLP_MODE_RAYS) return hipErrorInvalidValue;
-    const int n_tiles = (a.n_points + kPointsPerBlockBf16V2 - 1) / kPointsPerBlockBf16V2;
-    if (n_blocks > n_tiles) n_blocks = n_tiles;
-    if (n_blocks < 1) n_blocks = 1;
-    static bool attr_set = false;
-    if (!attr_set) { (void)hipFuncSetAttribute((const void *)nerf_mlp_kernel_f16v2<true, MLP_MODE_RAYS>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytesBf16V2); attr_set = true; }
-    hipLaunchKernelGGL((nerf_mlp_kernel_f16v2<true, MLP_MODE_RAYS>), dim3(n_blocks), dim3(256), kLdsBytesBf16V2, stream, a);
-    return hipGetLastError();
-}
-#endif
 #endif

@@ -36,31 +36,11 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 namespace {
 
 constexpr int kCB = kChunkBytesX3, kRS = kRingSlotsX3;
-#ifndef NERF_X3_AHEAD
-#define NERF_X3_AHEAD 2
-#endif
-constexpr int kX3Ahead = NERF_X3_AHEAD; // operand prefetch distance in units (1..3); a unit is six MFMAs = 192 cycles
+constexpr int kX3Ahead = 2; // operand prefetch distance in units (1..3); a unit is six MFMAs = 192 cycles
 
 #include "mlp_x3_pipe.hip.h"
 
-#ifndef NERF_X3_DIAG_DROP_W3
-#define NERF_X3_DIAG_DROP_W3 0
-#endif
-#ifndef NERF_X3_DIAG_MFMA_16X16
-#define NERF_X3_DIAG_MFMA_16X16 0 // timing/power experiment only (results are garbage): the same FLOPs as two 16x16x32 MFMAs
-#endif
-#if NERF_X3_DIAG_MFMA_16X16
-__device__ __forceinline__ f32x16 mfma_as_two_16x16(bf16x8 a, bf16x8 b, f32x16 c) {
-    f32x4 lo = {c[0], c[1], c[2], c[3]}, hi = {c[4], c[5], c[6], c[7]};
-    lo = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, lo, 0, 0, 0);
-    hi = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, hi, 0, 0, 0);
-    c[0] = lo[0]; c[1] = lo[1]; c[2] = lo[2]; c[3] = lo[3]; c[4] = hi[0]; c[5] = hi[1]; c[6] = hi[2]; c[7] = hi[3];
-    return c;
-}
-#define MFMA16(a, b, c) mfma_as_two_16x16((a), (b), (c))
-#else
 #define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
-#endif
 
 struct B3 { u32x4 h, m, l; }; // the three bf16x8 fragments of one k-step's B operand
 
@@ -135,11 +115,7 @@ __device__ __forceinline__ void k_step(f32x16 (&out)[8], const B3 &bc, const f32
         PrepState st;
         pipe_take<U>(P, a1, a2, a3);
         X3_PIN();
-#if NERF_X3_DIAG_DROP_W3 // accuracy / speed experiment only: five products, the weights' third part ignored
-        asm volatile("" ::"v"(a3));
-#else
         out[nt] = MFMA16(a3, b1, out[nt]);
-#endif
         X3_PIN();
         pipe_prefetch<U>(P);
         X3_PIN();

@@ -34,14 +34,8 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 namespace {
 
 constexpr int kCB = kChunkBytesF16X2, kRS = kRingSlotsF16X2;
-#ifndef NERF_F16X2_AHEAD
-#define NERF_F16X2_AHEAD 2
-#endif
-constexpr int kAhead = NERF_F16X2_AHEAD; // operand prefetch distance in units (1..3); a unit is three MFMAs = 96 cycles
+constexpr int kAhead = 2; // operand prefetch distance in units (1..3); a unit is three MFMAs = 96 cycles
 // Timing-only diagnostics (results are WRONG with any of these set; never shipped): what the non-MFMA cycles are spent on
-#ifndef NERF_F16X2_RANGE_WATCH
-#define NERF_F16X2_RANGE_WATCH 1 // 0 (variant builds): without the per-pair range watch, to price it
-#endif
 #ifndef NERF_F16X2_DIAG_NO_BARRIER
 #define NERF_F16X2_DIAG_NO_BARRIER 0
 #endif
@@ -180,9 +174,7 @@ __device__ __forceinline__ void prep_stage(const f32x16 &in, B2 &b, PrepState &s
         if (RELU) { x0 = relu(x0); x1 = relu(x1); }
         // Range watch (one v_max3_f32 per pair): beyond 65 504 the f16 parts become (inf, -inf), the products NaN, and a NaN does not
         // survive the integer-max ReLU of the next layer -- the outputs would be finite and WRONG (measured: sigma 296 instead of 1.5e7)
-#if NERF_F16X2_RANGE_WATCH
         asm volatile("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(amax) : "v"(x0), "v"(x1)); // as asm: the plain expression made hipcc spill 800 registers
-#endif
         st.x = f32x2{x0, x1};
     } else if constexpr (STAGE == 1) {
         const f16x2 hh = __builtin_convertvector(st.x, f16x2);
@@ -221,10 +213,8 @@ __device__ __forceinline__ void range_check(PipeH &P, unsigned int *counter, boo
 // guide's rule): the next unit's two ds_reads behind MFMA 1; the three stages of splitting one pair of the NEXT k-step's B operand
 // spread over a PAIR of units (8-tile layers: pair q in units 2q, 2q+1 -- stages 0, 1 behind MFMAs 2, 3 of the even unit, stage 2
 // behind MFMA 2 of the odd one; viewdirs, 4 units per k-step: all three stages in unit q); the LDS-DMA piece of units 4..7 behind
-// MFMA 1 (even units) or MFMA 3 (odd units, whose third gap is otherwise empty).
-#ifndef NERF_F16X2_SPREAD
-#define NERF_F16X2_SPREAD 1 // 0: everything behind MFMA 1 / per-unit stages (first version, 56.9 % of the bf16-class peak)
-#endif
+// MFMA 1 (even units) or MFMA 3 (odd units, whose third gap is otherwise empty).  (The first version, everything behind MFMA 1 and
+// per-unit stages in the 8-tile layers too, reached 56.9 % of the bf16-class peak.)
 template <int NT, int U0, bool HAS_NEXT, bool NRELU, int NKS>
 __device__ __forceinline__ void k_step(f32x16 (&out)[8], const B2 &bc, const f32x16 &nin, B2 &bn, PipeH &P) {
     const f16x8 b1 = __builtin_bit_cast(f16x8, bc.h), b2 = __builtin_bit_cast(f16x8, bc.l);
@@ -232,7 +222,7 @@ __device__ __forceinline__ void k_step(f32x16 (&out)[8], const B2 &bc, const f32
     static_for<0, NT>([&](auto nt_c) {
         constexpr int nt = decltype(nt_c)::value;
         constexpr int U = U0 + nt;
-        constexpr bool pairwise = NERF_F16X2_SPREAD && NT == 8;
+        constexpr bool pairwise = NT == 8;
         constexpr bool even = (nt & 1) == 0;
         constexpr int Q = NT == 4 ? nt : nt / 2;
         f16x8 a1, a2;

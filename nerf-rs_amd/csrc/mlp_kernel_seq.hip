@@ -53,27 +53,10 @@ __device__ __forceinline__ void pipe_start(Pipe &P, const LDS_AS char *lds, int 
     asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
     P.rd_slot_off = 0;
     P.rd_base = P.ring_lane;
-#pragma unroll
-    for (int j = 0; j < NERF_LDS_GROUP; ++j) {
-        P.nx[2 * j] = *(const LDS_AS f32x4 *)(P.rd_base + j * 2048);
-        P.nx[2 * j + 1] = *(const LDS_AS f32x4 *)(P.rd_base + j * 2048 + 1024);
-    }
+    pipe_prime(P);
 }
 
 } // namespace
-
-// Timing-only diagnostics (results are WRONG with any of these set; never part of the product build -- `make variant` only):
-#ifndef NERF_SEQ_DIAG_NO_PASS
-#define NERF_SEQ_DIAG_NO_PASS 0 // 1: live samples are staged but no colour pass ever runs
-#endif
-#ifndef NERF_SEQ_DIAG_STAMP
-#define NERF_SEQ_DIAG_STAMP 0 // k > 0: wave 0 of every workgroup accumulates s_memtime cycles of phase k of the colour passes into the NEXT launch
-                              // slot's counters (read back as nerf_stats.n_hybrid_rays = passes, n_exec_coarse_trunk += cycles): 1 whole pass,
-                              // 3 viewdirs loop, 4 tail (rgb head), 5 from the vote barrier to the first pass
-#endif
-#ifndef NERF_SEQ_DIAG_NO_STAGE
-#define NERF_SEQ_DIAG_NO_STAGE 0 // 1: no staging either (the trunk alone, with the scan)
-#endif
 
 // ---- LDS layout of the EXPORT kernel: [weight ring][small parameters][staging: 3 tiles x 32 columns x 1 KiB][per staged column:
 // sample index + ray direction][live counts of the four waves] -----------------------------------------------------------
@@ -107,14 +90,6 @@ __device__ __forceinline__ void ring_issue_start(Pipe &P, const char *gbase, uin
     for (int c = 0; c < n_chunks; ++c) pipe_issue(P);
     P.rd_slot_off = 0;
     P.rd_base = P.ring_lane;
-}
-
-__device__ __forceinline__ void pipe_prime(Pipe &P) { // operands of the first macro-step of the trunk (what pipe_start / pipe_restart do)
-#pragma unroll
-    for (int j = 0; j < NERF_LDS_GROUP; ++j) {
-        P.nx[2 * j] = *(const LDS_AS f32x4 *)(P.rd_base + j * 2048);
-        P.nx[2 * j + 1] = *(const LDS_AS f32x4 *)(P.rd_base + j * 2048 + 1024);
-    }
 }
 
 __device__ __forceinline__ void ring_advance(Pipe &P) {
@@ -170,8 +145,7 @@ __device__ __forceinline__ void store_tile(LDS_AS char *tile, int lane, int slot
 // Waves 0..2 each compute one colour channel.  On entry chunk 0 of the colour stream has landed (every wave past the barrier that
 // proves it) and chunks 1, 2 are in flight.
 __device__ __forceinline__ void colour_pass(Pipe &P, const Stage &S, int n_cols, bool last_pass, const char *trunk_gbase, const SeqArgs &A,
-                                            const LDS_AS float *small, int wave, int lane, unsigned long long &diag) {
-    (void)diag;
+                                            const LDS_AS float *small, int wave, int lane) {
     const int p = lane & 31, h = lane >> 5;
     const int t0 = S.head, t1 = S.head + 1 == kStageTiles ? 0 : S.head + 1;
     LDS_AS char *tile0 = S.tiles + t0 * kStageTileBytes, *tile1 = S.tiles + t1 * kStageTileBytes;
@@ -191,12 +165,9 @@ __device__ __forceinline__ void colour_pass(Pipe &P, const Stage &S, int n_cols,
     bias_tile(V0, small + kBiasViewOff + (wave * 2 + h) * 16);
     V1 = V0;
     f32x16 D0, D1; // the ninth input tile: the columns' direction encodings (every wave needs them for its output tile)
-    encode_dir<NERF_FAST_SINCOS != 0>(m0[1], m0[2], m0[3], h, D0);
-    encode_dir<NERF_FAST_SINCOS != 0>(m1[1], m1[2], m1[3], h, D1);
+    encode_dir(m0[1], m0[2], m0[3], h, D0);
+    encode_dir(m1[1], m1[2], m1[3], h, D1);
     int chunk = 0;
-#if NERF_SEQ_DIAG_STAMP == 3
-    const unsigned long long ts0 = __builtin_amdgcn_s_memtime();
-#endif
     for (int tt = 0; tt < 9; ++tt, ++chunk) { // input tiles 0..7: relu(h8), the staged trunk outputs (the fused kernel's order: k ascending); 8: the direction encoding (:219-220)
         float bq0[16], bq1[16]; // B operands of this input tile, one VALU burst
         if (tt < 8) {
@@ -229,12 +200,6 @@ __device__ __forceinline__ void colour_pass(Pipe &P, const Stage &S, int n_cols,
 #pragma unroll
         for (int k = 0; k < 16; ++k) c_cur[k] = c_nxt[k];
     }
-#if NERF_SEQ_DIAG_STAMP == 3
-    diag += __builtin_amdgcn_s_memtime() - ts0;
-#endif
-#if NERF_SEQ_DIAG_STAMP == 4
-    const unsigned long long ts0 = __builtin_amdgcn_s_memtime();
-#endif
     // viewdirs outputs -> the staging tiles (input-tile slot w); waves 0..2 each run one channel of the rgb head (VALU, the fused
     // kernel's own code and order per channel) for both groups
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); // every wave has read its last operands from the tiles
@@ -258,9 +223,6 @@ __device__ __forceinline__ void colour_pass(Pipe &P, const Stage &S, int n_cols,
         if (h == 0 && p < n_cols) A.rgb_out[3 * (size_t)__builtin_bit_cast(unsigned, m0[0]) + wave] = c0;
         if (h == 0 && 32 + p < n_cols) A.rgb_out[3 * (size_t)__builtin_bit_cast(unsigned, m1[0]) + wave] = c1;
     }
-#if NERF_SEQ_DIAG_STAMP == 4
-    diag += __builtin_amdgcn_s_memtime() - ts0;
-#endif
 }
 
 } // namespace
@@ -295,8 +257,6 @@ __global__ __launch_bounds__(256, 1) void nerf_trunk_seq_kernel(const SeqArgs A)
 
     RayWork W;
     work_init(W, A);
-    unsigned long long diag_cycles = 0;
-    unsigned diag_passes = 0;
     for (;;) {
         const bool running = work_acquire(W, A, vote, wave, lane);
         if (!running && !(EXPORT && S.count > 0)) break;
@@ -306,7 +266,7 @@ __global__ __launch_bounds__(256, 1) void nerf_trunk_seq_kernel(const SeqArgs A)
         if (running) {
             c = chunk_inputs(W, A, p);
             f32x16 E[2];
-            encode_point<NERF_FAST_SINCOS != 0>(c.px, c.py, c.pz, h, E);
+            encode_point(c.px, c.py, c.pz, h, E);
             f32x16 X[8];
             load_bias<8>(X, small + kBiasOff + 0 * 256, h);
             tile_steps<8, false>(E[0], X, P);
@@ -333,10 +293,6 @@ __global__ __launch_bounds__(256, 1) void nerf_trunk_seq_kernel(const SeqArgs A)
                 W.live_done += (unsigned)li.n_live;
             }
             asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory"); // counts visible; the ring is idle, its prefetches landed
-#if NERF_SEQ_DIAG_STAMP == 5
-            const unsigned long long diag_vote = __builtin_amdgcn_s_memtime();
-            bool diag_first = false;
-#endif
             int n_w4[4] = {0, 0, 0, 0};
             if (running) {
 #pragma unroll
@@ -345,22 +301,15 @@ __global__ __launch_bounds__(256, 1) void nerf_trunk_seq_kernel(const SeqArgs A)
             const int total = n_w4[0] + n_w4[1] + n_w4[2] + n_w4[3];
             // 0 = trunk stream (its chunks 0, 1 prefetched), 1 = colour stream issued, 2 = colour stream running (chunk 0 proven landed)
             int ring = 0;
-#if !(NERF_SEQ_DIAG_NO_PASS || NERF_SEQ_DIAG_NO_STAGE)
             if (S.count + total >= 64 || (!running && S.count > 0)) { // a pass will run in this step: start its stream under the deposits
                 ring_issue_start(P, colour_gbase, kColourChunks * kChunkBytes, 3);
                 ring = 1;
             }
-#endif
             for (int w = 0; w <= 4; ++w) {
                 const int n_w = w == 0 ? n_w4[0] : w == 1 ? n_w4[1] : w == 2 ? n_w4[2] : w == 3 ? n_w4[3] : 0;
                 // flush condition: wave w's samples would overflow the 96 columns / end of the step with two full tiles / end of the kernel
                 const bool flush = w < 4 ? (S.count + n_w > kStageCols) : (S.count >= 64 || (!running && S.count > 0));
-#if NERF_SEQ_DIAG_NO_PASS || NERF_SEQ_DIAG_NO_STAGE
-                if (flush) S.count &= 63;
-                if (false) {
-#else
                 if (flush) {
-#endif
                     if (ring == 1) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)\n\ts_barrier" ::: "memory"); // chunk 0 landed, deposits visible
                     else asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");                    // deposits since the last pass visible
                     ring = 2;
@@ -368,23 +317,13 @@ __global__ __launch_bounds__(256, 1) void nerf_trunk_seq_kernel(const SeqArgs A)
                         const int n_cols = S.count < 64 ? S.count : 64;
                         const int rest = S.count - n_cols;
                         const bool last = !(rest >= 64 || (!running && rest > 0)) && w == 4 && running; // the trunk continues right after this pass
-#if NERF_SEQ_DIAG_STAMP == 1
-                        const unsigned long long ts0 = __builtin_amdgcn_s_memtime();
-#endif
-#if NERF_SEQ_DIAG_STAMP == 5
-                        if (!diag_first) { diag_cycles += __builtin_amdgcn_s_memtime() - diag_vote; diag_first = true; }
-#endif
-                        colour_pass(P, S, n_cols, last, trunk_gbase, A, small, wave, lane, diag_cycles);
-                        ++diag_passes;
-#if NERF_SEQ_DIAG_STAMP == 1
-                        diag_cycles += __builtin_amdgcn_s_memtime() - ts0;
-#endif
+                        colour_pass(P, S, n_cols, last, trunk_gbase, A, small, wave, lane);
                         S.head = (S.head + (n_cols > 32 ? 2 : 1)) % kStageTiles;
                         S.count = rest;
                         if (last) { ring = 0; pipe_prime(P); }
                     }
                 }
-                if (!NERF_SEQ_DIAG_NO_STAGE && w < 4 && wave == w && li.live) {
+                if (w < 4 && wave == w && li.live) {
                     int slot = S.head * 32 + S.count + __popcll(li.mask & ((1ull << p) - 1ull));
                     slot = slot >= kStageCols ? slot - kStageCols : slot;
                     LDS_AS char *dst = S.tiles + (slot >> 5) * kStageTileBytes + ((slot & 31) + 32 * h) * 16;
@@ -417,14 +356,6 @@ __global__ __launch_bounds__(256, 1) void nerf_trunk_seq_kernel(const SeqArgs A)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // drain the unused DMA prefetches before the LDS allocation is released
     work_done(W, A, lane);
     pipe_zskip_report(P, A.zskip_stats, lane);
-#if NERF_SEQ_DIAG_STAMP
-    if (EXPORT && A.stats && wave == 0 && lane == 0) { // the next launch slot's counters: {u32 head, u32 live = passes, u64 = cycles}
-        atomicAdd(A.stats + 2, diag_cycles);
-        atomicAdd((unsigned *)(A.stats + 1) + 1, diag_passes);
-    }
-#else
-    (void)diag_cycles; (void)diag_passes;
-#endif
 }
 
 hipError_t nerf_seq_init() {

@@ -97,7 +97,8 @@ constexpr int kSmallBytes = kSmallFloats * 4;
 
 constexpr int kLdsBytes = kRingSlots * kChunkBytes + kSmallBytes;
 
-// ---- bf16 stream (mlp_kernel_bf16.hip): macro-step = 8 KiB (8 pieces of 64 lanes x 8 bf16), 32-KiB chunks.
+// ---- v1 bf16 stream (no kernel reads it any more: the host's intermediate piece order that every 16-bit stream is re-packed from,
+// nerf_networks.cpp upload_bf16_family): macro-step = 8 KiB (8 pieces of 64 lanes x 8 bf16), 32-KiB chunks.
 // Per input tile (32 k-rows) an 8-tile layer has 2 k-steps x 8 pieces = 2 macro-steps; the 4-tile viewdirs layer
 // 2 k-steps x 4 pieces = 1 macro-step.  viewdirs (9 tiles = 72 KiB) is zero-padded to 3 chunks.
 constexpr int kChunkBytesBf16 = 32768;

@@ -144,7 +144,7 @@ __global__ __launch_bounds__(256, 1) void SPLIT_KERNEL_FUSED(const MlpArgs A) {
         const bool audit = MODE == MLP_MODE_LIST && (entry >> 31) != 0; // an audited certificate: the raw pre-activation leaves the kernel (k_cert_audit)
 
         f32x16 E[2];
-        encode_point<true>(px, py, pz, h, E);
+        encode_point(px, py, pz, h, E);
 
         f32x16 X[8], Y[8];
         BS b;
@@ -188,7 +188,7 @@ __global__ __launch_bounds__(256, 1) void SPLIT_KERNEL_FUSED(const MlpArgs A) {
         if (FULL) {
             hidden_layer<true>(Y, X, small + kBiasOff + 8 * 256, P, h); // bottleneck: no activation on its output (:218)
             f32x16 D;
-            encode_dir<true>(dx, dy, dz, h, D);
+            encode_dir(dx, dy, dz, h, D);
             f32x16 (&V)[8] = Y;                                          // Y is dead after the bottleneck
             load_bias<4>(V, small + kBiasViewOff, h);
             asm volatile("" : "+a"(X[0]));
@@ -252,7 +252,7 @@ __global__ __launch_bounds__(256, 1) void SPLIT_KERNEL_TRUNK(const SeqArgs A) {
     while (work_acquire(W, A, vote, wave, lane)) {
         const ChunkIn c = chunk_inputs(W, A, p);
         f32x16 E[2];
-        encode_point<true>(c.px, c.py, c.pz, h, E);
+        encode_point(c.px, c.py, c.pz, h, E);
         f32x16 X[8], Y[8];
         BS b;
         load_bias<8>(X, small + kBiasOff + 0 * 256, h);
@@ -302,7 +302,7 @@ __global__ __launch_bounds__(256, 1) void SPLIT_KERNEL_COLOUR(const ColourArgs A
         const ColourIn c = colour_inputs(A, n_live, tile, wave, lane, Y);
         hidden_layer<true>(Y, X, small + kBiasOff + 8 * 256, P, h); // bottleneck
         f32x16 D;
-        encode_dir<true>(c.dx, c.dy, c.dz, h, D);
+        encode_dir(c.dx, c.dy, c.dz, h, D);
         f32x16 (&V)[8] = Y;
         load_bias<4>(V, small + kBiasViewOff, h);
         BS b;

@@ -1,6 +1,6 @@
-// mlp_x3_pipe.hip.h -- the weight-stream pipeline shared by the two bf16x3 kernels (mlp_kernel_bf16x3.hip, mlp_kernel_bf16x3b.hip):
+// mlp_x3_pipe.hip.h -- the weight-stream pipeline of the bf16x3 kernels (mlp_kernel_bf16x3.hip):
 // 24-KiB chunks of eight 3-KiB units in an LDS ring filled by LDS-DMA, one s_waitcnt + s_barrier per chunk at unit 4, operand
-// fragments prefetched kX3Ahead units ahead.  Included inside each kernel's anonymous namespace after kCB / kRS / kX3Ahead.
+// fragments prefetched kX3Ahead units ahead.  Included inside the kernel file's anonymous namespace after kCB / kRS / kX3Ahead.
 #pragma once
 
 template <int I, int N, class F>

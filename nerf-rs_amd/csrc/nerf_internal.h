@@ -25,7 +25,6 @@ struct DevNet {
     float *small = nullptr;     // small block of the packed image: the 16-bit arithmetics, which run the unfolded head
     float *small_f32 = nullptr; // small block of the folded image (viewdirs bias = b'): the f32 kernels
     uint16_t *wstream_bf16v2 = nullptr; // bf16 pieces in output-tile-major order (mlp_kernel_bf16v2.hip)
-    uint16_t *wstream_bf16v3 = nullptr; // bf16 pieces for the 16x16x32 kernel (mlp_kernel_bf16v3.hip)
     uint16_t *wstream_x3 = nullptr;     // three bf16 parts per weight (mlp_kernel_bf16x3.hip)
     uint16_t *wstream_x2 = nullptr;     // two f16 parts per weight (mlp_kernel_f16x2.hip); NULL if a weight exceeds the f16 range
     uint16_t *wstream_f16v2 = nullptr;  // one f16 per weight in wstream_bf16v2's order (mlp_kernel_f16v2.hip: certify_zero's pre-filter); NULL likewise
@@ -206,7 +205,6 @@ int timed(nerf_ctx *c, hipStream_t st, int kind, uint64_t points, F &&fn) {
 }
 
 // ---- nerf_networks.cpp: weight stream + launcher of the selected arithmetic ---------------------------------------------------------
-bool bf16_is_v2(); // false only in a -DNERF_BF16_V3=1 variant build, where NERF_MLP_BF16 runs mlp_kernel_bf16v3.hip
 inline bool valid_dtype(int d) { return d == NERF_MLP_F32 || d == NERF_MLP_BF16 || d == NERF_MLP_BF16X3 || d == NERF_MLP_F16X2; }
 inline bool split_dtype(int d) { return d == NERF_MLP_BF16X3 || d == NERF_MLP_F16X2; } // f32-accurate operand-splitting arithmetics
 // where a launch in `dtype` counts the points that left its range: the split arithmetics only

@@ -577,10 +577,9 @@ int check_image_modes(nerf_ctx *c, const nerf_render_opts *o) {
     if (o->skip_empty != 0 && o->skip_empty != 1) return fail(c, NERF_ERR_INVALID, "skip_empty must be 0 or 1");
     if (o->skip_dead != 0 && o->skip_dead != 1) return fail(c, NERF_ERR_INVALID, "skip_dead must be 0 or 1");
     const bool seq = o->skip_dead != 0;
-    if (seq && dtype == NERF_MLP_BF16 && !bf16_is_v2()) return fail(c, NERF_ERR_INVALID, "skip_dead with NERF_MLP_BF16 is not part of the NERF_BF16_V3 variant build");
     if (o->hybrid_sampling != 0 && o->hybrid_sampling != 1) return fail(c, NERF_ERR_INVALID, "hybrid_sampling must be 0 or 1");
     if (o->certify_zero != 0 && o->certify_zero != 1) return fail(c, NERF_ERR_INVALID, "certify_zero must be 0 or 1");
-    if (o->certify_zero && (dtype == NERF_MLP_BF16 || seq || o->skip_empty || !bf16_is_v2()))
+    if (o->certify_zero && (dtype == NERF_MLP_BF16 || seq || o->skip_empty))
         return fail(c, NERF_ERR_INVALID, "certify_zero needs mlp_dtype F32, BF16X3 or F16X2 and neither skip_empty nor skip_dead");
     if (o->hybrid_sampling && !(seq && !o->coarse_only && dtype != NERF_MLP_BF16)) // bf16 is its own arithmetic: there are no f32 sample positions to protect
         return fail(c, NERF_ERR_INVALID, "hybrid_sampling needs skip_dead = 1, mlp_dtype F32, BF16X3 or F16X2, and a hierarchical render");

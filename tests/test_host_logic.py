@@ -584,6 +584,28 @@ def test_one_file_variant_script_tags_its_library():
     assert "-DNERF_BUILD_VARIANT=" in src and "nerf_host_api.cpp" in src and "amdgpu-mfma-vgpr-form=1" in src
 
 
+def test_compile_time_switches_are_the_documented_ones():
+    """Every NERF_* name on a preprocessor conditional under nerf-rs_amd/csrc is a row of DESIGN.md's "Compile-time switches" table and
+    the other way round: a decided tuning switch is deleted with the path that lost, not left beside the kernel that ships."""
+    csrc = os.path.join(ROOT, "nerf-rs_amd", "csrc")
+    used = set()
+    for name in sorted(os.listdir(csrc)):
+        path = os.path.join(csrc, name)
+        if not os.path.isfile(path):
+            continue
+        for line in open(path, errors="replace"):
+            if re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b", line):
+                used.update(re.findall(r"\bNERF_[A-Z0-9_]+\b", line.split("//")[0]))
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+    section = re.search(r"^### Compile-time switches\n(.*?)^##", design, re.S | re.M)
+    assert section, "DESIGN.md has no 'Compile-time switches' section"
+    rows = [l for l in section.group(1).splitlines() if l.startswith("| `")]
+    documented = [re.match(r"\| `(NERF_[A-Z0-9_]+)` \|", l).group(1) for l in rows]
+    assert len(documented) == len(set(documented)) and len(documented) >= 10
+    assert all(l.count("|") == 5 for l in rows)  # switch, file, default, what it is for
+    assert used == set(documented), (sorted(used - set(documented)), sorted(set(documented) - used))
+
+
 def test_m0_belongs_to_the_lds_dma_statements(native, tmp_path):
     """The f32 and bf16 MLP kernels write M0 -- the LDS destination of their LDS-DMA pieces -- once per chunk quarter and leave it alone until
     the next chunk (mlp_common.hip.h dma_set_dst / glds_piece_m0), which is only right if hipcc uses M0 for nothing of its own.  Checked on
