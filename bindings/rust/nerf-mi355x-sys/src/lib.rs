@@ -285,6 +285,19 @@ extern "C" {
     pub fn nerf_stage_integrate_rgba8(ctx: *mut nerf_ctx, n_rays: usize, n: c_int, far: f32, rgb_aos: *const f32,
                                       sigma: *const f32, t: *const f32, background: *const f32, alpha_mode: c_int,
                                       rgba_out: *mut u8) -> c_int;
+    /// certify_zero's plan kernel on caller data; `list_out` / `aux_out` carry NERF_STAGE_GUARD_WORDS (64) guard words on either side
+    pub fn nerf_stage_cert_plan(ctx: *mut nerf_ctx, n_rays: usize, spr: c_int, far: f32, margin: f32, depth_limit: f32, audit_mask: u32,
+                                audit_mask_near: u32, audit_salt: u32, back_part: c_int, zero_threshold: f32, list_capacity: u32,
+                                aux_capacity: u32, t: *const f32, pre: *mut f32, jstar_out: *mut i32, list_out: *mut u32,
+                                counts_out: *mut u32, aux_out: *mut u32, rays_per_wave_out: *mut i32) -> c_int;
+    pub fn nerf_stage_cert_verify(ctx: *mut nerf_ctx, n_rays: usize, spr: c_int, far: f32, list_capacity: u32, t: *const f32,
+                                  jstar: *const i32, sigma: *mut f32, list_out: *mut u32, count: *mut u32,
+                                  fallback_rays: *mut u32) -> c_int;
+    pub fn nerf_stage_cert_audit(ctx: *mut nerf_ctx, aux: *const u32, aux_count: u32, aux_capacity: u32, n_sigma: usize,
+                                 sigma: *mut f32, audit: *mut u32) -> c_int;
+    pub fn nerf_stage_prefilter(ctx: *mut nerf_ctx, which: c_int, f16: c_int, origin: *const f32, dirs: *const f32, t: *const f32,
+                                n_rays: usize, spr: c_int, far: f32, cut_t: f32, pre_out: *mut f32,
+                                nonfinite_tiles: *mut u32) -> c_int;
 }
 
 /// Compares the sizes of the `#[repr(C)]` mirrors above with the library's own structs; call once before anything else.

@@ -648,6 +648,43 @@ int nerf_stage_integrate(nerf_ctx *ctx, size_t n_rays, int n, float far_, const 
 int nerf_stage_integrate_rgba8(nerf_ctx *ctx, size_t n_rays, int n, float far_, const float *rgb_aos, const float *sigma,
                                const float *t, const float background[3], int alpha_mode, uint8_t *rgba_out);
 
+/* ---- the device pieces of nerf_render_opts.certify_zero, one launch each on caller data (the launches a certified render makes).
+ * Argument errors are reported before the context is looked at.  A list or aux buffer is returned as the device held it, between
+ * guards: NERF_STAGE_GUARD_WORDS words, the entries, NERF_STAGE_GUARD_WORDS words, every one of them 0xFFFFFFFF before the launch. */
+#define NERF_STAGE_GUARD_WORDS 64
+/* The plan kernel over n_rays rays of spr samples.  pre (in/out, n_rays x spr): the pre-filter's density pre-activations; afterwards 0, or
+ * -1 on an uncertain sample at or behind the ray's predicted cut jstar_out[ray] (spr: no cut) = the first sample with optical depth
+ * sum max(pre, 0) max(delta, 0) in front of it > depth_limit.  A sample is certified iff -3e38 <= pre < -margin.  In front of the cut the
+ * uncertain samples are listed, and of the certified ones those with ((index ^ audit_salt) * 0x9E3779B1 mod 2^32) >> 7 & mask == 0, mask =
+ * audit_mask_near where pre > -2 margin, else audit_mask -- with bit 31 set and a record {index, bits of pre} in aux (at most 256 per
+ * rays_per_wave_out consecutive rays; the others are certified unaudited).  back_part != 0: audited certificates and listed samples with
+ * pre < -zero_threshold go to the back part (entry k at list_capacity - 1 - k).  counts_out[3] = {front, back, aux} entries WANTED:
+ * beyond a capacity they are counted, not stored, and an audit without an aux record loses its flag.
+ * list_out: list_capacity + 2 NERF_STAGE_GUARD_WORDS words; aux_out: 2 aux_capacity + 2 NERF_STAGE_GUARD_WORDS words. */
+int nerf_stage_cert_plan(nerf_ctx *ctx, size_t n_rays, int spr, float far_, float margin, float depth_limit, uint32_t audit_mask,
+                         uint32_t audit_mask_near, uint32_t audit_salt, int back_part, float zero_threshold, uint32_t list_capacity,
+                         uint32_t aux_capacity, const float *t, float *pre, int32_t *jstar_out, uint32_t *list_out,
+                         uint32_t *counts_out, uint32_t *aux_out, int32_t *rays_per_wave_out);
+/* The verify kernel: compute_weights' transmittance recurrence (src/lib.rs:261-280) over samples [0, jstar[ray]) of sigma (in/out: exact
+ * densities, -1 = marked).  Every mark at or behind jstar is cleared; if T did not fall below 1e-4 inside the prefix the marked samples are
+ * appended to the list at *count (in/out; counted beyond list_capacity, not stored) and *fallback_rays (in/out) += 1.  A ray with
+ * jstar = spr is left alone.  list_out: list_capacity + 2 NERF_STAGE_GUARD_WORDS words. */
+int nerf_stage_cert_verify(nerf_ctx *ctx, size_t n_rays, int spr, float far_, uint32_t list_capacity, const float *t, const int32_t *jstar,
+                           float *sigma, uint32_t *list_out, uint32_t *count, uint32_t *fallback_rays);
+/* The audit kernel over the first min(aux_count, aux_capacity) records {sample, bits of the pre-filter's pre-activation} of aux; sigma
+ * (in/out, n_sigma floats) holds the exact RAW pre-activation v of each.  audit (in/out, 4 words): [0] += records, [1] += those with v > 0 or
+ * NaN, [2] = max(itself, 0x7f800000 - bits(-v)) over v <= 0, [3] = max(itself, bits |pre - v|) over finite differences; sigma = 0 at every
+ * record unless v > 0. */
+int nerf_stage_cert_audit(nerf_ctx *ctx, const uint32_t *aux, uint32_t aux_count, uint32_t aux_capacity, size_t n_sigma, float *sigma,
+                          uint32_t *audit);
+/* The ray-sequential 16-bit pre-filter (f16 != 0: f16 operands, else bf16) of network `which` over n_rays rays from one origin: dirs
+ * n_rays x 3 (unit), t n_rays x spr.  pre_out: the raw density pre-activations; a ray is retired after the 32-sample chunk in which its
+ * transmittance (from max(pre, 0)) fell below cut_T -- its later samples read 0xFFFFFFFF, "not evaluated"; cut_T = 0 never retires a ray.
+ * *nonfinite_tiles: wave tiles of the f16 form with a non-finite pre-activation.  NERF_ERR_STATE: f16 asked for and the network has no
+ * f16 stream (a weight beyond the f16 range). */
+int nerf_stage_prefilter(nerf_ctx *ctx, int which, int f16, const float origin[3], const float *dirs, const float *t, size_t n_rays,
+                         int spr, float far_, float cut_T, float *pre_out, uint32_t *nonfinite_tiles);
+
 /* "" for the product build.  Tuning / timing-only builds (make variant: some of their switches make results WRONG on purpose)
  * report "NAME: compile definitions"; a host should refuse such a library outside experiments (the Python loader does). */
 const char *nerf_build_variant(void);
@@ -660,7 +697,8 @@ const char *nerf_build_variant(void);
  * nerf_density_grid_device, nerf_isosurface_grid, nerf_extract_mesh, nerf_extract_mesh_device, nerf_save_ply, nerf_component_filter,
  * nerf_component, nerf_lattice_components, nerf_lattice_components_device, nerf_isosurface_grid_filtered, nerf_extract_mesh_filtered,
  * nerf_extract_mesh_filtered_device, nerf_render_rays, nerf_render_rays_device, nerf_density_gradient_batch,
- * nerf_density_gradient_batch_device, nerf_render_rays_normals, nerf_render_rays_normals_device). */
+ * nerf_density_gradient_batch_device, nerf_render_rays_normals, nerf_render_rays_normals_device, nerf_stage_cert_plan,
+ * nerf_stage_cert_verify, nerf_stage_cert_audit, nerf_stage_prefilter). */
 int nerf_abi_version(void);
 /* sizeof(nerf_camera), sizeof(nerf_render_opts), sizeof(nerf_stats) as this library was built: lets a binding written in
  * another language (the Rust `-sys` crate, ctypes) check its struct mirrors at start-up. */

@@ -157,6 +157,11 @@ PROTOTYPES = {
                                           C.c_float, C.POINTER(C.c_uint8), f32p]),
     "nerf_stage_integrate": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_float, f32p, f32p, f32p, f32p, f32p]),
     "nerf_stage_integrate_rgba8": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_float, f32p, f32p, f32p, f32p, C.c_int, u8p]),
+    "nerf_stage_cert_plan": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.c_uint32,
+                                       C.c_int, C.c_float, C.c_uint32, C.c_uint32, f32p, f32p, i32p, u32p, u32p, u32p, i32p]),
+    "nerf_stage_cert_verify": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_uint32, f32p, i32p, f32p, u32p, u32p, u32p]),
+    "nerf_stage_cert_audit": (C.c_int, [C.c_void_p, u32p, C.c_uint32, C.c_uint32, C.c_size_t, f32p, u32p]),
+    "nerf_stage_prefilter": (C.c_int, [C.c_void_p, C.c_int, C.c_int, f32p, f32p, f32p, C.c_size_t, C.c_int, C.c_float, C.c_float, f32p, u32p]),
 }
 
 

@@ -20,6 +20,7 @@ from ._lib import CCamera, CComponent, CComponentFilter, COpts, CStats, NerfErro
 NET_COARSE, NET_FINE = 0, 1
 MLP_F32, MLP_BF16 = 0, 1
 ALPHA_OPAQUE, ALPHA_PREMULTIPLIED, ALPHA_STRAIGHT = 0, 1, 2
+STAGE_GUARD_WORDS = 64  # NERF_STAGE_GUARD_WORDS
 _ALPHAS = {"opaque": 0, "premultiplied": 1, "straight": 2}
 _DTYPES = {"f32": 0, "float32": 0, 0: 0, "bf16": 1, "bfloat16": 1, 1: 1, "bf16x3": 2, 2: 2, "f16x2": 3, 3: 3}
 
@@ -159,6 +160,60 @@ class Renderer:
         check(self._L.nerf_stage_integrate_rgba8(self.handle, R, n, far, _p(c), _p(s), _p(t), bg, _alpha(alpha),
                                                  out.ctypes.data_as(u8p)), self.handle)
         return out
+
+    # ---- certify_zero's device pieces, one launch each (include/nerf_mi355x.h) ----
+    def stage_cert_plan(self, pre, t, far, margin, depth_limit, audit_mask=127, audit_mask_near=15, audit_salt=0, zero_threshold=None,
+                        list_capacity=None, aux_capacity=None):
+        """k_cert_plan on (R, spr) pre-activations; zero_threshold=None: no back part.  Returns a dict: pre (rewritten), jstar, list (the
+        capacity entries, 0xFFFFFFFF = never written), counts (front, back, aux), aux ((aux_capacity, 2) records), rays_per_wave, and
+        guards = the guard words around list and aux (all still 0xFFFFFFFF unless the kernel wrote out of bounds)."""
+        p = _f32(pre).copy(); tt = _f32(t)
+        R, spr = p.shape
+        cap = R * spr if list_capacity is None else int(list_capacity)
+        acap = R * spr if aux_capacity is None else int(aux_capacity)
+        G = STAGE_GUARD_WORDS
+        lst = np.zeros(cap + 2 * G, np.uint32); aux = np.zeros(2 * acap + 2 * G, np.uint32)
+        js = np.zeros(R, np.int32); cnt = np.zeros(3, np.uint32); rpw = np.zeros(1, np.int32)
+        check(self._L.nerf_stage_cert_plan(self.handle, R, spr, far, margin, depth_limit, audit_mask, audit_mask_near, audit_salt,
+                                           int(zero_threshold is not None), 0.0 if zero_threshold is None else zero_threshold, cap, acap,
+                                           _p(tt), _p(p), js.ctypes.data_as(i32p), lst.ctypes.data_as(u32p), cnt.ctypes.data_as(u32p),
+                                           aux.ctypes.data_as(u32p), rpw.ctypes.data_as(i32p)), self.handle)
+        return {"pre": p, "jstar": js, "list": lst[G:G + cap], "counts": tuple(int(x) for x in cnt), "aux": aux[G:G + 2 * acap].reshape(acap, 2),
+                "rays_per_wave": int(rpw[0]), "guards": np.concatenate([lst[:G], lst[G + cap:], aux[:G], aux[G + 2 * acap:]])}
+
+    def stage_cert_verify(self, sigma, t, far, jstar, list_capacity=None, count=0, fallback_rays=0):
+        """k_cert_verify on (R, spr) exact densities with marks (-1) -> dict: sigma, list, count, fallback_rays, guards."""
+        s = _f32(sigma).copy(); tt = _f32(t)
+        R, spr = s.shape
+        cap = R * spr if list_capacity is None else int(list_capacity)
+        G = STAGE_GUARD_WORDS
+        js = np.ascontiguousarray(jstar, dtype=np.int32)
+        lst = np.zeros(cap + 2 * G, np.uint32); cnt = np.array([count], np.uint32); fb = np.array([fallback_rays], np.uint32)
+        check(self._L.nerf_stage_cert_verify(self.handle, R, spr, far, cap, _p(tt), js.ctypes.data_as(i32p), _p(s), lst.ctypes.data_as(u32p),
+                                             cnt.ctypes.data_as(u32p), fb.ctypes.data_as(u32p)), self.handle)
+        return {"sigma": s, "list": lst[G:G + cap], "count": int(cnt[0]), "fallback_rays": int(fb[0]),
+                "guards": np.concatenate([lst[:G], lst[G + cap:]])}
+
+    def stage_cert_audit(self, aux, sigma, audit=(0, 0, 0, 0), aux_count=None, aux_capacity=None):
+        """k_cert_audit on (n, 2) uint32 records and the flat density buffer -> (sigma, the four audit words)."""
+        a = np.ascontiguousarray(aux, dtype=np.uint32).reshape(-1, 2)
+        s = _f32(sigma).reshape(-1).copy()
+        w = np.array(audit, np.uint32)
+        n = len(a) if aux_count is None else int(aux_count)
+        cap = len(a) if aux_capacity is None else int(aux_capacity)
+        check(self._L.nerf_stage_cert_audit(self.handle, a.ctypes.data_as(u32p), n, cap, s.size, _p(s), w.ctypes.data_as(u32p)), self.handle)
+        return s, w
+
+    def stage_prefilter(self, which, origin, dirs, t, far, f16=True, cut_T=0.0):
+        """The ray-sequential 16-bit pre-filter of network `which` -> (raw pre-activations (R, spr), non-finite tile count)."""
+        o = _f32(origin).reshape(3); d = _f32(dirs).reshape(-1, 3); tt = _f32(t)
+        R, spr = tt.shape
+        if len(d) != R:
+            raise NerfError(-1, "dirs must hold one direction per ray")
+        out = np.empty((R, spr), np.float32); bad = np.zeros(1, np.uint32)
+        check(self._L.nerf_stage_prefilter(self.handle, int(which), int(bool(f16)), _p(o), _p(d), _p(tt), R, spr, far, cut_T, _p(out),
+                                           bad.ctypes.data_as(u32p)), self.handle)
+        return out, int(bad[0])
 
 
 class Network:

@@ -210,6 +210,9 @@ __device__ __forceinline__ void pack_tile(const f32x16 &t, u32x4 &k0, u32x4 &k1)
 struct Heads {
     float alpha[2];  // per sub-tile partial sums over this lane's features
     float rgb[2][3];
+#if NERF_V2_F16
+    uint32_t seen;   // largest |bits| among one pre-ReLU accumulator per layer and column (range_left)
+#endif
 };
 
 // Epilogue of one register pair PR (0..7) of a finished output tile for ONE sub-tile (4 VALU when only converting: two
@@ -222,6 +225,12 @@ __device__ __forceinline__ void convert_half(const f32x16 &acc, u32x4 &na, u32x4
 #endif
     constexpr int r0 = 2 * PR, r1 = 2 * PR + 1;
     const float x0 = acc[r0], x1 = acc[r1];
+#if NERF_V2_F16
+    if constexpr (PR == 0 && NTI == 0) { // one accumulator per layer, column and lane-half: non-finite iff an INPUT of this layer was (range_left)
+        const uint32_t m = __builtin_bit_cast(uint32_t, x0) & 0x7fffffffu;
+        H.seen = m > H.seen ? m : H.seen;
+    }
+#endif
     if constexpr (HEAD == 1 || HEAD == 2) { // alpha = sum_F w[F] relu(h8[F]) in f32 (src/network.rs:216)
         const f32x2 w = *(const LDS_AS f32x2 *)(small + kAlphaWOff + h * 128 + NTI * 16 + r0);
         H.alpha[SUB] = fmaf(w[1], relu(x1), fmaf(w[0], relu(x0), H.alpha[SUB]));
@@ -241,15 +250,22 @@ __device__ __forceinline__ void convert_half(const f32x16 &acc, u32x4 &na, u32x4
     }
 }
 
-// NERF_V2_F16: did the f16 range (65 504) not hold for one of this wave's points?  An activation beyond it is packed as +inf; every pre-activation of the
-// next layer is then +-inf or NaN (inf x w, inf - inf), +inf and NaN survive the ReLU (a signed-integer max), and so on down to the density
-// pre-activation, which comes out non-finite -- unless all 256 features of some layer turned -inf / negative NaN at once.  So nothing is watched in
-// the hot loop: a non-finite density pre-activation marks the tile (and is never certified: k_cert_plan treats it as uncertain).  (wave-uniform)
-__device__ __forceinline__ bool range_left(float pre0, float pre1) {
+// NERF_V2_F16: did the f16 range (65 504) not hold for one of this wave's points?  An activation beyond it is packed as +inf, and the next layer
+// turns it into +-inf (inf x w) or NaN (inf - inf, inf x 0) in EVERY accumulator of that column.  That does NOT reach the density
+// pre-activation by itself: the NaN the MFMA makes carries the sign bit, and the packed ReLU -- a signed-integer max -- sends it to 0 like
+// -inf; a layer whose inputs hold a few +inf comes out all-zero but for the rare +inf, the layers behind it compute finite numbers from
+// their biases and the skip connection, and the pre-activation is finite garbage (lego with dense0 x 2000, dense1 x 50: every point).  So
+// the layer behind the event is watched, where one look suffices: of every layer's first output tile, ONE pre-ReLU accumulator per column and
+// lane-half (convert_half: PR 0 of tile 0; two VALU operations per layer and sub-tile) -- it is non-finite exactly when an input of the layer
+// was.  A tile that saw one, or whose pre-activation is not finite, is marked; its 64 pre-activations leave as NaN (never certified:
+// k_cert_plan treats them as uncertain).  (wave-uniform)
+__device__ __forceinline__ bool range_left(float &pre0, float &pre1, const Heads &H) {
 #if NERF_V2_F16
-    return __any(!(fabsf(pre0) <= 3.0e38f) || !(fabsf(pre1) <= 3.0e38f));
+    const bool left = __any(!(fabsf(pre0) <= 3.0e38f) || !(fabsf(pre1) <= 3.0e38f) || H.seen >= 0x7f800000u);
+    if (left) pre0 = pre1 = __builtin_nanf("");
+    return left;
 #else
-    (void)pre0; (void)pre1;
+    (void)pre0; (void)pre1; (void)H;
     return false;
 #endif
 }
@@ -477,12 +493,15 @@ __global__ __launch_bounds__(256, 1) void V2SYM(nerf_mlp_kernel_bf16v2, nerf_mlp
         Acc C;
         Heads H;
         H.alpha[0] = H.alpha[1] = 0.f;
+#if NERF_V2_F16
+        H.seen = 0u;
+#endif
 #pragma unroll
         for (int c = 0; c < 3; ++c) H.rgb[0][c] = H.rgb[1][c] = 0.f;
 
         trunk_layers<FULL>(E0, E1, X0, X1, Y0, Y1, C, small, H, P, h);
-        const float pre0 = xhalf_sum(H.alpha[0]) + small[kMiscOff + 0], pre1 = xhalf_sum(H.alpha[1]) + small[kMiscOff + 0];
-        if (range_left(pre0, pre1) && A.nonfinite && lane == 0) atomicAdd(A.nonfinite, 1u); // NERF_V2_F16 only: this wave's 64 points cannot be trusted
+        float pre0 = xhalf_sum(H.alpha[0]) + small[kMiscOff + 0], pre1 = xhalf_sum(H.alpha[1]) + small[kMiscOff + 0];
+        if (range_left(pre0, pre1, H) && A.nonfinite && lane == 0) atomicAdd(A.nonfinite, 1u); // NERF_V2_F16 only: this wave's 64 points cannot be trusted
         // raw_pre (zero certification, nerf_render.cpp cert_pass): the pre-activation itself leaves the kernel -- how far below 0 it is decides
         // whether the f32 kernel needs to look at the sample at all
         const float s0 = A.raw_pre ? pre0 : fmaxf(pre0, 0.f); // ReLU(alpha) (src/network.rs:216)
@@ -627,11 +646,14 @@ __global__ __launch_bounds__(256, 1) void V2SYM(nerf_trunk_seq_kernel_bf16, nerf
         Acc C;
         Heads H;
         H.alpha[0] = H.alpha[1] = 0.f;
+#if NERF_V2_F16
+        H.seen = 0u;
+#endif
 #pragma unroll
         for (int c = 0; c < 3; ++c) H.rgb[0][c] = H.rgb[1][c] = 0.f;
         trunk_layers<EXPORT>(E0, E1, X0, X1, Y0, Y1, C, small, H, P, h);
-        const float pre0 = xhalf_sum(H.alpha[0]) + small[kMiscOff + 0], pre1 = xhalf_sum(H.alpha[1]) + small[kMiscOff + 0];
-        if (range_left(pre0, pre1) && A.nonfinite && lane == 0) atomicAdd(A.nonfinite, 1u); // NERF_V2_F16 only
+        float pre0 = xhalf_sum(H.alpha[0]) + small[kMiscOff + 0], pre1 = xhalf_sum(H.alpha[1]) + small[kMiscOff + 0];
+        if (range_left(pre0, pre1, H) && A.nonfinite && lane == 0) atomicAdd(A.nonfinite, 1u); // NERF_V2_F16 only
         if (!EXPORT && A.prefilter) { // wave-uniform
             chunk_finish_prefilter(W0, A, c0, pre0, p, h);
             chunk_finish_prefilter(W1, A, c1, pre1, p, h);
@@ -684,6 +706,9 @@ __global__ __launch_bounds__(256, 1) void nerf_colour_kernel_bf16(const ColourAr
         Acc C;
         Heads H;
         H.alpha[0] = H.alpha[1] = 0.f;
+#if NERF_V2_F16
+        H.seen = 0u;
+#endif
 #pragma unroll
         for (int c = 0; c < 3; ++c) H.rgb[0][c] = H.rgb[1][c] = 0.f;
         const float d0v[3] = {d0x, d0y, d0z}, d1v[3] = {d1x, d1y, d1z};

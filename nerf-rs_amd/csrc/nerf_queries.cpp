@@ -653,4 +653,167 @@ int nerf_stage_integrate_rgba8(nerf_ctx *c, size_t n_rays, int n, float far_, co
     return NERF_OK;
 } NERF_CATCH(c)
 
+// ---- certify_zero's device pieces on caller data (cert_pass's launches, one at a time) ---------------------------------------------
+// A list or aux buffer leaves as the device held it: kStageGuard words in front, the entries, kStageGuard words behind, all of them
+// 0xFFFFFFFF before the launch -- a word the kernel did not write still reads 0xFFFFFFFF, inside the capacity or outside.
+constexpr size_t kStageGuard = NERF_STAGE_GUARD_WORDS;
+
+// what the three list stages refuse without a device, in this order; *n = n_rays * spr
+static int cert_shape_check(nerf_ctx *c, size_t n_rays, int spr, size_t lds_bytes, size_t lds_max, uint32_t list_capacity, size_t *n) {
+    if (spr <= 0) return fail(c, NERF_ERR_INVALID, "spr must be positive");
+    if (lds_bytes > lds_max) return fail(c, NERF_ERR_INVALID, "too many samples per ray");
+    if (n_rays > (size_t)0x7fffffff / (size_t)spr) return fail(c, NERF_ERR_INVALID, "too many samples (a list entry holds 31 index bits)");
+    *n = n_rays * (size_t)spr;
+    if (list_capacity > *n) return fail(c, NERF_ERR_INVALID, "list_capacity exceeds n_rays * spr");
+    return NERF_OK;
+}
+
+static bool low_bit_mask(uint32_t m) { return (m & (m + 1u)) == 0u; } // 2^k - 1
+
+int nerf_stage_cert_plan(nerf_ctx *c, size_t n_rays, int spr, float far_, float margin, float depth_limit, uint32_t audit_mask,
+                         uint32_t audit_mask_near, uint32_t audit_salt, int back_part, float zero_threshold, uint32_t list_capacity,
+                         uint32_t aux_capacity, const float *t, float *pre, int32_t *jstar_out, uint32_t *list_out, uint32_t *counts_out,
+                         uint32_t *aux_out, int32_t *rays_per_wave_out) try {
+    size_t N = 0;
+    int rc, rpw = 0;
+    const size_t lds = spr > 0 ? cert_plan_lds_bytes(spr, &rpw) : 0;
+    if ((rc = cert_shape_check(c, n_rays, spr, lds, (size_t)159 * 1024, list_capacity, &N))) return rc;
+    if (aux_capacity > N) return fail(c, NERF_ERR_INVALID, "aux_capacity exceeds n_rays * spr");
+    if (!(margin >= 0.0f) || !(margin <= 3.0e38f)) return fail(c, NERF_ERR_INVALID, "margin must be finite and >= 0");
+    if (back_part && !(zero_threshold == zero_threshold)) return fail(c, NERF_ERR_INVALID, "zero_threshold is NaN");
+    if (depth_limit != depth_limit) return fail(c, NERF_ERR_INVALID, "depth_limit is NaN");
+    if (!low_bit_mask(audit_mask) || !low_bit_mask(audit_mask_near)) return fail(c, NERF_ERR_INVALID, "an audit mask must be 2^k - 1");
+    if (!t || !pre || !jstar_out || !list_out || !counts_out || !aux_out) return fail(c, NERF_ERR_INVALID, "NULL buffer");
+    if (!c) return fail(nullptr, NERF_ERR_INVALID, "ctx is NULL");
+    if (rays_per_wave_out) *rays_per_wave_out = rpw;
+    counts_out[0] = counts_out[1] = counts_out[2] = 0;
+    const size_t n_list = list_capacity + 2 * kStageGuard, n_aux = 2 * (size_t)aux_capacity + 2 * kStageGuard;
+    memset(list_out, 0xFF, n_list * 4);
+    memset(aux_out, 0xFF, n_aux * 4);
+    if (n_rays == 0) return NERF_OK;
+    DeviceGuard dg(c->device);
+    // scratch (words): pre, t, jstar, three counters (+ 1), guarded list, guarded aux
+    const size_t o_pre = 0, o_t = o_pre + N, o_j = o_t + N, o_cnt = o_j + n_rays, o_list = o_cnt + 4, o_aux = o_list + n_list, total = o_aux + n_aux;
+    if ((rc = ensure_bytes(c, &c->d_scratch, &c->scratch_bytes, total * 4))) return rc;
+    uint32_t *d = (uint32_t *)c->d_scratch;
+    HIP_TRY(c, hipMemcpyAsync(d + o_pre, pre, N * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d + o_t, t, N * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemsetAsync(d + o_j, 0xFF, n_rays * 4, c->stream));
+    HIP_TRY(c, hipMemsetAsync(d + o_cnt, 0, 4 * 4, c->stream));
+    HIP_TRY(c, hipMemsetAsync(d + o_list, 0xFF, (n_list + n_aux) * 4, c->stream));
+    CertPlanArgs q{};
+    q.pre = (float *)(d + o_pre); q.t = (const float *)(d + o_t); q.n_rays = (int)n_rays; q.spr = spr; q.far_ = far_;
+    q.margin = margin; q.depth_limit = depth_limit; q.audit_mask = audit_mask; q.audit_mask_near = audit_mask_near; q.audit_salt = audit_salt;
+    q.list = d + o_list + kStageGuard; q.count = d + o_cnt; q.capacity = list_capacity; q.jstar = (int *)(d + o_j);
+    if (back_part) { q.count_back = d + o_cnt + 1; q.zero_threshold = zero_threshold; }
+    q.aux = d + o_aux + kStageGuard; q.aux_count = d + o_cnt + 2; q.aux_capacity = aux_capacity;
+    HIP_TRY(c, launch_cert_plan(q, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(pre, d + o_pre, N * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(jstar_out, d + o_j, n_rays * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(counts_out, d + o_cnt, 3 * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(list_out, d + o_list, n_list * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(aux_out, d + o_aux, n_aux * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return NERF_OK;
+} NERF_CATCH(c)
+
+int nerf_stage_cert_verify(nerf_ctx *c, size_t n_rays, int spr, float far_, uint32_t list_capacity, const float *t, const int32_t *jstar,
+                           float *sigma, uint32_t *list_out, uint32_t *count, uint32_t *fallback_rays) try {
+    size_t N = 0;
+    int rc;
+    if ((rc = cert_shape_check(c, n_rays, spr, spr > 0 ? (size_t)4 * spr * sizeof(float) : 0, (size_t)160 * 1024, list_capacity, &N))) return rc;
+    if (!t || !jstar || !sigma || !list_out || !count || !fallback_rays) return fail(c, NERF_ERR_INVALID, "NULL buffer");
+    for (size_t r = 0; r < n_rays; ++r)
+        if (jstar[r] < 0 || jstar[r] > spr) return fail(c, NERF_ERR_INVALID, "jstar must lie in [0, spr]");
+    if (!c) return fail(nullptr, NERF_ERR_INVALID, "ctx is NULL");
+    const size_t n_list = list_capacity + 2 * kStageGuard;
+    memset(list_out, 0xFF, n_list * 4);
+    if (n_rays == 0) return NERF_OK;
+    DeviceGuard dg(c->device);
+    // scratch (words): sigma, t, jstar, {count, fall-back rays}, guarded list
+    const size_t o_s = 0, o_t = o_s + N, o_j = o_t + N, o_cnt = o_j + n_rays, o_list = o_cnt + 2, total = o_list + n_list;
+    if ((rc = ensure_bytes(c, &c->d_scratch, &c->scratch_bytes, total * 4))) return rc;
+    uint32_t *d = (uint32_t *)c->d_scratch;
+    const uint32_t cnt[2] = {*count, *fallback_rays};
+    HIP_TRY(c, hipMemcpyAsync(d + o_s, sigma, N * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d + o_t, t, N * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d + o_j, jstar, n_rays * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d + o_cnt, cnt, sizeof cnt, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemsetAsync(d + o_list, 0xFF, n_list * 4, c->stream));
+    CertVerifyArgs v{};
+    v.t = (const float *)(d + o_t); v.sigma = (float *)(d + o_s); v.n_rays = (int)n_rays; v.spr = spr; v.far_ = far_; v.jstar = (const int *)(d + o_j);
+    v.list = d + o_list + kStageGuard; v.count = d + o_cnt; v.capacity = list_capacity; v.fallback_rays = d + o_cnt + 1;
+    HIP_TRY(c, launch_cert_verify(v, c->stream));
+    uint32_t back[2] = {0, 0};
+    HIP_TRY(c, hipMemcpyAsync(sigma, d + o_s, N * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(back, d + o_cnt, sizeof back, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(list_out, d + o_list, n_list * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    *count = back[0]; *fallback_rays = back[1];
+    return NERF_OK;
+} NERF_CATCH(c)
+
+int nerf_stage_cert_audit(nerf_ctx *c, const uint32_t *aux, uint32_t aux_count, uint32_t aux_capacity, size_t n_sigma, float *sigma,
+                          uint32_t *audit) try {
+    const size_t n_rec = std::min(aux_count, aux_capacity);
+    if (n_sigma > (size_t)0x7fffffff) return fail(c, NERF_ERR_INVALID, "too many samples (a list entry holds 31 index bits)");
+    if (!audit || (n_rec && (!aux || !sigma))) return fail(c, NERF_ERR_INVALID, "NULL buffer");
+    for (size_t k = 0; k < n_rec; ++k)
+        if (aux[2 * k] >= n_sigma) return fail(c, NERF_ERR_INVALID, "an aux record names a sample outside sigma");
+    if (!c) return fail(nullptr, NERF_ERR_INVALID, "ctx is NULL");
+    DeviceGuard dg(c->device);
+    // scratch (words): sigma, the records, the count, the four audit words
+    const size_t o_s = 0, o_a = o_s + n_sigma, o_cnt = o_a + 2 * n_rec, o_w = o_cnt + 1, total = o_w + 4;
+    int rc;
+    if ((rc = ensure_bytes(c, &c->d_scratch, &c->scratch_bytes, total * 4))) return rc;
+    uint32_t *d = (uint32_t *)c->d_scratch;
+    if (n_sigma) HIP_TRY(c, hipMemcpyAsync(d + o_s, sigma, n_sigma * 4, hipMemcpyHostToDevice, c->stream));
+    if (n_rec) HIP_TRY(c, hipMemcpyAsync(d + o_a, aux, 2 * n_rec * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d + o_cnt, &aux_count, 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d + o_w, audit, 4 * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, launch_cert_audit(d + o_a, d + o_cnt, aux_capacity, (float *)(d + o_s), d + o_w, c->n_cus, c->stream));
+    if (n_sigma) HIP_TRY(c, hipMemcpyAsync(sigma, d + o_s, n_sigma * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(audit, d + o_w, 4 * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return NERF_OK;
+} NERF_CATCH(c)
+
+int nerf_stage_prefilter(nerf_ctx *c, int which, int f16, const float origin[3], const float *dirs, const float *t, size_t n_rays, int spr,
+                         float far_, float cut_T, float *pre_out, uint32_t *nonfinite_tiles) try {
+    if (which != NERF_NET_COARSE && which != NERF_NET_FINE) return fail(c, NERF_ERR_INVALID, "which must be NERF_NET_COARSE or NERF_NET_FINE");
+    if (spr <= 0) return fail(c, NERF_ERR_INVALID, "spr must be positive");
+    if (n_rays > (size_t)0x7fffffff / (size_t)spr) return fail(c, NERF_ERR_INVALID, "too many samples");
+    if (!(cut_T >= 0.0f) || !(cut_T < 1.0f)) return fail(c, NERF_ERR_INVALID, "cut_T must lie in [0, 1)");
+    if (!origin || !dirs || !t || !pre_out || !nonfinite_tiles) return fail(c, NERF_ERR_INVALID, "NULL buffer");
+    if (!c) return fail(nullptr, NERF_ERR_INVALID, "ctx is NULL");
+    const DevNet &net = c->net[which];
+    if (!net.loaded) return fail(c, NERF_ERR_STATE, "network not loaded");
+    if (f16 && !net.wstream_f16v2) return fail(c, NERF_ERR_STATE, "the f16 pre-filter is unavailable for this network: a weight exceeds the f16 range");
+    *nonfinite_tiles = 0;
+    if (n_rays == 0) return NERF_OK;
+    DeviceGuard dg(c->device);
+    const size_t N = n_rays * (size_t)spr;
+    // scratch (words): directions, t, pre-activations, {ray queue, non-finite tiles, samples evaluated (64 bits)}
+    const size_t o_d = 0, o_t = o_d + 3 * n_rays, o_p = o_t + N, o_cnt = (o_p + N + 1) & ~(size_t)1, total = o_cnt + 4;
+    int rc;
+    if ((rc = ensure_bytes(c, &c->d_scratch, &c->scratch_bytes, total * 4))) return rc;
+    uint32_t *d = (uint32_t *)c->d_scratch;
+    HIP_TRY(c, hipMemcpyAsync(d + o_d, dirs, 3 * n_rays * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d + o_t, t, N * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemsetAsync(d + o_p, 0xFF, N * 4, c->stream)); // NaN = "not evaluated", as cert_pass fills it
+    HIP_TRY(c, hipMemsetAsync(d + o_cnt, 0, 4 * 4, c->stream));
+    SeqArgs q{};
+    q.wstream = f16 ? (const float *)net.wstream_f16v2 : stream_of(net, NERF_MLP_BF16); q.small_params = net.small;
+    q.n_rays = (int)n_rays; q.samples_per_ray = spr; q.ray_dirs = (const float *)(d + o_d); q.t = (const float *)(d + o_t); q.far_ = far_;
+    copy3(q.origin, origin);
+    q.sigma_out = (float *)(d + o_p);
+    q.ray_counter = d + o_cnt; q.nonfinite = d + o_cnt + 1; q.stats = (unsigned long long *)(d + o_cnt + 2);
+    q.prefilter = 1; q.prefilter_cut_T = cut_T;
+    HIP_TRY(c, f16 ? nerf_trunk_seq_f16v2_launch(q, c->n_cus, c->stream) : nerf_trunk_seq_bf16_launch(q, false, c->n_cus, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(pre_out, d + o_p, N * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(nonfinite_tiles, d + o_cnt + 1, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return NERF_OK;
+} NERF_CATCH(c)
+
 } // extern "C"

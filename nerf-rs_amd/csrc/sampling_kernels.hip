@@ -623,7 +623,7 @@ __global__ __launch_bounds__(256) void k_cert_audit(const unsigned *__restrict__
         const float v = sigma[idx];
         ++n_aud;
         if (v <= 0.0f) {
-            const unsigned x = 0x7f800000u - __float_as_uint(-v); // -v >= 0 (or +0 for -0): bits ordered like the floats
+            const unsigned x = 0x7f800000u - __float_as_uint(fabsf(v)); // |v| = -v >= 0, and +0 for BOTH zeros (-(+0) = -0 would wrap): bits ordered like the floats
             best = x > best ? x : best;
         } else ++n_bad; // positive or NaN
         const float err = fabsf(pre_b - v);
