@@ -178,6 +178,12 @@ typedef struct {
  *                           take the same 32-sample segment of four neighbouring rays (whenever the samples per ray are a multiple of 32
  *                           and there are four rays), so that they skip alike and wait less for each other.  Which waves share a
  *                           workgroup changes no value: every output keeps its bits (nerf_debug_ray_grouping shows the mapping).
+ *   NERF_WAVE_TILING=0      a wave of a ray-mode NERF_MLP_F32 launch holds 32 consecutive samples of one ray.  Default, for image renders (whole
+ *                           rows of pixels; caller-supplied ray batches are never tiled) with samples per ray a multiple of 32: a wave holds a few
+ *                           consecutive samples of each ray of a small block of neighbouring pixels (8 x 4 pixels x 1 sample in the density-only
+ *                           sampling launch, 4 x 2 pixels x 4 samples in the launch that produces colours), whose points lie close together and
+ *                           so have more dead hidden units in common for the zero-step skip.  Independent of NERF_RAY_GROUPING; every output
+ *                           keeps its bits (nerf_debug_wave_tiling shows the mapping).
  *   NERF_DEBUG_ZSKIP=1      diagnostic: every f32 MLP launch synchronises and prints its executed / total ReLU k-steps to stderr.
  *   NERF_DEBUG_CLOCK=1      diagnostic: nerf_debug_shader_clock_mhz. */
 int nerf_create(int device_id, nerf_ctx **out);
@@ -235,6 +241,14 @@ int nerf_debug_split_f16x2(const float *values, size_t n, uint16_t *parts /* 2 n
  * the kernel calls.  Grouped (enabled, samples_per_ray a multiple of 32, n_rays >= 4): wave w of tile T = b S + j, S = samples_per_ray / 32,
  * j < S, b < n_rays / 4, holds segment j of ray 4 b + w; the last n_rays % 4 rays and every other launch: slot 128 T + 32 w.  Host-only. */
 int nerf_debug_ray_grouping(int n_rays, int samples_per_ray, int enabled, int32_t *first_slot_of_wave_tile);
+/* Diagnostic: the same for an image pass of `rows` whole rows of rays_per_row rays, lane by lane (see NERF_WAVE_TILING at nerf_create;
+ * ray_grouping, wave_tiling: the context's two switches; full: 1 for a launch that also produces colours, 0 for the density-only sampling
+ * launch -- the two kinds start from different pixel blocks).  For every workgroup tile T, wave w = 0..3 and lane p = 0..31,
+ * slot[(4 T + w) 32 + p] = the sample slot (ray * samples_per_ray + sample, rays row-major) that lane evaluates, or -1 for a padding lane
+ * of the launch's last tile; from the functions the kernel calls.  With wave_tiling = 0, or where a launch is not tiled (samples_per_ray no
+ * multiple of 32, fewer rows than the block is high, no block of 4 pixels whose width divides rays_per_row), it is nerf_debug_ray_grouping's
+ * table spelled out: first slot + p.  Host-only. */
+int nerf_debug_wave_tiling(int rows, int rays_per_row, int samples_per_ray, int full, int ray_grouping, int wave_tiling, int32_t *slot);
 
 /* ---- S2: Network::forward_batch (src/network.rs:197-237) -------------------------------------------------- */
 /* host pointers, synchronous.  n == 0 is a no-op (src/network.rs:199-201).

@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "mlp_layout.h"
+
 enum { MLP_MODE_POINTS = 0, MLP_MODE_RAYS = 1, MLP_MODE_LIST = 2, MLP_MODE_GRID = 3 }; // LIST (f32 and split kernels): ray mode over a device-side list of sample indices (bit 31 of an entry: audited certificate)
 // GRID (f32 sigma-only kernel, nerf_density_grid): the kernel makes its own points, slot i = cell (i % nx, (i / nx) % ny, i / (nx ny)) of a lattice
 
@@ -47,11 +49,13 @@ struct MlpArgs {
     // tile_steps; bit-identical for a network whose parameters are all finite -- DevNet.zero_skip).  0: every k-step is executed.
     int zero_skip;
     unsigned long long *zskip_stats; // optional diagnostic (NERF_DEBUG_ZSKIP): {executed, total} ReLU k-steps of the launch, printed to stderr
-    // f32 kernels, MLP_MODE_RAYS (appended likewise): ray grouping (mlp_layout.h ray_group_first_slot).  The caller sets ray_grouping (the
-    // context's switch, NERF_RAY_GROUPING); nerf_mlp_launch derives the other two from the launch's shape, whatever the caller left in them.
-    int ray_grouping;   // 0: every workgroup tile is 128 consecutive samples
-    int group_segments; // S = samples_per_ray / 32 of a grouped launch, 0 = off
-    int group_tiles;    // workgroup tiles [0, group_tiles) are grouped
+    // f32 kernels, MLP_MODE_RAYS (appended likewise): ray grouping and wave tiling (mlp_layout.h ray_launch_slot).  The caller sets the two
+    // switches (the context's, NERF_RAY_GROUPING / NERF_WAVE_TILING) and, for an image pass, rays_per_row; nerf_mlp_launch derives ray_map from
+    // them and the launch's shape, whatever the caller left in it.
+    int ray_grouping;   // 0: a workgroup tile is four consecutive wave tiles
+    int wave_tiling;    // 0: a wave tile is 32 consecutive samples of one ray
+    int rays_per_row;   // the launch's rays are whole rows of this many pixels; 0: unknown (caller-supplied ray batches), never tiled
+    nerfmlp::RayLaunchMap ray_map;
 };
 
 // Sets the dynamic-LDS attribute of every kernel instantiation on the current device.

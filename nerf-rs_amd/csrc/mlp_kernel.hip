@@ -20,6 +20,9 @@
 //     tile_steps; MlpArgs.zero_skip).
 //   * in ray mode the four waves of a workgroup take the same 32-sample segment of four neighbouring rays (mlp_layout.h ray grouping):
 //     they meet at every chunk's barrier, and rays of like depth have like numbers of dead k-steps.
+//   * in the ray-mode launches of an image pass a wave's 32 points are a few consecutive samples of each ray of a small block of pixels
+//     (mlp_layout.h wave tiling), not 32 samples of one ray: points that lie close together share dead hidden units, so more k-steps are
+//     zero on all of the wave's columns.  Only the slot a lane loads from and stores to changes; nothing enters the MFMA stream.
 // Per 32-point wave tile: at most 8256 MFMAs (full; 9280 before the fold) / 7680 (sigma only) x 64 cycles.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -79,19 +82,24 @@ __global__ __launch_bounds__(256, 1) void nerf_mlp_kernel(const MlpArgs A) {
     const int n_tiles = (n_points + kPointsPerBlock - 1) / kPointsPerBlock;
     // what load_raw fetches: the sigma-only point instance (nerf_density_batch) has no directions to read
     constexpr int LOAD = (!FULL && MODE == MLP_MODE_POINTS) ? 4 : MODE;
-    // first slot of this wave's 32 points in workgroup tile T.  Ray mode: through the ray grouping (mlp_layout.h: the four waves take one
-    // segment of four neighbouring rays; MlpArgs.group_segments == 0: ungrouped); every other mode 128 consecutive slots per workgroup
-    auto first_slot = [&](int T) {
-        return MODE == MLP_MODE_RAYS ? ray_group_first_slot(T, wave, A.group_segments, A.group_tiles) : T * kPointsPerBlock + wave * kPointsPerWave;
+    // slot of this lane's point in workgroup tile T.  Ray mode: through the launch's map (mlp_layout.h ray_launch_slot: wave tiling -- a wave
+    // holds a few samples of each ray of a block of pixels -- and ray grouping -- the four waves take the same stretch of four neighbouring
+    // bundles / rays; MlpArgs.ray_map, all off: 128 consecutive slots); every other mode 128 consecutive slots per workgroup.  The wave-uniform
+    // part (base_of) is scalar work once per tile: formed for the look-ahead, then carried over in a scalar register; the lane's part of a tiled
+    // slot is formed once per kernel, and a tile costs the lanes one select and one add.
+    const int lane_part = (MODE == MLP_MODE_RAYS && A.ray_map.wt.ss) ? wave_tile_lane_part(A.ray_map.wt, p) : p;
+    auto base_of = [&](int T) {
+        return MODE == MLP_MODE_RAYS ? ray_launch_base(A.ray_map, T, wave) : T * kPointsPerBlock + wave * kPointsPerWave;
     };
-    int slot0_next = first_slot(blockIdx.x); // wave-uniform, formed once per tile: for the look-ahead, then carried over
-    RawIn nxt = load_raw_at<LOAD>(A, slot0_next + p); // the next tile's t / direction are loaded one tile ahead
+    auto lane_of = [&](int T) { return (MODE == MLP_MODE_RAYS && ray_launch_tiled(A.ray_map, T)) ? lane_part : p; };
+    int base_next = base_of(blockIdx.x); // wave-uniform
+    RawIn nxt = load_raw_at<LOAD>(A, base_next + lane_of(blockIdx.x)); // the next tile's t / direction are loaded one tile ahead
     for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const int slot = slot0_next + p;
+        const int slot = base_next + lane_of(tile);
         const bool valid = slot < n_points;
-        slot0_next = first_slot(tile + gridDim.x);
+        base_next = base_of(tile + gridDim.x);
         const RawIn in = nxt;
-        nxt = load_raw_at<LOAD>(A, slot0_next + p); // consumed one tile (~250 us) later
+        nxt = load_raw_at<LOAD>(A, base_next + lane_of(tile + gridDim.x)); // consumed one tile (~250 us) later
         float px, py, pz;
         point_of<MODE>(A, in, px, py, pz);
         const float dx = in.dx, dy = in.dy, dz = in.dz;
@@ -220,13 +228,12 @@ hipError_t nerf_mlp_init() {
     return hipSuccess;
 }
 
-// Every ray-mode launch comes through here (plain and skip_empty renders, shared-origin ray batches, coarse and fine passes): the ray
-// grouping of this launch, from its shape and the context's switch (MlpArgs.ray_grouping)
+// Every ray-mode launch comes through here (plain and skip_empty renders, shared-origin ray batches, coarse and fine passes): the wave
+// tiling and ray grouping of this launch, from its shape and the context's switches (MlpArgs.wave_tiling, .ray_grouping).  The pixel block
+// depends on the kind of launch (mlp_layout.h kWaveTileSigma* / kWaveTileFull*); a launch without rays_per_row (a ray batch) is never tiled.
 static hipError_t launch_mlp_rays(const MlpArgs &a, bool full, int n_blocks, hipStream_t stream) {
     MlpArgs g = a;
-    const RayGrouping rg = ray_grouping_of(a.n_points, a.samples_per_ray, a.ray_grouping != 0);
-    g.group_segments = rg.segments;
-    g.group_tiles = rg.group_tiles;
+    g.ray_map = ray_launch_map_of(a.n_points, a.samples_per_ray, a.rays_per_row, full, a.ray_grouping != 0, a.wave_tiling != 0);
     return full ? launch_t<true, MLP_MODE_RAYS>(g, n_blocks, stream) : launch_t<false, MLP_MODE_RAYS>(g, n_blocks, stream);
 }
 

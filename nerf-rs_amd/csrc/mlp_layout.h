@@ -64,6 +64,94 @@ NERF_HOST_DEVICE inline int ray_group_first_slot(int tile, int wave, int segment
     return wave_tile * kPointsPerWave;
 }
 
+// ---- wave tiling (f32 kernels, MLP_MODE_RAYS, image passes): which 32 samples make up a wave tile.  Untiled, a wave holds 32 consecutive
+// samples of one ray -- in the coarse pass half of near..far, over which few hidden units are dead on all 32 columns.  A zero k-step needs one
+// B register = two hidden units dead on ALL of the wave's points (mlp_f32_core.hip.h tile_steps), and neighbouring pixels' rays at the same
+// sample index lie far closer together than 32 samples of one ray do.  Tiled, a wave holds ss consecutive samples of each ray of a tw x th
+// block of pixels (tw th ss = 32).  An image pass is R whole rows of rw rays, spr samples each (slot = ray * spr + sample):
+//   bundle   = a tw x th block of pixels, numbered row-major over the (rw / tw) x (R / th) grid;
+//   wave tile (bundle, j), j < S_t = spr / ss, holds samples j ss .. j ss + ss - 1 of the bundle's tw th rays; lane p = (dy, dx, ds) with
+//              ds = p % ss, dx = (p / ss) % tw, dy = p / (ss tw):
+//              slot = ((by th + dy) rw + bx tw + dx) spr + j ss + ds = [wave-uniform base of the wave tile] + [lane part (dy rw + dx) spr + ds];
+//   workgroup tiles of the tiled region come from ray_group_first_slot with bundle for ray and S_t for S (grouped: wave w of tile b S_t + j takes
+//              wave tile j of bundle 4 b + w; ungrouped: four consecutive wave tiles).  S_t is a multiple of 4: whole 128-point tiles, no padding;
+//   tail     = the last R % th rows, contiguous slots behind the tiled region, keep the untiled mapping (ray grouping of those rows), shifted.
+// Again a permutation of the launch's points, every one evaluated alone in its MFMA column: no value changes.  Outputs go to sigma_out[slot] /
+// rgb_out[3 slot] as before: a cache line of them is now written in parts by several workgroups, which needs no synchronisation -- every byte
+// has exactly one writer, and nothing reads the arrays before the launch ends.
+struct WaveTiling {
+    int ss;            // consecutive samples per ray in a wave; 0 = tiling off (the other fields are then unused)
+    int tw, th;        // pixels per bundle
+    int rw, spr;       // rays per row, samples per ray
+    int bundles_x;     // rw / tw
+    int segments;      // S_t of a grouped launch, 0 = four consecutive wave tiles per workgroup tile
+    int group_tiles;   // workgroup tiles [0, group_tiles) of the tiled region are grouped
+    int tiled_tiles;   // workgroup tiles [0, tiled_tiles) are tiled ...
+    int tiled_points;  // ... and cover slots [0, tiled_points); the tail's slots follow
+};
+// Pixel block a pass kind starts from (tw is halved until it divides rw).  These are the CPU model's best shape per pass (tools/wave_tile_model.py,
+// profiles/wavetile_cpu_model.txt), and each beats the untiled kernel on the device by far more than the launch spread.  They are the
+// only shapes measured on the device so far: the model's other candidates (8x1x4, 4x4x2; 8x4x1 for the full launch) are still to be A/B'd there.
+constexpr int kWaveTileSigmaW = 8, kWaveTileSigmaH = 4; // sigma-only sampling launch: 8 x 4 pixels x 1 sample
+constexpr int kWaveTileFullW = 4, kWaveTileFullH = 2;   // full launch: 4 x 2 pixels x 4 samples
+// on iff allowed, whole 32-sample segments per ray, an image pass (rw > 0 rays per row, whole rows) of at least th rows, and a block of at least 4 pixels
+NERF_HOST_DEVICE inline WaveTiling wave_tiling_of(int n_points, int samples_per_ray, int rw, bool full, bool allowed, bool grouping) {
+    WaveTiling w = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    if (!allowed || rw <= 0 || samples_per_ray <= 0 || samples_per_ray % kPointsPerWave != 0 || n_points <= 0) return w;
+    const int n_rays = n_points / samples_per_ray;
+    if (n_rays % rw != 0 || n_rays * samples_per_ray != n_points) return w;
+    int tw = full ? kWaveTileFullW : kWaveTileSigmaW;
+    const int th = full ? kWaveTileFullH : kWaveTileSigmaH;
+    if (tw <= 0 || th <= 0) return w;
+    while (rw % tw != 0) tw >>= 1;
+    const int rows = n_rays / rw;
+    if (rows < th || tw * th < 4 || kPointsPerWave % (tw * th) != 0) return w;
+    w.ss = kPointsPerWave / (tw * th);
+    w.tw = tw; w.th = th; w.rw = rw; w.spr = samples_per_ray;
+    w.bundles_x = rw / tw;
+    const int s_t = samples_per_ray / w.ss, n_bundles = w.bundles_x * (rows / th);
+    w.tiled_points = (rows / th) * th * rw * samples_per_ray;
+    w.tiled_tiles = w.tiled_points / kPointsPerBlock;
+    if (grouping && n_bundles >= kWavesPerBlock) { w.segments = s_t; w.group_tiles = (n_bundles / kWavesPerBlock) * s_t; }
+    return w;
+}
+// lane p's part of a tiled slot
+NERF_HOST_DEVICE inline int wave_tile_lane_part(const WaveTiling &w, int p) {
+    const int ds = p % w.ss, q = p / w.ss;
+    return ((q / w.tw) * w.rw + q % w.tw) * w.spr + ds;
+}
+// the wave-uniform part of wave `wave` of workgroup tile `tile` < tiled_tiles (two wave-uniform divisions more than ray_group_first_slot)
+NERF_HOST_DEVICE inline int wave_tile_base_slot(const WaveTiling &w, int tile, int wave) {
+    const int s_t = w.spr / w.ss;
+    const int wave_tile = ray_group_first_slot(tile, wave, w.segments, w.group_tiles) / kPointsPerWave;
+    const int bundle = (int)((unsigned)wave_tile / (unsigned)s_t), j = wave_tile - bundle * s_t;
+    const int by = (int)((unsigned)bundle / (unsigned)w.bundles_x), bx = bundle - by * w.bundles_x;
+    return (by * w.th * w.rw + bx * w.tw) * w.spr + j * w.ss;
+}
+// One ray-mode launch's whole mapping: tiled region + tail (the ray grouping of the tail's rays; with tiling off, of the whole launch)
+struct RayLaunchMap {
+    WaveTiling wt;
+    RayGrouping tail;
+};
+NERF_HOST_DEVICE inline RayLaunchMap ray_launch_map_of(int n_points, int samples_per_ray, int rw, bool full, bool grouping, bool tiling) {
+    RayLaunchMap m;
+    m.wt = wave_tiling_of(n_points, samples_per_ray, rw, full, tiling, grouping);
+    m.tail = ray_grouping_of(n_points - (m.wt.ss ? m.wt.tiled_points : 0), samples_per_ray, grouping);
+    return m;
+}
+// slot of lane p (0..31) of wave `wave` of workgroup tile `tile`; lane_part = wave_tile_lane_part(m.wt, p) (anything if tiling is off).
+// May lie at or beyond n_points in the launch's last tile and in the look-ahead tile: the caller clamps / masks as before.
+// The kernel forms the wave-uniform part once per tile (ray_launch_base) and adds the lane's part (tiled: lane_part, else p).
+NERF_HOST_DEVICE inline bool ray_launch_tiled(const RayLaunchMap &m, int tile) { return m.wt.ss != 0 && tile < m.wt.tiled_tiles; }
+NERF_HOST_DEVICE inline int ray_launch_base(const RayLaunchMap &m, int tile, int wave) {
+    if (ray_launch_tiled(m, tile)) return wave_tile_base_slot(m.wt, tile, wave);
+    const int first = m.wt.ss ? m.wt.tiled_tiles : 0, shift = m.wt.ss ? m.wt.tiled_points : 0;
+    return shift + ray_group_first_slot(tile - first, wave, m.tail.segments, m.tail.group_tiles);
+}
+NERF_HOST_DEVICE inline int ray_launch_slot(const RayLaunchMap &m, int tile, int wave, int p, int lane_part) {
+    return ray_launch_base(m, tile, wave) + (ray_launch_tiled(m, tile) ? lane_part : p);
+}
+
 // k-steps per layer (K padded to the 32-slot tiles) and output tiles
 constexpr int kStepsL0 = 32;    // 64 encoding slots (63 used)
 constexpr int kStepsHid = 128;  // 256

@@ -134,6 +134,7 @@ int nerf_create(int device_id, nerf_ctx **out) try {
     if (const char *env = getenv("NERF_DEBUG_NORMALS")) c->debug_normals = atoi(env) > 0;
     if (const char *env = getenv("NERF_ZERO_STEP_SKIP")) c->zero_step_skip = atoi(env) != 0;
     if (const char *env = getenv("NERF_RAY_GROUPING")) c->ray_grouping = atoi(env) != 0;
+    if (const char *env = getenv("NERF_WAVE_TILING")) c->wave_tiling = atoi(env) != 0;
     if (const char *env = getenv("NERF_DEBUG_ZSKIP")) {
         if (atoi(env) > 0 && hipMalloc((void **)&c->d_zskip, 2 * sizeof(unsigned long long)) != hipSuccess) c->d_zskip = nullptr;
     }

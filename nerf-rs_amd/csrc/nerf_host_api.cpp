@@ -182,6 +182,23 @@ int nerf_debug_ray_grouping(int n_rays, int samples_per_ray, int enabled, int32_
     return NERF_OK;
 } NERF_HOST_CATCH
 
+int nerf_debug_wave_tiling(int rows, int rays_per_row, int samples_per_ray, int full, int ray_grouping, int wave_tiling, int32_t *slot) try {
+    using namespace nerfmlp;
+    if (rows <= 0 || rays_per_row <= 0 || samples_per_ray <= 0 || !slot) return fail_noctx(NERF_ERR_INVALID, "rows, rays_per_row and samples_per_ray must be > 0, the table not NULL");
+    const long long n_points = (long long)rows * rays_per_row * samples_per_ray;
+    if (n_points > INT32_MAX - kPointsPerBlock) return fail_noctx(NERF_ERR_INVALID, "too many samples for one launch");
+    const int n = (int)n_points, n_tiles = (n + kPointsPerBlock - 1) / kPointsPerBlock;
+    // as the ray-mode launcher of the f32 kernels (mlp_kernel.hip launch_mlp_rays), then lane by lane as the kernel
+    const RayLaunchMap m = ray_launch_map_of(n, samples_per_ray, rays_per_row, full != 0, ray_grouping != 0, wave_tiling != 0);
+    for (int tile = 0; tile < n_tiles; ++tile)
+        for (int wave = 0; wave < kWavesPerBlock; ++wave)
+            for (int p = 0; p < kPointsPerWave; ++p) {
+                const int s = ray_launch_slot(m, tile, wave, p, m.wt.ss ? wave_tile_lane_part(m.wt, p) : p);
+                slot[((size_t)tile * kWavesPerBlock + wave) * kPointsPerWave + p] = s < n ? s : -1;
+            }
+    return NERF_OK;
+} NERF_HOST_CATCH
+
 int nerf_camera_from_json(const char *path, int width, int height, nerf_camera *out) try {
     if (!path || !out) return fail_noctx(NERF_ERR_INVALID, "NULL argument");
     std::string err;

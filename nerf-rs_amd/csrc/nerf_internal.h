@@ -119,6 +119,7 @@ struct nerf_ctx {
     bool clock_valid = false;
     bool zero_step_skip = true;            // NERF_ZERO_STEP_SKIP=0 at nerf_create: the f32 kernels execute every k-step (networks loaded afterwards)
     bool ray_grouping = true;              // NERF_RAY_GROUPING=0 at nerf_create: ray-mode f32 launches keep 128 consecutive samples per workgroup tile (mlp_layout.h)
+    bool wave_tiling = true;               // NERF_WAVE_TILING=0 at nerf_create: a wave of a ray-mode f32 launch keeps 32 consecutive samples of one ray (mlp_layout.h)
     unsigned long long *d_zskip = nullptr; // diagnostic (NERF_DEBUG_ZSKIP=1): {executed, total} ReLU k-steps of the f32 launch under way
     size_t max_rays_per_pass = (size_t)1 << 20;
     std::vector<hipEvent_t> ev_pool;

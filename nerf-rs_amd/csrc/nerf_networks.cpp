@@ -25,8 +25,12 @@ const float *stream_of(const DevNet &n, int dtype) {
 }
 const float *small_of(const DevNet &n, int dtype) { return dtype == NERF_MLP_F32 ? n.small_f32 : n.small; }
 // zero-step skipping of the f32 kernels (MlpArgs / SeqArgs; the other arithmetics ignore the two fields): per network, decided at load
-// ... and the context's ray grouping (MlpArgs.ray_grouping: the ray-mode launcher of the f32 kernels reads it, nothing else does)
-void zskip_of(const nerf_ctx *c, const DevNet &n, MlpArgs &a) { a.zero_skip = n.zero_skip ? 1 : 0; a.zskip_stats = c->d_zskip; a.ray_grouping = c->ray_grouping ? 1 : 0; }
+// ... and the context's ray grouping and wave tiling (MlpArgs.ray_grouping, .wave_tiling: the ray-mode launcher of the f32 kernels reads
+// them, nothing else does; tiling also needs MlpArgs.rays_per_row, which only an image pass knows: nerf_render.cpp eval_net)
+void zskip_of(const nerf_ctx *c, const DevNet &n, MlpArgs &a) {
+    a.zero_skip = n.zero_skip ? 1 : 0; a.zskip_stats = c->d_zskip;
+    a.ray_grouping = c->ray_grouping ? 1 : 0; a.wave_tiling = c->wave_tiling ? 1 : 0;
+}
 void zskip_of(const nerf_ctx *c, const DevNet &n, SeqArgs &a) { a.zero_skip = n.zero_skip ? 1 : 0; a.zskip_stats = c->d_zskip; }
 
 hipError_t init_mlp_kernels() {

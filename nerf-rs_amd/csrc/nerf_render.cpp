@@ -333,6 +333,7 @@ int eval_net(nerf_ctx *c, const RenderJob &j, const Pass &p, int which, int dt, 
     else { a.mode = MLP_MODE_RAYS; copy3(a.origin, j.origin); }
     a.wstream = stream_of(net, dt); a.small_params = small_of(net, dt); zskip_of(c, net, a);
     a.n_points = p.n_rays * spr; a.samples_per_ray = spr; a.t = t;
+    a.rays_per_row = j.batch ? 0 : p.g.rw; // an image pass is whole rows of the window: the f32 ray-mode launcher may tile its waves over pixel blocks (mlp_layout.h)
     a.sigma_out = sigma_out; a.rgb_out = rgb_out; // the coarse network: sigma only unless its colours are composited (reference discards them, src/lib.rs:404)
     a.skip_empty = j.skip_empty; a.skip_counter = j.skip_empty ? c->d_skip : nullptr; // only full kernels look at it
     a.nonfinite = nonfinite_of(c, dt);
