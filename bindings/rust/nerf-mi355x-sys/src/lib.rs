@@ -243,6 +243,40 @@ extern "C" {
                                            opts: *const nerf_render_opts, background: *const f32, d_rgb_out: *mut f32,
                                            d_depth_out: *mut f32, d_opacity_out: *mut f32, h: f32, d_normals_out: *mut f32,
                                            stream: *mut c_void, stats: *mut nerf_stats) -> c_int;
+    /// Ray clipping (include/nerf_mi355x.h, "ray clipping"): grow an occupancy grid (nerf_density_grid's words) by `radius` cells (1..4,
+    /// Chebyshev); `occ_bits` and `occ_out` must not overlap.  `n_occupied` / `bounds` optional, as nerf_density_grid reports them.
+    pub fn nerf_occupancy_dilate(ctx: *mut nerf_ctx, occ_bits: *const u32, dims: *const i32, radius: c_int, occ_out: *mut u32,
+                                 n_occupied: *mut u64, bounds: *mut i32) -> c_int;
+    pub fn nerf_occupancy_dilate_device(ctx: *mut nerf_ctx, d_occ_bits: *const u32, dims: *const i32, radius: c_int, d_occ_out: *mut u32,
+                                        n_occupied: *mut u64, bounds: *mut i32, stream: *mut c_void) -> c_int;
+    /// Per ray the span {t_first, t_last} of the occupied cells it crosses inside its [near, far] (`bounds_out` n_rays x 2; a miss keeps
+    /// its input bounds) and a 0/1 flag (`hit_out`); `n_hit` optional.  Ray arguments as nerf_render_rays.
+    pub fn nerf_clip_rays(ctx: *mut nerf_ctx, occ_bits: *const u32, lo: *const f32, step: *const f32, dims: *const i32,
+                          origins: *const f32, n_origins: usize, dirs: *const f32, n_rays: usize, normalize: c_int, near: f32, far: f32,
+                          bounds: *const f32, bounds_out: *mut f32, hit_out: *mut u8, n_hit: *mut u64) -> c_int;
+    pub fn nerf_clip_rays_device(ctx: *mut nerf_ctx, d_occ_bits: *const u32, lo: *const f32, step: *const f32, dims: *const i32,
+                                 d_origins: *const f32, n_origins: usize, d_dirs: *const f32, n_rays: usize, normalize: c_int, near: f32,
+                                 far: f32, d_bounds: *const f32, d_bounds_out: *mut f32, d_hit_out: *mut u8, n_hit: *mut u64,
+                                 stream: *mut c_void) -> c_int;
+    /// The same on the CPU, from the function the kernel calls: no context, no device.  `n_refused_reads` (optional): out-of-grid cell
+    /// indices the range check turned away -- 0 unless the walk is wrong.
+    pub fn nerf_debug_clip_rays(occ_bits: *const u32, lo: *const f32, step: *const f32, dims: *const i32, origins: *const f32,
+                                n_origins: usize, dirs: *const f32, n_rays: usize, normalize: c_int, near: f32, far: f32,
+                                bounds: *const f32, bounds_out: *mut f32, hit_out: *mut u8, n_hit: *mut u64,
+                                n_refused_reads: *mut u64) -> c_int;
+    /// Clip, drop the misses, render the rest on the device: a hit ray carries the bits of `nerf_render_rays` for that ray alone with
+    /// the clipped bounds and its own rng index; a missed ray gets the background, depth 0, opacity 0.  `hit_out` / `n_hit` optional.
+    pub fn nerf_render_rays_clipped(ctx: *mut nerf_ctx, occ_bits: *const u32, lo: *const f32, step: *const f32, dims: *const i32,
+                                    origins: *const f32, n_origins: usize, dirs: *const f32, n_rays: usize, normalize: c_int, near: f32,
+                                    far: f32, bounds: *const f32, rng_index: *const u32, opts: *const nerf_render_opts,
+                                    background: *const f32, rgb_out: *mut f32, depth_out: *mut f32, opacity_out: *mut f32,
+                                    hit_out: *mut u8, n_hit: *mut u64, stats: *mut nerf_stats) -> c_int;
+    pub fn nerf_render_rays_clipped_device(ctx: *mut nerf_ctx, d_occ_bits: *const u32, lo: *const f32, step: *const f32, dims: *const i32,
+                                           d_origins: *const f32, n_origins: usize, d_dirs: *const f32, n_rays: usize, normalize: c_int,
+                                           near: f32, far: f32, d_bounds: *const f32, d_rng_index: *const u32,
+                                           opts: *const nerf_render_opts, background: *const f32, d_rgb_out: *mut f32,
+                                           d_depth_out: *mut f32, d_opacity_out: *mut f32, d_hit_out: *mut u8, n_hit: *mut u64,
+                                           stream: *mut c_void, stats: *mut nerf_stats) -> c_int;
     /// render_image over several GPUs: `ctxs[i]` = one context per device, row bands on per-context host threads + streams,
     /// gathered into `rgb_out` by `gather` (NERF_GATHER_*).  The reference's counterpart is the rayon fan-out, src/lib.rs:533-557.
     pub fn nerf_render_image_multi(ctxs: *const *mut nerf_ctx, n: c_int, cam: *const nerf_camera, opts: *const nerf_render_opts,

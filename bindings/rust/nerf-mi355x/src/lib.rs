@@ -331,6 +331,65 @@ impl Gpu {
         })?;
         Ok((rgb, depth, opacity, normals, stats))
     }
+
+    /// Grow the occupancy words of `density_grid` by `radius` cells (1..4, Chebyshev distance; nerf_occupancy_dilate)
+    /// -> (words, occupied cells, inclusive index bounds).
+    pub fn dilate_occupancy(&self, bits: &[u32], dims: [i32; 3], radius: i32) -> Result<(Vec<u32>, u64, [i32; 6]), Error> {
+        let n = dims.iter().map(|&d| d.max(0) as usize).product::<usize>(); // a dim <= 0: the library refuses the call
+        assert!(n == 0 || bits.len() == (n + 31) / 32, "bits.len() must be ceil(n_cells / 32)");
+        let (mut out, mut count, mut bounds) = (vec![0u32; bits.len()], 0u64, [0i32; 6]);
+        check(self.ctx, unsafe {
+            sys::nerf_occupancy_dilate(self.ctx, bits.as_ptr(), dims.as_ptr(), radius, out.as_mut_ptr(), &mut count, bounds.as_mut_ptr())
+        })?;
+        Ok((out, count, bounds))
+    }
+
+    /// Per ray the span of the occupied cells of an occupancy grid (words over the lattice `lo`, `step`, `dims`) inside the ray's
+    /// [near, far] (nerf_clip_rays; ray arguments as `render_rays`) -> (bounds n x 2, hit flags n, number of hits): a hit ray's
+    /// bounds are {t_first, t_last}, ready for `render_rays`; a missed ray keeps its input {near, far}.
+    #[allow(clippy::too_many_arguments, clippy::type_complexity)]
+    pub fn clip_rays(&self, bits: &[u32], lo: [f32; 3], step: [f32; 3], dims: [i32; 3], origins: &[f32], dirs: &[f32], normalize: bool,
+                     near: f32, far: f32, bounds: Option<&[f32]>) -> Result<(Vec<f32>, Vec<u8>, u64), Error> {
+        let n = dirs.len() / 3;
+        let cells = dims.iter().map(|&d| d.max(0) as usize).product::<usize>();
+        assert!(cells == 0 || bits.len() == (cells + 31) / 32, "bits.len() must be ceil(n_cells / 32)");
+        assert_eq!(dirs.len(), 3 * n, "dirs.len() must be 3 * n_rays");
+        assert!(origins.len() == 3 || origins.len() == 3 * n, "origins must hold one origin or one per ray");
+        assert!(bounds.map_or(true, |b| b.len() == 2 * n), "bounds.len() must be 2 * n_rays");
+        let (mut out, mut hit, mut n_hit) = (vec![0f32; 2 * n], vec![0u8; n], 0u64);
+        check(self.ctx, unsafe {
+            sys::nerf_clip_rays(self.ctx, bits.as_ptr(), lo.as_ptr(), step.as_ptr(), dims.as_ptr(), origins.as_ptr(), origins.len() / 3, dirs.as_ptr(), n,
+                                normalize as i32, near, far, bounds.map_or(std::ptr::null(), |b| b.as_ptr()), out.as_mut_ptr(), hit.as_mut_ptr(),
+                                &mut n_hit)
+        })?;
+        Ok((out, hit, n_hit))
+    }
+
+    /// `render_rays` behind `clip_rays`, on the device (nerf_render_rays_clipped): the rays that cross an occupied cell are rendered
+    /// over their clipped bounds -- `render_rays`' bits for those rays alone --, the others get the background, depth 0 and opacity 0.
+    /// -> (rgb n x 3, depth n, opacity n, hit flags n, number of hits, stats of the compacted batch).
+    #[allow(clippy::too_many_arguments, clippy::type_complexity)]
+    pub fn render_rays_clipped(&self, bits: &[u32], lo: [f32; 3], step: [f32; 3], dims: [i32; 3], origins: &[f32], dirs: &[f32], normalize: bool,
+                               near: f32, far: f32, bounds: Option<&[f32]>, rng_index: Option<&[u32]>, opts: &RenderOpts,
+                               background: Option<[f32; 3]>) -> Result<(Vec<f32>, Vec<f32>, Vec<f32>, Vec<u8>, u64, Stats), Error> {
+        let n = dirs.len() / 3;
+        let cells = dims.iter().map(|&d| d.max(0) as usize).product::<usize>();
+        assert!(cells == 0 || bits.len() == (cells + 31) / 32, "bits.len() must be ceil(n_cells / 32)");
+        assert_eq!(dirs.len(), 3 * n, "dirs.len() must be 3 * n_rays");
+        assert!(origins.len() == 3 || origins.len() == 3 * n, "origins must hold one origin or one per ray");
+        assert!(bounds.map_or(true, |b| b.len() == 2 * n), "bounds.len() must be 2 * n_rays");
+        assert!(rng_index.map_or(true, |i| i.len() == n), "rng_index.len() must be n_rays");
+        let (mut rgb, mut depth, mut opacity, mut hit, mut n_hit) = (vec![0f32; 3 * n], vec![0f32; n], vec![0f32; n], vec![0u8; n], 0u64);
+        let mut stats = Stats::default();
+        let bg = background.as_ref().map_or(std::ptr::null(), |b| b.as_ptr());
+        check(self.ctx, unsafe {
+            sys::nerf_render_rays_clipped(self.ctx, bits.as_ptr(), lo.as_ptr(), step.as_ptr(), dims.as_ptr(), origins.as_ptr(), origins.len() / 3,
+                                          dirs.as_ptr(), n, normalize as i32, near, far, bounds.map_or(std::ptr::null(), |b| b.as_ptr()),
+                                          rng_index.map_or(std::ptr::null(), |i| i.as_ptr()), opts, bg, rgb.as_mut_ptr(), depth.as_mut_ptr(),
+                                          opacity.as_mut_ptr(), hit.as_mut_ptr(), &mut n_hit, &mut stats)
+        })?;
+        Ok((rgb, depth, opacity, hit, n_hit, stats))
+    }
 }
 
 impl Drop for Gpu {

@@ -558,6 +558,98 @@ int nerf_render_rays_normals_device(nerf_ctx *ctx, const float *d_origins, size_
                                     float *d_rgb_out, float *d_depth_out, float *d_opacity_out, float h, float *d_normals_out,
                                     void *stream, nerf_stats *stats);
 
+/* ---- ray clipping: per-ray [near, far] from an occupancy grid, on the device -----------------------------------------------------------
+ * nerf_density_grid packs one occupancy bit per lattice cell; nerf_render_rays takes per-ray bounds.  These entry points are the step
+ * between them -- the "occupancy grid -> ray marching bounds" of other NeRF renderers (nerf-rs_amd/csrc/ray_clip_kernels.hip) -- and a render
+ * that drops the rays which meet no occupied cell.  This is NOT a certificate: an occupancy grid says nothing about points that were never
+ * evaluated (a thin structure between lattice points is lost), so the clip is the caller's explicit choice -- threshold and dilation are
+ * the caller's, the clipped bounds are returned, and the render that follows is specified exactly in terms of nerf_render_rays.
+ * Every arithmetic step is f32, rounded once, never contracted; division and sqrt are correctly rounded; fl() marks each rounding.
+ * max(a, b) = a > b ? a : b and min(a, b) = a < b ? a : b (a NaN in a is dropped, one in b is kept).  A host can restate every output
+ * bit for bit (tests/helpers/ray_clip.py does; nerf_debug_clip_rays is the same function the kernel calls, run on the host).
+ * GRID      occupancy words in nerf_density_grid's layout: bit b of word w is cell 32 w + b, the linear cell is ix + dims[0] (iy + dims[1] iz);
+ *           ceil(N / 32) words, N = dims[0] dims[1] dims[2] <= INT32_MAX.
+ * DILATION  nerf_occupancy_dilate: a cell of occ_out is set iff an input cell within Chebyshev distance radius (1..4) of it, inside the
+ *           grid, is set; the bits behind cell N - 1 are 0.  n_occupied and bounds (both optional) as nerf_density_grid reports them.
+ *           occ_bits and occ_out must not overlap.
+ * DIRECTION d = dirs[r], or normalised exactly as nerf_render_rays does (DIRECTION there); [near, far] = bounds[r], or {near_, far_}.
+ * CELLS     cell i is the box centred on lattice point i.  Per axis a:
+ *             G_lo_a = fl(lo_a - fl(0.5 step_a));  G_hi_a = fl(lo_a + fl(step_a fl((float)dims_a - 0.5)))
+ *             plane k: P_a(k) = fl(G_lo_a + fl(step_a (float)k))
+ * SLAB      t_in = near, t_out = far; then per axis a = x, y, z:
+ *             d_a == 0: the ray is a MISS unless G_lo_a <= o_a < G_hi_a; otherwise the axis constrains nothing
+ *             else      inv_a = fl(1 / d_a), ta = fl(fl(G_lo_a - o_a) inv_a), tb = fl(fl(G_hi_a - o_a) inv_a),
+ *                       t_in = max(t_in, min(ta, tb)), t_out = min(t_out, max(ta, tb))
+ *           a MISS unless t_in < t_out.
+ * ENTRY     p_a = fl(o_a + fl(d_a t_in)), q_a = fl(fl(p_a - G_lo_a) / step_a), i_a = clamp(floor(q_a), 0, dims_a - 1); a NaN q_a gives 0
+ *           by an explicit test.
+ * CROSSINGS s_a = sign(d_a) (0 for a NaN).  s_a != 0: tn_a = fl(fl(P_a(i_a + (s_a > 0)) - o_a) inv_a), always recomputed from the plane's
+ *           index, never accumulated; s_a == 0: tn_a = +inf.
+ * WALK      t_cur = t_in; at most dims_x + dims_y + dims_z + 3 rounds of
+ *             1. a* = the lowest axis with the least tn (tn_y replaces tn_x only if tn_y < tn_x, then tn_z likewise); m = tn_a*;
+ *                t_exit = min(m, t_out)
+ *             2. if cell i is occupied and t_exit > t_cur: on the first such cell t_first = t_cur; always t_last = t_exit
+ *             3. stop if t_out <= m
+ *             4. i_a* += s_a*; stop if it leaves [0, dims_a*)
+ *             5. t_cur = max(t_cur, m); tn_a* is recomputed
+ * RESULT    a ray with such a cell is a HIT: bounds_out[r] = {t_first, t_last} (t_first < t_last), hit_out[r] = 1.  A MISS:
+ *           bounds_out[r] = the ray's input {near, far}, hit_out[r] = 0.  n_hit = the sum of the flags.
+ * GUARANTEES the walk ends after the bounded number of rounds whatever the floats are; no cell index outside the grid is ever read (the
+ *           index is range-checked before the word is loaded); a ray's outputs depend on that ray and the grid alone -- a non-finite
+ *           ray has unspecified outputs, for that ray only.  No per-ray host checks.
+ * NERF_ERR_INVALID (checked before the context or the device is needed, "ctx is NULL" last): a NULL occ_bits / lo / step / dims, a
+ *           dim < 1, a non-finite lo, a step that is not finite or <= 0, N > INT32_MAX; n_rays > INT32_MAX; with n_rays > 0 a NULL
+ *           origins / dirs / bounds_out / hit_out; n_origins outside {1, n_rays}; near_ / far_ not finite or far_ <= near_ when bounds is
+ *           NULL.  nerf_occupancy_dilate: a NULL occ_bits / dims / occ_out, a dim < 1, N > INT32_MAX, radius outside 1..4, overlapping
+ *           occ_bits and occ_out.  n_rays == 0 is a no-op (*n_hit = 0).
+ * Host pointers, synchronous; need a context, not a network. */
+int nerf_occupancy_dilate(nerf_ctx *ctx, const uint32_t *occ_bits, const int32_t dims[3], int radius, uint32_t *occ_out,
+                          uint64_t *n_occupied, int32_t bounds[6]);
+/* d_occ_bits / d_occ_out: device pointers; n_occupied / bounds: HOST pointers.  Asynchronous on `stream` unless n_occupied or bounds is
+ * given: then the call synchronises the stream before it returns. */
+int nerf_occupancy_dilate_device(nerf_ctx *ctx, const uint32_t *d_occ_bits, const int32_t dims[3], int radius, uint32_t *d_occ_out,
+                                 uint64_t *n_occupied, int32_t bounds[6], void *stream);
+int nerf_clip_rays(nerf_ctx *ctx, const uint32_t *occ_bits, const float lo[3], const float step[3], const int32_t dims[3],
+                   const float *origins /* n_origins x 3 */, size_t n_origins /* 1 or n_rays */, const float *dirs /* n_rays x 3 */,
+                   size_t n_rays, int normalize, float near_, float far_, const float *bounds /* n_rays x 2 or NULL */,
+                   float *bounds_out /* n_rays x 2 */, uint8_t *hit_out /* n_rays */, uint64_t *n_hit /* may be NULL */);
+/* occ_bits, origins, dirs, bounds and the two outputs are DEVICE pointers; n_hit is a HOST pointer: asynchronous on `stream` unless it
+ * is given -- then the call synchronises the stream before it returns. */
+int nerf_clip_rays_device(nerf_ctx *ctx, const uint32_t *d_occ_bits, const float lo[3], const float step[3], const int32_t dims[3],
+                          const float *d_origins, size_t n_origins, const float *d_dirs, size_t n_rays, int normalize, float near_,
+                          float far_, const float *d_bounds, float *d_bounds_out, uint8_t *d_hit_out, uint64_t *n_hit, void *stream);
+/* Diagnostic: nerf_clip_rays on the CPU, from the function the kernel calls -- no context, no device.  Same arguments (host pointers) and
+ * refusals; n_refused_reads (optional) = cell indices outside the grid that the range check in front of the word load turned away,
+ * summed over the rays: 0 unless the walk is wrong.  Host-only. */
+int nerf_debug_clip_rays(const uint32_t *occ_bits, const float lo[3], const float step[3], const int32_t dims[3], const float *origins,
+                         size_t n_origins, const float *dirs, size_t n_rays, int normalize, float near_, float far_, const float *bounds,
+                         float *bounds_out, uint8_t *hit_out, uint64_t *n_hit, uint64_t *n_refused_reads);
+/* Clip, drop the misses, render the rest -- all on the device: nerf_clip_rays; the hit rays compacted in ascending ray order (prefix sums:
+ * the same bits in every run); nerf_render_rays' pipeline on the compacted batch; the results scattered back.
+ *   HIT ray r   rgb / depth / opacity = exactly the bits nerf_render_rays returns for that ray alone with bounds = {t_first, t_last} of
+ *               nerf_clip_rays and rng_index = index_r (rng_index[r], or r when rng_index is NULL).
+ *   MISSED ray  rgb = background (NULL = white), depth 0, opacity 0: what the compositing arithmetic gives an empty ray.
+ * hit_out (n_rays bytes) and n_hit are optional.  The hit count comes back to the host once to size the batch (one stream
+ * synchronisation); n_hit == 0 launches nothing after the clip.  Every argument, refusal and per-ray host check of nerf_render_rays
+ * applies unchanged, then the grid's refusals above.  nerf_stats is filled as for the compacted batch (n_rays = n_hit; all zero when
+ * nothing was hit).  Workspace: at most 72 bytes per ray in the context, grown on demand -- a warm call allocates nothing.  Normals are not
+ * offered here.  Host pointers, synchronous. */
+int nerf_render_rays_clipped(nerf_ctx *ctx, const uint32_t *occ_bits, const float lo[3], const float step[3], const int32_t dims[3],
+                             const float *origins /* n_origins x 3 */, size_t n_origins /* 1 or n_rays */,
+                             const float *dirs /* n_rays x 3 */, size_t n_rays, int normalize, float near_, float far_,
+                             const float *bounds /* n_rays x 2 or NULL */, const uint32_t *rng_index /* n_rays or NULL */,
+                             const nerf_render_opts *opts, const float background[3] /* NULL = white */,
+                             float *rgb_out /* n_rays x 3 */, float *depth_out /* n_rays or NULL */, float *opacity_out /* n_rays or NULL */,
+                             uint8_t *hit_out /* n_rays or NULL */, uint64_t *n_hit /* may be NULL */, nerf_stats *stats /* may be NULL */);
+/* device pointers but for lo, step, dims, opts, background, n_hit and stats; synchronises `stream` once, after the clip, to read the hit
+ * count (and the shared origin when n_origins == 1); what follows is asynchronous unless stats != NULL. */
+int nerf_render_rays_clipped_device(nerf_ctx *ctx, const uint32_t *d_occ_bits, const float lo[3], const float step[3], const int32_t dims[3],
+                                    const float *d_origins, size_t n_origins, const float *d_dirs, size_t n_rays, int normalize,
+                                    float near_, float far_, const float *d_bounds, const uint32_t *d_rng_index,
+                                    const nerf_render_opts *opts, const float background[3],
+                                    float *d_rgb_out, float *d_depth_out, float *d_opacity_out, uint8_t *d_hit_out, uint64_t *n_hit,
+                                    void *stream, nerf_stats *stats);
+
 /* ---- S3 over several GPUs of one node (reference: the rayon fan-out over blocks + scatter, src/lib.rs:533-557) ------
  * ctxs[i] is one context per device (nerf_create / nerf_create_multi), each with both networks loaded (weights are
  * replicated).  Context i renders band i of n of the output rows (nerf_render_opts.band_*, set here: the caller's values are
@@ -712,7 +804,8 @@ const char *nerf_build_variant(void);
  * nerf_component, nerf_lattice_components, nerf_lattice_components_device, nerf_isosurface_grid_filtered, nerf_extract_mesh_filtered,
  * nerf_extract_mesh_filtered_device, nerf_render_rays, nerf_render_rays_device, nerf_density_gradient_batch,
  * nerf_density_gradient_batch_device, nerf_render_rays_normals, nerf_render_rays_normals_device, nerf_stage_cert_plan,
- * nerf_stage_cert_verify, nerf_stage_cert_audit, nerf_stage_prefilter). */
+ * nerf_stage_cert_verify, nerf_stage_cert_audit, nerf_stage_prefilter, nerf_occupancy_dilate, nerf_occupancy_dilate_device, nerf_clip_rays,
+ * nerf_clip_rays_device, nerf_debug_clip_rays, nerf_render_rays_clipped, nerf_render_rays_clipped_device). */
 int nerf_abi_version(void);
 /* sizeof(nerf_camera), sizeof(nerf_render_opts), sizeof(nerf_stats) as this library was built: lets a binding written in
  * another language (the Rust `-sys` crate, ctypes) check its struct mirrors at start-up. */

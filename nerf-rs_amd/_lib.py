@@ -135,6 +135,19 @@ PROTOTYPES = {
     "nerf_render_rays_normals_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_float,
                                                   C.c_void_p, C.c_void_p, C.POINTER(COpts), f32p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
                                                   C.c_void_p, C.c_void_p, C.POINTER(CStats)]),
+    "nerf_occupancy_dilate": (C.c_int, [C.c_void_p, u32p, i32p, C.c_int, u32p, C.POINTER(C.c_uint64), i32p]),
+    "nerf_occupancy_dilate_device": (C.c_int, [C.c_void_p, C.c_void_p, i32p, C.c_int, C.c_void_p, C.POINTER(C.c_uint64), i32p, C.c_void_p]),
+    "nerf_clip_rays": (C.c_int, [C.c_void_p, u32p, f32p, f32p, i32p, f32p, C.c_size_t, f32p, C.c_size_t, C.c_int, C.c_float, C.c_float, f32p,
+                                 f32p, u8p, C.POINTER(C.c_uint64)]),
+    "nerf_clip_rays_device": (C.c_int, [C.c_void_p, C.c_void_p, f32p, f32p, i32p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int,
+                                        C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]),
+    "nerf_debug_clip_rays": (C.c_int, [u32p, f32p, f32p, i32p, f32p, C.c_size_t, f32p, C.c_size_t, C.c_int, C.c_float, C.c_float, f32p,
+                                       f32p, u8p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "nerf_render_rays_clipped": (C.c_int, [C.c_void_p, u32p, f32p, f32p, i32p, f32p, C.c_size_t, f32p, C.c_size_t, C.c_int, C.c_float, C.c_float,
+                                           f32p, u32p, C.POINTER(COpts), f32p, f32p, f32p, f32p, u8p, C.POINTER(C.c_uint64), C.POINTER(CStats)]),
+    "nerf_render_rays_clipped_device": (C.c_int, [C.c_void_p, C.c_void_p, f32p, f32p, i32p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int,
+                                                  C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(COpts), f32p, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p, C.POINTER(CStats)]),
     "nerf_create_multi": (C.c_int, [C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p)]),
     "nerf_multi_release": (None, []),
     "nerf_band_rows": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),

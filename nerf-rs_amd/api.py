@@ -744,6 +744,152 @@ def render_rays_device(coarse, fine, d_origins, n_origins, d_dirs, n_rays, near,
     return Stats(st) if return_stats else None
 
 
+def _occupancy_args(bits, dims):
+    d = np.asarray(dims)
+    if d.size != 3 or np.any(d != np.floor(d)) or np.any(np.abs(d) >= 2 ** 31):
+        raise NerfError(-1, "dims must be three integers")
+    dims_c = np.ascontiguousarray(d.reshape(-1), dtype=np.int32)
+    n = int(np.prod(dims_c.astype(np.int64))) if np.all(dims_c > 0) else 0     # a dim <= 0: the library refuses the call
+    words = np.ascontiguousarray(bits, dtype=np.uint32).reshape(-1)
+    if n > 0 and words.size != (n + 31) // 32:
+        raise NerfError(-1, "bits must hold ceil(nx * ny * nz / 32) words")
+    return words, dims_c, n
+
+
+def dilate_occupancy(renderer, bits, dims, radius, return_stats=False):
+    """Grow the occupancy words of density_grid by `radius` cells (1..4, Chebyshev distance: a cell is set iff a set cell lies within
+    `radius` of it along every axis) -> words of the same layout (nerf_occupancy_dilate); return_stats: (words, count, bounds) as
+    density_grid reports them."""
+    words, dims_c, n = _occupancy_args(bits, dims)
+    out = np.zeros(words.size, np.uint32)
+    cnt, bounds = C.c_uint64(0), np.zeros(6, np.int32)
+    check(renderer._L.nerf_occupancy_dilate(renderer.handle, words.ctypes.data_as(u32p), dims_c.ctypes.data_as(i32p), int(radius),
+                                            out.ctypes.data_as(u32p), C.byref(cnt) if return_stats else None,
+                                            bounds.ctypes.data_as(i32p) if return_stats else None), renderer.handle)
+    return (out, int(cnt.value), tuple(int(v) for v in bounds)) if return_stats else out
+
+
+def dilate_occupancy_device(renderer, d_bits, dims, radius, d_out, want_stats=False, stream=0):
+    """nerf_occupancy_dilate_device: raw device pointers (ints), asynchronous on `stream`; want_stats synchronises it and returns
+    (count, bounds), else None."""
+    dims_c = np.ascontiguousarray(np.asarray(dims).reshape(-1), dtype=np.int32)
+    cnt, bounds = C.c_uint64(0), np.zeros(6, np.int32)
+    check(renderer._L.nerf_occupancy_dilate_device(renderer.handle, d_bits, dims_c.ctypes.data_as(i32p), int(radius), d_out,
+                                                   C.byref(cnt) if want_stats else None, bounds.ctypes.data_as(i32p) if want_stats else None,
+                                                   stream), renderer.handle)
+    return (int(cnt.value), tuple(int(v) for v in bounds)) if want_stats else None
+
+
+def _clip_ray_args(origins, dirs, bounds):
+    d = _f32(dirs)
+    if d.ndim != 2 or d.shape[1] != 3:
+        raise NerfError(-1, "dirs must be an (n, 3) array")
+    n = d.shape[0]
+    o = _f32(origins)
+    if o.shape not in ((3,), (n, 3)):
+        raise NerfError(-1, "origins must have shape (3,) or (n, 3)")
+    b = None if bounds is None else _f32(bounds)
+    if b is not None and b.shape != (n, 2):
+        raise NerfError(-1, "bounds must be an (n, 2) array of (near, far)")
+    return o, d, b, n
+
+
+def clip_rays(renderer, bits, lo, step, dims, origins, dirs, near, far, bounds=None, normalize=True, return_count=False, debug_cpu=False):
+    """Per ray the span of the occupied cells of a density_grid occupancy (bits over the lattice lo, step, dims) inside the ray's
+    [near, far] (nerf_clip_rays) -> (bounds (n, 2) float32, hit (n,) bool): a hit ray's bounds are (t_first, t_last), to be handed to
+    render_rays(bounds=...); a missed ray keeps its input (near, far).  origins, dirs, near, far, bounds, normalize as in render_rays.
+    return_count: the number of hits follows.  debug_cpu=True runs the same function on the host (nerf_debug_clip_rays; renderer may
+    be None) and appends the number of out-of-grid reads the range check refused (always 0)."""
+    words, dims_c, _ = _occupancy_args(bits, dims)
+    lo_c, step_c = _f32(lo).reshape(-1), _f32(step).reshape(-1)
+    if lo_c.size != 3 or step_c.size != 3:
+        raise NerfError(-1, "lo and step must have three entries each")
+    o, d, b, n = _clip_ray_args(origins, dirs, bounds)
+    out, hit = np.empty((n, 2), np.float32), np.empty(n, np.uint8)
+    cnt, refused = C.c_uint64(0), C.c_uint64(0)
+    tail = (words.ctypes.data_as(u32p), _p(lo_c), _p(step_c), dims_c.ctypes.data_as(i32p), _p(o), 1 if o.ndim == 1 else n, _p(d), n,
+            int(bool(normalize)), float(near), float(far), None if b is None else _p(b), _p(out), hit.ctypes.data_as(u8p), C.byref(cnt))
+    if debug_cpu:
+        check(_lib.load_library().nerf_debug_clip_rays(*tail, C.byref(refused)))
+    else:
+        check(renderer._L.nerf_clip_rays(renderer.handle, *tail), renderer.handle)
+    res = (out, hit.astype(bool))
+    if return_count:
+        res += (int(cnt.value),)
+    if debug_cpu:
+        res += (int(refused.value),)
+    return res
+
+
+def clip_rays_device(renderer, d_bits, lo, step, dims, d_origins, n_origins, d_dirs, n_rays, near, far, d_bounds_out, d_hit_out, *,
+                     d_bounds=None, normalize=True, want_count=False, stream=0):
+    """nerf_clip_rays_device: raw device pointers (ints; d_bounds may be None), asynchronous on `stream`; want_count synchronises it
+    and returns the number of hits, else None."""
+    lo_c, step_c, dims_c, _ = _grid_args(lo, step, dims)
+    cnt = C.c_uint64(0)
+    check(renderer._L.nerf_clip_rays_device(renderer.handle, d_bits, _p(lo_c), _p(step_c), dims_c.ctypes.data_as(i32p), d_origins, int(n_origins),
+                                            d_dirs, int(n_rays), int(bool(normalize)), float(near), float(far), d_bounds, d_bounds_out, d_hit_out,
+                                            C.byref(cnt) if want_count else None, stream), renderer.handle)
+    return int(cnt.value) if want_count else None
+
+
+def render_rays_clipped(coarse, fine, bits, lo, step, dims, origins, dirs, near, far, fine_samples_per_ray=128, *, n_coarse=64, bounds=None,
+                        normalize=True, rng_index=None, seed=0, coarse_only=False, dtype="f32", background=None, aux=False,
+                        return_hit=False, return_stats=False):
+    """render_rays behind clip_rays, on the device (nerf_render_rays_clipped): the rays that cross an occupied cell of the grid are
+    rendered over their clipped bounds -- the bits of render_rays for those rays alone with bounds = clip_rays' and rng_index = their
+    own index --, the others get the background, depth 0 and opacity 0 without a network evaluation.  Arguments as render_rays plus
+    the grid (bits, lo, step, dims as density_grid / dilate_occupancy give them).  return_hit: hit (n,) bool and the number of hits
+    follow the arrays; the stats (those of the compacted batch: n_rays = hits) follow if return_stats."""
+    R = coarse.renderer
+    if fine is not None and fine.renderer is not R:
+        raise NerfError(-1, "coarse and fine networks must live in the same Renderer")
+    words, dims_c, _ = _occupancy_args(bits, dims)
+    lo_c, step_c = _f32(lo).reshape(-1), _f32(step).reshape(-1)
+    if lo_c.size != 3 or step_c.size != 3:
+        raise NerfError(-1, "lo and step must have three entries each")
+    o, d, b, n = _clip_ray_args(origins, dirs, bounds)
+    idx = None if rng_index is None else np.ascontiguousarray(rng_index, dtype=np.uint32)
+    if idx is not None and idx.shape != (n,):
+        raise NerfError(-1, "rng_index must have one entry per ray")
+    opts = _ray_opts(n_coarse, fine_samples_per_ray, seed, coarse_only, dtype)
+    keep, bg = _background(background)
+    rgb = np.empty((n, 3), np.float32)
+    depth, opacity = (np.empty(n, np.float32), np.empty(n, np.float32)) if aux else (None, None)
+    hit, cnt, st = np.empty(n, np.uint8), C.c_uint64(0), CStats()
+    check(R._L.nerf_render_rays_clipped(R.handle, words.ctypes.data_as(u32p), _p(lo_c), _p(step_c), dims_c.ctypes.data_as(i32p), _p(o),
+                                        1 if o.ndim == 1 else n, _p(d), n, int(bool(normalize)), float(near), float(far),
+                                        None if b is None else _p(b), None if idx is None else idx.ctypes.data_as(u32p), C.byref(opts), bg,
+                                        _p(rgb), None if depth is None else _p(depth), None if opacity is None else _p(opacity),
+                                        hit.ctypes.data_as(u8p), C.byref(cnt), C.byref(st)), R.handle)
+    out = (rgb, depth, opacity) if aux else (rgb,)
+    if return_hit:
+        out += (hit.astype(bool), int(cnt.value))
+    if return_stats:
+        out += (Stats(st),)
+    return out if len(out) > 1 else out[0]
+
+
+def render_rays_clipped_device(coarse, fine, d_bits, lo, step, dims, d_origins, n_origins, d_dirs, n_rays, near, far, fine_samples_per_ray,
+                               d_rgb, *, n_coarse=64, d_bounds=None, normalize=True, d_rng_index=None, seed=0, coarse_only=False, dtype="f32",
+                               background=None, d_depth=None, d_opacity=None, d_hit=None, stream=0, return_stats=False):
+    """nerf_render_rays_clipped_device: raw device pointers (ints; d_bounds, d_rng_index, d_depth, d_opacity, d_hit may be None).
+    Synchronises `stream` once after the clip (the hit count sizes the render); what follows is asynchronous unless return_stats.
+    Returns the number of hits, or (hits, stats)."""
+    R = coarse.renderer
+    if fine is not None and fine.renderer is not R:
+        raise NerfError(-1, "coarse and fine networks must live in the same Renderer")
+    lo_c, step_c, dims_c, _ = _grid_args(lo, step, dims)
+    opts = _ray_opts(n_coarse, fine_samples_per_ray, seed, coarse_only, dtype)
+    keep, bg = _background(background)
+    cnt, st = C.c_uint64(0), CStats()
+    check(R._L.nerf_render_rays_clipped_device(R.handle, d_bits, _p(lo_c), _p(step_c), dims_c.ctypes.data_as(i32p), d_origins, int(n_origins),
+                                               d_dirs, int(n_rays), int(bool(normalize)), float(near), float(far), d_bounds, d_rng_index,
+                                               C.byref(opts), bg, d_rgb, d_depth, d_opacity, d_hit, C.byref(cnt), stream,
+                                               C.byref(st) if return_stats else None), R.handle)
+    return (int(cnt.value), Stats(st)) if return_stats else int(cnt.value)
+
+
 def render_image_normals(coarse, fine, camera, fine_samples_per_ray=128, *, h, seed=0, coarse_only=False, crop=None, dtype="f32",
                          background=None, return_stats=False):
     """A camera's window with a normal map -> (rgb (h, w, 3), depth (h, w), opacity (h, w), normals (h, w, 3)) float32.

@@ -17,6 +17,9 @@
 // --rays-normals FILE beside --rays-out adds n x 3 f32 per-ray normals (nerf_render_rays_normals; --normals-step H, default 1e-3, is the
 // central-difference step).  --normals FILE.ppm writes the normal map of the image run, encoded 0.5 n + 0.5 per component: the window's rays
 // (nerf_stage_ray_dirs, rng_index = row * nx + col) go through nerf_render_rays_normals once more on the first context.
+// --rays-occupancy FILE.bits beside --rays clips the rays to the occupied cells of an occupancy grid first (nerf_render_rays_clipped): FILE holds the
+// words --grid-occupancy wrote for the lattice that --density-grid / --grid-lo / --grid-step name (no grid output flag is then needed);
+// --occupancy-dilate R (1..4) grows it by R cells first (nerf_occupancy_dilate).  Rays that cross no occupied cell get the background.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -37,8 +40,9 @@ static void usage(const char *argv0) {
             "           [--grid-out FILE.raw] [--grid-occupancy FILE.bits] [--mesh FILE.ply [--mesh-iso V] [--mesh-colour]\n"
             "            [--mesh-keep-largest K] [--mesh-min-points M]]]\n"
             "           (at least one of the three files; no image flag: no render)\n"
-            "          [--rays FILE.f32 --rays-out FILE.f32 [--rays-bounds FILE.f32] [--rays-normals FILE.f32]]\n"
-            "           (n x 6 f32 in, n x 3 f32 out; no image flag: no render)\n"
+            "          [--rays FILE.f32 --rays-out FILE.f32 [--rays-bounds FILE.f32] [--rays-normals FILE.f32]\n"
+            "           [--rays-occupancy FILE.bits --density-grid NX,NY,NZ --grid-lo X,Y,Z --grid-step SX,SY,SZ [--occupancy-dilate R]]]\n"
+            "           (n x 6 f32 in, n x 3 f32 out; no image flag: no render; --rays-occupancy: clip the rays to the grid's occupied cells first)\n"
             "          [--normals FILE.ppm] [--normals-step H]   (normal map of the image run, 0.5 n + 0.5; H: central-difference step, default 1e-3)\n"
             "defaults: --scene lego_rust --width 256 --height 256 --coarse 64 --fine 128 --out output.ppm --mesh-iso 10\n",
             argv0);
@@ -47,7 +51,8 @@ static void usage(const char *argv0) {
 int main(int argc, char **argv) {
     std::string scene = getenv("NERF_SCENE_DIR") ? getenv("NERF_SCENE_DIR") : "lego_rust";
     std::string out = "output.ppm", depth_path, opacity_path, rgba_path;
-    std::string grid_out, grid_bits_path, mesh_path, rays_path, rays_out_path, rays_bounds_path, rays_normals_path, normals_path;
+    std::string grid_out, grid_bits_path, mesh_path, rays_path, rays_out_path, rays_bounds_path, rays_normals_path, normals_path, rays_occ_path;
+    int occ_dilate = 0;
     float normals_step = 1e-3f;
     float mesh_iso = 10.0f;
     bool mesh_colour = false, have_mesh_opt = false;
@@ -108,6 +113,8 @@ int main(int argc, char **argv) {
         else if (a == "--rays-out") rays_out_path = next();
         else if (a == "--rays-bounds") rays_bounds_path = next();
         else if (a == "--rays-normals") rays_normals_path = next();
+        else if (a == "--rays-occupancy") rays_occ_path = next();
+        else if (a == "--occupancy-dilate") occ_dilate = atoi(next());
         else if (a == "--normals") { normals_path = next(); want_image = true; }
         else if (a == "--normals-step") normals_step = strtof(next(), nullptr);
         else if (a == "--mesh-iso") { mesh_iso = strtof(next(), nullptr); have_mesh_opt = true; }
@@ -128,7 +135,11 @@ int main(int argc, char **argv) {
         } else { usage(argv[0]); return a == "--help" || a == "-h" ? 0 : 2; }
     }
 
-    if (want_grid && (!have_grid_lo || !have_grid_step || (grid_out.empty() && grid_bits_path.empty() && mesh_path.empty()))) { usage(argv[0]); return 2; }
+    const bool grid_files = !(grid_out.empty() && grid_bits_path.empty() && mesh_path.empty());
+    if (want_grid && (!have_grid_lo || !have_grid_step || (!grid_files && rays_occ_path.empty()))) { usage(argv[0]); return 2; }
+    // --rays-occupancy: the lattice flags describe the file's grid; it goes with --rays, not with normals; --occupancy-dilate goes with it
+    if (!rays_occ_path.empty() && (rays_path.empty() || !want_grid || !rays_normals_path.empty())) { usage(argv[0]); return 2; }
+    if (occ_dilate != 0 && (rays_occ_path.empty() || occ_dilate < 1 || occ_dilate > 4)) { usage(argv[0]); return 2; }
     if (!want_grid && (have_grid_lo || have_grid_step || !grid_out.empty() || !grid_bits_path.empty() || !mesh_path.empty())) { usage(argv[0]); return 2; }
     if (mesh_path.empty() && have_mesh_opt) { usage(argv[0]); return 2; }
     if (rays_path.empty() != rays_out_path.empty() || (rays_path.empty() && !(rays_bounds_path.empty() && rays_normals_path.empty()))) { usage(argv[0]); return 2; }
@@ -169,7 +180,29 @@ int main(int argc, char **argv) {
             for (int k = 0; k < 3; ++k) { o[3 * r + k] = rays[6 * r + k]; d[3 * r + k] = rays[6 * r + 3 + k]; }
         nerf_stats rst;
         const float *rb = ray_bounds.empty() ? nullptr : ray_bounds.data(), *bg = have_background ? background : nullptr;
-        if (normals.empty() ? nerf_render_rays(ctx, o.data(), n, d.data(), n, 1, jc.near_, jc.far_, rb, nullptr, &opts, bg, rgb.data(), nullptr, nullptr, &rst)
+        uint64_t n_hit = 0;
+        std::vector<uint32_t> occ;
+        if (!rays_occ_path.empty()) { // the occupancy words of the lattice the grid flags name, grown on request
+            const bool ok_dims = grid_dims[0] > 0 && grid_dims[1] > 0 && grid_dims[2] > 0;
+            const unsigned long long cells = ok_dims ? (unsigned long long)grid_dims[0] * (unsigned long long)grid_dims[1] * (unsigned long long)grid_dims[2] : 0;
+            if (!ok_dims || cells > 0x7fffffffull) { fprintf(stderr, "error: --density-grid must name at most 2^31 - 1 cells\n"); return 1; }
+            FILE *f = fopen(rays_occ_path.c_str(), "rb");
+            occ.resize((size_t)((cells + 31) / 32));
+            const bool ok = f && fread(occ.data(), sizeof(uint32_t), occ.size(), f) == occ.size() && fgetc(f) == EOF;
+            if (f) fclose(f);
+            if (!ok) {
+                fprintf(stderr, "error: %s must hold the %zu occupancy words of a %d x %d x %d grid\n", rays_occ_path.c_str(), occ.size(), grid_dims[0], grid_dims[1], grid_dims[2]);
+                return 1;
+            }
+            if (occ_dilate) {
+                std::vector<uint32_t> grown(occ.size());
+                if (nerf_occupancy_dilate(ctx, occ.data(), grid_dims, occ_dilate, grown.data(), nullptr, nullptr)) { fprintf(stderr, "error: %s\n", nerf_last_error(ctx)); return 1; }
+                occ.swap(grown);
+            }
+        }
+        if (!occ.empty() ? nerf_render_rays_clipped(ctx, occ.data(), grid_lo, grid_step, grid_dims, o.data(), n, d.data(), n, 1, jc.near_, jc.far_, rb, nullptr, &opts, bg,
+                                                    rgb.data(), nullptr, nullptr, nullptr, &n_hit, &rst)
+            : normals.empty() ? nerf_render_rays(ctx, o.data(), n, d.data(), n, 1, jc.near_, jc.far_, rb, nullptr, &opts, bg, rgb.data(), nullptr, nullptr, &rst)
                             : nerf_render_rays_normals(ctx, o.data(), n, d.data(), n, 1, jc.near_, jc.far_, rb, nullptr, &opts, bg, rgb.data(), nullptr, nullptr,
                                                        normals_step, normals.data(), &rst)) {
             fprintf(stderr, "error: %s\n", nerf_last_error(ctx));
@@ -183,8 +216,13 @@ int main(int argc, char **argv) {
         };
         if (!put(rays_out_path, rgb.data(), rgb.size())) return 1;
         if (!normals.empty() && !put(rays_normals_path, normals.data(), 3 * n)) return 1;
-        printf("%zu rays (%d coarse + %d fine samples): device %.2f ms in %u pass(es)\n", n, opts.n_coarse, opts.coarse_only ? 0 : opts.n_fine, n ? rst.ms_total : 0.0,
-               n ? rst.n_passes : 0u);
+        if (!occ.empty()) { // the stats are those of the compacted batch
+            printf("%zu rays, %llu of them cross an occupied cell (%d coarse + %d fine samples): device %.2f ms in %u pass(es)\n", n, (unsigned long long)n_hit,
+                   opts.n_coarse, opts.coarse_only ? 0 : opts.n_fine, n_hit ? rst.ms_total : 0.0, n_hit ? rst.n_passes : 0u);
+            if (!grid_files) want_grid = false; // the lattice flags only described the occupancy file
+        } else
+            printf("%zu rays (%d coarse + %d fine samples): device %.2f ms in %u pass(es)\n", n, opts.n_coarse, opts.coarse_only ? 0 : opts.n_fine, n ? rst.ms_total : 0.0,
+                   n ? rst.n_passes : 0u);
         if (!want_image && !want_grid) {
             for (nerf_ctx *c : ctxs) nerf_destroy(c);
             return 0;

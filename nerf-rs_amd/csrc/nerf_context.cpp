@@ -171,7 +171,7 @@ void nerf_destroy(nerf_ctx *c) {
     (void)hipDeviceSynchronize();
     for (auto &n : c->net) { if (n.wstream) (void)hipFree(n.wstream); if (n.small) (void)hipFree(n.small); if (n.small_f32) (void)hipFree(n.small_f32); if (n.wstream_bf16v2) (void)hipFree(n.wstream_bf16v2); if (n.wstream_x3) (void)hipFree(n.wstream_x3); if (n.wstream_x2) (void)hipFree(n.wstream_x2); if (n.wstream_f16v2) (void)hipFree(n.wstream_f16v2); }
     void *bufs[] = {c->d_dirs, c->d_tc, c->d_sc, c->d_rgbc, c->d_tf, c->d_sf, c->d_rgbf, c->d_rayfb, c->d_rayaux, c->d_out, c->d_pack, c->d_scratch,
-                    c->d_mesh, c->d_batch, c->d_comp, c->d_normal, c->d_stencil, c->d_clock, c->d_zskip, c->d_skip, c->d_nonfinite, c->d_seq, c->d_h8,
+                    c->d_mesh, c->d_batch, c->d_comp, c->d_normal, c->d_stencil, c->d_clip, c->d_clock, c->d_zskip, c->d_skip, c->d_nonfinite, c->d_seq, c->d_h8,
                     c->d_slot_point, c->d_flag_list, c->d_point_list, c->d_jstar, c->d_cert_aux, c->d_cert};
     for (void *p : bufs) if (p) (void)hipFree(p);
     recycle_render(c);

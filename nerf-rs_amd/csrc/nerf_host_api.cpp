@@ -1,6 +1,6 @@
 // nerf_host_api.cpp -- the HOST-ONLY entry points of the C ABI (include/nerf_mi355x.h): everything that parses files from disk or
 // converts host buffers and never touches the device -- weight-directory validation and packing, the packed-blob reader, camera
-// construction (incl. the hand-written JSON reader), PPM / PFM / PAM / PLY writers, quantisers, the split diagnostics.  No HIP header is included,
+// construction (incl. the hand-written JSON reader), PPM / PFM / PAM / PLY writers, quantisers, the split diagnostics, the ray-clip walk on the CPU (ray_clip_core.h).  No HIP header is included,
 // so this file and host_util.cpp also build with plain g++ under AddressSanitizer + UBSan (`make host-asan`; driven by
 // tests/test_host_asan.py on the CPU box with truncated / oversized / malformed inputs).
 #include <math.h>
@@ -16,6 +16,7 @@
 #include "../../include/nerf_mi355x.h"
 #include "host_util.h"
 #include "mlp_layout.h"
+#include "ray_clip_core.h"
 
 using namespace nerfhost;
 
@@ -196,6 +197,26 @@ int nerf_debug_wave_tiling(int rows, int rays_per_row, int samples_per_ray, int 
                 const int s = ray_launch_slot(m, tile, wave, p, m.wt.ss ? wave_tile_lane_part(m.wt, p) : p);
                 slot[((size_t)tile * kWavesPerBlock + wave) * kPointsPerWave + p] = s < n ? s : -1;
             }
+    return NERF_OK;
+} NERF_HOST_CATCH
+
+int nerf_debug_clip_rays(const uint32_t *occ_bits, const float lo[3], const float step[3], const int32_t dims[3], const float *origins,
+                         size_t n_origins, const float *dirs, size_t n_rays, int normalize, float near_, float far_, const float *bounds,
+                         float *bounds_out, uint8_t *hit_out, uint64_t *n_hit, uint64_t *n_refused_reads) try {
+    const char *why = nerfclip::check_grid(occ_bits, lo, step, dims);
+    if (!why) why = nerfclip::check_rays(origins, n_origins, dirs, n_rays, near_, far_, bounds, bounds_out, hit_out);
+    if (why) return fail_noctx(NERF_ERR_INVALID, why);
+    uint64_t hits = 0, refused = 0;
+    for (size_t r = 0; r < n_rays; ++r) { // as k_clip_rays (ray_clip_kernels.hip), one ray after the other
+        float near_r, far_r;
+        const nerfclip::Result res = nerfclip::clip_batch_ray(occ_bits, lo, step, dims, origins, n_origins == 1 ? 0 : 1, dirs, normalize ? 1 : 0, near_, far_,
+                                                              bounds, r, &near_r, &far_r);
+        bounds_out[2 * r] = res.t_first; bounds_out[2 * r + 1] = res.t_last;
+        hit_out[r] = res.hit ? 1 : 0;
+        hits += res.hit ? 1 : 0; refused += res.refused;
+    }
+    if (n_hit) *n_hit = hits;
+    if (n_refused_reads) *n_refused_reads = refused;
     return NERF_OK;
 } NERF_HOST_CATCH
 

@@ -82,6 +82,8 @@ struct nerf_ctx {
     // per stencil point 16 B {3 coordinates, sigma}; the latter also serves nerf_density_gradient_batch, chunk by chunk
     void *d_normal = nullptr; size_t normal_bytes = 0;
     void *d_stencil = nullptr; size_t stencil_bytes = 0;
+    // ray clipping (ray_clip_kernels.h): per ray of a batch the clipped bounds, hit flag and compacted copies of a clipped render; block sums
+    void *d_clip = nullptr; size_t clip_bytes = 0;
     size_t gradient_chunk = (size_t)1 << 20;             // points per internal chunk of nerf_density_gradient_batch (NERF_GRADIENT_CHUNK)
     bool debug_normals = false;                          // NERF_DEBUG_NORMALS=1: a normals render with stats prints its live share and kernel times
     uint64_t normal_live = 0, normal_samples = 0;        // of the last normals render: live / composited samples

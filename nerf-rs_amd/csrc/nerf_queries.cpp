@@ -1,5 +1,5 @@
 // nerf_queries.cpp -- the device entry points that are not renders (include/nerf_mi355x.h): network evaluation at caller points, density
-// batches and grids, isosurface meshes and lattice components, density gradients, and the nerf_stage_* calls that run one kernel of the
+// batches and grids, occupancy dilation and ray clipping, isosurface meshes and lattice components, density gradients, and the nerf_stage_* calls that run one kernel of the
 // render pipeline on caller data.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -14,6 +14,8 @@
 #include "isosurface_kernels.h"
 #include "mlp_kernel.h"
 #include "normal_kernels.h"
+#include "ray_clip_core.h"
+#include "ray_clip_kernels.h"
 #include "sampling_kernels.h"
 
 #include "nerf_internal.h"
@@ -199,6 +201,141 @@ int nerf_density_grid(nerf_ctx *c, int which, const float lo[3], const float ste
     if (stats) HIP_TRY(c, hipMemcpyAsync(h, d_stats, sizeof h, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (stats) density_grid_stats_out(h, n_occupied, bounds);
+    return NERF_OK;
+} NERF_CATCH(c)
+
+// ---- ray clipping (ray_clip_kernels.hip): occupancy dilation and the per-ray span of the occupied cells -----------------------------------
+// everything nerf_occupancy_dilate* can refuse without a device; *n_cells = dims[0] dims[1] dims[2]
+static int dilate_check(nerf_ctx *c, const uint32_t *in, const int32_t *dims, int radius, const uint32_t *out, size_t *n_cells) {
+    if (!in || !dims || !out) return fail(c, NERF_ERR_INVALID, "occ_bits, dims and occ_out must not be NULL");
+    for (int k = 0; k < 3; ++k)
+        if (dims[k] < 1) return fail(c, NERF_ERR_INVALID, "dims must be positive");
+    const unsigned long long plane = (unsigned long long)dims[0] * (unsigned long long)dims[1];
+    if (plane > 0x7fffffffull || plane * (unsigned long long)dims[2] > 0x7fffffffull)
+        return fail(c, NERF_ERR_INVALID, "grid too large: dims[0] * dims[1] * dims[2] must be at most INT32_MAX");
+    *n_cells = (size_t)(plane * (unsigned long long)dims[2]);
+    if (radius < 1 || radius > 4) return fail(c, NERF_ERR_INVALID, "radius must be 1, 2, 3 or 4");
+    const size_t n_words = (*n_cells + 31) / 32;
+    if (in < out + n_words && out < in + n_words) return fail(c, NERF_ERR_INVALID, "occ_bits and occ_out must not overlap");
+    if (!c) return fail(nullptr, NERF_ERR_INVALID, "ctx is NULL");
+    return NERF_OK;
+}
+
+// the dilation and, when asked for, the statistics of its output (through c->d_scratch: 8 ints); arguments already checked
+static int dilate_device(nerf_ctx *c, const uint32_t *d_in, const int32_t *dims, int radius, uint32_t *d_out, size_t n_cells, int *d_stats,
+                         uint64_t *n_occupied, int32_t *bounds, hipStream_t st) {
+    HIP_TRY(c, launch_occupancy_dilate(d_in, d_out, dims[0], dims[1], dims[2], radius, st));
+    if (!d_stats) return NERF_OK;
+    HIP_TRY(c, launch_occupancy_stats(d_out, n_cells, dims[0], dims[1], dims[2], d_stats, st));
+    int h[8];
+    HIP_TRY(c, hipMemcpyAsync(h, d_stats, sizeof h, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    density_grid_stats_out(h, n_occupied, bounds);
+    return NERF_OK;
+}
+
+int nerf_occupancy_dilate_device(nerf_ctx *c, const uint32_t *d_occ_bits, const int32_t dims[3], int radius, uint32_t *d_occ_out,
+                                 uint64_t *n_occupied, int32_t bounds[6], void *stream) try {
+    size_t n_cells = 0;
+    int rc;
+    if ((rc = dilate_check(c, d_occ_bits, dims, radius, d_occ_out, &n_cells))) return rc;
+    DeviceGuard dg(c->device);
+    const bool stats = n_occupied || bounds;
+    if (stats && (rc = ensure_bytes(c, &c->d_scratch, &c->scratch_bytes, 8 * sizeof(int)))) return rc;
+    return dilate_device(c, d_occ_bits, dims, radius, d_occ_out, n_cells, stats ? (int *)c->d_scratch : nullptr, n_occupied, bounds, (hipStream_t)stream);
+} NERF_CATCH(c)
+
+int nerf_occupancy_dilate(nerf_ctx *c, const uint32_t *occ_bits, const int32_t dims[3], int radius, uint32_t *occ_out, uint64_t *n_occupied,
+                          int32_t bounds[6]) try {
+    size_t n_cells = 0;
+    int rc;
+    if ((rc = dilate_check(c, occ_bits, dims, radius, occ_out, &n_cells))) return rc;
+    DeviceGuard dg(c->device);
+    // staging: [8 ints of statistics][input words][output words]
+    const size_t n_words = (n_cells + 31) / 32;
+    if ((rc = ensure_bytes(c, &c->d_scratch, &c->scratch_bytes, 8 * sizeof(int) + 2 * n_words * sizeof(uint32_t)))) return rc;
+    int *d_stats = (int *)c->d_scratch;
+    uint32_t *d_in = (uint32_t *)(d_stats + 8), *d_out = d_in + n_words;
+    HIP_TRY(c, hipMemcpyAsync(d_in, occ_bits, n_words * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    if ((rc = dilate_device(c, d_in, dims, radius, d_out, n_cells, (n_occupied || bounds) ? d_stats : nullptr, n_occupied, bounds, c->stream))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(occ_out, d_out, n_words * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return NERF_OK;
+} NERF_CATCH(c)
+
+// everything nerf_clip_rays* can refuse without a device
+static int clip_check(nerf_ctx *c, const void *occ_bits, const float *lo, const float *step, const int32_t *dims, const void *origins, size_t n_origins,
+                      const void *dirs, size_t n_rays, float near_, float far_, const void *bounds, const void *bounds_out, const void *hit_out) {
+    const char *why = nerfclip::check_grid(occ_bits, lo, step, dims);
+    if (!why) why = nerfclip::check_rays(origins, n_origins, dirs, n_rays, near_, far_, bounds, bounds_out, hit_out);
+    if (why) return fail(c, NERF_ERR_INVALID, why);
+    if (!c) return fail(nullptr, NERF_ERR_INVALID, "ctx is NULL");
+    return NERF_OK;
+}
+
+// the clip launch on device pointers; with n_hit the block sums go through c->d_clip and the total comes back (one synchronisation)
+static int clip_device(nerf_ctx *c, const uint32_t *d_bits, const float *lo, const float *step, const int32_t *dims, const float *d_origins,
+                       size_t n_origins, const float *d_dirs, size_t n_rays, int normalize, float near_, float far_, const float *d_bounds,
+                       float *d_bounds_out, uint8_t *d_hit_out, uint64_t *n_hit, hipStream_t st) {
+    ClipRaysArgs a{};
+    a.bits = d_bits;
+    for (int k = 0; k < 3; ++k) { a.lo[k] = lo[k]; a.step[k] = step[k]; a.dims[k] = dims[k]; }
+    a.origins = d_origins; a.per_ray_origins = n_origins == 1 ? 0 : 1; a.dirs = d_dirs; a.n_rays = (int)n_rays; a.normalize = normalize ? 1 : 0;
+    a.near_ = near_; a.far_ = far_; a.bounds = d_bounds; a.bounds_out = d_bounds_out; a.hit_out = d_hit_out;
+    uint32_t *d_totals = nullptr;
+    if (n_hit) {
+        const size_t n_blocks = (n_rays + kClipBlock - 1) / kClipBlock;
+        int rc;
+        if ((rc = ensure_bytes(c, &c->d_clip, &c->clip_bytes, (n_blocks + 2) * sizeof(uint32_t)))) return rc;
+        d_totals = (uint32_t *)c->d_clip;
+        a.bsum = d_totals + 2;
+    }
+    HIP_TRY(c, launch_clip_rays(a, st));
+    if (n_hit) {
+        HIP_TRY(c, launch_clip_scan(a.bsum, a.n_rays, d_totals, st));
+        uint32_t h[2];
+        HIP_TRY(c, hipMemcpyAsync(h, d_totals, sizeof h, hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipStreamSynchronize(st));
+        *n_hit = h[0];
+    }
+    return NERF_OK;
+}
+
+int nerf_clip_rays_device(nerf_ctx *c, const uint32_t *d_occ_bits, const float lo[3], const float step[3], const int32_t dims[3],
+                          const float *d_origins, size_t n_origins, const float *d_dirs, size_t n_rays, int normalize, float near_, float far_,
+                          const float *d_bounds, float *d_bounds_out, uint8_t *d_hit_out, uint64_t *n_hit, void *stream) try {
+    int rc;
+    if ((rc = clip_check(c, d_occ_bits, lo, step, dims, d_origins, n_origins, d_dirs, n_rays, near_, far_, d_bounds, d_bounds_out, d_hit_out))) return rc;
+    if (n_hit) *n_hit = 0;
+    if (n_rays == 0) return NERF_OK;
+    DeviceGuard dg(c->device);
+    return clip_device(c, d_occ_bits, lo, step, dims, d_origins, n_origins, d_dirs, n_rays, normalize, near_, far_, d_bounds, d_bounds_out, d_hit_out,
+                       n_hit, (hipStream_t)stream);
+} NERF_CATCH(c)
+
+int nerf_clip_rays(nerf_ctx *c, const uint32_t *occ_bits, const float lo[3], const float step[3], const int32_t dims[3], const float *origins,
+                   size_t n_origins, const float *dirs, size_t n_rays, int normalize, float near_, float far_, const float *bounds,
+                   float *bounds_out, uint8_t *hit_out, uint64_t *n_hit) try {
+    int rc;
+    if ((rc = clip_check(c, occ_bits, lo, step, dims, origins, n_origins, dirs, n_rays, near_, far_, bounds, bounds_out, hit_out))) return rc;
+    if (n_hit) *n_hit = 0;
+    if (n_rays == 0) return NERF_OK;
+    DeviceGuard dg(c->device);
+    // staging (words): occupancy, dirs, origins, [bounds], bounds_out, hit flags
+    const size_t R = n_rays, n_words = ((size_t)dims[0] * dims[1] * dims[2] + 31) / 32, n_o = n_origins == 1 ? 1 : R;
+    const size_t o_g = 0, o_d = o_g + n_words, o_o = o_d + 3 * R, o_b = o_o + 3 * n_o, o_c = o_b + (bounds ? 2 * R : 0), o_h = o_c + 2 * R,
+                 total = o_h + (R + 3) / 4;
+    if ((rc = ensure_bytes(c, &c->d_scratch, &c->scratch_bytes, total * 4))) return rc;
+    uint32_t *d = (uint32_t *)c->d_scratch;
+    HIP_TRY(c, hipMemcpyAsync(d + o_g, occ_bits, n_words * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d + o_d, dirs, 3 * R * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d + o_o, origins, 3 * n_o * 4, hipMemcpyHostToDevice, c->stream));
+    if (bounds) HIP_TRY(c, hipMemcpyAsync(d + o_b, bounds, 2 * R * 4, hipMemcpyHostToDevice, c->stream));
+    if ((rc = clip_device(c, d + o_g, lo, step, dims, (const float *)(d + o_o), n_origins, (const float *)(d + o_d), R, normalize, near_, far_,
+                          bounds ? (const float *)(d + o_b) : nullptr, (float *)(d + o_c), (uint8_t *)(d + o_h), n_hit, c->stream))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(bounds_out, d + o_c, 2 * R * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(hit_out, d + o_h, R, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     return NERF_OK;
 } NERF_CATCH(c)
 

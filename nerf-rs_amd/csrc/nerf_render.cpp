@@ -15,6 +15,8 @@
 #include "mlp_layout.h"
 #include "normal_kernels.h"
 #include "ray_batch_kernels.h"
+#include "ray_clip_core.h"
+#include "ray_clip_kernels.h"
 #include "sampling_kernels.h"
 
 using namespace nerfhost;
@@ -83,6 +85,33 @@ struct NormalWorkspace {
         base = (uint32_t *)q; q += al(4 * rays);
         bsum = (uint32_t *)q; q += al(4 * blocks(rays));
         totals = (uint32_t *)q;
+    }
+};
+
+// The workspace of a clipped render (nerf_render_rays_clipped) in c->d_clip for a batch of n rays, every part 256-byte aligned: the clip's
+// outputs, the block sums, and the compacted batch with its outputs (sized for n hits, so that the hit count never reallocates).
+struct ClipWorkspace {
+    uint32_t *totals = nullptr, *bsum = nullptr, *ray_of = nullptr, *rng_c = nullptr;
+    float *clip_bounds = nullptr, *dirs_c = nullptr, *origins_c = nullptr, *bounds_c = nullptr, *rgb_c = nullptr, *depth_c = nullptr, *opacity_c = nullptr;
+    uint8_t *hit = nullptr;
+    static size_t al(size_t bytes) { return (bytes + 255) / 256 * 256; }
+    static size_t bytes(size_t n, bool per_ray_origins) { return ClipWorkspace(nullptr, n, per_ray_origins).end; }
+    size_t end = 0;
+    ClipWorkspace(void *p, size_t n, bool per_ray_origins) {
+        char *base = (char *)p;
+        auto take = [&](size_t b) { char *q = base ? base + end : nullptr; end += al(b); return (void *)q; };
+        totals = (uint32_t *)take(8);
+        bsum = (uint32_t *)take(4 * ((n + kClipBlock - 1) / kClipBlock));
+        hit = (uint8_t *)take(n);
+        clip_bounds = (float *)take(8 * n);
+        ray_of = (uint32_t *)take(4 * n);
+        rng_c = (uint32_t *)take(4 * n);
+        dirs_c = (float *)take(12 * n);
+        origins_c = (float *)take(per_ray_origins ? 12 * n : 0);
+        bounds_c = (float *)take(8 * n);
+        rgb_c = (float *)take(12 * n);
+        depth_c = (float *)take(4 * n);
+        opacity_c = (float *)take(4 * n);
     }
 };
 
@@ -1075,6 +1104,111 @@ static int rays_host(nerf_ctx *c, const float *origins, size_t n_origins, const 
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return NERF_OK;
 }
+
+// ---- clipped ray batches -----------------------------------------------------------------------------------------------------
+// what nerf_render_rays_clipped* refuses without a context or a device: nerf_render_rays' refusals, then the grid's
+static int check_rays_clipped(nerf_ctx *c, const void *occ_bits, const float *lo, const float *step, const int32_t *dims, const void *origins,
+                              size_t n_origins, const void *dirs, size_t n_rays, float near_, float far_, const void *bounds,
+                              const nerf_render_opts *opts, const float *background, const void *rgb_out) {
+    int rc;
+    if ((rc = check_ray_batch(c, origins, n_origins, dirs, n_rays, near_, far_, bounds, opts, background, rgb_out))) return rc;
+    if (const char *why = nerfclip::check_grid(occ_bits, lo, step, dims)) return fail(c, NERF_ERR_INVALID, why);
+    return NERF_OK;
+}
+
+// clip -> count -> [gather -> render_rays_device on the compacted batch -> scatter]; every pointer but lo / step / dims / opts / background /
+// n_hit / stats is a device pointer; arguments already checked, n_rays > 0
+static int rays_clipped_device(nerf_ctx *c, const uint32_t *d_bits, const float *lo, const float *step, const int32_t *dims, const float *d_origins,
+                               size_t n_origins, const float *d_dirs, size_t n_rays, int normalize, float near_, float far_, const float *d_bounds,
+                               const uint32_t *d_rng_index, const nerf_render_opts *opts, const float *background, float *d_rgb_out,
+                               float *d_depth_out, float *d_opacity_out, uint8_t *d_hit_out, uint64_t *n_hit, hipStream_t st, nerf_stats *stats) {
+    int rc;
+    const bool per_ray = n_origins != 1;
+    if ((rc = ensure_bytes(c, &c->d_clip, &c->clip_bytes, ClipWorkspace::bytes(n_rays, per_ray)))) return rc;
+    const ClipWorkspace w(c->d_clip, n_rays, per_ray);
+    ClipRaysArgs a{};
+    a.bits = d_bits;
+    for (int k = 0; k < 3; ++k) { a.lo[k] = lo[k]; a.step[k] = step[k]; a.dims[k] = dims[k]; a.bg[k] = background ? background[k] : 1.0f; }
+    a.origins = d_origins; a.per_ray_origins = per_ray ? 1 : 0; a.dirs = d_dirs; a.n_rays = (int)n_rays; a.normalize = normalize ? 1 : 0;
+    a.near_ = near_; a.far_ = far_; a.bounds = d_bounds; a.bounds_out = w.clip_bounds; a.hit_out = d_hit_out ? d_hit_out : w.hit; a.bsum = w.bsum;
+    a.rgb_fill = d_rgb_out; a.depth_fill = d_depth_out; a.opacity_fill = d_opacity_out; // the missed rays are finished here
+    HIP_TRY(c, launch_clip_rays(a, st));
+    HIP_TRY(c, launch_clip_scan(w.bsum, a.n_rays, w.totals, st));
+    uint32_t totals[2] = {0, 0};
+    float origin[3] = {0.0f, 0.0f, 0.0f};
+    HIP_TRY(c, hipMemcpyAsync(totals, w.totals, sizeof totals, hipMemcpyDeviceToHost, st));
+    if (!per_ray) HIP_TRY(c, hipMemcpyAsync(origin, d_origins, sizeof origin, hipMemcpyDeviceToHost, st)); // rides in the MLP kernels' arguments
+    HIP_TRY(c, hipStreamSynchronize(st)); // the hit count sizes every launch that follows
+    const size_t H = totals[0];
+    if (H > n_rays) return fail(c, NERF_ERR_HIP, "clipped render: the hit count exceeds the batch");
+    if (n_hit) *n_hit = H;
+    if (H == 0) { // nothing to render: the clip launch has written every ray
+        if (stats) memset(stats, 0, sizeof *stats);
+        return NERF_OK;
+    }
+    ClipGatherArgs g{};
+    g.n_rays = a.n_rays; g.hit = a.hit_out; g.bsum = w.bsum; g.dirs = d_dirs; g.origins = per_ray ? d_origins : nullptr; g.clip_bounds = w.clip_bounds;
+    g.rng_index = d_rng_index; g.ray_of = w.ray_of; g.dirs_c = w.dirs_c; g.origins_c = w.origins_c; g.bounds_c = w.bounds_c; g.rng_c = w.rng_c;
+    HIP_TRY(c, launch_clip_gather(g, st));
+    const RayBatch b{per_ray ? nullptr : origin, per_ray ? w.origins_c : nullptr, w.dirs_c, H, normalize ? 1 : 0, near_, far_, w.bounds_c, w.rng_c};
+    if ((rc = render_rays_device(c, b, opts, background, w.rgb_c, d_depth_out ? w.depth_c : nullptr, d_opacity_out ? w.opacity_c : nullptr, st, stats)))
+        return rc;
+    const ClipScatterArgs s{(uint32_t)H, w.ray_of, w.rgb_c, w.depth_c, w.opacity_c, d_rgb_out, d_depth_out, d_opacity_out};
+    HIP_TRY(c, launch_clip_scatter(s, st));
+    if (stats) HIP_TRY(c, hipStreamSynchronize(st)); // as nerf_render_rays_device: with stats the outputs are complete on return
+    return NERF_OK;
+}
+
+int nerf_render_rays_clipped_device(nerf_ctx *c, const uint32_t *d_occ_bits, const float lo[3], const float step[3], const int32_t dims[3],
+                                    const float *d_origins, size_t n_origins, const float *d_dirs, size_t n_rays, int normalize, float near_,
+                                    float far_, const float *d_bounds, const uint32_t *d_rng_index, const nerf_render_opts *opts,
+                                    const float background[3], float *d_rgb_out, float *d_depth_out, float *d_opacity_out, uint8_t *d_hit_out,
+                                    uint64_t *n_hit, void *stream, nerf_stats *stats) try {
+    int rc;
+    if ((rc = check_rays_clipped(c, d_occ_bits, lo, step, dims, d_origins, n_origins, d_dirs, n_rays, near_, far_, d_bounds, opts, background, d_rgb_out)))
+        return rc;
+    if (!c) return fail(nullptr, NERF_ERR_INVALID, "ctx is NULL");
+    if (n_hit) *n_hit = 0;
+    if (n_rays == 0) return NERF_OK;
+    DeviceGuard dg(c->device);
+    return rays_clipped_device(c, d_occ_bits, lo, step, dims, d_origins, n_origins, d_dirs, n_rays, normalize, near_, far_, d_bounds, d_rng_index, opts,
+                               background, d_rgb_out, d_depth_out, d_opacity_out, d_hit_out, n_hit, (hipStream_t)stream, stats);
+} NERF_CATCH(c)
+
+int nerf_render_rays_clipped(nerf_ctx *c, const uint32_t *occ_bits, const float lo[3], const float step[3], const int32_t dims[3],
+                             const float *origins, size_t n_origins, const float *dirs, size_t n_rays, int normalize, float near_, float far_,
+                             const float *bounds, const uint32_t *rng_index, const nerf_render_opts *opts, const float background[3], float *rgb_out,
+                             float *depth_out, float *opacity_out, uint8_t *hit_out, uint64_t *n_hit, nerf_stats *stats) try {
+    int rc;
+    if ((rc = check_rays_clipped(c, occ_bits, lo, step, dims, origins, n_origins, dirs, n_rays, near_, far_, bounds, opts, background, rgb_out))) return rc;
+    if ((rc = check_ray_batch_rays(c, origins, n_origins, dirs, n_rays, normalize, bounds))) return rc;
+    if (!c) return fail(nullptr, NERF_ERR_INVALID, "ctx is NULL");
+    if (n_hit) *n_hit = 0;
+    if (n_rays == 0) return NERF_OK;
+    DeviceGuard dg(c->device);
+    // staging (words): occupancy, dirs, origins, [bounds], [rng_index], rgb, [depth], [opacity], [hit flags]
+    const size_t R = n_rays, n_words = ((size_t)dims[0] * dims[1] * dims[2] + 31) / 32, n_o = n_origins == 1 ? 1 : R;
+    const size_t o_g = 0, o_d = o_g + n_words, o_o = o_d + 3 * R, o_b = o_o + 3 * n_o, o_i = o_b + (bounds ? 2 * R : 0), o_c = o_i + (rng_index ? R : 0),
+                 o_z = o_c + 3 * R, o_a = o_z + (depth_out ? R : 0), o_h = o_a + (opacity_out ? R : 0), total = o_h + (hit_out ? (R + 3) / 4 : 0);
+    if ((rc = ensure_bytes(c, (void **)&c->d_out, &c->out_floats, total * sizeof(float)))) return rc;
+    float *d = c->d_out;
+    HIP_TRY(c, hipMemcpyAsync(d + o_g, occ_bits, n_words * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d + o_d, dirs, 3 * R * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d + o_o, origins, 3 * n_o * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (bounds) HIP_TRY(c, hipMemcpyAsync(d + o_b, bounds, 2 * R * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (rng_index) HIP_TRY(c, hipMemcpyAsync(d + o_i, rng_index, R * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    nerf_stats local; // a synchronous render always reads its counters (see nerf_render_image_aux)
+    if ((rc = rays_clipped_device(c, (const uint32_t *)(d + o_g), lo, step, dims, d + o_o, n_origins, d + o_d, R, normalize, near_, far_,
+                                  bounds ? d + o_b : nullptr, rng_index ? (const uint32_t *)(d + o_i) : nullptr, opts, background, d + o_c,
+                                  depth_out ? d + o_z : nullptr, opacity_out ? d + o_a : nullptr, hit_out ? (uint8_t *)(d + o_h) : nullptr, n_hit,
+                                  c->stream, stats ? stats : &local))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(rgb_out, d + o_c, 3 * R * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (depth_out) HIP_TRY(c, hipMemcpyAsync(depth_out, d + o_z, R * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (opacity_out) HIP_TRY(c, hipMemcpyAsync(opacity_out, d + o_a, R * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (hit_out) HIP_TRY(c, hipMemcpyAsync(hit_out, d + o_h, R, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return NERF_OK;
+} NERF_CATCH(c)
 
 int nerf_render_rays(nerf_ctx *c, const float *origins, size_t n_origins, const float *dirs, size_t n_rays, int normalize, float near_, float far_,
                      const float *bounds, const uint32_t *rng_index, const nerf_render_opts *opts, const float background[3], float *rgb_out,
