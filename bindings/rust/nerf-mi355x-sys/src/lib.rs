@@ -227,6 +227,17 @@ extern "C" {
                                    opts: *const nerf_render_opts, background: *const f32, d_rgb_out: *mut f32,
                                    d_depth_out: *mut f32, d_opacity_out: *mut f32, stream: *mut c_void,
                                    stats: *mut nerf_stats) -> c_int;
+    /// `nerf_render_rays` with zero certification inside every pass (`nerf_render_opts.certify_zero` of an image render): the same bits for a
+    /// fraction of the network evaluations; mlp_dtype F32, BF16X3 or F16X2.  The device form always synchronises the stream (the audit is read on the host).
+    pub fn nerf_render_rays_certified(ctx: *mut nerf_ctx, origins: *const f32, n_origins: usize, dirs: *const f32, n_rays: usize,
+                                      normalize: c_int, near: f32, far: f32, bounds: *const f32, rng_index: *const u32,
+                                      opts: *const nerf_render_opts, background: *const f32, rgb_out: *mut f32, depth_out: *mut f32,
+                                      opacity_out: *mut f32, stats: *mut nerf_stats) -> c_int;
+    pub fn nerf_render_rays_certified_device(ctx: *mut nerf_ctx, d_origins: *const f32, n_origins: usize, d_dirs: *const f32, n_rays: usize,
+                                             normalize: c_int, near: f32, far: f32, d_bounds: *const f32, d_rng_index: *const u32,
+                                             opts: *const nerf_render_opts, background: *const f32, d_rgb_out: *mut f32,
+                                             d_depth_out: *mut f32, d_opacity_out: *mut f32, stream: *mut c_void,
+                                             stats: *mut nerf_stats) -> c_int;
     /// Central differences of sigma with step `h` at n points (3 x n SoA) -> `grad_soa` 3 x n: per axis (sigma(p + h e) - sigma(p - h e))
     /// over the f32 difference of the two coordinates, 0 where that is 0.  Conventions: include/nerf_mi355x.h, "surface normals".
     pub fn nerf_density_gradient_batch(ctx: *mut nerf_ctx, which: c_int, pts_soa: *const f32, n: usize, h: f32, grad_soa: *mut f32) -> c_int;
@@ -277,6 +288,18 @@ extern "C" {
                                            opts: *const nerf_render_opts, background: *const f32, d_rgb_out: *mut f32,
                                            d_depth_out: *mut f32, d_opacity_out: *mut f32, d_hit_out: *mut u8, n_hit: *mut u64,
                                            stream: *mut c_void, stats: *mut nerf_stats) -> c_int;
+    /// `nerf_render_rays_clipped` with the compacted batch rendered under zero certification: the same bits; the device form synchronises the stream.
+    pub fn nerf_render_rays_clipped_certified(ctx: *mut nerf_ctx, occ_bits: *const u32, lo: *const f32, step: *const f32, dims: *const i32,
+                                              origins: *const f32, n_origins: usize, dirs: *const f32, n_rays: usize, normalize: c_int, near: f32,
+                                              far: f32, bounds: *const f32, rng_index: *const u32, opts: *const nerf_render_opts,
+                                              background: *const f32, rgb_out: *mut f32, depth_out: *mut f32, opacity_out: *mut f32,
+                                              hit_out: *mut u8, n_hit: *mut u64, stats: *mut nerf_stats) -> c_int;
+    pub fn nerf_render_rays_clipped_certified_device(ctx: *mut nerf_ctx, d_occ_bits: *const u32, lo: *const f32, step: *const f32, dims: *const i32,
+                                                     d_origins: *const f32, n_origins: usize, d_dirs: *const f32, n_rays: usize, normalize: c_int,
+                                                     near: f32, far: f32, d_bounds: *const f32, d_rng_index: *const u32,
+                                                     opts: *const nerf_render_opts, background: *const f32, d_rgb_out: *mut f32,
+                                                     d_depth_out: *mut f32, d_opacity_out: *mut f32, d_hit_out: *mut u8, n_hit: *mut u64,
+                                                     stream: *mut c_void, stats: *mut nerf_stats) -> c_int;
     /// render_image over several GPUs: `ctxs[i]` = one context per device, row bands on per-context host threads + streams,
     /// gathered into `rgb_out` by `gather` (NERF_GATHER_*).  The reference's counterpart is the rayon fan-out, src/lib.rs:533-557.
     pub fn nerf_render_image_multi(ctxs: *const *mut nerf_ctx, n: c_int, cam: *const nerf_camera, opts: *const nerf_render_opts,
@@ -334,6 +357,10 @@ extern "C" {
     pub fn nerf_stage_prefilter(ctx: *mut nerf_ctx, which: c_int, f16: c_int, origin: *const f32, dirs: *const f32, t: *const f32,
                                 n_rays: usize, spr: c_int, far: f32, cut_t: f32, pre_out: *mut f32,
                                 nonfinite_tiles: *mut u32) -> c_int;
+    /// `nerf_stage_prefilter` with one origin per ray (`origins` n_rays x 3).
+    pub fn nerf_stage_prefilter_rays(ctx: *mut nerf_ctx, which: c_int, f16: c_int, origins: *const f32, dirs: *const f32, t: *const f32,
+                                     n_rays: usize, spr: c_int, far: f32, cut_t: f32, pre_out: *mut f32,
+                                     nonfinite_tiles: *mut u32) -> c_int;
 }
 
 /// Compares the sizes of the `#[repr(C)]` mirrors above with the library's own structs; call once before anything else.

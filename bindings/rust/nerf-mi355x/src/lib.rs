@@ -309,6 +309,27 @@ impl Gpu {
         Ok((rgb, depth, opacity, stats))
     }
 
+    /// `render_rays` with zero certification inside every pass (nerf_render_rays_certified; `RenderOpts.certify_zero` of an image render): the
+    /// same bits for a fraction of the network evaluations; `stats` carries the audit.  mlp_dtype F32, BF16X3 or F16X2.
+    #[allow(clippy::too_many_arguments)]
+    pub fn render_rays_certified(&self, origins: &[f32], dirs: &[f32], normalize: bool, near: f32, far: f32, bounds: Option<&[f32]>,
+                                 rng_index: Option<&[u32]>, opts: &RenderOpts, background: Option<[f32; 3]>) -> Result<(Vec<f32>, Vec<f32>, Vec<f32>, Stats), Error> {
+        let n = dirs.len() / 3;
+        assert_eq!(dirs.len(), 3 * n, "dirs.len() must be 3 * n_rays");
+        assert!(origins.len() == 3 || origins.len() == 3 * n, "origins must hold one origin or one per ray");
+        assert!(bounds.map_or(true, |b| b.len() == 2 * n), "bounds.len() must be 2 * n_rays");
+        assert!(rng_index.map_or(true, |i| i.len() == n), "rng_index.len() must be n_rays");
+        let (mut rgb, mut depth, mut opacity) = (vec![0f32; 3 * n], vec![0f32; n], vec![0f32; n]);
+        let mut stats = Stats::default();
+        let bg = background.as_ref().map_or(std::ptr::null(), |b| b.as_ptr());
+        check(self.ctx, unsafe {
+            sys::nerf_render_rays_certified(self.ctx, origins.as_ptr(), origins.len() / 3, dirs.as_ptr(), n, normalize as i32, near, far,
+                                            bounds.map_or(std::ptr::null(), |b| b.as_ptr()), rng_index.map_or(std::ptr::null(), |i| i.as_ptr()), opts, bg,
+                                            rgb.as_mut_ptr(), depth.as_mut_ptr(), opacity.as_mut_ptr(), &mut stats)
+        })?;
+        Ok((rgb, depth, opacity, stats))
+    }
+
     /// `render_rays` with one normal per ray (nerf_render_rays_normals): minus the weighted sum of the density gradients, step `h`, at
     /// the samples of weight > 0, normalised; (0, 0, 0) for a ray without such a sample.  -> (rgb, depth, opacity, normals n x 3, stats);
     /// the first three are `render_rays`' bits.

@@ -474,9 +474,11 @@ int nerf_render_image_rgba8_device(nerf_ctx *ctx, const nerf_camera *cam, const 
  *              n_origins == n_rays with one origin repeated gives the bits of n_origins == 1.
  * LIMITS       n_rays == 0 is a no-op; n_rays <= INT32_MAX.  The batch runs in passes of at most NERF_MAX_RAYS_PER_PASS rays with
  *              rays * samples <= 0x3fffffff, like an image; the limit on samples per ray is the image renders'.  Per-ray origins cost a
- *              workspace of 24 bytes per sample of a pass in the context, grown on demand: a warm call allocates nothing.
- * FIRST VERSION: the options tied to the pixel grid or to the ray-sequential and list kernels are refused -- NERF_ERR_INVALID when any of
- *              opts->crop_*, ssaa > 1, band_count > 1, skip_empty, skip_dead, hybrid_sampling, certify_zero is set.  Also NERF_ERR_INVALID:
+ *              workspace of 24 bytes per sample of a pass in the context, grown on demand: a warm call allocates nothing.  (The certified
+ *              forms below expand nothing: no such workspace.)
+ * REFUSED      the options tied to the pixel grid or to the ray-sequential kernels -- NERF_ERR_INVALID when any of opts->crop_*, ssaa > 1,
+ *              band_count > 1, skip_empty, skip_dead, hybrid_sampling is set; opts->certify_zero too, on these entry points: zero
+ *              certification of a batch is nerf_render_rays_certified / nerf_render_rays_clipped_certified.  Also NERF_ERR_INVALID:
  *              a NULL origins / dirs / opts / rgb_out, n_origins outside {1, n_rays}, n_coarse <= 0, n_fine < 0, a bad mlp_dtype, near_ /
  *              far_ not finite or far_ <= near_ when bounds is NULL, a non-finite background.  All of this is checked before the context
  *              or the device is needed.
@@ -502,6 +504,37 @@ int nerf_render_rays_device(nerf_ctx *ctx, const float *d_origins, size_t n_orig
                             float near_, float far_, const float *d_bounds, const uint32_t *d_rng_index,
                             const nerf_render_opts *opts, const float background[3],
                             float *d_rgb_out, float *d_depth_out, float *d_opacity_out, void *stream, nerf_stats *stats);
+/* nerf_render_rays with zero certification (nerf_render_opts.certify_zero of an image render) inside every pass: the 16-bit pre-filter
+ * certifies the samples whose density is 0 and predicts each ray's transmittance cut, the exact kernels evaluate the remaining samples
+ * from a device-side list.
+ * OUTPUTS      rgb_out, depth_out, opacity_out are those of nerf_render_rays with the same arguments, bit for bit -- shared origin or
+ *              per-ray origins, near_ / far_ or per-ray bounds, rng_index, normalize, background, coarse_only, n_fine == 0, several passes.
+ * SWITCH       the entry point is the switch: opts->certify_zero must be 0 or 1 and is otherwise not consulted.
+ * REFUSED      mlp_dtype NERF_MLP_BF16 ("certify_zero needs mlp_dtype F32, BF16X3 or F16X2 ...", as for an image); skip_empty, skip_dead,
+ *              hybrid_sampling, crop_*, ssaa > 1, band_count > 1 with nerf_render_rays' messages.  Every other argument check and per-ray
+ *              host check is nerf_render_rays', in the same order, made before the context or the device is needed; a NULL context is
+ *              reported last.
+ * AUDIT        as for an image: a batch stands only if the audit found no wrong certificate and enough headroom; otherwise the margin is
+ *              widened (per context and network) or the list grown and the BATCH IS RENDERED AGAIN, at most 8 times, then NERF_ERR_STATE.
+ *              nerf_stats carries n_certify_*, certify_margin / _headroom / _max_error and n_exec_* as for an image.
+ * LIMITS       nerf_render_rays'.  Per-ray origins are read by the certified kernels themselves (one origin per list entry / per ray of
+ *              the pre-filter): no points are expanded and the 24-byte-per-sample workspace is not needed.  The fused pre-filter
+ *              (NERF_CERTIFY_SEQ_PREFILTER=0) knows one origin only: a pass with per-ray origins uses the ray-sequential pre-filter
+ *              whatever that setting says.  Normals are not offered.  nerf_kernel_time_query keeps counting image renders only.
+ * Host pointers, synchronous. */
+int nerf_render_rays_certified(nerf_ctx *ctx, const float *origins /* n_origins x 3 */, size_t n_origins /* 1 or n_rays */,
+                               const float *dirs /* n_rays x 3 */, size_t n_rays, int normalize,
+                               float near_, float far_, const float *bounds /* n_rays x 2 or NULL */,
+                               const uint32_t *rng_index /* n_rays or NULL */,
+                               const nerf_render_opts *opts, const float background[3] /* NULL = white */,
+                               float *rgb_out /* n_rays x 3 */, float *depth_out /* n_rays or NULL */, float *opacity_out /* n_rays or NULL */,
+                               nerf_stats *stats /* may be NULL */);
+/* device pointers as for nerf_render_rays_device.  SYNCHRONISES `stream` before returning, with or without stats: the audit that decides
+ * whether the batch stands is read on the host (and with n_origins == 1 the origin is read back first, as there). */
+int nerf_render_rays_certified_device(nerf_ctx *ctx, const float *d_origins, size_t n_origins, const float *d_dirs, size_t n_rays, int normalize,
+                                      float near_, float far_, const float *d_bounds, const uint32_t *d_rng_index,
+                                      const nerf_render_opts *opts, const float background[3],
+                                      float *d_rgb_out, float *d_depth_out, float *d_opacity_out, void *stream, nerf_stats *stats);
 
 /* ---- surface normals: the gradient of sigma at caller points, and one normal per ray of a batch -------------------------------------------
  * The mesh normals above difference sigma over a whole lattice spacing.  These entry points difference the network itself, with a step h
@@ -649,6 +682,25 @@ int nerf_render_rays_clipped_device(nerf_ctx *ctx, const uint32_t *d_occ_bits, c
                                     const nerf_render_opts *opts, const float background[3],
                                     float *d_rgb_out, float *d_depth_out, float *d_opacity_out, uint8_t *d_hit_out, uint64_t *n_hit,
                                     void *stream, nerf_stats *stats);
+/* nerf_render_rays_clipped with the compacted batch rendered by nerf_render_rays_certified's pipeline.  Outputs -- rgb, depth, opacity, hit
+ * flags, scatter and n_hit -- are those of nerf_render_rays_clipped with the same arguments, bit for bit.  Arguments and refusals:
+ * nerf_render_rays_certified's, then the grid's.  A retry of the audit renders the compacted batch again and does not clip again.
+ * nerf_stats as for the compacted batch, with the certify fields.  Host pointers, synchronous. */
+int nerf_render_rays_clipped_certified(nerf_ctx *ctx, const uint32_t *occ_bits, const float lo[3], const float step[3], const int32_t dims[3],
+                                       const float *origins /* n_origins x 3 */, size_t n_origins /* 1 or n_rays */,
+                                       const float *dirs /* n_rays x 3 */, size_t n_rays, int normalize, float near_, float far_,
+                                       const float *bounds /* n_rays x 2 or NULL */, const uint32_t *rng_index /* n_rays or NULL */,
+                                       const nerf_render_opts *opts, const float background[3] /* NULL = white */,
+                                       float *rgb_out /* n_rays x 3 */, float *depth_out /* n_rays or NULL */, float *opacity_out /* n_rays or NULL */,
+                                       uint8_t *hit_out /* n_rays or NULL */, uint64_t *n_hit /* may be NULL */, nerf_stats *stats /* may be NULL */);
+/* device pointers as for nerf_render_rays_clipped_device.  SYNCHRONISES `stream` after the clip (the hit count) and again before returning,
+ * with or without stats: the audit is read on the host. */
+int nerf_render_rays_clipped_certified_device(nerf_ctx *ctx, const uint32_t *d_occ_bits, const float lo[3], const float step[3],
+                                              const int32_t dims[3], const float *d_origins, size_t n_origins, const float *d_dirs, size_t n_rays,
+                                              int normalize, float near_, float far_, const float *d_bounds, const uint32_t *d_rng_index,
+                                              const nerf_render_opts *opts, const float background[3],
+                                              float *d_rgb_out, float *d_depth_out, float *d_opacity_out, uint8_t *d_hit_out, uint64_t *n_hit,
+                                              void *stream, nerf_stats *stats);
 
 /* ---- S3 over several GPUs of one node (reference: the rayon fan-out over blocks + scatter, src/lib.rs:533-557) ------
  * ctxs[i] is one context per device (nerf_create / nerf_create_multi), each with both networks loaded (weights are
@@ -790,6 +842,10 @@ int nerf_stage_cert_audit(nerf_ctx *ctx, const uint32_t *aux, uint32_t aux_count
  * f16 stream (a weight beyond the f16 range). */
 int nerf_stage_prefilter(nerf_ctx *ctx, int which, int f16, const float origin[3], const float *dirs, const float *t, size_t n_rays,
                          int spr, float far_, float cut_T, float *pre_out, uint32_t *nonfinite_tiles);
+/* The same with one origin per ray (origins: n_rays x 3), as a certified ray batch with per-ray origins launches it: row r of pre_out
+ * carries the bits nerf_stage_prefilter returns for ray r alone with origin = origins[r]. */
+int nerf_stage_prefilter_rays(nerf_ctx *ctx, int which, int f16, const float *origins, const float *dirs, const float *t, size_t n_rays,
+                              int spr, float far_, float cut_T, float *pre_out, uint32_t *nonfinite_tiles);
 
 /* "" for the product build.  Tuning / timing-only builds (make variant: some of their switches make results WRONG on purpose)
  * report "NAME: compile definitions"; a host should refuse such a library outside experiments (the Python loader does). */
@@ -805,7 +861,9 @@ const char *nerf_build_variant(void);
  * nerf_extract_mesh_filtered_device, nerf_render_rays, nerf_render_rays_device, nerf_density_gradient_batch,
  * nerf_density_gradient_batch_device, nerf_render_rays_normals, nerf_render_rays_normals_device, nerf_stage_cert_plan,
  * nerf_stage_cert_verify, nerf_stage_cert_audit, nerf_stage_prefilter, nerf_occupancy_dilate, nerf_occupancy_dilate_device, nerf_clip_rays,
- * nerf_clip_rays_device, nerf_debug_clip_rays, nerf_render_rays_clipped, nerf_render_rays_clipped_device). */
+ * nerf_clip_rays_device, nerf_debug_clip_rays, nerf_render_rays_clipped, nerf_render_rays_clipped_device, nerf_render_rays_certified,
+ * nerf_render_rays_certified_device, nerf_render_rays_clipped_certified, nerf_render_rays_clipped_certified_device,
+ * nerf_stage_prefilter_rays). */
 int nerf_abi_version(void);
 /* sizeof(nerf_camera), sizeof(nerf_render_opts), sizeof(nerf_stats) as this library was built: lets a binding written in
  * another language (the Rust `-sys` crate, ctypes) check its struct mirrors at start-up. */

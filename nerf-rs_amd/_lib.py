@@ -176,7 +176,12 @@ PROTOTYPES = {
     "nerf_stage_cert_verify": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_uint32, f32p, i32p, f32p, u32p, u32p, u32p]),
     "nerf_stage_cert_audit": (C.c_int, [C.c_void_p, u32p, C.c_uint32, C.c_uint32, C.c_size_t, f32p, u32p]),
     "nerf_stage_prefilter": (C.c_int, [C.c_void_p, C.c_int, C.c_int, f32p, f32p, f32p, C.c_size_t, C.c_int, C.c_float, C.c_float, f32p, u32p]),
+    "nerf_stage_prefilter_rays": (C.c_int, [C.c_void_p, C.c_int, C.c_int, f32p, f32p, f32p, C.c_size_t, C.c_int, C.c_float, C.c_float, f32p, u32p]),
 }
+# the certified ray batches (zero certification inside every pass) take the argument lists of their uncertified counterparts
+for _name in ("nerf_render_rays", "nerf_render_rays_device", "nerf_render_rays_clipped", "nerf_render_rays_clipped_device"):
+    PROTOTYPES[_name.replace("nerf_render_rays", "nerf_render_rays_certified") if "clipped" not in _name
+               else _name.replace("clipped", "clipped_certified")] = (PROTOTYPES[_name][0], list(PROTOTYPES[_name][1]))
 
 
 def lib_path():

@@ -204,15 +204,21 @@ class Renderer:
         check(self._L.nerf_stage_cert_audit(self.handle, a.ctypes.data_as(u32p), n, cap, s.size, _p(s), w.ctypes.data_as(u32p)), self.handle)
         return s, w
 
-    def stage_prefilter(self, which, origin, dirs, t, far, f16=True, cut_T=0.0):
-        """The ray-sequential 16-bit pre-filter of network `which` -> (raw pre-activations (R, spr), non-finite tile count)."""
-        o = _f32(origin).reshape(3); d = _f32(dirs).reshape(-1, 3); tt = _f32(t)
+    def stage_prefilter(self, which, origin, dirs, t, far, f16=True, cut_T=0.0, origins=None):
+        """The ray-sequential 16-bit pre-filter of network `which` -> (raw pre-activations (R, spr), non-finite tile count).
+        origins (R, 3) in place of origin (then None): one origin per ray (nerf_stage_prefilter_rays)."""
+        d = _f32(dirs).reshape(-1, 3); tt = _f32(t)
         R, spr = tt.shape
         if len(d) != R:
             raise NerfError(-1, "dirs must hold one direction per ray")
+        if (origin is None) == (origins is None):
+            raise NerfError(-1, "give either origin or origins")
+        o = _f32(origin).reshape(3) if origins is None else _f32(origins).reshape(-1, 3)
+        if origins is not None and len(o) != R:
+            raise NerfError(-1, "origins must hold one origin per ray")
         out = np.empty((R, spr), np.float32); bad = np.zeros(1, np.uint32)
-        check(self._L.nerf_stage_prefilter(self.handle, int(which), int(bool(f16)), _p(o), _p(d), _p(tt), R, spr, far, cut_T, _p(out),
-                                           bad.ctypes.data_as(u32p)), self.handle)
+        call = self._L.nerf_stage_prefilter if origins is None else self._L.nerf_stage_prefilter_rays
+        check(call(self.handle, int(which), int(bool(f16)), _p(o), _p(d), _p(tt), R, spr, far, cut_T, _p(out), bad.ctypes.data_as(u32p)), self.handle)
         return out, int(bad[0])
 
 
@@ -671,7 +677,8 @@ def _ray_opts(n_coarse, fine_samples_per_ray, seed, coarse_only, dtype):
 
 
 def render_rays(coarse, fine, origins, dirs, near, far, fine_samples_per_ray=128, *, n_coarse=64, bounds=None, normalize=True,
-                rng_index=None, seed=0, coarse_only=False, dtype="f32", background=None, aux=False, return_stats=False, normals_h=None):
+                rng_index=None, seed=0, coarse_only=False, dtype="f32", background=None, aux=False, return_stats=False, normals_h=None,
+                certify_zero=False):
     """The caller's rays instead of a camera's (nerf_render_rays) -> rgb (n, 3) float32.
 
     origins: (3,) -- one origin for every ray -- or (n, 3); dirs: (n, 3), normalised on the device unless normalize=False (the caller
@@ -682,7 +689,11 @@ def render_rays(coarse, fine, origins, dirs, near, far, fine_samples_per_ray=128
     normals_h: a central-difference step h (finite, > 0) -> the per-ray normals (n, 3) follow the other arrays (the fourth array with
     aux=True): minus the weighted sum of the density gradients at the live samples, normalised; zero for a ray without a live sample
     (nerf_render_rays_normals).  Colour, depth and opacity keep their bits.
-    The per-pixel options of render_image (crop, ssaa, bands, the skip modes) do not exist for rays."""
+    certify_zero=True: zero certification inside every pass, as render_image(certify_zero=True) -- the same bits for a fraction of the
+    network evaluations (nerf_render_rays_certified; dtype f32, bf16x3 or f16x2; not with normals_h); the stats carry the audit.
+    The other per-pixel options of render_image (crop, ssaa, bands, skip_empty, skip_dead, hybrid_sampling) do not exist for rays."""
+    if certify_zero and normals_h is not None:
+        raise NerfError(-1, "normals are not offered on a certified batch")
     R = coarse.renderer
     if fine is not None and fine.renderer is not R:
         raise NerfError(-1, "coarse and fine networks must live in the same Renderer")
@@ -707,7 +718,9 @@ def render_rays(coarse, fine, origins, dirs, near, far, fine_samples_per_ray=128
     head = (R.handle, _p(o), 1 if o.ndim == 1 else n, _p(d), n, int(bool(normalize)), float(near), float(far),
             None if b is None else _p(b), None if idx is None else idx.ctypes.data_as(u32p), C.byref(opts), bg,
             _p(rgb), None if depth is None else _p(depth), None if opacity is None else _p(opacity))
-    if normals_h is None:
+    if certify_zero:
+        check(R._L.nerf_render_rays_certified(*head, C.byref(st)), R.handle)
+    elif normals_h is None:
         check(R._L.nerf_render_rays(*head, C.byref(st)), R.handle)
     else:
         normals = np.empty((n, 3), np.float32)
@@ -722,13 +735,16 @@ def render_rays(coarse, fine, origins, dirs, near, far, fine_samples_per_ray=128
 
 def render_rays_device(coarse, fine, d_origins, n_origins, d_dirs, n_rays, near, far, fine_samples_per_ray, d_rgb, *, n_coarse=64,
                        d_bounds=None, normalize=True, d_rng_index=None, seed=0, coarse_only=False, dtype="f32", background=None,
-                       d_depth=None, d_opacity=None, stream=0, return_stats=False, d_normals=None, normals_h=None):
+                       d_depth=None, d_opacity=None, stream=0, return_stats=False, d_normals=None, normals_h=None, certify_zero=False):
     """nerf_render_rays_device: raw device pointers (ints; d_bounds, d_rng_index, d_depth, d_opacity may be None), asynchronous on
     `stream` (n_origins == 1 reads the origin back first and synchronises the stream once; return_stats synchronises it at the end).
     n_origins is 1 or n_rays.  d_normals (n_rays x 3 floats) together with normals_h: nerf_render_rays_normals_device, which
-    synchronises the stream once per pass to read that pass's live count.  Returns None / the stats."""
+    synchronises the stream once per pass to read that pass's live count.  certify_zero=True: nerf_render_rays_certified_device, which
+    always synchronises the stream before returning (the audit is read on the host); not with normals.  Returns None / the stats."""
     if (d_normals is None) != (normals_h is None):
         raise NerfError(-1, "d_normals and normals_h go together")
+    if certify_zero and d_normals is not None:
+        raise NerfError(-1, "normals are not offered on a certified batch")
     R = coarse.renderer
     if fine is not None and fine.renderer is not R:
         raise NerfError(-1, "coarse and fine networks must live in the same Renderer")
@@ -737,7 +753,9 @@ def render_rays_device(coarse, fine, d_origins, n_origins, d_dirs, n_rays, near,
     st = CStats()
     head = (R.handle, d_origins, int(n_origins), d_dirs, int(n_rays), int(bool(normalize)), float(near), float(far),
             d_bounds, d_rng_index, C.byref(opts), bg, d_rgb, d_depth, d_opacity)
-    if d_normals is None:
+    if certify_zero:
+        check(R._L.nerf_render_rays_certified_device(*head, stream, C.byref(st) if return_stats else None), R.handle)
+    elif d_normals is None:
         check(R._L.nerf_render_rays_device(*head, stream, C.byref(st) if return_stats else None), R.handle)
     else:
         check(R._L.nerf_render_rays_normals_device(*head, float(normals_h), d_normals, stream, C.byref(st) if return_stats else None), R.handle)
@@ -835,12 +853,13 @@ def clip_rays_device(renderer, d_bits, lo, step, dims, d_origins, n_origins, d_d
 
 def render_rays_clipped(coarse, fine, bits, lo, step, dims, origins, dirs, near, far, fine_samples_per_ray=128, *, n_coarse=64, bounds=None,
                         normalize=True, rng_index=None, seed=0, coarse_only=False, dtype="f32", background=None, aux=False,
-                        return_hit=False, return_stats=False):
+                        return_hit=False, return_stats=False, certify_zero=False):
     """render_rays behind clip_rays, on the device (nerf_render_rays_clipped): the rays that cross an occupied cell of the grid are
     rendered over their clipped bounds -- the bits of render_rays for those rays alone with bounds = clip_rays' and rng_index = their
     own index --, the others get the background, depth 0 and opacity 0 without a network evaluation.  Arguments as render_rays plus
     the grid (bits, lo, step, dims as density_grid / dilate_occupancy give them).  return_hit: hit (n,) bool and the number of hits
-    follow the arrays; the stats (those of the compacted batch: n_rays = hits) follow if return_stats."""
+    follow the arrays; the stats (those of the compacted batch: n_rays = hits) follow if return_stats.  certify_zero=True: the compacted
+    batch is rendered with zero certification (nerf_render_rays_clipped_certified) -- the same bits."""
     R = coarse.renderer
     if fine is not None and fine.renderer is not R:
         raise NerfError(-1, "coarse and fine networks must live in the same Renderer")
@@ -857,7 +876,8 @@ def render_rays_clipped(coarse, fine, bits, lo, step, dims, origins, dirs, near,
     rgb = np.empty((n, 3), np.float32)
     depth, opacity = (np.empty(n, np.float32), np.empty(n, np.float32)) if aux else (None, None)
     hit, cnt, st = np.empty(n, np.uint8), C.c_uint64(0), CStats()
-    check(R._L.nerf_render_rays_clipped(R.handle, words.ctypes.data_as(u32p), _p(lo_c), _p(step_c), dims_c.ctypes.data_as(i32p), _p(o),
+    call = R._L.nerf_render_rays_clipped_certified if certify_zero else R._L.nerf_render_rays_clipped
+    check(call(R.handle, words.ctypes.data_as(u32p), _p(lo_c), _p(step_c), dims_c.ctypes.data_as(i32p), _p(o),
                                         1 if o.ndim == 1 else n, _p(d), n, int(bool(normalize)), float(near), float(far),
                                         None if b is None else _p(b), None if idx is None else idx.ctypes.data_as(u32p), C.byref(opts), bg,
                                         _p(rgb), None if depth is None else _p(depth), None if opacity is None else _p(opacity),
@@ -872,9 +892,10 @@ def render_rays_clipped(coarse, fine, bits, lo, step, dims, origins, dirs, near,
 
 def render_rays_clipped_device(coarse, fine, d_bits, lo, step, dims, d_origins, n_origins, d_dirs, n_rays, near, far, fine_samples_per_ray,
                                d_rgb, *, n_coarse=64, d_bounds=None, normalize=True, d_rng_index=None, seed=0, coarse_only=False, dtype="f32",
-                               background=None, d_depth=None, d_opacity=None, d_hit=None, stream=0, return_stats=False):
+                               background=None, d_depth=None, d_opacity=None, d_hit=None, stream=0, return_stats=False, certify_zero=False):
     """nerf_render_rays_clipped_device: raw device pointers (ints; d_bounds, d_rng_index, d_depth, d_opacity, d_hit may be None).
     Synchronises `stream` once after the clip (the hit count sizes the render); what follows is asynchronous unless return_stats.
+    certify_zero=True: nerf_render_rays_clipped_certified_device, which also synchronises the stream before returning.
     Returns the number of hits, or (hits, stats)."""
     R = coarse.renderer
     if fine is not None and fine.renderer is not R:
@@ -883,7 +904,8 @@ def render_rays_clipped_device(coarse, fine, d_bits, lo, step, dims, d_origins, 
     opts = _ray_opts(n_coarse, fine_samples_per_ray, seed, coarse_only, dtype)
     keep, bg = _background(background)
     cnt, st = C.c_uint64(0), CStats()
-    check(R._L.nerf_render_rays_clipped_device(R.handle, d_bits, _p(lo_c), _p(step_c), dims_c.ctypes.data_as(i32p), d_origins, int(n_origins),
+    call = R._L.nerf_render_rays_clipped_certified_device if certify_zero else R._L.nerf_render_rays_clipped_device
+    check(call(R.handle, d_bits, _p(lo_c), _p(step_c), dims_c.ctypes.data_as(i32p), d_origins, int(n_origins),
                                                d_dirs, int(n_rays), int(bool(normalize)), float(near), float(far), d_bounds, d_rng_index,
                                                C.byref(opts), bg, d_rgb, d_depth, d_opacity, d_hit, C.byref(cnt), stream,
                                                C.byref(st) if return_stats else None), R.handle)

@@ -179,7 +179,8 @@ __device__ __forceinline__ void rgb_head(const Tiles &V, const LDS_AS float *sma
 
 // Raw per-point inputs: 6 floats.  MODE_POINTS: position + direction as given (src/network.rs:197).  MODE_RAYS:
 // (t, unused, unused) + the ray's unit direction; p = origin + dir_hat * t is formed at use with the multiply and the
-// add rounded separately (src/lib.rs:396 / :436).  The index is clamped: padding lanes of the last tile and the
+// add rounded separately (src/lib.rs:396 / :436; MODE 2 alone takes the origin of the entry's ray from MlpArgs.ray_origins when that is
+// set: point_of).  The index is clamped: padding lanes of the last tile and the
 // look-ahead tile read the last point.  MODE 3 (MLP_MODE_GRID) and 4 (MLP_MODE_POINTS without directions) belong to the f32
 // sigma-only kernel (mlp_kernel.hip) alone.
 struct RawIn { float a, b, c, dx, dy, dz; };
@@ -258,9 +259,17 @@ __device__ __forceinline__ void point_of(const Args &A, const RawIn &in, float &
         py = __fadd_rn(A.grid_lo[1], __fmul_rn(A.grid_step[1], in.b));
         pz = __fadd_rn(A.grid_lo[2], __fmul_rn(A.grid_step[2], in.c));
     } else {
-        px = __fadd_rn(A.origin[0], __fmul_rn(in.dx, in.a));
-        py = __fadd_rn(A.origin[1], __fmul_rn(in.dy, in.a));
-        pz = __fadd_rn(A.origin[2], __fmul_rn(in.dz, in.a));
+        float ox = A.origin[0], oy = A.origin[1], oz = A.origin[2];
+        if (MODE == 2) { // a certified ray batch with per-ray origins (MlpArgs.ray_origins; wave-uniform test): the entry rides in in.b
+            if (A.ray_origins) {
+                const unsigned ray = (__builtin_bit_cast(unsigned, in.b) & 0x7fffffffu) / (unsigned)A.samples_per_ray;
+                const float *o = A.ray_origins + 3 * (size_t)ray;
+                ox = o[0]; oy = o[1]; oz = o[2];
+            }
+        }
+        px = __fadd_rn(ox, __fmul_rn(in.dx, in.a));
+        py = __fadd_rn(oy, __fmul_rn(in.dy, in.a));
+        pz = __fadd_rn(oz, __fmul_rn(in.dz, in.a));
     }
 }
 

@@ -56,6 +56,9 @@ struct MlpArgs {
     int wave_tiling;    // 0: a wave tile is 32 consecutive samples of one ray
     int rays_per_row;   // the launch's rays are whole rows of this many pixels; 0: unknown (caller-supplied ray batches), never tiled
     nerfmlp::RayLaunchMap ray_map;
+    // MLP_MODE_LIST (appended likewise): per-ray origins of a certified ray batch, n_rays x 3, device; the point of list entry idx is
+    // fl(ray_origins[idx / samples_per_ray] + fl(d * t)) per coordinate.  NULL: `origin` above.  No other mode reads it.
+    const float *ray_origins;
 };
 
 // Sets the dynamic-LDS attribute of every kernel instantiation on the current device.
@@ -121,6 +124,9 @@ struct SeqArgs {
     float prefilter_cut_T;
     int zero_skip;                   // f32 trunk: as MlpArgs.zero_skip (appended: the fields above keep their kernarg offsets)
     unsigned long long *zskip_stats; // as MlpArgs.zskip_stats
+    // 16-bit trunks without export (certify_zero's pre-filter; appended likewise): per-ray origins, n_rays x 3, device, read once per ray
+    // when a wave takes it from the queue.  NULL: `origin` above.  The f32 and split trunks and the exporting forms never read it.
+    const float *ray_origins;
 };
 struct ColourArgs {
     const float *wstream;      // the same stream (bottleneck + viewdirs part is used)

@@ -630,10 +630,11 @@ __global__ __launch_bounds__(256, 1) void V2SYM(nerf_trunk_seq_kernel_bf16, nerf
     work_init(W0, A);
     work_init(W1, A);
     for (;;) {
-        work_take(W0, A, lane);
-        work_take(W1, A, lane);
+        // without export (the pre-filter's form) a ray may bring its own origin (SeqArgs.ray_origins: certified ray batches)
+        work_take<!EXPORT>(W0, A, lane);
+        work_take<!EXPORT>(W1, A, lane);
         if (!work_vote(W0.ray < A.n_rays || W1.ray < A.n_rays, vote, wave, lane)) break;
-        const ChunkIn c0 = chunk_inputs(W0, A, p), c1 = chunk_inputs(W1, A, p);
+        const ChunkIn c0 = chunk_inputs<!EXPORT>(W0, A, p), c1 = chunk_inputs<!EXPORT>(W1, A, p);
         u32x4 E0[4], E1[4];
         {
             f32x16 E[2];

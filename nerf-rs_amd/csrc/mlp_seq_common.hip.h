@@ -23,6 +23,7 @@ struct RayWork {
     float T;                         // transmittance in front of the current chunk
     unsigned long long samples_done; // statistics: samples this wave evaluated (a ray's last chunk may be partial)
     unsigned long long live_done;    // statistics: samples with weight > 0 this wave found (in-kernel colour passes only)
+    float ox, oy, oz;                // PER_RAY_ORIGIN forms only (work_take, chunk_inputs): the origin of the ray under way
 };
 
 __device__ __forceinline__ void work_init(RayWork &W, const SeqArgs &A) {
@@ -31,10 +32,14 @@ __device__ __forceinline__ void work_init(RayWork &W, const SeqArgs &A) {
     W.T = 1.0f;
     W.samples_done = 0;
     W.live_done = 0;
+    W.ox = A.origin[0]; W.oy = A.origin[1]; W.oz = A.origin[2];
 }
 
 // Take the next ray from the device-side queue if the current one is finished, then vote: the four waves of a workgroup walk the
 // weight stream in lockstep, so they leave together once nobody has a ray.  Contains one workgroup barrier.  `vote` = 4 ints of LDS.
+// PER_RAY_ORIGIN (the 16-bit trunks without export: certify_zero's pre-filter): a ray taken from the queue brings its own origin when
+// SeqArgs.ray_origins is set -- one wave-uniform read per ray, not per sample.  The other forms never look at that field.
+template <bool PER_RAY_ORIGIN = false>
 __device__ __forceinline__ void work_take(RayWork &W, const SeqArgs &A, int lane) {
     if (W.chunk >= W.n_chunks) {
         unsigned r = 0;
@@ -46,6 +51,12 @@ __device__ __forceinline__ void work_take(RayWork &W, const SeqArgs &A, int lane
         } else W.ray = r < (unsigned)A.n_rays ? (int)r : A.n_rays;
         W.chunk = 0;
         W.T = 1.0f;
+        if (PER_RAY_ORIGIN) {
+            if (A.ray_origins && W.ray < A.n_rays) {
+                const float *o = A.ray_origins + 3 * (size_t)W.ray;
+                W.ox = o[0]; W.oy = o[1]; W.oz = o[2];
+            }
+        }
     }
 }
 
@@ -68,6 +79,7 @@ struct ChunkIn {
     float t, t_next, dx, dy, dz, px, py, pz;
 };
 
+template <bool PER_RAY_ORIGIN = false>
 __device__ __forceinline__ ChunkIn chunk_inputs(const RayWork &W, const SeqArgs &A, int p) {
     ChunkIn c;
     const int M = A.samples_per_ray;
@@ -79,9 +91,9 @@ __device__ __forceinline__ ChunkIn chunk_inputs(const RayWork &W, const SeqArgs 
     c.t_next = A.t[c.base + (c.s + 1 < M ? c.s + 1 : M - 1)];
     const float *dv = A.ray_dirs + 3 * (size_t)(c.has ? W.ray : 0);
     c.dx = dv[0]; c.dy = dv[1]; c.dz = dv[2];
-    c.px = __fadd_rn(A.origin[0], __fmul_rn(c.dx, c.t));
-    c.py = __fadd_rn(A.origin[1], __fmul_rn(c.dy, c.t));
-    c.pz = __fadd_rn(A.origin[2], __fmul_rn(c.dz, c.t));
+    c.px = __fadd_rn(PER_RAY_ORIGIN ? W.ox : A.origin[0], __fmul_rn(c.dx, c.t));
+    c.py = __fadd_rn(PER_RAY_ORIGIN ? W.oy : A.origin[1], __fmul_rn(c.dy, c.t));
+    c.pz = __fadd_rn(PER_RAY_ORIGIN ? W.oz : A.origin[2], __fmul_rn(c.dz, c.t));
     return c;
 }
 

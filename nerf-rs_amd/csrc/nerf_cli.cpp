@@ -17,6 +17,8 @@
 // --rays-normals FILE beside --rays-out adds n x 3 f32 per-ray normals (nerf_render_rays_normals; --normals-step H, default 1e-3, is the
 // central-difference step).  --normals FILE.ppm writes the normal map of the image run, encoded 0.5 n + 0.5 per component: the window's rays
 // (nerf_stage_ray_dirs, rng_index = row * nx + col) go through nerf_render_rays_normals once more on the first context.
+// --certify-zero beside --rays renders the batch with zero certification (nerf_render_rays_certified / _clipped_certified): the same bytes, and the
+// audit line of an image render.
 // --rays-occupancy FILE.bits beside --rays clips the rays to the occupied cells of an occupancy grid first (nerf_render_rays_clipped): FILE holds the
 // words --grid-occupancy wrote for the lattice that --density-grid / --grid-lo / --grid-step name (no grid output flag is then needed);
 // --occupancy-dilate R (1..4) grows it by R cells first (nerf_occupancy_dilate).  Rays that cross no occupied cell get the background.
@@ -200,8 +202,11 @@ int main(int argc, char **argv) {
                 occ.swap(grown);
             }
         }
-        if (!occ.empty() ? nerf_render_rays_clipped(ctx, occ.data(), grid_lo, grid_step, grid_dims, o.data(), n, d.data(), n, 1, jc.near_, jc.far_, rb, nullptr, &opts, bg,
-                                                    rgb.data(), nullptr, nullptr, nullptr, &n_hit, &rst)
+        const bool certified = opts.certify_zero != 0; // --certify-zero: the certified forms of the two calls, the same bytes in --rays-out
+        if (certified && !normals.empty()) { fprintf(stderr, "error: --rays-normals is not offered with --certify-zero\n"); return 1; }
+        if (!occ.empty() ? (certified ? nerf_render_rays_clipped_certified : nerf_render_rays_clipped)(ctx, occ.data(), grid_lo, grid_step, grid_dims, o.data(), n, d.data(), n, 1,
+                                                    jc.near_, jc.far_, rb, nullptr, &opts, bg, rgb.data(), nullptr, nullptr, nullptr, &n_hit, &rst)
+            : certified ? nerf_render_rays_certified(ctx, o.data(), n, d.data(), n, 1, jc.near_, jc.far_, rb, nullptr, &opts, bg, rgb.data(), nullptr, nullptr, &rst)
             : normals.empty() ? nerf_render_rays(ctx, o.data(), n, d.data(), n, 1, jc.near_, jc.far_, rb, nullptr, &opts, bg, rgb.data(), nullptr, nullptr, &rst)
                             : nerf_render_rays_normals(ctx, o.data(), n, d.data(), n, 1, jc.near_, jc.far_, rb, nullptr, &opts, bg, rgb.data(), nullptr, nullptr,
                                                        normals_step, normals.data(), &rst)) {
@@ -223,6 +228,11 @@ int main(int argc, char **argv) {
         } else
             printf("%zu rays (%d coarse + %d fine samples): device %.2f ms in %u pass(es)\n", n, opts.n_coarse, opts.coarse_only ? 0 : opts.n_fine, n ? rst.ms_total : 0.0,
                    n ? rst.n_passes : 0u);
+        if (certified && (occ.empty() ? n > 0 : n_hit > 0)) // the audit of the batch, as an image render prints it below
+            printf("certify_zero audit: %llu certificates evaluated all the same, %llu violations, margins %.3g / %.3g, least headroom %.3g / %.3g, largest bf16 error %.3g / %.3g, "
+                   "batch rendered again %u time(s), %u rays beyond their predicted cut\n", (unsigned long long)rst.n_certify_audited, (unsigned long long)rst.n_certify_violations,
+                   (double)rst.certify_margin[0], (double)rst.certify_margin[1], (double)rst.certify_headroom[0], (double)rst.certify_headroom[1],
+                   (double)rst.certify_max_error[0], (double)rst.certify_max_error[1], rst.n_certify_retries, rst.n_certify_fallback_rays);
         if (!want_image && !want_grid) {
             for (nerf_ctx *c : ctxs) nerf_destroy(c);
             return 0;

@@ -915,13 +915,16 @@ int nerf_stage_cert_audit(nerf_ctx *c, const uint32_t *aux, uint32_t aux_count, 
     return NERF_OK;
 } NERF_CATCH(c)
 
-int nerf_stage_prefilter(nerf_ctx *c, int which, int f16, const float origin[3], const float *dirs, const float *t, size_t n_rays, int spr,
-                         float far_, float cut_T, float *pre_out, uint32_t *nonfinite_tiles) try {
+} // extern "C"
+
+// nerf_stage_prefilter (origin: one for every ray) and nerf_stage_prefilter_rays (origins: n_rays x 3, SeqArgs.ray_origins)
+static int stage_prefilter(nerf_ctx *c, int which, int f16, const float *origin, const float *origins, const float *dirs, const float *t, size_t n_rays,
+                           int spr, float far_, float cut_T, float *pre_out, uint32_t *nonfinite_tiles) {
     if (which != NERF_NET_COARSE && which != NERF_NET_FINE) return fail(c, NERF_ERR_INVALID, "which must be NERF_NET_COARSE or NERF_NET_FINE");
     if (spr <= 0) return fail(c, NERF_ERR_INVALID, "spr must be positive");
     if (n_rays > (size_t)0x7fffffff / (size_t)spr) return fail(c, NERF_ERR_INVALID, "too many samples");
     if (!(cut_T >= 0.0f) || !(cut_T < 1.0f)) return fail(c, NERF_ERR_INVALID, "cut_T must lie in [0, 1)");
-    if (!origin || !dirs || !t || !pre_out || !nonfinite_tiles) return fail(c, NERF_ERR_INVALID, "NULL buffer");
+    if ((!origin && !origins) || !dirs || !t || !pre_out || !nonfinite_tiles) return fail(c, NERF_ERR_INVALID, "NULL buffer");
     if (!c) return fail(nullptr, NERF_ERR_INVALID, "ctx is NULL");
     const DevNet &net = c->net[which];
     if (!net.loaded) return fail(c, NERF_ERR_STATE, "network not loaded");
@@ -930,19 +933,21 @@ int nerf_stage_prefilter(nerf_ctx *c, int which, int f16, const float origin[3],
     if (n_rays == 0) return NERF_OK;
     DeviceGuard dg(c->device);
     const size_t N = n_rays * (size_t)spr;
-    // scratch (words): directions, t, pre-activations, {ray queue, non-finite tiles, samples evaluated (64 bits)}
-    const size_t o_d = 0, o_t = o_d + 3 * n_rays, o_p = o_t + N, o_cnt = (o_p + N + 1) & ~(size_t)1, total = o_cnt + 4;
+    // scratch (words): directions, t, pre-activations, {ray queue, non-finite tiles, samples evaluated (64 bits)}, [origins]
+    const size_t o_d = 0, o_t = o_d + 3 * n_rays, o_p = o_t + N, o_cnt = (o_p + N + 1) & ~(size_t)1, o_o = o_cnt + 4, total = o_o + (origins ? 3 * n_rays : 0);
     int rc;
     if ((rc = ensure_bytes(c, &c->d_scratch, &c->scratch_bytes, total * 4))) return rc;
     uint32_t *d = (uint32_t *)c->d_scratch;
     HIP_TRY(c, hipMemcpyAsync(d + o_d, dirs, 3 * n_rays * 4, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(d + o_t, t, N * 4, hipMemcpyHostToDevice, c->stream));
+    if (origins) HIP_TRY(c, hipMemcpyAsync(d + o_o, origins, 3 * n_rays * 4, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemsetAsync(d + o_p, 0xFF, N * 4, c->stream)); // NaN = "not evaluated", as cert_pass fills it
     HIP_TRY(c, hipMemsetAsync(d + o_cnt, 0, 4 * 4, c->stream));
     SeqArgs q{};
     q.wstream = f16 ? (const float *)net.wstream_f16v2 : stream_of(net, NERF_MLP_BF16); q.small_params = net.small;
     q.n_rays = (int)n_rays; q.samples_per_ray = spr; q.ray_dirs = (const float *)(d + o_d); q.t = (const float *)(d + o_t); q.far_ = far_;
-    copy3(q.origin, origin);
+    if (origins) q.ray_origins = (const float *)(d + o_o);
+    else copy3(q.origin, origin);
     q.sigma_out = (float *)(d + o_p);
     q.ray_counter = d + o_cnt; q.nonfinite = d + o_cnt + 1; q.stats = (unsigned long long *)(d + o_cnt + 2);
     q.prefilter = 1; q.prefilter_cut_T = cut_T;
@@ -951,6 +956,18 @@ int nerf_stage_prefilter(nerf_ctx *c, int which, int f16, const float origin[3],
     HIP_TRY(c, hipMemcpyAsync(nonfinite_tiles, d + o_cnt + 1, 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return NERF_OK;
+}
+
+extern "C" {
+
+int nerf_stage_prefilter(nerf_ctx *c, int which, int f16, const float origin[3], const float *dirs, const float *t, size_t n_rays, int spr,
+                         float far_, float cut_T, float *pre_out, uint32_t *nonfinite_tiles) try {
+    return stage_prefilter(c, which, f16, origin, nullptr, dirs, t, n_rays, spr, far_, cut_T, pre_out, nonfinite_tiles);
+} NERF_CATCH(c)
+
+int nerf_stage_prefilter_rays(nerf_ctx *c, int which, int f16, const float *origins, const float *dirs, const float *t, size_t n_rays, int spr,
+                              float far_, float cut_T, float *pre_out, uint32_t *nonfinite_tiles) try {
+    return stage_prefilter(c, which, f16, nullptr, origins, dirs, t, n_rays, spr, far_, cut_T, pre_out, nonfinite_tiles);
 } NERF_CATCH(c)
 
 } // extern "C"

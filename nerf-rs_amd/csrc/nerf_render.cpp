@@ -136,6 +136,7 @@ struct RenderJob {
     uint64_t seed;
     float near_, far_;       // the shared bounds ...
     float *d_far;            // ... or, for a batch with per-ray bounds, the far of each ray of the pass under way (k_batch_prepare writes it)
+    float far_cert;          // certify_zero: the far the certify kernels are given -- far_, or below every t for per-ray bounds (cert_pass)
     const float *background; // 3 floats, or NULL = the reference's white
     // outputs, per ray: the pass that starts at ray r0 writes out + 3 r0, depth + r0, opacity + r0 (r0 = row x RW of an image)
     float *out, *depth, *opacity;
@@ -143,16 +144,16 @@ struct RenderJob {
     int kind_colour;          // event kind of the colour-producing launch: 1 for images (-> c->dominant), 5 for batches
     const char *what;         // "frame" / "batch", for the non-finite error
     hipStream_t st;
-    // modes (images only: ray batches refuse them)
+    // modes (skip_empty, skip_dead, hybrid_sampling: images only, ray batches refuse them)
     int skip_empty;
-    bool seq, hybrid, certify; // skip_dead, hybrid_sampling with something to resample, certify_zero
+    bool seq, hybrid, certify; // skip_dead, hybrid_sampling with something to resample, certify_zero (batches: nerf_render_rays_certified)
     size_t cert_cap, aux_cap;  // certify_zero: capacity of the sample list and of the audit records
     unsigned long long *clock_out; // NERF_DEBUG_CLOCK: where the fine launch leaves its clocks
     // the ray source: a camera window (g: everything but the pass's own n_rays and first row) or the caller's rays
     const RayBatch *batch;
     RayGenArgs g;
     float origin[3];           // the shared origin (batches with per-ray origins: unused)
-    float *d_pts, *d_daos;     // per-ray origins: the points and per-sample directions of one launch (k_batch_points)
+    float *d_pts, *d_daos;     // per-ray origins, uncertified: the points and per-sample directions of one launch (k_batch_points)
     // normals (batches only): per-ray output, central-difference step, samples per ray the final compositing integrates, pass workspace
     float *normals; float h; int n_comp; NormalWorkspace nw;
 };
@@ -287,6 +288,10 @@ int seq_pass(nerf_ctx *c, const RenderJob &j, const Pass &p, const DevNet &net, 
 // Per network: 16-bit pre-activations of all samples -> plan (list 1, predicted cuts) -> exact kernel on list 1 -> audit -> exact
 // transmittance confirms the cuts (list 2 = what is left of the rays it does not) -> exact kernel on list 2.
 // a: the plain ray-mode launch of this network in arithmetic dt (eval_net), from which every launch here is derived.
+// A batch with per-ray origins (p.origins) hands them to the pre-filter and to the list launches as ray_origins: nothing is expanded into
+// points, and the fused pre-filter (NERF_CERTIFY_SEQ_PREFILTER=0), which knows one origin only, gives way to the ray-sequential one.
+// far_: only the interval behind a ray's LAST sample depends on it, and no certify kernel's result does: the kernels get
+// j.far_cert, the exact per-ray far stays with k_resample and k_composite.
 int cert_pass(nerf_ctx *c, const RenderJob &j, const Pass &p, const MlpArgs &a, const DevNet &net, int which, int dt, int kind) {
     const hipStream_t st = j.st;
     const int n_pts = a.n_points, spr = a.samples_per_ray;
@@ -299,22 +304,24 @@ int cert_pass(nerf_ctx *c, const RenderJob &j, const Pass &p, const MlpArgs &a, 
     const bool pf16 = c->cert_prefilter_f16[which];
     const float *pf_stream = pf16 ? (const float *)net.wstream_f16v2 : stream_of(net, NERF_MLP_BF16);
     MlpArgs b = a;
+    b.ray_origins = p.origins;
     b.wstream = pf_stream; b.small_params = net.small;
     b.rgb_out = nullptr; b.raw_pre = 1; b.skip_empty = 0; b.skip_counter = nullptr; b.nonfinite = pf16 ? slots + 12 : nullptr;
     const int kind_side = which == 0 && !rgb_out ? 0 : 4;
     int rc = timed(c, st, kind_side, 0, [&]() -> int {
-        if (c->cert_seq_prefilter) {
+        if (c->cert_seq_prefilter || p.origins) {
             // the pre-filter walks each ray front to back and stops where its own (bf16) transmittance predicts the cut, a little
             // later than k_cert_plan will (depth + 0.5): samples it never reaches stay NaN = "not evaluated" = uncertain
             HIP_TRY(c, hipMemsetAsync(sigma_out, 0xFF, (size_t)n_pts * sizeof(float), st));
             SeqArgs q = seq_args(c, j, p, pf_stream, net.small, spr, t_in, sigma_out);
+            q.far_ = j.far_cert; q.ray_origins = p.origins;
             q.ray_counter = slots + 8; q.stats = (unsigned long long *)(slots + 10);
             q.prefilter = 1; q.prefilter_cut_T = expf(-(c->cert_depth_limit + 0.5f));
             q.nonfinite = pf16 ? slots + 12 : nullptr;
             HIP_TRY(c, pf16 ? nerf_trunk_seq_f16v2_launch(q, c->n_cus, st) : nerf_trunk_seq_bf16_launch(q, false, c->n_cus, st));
         } else HIP_TRY(c, pf16 ? nerf_mlp_f16v2_launch(b, c->n_cus, st) : launch_mlp(c, NERF_MLP_BF16, b, false, st));
         CertPlanArgs q{};
-        q.pre = sigma_out; q.t = t_in; q.n_rays = p.n_rays; q.spr = spr; q.far_ = j.far_;
+        q.pre = sigma_out; q.t = t_in; q.n_rays = p.n_rays; q.spr = spr; q.far_ = j.far_cert;
         q.margin = c->cert_margin[which]; q.depth_limit = c->cert_depth_limit;
         q.audit_mask = c->cert_audit_mask; q.audit_mask_near = c->cert_audit_mask_near;
         q.audit_salt = (unsigned)(j.seed * 0x9E3779B97F4A7C15ull >> 32) + 0x632BE5ABu * p.index + (unsigned)which;
@@ -339,7 +346,7 @@ int cert_pass(nerf_ctx *c, const RenderJob &j, const Pass &p, const MlpArgs &a, 
     return timed(c, st, kind_side, 0, [&]() -> int {
         HIP_TRY(c, launch_cert_audit(c->d_cert_aux, slots + 7, (unsigned)j.aux_cap, sigma_out, slots + 2, c->n_cus, st));
         CertVerifyArgs v{};
-        v.t = t_in; v.sigma = sigma_out; v.n_rays = p.n_rays; v.spr = spr; v.far_ = j.far_; v.jstar = c->d_jstar;
+        v.t = t_in; v.sigma = sigma_out; v.n_rays = p.n_rays; v.spr = spr; v.far_ = j.far_cert; v.jstar = c->d_jstar;
         v.list = c->d_point_list; v.count = slots + 1; v.capacity = cap; v.fallback_rays = slots + 6;
         HIP_TRY(c, launch_cert_verify(v, st));
         l.point_list_count = slots + 1; l.point_list_count_back = nullptr;
@@ -349,16 +356,17 @@ int cert_pass(nerf_ctx *c, const RenderJob &j, const Pass &p, const MlpArgs &a, 
 }
 
 // steps 2 and 5: network `which` in arithmetic dt over the spr samples per ray at t of the pass's rays; rgb_out == NULL: densities only.
-// Four ways: ray-sequential (skip_dead), certified (certify_zero), or plainly -- in ray mode from the shared origin (the origin rides in the
-// kernel arguments), or for per-ray origins in points mode behind k_batch_points, which expands the samples into points + per-sample
-// directions; points mode forms nothing itself and then runs the same per-column arithmetic: the two plain paths carry the same bits.
+// Four ways: ray-sequential (skip_dead), certified (certify_zero: per-ray origins go along as ray_origins, cert_pass), or plainly -- in ray
+// mode from the shared origin (the origin rides in the kernel arguments), or for per-ray origins in points mode behind k_batch_points, which
+// expands the samples into points + per-sample directions; points mode forms nothing itself and then runs the same per-column arithmetic:
+// the two plain paths carry the same bits.
 int eval_net(nerf_ctx *c, const RenderJob &j, const Pass &p, int which, int dt, int spr, const float *t, float *sigma_out, float *rgb_out, int kind) {
     const DevNet &net = c->net[which];
     if (j.seq) return seq_pass(c, j, p, net, dt, spr, t, sigma_out, rgb_out, 3 * (int)p.index + which, kind);
     const hipStream_t st = j.st;
     MlpArgs a{};
     a.ray_dirs = c->d_dirs;
-    if (p.origins) a.mode = MLP_MODE_POINTS;
+    if (p.origins && !j.certify) a.mode = MLP_MODE_POINTS;
     else { a.mode = MLP_MODE_RAYS; copy3(a.origin, j.origin); }
     a.wstream = stream_of(net, dt); a.small_params = small_of(net, dt); zskip_of(c, net, a);
     a.n_points = p.n_rays * spr; a.samples_per_ray = spr; a.t = t;
@@ -721,7 +729,7 @@ int render_once(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *o, 
     if ((rc = check_sample_plan(c, o, PLAN_LIMITS))) return rc;
     RenderJob j{};
     plan_job(c, o, j);
-    j.near_ = cam->near_; j.far_ = cam->far_; j.background = background;
+    j.near_ = cam->near_; j.far_ = cam->far_; j.far_cert = j.far_; j.background = background;
     j.kind_colour = 1; j.what = "frame"; j.st = st;
     j.skip_empty = o->skip_empty; j.seq = o->skip_dead != 0; j.certify = o->certify_zero != 0;
     j.hybrid = o->hybrid_sampling != 0 && j.nf > 0; // without resampling there is nothing to protect
@@ -787,8 +795,11 @@ int render_once(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *o, 
 // tied to either; a pass is at most max_rays_per_pass rays (rays * samples <= 0x3fffffff, as above).
 // arguments already checked (check_ray_batch, check_normals); asynchronous on st unless stats != NULL or d_normals != NULL (n_rays x 3: the
 // compositing launch then also hands out its weights, and normals_pass follows it in every pass).
+// cert != NULL: one attempt at a certified batch (nerf_render_rays_certified; certify_retry decides whether it stands) -- zero certification
+// inside every pass, per-ray origins as ray_origins of the certified kernels (no expansion, no 24-byte-per-sample workspace); synchronises
+// st, because the audit is read on the host.
 int render_rays_device(nerf_ctx *c, const RayBatch &b, const nerf_render_opts *o, const float *background, float *d_out, float *d_depth,
-                       float *d_opacity, hipStream_t st, nerf_stats *stats, float h = 0.0f, float *d_normals = nullptr) {
+                       float *d_opacity, hipStream_t st, nerf_stats *stats, float h = 0.0f, float *d_normals = nullptr, CertOutcome *cert = nullptr) {
     int rc;
     if ((rc = check_sample_plan(c, o, PLAN_NETWORKS))) return rc;
     RenderJob j{};
@@ -799,6 +810,9 @@ int render_rays_device(nerf_ctx *c, const RayBatch &b, const nerf_render_opts *o
     // belong to image renders)
     j.kind_colour = 5; j.what = "batch"; j.st = st;
     j.batch = &b; j.normals = d_normals; j.h = h;
+    j.certify = cert != nullptr;
+    // per-ray bounds: a finite far below every t -- the certify kernels' interval behind the last sample is clamped to 0 (cert_pass)
+    j.far_cert = b.d_bounds ? -3.0e38f : b.far_;
     size_t pass_cap = pass_capacity(c, j.M);
     // normals: if every sample of a pass were live its 6 stencil points each must still fit one MLP launch
     if (d_normals) pass_cap = std::max<size_t>(1, std::min<size_t>(pass_cap, max_batch_points(c->n_cus) / (6 * (size_t)j.M)));
@@ -809,23 +823,26 @@ int render_rays_device(nerf_ctx *c, const RayBatch &b, const nerf_render_opts *o
     j.nw = NormalWorkspace(c->d_normal, j.pass_rays, j.pass_rays * (size_t)j.n_comp);
     c->normal_live = 0; c->normal_samples = 0;
     // c->d_batch (floats): [far per ray, padded to 64][points 3 x n SoA][directions n x 3 AoS], n = the pass's rays x M
-    const bool expand = b.d_origins != nullptr;
+    const bool expand = b.d_origins != nullptr && !j.certify;
     const size_t far_floats = b.d_bounds ? (j.pass_rays + 63) / 64 * 64 : 0, n_max = j.pass_rays * (size_t)j.M;
     if (far_floats || expand) {
         if ((rc = ensure_bytes(c, &c->d_batch, &c->batch_bytes, (far_floats + (expand ? 6 * n_max : 0)) * sizeof(float)))) return rc;
         j.d_far = b.d_bounds ? (float *)c->d_batch : nullptr;
         j.d_pts = (float *)c->d_batch + far_floats; j.d_daos = j.d_pts + 3 * n_max;
     }
-    if (!expand) copy3(j.origin, b.h_origin);
+    if (b.h_origin) copy3(j.origin, b.h_origin);
+    if (j.certify && (rc = reserve_certify(c, j, (j.n_rays + j.pass_rays - 1) / j.pass_rays, cert))) return rc;
     recycle_render(c);
     uint32_t passes = 0;
     if ((rc = render_passes(c, j, &passes))) return rc;
-    return finish_stats(c, j, passes, stats, nullptr);
+    if (cert && (rc = read_cert_outcome(c, j, passes, cert))) return rc;
+    return finish_stats(c, j, passes, stats, cert);
 }
 
 // everything nerf_render_rays* can refuse without a context or a device, in the header's order
+// certified: the nerf_render_rays*_certified forms -- the entry point is the switch, opts->certify_zero is only checked for its range
 int check_ray_batch(nerf_ctx *c, const void *origins, size_t n_origins, const void *dirs, size_t n_rays, float near_, float far_, const void *bounds,
-                    const nerf_render_opts *o, const float *background, const void *rgb_out) {
+                    const nerf_render_opts *o, const float *background, const void *rgb_out, bool certified = false) {
     if (!o) return fail(c, NERF_ERR_INVALID, "opts is NULL");
     if (n_rays > (size_t)0x7fffffff) return fail(c, NERF_ERR_INVALID, "n_rays must be at most INT32_MAX");
     if (n_rays > 0 && (!origins || !dirs || !rgb_out)) return fail(c, NERF_ERR_INVALID, "origins, dirs and rgb_out must not be NULL");
@@ -833,10 +850,13 @@ int check_ray_batch(nerf_ctx *c, const void *origins, size_t n_origins, const vo
     if (o->crop_x0 || o->crop_y0 || o->crop_w || o->crop_h) return fail(c, NERF_ERR_INVALID, "ray batches have no pixel grid: crop_* must be 0");
     if (o->ssaa > 1) return fail(c, NERF_ERR_INVALID, "ray batches have no pixel grid: ssaa must be 0 or 1");
     if (o->band_count > 1) return fail(c, NERF_ERR_INVALID, "ray batches have no rows: band_count must be 0 or 1");
-    if (o->skip_empty || o->skip_dead || o->hybrid_sampling || o->certify_zero)
+    if (o->skip_empty || o->skip_dead || o->hybrid_sampling || (o->certify_zero && !certified))
         return fail(c, NERF_ERR_INVALID, "skip_empty, skip_dead, hybrid_sampling and certify_zero are not available for ray batches (first version)");
+    if (o->certify_zero != 0 && o->certify_zero != 1) return fail(c, NERF_ERR_INVALID, "certify_zero must be 0 or 1");
     int rc;
     if ((rc = check_sample_plan(c, o, PLAN_COUNTS))) return rc;
+    if (certified && o->mlp_dtype == NERF_MLP_BF16) // the image path's refusal (check_image_modes)
+        return fail(c, NERF_ERR_INVALID, "certify_zero needs mlp_dtype F32, BF16X3 or F16X2 and neither skip_empty nor skip_dead");
     if (!bounds) {
         if (!std::isfinite(near_) || !std::isfinite(far_)) return fail(c, NERF_ERR_INVALID, "near_ and far_ must be finite when bounds is NULL");
         if (!(far_ > near_)) return fail(c, NERF_ERR_INVALID, "far_ must be greater than near_ when bounds is NULL");
@@ -873,23 +893,22 @@ int check_normals(nerf_ctx *c, float h, const void *normals_out) {
     return NERF_OK;
 }
 
-} // namespace
-
-// certify_zero frames are AUDITED (k_cert_audit: 1 in 16 of the samples certified by less than twice the margin and 1 in 128 of the others are evaluated exactly all the same).  A frame stands only if no
+// certify_zero renders are AUDITED (k_cert_audit: 1 in 16 of the samples certified by less than twice the margin and 1 in 128 of the others are evaluated exactly all the same).  A frame stands only if no
 // audited certificate was wrong and the closest audited sample kept at least half the margin between itself and a positive density;
 // otherwise the network's margin is widened -- for good: c->cert_margin is per context and network, reset when a network is loaded --
 // and the frame is rendered again.  The same loop grows the sample list when a pass wanted more entries than it had.  Margins are
 // measurements, not proofs: what this buys is that a network on which bf16 is less accurate than on the lego scene
 // calibrates itself or fails loudly (NERF_ERR_STATE) instead of returning a silently different frame.
 // Every attempt writes the whole frame -- colour and the requested maps -- so the maps returned are those of the frame that stands.
-int nerfint::render_device(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *o, float *d_out, float *d_depth, float *d_opacity,
-                           hipStream_t st, nerf_stats *stats, const float *background) {
-    if (!o || !o->certify_zero) return render_once(c, cam, o, d_out, d_depth, d_opacity, st, stats, nullptr, background);
+// One copy for image renders (render_device) and certified ray batches (rays_certified_device, rays_clipped_device): attempt(&outcome)
+// renders the whole frame / batch once; what = "frame" / "batch".
+template <class Attempt>
+int certify_retry(nerf_ctx *c, nerf_stats *stats, const char *what, Attempt attempt) {
     constexpr int kMaxRetries = 8;
     uint64_t violations = 0;
-    for (int attempt = 0;; ++attempt) {
+    for (int tries = 0;; ++tries) {
         CertOutcome oc;
-        const int rc = render_once(c, cam, o, d_out, d_depth, d_opacity, st, stats, &oc, background);
+        const int rc = attempt(&oc);
         if (rc) return rc;
         bool again = false;
         std::string why;
@@ -918,15 +937,23 @@ int nerfint::render_device(nerf_ctx *c, const nerf_camera *cam, const nerf_rende
                                                                                  : "the 16-bit pass was off by more than half the margin on an audited certificate";
             }
         }
-        if (stats) { stats->n_certify_retries = (uint32_t)attempt; stats->n_certify_violations = violations; }
+        if (stats) { stats->n_certify_retries = (uint32_t)tries; stats->n_certify_violations = violations; }
         if (!again) return NERF_OK;
-        if (attempt == kMaxRetries) {
+        if (tries == kMaxRetries) {
             char msg[320];
-            snprintf(msg, sizeof msg, "certify_zero: %s after %d renders of this frame (margins now %g / %g): the 16-bit pass cannot certify this network's "
-                     "zero densities; render with certify_zero = 0", why.c_str(), attempt + 1, (double)c->cert_margin[0], (double)c->cert_margin[1]);
+            snprintf(msg, sizeof msg, "certify_zero: %s after %d renders of this %s (margins now %g / %g): the 16-bit pass cannot certify this network's "
+                     "zero densities; render with certify_zero = 0", why.c_str(), tries + 1, what, (double)c->cert_margin[0], (double)c->cert_margin[1]);
             return fail(c, NERF_ERR_STATE, msg);
         }
     }
+}
+
+} // namespace
+
+int nerfint::render_device(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *o, float *d_out, float *d_depth, float *d_opacity,
+                           hipStream_t st, nerf_stats *stats, const float *background) {
+    if (!o || !o->certify_zero) return render_once(c, cam, o, d_out, d_depth, d_opacity, st, stats, nullptr, background);
+    return certify_retry(c, stats, "frame", [&](CertOutcome *oc) { return render_once(c, cam, o, d_out, d_depth, d_opacity, st, stats, oc, background); });
 }
 
 int nerfint::output_window(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *opts, size_t *w_out, size_t *h_out) {
@@ -1034,13 +1061,13 @@ int nerf_render_image_rgba8(nerf_ctx *c, const nerf_camera *cam, const nerf_rend
 } NERF_CATCH(c)
 
 // ---- ray batches ---------------------------------------------------------------------------------------------------------------------
-// nerf_render_rays_device and nerf_render_rays_normals_device (want_normals)
+// nerf_render_rays_device, nerf_render_rays_normals_device (want_normals) and nerf_render_rays_certified_device (certified)
 static int rays_device(nerf_ctx *c, const float *d_origins, size_t n_origins, const float *d_dirs, size_t n_rays, int normalize, float near_,
                        float far_, const float *d_bounds, const uint32_t *d_rng_index, const nerf_render_opts *opts, const float background[3],
                        float *d_rgb_out, float *d_depth_out, float *d_opacity_out, bool want_normals, float h, float *d_normals_out, void *stream,
-                       nerf_stats *stats) {
+                       nerf_stats *stats, bool certified = false) {
     int rc;
-    if ((rc = check_ray_batch(c, d_origins, n_origins, d_dirs, n_rays, near_, far_, d_bounds, opts, background, d_rgb_out))) return rc;
+    if ((rc = check_ray_batch(c, d_origins, n_origins, d_dirs, n_rays, near_, far_, d_bounds, opts, background, d_rgb_out, certified))) return rc;
     if (want_normals && (rc = check_normals(c, h, d_normals_out))) return rc;
     if (!c) return fail(nullptr, NERF_ERR_INVALID, "ctx is NULL");
     if (n_rays == 0) return NERF_OK;
@@ -1053,6 +1080,10 @@ static int rays_device(nerf_ctx *c, const float *d_origins, size_t n_origins, co
         HIP_TRY(c, hipStreamSynchronize(st));
         b.h_origin = origin;
     } else b.d_origins = d_origins;
+    if (certified) // a retry renders the batch again
+        return certify_retry(c, stats, "batch", [&](CertOutcome *oc) {
+            return render_rays_device(c, b, opts, background, d_rgb_out, d_depth_out, d_opacity_out, st, stats, 0.0f, nullptr, oc);
+        });
     return render_rays_device(c, b, opts, background, d_rgb_out, d_depth_out, d_opacity_out, st, stats, h, want_normals ? d_normals_out : nullptr);
 }
 
@@ -1071,12 +1102,12 @@ int nerf_render_rays_normals_device(nerf_ctx *c, const float *d_origins, size_t 
                        d_opacity_out, true, h, d_normals_out, stream, stats);
 } NERF_CATCH(c)
 
-// nerf_render_rays and nerf_render_rays_normals (want_normals)
+// nerf_render_rays, nerf_render_rays_normals (want_normals) and nerf_render_rays_certified (certified)
 static int rays_host(nerf_ctx *c, const float *origins, size_t n_origins, const float *dirs, size_t n_rays, int normalize, float near_, float far_,
                      const float *bounds, const uint32_t *rng_index, const nerf_render_opts *opts, const float background[3], float *rgb_out,
-                     float *depth_out, float *opacity_out, bool want_normals, float h, float *normals_out, nerf_stats *stats) {
+                     float *depth_out, float *opacity_out, bool want_normals, float h, float *normals_out, nerf_stats *stats, bool certified = false) {
     int rc;
-    if ((rc = check_ray_batch(c, origins, n_origins, dirs, n_rays, near_, far_, bounds, opts, background, rgb_out))) return rc;
+    if ((rc = check_ray_batch(c, origins, n_origins, dirs, n_rays, near_, far_, bounds, opts, background, rgb_out, certified))) return rc;
     if (want_normals && (rc = check_normals(c, h, normals_out))) return rc;
     if ((rc = check_ray_batch_rays(c, origins, n_origins, dirs, n_rays, normalize, bounds))) return rc;
     if (!c) return fail(nullptr, NERF_ERR_INVALID, "ctx is NULL");
@@ -1095,8 +1126,13 @@ static int rays_host(nerf_ctx *c, const float *origins, size_t n_origins, const 
     RayBatch b{n_origins == 1 ? origins : nullptr, n_origins == 1 ? nullptr : d + o_o, d + o_d, n_rays, normalize ? 1 : 0, near_, far_,
                bounds ? d + o_b : nullptr, rng_index ? (const uint32_t *)(d + o_i) : nullptr};
     nerf_stats local; // a synchronous render always reads its counters (see nerf_render_image_aux)
-    if ((rc = render_rays_device(c, b, opts, background, d + o_c, depth_out ? d + o_z : nullptr, opacity_out ? d + o_a : nullptr, c->stream,
-                                 stats ? stats : &local, h, want_normals ? d + o_n : nullptr))) return rc;
+    nerf_stats *const sp = stats ? stats : &local;
+    float *const d_depth = depth_out ? d + o_z : nullptr, *const d_opacity = opacity_out ? d + o_a : nullptr;
+    if (certified) rc = certify_retry(c, sp, "batch", [&](CertOutcome *oc) {
+            return render_rays_device(c, b, opts, background, d + o_c, d_depth, d_opacity, c->stream, sp, 0.0f, nullptr, oc);
+        });
+    else rc = render_rays_device(c, b, opts, background, d + o_c, d_depth, d_opacity, c->stream, sp, h, want_normals ? d + o_n : nullptr);
+    if (rc) return rc;
     HIP_TRY(c, hipMemcpyAsync(rgb_out, d + o_c, 3 * R * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     if (want_normals) HIP_TRY(c, hipMemcpyAsync(normals_out, d + o_n, 3 * R * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     if (depth_out) HIP_TRY(c, hipMemcpyAsync(depth_out, d + o_z, R * sizeof(float), hipMemcpyDeviceToHost, c->stream));
@@ -1109,19 +1145,21 @@ static int rays_host(nerf_ctx *c, const float *origins, size_t n_origins, const 
 // what nerf_render_rays_clipped* refuses without a context or a device: nerf_render_rays' refusals, then the grid's
 static int check_rays_clipped(nerf_ctx *c, const void *occ_bits, const float *lo, const float *step, const int32_t *dims, const void *origins,
                               size_t n_origins, const void *dirs, size_t n_rays, float near_, float far_, const void *bounds,
-                              const nerf_render_opts *opts, const float *background, const void *rgb_out) {
+                              const nerf_render_opts *opts, const float *background, const void *rgb_out, bool certified) {
     int rc;
-    if ((rc = check_ray_batch(c, origins, n_origins, dirs, n_rays, near_, far_, bounds, opts, background, rgb_out))) return rc;
+    if ((rc = check_ray_batch(c, origins, n_origins, dirs, n_rays, near_, far_, bounds, opts, background, rgb_out, certified))) return rc;
     if (const char *why = nerfclip::check_grid(occ_bits, lo, step, dims)) return fail(c, NERF_ERR_INVALID, why);
     return NERF_OK;
 }
 
 // clip -> count -> [gather -> render_rays_device on the compacted batch -> scatter]; every pointer but lo / step / dims / opts / background /
-// n_hit / stats is a device pointer; arguments already checked, n_rays > 0
+// n_hit / stats is a device pointer; arguments already checked, n_rays > 0.  certified: the compacted batch is rendered with zero
+// certification; a retry renders the compacted batch again and does not clip again
 static int rays_clipped_device(nerf_ctx *c, const uint32_t *d_bits, const float *lo, const float *step, const int32_t *dims, const float *d_origins,
                                size_t n_origins, const float *d_dirs, size_t n_rays, int normalize, float near_, float far_, const float *d_bounds,
                                const uint32_t *d_rng_index, const nerf_render_opts *opts, const float *background, float *d_rgb_out,
-                               float *d_depth_out, float *d_opacity_out, uint8_t *d_hit_out, uint64_t *n_hit, hipStream_t st, nerf_stats *stats) {
+                               float *d_depth_out, float *d_opacity_out, uint8_t *d_hit_out, uint64_t *n_hit, hipStream_t st, nerf_stats *stats,
+                               bool certified) {
     int rc;
     const bool per_ray = n_origins != 1;
     if ((rc = ensure_bytes(c, &c->d_clip, &c->clip_bytes, ClipWorkspace::bytes(n_rays, per_ray)))) return rc;
@@ -1151,36 +1189,44 @@ static int rays_clipped_device(nerf_ctx *c, const uint32_t *d_bits, const float 
     g.rng_index = d_rng_index; g.ray_of = w.ray_of; g.dirs_c = w.dirs_c; g.origins_c = w.origins_c; g.bounds_c = w.bounds_c; g.rng_c = w.rng_c;
     HIP_TRY(c, launch_clip_gather(g, st));
     const RayBatch b{per_ray ? nullptr : origin, per_ray ? w.origins_c : nullptr, w.dirs_c, H, normalize ? 1 : 0, near_, far_, w.bounds_c, w.rng_c};
-    if ((rc = render_rays_device(c, b, opts, background, w.rgb_c, d_depth_out ? w.depth_c : nullptr, d_opacity_out ? w.opacity_c : nullptr, st, stats)))
-        return rc;
+    float *const depth_c = d_depth_out ? w.depth_c : nullptr, *const opacity_c = d_opacity_out ? w.opacity_c : nullptr;
+    if (certified) rc = certify_retry(c, stats, "batch", [&](CertOutcome *oc) {
+            return render_rays_device(c, b, opts, background, w.rgb_c, depth_c, opacity_c, st, stats, 0.0f, nullptr, oc);
+        });
+    else rc = render_rays_device(c, b, opts, background, w.rgb_c, depth_c, opacity_c, st, stats);
+    if (rc) return rc;
     const ClipScatterArgs s{(uint32_t)H, w.ray_of, w.rgb_c, w.depth_c, w.opacity_c, d_rgb_out, d_depth_out, d_opacity_out};
     HIP_TRY(c, launch_clip_scatter(s, st));
-    if (stats) HIP_TRY(c, hipStreamSynchronize(st)); // as nerf_render_rays_device: with stats the outputs are complete on return
+    if (stats || certified) HIP_TRY(c, hipStreamSynchronize(st)); // as nerf_render_rays_device: with stats the outputs are complete on return; certified forms always are
     return NERF_OK;
 }
 
-int nerf_render_rays_clipped_device(nerf_ctx *c, const uint32_t *d_occ_bits, const float lo[3], const float step[3], const int32_t dims[3],
-                                    const float *d_origins, size_t n_origins, const float *d_dirs, size_t n_rays, int normalize, float near_,
-                                    float far_, const float *d_bounds, const uint32_t *d_rng_index, const nerf_render_opts *opts,
-                                    const float background[3], float *d_rgb_out, float *d_depth_out, float *d_opacity_out, uint8_t *d_hit_out,
-                                    uint64_t *n_hit, void *stream, nerf_stats *stats) try {
+// nerf_render_rays_clipped_device and nerf_render_rays_clipped_certified_device (certified)
+static int clipped_device(nerf_ctx *c, const uint32_t *d_occ_bits, const float lo[3], const float step[3], const int32_t dims[3],
+                          const float *d_origins, size_t n_origins, const float *d_dirs, size_t n_rays, int normalize, float near_,
+                          float far_, const float *d_bounds, const uint32_t *d_rng_index, const nerf_render_opts *opts,
+                          const float background[3], float *d_rgb_out, float *d_depth_out, float *d_opacity_out, uint8_t *d_hit_out,
+                          uint64_t *n_hit, void *stream, nerf_stats *stats, bool certified) {
     int rc;
-    if ((rc = check_rays_clipped(c, d_occ_bits, lo, step, dims, d_origins, n_origins, d_dirs, n_rays, near_, far_, d_bounds, opts, background, d_rgb_out)))
+    if ((rc = check_rays_clipped(c, d_occ_bits, lo, step, dims, d_origins, n_origins, d_dirs, n_rays, near_, far_, d_bounds, opts, background, d_rgb_out,
+                                 certified)))
         return rc;
     if (!c) return fail(nullptr, NERF_ERR_INVALID, "ctx is NULL");
     if (n_hit) *n_hit = 0;
     if (n_rays == 0) return NERF_OK;
     DeviceGuard dg(c->device);
     return rays_clipped_device(c, d_occ_bits, lo, step, dims, d_origins, n_origins, d_dirs, n_rays, normalize, near_, far_, d_bounds, d_rng_index, opts,
-                               background, d_rgb_out, d_depth_out, d_opacity_out, d_hit_out, n_hit, (hipStream_t)stream, stats);
-} NERF_CATCH(c)
+                               background, d_rgb_out, d_depth_out, d_opacity_out, d_hit_out, n_hit, (hipStream_t)stream, stats, certified);
+}
 
-int nerf_render_rays_clipped(nerf_ctx *c, const uint32_t *occ_bits, const float lo[3], const float step[3], const int32_t dims[3],
-                             const float *origins, size_t n_origins, const float *dirs, size_t n_rays, int normalize, float near_, float far_,
-                             const float *bounds, const uint32_t *rng_index, const nerf_render_opts *opts, const float background[3], float *rgb_out,
-                             float *depth_out, float *opacity_out, uint8_t *hit_out, uint64_t *n_hit, nerf_stats *stats) try {
+// nerf_render_rays_clipped and nerf_render_rays_clipped_certified (certified)
+static int clipped_host(nerf_ctx *c, const uint32_t *occ_bits, const float lo[3], const float step[3], const int32_t dims[3],
+                        const float *origins, size_t n_origins, const float *dirs, size_t n_rays, int normalize, float near_, float far_,
+                        const float *bounds, const uint32_t *rng_index, const nerf_render_opts *opts, const float background[3], float *rgb_out,
+                        float *depth_out, float *opacity_out, uint8_t *hit_out, uint64_t *n_hit, nerf_stats *stats, bool certified) {
     int rc;
-    if ((rc = check_rays_clipped(c, occ_bits, lo, step, dims, origins, n_origins, dirs, n_rays, near_, far_, bounds, opts, background, rgb_out))) return rc;
+    if ((rc = check_rays_clipped(c, occ_bits, lo, step, dims, origins, n_origins, dirs, n_rays, near_, far_, bounds, opts, background, rgb_out, certified)))
+        return rc;
     if ((rc = check_ray_batch_rays(c, origins, n_origins, dirs, n_rays, normalize, bounds))) return rc;
     if (!c) return fail(nullptr, NERF_ERR_INVALID, "ctx is NULL");
     if (n_hit) *n_hit = 0;
@@ -1201,13 +1247,48 @@ int nerf_render_rays_clipped(nerf_ctx *c, const uint32_t *occ_bits, const float 
     if ((rc = rays_clipped_device(c, (const uint32_t *)(d + o_g), lo, step, dims, d + o_o, n_origins, d + o_d, R, normalize, near_, far_,
                                   bounds ? d + o_b : nullptr, rng_index ? (const uint32_t *)(d + o_i) : nullptr, opts, background, d + o_c,
                                   depth_out ? d + o_z : nullptr, opacity_out ? d + o_a : nullptr, hit_out ? (uint8_t *)(d + o_h) : nullptr, n_hit,
-                                  c->stream, stats ? stats : &local))) return rc;
+                                  c->stream, stats ? stats : &local, certified))) return rc;
     HIP_TRY(c, hipMemcpyAsync(rgb_out, d + o_c, 3 * R * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     if (depth_out) HIP_TRY(c, hipMemcpyAsync(depth_out, d + o_z, R * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     if (opacity_out) HIP_TRY(c, hipMemcpyAsync(opacity_out, d + o_a, R * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     if (hit_out) HIP_TRY(c, hipMemcpyAsync(hit_out, d + o_h, R, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return NERF_OK;
+}
+
+int nerf_render_rays_clipped_device(nerf_ctx *c, const uint32_t *d_occ_bits, const float lo[3], const float step[3], const int32_t dims[3],
+                                    const float *d_origins, size_t n_origins, const float *d_dirs, size_t n_rays, int normalize, float near_,
+                                    float far_, const float *d_bounds, const uint32_t *d_rng_index, const nerf_render_opts *opts,
+                                    const float background[3], float *d_rgb_out, float *d_depth_out, float *d_opacity_out, uint8_t *d_hit_out,
+                                    uint64_t *n_hit, void *stream, nerf_stats *stats) try {
+    return clipped_device(c, d_occ_bits, lo, step, dims, d_origins, n_origins, d_dirs, n_rays, normalize, near_, far_, d_bounds, d_rng_index, opts,
+                          background, d_rgb_out, d_depth_out, d_opacity_out, d_hit_out, n_hit, stream, stats, false);
+} NERF_CATCH(c)
+
+int nerf_render_rays_clipped_certified_device(nerf_ctx *c, const uint32_t *d_occ_bits, const float lo[3], const float step[3], const int32_t dims[3],
+                                              const float *d_origins, size_t n_origins, const float *d_dirs, size_t n_rays, int normalize,
+                                              float near_, float far_, const float *d_bounds, const uint32_t *d_rng_index,
+                                              const nerf_render_opts *opts, const float background[3], float *d_rgb_out, float *d_depth_out,
+                                              float *d_opacity_out, uint8_t *d_hit_out, uint64_t *n_hit, void *stream, nerf_stats *stats) try {
+    return clipped_device(c, d_occ_bits, lo, step, dims, d_origins, n_origins, d_dirs, n_rays, normalize, near_, far_, d_bounds, d_rng_index, opts,
+                          background, d_rgb_out, d_depth_out, d_opacity_out, d_hit_out, n_hit, stream, stats, true);
+} NERF_CATCH(c)
+
+int nerf_render_rays_clipped(nerf_ctx *c, const uint32_t *occ_bits, const float lo[3], const float step[3], const int32_t dims[3],
+                             const float *origins, size_t n_origins, const float *dirs, size_t n_rays, int normalize, float near_, float far_,
+                             const float *bounds, const uint32_t *rng_index, const nerf_render_opts *opts, const float background[3], float *rgb_out,
+                             float *depth_out, float *opacity_out, uint8_t *hit_out, uint64_t *n_hit, nerf_stats *stats) try {
+    return clipped_host(c, occ_bits, lo, step, dims, origins, n_origins, dirs, n_rays, normalize, near_, far_, bounds, rng_index, opts, background,
+                        rgb_out, depth_out, opacity_out, hit_out, n_hit, stats, false);
+} NERF_CATCH(c)
+
+int nerf_render_rays_clipped_certified(nerf_ctx *c, const uint32_t *occ_bits, const float lo[3], const float step[3], const int32_t dims[3],
+                                       const float *origins, size_t n_origins, const float *dirs, size_t n_rays, int normalize, float near_,
+                                       float far_, const float *bounds, const uint32_t *rng_index, const nerf_render_opts *opts,
+                                       const float background[3], float *rgb_out, float *depth_out, float *opacity_out, uint8_t *hit_out,
+                                       uint64_t *n_hit, nerf_stats *stats) try {
+    return clipped_host(c, occ_bits, lo, step, dims, origins, n_origins, dirs, n_rays, normalize, near_, far_, bounds, rng_index, opts, background,
+                        rgb_out, depth_out, opacity_out, hit_out, n_hit, stats, true);
 } NERF_CATCH(c)
 
 int nerf_render_rays(nerf_ctx *c, const float *origins, size_t n_origins, const float *dirs, size_t n_rays, int normalize, float near_, float far_,
@@ -1222,6 +1303,21 @@ int nerf_render_rays_normals(nerf_ctx *c, const float *origins, size_t n_origins
                              float *rgb_out, float *depth_out, float *opacity_out, float h, float *normals_out, nerf_stats *stats) try {
     return rays_host(c, origins, n_origins, dirs, n_rays, normalize, near_, far_, bounds, rng_index, opts, background, rgb_out, depth_out, opacity_out,
                      true, h, normals_out, stats);
+} NERF_CATCH(c)
+
+int nerf_render_rays_certified(nerf_ctx *c, const float *origins, size_t n_origins, const float *dirs, size_t n_rays, int normalize, float near_,
+                               float far_, const float *bounds, const uint32_t *rng_index, const nerf_render_opts *opts, const float background[3],
+                               float *rgb_out, float *depth_out, float *opacity_out, nerf_stats *stats) try {
+    return rays_host(c, origins, n_origins, dirs, n_rays, normalize, near_, far_, bounds, rng_index, opts, background, rgb_out, depth_out, opacity_out,
+                     false, 0.0f, nullptr, stats, true);
+} NERF_CATCH(c)
+
+int nerf_render_rays_certified_device(nerf_ctx *c, const float *d_origins, size_t n_origins, const float *d_dirs, size_t n_rays, int normalize,
+                                      float near_, float far_, const float *d_bounds, const uint32_t *d_rng_index, const nerf_render_opts *opts,
+                                      const float background[3], float *d_rgb_out, float *d_depth_out, float *d_opacity_out, void *stream,
+                                      nerf_stats *stats) try {
+    return rays_device(c, d_origins, n_origins, d_dirs, n_rays, normalize, near_, far_, d_bounds, d_rng_index, opts, background, d_rgb_out, d_depth_out,
+                       d_opacity_out, false, 0.0f, nullptr, stream, stats, true);
 } NERF_CATCH(c)
 
 } // extern "C"
