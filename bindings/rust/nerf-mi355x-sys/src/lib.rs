@@ -146,7 +146,9 @@ extern "C" {
     pub fn nerf_debug_ray_grouping(n_rays: c_int, samples_per_ray: c_int, enabled: c_int, first_slot_of_wave_tile: *mut i32) -> c_int;
     pub fn nerf_debug_wave_tiling(rows: c_int, rays_per_row: c_int, samples_per_ray: c_int, full: c_int, ray_grouping: c_int, wave_tiling: c_int,
                                   slot: *mut i32) -> c_int;
+    pub fn nerf_debug_tile_rotation(n_tiles: c_int, n_workgroups: c_int, rotation: c_int, workgroup_of_tile: *mut i32, round_of_tile: *mut i32) -> c_int;
     pub fn nerf_debug_shader_clock_mhz(ctx: *mut nerf_ctx, mhz: *mut f64) -> c_int;
+    pub fn nerf_debug_workgroup_clocks(ctx: *mut nerf_ctx, out: *mut u64, n_workgroups: usize) -> c_int;
     pub fn nerf_forward_batch(ctx: *mut nerf_ctx, which: c_int, pts_soa: *const f32, dirs_aos: *const f32, n: usize,
                               rgb_aos: *mut f32, sigma: *mut f32) -> c_int;
     pub fn nerf_forward_batch_ex(ctx: *mut nerf_ctx, which: c_int, mlp_dtype: c_int, pts_soa: *const f32, dirs_aos: *const f32,
@@ -333,6 +335,7 @@ extern "C" {
                                normalize: c_int, dirs_out: *mut f32) -> c_int;
     pub fn nerf_stage_stratified(ctx: *mut nerf_ctx, cam: *const nerf_camera, x0: c_int, y0: c_int, w: c_int, h: c_int,
                                  count: c_int, seed: u64, t_out: *mut f32) -> c_int;
+    pub fn nerf_stage_depth_order(ctx: *mut nerf_ctx, rows: c_int, rays_per_row: c_int, samples_per_ray: c_int, t: *const f32, table_out: *mut u32) -> c_int;
     pub fn nerf_stage_resample(ctx: *mut nerf_ctx, n_rays: usize, nc: c_int, nf: c_int, far: f32, seed: u64,
                                pixel_index: *const u32, t_coarse: *const f32, sigma_coarse: *const f32, u: *const f32,
                                w_out: *mut f32, cdf_out: *mut f32, t_new_out: *mut f32, t_fine_out: *mut f32) -> c_int;

@@ -184,8 +184,16 @@ typedef struct {
  *                           sampling launch, 4 x 2 pixels x 4 samples in the launch that produces colours), whose points lie close together and
  *                           so have more dead hidden units in common for the zero-step skip.  Independent of NERF_RAY_GROUPING; every output
  *                           keeps its bits (nerf_debug_wave_tiling shows the mapping).
+ *   NERF_DEPTH_ORDER=0      switches off depth ordering: in the f32 launch that produces the colours of an image pass (rows a multiple of 8 pixels
+ *                           wide, at least 4 of them, samples per ray a multiple of 32 and at most 512; not skip_empty renders, not ray batches)
+ *                           the samples of every 8 x 4 pixel block are merged by depth on the device and a wave holds 32 neighbours of that order,
+ *                           not 4 samples of each ray of a 4 x 2 block: a ray places its importance samples where its own densities are, so only
+ *                           depth says which samples of neighbouring rays lie together.  Off with NERF_WAVE_TILING=0 too; every output keeps
+ *                           its bits (nerf_stage_depth_order shows the order).
+ *   NERF_TILE_ROTATION=0    the persistent workgroups of the fused f32 kernel take tile k G + c in round k, not k G + ((c + k) mod G): the
+ *                           rotation spreads tiles of systematically different cost (sample index, depth rank) over all workgroups.
  *   NERF_DEBUG_ZSKIP=1      diagnostic: every f32 MLP launch synchronises and prints its executed / total ReLU k-steps to stderr.
- *   NERF_DEBUG_CLOCK=1      diagnostic: nerf_debug_shader_clock_mhz. */
+ *   NERF_DEBUG_CLOCK=1      diagnostic: nerf_debug_shader_clock_mhz, nerf_debug_workgroup_clocks of the fine launch; 2: of the sampling launch. */
 int nerf_create(int device_id, nerf_ctx **out);
 void nerf_destroy(nerf_ctx *ctx);
 /* Message of the last failing call on ctx (or of the last failing context-free call when ctx == NULL). */
@@ -249,6 +257,10 @@ int nerf_debug_ray_grouping(int n_rays, int samples_per_ray, int enabled, int32_
  * multiple of 32, fewer rows than the block is high, no block of 4 pixels whose width divides rays_per_row), it is nerf_debug_ray_grouping's
  * table spelled out: first slot + p.  Host-only. */
 int nerf_debug_wave_tiling(int rows, int rays_per_row, int samples_per_ray, int full, int ray_grouping, int wave_tiling, int32_t *slot);
+/* Which persistent workgroup of n_workgroups takes which of n_tiles workgroup tiles of a fused f32 launch, and in which of its rounds: the
+ * kernel's own tile walk run on the host (rotation != 0: round k's tile of workgroup c is k G + ((c + k) mod G); 0: k G + c).  Both
+ * tables hold n_tiles entries; a tile nobody takes keeps -1, a tile taken twice -2 (neither may occur).  No device needed. */
+int nerf_debug_tile_rotation(int n_tiles, int n_workgroups, int rotation, int32_t *workgroup_of_tile, int32_t *round_of_tile);
 
 /* ---- S2: Network::forward_batch (src/network.rs:197-237) -------------------------------------------------- */
 /* host pointers, synchronous.  n == 0 is a no-op (src/network.rs:199-201).
@@ -745,9 +757,13 @@ int nerf_band_rows(int window_rows, int band_index, int band_count, int band_str
 int nerf_kernel_time_query(nerf_ctx *ctx, double *ms_dominant_mlp, uint64_t *points_dominant_mlp, uint32_t *n_launches,
                            int reset);
 
-/* Diagnostic: median in-kernel shader clock (MHz) of the last fine-network MLP launch, from s_memtime / s_memrealtime
- * stamps around the tile loop.  Only available when NERF_DEBUG_CLOCK=1 was set before nerf_create. */
+/* Diagnostic: median in-kernel shader clock (MHz) of the last fine-network MLP launch (NERF_DEBUG_CLOCK=1) or of the last sampling
+ * (coarse-network) launch (NERF_DEBUG_CLOCK=2), from s_memtime / s_memrealtime stamps around the tile loop.  Only available when
+ * NERF_DEBUG_CLOCK was set to 1 or 2 before nerf_create (NERF_ERR_STATE otherwise, and before the first frame). */
 int nerf_debug_shader_clock_mhz(nerf_ctx *ctx, double *mhz);
+/* Diagnostic: per persistent workgroup of that launch (of the last sampling launch under NERF_DEBUG_CLOCK=2) {shader cycles, 100 MHz ticks} of
+ * its tile loop; out: 2 * n_workgroups values, n_workgroups <= the device's CUs.  The spread of the ticks is the launch's load imbalance. */
+int nerf_debug_workgroup_clocks(nerf_ctx *ctx, uint64_t *out, size_t n_workgroups);
 
 /* ---- host helpers around the path ------------------------------------------------------------------------ */
 /* camera_from_samples (src/lib.rs:614-645): reads near, far, camera_origin, camera_forward, camera_up, hwf. */
@@ -798,6 +814,15 @@ int nerf_stage_resample(nerf_ctx *ctx, size_t n_rays, int nc, int nf, float far_
 int nerf_stage_hybrid_flags(nerf_ctx *ctx, size_t n_rays, int nc, int nf, float far_, uint64_t seed,
                             const uint32_t *pixel_index, const float *t_coarse, const float *sigma_coarse, const float *u,
                             float tau, uint8_t *flags_out, float *t_new_out);
+/* The depth-order table of an image pass (debug / tests): the kernel that runs in front of the fine f32 launch of a pass of `rows` rows of
+ * rays_per_row rays with samples_per_ray samples each, on the caller's t (rows x rays_per_row x samples_per_ray, any bits).  The first
+ * (rows / 4) * 4 rows are cut in 8 x 4 pixel blocks, row-major; entry q of block b (table_out[32 samples_per_ray b + q]) is the slot
+ * ray * samples_per_ray + sample of the point at position q of the block's ascending order by (uint32 bits of t, ray-in-block row-major,
+ * sample).  The fine kernel's workgroup tile T evaluates entries 128 T .. 128 T + 127, wave w entries 128 T + 32 w ...  Needs
+ * rays_per_row % 8 == 0, rows >= 4, samples_per_ray % 32 == 0 and <= 512 (NERF_ERR_INVALID otherwise: such a pass keeps the static
+ * mapping of nerf_debug_wave_tiling, as do skip_empty renders and contexts created under NERF_DEPTH_ORDER=0 or NERF_WAVE_TILING=0).
+ * table_out: (rows / 4) * 4 * rays_per_row * samples_per_ray entries. */
+int nerf_stage_depth_order(nerf_ctx *ctx, int rows, int rays_per_row, int samples_per_ray, const float *t, uint32_t *table_out);
 /* integrate_ray (src/lib.rs:176-195); w_out (n_rays x n) optional */
 int nerf_stage_integrate(nerf_ctx *ctx, size_t n_rays, int n, float far_, const float *rgb_aos, const float *sigma,
                          const float *t, float *rgb_out, float *w_out);

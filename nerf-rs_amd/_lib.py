@@ -82,6 +82,7 @@ PROTOTYPES = {
     "nerf_debug_split_f16x2": (C.c_int, [f32p, C.c_size_t, C.POINTER(C.c_uint16)]),
     "nerf_debug_certify_policy": (C.c_int, [C.c_float, C.c_uint64, C.c_uint64, C.c_float, C.c_float, f32p]),
     "nerf_debug_ray_grouping": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
+    "nerf_debug_tile_rotation": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "nerf_debug_wave_tiling": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
     "nerf_forward_batch": (C.c_int, [C.c_void_p, C.c_int, f32p, f32p, C.c_size_t, f32p, f32p]),
     "nerf_forward_batch_ex": (C.c_int, [C.c_void_p, C.c_int, C.c_int, f32p, f32p, C.c_size_t, f32p, f32p]),
@@ -154,6 +155,7 @@ PROTOTYPES = {
     "nerf_kernel_time_query": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64),
                                          C.POINTER(C.c_uint32), C.c_int]),
     "nerf_debug_shader_clock_mhz": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "nerf_debug_workgroup_clocks": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_size_t]),
     "nerf_camera_from_json": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.POINTER(CCamera)]),
     "nerf_camera_from_values": (C.c_int, [C.c_float, C.c_float, f32p, f32p, f32p, f32p, C.c_int, C.c_int,
                                           C.POINTER(CCamera)]),
@@ -165,6 +167,7 @@ PROTOTYPES = {
     "nerf_stage_ray_dirs": (C.c_int, [C.c_void_p, C.POINTER(CCamera), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p]),
     "nerf_stage_stratified": (C.c_int, [C.c_void_p, C.POINTER(CCamera), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                         C.c_uint64, f32p]),
+    "nerf_stage_depth_order": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, f32p, u32p]),
     "nerf_stage_resample": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_float, C.c_uint64, u32p, f32p, f32p,
                                       f32p, f32p, f32p, f32p, f32p]),
     "nerf_stage_hybrid_flags": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_float, C.c_uint64, u32p, f32p, f32p, f32p,

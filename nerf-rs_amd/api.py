@@ -109,6 +109,12 @@ class Renderer:
         check(self._L.nerf_kernel_time_query(self.handle, C.byref(ms), C.byref(pts), C.byref(n), int(reset)), self.handle)
         return ms.value, pts.value, n.value
 
+    def workgroup_clocks(self):
+        """Per persistent workgroup {shader cycles, 100 MHz ticks} of the last fine (NERF_DEBUG_CLOCK=1) or sampling (=2) launch -> (n_cus, 2) uint64."""
+        out = np.zeros((self.device_info()["n_cus"], 2), np.uint64)
+        check(self._L.nerf_debug_workgroup_clocks(self.handle, out.ctypes.data_as(C.POINTER(C.c_uint64)), out.shape[0]), self.handle)
+        return out
+
     # ---- stage entry points (parity tests; hosts that own ray setup) ----
     def stage_ray_dirs(self, cam, x0, y0, w, h, normalize=True):
         out = np.empty((h, w, 3), np.float32)
@@ -131,6 +137,15 @@ class Renderer:
                                           None if pix is None else pix.ctypes.data_as(u32p), _p(t), _p(s),
                                           None if uu is None else _p(uu), _p(w), _p(cdf), _p(tn), _p(tf)), self.handle)
         return {"w": w, "cdf": cdf, "t_new": tn, "t_fine": tf}
+
+    def stage_depth_order(self, t):
+        """The depth-order table of an image pass with sample positions t (rows, rays_per_row, samples_per_ray): the slots of the first
+        (rows // 4) * 4 rows, per 8 x 4 pixel block in ascending (bits of t, ray-in-block, sample) order (nerf_stage_depth_order) -> uint32."""
+        t = _f32(t)
+        rows, rw, spr = t.shape
+        out = np.empty((rows // 4) * 4 * rw * spr, np.uint32)
+        check(self._L.nerf_stage_depth_order(self.handle, rows, rw, spr, _p(t), out.ctypes.data_as(u32p)), self.handle)
+        return out
 
     def stage_hybrid_flags(self, t_coarse, sigma_coarse, nf, far, seed=0, pixel_index=None, u=None, tau=0.0):
         """hybrid_sampling's per-ray decision for the given coarse densities -> (flags (R,) bool, t_new (R, nf) unsorted draws)."""

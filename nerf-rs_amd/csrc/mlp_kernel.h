@@ -59,7 +59,23 @@ struct MlpArgs {
     // MLP_MODE_LIST (appended likewise): per-ray origins of a certified ray batch, n_rays x 3, device; the point of list entry idx is
     // fl(ray_origins[idx / samples_per_ray] + fl(d * t)) per coordinate.  NULL: `origin` above.  No other mode reads it.
     const float *ray_origins;
+    // f32 fused kernel, the full MLP_MODE_RAYS launch of an image pass (appended likewise): depth ordering (mlp_layout.h DepthOrder).  The caller
+    // sets the context's switch (depth_order, NERF_DEPTH_ORDER) and, where nerf_mlp_depth_order says the launch qualifies, the pass's table
+    // (sampling_kernels.h launch_depth_order: one slot per point of the ordered region); nerf_mlp_launch derives order_tiles / order_points and
+    // the map of the rows behind the region.  order_table == NULL: today's static mapping.
+    int depth_order;
+    const unsigned int *order_table;
+    int order_tiles, order_points;
+    // f32 fused kernel, every mode: round k's tile of workgroup c is k G + ((c + k) mod G) (mlp_layout.h rotated_tile); 0: k G + c
+    int tile_rotation;
 };
+
+// The ordered region of a launch with these arguments (n_points, samples_per_ray, rays_per_row, mode, skip_empty and the two switches
+// wave_tiling / depth_order); tiles == 0: the launch does not qualify and needs no table.
+inline nerfmlp::DepthOrder nerf_mlp_depth_order(const MlpArgs &a, bool full) {
+    return nerfmlp::depth_order_of(a.n_points, a.samples_per_ray, a.rays_per_row, full,
+                                   a.mode == MLP_MODE_RAYS && a.depth_order != 0 && a.wave_tiling != 0 && a.skip_empty == 0);
+}
 
 // Sets the dynamic-LDS attribute of every kernel instantiation on the current device.
 hipError_t nerf_mlp_init();

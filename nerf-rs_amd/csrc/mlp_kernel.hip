@@ -23,6 +23,11 @@
 //   * in the ray-mode launches of an image pass a wave's 32 points are a few consecutive samples of each ray of a small block of pixels
 //     (mlp_layout.h wave tiling), not 32 samples of one ray: points that lie close together share dead hidden units, so more k-steps are
 //     zero on all of the wave's columns.  Only the slot a lane loads from and stores to changes; nothing enters the MFMA stream.
+//   * in the full ray-mode launch of an image pass the waves are cut from the depth-sorted samples of 8 x 4 pixel blocks instead (mlp_layout.h
+//     depth ordering; the pass's order table comes from sampling_kernels.hip k_depth_order): a ray places its fine samples where its own
+//     densities are, so depth, not the sample index, says which samples of neighbouring rays lie together.
+//   * the persistent workgroups rotate through the tiles of a round (mlp_layout.h rotated_tile), so that tiles whose cost follows their
+//     position in the launch (sample index, depth rank) are spread over all workgroups.
 // Per 32-point wave tile: at most 8256 MFMAs (full; 9280 before the fold) / 7680 (sigma only) x 64 cycles.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -87,19 +92,44 @@ __global__ __launch_bounds__(256, 1) void nerf_mlp_kernel(const MlpArgs A) {
     // bundles / rays; MlpArgs.ray_map, all off: 128 consecutive slots); every other mode 128 consecutive slots per workgroup.  The wave-uniform
     // part (base_of) is scalar work once per tile: formed for the look-ahead, then carried over in a scalar register; the lane's part of a tiled
     // slot is formed once per kernel, and a tile costs the lanes one select and one add.
+    //
+    // Depth ordering (the full ray-mode launch of an image pass, mlp_layout.h DepthOrder): the first A.order_tiles workgroup tiles take their
+    // slots from the pass's order table, lane p of wave w of tile T entry 128 T + 32 w + p; the launch's map describes the rows behind them,
+    // shifted by A.order_points slots.  The entry is loaded TWO tiles ahead, so that the t / direction loads that depend on it can still go
+    // out one tile ahead.  In this instantiation every tile's prologue pays one select more (table entry, or base + lane part as before); the
+    // scalar base of the map is formed for ordered tiles too and left unused there.
+    //
+    // Tile rotation (mlp_layout.h rotated_tile, walked by tile_walk_next): round k's tile of this workgroup is k G + ((blockIdx.x + k) mod G);
+    // scalar work once per tile.
+    constexpr bool ORDER = FULL && MODE == MLP_MODE_RAYS;
+    const int order_tiles = ORDER ? A.order_tiles : 0, order_points = ORDER ? A.order_points : 0;
     const int lane_part = (MODE == MLP_MODE_RAYS && A.ray_map.wt.ss) ? wave_tile_lane_part(A.ray_map.wt, p) : p;
+    auto ordered = [&](int T) { return ORDER && T < order_tiles; };
+    auto map_tile = [&](int T) { return ORDER ? max(T - order_tiles, 0) : T; }; // the tile's number in the launch's map
     auto base_of = [&](int T) {
-        return MODE == MLP_MODE_RAYS ? ray_launch_base(A.ray_map, T, wave) : T * kPointsPerBlock + wave * kPointsPerWave;
+        return MODE == MLP_MODE_RAYS ? order_points + ray_launch_base(A.ray_map, map_tile(T), wave) : T * kPointsPerBlock + wave * kPointsPerWave;
     };
-    auto lane_of = [&](int T) { return (MODE == MLP_MODE_RAYS && ray_launch_tiled(A.ray_map, T)) ? lane_part : p; };
+    auto lane_of = [&](int T) { return (MODE == MLP_MODE_RAYS && ray_launch_tiled(A.ray_map, map_tile(T))) ? lane_part : p; };
+    // the table entry of this lane in tile T; nothing is loaded for a tile outside the ordered region (tiles at or beyond n_tiles included).
+    // Bounded like every other slot is before it becomes an address: no content of the table can make a lane read or write outside the launch.
+    auto entry_of = [&](int T) {
+        return ordered(T) ? (int)min(A.order_table[(size_t)T * kPointsPerBlock + wave * kPointsPerWave + p], (unsigned)order_points - 1u) : 0;
+    };
+    const int G = gridDim.x;
+    TileWalk walk = {0, 0};
+    auto next_round_tile = [&]() { return tile_walk_next(walk, (int)blockIdx.x, G, A.tile_rotation != 0); };
+    int tile_next = next_round_tile();  // round 1's tile (round 0's is blockIdx.x)
+    int tile_next2 = next_round_tile(); // round 2's
     int base_next = base_of(blockIdx.x); // wave-uniform
-    RawIn nxt = load_raw_at<LOAD>(A, base_next + lane_of(blockIdx.x)); // the next tile's t / direction are loaded one tile ahead
-    for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const int slot = base_next + lane_of(tile);
+    int ord_cur = entry_of(blockIdx.x), ord_next = entry_of(tile_next); // ORDER only: this lane's table entry of the coming tile and of the one behind it
+    RawIn nxt = load_raw_at<LOAD>(A, ordered(blockIdx.x) ? ord_cur : base_next + lane_of(blockIdx.x)); // the next tile's t / direction are loaded one tile ahead
+    for (int tile = blockIdx.x; tile < n_tiles; tile = tile_next, tile_next = tile_next2, tile_next2 = next_round_tile()) {
+        const int slot = ordered(tile) ? ord_cur : base_next + lane_of(tile);
         const bool valid = slot < n_points;
-        base_next = base_of(tile + gridDim.x);
+        base_next = base_of(tile_next);
+        if (ORDER) { ord_cur = ord_next; ord_next = entry_of(tile_next2); }
         const RawIn in = nxt;
-        nxt = load_raw_at<LOAD>(A, base_next + lane_of(tile + gridDim.x)); // consumed one tile (~250 us) later
+        nxt = load_raw_at<LOAD>(A, ordered(tile_next) ? ord_cur : base_next + lane_of(tile_next)); // consumed one tile (~250 us) later
         float px, py, pz;
         point_of<MODE>(A, in, px, py, pz);
         const float dx = in.dx, dy = in.dy, dz = in.dz;
@@ -231,9 +261,16 @@ hipError_t nerf_mlp_init() {
 // Every ray-mode launch comes through here (plain and skip_empty renders, shared-origin ray batches, coarse and fine passes): the wave
 // tiling and ray grouping of this launch, from its shape and the context's switches (MlpArgs.wave_tiling, .ray_grouping).  The pixel block
 // depends on the kind of launch (mlp_layout.h kWaveTileSigma* / kWaveTileFull*); a launch without rays_per_row (a ray batch) is never tiled.
+// A full launch whose caller built the pass's depth-order table (MlpArgs.order_table; nerf_render.cpp eval_net) takes the first (rows / 4) * 4
+// rows from it and maps the rows behind them like a launch of their own.
 static hipError_t launch_mlp_rays(const MlpArgs &a, bool full, int n_blocks, hipStream_t stream) {
     MlpArgs g = a;
-    g.ray_map = ray_launch_map_of(a.n_points, a.samples_per_ray, a.rays_per_row, full, a.ray_grouping != 0, a.wave_tiling != 0);
+    // depth ordering: the first (rows / 4) * 4 rows of a qualifying full launch whose caller built the pass's table; the map covers the rest
+    DepthOrder d = {0, 0, 0, 0};
+    if (a.order_table) d = nerf_mlp_depth_order(a, full);
+    g.order_tiles = d.tiles; g.order_points = d.points;
+    if (!d.tiles) g.order_table = nullptr;
+    g.ray_map = ray_launch_map_of(a.n_points - d.points, a.samples_per_ray, a.rays_per_row, full, a.ray_grouping != 0, a.wave_tiling != 0);
     return full ? launch_t<true, MLP_MODE_RAYS>(g, n_blocks, stream) : launch_t<false, MLP_MODE_RAYS>(g, n_blocks, stream);
 }
 

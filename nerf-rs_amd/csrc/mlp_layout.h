@@ -152,6 +152,66 @@ NERF_HOST_DEVICE inline int ray_launch_slot(const RayLaunchMap &m, int tile, int
     return ray_launch_base(m, tile, wave) + (ray_launch_tiled(m, tile) ? lane_part : p);
 }
 
+// ---- depth ordering (f32 kernels, the full ray-mode launch of an image pass): wave tiles cut from the depth-sorted samples of a pixel block.
+// The fine pass places each ray's importance samples differently, so "sample index k" is another depth on every ray of a static tile and the
+// wave's 32 points are spread along the rays.  Ordered, the spr samples of all 32 rays of an 8 x 4 pixel block are merged by depth t (a device
+// table, sampling_kernels.hip k_depth_order: position q of block b's sorted order holds the slot ray * spr + sample), and the block's
+// 32 spr points are cut into waves of 32 in that order: workgroup tile T takes table entries 128 T .. 128 T + 127, four consecutive depth slabs
+// of one block (tools/depth_order_model.py: the best of the compositions modelled).  Blocks are numbered row-major over the (rw / 8) x (rows / 4)
+// grid; the region covers the first (rows / 4) * 4 rows = slots [0, points) = workgroup tiles [0, tiles), whole (32 spr is a multiple of 128).
+// The rows behind it are a launch of their own shape (ray_launch_map_of of the remaining points), shifted by `points` slots and `tiles` tiles.
+// A permutation of the launch's points as the two mappings above, if the table is a permutation of each block's slots -- the order kernel
+// sorts (key, slot) pairs, so it is one for any bits of t.  Not for skip_empty launches: their workgroup vote spans the 128 points of a tile.
+constexpr int kDepthBlockW = 8, kDepthBlockH = 4;
+constexpr int kDepthOrderMaxSpr = 512; // the order kernel sorts a block's 32 spr keys (padded to a power of two) in LDS: 8 bytes each
+struct DepthOrder {
+    int tiles;     // workgroup tiles [0, tiles) are ordered; 0 = off
+    int points;    // ... and cover slots [0, points)
+    int blocks_x;  // rw / 8
+    int blocks;    // pixel blocks of the region
+};
+NERF_HOST_DEVICE inline DepthOrder depth_order_of(int n_points, int samples_per_ray, int rw, bool full, bool allowed) {
+    DepthOrder d = {0, 0, 0, 0};
+    if (!allowed || !full || rw <= 0 || rw % kDepthBlockW != 0 || samples_per_ray <= 0 || samples_per_ray % kPointsPerWave != 0 ||
+        samples_per_ray > kDepthOrderMaxSpr || n_points <= 0) return d;
+    const int n_rays = n_points / samples_per_ray;
+    if (n_rays % rw != 0 || n_rays * samples_per_ray != n_points) return d;
+    const int rows = n_rays / rw;
+    if (rows < kDepthBlockH) return d;
+    d.blocks_x = rw / kDepthBlockW;
+    d.blocks = d.blocks_x * (rows / kDepthBlockH);
+    d.points = (rows / kDepthBlockH) * kDepthBlockH * rw * samples_per_ray;
+    d.tiles = d.points / kPointsPerBlock;
+    return d;
+}
+// slot of sample s of ray (dy, dx) of pixel block b: what the order kernel stores for it
+NERF_HOST_DEVICE inline int depth_block_slot(int b, int blocks_x, int rw, int spr, int ray_in_block, int s) {
+    const int by = (int)((unsigned)b / (unsigned)blocks_x), bx = b - by * blocks_x;
+    const int dy = ray_in_block / kDepthBlockW, dx = ray_in_block % kDepthBlockW;
+    return ((by * kDepthBlockH + dy) * rw + bx * kDepthBlockW + dx) * spr + s;
+}
+
+// ---- tile rotation (f32 fused kernel): in round k persistent workgroup c of G takes tile k G + ((c + k) mod G), not k G + c.  A launch's
+// tiles come in periods (64 sample indices of the coarse pass, the depth slabs of a block in an ordered fine pass) whose cost differs
+// systematically, and 256 is a multiple of those periods: unrotated, a workgroup sees the same class in every round and the slowest class
+// sets the launch time.  Every tile below n_tiles is still taken exactly once (a round is a permutation of its G tiles).
+NERF_HOST_DEVICE inline int rotated_tile(int k, int c, int G) {
+    const int r = (int)((unsigned)(c + k % G) % (unsigned)G);
+    return k * G + r;
+}
+// The same sequence without a division, as the kernel walks it: start at round 0 (tile c), tile_walk_next gives round 1's tile, round 2's, ...
+// With rotate == false: k G + c.  nerf_debug_tile_rotation (tests/test_tile_rotation_host.py) walks it for every workgroup and compares it
+// with rotated_tile.
+struct TileWalk {
+    int round_base, rot; // k G and k mod G of the round whose tile was formed last
+};
+NERF_HOST_DEVICE inline int tile_walk_next(TileWalk &w, int c, int G, bool rotate) {
+    w.round_base += G;
+    if (rotate) w.rot = w.rot + 1 == G ? 0 : w.rot + 1;
+    const int r = c + w.rot;
+    return w.round_base + (r >= G ? r - G : r);
+}
+
 // k-steps per layer (K padded to the 32-slot tiles) and output tiles
 constexpr int kStepsL0 = 32;    // 64 encoding slots (63 used)
 constexpr int kStepsHid = 128;  // 256

@@ -135,11 +135,14 @@ int nerf_create(int device_id, nerf_ctx **out) try {
     if (const char *env = getenv("NERF_ZERO_STEP_SKIP")) c->zero_step_skip = atoi(env) != 0;
     if (const char *env = getenv("NERF_RAY_GROUPING")) c->ray_grouping = atoi(env) != 0;
     if (const char *env = getenv("NERF_WAVE_TILING")) c->wave_tiling = atoi(env) != 0;
+    if (const char *env = getenv("NERF_DEPTH_ORDER")) c->depth_order = atoi(env) != 0;
+    if (const char *env = getenv("NERF_TILE_ROTATION")) c->tile_rotation = atoi(env) != 0;
     if (const char *env = getenv("NERF_DEBUG_ZSKIP")) {
         if (atoi(env) > 0 && hipMalloc((void **)&c->d_zskip, 2 * sizeof(unsigned long long)) != hipSuccess) c->d_zskip = nullptr;
     }
     if (const char *env = getenv("NERF_DEBUG_CLOCK")) {
         if (atoi(env) > 0 && hipMalloc((void **)&c->d_clock, (size_t)c->n_cus * 2 * sizeof(unsigned long long)) != hipSuccess) c->d_clock = nullptr;
+        c->clock_coarse = atoi(env) == 2; // 2: the sampling (coarse) launch leaves its clocks instead of the fine one
     }
     if (hipMalloc((void **)&c->d_skip, sizeof(unsigned long long)) != hipSuccess) c->d_skip = nullptr;
     if (hipMalloc((void **)&c->d_nonfinite, sizeof(unsigned int)) != hipSuccess) c->d_nonfinite = nullptr;
@@ -172,7 +175,7 @@ void nerf_destroy(nerf_ctx *c) {
     for (auto &n : c->net) { if (n.wstream) (void)hipFree(n.wstream); if (n.small) (void)hipFree(n.small); if (n.small_f32) (void)hipFree(n.small_f32); if (n.wstream_bf16v2) (void)hipFree(n.wstream_bf16v2); if (n.wstream_x3) (void)hipFree(n.wstream_x3); if (n.wstream_x2) (void)hipFree(n.wstream_x2); if (n.wstream_f16v2) (void)hipFree(n.wstream_f16v2); }
     void *bufs[] = {c->d_dirs, c->d_tc, c->d_sc, c->d_rgbc, c->d_tf, c->d_sf, c->d_rgbf, c->d_rayfb, c->d_rayaux, c->d_out, c->d_pack, c->d_scratch,
                     c->d_mesh, c->d_batch, c->d_comp, c->d_normal, c->d_stencil, c->d_clip, c->d_clock, c->d_zskip, c->d_skip, c->d_nonfinite, c->d_seq, c->d_h8,
-                    c->d_slot_point, c->d_flag_list, c->d_point_list, c->d_jstar, c->d_cert_aux, c->d_cert};
+                    c->d_slot_point, c->d_flag_list, c->d_point_list, c->d_jstar, c->d_cert_aux, c->d_cert, c->d_order};
     for (void *p : bufs) if (p) (void)hipFree(p);
     recycle_render(c);
     recycle_dominant(c, 0);
@@ -228,6 +231,16 @@ int nerf_debug_shader_clock_mhz(nerf_ctx *c, double *mhz) try {
     if (f.empty()) return fail(c, NERF_ERR_STATE, "no clock samples");
     std::sort(f.begin(), f.end());
     *mhz = f[f.size() / 2];
+    return NERF_OK;
+} NERF_CATCH(c)
+
+int nerf_debug_workgroup_clocks(nerf_ctx *c, uint64_t *out, size_t n_workgroups) try {
+    if (!c || !out) return fail(c, NERF_ERR_INVALID, "NULL argument");
+    if (!c->d_clock || !c->clock_valid) return fail(c, NERF_ERR_STATE, "set NERF_DEBUG_CLOCK=1 (or 2) before nerf_create and render a frame first");
+    if (n_workgroups > (size_t)c->n_cus) return fail(c, NERF_ERR_INVALID, "more workgroups than the context launches");
+    DeviceGuard dg(c->device);
+    HIP_TRY(c, hipDeviceSynchronize());
+    HIP_TRY(c, hipMemcpy(out, c->d_clock, n_workgroups * 2 * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return NERF_OK;
 } NERF_CATCH(c)
 

@@ -200,6 +200,25 @@ int nerf_debug_wave_tiling(int rows, int rays_per_row, int samples_per_ray, int 
     return NERF_OK;
 } NERF_HOST_CATCH
 
+int nerf_debug_tile_rotation(int n_tiles, int n_workgroups, int rotation, int32_t *workgroup_of_tile, int32_t *round_of_tile) try {
+    using namespace nerfmlp;
+    if (n_tiles <= 0 || n_workgroups <= 0 || !workgroup_of_tile || !round_of_tile) return fail_noctx(NERF_ERR_INVALID, "n_tiles and n_workgroups must be > 0, the tables not NULL");
+    if ((long long)n_tiles + 2ll * n_workgroups > INT32_MAX) return fail_noctx(NERF_ERR_INVALID, "too many tiles");
+    for (int t = 0; t < n_tiles; ++t) workgroup_of_tile[t] = round_of_tile[t] = -1;
+    // as the tile loop of the fused f32 kernel (mlp_kernel.hip): workgroup c starts at tile c and walks on with tile_walk_next while the tile
+    // lies below n_tiles; a tile taken twice keeps -2
+    for (int c = 0; c < n_workgroups; ++c) {
+        TileWalk w = {0, 0};
+        int k = 0;
+        for (int tile = c; tile < n_tiles; tile = tile_walk_next(w, c, n_workgroups, rotation != 0), ++k) {
+            if (rotation && tile != rotated_tile(k, c, n_workgroups)) return fail_noctx(NERF_ERR_INVALID, "internal error: the walk left rotated_tile");
+            workgroup_of_tile[tile] = workgroup_of_tile[tile] == -1 ? c : -2;
+            round_of_tile[tile] = k;
+        }
+    }
+    return NERF_OK;
+} NERF_HOST_CATCH
+
 int nerf_debug_clip_rays(const uint32_t *occ_bits, const float lo[3], const float step[3], const int32_t dims[3], const float *origins,
                          size_t n_origins, const float *dirs, size_t n_rays, int normalize, float near_, float far_, const float *bounds,
                          float *bounds_out, uint8_t *hit_out, uint64_t *n_hit, uint64_t *n_refused_reads) try {

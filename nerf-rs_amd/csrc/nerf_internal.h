@@ -119,9 +119,13 @@ struct nerf_ctx {
     unsigned int *d_nonfinite = nullptr;   // device counter of non-finite density pre-activations (split arithmetics)
     unsigned long long *d_clock = nullptr; // diagnostic: per-workgroup {cycles, 100 MHz ticks} of the last fine-MLP launch
     bool clock_valid = false;
+    bool clock_coarse = false;             // NERF_DEBUG_CLOCK=2: the clocks are those of the last sampling (coarse) launch
     bool zero_step_skip = true;            // NERF_ZERO_STEP_SKIP=0 at nerf_create: the f32 kernels execute every k-step (networks loaded afterwards)
     bool ray_grouping = true;              // NERF_RAY_GROUPING=0 at nerf_create: ray-mode f32 launches keep 128 consecutive samples per workgroup tile (mlp_layout.h)
     bool wave_tiling = true;               // NERF_WAVE_TILING=0 at nerf_create: a wave of a ray-mode f32 launch keeps 32 consecutive samples of one ray (mlp_layout.h)
+    bool depth_order = true;               // NERF_DEPTH_ORDER=0 at nerf_create: the fine launch of an image pass keeps the static wave tiling (mlp_layout.h DepthOrder)
+    bool tile_rotation = true;             // NERF_TILE_ROTATION=0 at nerf_create: round k's tile of persistent workgroup c of the f32 fused kernel is k G + c (mlp_layout.h rotated_tile)
+    unsigned int *d_order = nullptr; size_t order_bytes = 0; // depth-order table of the pass under way: one slot per point of its ordered region
     unsigned long long *d_zskip = nullptr; // diagnostic (NERF_DEBUG_ZSKIP=1): {executed, total} ReLU k-steps of the f32 launch under way
     size_t max_rays_per_pass = (size_t)1 << 20;
     std::vector<hipEvent_t> ev_pool;

@@ -30,6 +30,7 @@ const float *small_of(const DevNet &n, int dtype) { return dtype == NERF_MLP_F32
 void zskip_of(const nerf_ctx *c, const DevNet &n, MlpArgs &a) {
     a.zero_skip = n.zero_skip ? 1 : 0; a.zskip_stats = c->d_zskip;
     a.ray_grouping = c->ray_grouping ? 1 : 0; a.wave_tiling = c->wave_tiling ? 1 : 0;
+    a.depth_order = c->depth_order ? 1 : 0; a.tile_rotation = c->tile_rotation ? 1 : 0; // the table itself is the pass pipeline's (nerf_render.cpp eval_net)
 }
 void zskip_of(const nerf_ctx *c, const DevNet &n, SeqArgs &a) { a.zero_skip = n.zero_skip ? 1 : 0; a.zskip_stats = c->d_zskip; }
 

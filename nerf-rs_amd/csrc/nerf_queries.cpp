@@ -735,6 +735,28 @@ int nerf_stage_hybrid_flags(nerf_ctx *c, size_t n_rays, int nc, int nf, float fa
                           tau > 0.0f ? tau : c->hybrid_tau, flags_out);
 } NERF_CATCH(c)
 
+int nerf_stage_depth_order(nerf_ctx *c, int rows, int rays_per_row, int samples_per_ray, const float *t, uint32_t *table_out) try {
+    if (!c) return fail(nullptr, NERF_ERR_INVALID, "ctx is NULL");
+    if (!t || !table_out) return fail(c, NERF_ERR_INVALID, "NULL buffer");
+    if (rows <= 0 || rays_per_row <= 0 || samples_per_ray <= 0 || (long long)rows * rays_per_row * samples_per_ray > 0x3fffffff)
+        return fail(c, NERF_ERR_INVALID, "rows, rays_per_row and samples_per_ray must be > 0 and within one pass");
+    const int n = rows * rays_per_row * samples_per_ray;
+    const nerfmlp::DepthOrder d = nerfmlp::depth_order_of(n, samples_per_ray, rays_per_row, true, true); // as the full launch of an image pass of this shape
+    if (d.tiles == 0) return fail(c, NERF_ERR_INVALID, "this window is not depth-ordered: rays_per_row % 8 == 0, rows >= 4, samples_per_ray % 32 == 0 and <= 512");
+    DeviceGuard dg(c->device);
+    int rc;
+    if ((rc = ensure_bytes(c, &c->d_scratch, &c->scratch_bytes, ((size_t)n + d.points) * 4))) return rc;
+    float *d_t = (float *)c->d_scratch;
+    unsigned int *d_table = (unsigned int *)(d_t + n);
+    HIP_TRY(c, hipMemcpyAsync(d_t, t, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    DepthOrderArgs q{};
+    q.t = d_t; q.rw = rays_per_row; q.spr = samples_per_ray; q.blocks_x = d.blocks_x; q.blocks = d.blocks; q.table = d_table;
+    HIP_TRY(c, launch_depth_order(q, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(table_out, d_table, (size_t)d.points * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return NERF_OK;
+} NERF_CATCH(c)
+
 int nerf_stage_integrate(nerf_ctx *c, size_t n_rays, int n, float far_, const float *rgb, const float *sigma, const float *t,
                          float *rgb_out, float *w_out) try {
     if (!c) return fail(nullptr, NERF_ERR_INVALID, "ctx is NULL");

@@ -374,7 +374,7 @@ int eval_net(nerf_ctx *c, const RenderJob &j, const Pass &p, int which, int dt, 
     a.sigma_out = sigma_out; a.rgb_out = rgb_out; // the coarse network: sigma only unless its colours are composited (reference discards them, src/lib.rs:404)
     a.skip_empty = j.skip_empty; a.skip_counter = j.skip_empty ? c->d_skip : nullptr; // only full kernels look at it
     a.nonfinite = nonfinite_of(c, dt);
-    if (which == NERF_NET_FINE) a.clock_out = j.clock_out;
+    if (which == (c->clock_coarse ? NERF_NET_COARSE : NERF_NET_FINE)) a.clock_out = j.clock_out;
     if (j.certify) return cert_pass(c, j, p, a, net, which, dt, kind);
     bool full = rgb_out != nullptr;
     if (p.origins) {
@@ -387,6 +387,19 @@ int eval_net(nerf_ctx *c, const RenderJob &j, const Pass &p, int which, int dt, 
         a.pts_soa = j.d_pts; a.dirs_aos = j.d_daos;
         int rc;
         if ((rc = timed(c, st, 2, 0, [&]() -> int { HIP_TRY(c, launch_batch_points(q, st)); return NERF_OK; }))) return rc;
+    }
+    // depth ordering (mlp_layout.h DepthOrder): the fine f32 launch of an image pass takes its waves from the pass's depth-sorted pixel blocks;
+    // the table is built here, behind the resampler that wrote t, on the render's stream
+    if (dt == NERF_MLP_F32 && !p.origins) {
+        const nerfmlp::DepthOrder d = nerf_mlp_depth_order(a, full);
+        if (d.tiles > 0) {
+            int rc;
+            if ((rc = ensure_bytes(c, (void **)&c->d_order, &c->order_bytes, (size_t)d.points * sizeof(unsigned int)))) return rc;
+            DepthOrderArgs q{};
+            q.t = t; q.rw = a.rays_per_row; q.spr = spr; q.blocks_x = d.blocks_x; q.blocks = d.blocks; q.table = c->d_order;
+            if ((rc = timed(c, st, 2, 0, [&]() -> int { HIP_TRY(c, launch_depth_order(q, st)); return NERF_OK; }))) return rc;
+            a.order_table = c->d_order;
+        }
     }
     return timed(c, st, kind, (uint64_t)a.n_points, [&]() -> int { HIP_TRY(c, launch_mlp(c, dt, a, full, st)); return NERF_OK; });
 }

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/nerf_mi355x.h"
+#include "mlp_layout.h"
 
 // A pass renders the rectangle [ry0, ry0+rh) x [rx0, rx0+rw) of the (rny x rnx) ray grid; ray r of the pass is
 // (ry0 + r / rw, rx0 + r % rw); its RNG pixel index is row * rnx + col.
@@ -81,6 +82,17 @@ hipError_t launch_bands_to_frame(const float *slots, float *frame, int w, int h,
 // out8 (device, 8 ints) = {count low, count high, ix_min, iy_min, iz_min, ix_max, iy_max, iz_max}; empty: mins = dims, maxs = -1
 hipError_t launch_occupancy_stats(const uint32_t *words, size_t n_cells, int nx, int ny, int nz, int *out8, hipStream_t st);
 size_t resample_lds_bytes(int nc, int nf);
+// Depth-order table of an image pass (mlp_layout.h DepthOrder; kernel: sampling_kernels.hip k_depth_order): for each of `blocks` 8 x 4 pixel
+// blocks (row-major, blocks_x = rw / 8 per row of blocks) the slots ray * spr + sample of its 32 spr points in ascending order of
+// (bits of t, ray-in-block, sample); table holds 32 spr blocks entries.  spr <= kDepthOrderMaxSpr; any bits of t give a permutation.
+struct DepthOrderArgs {
+    const float *t;      // rows x rw x spr, rows >= 4 (blocks / blocks_x)
+    int rw, spr, blocks_x, blocks;
+    unsigned int *table;
+    int row_pow2 = 0;    // set by launch_depth_order: smallest power of two >= spr
+};
+hipError_t launch_depth_order(const DepthOrderArgs &a, hipStream_t st);
+size_t depth_order_lds_bytes(int spr);
 size_t composite_lds_bytes(int n);
 // ---- zero certification (nerf_render_opts.certify_zero; kernels and protocol: sampling_kernels.hip) ------------------------------------
 struct CertPlanArgs {

@@ -753,6 +753,103 @@ hipError_t launch_occupancy_stats(const uint32_t *words, size_t n_cells, int nx,
     return hipGetLastError();
 }
 
+// ---- depth-order table (mlp_layout.h DepthOrder) ----------------------------------------------------------------------------------------
+// One workgroup per 8 x 4 pixel block of an image pass: the spr samples of the block's 32 rays, merged by depth.  A point's key is
+//     (uint32 bits of t) << 32 | (ray-in-block, row-major) * spr + sample
+// -- unique within the block whatever t holds -- and position q of the block's ascending order stores the point's slot ray * spr + sample in
+// table[32 spr b + q].  The keys are sorted as such, by a bitonic network in LDS over P = 32 * row_pow2 entries (each ray's row padded to a
+// power of two with keys above every real one): the table is a permutation of the block's slots for ANY bits of t -- ties, NaN, rows that are
+// not ascending.  Rows that ARE ascending (every pass the resampler wrote) are sorted runs already: odd rows are then mirrored, which is the
+// state a bitonic sort is in after its first log2(row_pow2) merges, and only the merges across rows run (55 of 91 steps at 64 + 128); one
+// row out of order anywhere in the block and the whole network runs.  The last three steps of a merge (partners 4, 2, 1 apart) stay in
+// the registers of the thread that holds the 8 entries.
+constexpr int kOrderThreads = 1024;
+__device__ __forceinline__ void order_cas(unsigned long long &a, unsigned long long &b, bool asc) {
+    const unsigned long long lo = a < b ? a : b, hi = a < b ? b : a;
+    a = asc ? lo : hi; b = asc ? hi : lo;
+}
+__global__ __launch_bounds__(kOrderThreads) void k_depth_order(const DepthOrderArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned long long s_key[];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int rp = a.row_pow2, P = 32 * rp, spr = a.spr;
+    const unsigned long long pad = ~0ull;
+    for (int i = tid; i < P; i += kOrderThreads) {
+        const int r = i / rp, s = i - r * rp;
+        unsigned long long key = pad;
+        if (s < spr) {
+            const int slot = nerfmlp::depth_block_slot(b, a.blocks_x, a.rw, spr, r, s);
+            key = ((unsigned long long)__float_as_uint(a.t[slot]) << 32) | (unsigned)(r * spr + s);
+        }
+        s_key[i] = key;
+    }
+    __syncthreads();
+    int out_of_order = 0;
+    for (int i = tid; i < P; i += kOrderThreads) {
+        const int s = i & (rp - 1);
+        if (s + 1 < spr && s_key[i] > s_key[i + 1]) out_of_order = 1;
+    }
+    const bool full_sort = __syncthreads_or(out_of_order) != 0; // block-uniform
+    if (!full_sort) { // mirror the odd rows: run r ascends iff r is even
+        constexpr int kPerThread = 32 * nerfmlp::kDepthOrderMaxSpr / kOrderThreads; // P <= 32 * kDepthOrderMaxSpr
+        unsigned long long keep[kPerThread];
+#pragma unroll
+        for (int n = 0; n < kPerThread; ++n) { const int i = tid + n * kOrderThreads; keep[n] = i < P ? s_key[i] : pad; }
+        __syncthreads();
+#pragma unroll
+        for (int n = 0; n < kPerThread; ++n) {
+            const int i = tid + n * kOrderThreads, r = i / rp, s = i - r * rp;
+            if (i < P && (r & 1)) s_key[r * rp + (rp - 1 - s)] = keep[n];
+        }
+        __syncthreads();
+    }
+    for (int k = full_sort ? 2 : 2 * rp; k <= P; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            if (j == 4) { // partners 4, 2 and 1 apart: the 8 aligned entries of one thread, which share the merge's direction (k >= 8)
+                for (int g = tid; g < P / 8; g += kOrderThreads) {
+                    unsigned long long v[8];
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) v[e] = s_key[8 * g + e];
+                    const bool asc = ((8 * g) & k) == 0;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) order_cas(v[e], v[e + 4], asc);
+#pragma unroll
+                    for (int e = 0; e < 8; e += 4) { order_cas(v[e], v[e + 2], asc); order_cas(v[e + 1], v[e + 3], asc); }
+#pragma unroll
+                    for (int e = 0; e < 8; e += 2) order_cas(v[e], v[e + 1], asc);
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) s_key[8 * g + e] = v[e];
+                }
+                __syncthreads();
+                break;
+            }
+            for (int q = tid; q < P / 2; q += kOrderThreads) {
+                const int i = ((q & ~(j - 1)) << 1) | (q & (j - 1)), l = i | j;
+                unsigned long long x = s_key[i], y = s_key[l];
+                order_cas(x, y, (i & k) == 0);
+                s_key[i] = x; s_key[l] = y;
+            }
+            __syncthreads();
+        }
+    }
+    unsigned int *out = a.table + (size_t)b * 32 * spr;
+    for (int q = tid; q < 32 * spr; q += kOrderThreads) {
+        const unsigned idx = (unsigned)s_key[q]; // the pads sort behind every real key
+        const int r = (int)(idx / (unsigned)spr), s = (int)(idx - (unsigned)r * (unsigned)spr);
+        out[q] = (unsigned)nerfmlp::depth_block_slot(b, a.blocks_x, a.rw, spr, r, s);
+    }
+}
+
+static int pow2_at_least(int v);
+size_t depth_order_lds_bytes(int spr) { return (size_t)32 * pow2_at_least(spr) * sizeof(unsigned long long); }
+hipError_t launch_depth_order(const DepthOrderArgs &a, hipStream_t st) {
+    if (a.blocks <= 0) return hipSuccess;
+    if (a.spr <= 0 || a.spr > nerfmlp::kDepthOrderMaxSpr || a.blocks_x <= 0 || a.rw != a.blocks_x * nerfmlp::kDepthBlockW || !a.t || !a.table) return hipErrorInvalidValue;
+    DepthOrderArgs b = a;
+    b.row_pow2 = pow2_at_least(a.spr);
+    hipLaunchKernelGGL(k_depth_order, dim3(a.blocks), dim3(kOrderThreads), depth_order_lds_bytes(a.spr), st, b);
+    return hipGetLastError();
+}
+
 // ---- launchers -----------------------------------------------------------------------------------------
 hipError_t launch_ray_dirs(const RayGenArgs &a, float *dirs, hipStream_t st) {
     if (a.n_rays <= 0) return hipSuccess;
@@ -777,6 +874,7 @@ hipError_t sampling_init(void) {
     hipError_t e = hipFuncSetAttribute((const void *)k_resample, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_cert_plan, hipFuncAttributeMaxDynamicSharedMemorySize, kCertPlanMaxLds); // (+ 60 B static)
     if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_cert_verify, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_depth_order, hipFuncAttributeMaxDynamicSharedMemorySize, (int)depth_order_lds_bytes(nerfmlp::kDepthOrderMaxSpr));
     return e;
 }
 
