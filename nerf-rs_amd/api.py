@@ -691,6 +691,34 @@ def _ray_opts(n_coarse, fine_samples_per_ray, seed, coarse_only, dtype):
     return RenderOpts(n_coarse, fine_samples_per_ray, coarse_only, None, 1, seed, dtype).to_c()
 
 
+def _ray_args(origins, dirs, bounds):
+    """origins (3,) or (n, 3), dirs (n, 3), bounds None or (n, 2) -> contiguous float32 arrays and n, or NerfError."""
+    d = _f32(dirs)
+    if d.ndim != 2 or d.shape[1] != 3:
+        raise NerfError(-1, "dirs must be an (n, 3) array")
+    n = d.shape[0]
+    o = _f32(origins)
+    if o.shape not in ((3,), (n, 3)):
+        raise NerfError(-1, "origins must have shape (3,) or (n, 3)")
+    b = None if bounds is None else _f32(bounds)
+    if b is not None and b.shape != (n, 2):
+        raise NerfError(-1, "bounds must be an (n, 2) array of (near, far)")
+    return o, d, b, n
+
+
+def _ptr(a):
+    """A numpy array -> the pointer the C ABI takes; None and raw device pointers (ints) pass."""
+    if not isinstance(a, np.ndarray):
+        return a
+    return a.ctypes.data_as({np.dtype(np.uint32): u32p, np.dtype(np.uint8): u8p}.get(a.dtype, f32p))
+
+
+def _ray_head(origins, n_origins, dirs, n_rays, normalize, near, far, bounds, rng_index, opts, bg, rgb, depth, opacity):
+    """What every nerf_render_rays* entry point takes from `origins` to `opacity_out`; arrays or raw device pointers."""
+    return (_ptr(origins), int(n_origins), _ptr(dirs), int(n_rays), int(bool(normalize)), float(near), float(far), _ptr(bounds), _ptr(rng_index),
+            C.byref(opts), bg, _ptr(rgb), _ptr(depth), _ptr(opacity))
+
+
 def render_rays(coarse, fine, origins, dirs, near, far, fine_samples_per_ray=128, *, n_coarse=64, bounds=None, normalize=True,
                 rng_index=None, seed=0, coarse_only=False, dtype="f32", background=None, aux=False, return_stats=False, normals_h=None,
                 certify_zero=False):
@@ -712,16 +740,7 @@ def render_rays(coarse, fine, origins, dirs, near, far, fine_samples_per_ray=128
     R = coarse.renderer
     if fine is not None and fine.renderer is not R:
         raise NerfError(-1, "coarse and fine networks must live in the same Renderer")
-    d = _f32(dirs)
-    if d.ndim != 2 or d.shape[1] != 3:
-        raise NerfError(-1, "dirs must be an (n, 3) array")
-    n = d.shape[0]
-    o = _f32(origins)
-    if o.shape not in ((3,), (n, 3)):
-        raise NerfError(-1, "origins must have shape (3,) or (n, 3)")
-    b = None if bounds is None else _f32(bounds)
-    if b is not None and b.shape != (n, 2):
-        raise NerfError(-1, "bounds must be an (n, 2) array of (near, far)")
+    o, d, b, n = _ray_args(origins, dirs, bounds)
     idx = None if rng_index is None else np.ascontiguousarray(rng_index, dtype=np.uint32)
     if idx is not None and idx.shape != (n,):
         raise NerfError(-1, "rng_index must have one entry per ray")
@@ -730,16 +749,14 @@ def render_rays(coarse, fine, origins, dirs, near, far, fine_samples_per_ray=128
     rgb = np.empty((n, 3), np.float32)
     depth, opacity = (np.empty(n, np.float32), np.empty(n, np.float32)) if aux else (None, None)
     st = CStats()
-    head = (R.handle, _p(o), 1 if o.ndim == 1 else n, _p(d), n, int(bool(normalize)), float(near), float(far),
-            None if b is None else _p(b), None if idx is None else idx.ctypes.data_as(u32p), C.byref(opts), bg,
-            _p(rgb), None if depth is None else _p(depth), None if opacity is None else _p(opacity))
+    head = _ray_head(o, 1 if o.ndim == 1 else n, d, n, normalize, near, far, b, idx, opts, bg, rgb, depth, opacity)
     if certify_zero:
-        check(R._L.nerf_render_rays_certified(*head, C.byref(st)), R.handle)
+        check(R._L.nerf_render_rays_certified(R.handle, *head, C.byref(st)), R.handle)
     elif normals_h is None:
-        check(R._L.nerf_render_rays(*head, C.byref(st)), R.handle)
+        check(R._L.nerf_render_rays(R.handle, *head, C.byref(st)), R.handle)
     else:
         normals = np.empty((n, 3), np.float32)
-        check(R._L.nerf_render_rays_normals(*head, float(normals_h), _p(normals), C.byref(st)), R.handle)
+        check(R._L.nerf_render_rays_normals(R.handle, *head, float(normals_h), _p(normals), C.byref(st)), R.handle)
     out = (rgb, depth, opacity) if aux else (rgb,)
     if normals_h is not None:
         out += (normals,)
@@ -766,14 +783,13 @@ def render_rays_device(coarse, fine, d_origins, n_origins, d_dirs, n_rays, near,
     opts = _ray_opts(n_coarse, fine_samples_per_ray, seed, coarse_only, dtype)
     keep, bg = _background(background)
     st = CStats()
-    head = (R.handle, d_origins, int(n_origins), d_dirs, int(n_rays), int(bool(normalize)), float(near), float(far),
-            d_bounds, d_rng_index, C.byref(opts), bg, d_rgb, d_depth, d_opacity)
+    head = _ray_head(d_origins, n_origins, d_dirs, n_rays, normalize, near, far, d_bounds, d_rng_index, opts, bg, d_rgb, d_depth, d_opacity)
     if certify_zero:
-        check(R._L.nerf_render_rays_certified_device(*head, stream, C.byref(st) if return_stats else None), R.handle)
+        check(R._L.nerf_render_rays_certified_device(R.handle, *head, stream, C.byref(st) if return_stats else None), R.handle)
     elif d_normals is None:
-        check(R._L.nerf_render_rays_device(*head, stream, C.byref(st) if return_stats else None), R.handle)
+        check(R._L.nerf_render_rays_device(R.handle, *head, stream, C.byref(st) if return_stats else None), R.handle)
     else:
-        check(R._L.nerf_render_rays_normals_device(*head, float(normals_h), d_normals, stream, C.byref(st) if return_stats else None), R.handle)
+        check(R._L.nerf_render_rays_normals_device(R.handle, *head, float(normals_h), d_normals, stream, C.byref(st) if return_stats else None), R.handle)
     return Stats(st) if return_stats else None
 
 
@@ -813,20 +829,6 @@ def dilate_occupancy_device(renderer, d_bits, dims, radius, d_out, want_stats=Fa
     return (int(cnt.value), tuple(int(v) for v in bounds)) if want_stats else None
 
 
-def _clip_ray_args(origins, dirs, bounds):
-    d = _f32(dirs)
-    if d.ndim != 2 or d.shape[1] != 3:
-        raise NerfError(-1, "dirs must be an (n, 3) array")
-    n = d.shape[0]
-    o = _f32(origins)
-    if o.shape not in ((3,), (n, 3)):
-        raise NerfError(-1, "origins must have shape (3,) or (n, 3)")
-    b = None if bounds is None else _f32(bounds)
-    if b is not None and b.shape != (n, 2):
-        raise NerfError(-1, "bounds must be an (n, 2) array of (near, far)")
-    return o, d, b, n
-
-
 def clip_rays(renderer, bits, lo, step, dims, origins, dirs, near, far, bounds=None, normalize=True, return_count=False, debug_cpu=False):
     """Per ray the span of the occupied cells of a density_grid occupancy (bits over the lattice lo, step, dims) inside the ray's
     [near, far] (nerf_clip_rays) -> (bounds (n, 2) float32, hit (n,) bool): a hit ray's bounds are (t_first, t_last), to be handed to
@@ -837,7 +839,7 @@ def clip_rays(renderer, bits, lo, step, dims, origins, dirs, near, far, bounds=N
     lo_c, step_c = _f32(lo).reshape(-1), _f32(step).reshape(-1)
     if lo_c.size != 3 or step_c.size != 3:
         raise NerfError(-1, "lo and step must have three entries each")
-    o, d, b, n = _clip_ray_args(origins, dirs, bounds)
+    o, d, b, n = _ray_args(origins, dirs, bounds)
     out, hit = np.empty((n, 2), np.float32), np.empty(n, np.uint8)
     cnt, refused = C.c_uint64(0), C.c_uint64(0)
     tail = (words.ctypes.data_as(u32p), _p(lo_c), _p(step_c), dims_c.ctypes.data_as(i32p), _p(o), 1 if o.ndim == 1 else n, _p(d), n,
@@ -882,7 +884,7 @@ def render_rays_clipped(coarse, fine, bits, lo, step, dims, origins, dirs, near,
     lo_c, step_c = _f32(lo).reshape(-1), _f32(step).reshape(-1)
     if lo_c.size != 3 or step_c.size != 3:
         raise NerfError(-1, "lo and step must have three entries each")
-    o, d, b, n = _clip_ray_args(origins, dirs, bounds)
+    o, d, b, n = _ray_args(origins, dirs, bounds)
     idx = None if rng_index is None else np.ascontiguousarray(rng_index, dtype=np.uint32)
     if idx is not None and idx.shape != (n,):
         raise NerfError(-1, "rng_index must have one entry per ray")
@@ -892,11 +894,9 @@ def render_rays_clipped(coarse, fine, bits, lo, step, dims, origins, dirs, near,
     depth, opacity = (np.empty(n, np.float32), np.empty(n, np.float32)) if aux else (None, None)
     hit, cnt, st = np.empty(n, np.uint8), C.c_uint64(0), CStats()
     call = R._L.nerf_render_rays_clipped_certified if certify_zero else R._L.nerf_render_rays_clipped
-    check(call(R.handle, words.ctypes.data_as(u32p), _p(lo_c), _p(step_c), dims_c.ctypes.data_as(i32p), _p(o),
-                                        1 if o.ndim == 1 else n, _p(d), n, int(bool(normalize)), float(near), float(far),
-                                        None if b is None else _p(b), None if idx is None else idx.ctypes.data_as(u32p), C.byref(opts), bg,
-                                        _p(rgb), None if depth is None else _p(depth), None if opacity is None else _p(opacity),
-                                        hit.ctypes.data_as(u8p), C.byref(cnt), C.byref(st)), R.handle)
+    head = _ray_head(o, 1 if o.ndim == 1 else n, d, n, normalize, near, far, b, idx, opts, bg, rgb, depth, opacity)
+    check(call(R.handle, words.ctypes.data_as(u32p), _p(lo_c), _p(step_c), dims_c.ctypes.data_as(i32p), *head, hit.ctypes.data_as(u8p), C.byref(cnt),
+               C.byref(st)), R.handle)
     out = (rgb, depth, opacity) if aux else (rgb,)
     if return_hit:
         out += (hit.astype(bool), int(cnt.value))
@@ -920,10 +920,9 @@ def render_rays_clipped_device(coarse, fine, d_bits, lo, step, dims, d_origins, 
     keep, bg = _background(background)
     cnt, st = C.c_uint64(0), CStats()
     call = R._L.nerf_render_rays_clipped_certified_device if certify_zero else R._L.nerf_render_rays_clipped_device
-    check(call(R.handle, d_bits, _p(lo_c), _p(step_c), dims_c.ctypes.data_as(i32p), d_origins, int(n_origins),
-                                               d_dirs, int(n_rays), int(bool(normalize)), float(near), float(far), d_bounds, d_rng_index,
-                                               C.byref(opts), bg, d_rgb, d_depth, d_opacity, d_hit, C.byref(cnt), stream,
-                                               C.byref(st) if return_stats else None), R.handle)
+    head = _ray_head(d_origins, n_origins, d_dirs, n_rays, normalize, near, far, d_bounds, d_rng_index, opts, bg, d_rgb, d_depth, d_opacity)
+    check(call(R.handle, d_bits, _p(lo_c), _p(step_c), dims_c.ctypes.data_as(i32p), *head, d_hit, C.byref(cnt), stream,
+               C.byref(st) if return_stats else None), R.handle)
     return (int(cnt.value), Stats(st)) if return_stats else int(cnt.value)
 
 

@@ -4,7 +4,7 @@
 // camera JSON files: every call must come back with a status code and a message -- a sanitizer report aborts with a non-zero exit.
 //   host_asan_driver check_dir <dir> | pack_dir <dir> <blob> | check_blob <blob> | camera_json <json> <w> <h> |
 //                    debug_pack <dir> | debug_fold <dir> | quantize | save_ppm <path> <w> <h> | save_pfm <path> <w> <h> | save_pam <path> <w> <h> | split |
-//                    ply <path> <n_vertices> <n_triangles> <normals 0|1> <colours 0|1>
+//                    ply <path> <n_vertices> <n_triangles> <normals 0|1> <colours 0|1> | stage_layout
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -15,6 +15,7 @@
 
 #include "../../include/nerf_mi355x.h"
 #include "host_util.h"
+#include "stage_layout.h"
 
 static int report(const char *what, int rc) {
     printf("%s rc=%d msg=%s\n", what, rc, rc ? nerfhost::last_error_noctx() : "");
@@ -142,6 +143,44 @@ int main(int argc, char **argv) {
         for (int i = 0; i < 24; ++i) printf("%04x ", p2[i]);
         printf("\n");
         return report("split", rc);
+    }
+    if (cmd == "stage_layout") { // the bump allocator behind every staging layout and pass workspace (stage_layout.h); rc = the first failed check
+        using nerfint::StageLayout;
+        const size_t A = StageLayout::kAlign;
+        int rc = 0;
+        std::vector<char> base(8 * A);
+        float src[3] = {1.f, 2.f, 3.f}, dst[5];
+        StageLayout l;
+        const int up = l.add(sizeof(float), 3, src);                     // 12 bytes: the next part starts one alignment unit later
+        const int absent = l.opt(false, sizeof(float), 1000, src, dst);  // an absent part: no space, no copy, no address
+        const int present = l.opt(true, sizeof(float), 5, nullptr, dst);
+        const int empty = l.add(sizeof(float), 0, src, dst);             // a zero-length part: an address, no bytes
+        const int guarded = l.add(4, 32 + 70 + 32, nullptr, dst, 0xFF);  // guard words, list, guard words: ONE part, contiguous
+        const int last = l.add(1, A + 1, nullptr, nullptr, 0x00);
+        if (l.refused || l.n_parts != 5 || absent != StageLayout::kAbsent || up != 0 || present != 1 || last != 4) rc = 1;
+        if (!rc && l.at<char>(base.data(), absent) != nullptr) rc = 2;
+        for (int k = 0; k < l.n_parts && !rc; ++k)
+            if (l.parts[k].offset % A || l.at<char>(base.data(), k) != base.data() + l.parts[k].offset) rc = 3;
+        if (!rc && (l.parts[present].offset != A || l.parts[empty].offset != 2 * A || l.parts[empty].bytes != 0 || l.parts[guarded].offset != 2 * A)) rc = 4;
+        if (!rc && (l.parts[guarded].bytes != 4 * 134 || l.parts[last].offset != 2 * A + 3 * A || l.total != 5 * A + 2 * A || l.total > base.size())) rc = 5;
+        if (!rc && (l.parts[up].upload != src || l.parts[up].download || l.parts[up].fill != StageLayout::kNoFill || l.parts[present].download != dst ||
+                    l.parts[guarded].fill != 0xFF || l.parts[last].fill != 0x00)) rc = 6;
+        for (int k = 0; k < l.n_parts && !rc; ++k) { // every part lies inside the total, and a fill of each stays inside the buffer
+            if (l.parts[k].offset + l.parts[k].bytes > l.total) rc = 7;
+            else if (l.parts[k].fill != StageLayout::kNoFill) memset(l.at<char>(base.data(), k), l.parts[k].fill, l.parts[k].bytes);
+        }
+        // sizes that would overflow size_t are refused, not wrapped: elem * count, the padding of one part, the running total
+        StageLayout o1, o2, o3;
+        if (!rc && (o1.add(8, SIZE_MAX / 4) != StageLayout::kAbsent || !o1.refused)) rc = 8;
+        if (!rc && (o2.add(1, SIZE_MAX - 3) != StageLayout::kAbsent || !o2.refused)) rc = 9;
+        if (!rc && (o3.add(1, SIZE_MAX / 2) < 0 || o3.add(1, SIZE_MAX / 2) != StageLayout::kAbsent || !o3.refused)) rc = 10;
+        if (!rc && o3.add(1, 1) != StageLayout::kAbsent) rc = 11; // a refused layout stays refused
+        StageLayout many;                                          // more parts than the table holds: refused as well
+        for (int k = 0; k < StageLayout::kMaxParts; ++k) if (many.add(4, 1) != k) rc = rc ? rc : 12;
+        if (!rc && (many.add(4, 1) != StageLayout::kAbsent || !many.refused)) rc = 13;
+        printf("stage_layout total %zu parts %d\n", l.total, l.n_parts);
+        if (rc) nerfhost::fail_noctx(rc, "stage_layout: check failed");
+        return report("stage_layout", rc);
     }
     fprintf(stderr, "usage: see the header comment\n");
     return 2;

@@ -30,7 +30,7 @@ hipEvent_t get_event(nerf_ctx *c) {
 }
 
 void recycle_render(nerf_ctx *c) {
-    for (auto &p : c->last_render) if (p.kind != 1) { c->ev_pool.push_back(p.a); c->ev_pool.push_back(p.b); }
+    for (auto &p : c->last_render) if (!p.dominant) { c->ev_pool.push_back(p.a); c->ev_pool.push_back(p.b); }
     c->last_render.clear();
 }
 
@@ -41,31 +41,61 @@ void recycle_dominant(nerf_ctx *c, size_t keep) {
     }
 }
 
-int ensure_bytes(nerf_ctx *c, void **p, size_t *cur, size_t need) {
-    if (*cur >= need) return NERF_OK;
-    if (*p) { HIP_TRY(c, hipDeviceSynchronize()); HIP_TRY(c, hipFree(*p)); *p = nullptr; *cur = 0; }
-    HIP_TRY(c, hipMalloc(p, need));
-    *cur = need;
+int DevBuf::ensure(nerf_ctx *c, size_t need) {
+    if (bytes >= need) return NERF_OK;
+    if (p) { HIP_TRY(c, hipDeviceSynchronize()); HIP_TRY(c, hipFree(p)); p = nullptr; bytes = 0; }
+    HIP_TRY(c, hipMalloc(&p, need));
+    bytes = need;
+    return NERF_OK;
+}
+
+int DevBuf::release(nerf_ctx *c) {
+    if (!p) return NERF_OK;
+    HIP_TRY(c, hipDeviceSynchronize());
+    HIP_TRY(c, hipFree(p));
+    p = nullptr; bytes = 0;
+    return NERF_OK;
+}
+
+int Staging::begin() {
+    if (refused) return fail(c, NERF_ERR_INVALID, "internal error: staging layout too large");
+    int rc;
+    if ((rc = buf.ensure(c, total))) return rc;
+    for (int k = 0; k < n_parts; ++k) {
+        const Part &q = parts[k];
+        if (!q.bytes) continue;
+        if (q.upload) HIP_TRY(c, hipMemcpyAsync(at<char>(k), q.upload, q.bytes, hipMemcpyHostToDevice, st));
+        if (q.fill != kNoFill) HIP_TRY(c, hipMemsetAsync(at<char>(k), q.fill, q.bytes, st));
+    }
+    return NERF_OK;
+}
+
+int Staging::finish() {
+    for (int k = 0; k < n_parts; ++k)
+        if (parts[k].download && parts[k].bytes) HIP_TRY(c, hipMemcpyAsync(parts[k].download, at<char>(k), parts[k].bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
     return NERF_OK;
 }
 
 // The coarse network's colours exist only in a coarse_only render (the reference discards them otherwise, src/lib.rs:404):
 // their buffer (rays x nc x 3 floats, 492 MB for an 800x800 pass) is allocated on first such use only.
 int ensure_workspace(nerf_ctx *c, size_t rays, size_t nc, size_t m, bool need_rgbc) {
-    if (rays <= c->ws_rays && nc <= c->ws_nc && m <= c->ws_m && (!need_rgbc || c->d_rgbc)) return NERF_OK;
+    if (rays <= c->ws_rays && nc <= c->ws_nc && m <= c->ws_m && (!need_rgbc || c->buf[BUF_RGBC].p)) return NERF_OK;
     rays = std::max(rays, c->ws_rays); nc = std::max(nc, c->ws_nc); m = std::max(m, c->ws_m);
-    need_rgbc = need_rgbc || c->d_rgbc != nullptr;
+    need_rgbc = need_rgbc || c->buf[BUF_RGBC].p != nullptr;
     HIP_TRY(c, hipDeviceSynchronize());
-    float **ptrs[] = {&c->d_dirs, &c->d_tc, &c->d_sc, &c->d_rgbc, &c->d_tf, &c->d_sf, &c->d_rgbf};
-    for (auto p : ptrs) if (*p) { HIP_TRY(c, hipFree(*p)); *p = nullptr; }
+    for (int k = BUF_DIRS; k <= BUF_RGBF; ++k) {
+        DevBuf &b = c->buf[k];
+        if (b.p) { HIP_TRY(c, hipFree(b.p)); b.p = nullptr; b.bytes = 0; }
+    }
     c->ws_rays = c->ws_nc = c->ws_m = 0;
-    HIP_TRY(c, hipMalloc((void **)&c->d_dirs, rays * 3 * sizeof(float)));
-    HIP_TRY(c, hipMalloc((void **)&c->d_tc, rays * nc * sizeof(float)));
-    HIP_TRY(c, hipMalloc((void **)&c->d_sc, rays * nc * sizeof(float)));
-    if (need_rgbc) HIP_TRY(c, hipMalloc((void **)&c->d_rgbc, rays * nc * 3 * sizeof(float)));
-    HIP_TRY(c, hipMalloc((void **)&c->d_tf, rays * m * sizeof(float)));
-    HIP_TRY(c, hipMalloc((void **)&c->d_sf, rays * m * sizeof(float)));
-    HIP_TRY(c, hipMalloc((void **)&c->d_rgbf, rays * m * 3 * sizeof(float)));
+    const size_t floats[] = {rays * 3, rays * nc, rays * nc, need_rgbc ? rays * nc * 3 : 0, rays * m, rays * m, rays * m * 3};
+    for (int k = BUF_DIRS; k <= BUF_RGBF; ++k) {
+        DevBuf &b = c->buf[k];
+        if (k == BUF_RGBC && !need_rgbc) continue;
+        HIP_TRY(c, hipMalloc(&b.p, floats[k - BUF_DIRS] * sizeof(float)));
+        b.bytes = floats[k - BUF_DIRS] * sizeof(float);
+    }
     c->ws_rays = rays; c->ws_nc = nc; c->ws_m = m;
     return NERF_OK;
 }
@@ -173,10 +203,9 @@ void nerf_destroy(nerf_ctx *c) {
     DeviceGuard dg(c->device);
     (void)hipDeviceSynchronize();
     for (auto &n : c->net) { if (n.wstream) (void)hipFree(n.wstream); if (n.small) (void)hipFree(n.small); if (n.small_f32) (void)hipFree(n.small_f32); if (n.wstream_bf16v2) (void)hipFree(n.wstream_bf16v2); if (n.wstream_x3) (void)hipFree(n.wstream_x3); if (n.wstream_x2) (void)hipFree(n.wstream_x2); if (n.wstream_f16v2) (void)hipFree(n.wstream_f16v2); }
-    void *bufs[] = {c->d_dirs, c->d_tc, c->d_sc, c->d_rgbc, c->d_tf, c->d_sf, c->d_rgbf, c->d_rayfb, c->d_rayaux, c->d_out, c->d_pack, c->d_scratch,
-                    c->d_mesh, c->d_batch, c->d_comp, c->d_normal, c->d_stencil, c->d_clip, c->d_clock, c->d_zskip, c->d_skip, c->d_nonfinite, c->d_seq, c->d_h8,
-                    c->d_slot_point, c->d_flag_list, c->d_point_list, c->d_jstar, c->d_cert_aux, c->d_cert, c->d_order};
-    for (void *p : bufs) if (p) (void)hipFree(p);
+    for (DevBuf &b : c->buf) if (b.p) (void)hipFree(b.p);
+    void *counters[] = {c->d_clock, c->d_zskip, c->d_skip, c->d_nonfinite}; // fixed-size, allocated by nerf_create
+    for (void *p : counters) if (p) (void)hipFree(p);
     recycle_render(c);
     recycle_dominant(c, 0);
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
@@ -211,9 +240,8 @@ int nerf_kernel_time_query(nerf_ctx *c, double *ms, uint64_t *points, uint32_t *
     if (points) *points = pts;
     if (n_launches) *n_launches = nl;
     if (reset) {
-        // last_render may still list these pairs (kind 1); it never recycles them, and they are not read again
-        for (auto &p : c->last_render) if (p.kind == 1) p.kind = 3;
-        c->last_render.erase(std::remove_if(c->last_render.begin(), c->last_render.end(), [](const EvPair &p) { return p.kind == 3; }), c->last_render.end());
+        // last_render may still list these pairs; it never recycles them, and they are not read again
+        c->last_render.erase(std::remove_if(c->last_render.begin(), c->last_render.end(), [](const EvPair &p) { return p.dominant; }), c->last_render.end());
         recycle_dominant(c, 0);
     }
     return NERF_OK;

@@ -4,6 +4,7 @@
 // nothing here is part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include <algorithm>
@@ -13,6 +14,7 @@
 #include <vector>
 
 #include "../../include/nerf_mi355x.h"
+#include "stage_layout.h"
 
 struct MlpArgs;    // mlp_kernel.h
 struct SeqArgs;
@@ -46,12 +48,82 @@ constexpr float kCertMarginCoarse = 1.0f, kCertMarginFine = 3.0f;
 // (audited errors on lego: 0.03-0.055 / 0.12-0.17; floor sweep: profiles/r04_certify_f16_prefilter_margin_sweep.log -- fine 0.3 trips the half-margin rule).
 constexpr float kCertMarginCoarseF16 = 0.25f, kCertMarginFineF16 = 0.5f;
 
+// what a pair of events brackets (finish_stats sorts the times by it)
+enum EvKind {
+    EV_COARSE_MLP = 0,   // the sampling pass's network launch
+    EV_IMAGE_COLOUR = 1, // the colour-producing network launch of an image render: the dominant kernel (nerf_kernel_time_query)
+    EV_OTHER = 2,
+    EV_COLOUR_SIDE = 4,  // colour head of skip_dead; certify_zero's launches around the list kernel of the colour-producing network
+    EV_BATCH_COLOUR = 5, // the colour-producing network launch of a ray batch (never in `dominant`)
+    EV_NORMAL_SIGMA = 6, // the sigma-only stencil launch of a normals render
+    EV_NORMAL_SMALL = 7, // its small kernels
+};
+
 struct EvPair {
     hipEvent_t a, b;
-    int kind; // 0 coarse mlp, 1 fine mlp (dominant), 2 other, 4 colour head of skip_dead, 5 the colour-producing mlp of a ray batch (not in `dominant`),
-              // 6 the sigma-only stencil launch of a normals render, 7 its small kernels (neither in `dominant`)
+    EvKind kind;
+    bool dominant; // owned by ctx->dominant (handed over by a finished image render: recycle_dominant returns it to the pool); else by
+                   // ctx->last_render (recycle_render does)
     uint64_t points;
 };
+
+// A device buffer of the context that grows on demand and is freed with it: nerf_destroy walks nerf_ctx::buf.
+struct DevBuf {
+    void *p = nullptr;
+    size_t bytes = 0; // capacity
+    int ensure(nerf_ctx *c, size_t need); // grows only; a regrow synchronises the device and frees the old buffer first
+    int release(nerf_ctx *c);             // synchronises the device and frees
+};
+
+enum BufId {
+    // pass workspace: ensure_workspace grows the seven together (BUF_RGBC only once a coarse_only render asks for it)
+    BUF_DIRS, BUF_TC, BUF_SC, BUF_RGBC, BUF_TF, BUF_SF, BUF_RGBF,
+    BUF_RAYFB,      // SSAA ray framebuffer
+    BUF_RAYAUX,     // SSAA ray-level depth + opacity maps (nerf_render_image_aux)
+    BUF_OUT,        // staging of the host-pointer render entry points (and of nerf_render_image_multi's bands)
+    BUF_PACK,       // RGBA8 renders: the f32 frame [+ opacity plane] the pack kernel reads (a host-pointer call stages the packed words in BUF_OUT)
+    BUF_BATCH,      // ray batches with per-ray origins / bounds: per pass {far per ray, points 3 x n SoA, directions n x 3 AoS}
+    BUF_SCRATCH,    // staging of forward_batch, the queries and the stage calls; an extracted mesh
+    BUF_MESH,       // isosurface extraction (isosurface_kernels.h): the per-lattice-point workspace
+    BUF_COMP,       // lattice components (components_kernels.h): labels, sizes / keep flags; only when a filter or a component query is asked for
+    BUF_NORMAL,     // surface normals (normal_kernels.h): per pass {weights, live list: 4 B per sample each; count, base per ray; block sums; total}
+    BUF_STENCIL,    // per stencil point 16 B {3 coordinates, sigma}; also serves nerf_density_gradient_batch, chunk by chunk
+    BUF_CLIP,       // ray clipping (ray_clip_kernels.h): per ray of a batch the clipped bounds, hit flag and compacted copies of a clipped render; block sums
+    BUF_SEQ,        // skip_dead: one SeqCounters per MLP launch of a render
+    BUF_H8,         // ... the compacted trunk outputs of the live samples (reserve_seq gives a much too large one back)
+    BUF_SLOT_POINT, // ... and their sample indices
+    BUF_FLAG_LIST,  // hybrid sampling: rays whose coarse pass is redone in f32
+    BUF_POINT_LIST, // certify_zero: samples the exact kernel evaluates (one list, reused by every launch)
+    BUF_CERT,       // ... one CertCounters per (pass, network)
+    BUF_JSTAR,      // ... per ray of a pass: first sample behind the predicted cut
+    BUF_CERT_AUX,   // ... {sample, 16-bit (pre-filter) pre-activation} of the audited certificates of a launch
+    BUF_ORDER,      // depth-order table of the pass under way: one slot per point of its ordered region
+    BUF_COUNT
+};
+
+// The counters of one (pass, network) of a certify_zero render (nerf_render.cpp cert_pass, sampling_kernels.hip k_cert_*).  Device code
+// receives pointers to single words; launch_cert_audit receives &audited and writes the four words from there.
+struct CertCounters {
+    uint32_t list1_len, list2_len;                            // wanted lengths of the two sample lists (entries beyond the capacity are counted, not stored)
+    uint32_t audited, violations, headroom_code, max_err_bits; // the audit
+    uint32_t fallback_rays;                                   // rays whose predicted cut the exact transmittance did not confirm
+    uint32_t aux_count;                                       // audit records
+    uint32_t pf_ray_head;                                     // the pre-filter's ray queue
+    uint32_t list1_back_len;                                  // list 1's back part (probable zeros, audited certificates)
+    unsigned long long pf_samples;                            // samples the pre-filter evaluated
+    uint32_t range_left;                                      // f16 pre-filter: wave tiles in which an activation left the f16 range
+    uint32_t unused[3];
+};
+static_assert(sizeof(CertCounters) == 64 && offsetof(CertCounters, audited) == 8 && offsetof(CertCounters, max_err_bits) == 20 &&
+              offsetof(CertCounters, pf_samples) == 40 && offsetof(CertCounters, range_left) == 48, "CertCounters: sixteen words, the u64 at words 10 and 11");
+
+// The counters of one MLP launch of a skip_dead render (per pass: coarse, fine, hybrid f32 redo of the coarse pass).
+struct SeqCounters {
+    uint32_t ray_head;            // ray queue
+    uint32_t live_count;          // live samples; the hybrid redo's slot: flagged rays
+    unsigned long long evaluated; // samples the trunk launch evaluated
+};
+static_assert(sizeof(SeqCounters) == 16 && offsetof(SeqCounters, evaluated) == 8, "SeqCounters: four words");
 
 } // namespace nerfint
 
@@ -62,42 +134,13 @@ struct nerf_ctx {
     std::string err;
     hipStream_t stream = nullptr; // used by the host-pointer entry points
     nerfint::DevNet net[2];
-    // pass workspace
-    size_t ws_rays = 0, ws_nc = 0, ws_m = 0;
-    float *d_dirs = nullptr, *d_tc = nullptr, *d_sc = nullptr, *d_rgbc = nullptr, *d_tf = nullptr, *d_sf = nullptr,
-          *d_rgbf = nullptr;
-    float *d_rayfb = nullptr; size_t rayfb_floats = 0; // SSAA ray framebuffer
-    float *d_rayaux = nullptr; size_t rayaux_bytes = 0; // SSAA ray-level depth + opacity maps (nerf_render_image_aux)
-    float *d_out = nullptr; size_t out_floats = 0;       // host-pointer render output staging
-    float *d_pack = nullptr; size_t pack_bytes = 0;      // RGBA8 renders: the f32 frame [+ opacity plane] the pack kernel reads (a host-pointer call stages the packed words in d_out)
-    // ray batches with per-ray origins / bounds (nerf_render_rays): per pass {far per ray, points 3 x n SoA, directions n x 3 AoS}
-    void *d_batch = nullptr; size_t batch_bytes = 0;
-    // scratch for forward_batch / stage calls
-    void *d_scratch = nullptr; size_t scratch_bytes = 0;
-    // isosurface extraction (isosurface_kernels.h): the per-lattice-point workspace; the mesh itself is staged in d_scratch
-    void *d_mesh = nullptr; size_t mesh_bytes = 0;
-    // lattice components (components_kernels.h): labels, sizes / keep flags; allocated only when a filter or a component query is asked for
-    void *d_comp = nullptr; size_t comp_bytes = 0;
-    // surface normals (normal_kernels.h): per pass {weights, live list: 4 B per sample each; count, base per ray; block sums; total}, and
-    // per stencil point 16 B {3 coordinates, sigma}; the latter also serves nerf_density_gradient_batch, chunk by chunk
-    void *d_normal = nullptr; size_t normal_bytes = 0;
-    void *d_stencil = nullptr; size_t stencil_bytes = 0;
-    // ray clipping (ray_clip_kernels.h): per ray of a batch the clipped bounds, hit flag and compacted copies of a clipped render; block sums
-    void *d_clip = nullptr; size_t clip_bytes = 0;
+    size_t ws_rays = 0, ws_nc = 0, ws_m = 0; // what the pass workspace holds
+    nerfint::DevBuf buf[nerfint::BUF_COUNT];
+    template <class T = float>
+    T *dev(nerfint::BufId id) const { return (T *)buf[id].p; } // the buffer, typed
     size_t gradient_chunk = (size_t)1 << 20;             // points per internal chunk of nerf_density_gradient_batch (NERF_GRADIENT_CHUNK)
     bool debug_normals = false;                          // NERF_DEBUG_NORMALS=1: a normals render with stats prints its live share and kernel times
     uint64_t normal_live = 0, normal_samples = 0;        // of the last normals render: live / composited samples
-    // skip_dead: device queue/counters {u32 ray counter, u32 live count, u64 chunk count} per MLP launch of a render, the
-    // compacted trunk outputs of the live samples and their sample indices
-    unsigned int *d_seq = nullptr; size_t seq_slots = 0;
-    float *d_h8 = nullptr; size_t h8_bytes = 0;
-    unsigned int *d_slot_point = nullptr; size_t slot_point_bytes = 0;
-    unsigned int *d_flag_list = nullptr; size_t flag_list_bytes = 0; // hybrid sampling: rays whose coarse pass is redone in f32
-    // zero certification (nerf_render_opts.certify_zero; nerf_render.cpp cert_pass, sampling_kernels.hip k_cert_*)
-    unsigned int *d_point_list = nullptr; size_t point_list_bytes = 0; // samples the exact kernel evaluates (one list, reused by every launch)
-    unsigned int *d_cert = nullptr; size_t cert_bytes = 0;             // counters, 8 per (pass, network)
-    int *d_jstar = nullptr; size_t jstar_bytes = 0;                    // per ray of a pass: first sample behind the predicted cut
-    unsigned int *d_cert_aux = nullptr; size_t cert_aux_bytes = 0;     // {sample, 16-bit (pre-filter) pre-activation} of the audited certificates of a launch
     float cert_margin[2] = {nerfint::kCertMarginCoarse, nerfint::kCertMarginFine}; // widened by render_device when an audit fails; reset at load
     float cert_margin_floor[2] = {nerfint::kCertMarginCoarse, nerfint::kCertMarginFine};
     float cert_margin_floor_f16[2] = {nerfint::kCertMarginCoarseF16, nerfint::kCertMarginFineF16};
@@ -113,7 +156,7 @@ struct nerf_ctx {
     bool cert_seq_prefilter = true;       // 16-bit pre-filter ray-sequential with its own predicted cut (false: the fused 16-bit kernel over all samples)
     double cert_list_frac = 0.5;          // list capacity as a fraction of a pass's samples: what earlier frames needed + 25 %
     float hybrid_tau = 1e-5f;                                        // a draw predicted to move by more than this (in t) flags its ray
-    size_t max_export_bytes = (size_t)16 << 30; // budget of d_h8: bounds the rays per pass of skip_dead in a SPLIT arithmetic (NERF_MAX_EXPORT_BYTES);
+    size_t max_export_bytes = (size_t)16 << 30; // budget of BUF_H8: bounds the rays per pass of skip_dead in a SPLIT arithmetic (NERF_MAX_EXPORT_BYTES);
                                                 // 16 GiB = 8 passes per 800x800 frame, 1.4 % slower than one pass of 128 GiB
     unsigned long long *d_skip = nullptr;  // device counter of skipped 128-point tiles (skip_empty)
     unsigned int *d_nonfinite = nullptr;   // device counter of non-finite density pre-activations (split arithmetics)
@@ -125,7 +168,6 @@ struct nerf_ctx {
     bool wave_tiling = true;               // NERF_WAVE_TILING=0 at nerf_create: a wave of a ray-mode f32 launch keeps 32 consecutive samples of one ray (mlp_layout.h)
     bool depth_order = true;               // NERF_DEPTH_ORDER=0 at nerf_create: the fine launch of an image pass keeps the static wave tiling (mlp_layout.h DepthOrder)
     bool tile_rotation = true;             // NERF_TILE_ROTATION=0 at nerf_create: round k's tile of persistent workgroup c of the f32 fused kernel is k G + c (mlp_layout.h rotated_tile)
-    unsigned int *d_order = nullptr; size_t order_bytes = 0; // depth-order table of the pass under way: one slot per point of its ordered region
     unsigned long long *d_zskip = nullptr; // diagnostic (NERF_DEBUG_ZSKIP=1): {executed, total} ReLU k-steps of the f32 launch under way
     size_t max_rays_per_pass = (size_t)1 << 20;
     std::vector<hipEvent_t> ev_pool;
@@ -173,12 +215,19 @@ inline void copy3(float *dst, const float *src) { dst[0] = src[0]; dst[1] = src[
     catch (...) { return fail((c), NERF_ERR_INVALID, "internal error"); }
 
 // ---- nerf_context.cpp -------------------------------------------------------------------------------------------------------------
-int ensure_bytes(nerf_ctx *c, void **p, size_t *cur, size_t need);
-// the pass workspace (d_dirs .. d_rgbf) for `rays` rays of nc coarse and m fine-pass samples; d_rgbc only when need_rgbc
+// the pass workspace (BUF_DIRS .. BUF_RGBF) for `rays` rays of nc coarse and m fine-pass samples; BUF_RGBC only when need_rgbc
 int ensure_workspace(nerf_ctx *c, size_t rays, size_t nc, size_t m, bool need_rgbc);
+// A StageLayout over one buffer of the context and a stream: what a host-pointer entry point does around its launches.
+struct Staging : StageLayout {
+    nerf_ctx *c; DevBuf &buf; hipStream_t st;
+    Staging(nerf_ctx *c_, BufId id, hipStream_t st_) : c(c_), buf(c_->buf[id]), st(st_) {}
+    template <class T = float>
+    T *at(int part) const { return StageLayout::at<T>(buf.p, part); }
+    int begin();  // grows the buffer to the layout's total, then issues the uploads and the fills
+    int finish(); // issues the downloads, then the one hipStreamSynchronize
+};
 hipEvent_t get_event(nerf_ctx *c);
-// Event pairs of kind 1 (dominant MLP kernel) are owned by ctx->dominant once a render has finished; every other
-// pair is owned by ctx->last_render.
+// returns last_render's own pairs to the pool (EvPair::dominant) and forgets the rest
 void recycle_render(nerf_ctx *c);
 void recycle_dominant(nerf_ctx *c, size_t keep);
 
@@ -186,8 +235,8 @@ void recycle_dominant(nerf_ctx *c, size_t keep);
 // returned early) the destructor hands the events back to the pool.
 struct Timed {
     nerf_ctx *c; hipStream_t st; EvPair p; bool on = true;
-    Timed(nerf_ctx *c_, hipStream_t st_, int kind, uint64_t points) : c(c_), st(st_) {
-        p.kind = kind; p.points = points; p.a = get_event(c); p.b = get_event(c);
+    Timed(nerf_ctx *c_, hipStream_t st_, EvKind kind, uint64_t points) : c(c_), st(st_) {
+        p.kind = kind; p.dominant = false; p.points = points; p.a = get_event(c); p.b = get_event(c);
         if (!p.a || !p.b) on = false;
         if (on) (void)hipEventRecord(p.a, st);
     }
@@ -203,7 +252,7 @@ struct Timed {
 };
 // fn (-> int, a status) between two events of `kind` in c->last_render
 template <class F>
-int timed(nerf_ctx *c, hipStream_t st, int kind, uint64_t points, F &&fn) {
+int timed(nerf_ctx *c, hipStream_t st, EvKind kind, uint64_t points, F &&fn) {
     Timed t(c, st, kind, points);
     const int rc = fn();
     if (rc) return rc;

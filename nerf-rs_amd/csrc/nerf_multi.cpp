@@ -200,8 +200,8 @@ int render_multi(nerf_ctx *const *ctxs, int n, const nerf_camera *cam, const ner
         }
     }
 
-    // Destination buffers.  HOST: each context's d_out holds its band.  PEER: ctxs[0]'s d_out holds the frame (its own band is
-    // rendered in place), the others hold their band -- striped: ctxs[0]'s d_out = n slots + the frame.  RCCL: every d_out = n slots
+    // Destination buffers.  HOST: each context's BUF_OUT holds its band.  PEER: ctxs[0]'s BUF_OUT holds the frame (its own band is
+    // rendered in place), the others hold their band -- striped: ctxs[0]'s BUF_OUT = n slots + the frame.  RCCL: every BUF_OUT = n slots
     // (the in-place all-gather buffer), then the frame is assembled behind them when the bands are ragged or striped.
     const bool ragged = (ch % n) != 0 || stripe > 0 || np > 1; // with maps a slot is not the frame's rows: compact it as well
     std::vector<Job> jobs(n);
@@ -213,23 +213,23 @@ int render_multi(nerf_ctx *const *ctxs, int n, const nerf_camera *cam, const ner
         if (gather == NERF_GATHER_PEER && i == 0) need = stripe ? slot_floats * n + frame_floats : frame_floats;
         if (gather == NERF_GATHER_RCCL) need = slot_floats * n + (ragged ? frame_floats : 0);
         int rc;
-        if ((rc = ensure_bytes(c, (void **)&c->d_out, &c->out_floats, need * sizeof(float)))) return rc;
+        if ((rc = c->buf[BUF_OUT].ensure(c, need * sizeof(float)))) return rc;
         Job &J = jobs[i];
         J.c = c; J.o = *opts;
         J.o.crop_x0 = x0; J.o.crop_y0 = y0; J.o.crop_w = cw; J.o.crop_h = ch; // the caller's window; the band is selected by band_*
         J.o.band_index = i; J.o.band_count = n; J.o.band_stripe_rows = stripe;
         J.rows = rows;
         J.b0 = b0;                                                              // contiguous bands only
-        J.d_band = c->d_out; J.cap = rows;
+        J.d_band = c->dev(BUF_OUT); J.cap = rows;
         if (gather == NERF_GATHER_PEER && i == 0) J.cap = stripe ? max_rows : ch; // b0 == 0: the frame (contiguous) or slot 0 (striped)
-        if (gather == NERF_GATHER_RCCL) { J.d_band = c->d_out + slot_floats * i; J.cap = max_rows; }
+        if (gather == NERF_GATHER_RCCL) { J.d_band = c->dev(BUF_OUT) + slot_floats * i; J.cap = max_rows; }
         J.stats = per_ctx ? &per_ctx[i] : rgba ? &J.local : nullptr;
         if (per_ctx) memset(&per_ctx[i], 0, sizeof(nerf_stats));
     }
 
     // Fan out: one host thread per context (HIP's current device is per thread).  A thread enqueues its band's kernels on
     // its context's stream, then its share of the gather, and waits for its own stream only.
-    float *d_frame0 = c0->d_out;
+    float *d_frame0 = c0->dev(BUF_OUT);
     const int dev0 = c0->device;
     auto work_body = [&](int i) {
         Job &J = jobs[i];
@@ -324,8 +324,8 @@ int render_multi(nerf_ctx *const *ctxs, int n, const nerf_camera *cam, const ner
                 for (int k = 0; k < n && rc_first == NERF_OK; ++k) {
                     if (k == i) continue;
                     if (!note(hipStreamWaitEvent(c->stream, rendered[k], 0), "hipStreamWaitEvent")) break;
-                    const float *src = ctxs[k]->d_out + slot_floats * k;
-                    float *dst = c->d_out + slot_floats * k;
+                    const float *src = ctxs[k]->dev(BUF_OUT) + slot_floats * k;
+                    float *dst = c->dev(BUF_OUT) + slot_floats * k;
                     note(ctxs[k]->device == c->device
                              ? hipMemcpyAsync(dst, src, slot_floats * sizeof(float), hipMemcpyDeviceToDevice, c->stream)
                              : hipMemcpyPeerAsync(dst, c->device, src, ctxs[k]->device, slot_floats * sizeof(float), c->stream),
@@ -335,7 +335,7 @@ int render_multi(nerf_ctx *const *ctxs, int n, const nerf_camera *cam, const ner
         } else {
             ncclResult_t r = g_rccl.GroupStart();
             for (int i = 0; i < n && r == ncclSuccess; ++i)
-                r = g_rccl.AllGather(jobs[i].d_band, ctxs[i]->d_out, slot_floats, rgba ? ncclUint32 : ncclFloat, comms[i], ctxs[i]->stream);
+                r = g_rccl.AllGather(jobs[i].d_band, ctxs[i]->dev(BUF_OUT), slot_floats, rgba ? ncclUint32 : ncclFloat, comms[i], ctxs[i]->stream);
             const ncclResult_t r2 = g_rccl.GroupEnd();
             if (r == ncclSuccess) r = r2;
             if (r != ncclSuccess) { rc_first = NERF_ERR_HIP; err_first = std::string("ncclAllGather: ") + g_rccl.GetErrorString(r); }
@@ -343,20 +343,20 @@ int render_multi(nerf_ctx *const *ctxs, int n, const nerf_camera *cam, const ner
         for (int i = 0; i < n; ++i) {
             nerf_ctx *c = ctxs[i];
             DeviceGuard dg(c->device);
-            float *frame = c->d_out + slot_floats * n;
+            float *frame = c->dev(BUF_OUT) + slot_floats * n;
             for (int p = 0; p < np && rc_first == NERF_OK; ++p) {
                 const size_t rf = (size_t)cw * planes[p].nch;
                 if (stripe) // slots of packed rows -> frame behind them (every device ends up with the whole frame)
-                    note(launch_bands_to_frame(at(c->d_out, max_rows, p), at(frame, ch, p), cw, ch, n, stripe, slot_floats, planes[p].nch, c->stream), "bands -> frame");
+                    note(launch_bands_to_frame(at(c->dev(BUF_OUT), max_rows, p), at(frame, ch, p), cw, ch, n, stripe, slot_floats, planes[p].nch, c->stream), "bands -> frame");
                 else if (ragged) { // slots -> contiguous frame behind them (every device ends up with the whole frame)
                     for (int k = 0; k < n; ++k)
                         if (jobs[k].rows)
-                            note(hipMemcpyAsync(at(frame, ch, p) + rf * jobs[k].b0, at(c->d_out + slot_floats * k, max_rows, p), rf * jobs[k].rows * sizeof(float),
+                            note(hipMemcpyAsync(at(frame, ch, p) + rf * jobs[k].b0, at(c->dev(BUF_OUT) + slot_floats * k, max_rows, p), rf * jobs[k].rows * sizeof(float),
                                                 hipMemcpyDeviceToDevice, c->stream), "slot compaction");
                 }
             }
         }
-        d_frame0 = ragged ? c0->d_out + slot_floats * n : c0->d_out;
+        d_frame0 = ragged ? c0->dev(BUF_OUT) + slot_floats * n : c0->dev(BUF_OUT);
         if (rc_first == NERF_OK) {
             DeviceGuard dg(c0->device);
             for (int p = 0; p < np; ++p)
@@ -373,8 +373,8 @@ int render_multi(nerf_ctx *const *ctxs, int n, const nerf_camera *cam, const ner
         DeviceGuard dg(c0->device);
         if (stripe) { // every band has arrived in its slot (the threads synchronised their streams): rows -> their places
             for (int p = 0; p < np; ++p)
-                HIP_TRY(c0, launch_bands_to_frame(at(c0->d_out, max_rows, p), at(c0->d_out + slot_floats * n, ch, p), cw, ch, n, stripe, slot_floats, planes[p].nch, c0->stream));
-            d_frame0 = c0->d_out + slot_floats * n;
+                HIP_TRY(c0, launch_bands_to_frame(at(c0->dev(BUF_OUT), max_rows, p), at(c0->dev(BUF_OUT) + slot_floats * n, ch, p), cw, ch, n, stripe, slot_floats, planes[p].nch, c0->stream));
+            d_frame0 = c0->dev(BUF_OUT) + slot_floats * n;
         }
         for (int p = 0; p < np; ++p)
             HIP_TRY(c0, hipMemcpyAsync(planes[p].host, at(d_frame0, ch, p), (size_t)cw * planes[p].nch * ch * sizeof(float), hipMemcpyDeviceToHost, c0->stream));

@@ -22,6 +22,8 @@
 
 using namespace nerfint;
 
+constexpr size_t F = sizeof(float);
+
 extern "C" {
 
 static int forward_device(nerf_ctx *c, int which, int dtype, const float *d_pts, const float *d_dirs, size_t n, float *d_rgb,
@@ -60,18 +62,15 @@ int nerf_forward_batch_ex(nerf_ctx *c, int which, int dtype, const float *pts, c
     if (!pts || !dirs || !rgb || !sigma) return fail(c, NERF_ERR_INVALID, "NULL buffer");
     DeviceGuard dg(c->device);
     int rc;
-    if ((rc = ensure_bytes(c, &c->d_scratch, &c->scratch_bytes, n * 10 * sizeof(float)))) return rc;
-    float *d_pts = (float *)c->d_scratch, *d_dirs = d_pts + 3 * n, *d_rgb = d_dirs + 3 * n, *d_sig = d_rgb + 3 * n;
-    HIP_TRY(c, hipMemcpyAsync(d_pts, pts, 3 * n * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(d_dirs, dirs, 3 * n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    Staging s(c, BUF_SCRATCH, c->stream);
+    const int i_pts = s.add(F, 3 * n, pts), i_dirs = s.add(F, 3 * n, dirs), i_rgb = s.add(F, 3 * n, nullptr, rgb), i_sig = s.add(F, n, nullptr, sigma);
+    if ((rc = s.begin())) return rc;
     const bool watch = split_dtype(dtype) && c->d_nonfinite;
     if (watch) HIP_TRY(c, hipMemsetAsync(c->d_nonfinite, 0, sizeof(unsigned int), c->stream));
-    if ((rc = forward_device(c, which, dtype, d_pts, d_dirs, n, d_rgb, d_sig, c->stream))) return rc;
-    HIP_TRY(c, hipMemcpyAsync(rgb, d_rgb, 3 * n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(sigma, d_sig, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if ((rc = forward_device(c, which, dtype, s.at(i_pts), s.at(i_dirs), n, s.at(i_rgb), s.at(i_sig), c->stream))) return rc;
     unsigned int bad = 0;
     if (watch) HIP_TRY(c, hipMemcpyAsync(&bad, c->d_nonfinite, sizeof bad, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if ((rc = s.finish())) return rc;
     if (bad) {
         char msg[320];
         snprintf(msg, sizeof msg, "%u of %zu points: an operand left the range of the split arithmetic (NERF_MLP_F16X2: |activation| <= 65504) or a "
@@ -110,13 +109,11 @@ int nerf_density_batch(nerf_ctx *c, int which, const float *pts, size_t n, float
     int rc;
     if ((rc = density_batch_check(c, which, pts, sigma, n)) || n == 0) return rc;
     DeviceGuard dg(c->device);
-    if ((rc = ensure_bytes(c, &c->d_scratch, &c->scratch_bytes, n * 4 * sizeof(float)))) return rc;
-    float *d_pts = (float *)c->d_scratch, *d_sig = d_pts + 3 * n;
-    HIP_TRY(c, hipMemcpyAsync(d_pts, pts, 3 * n * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    if ((rc = density_batch_device(c, which, d_pts, n, d_sig, c->stream))) return rc;
-    HIP_TRY(c, hipMemcpyAsync(sigma, d_sig, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return NERF_OK;
+    Staging s(c, BUF_SCRATCH, c->stream);
+    const int i_pts = s.add(F, 3 * n, pts), i_sig = s.add(F, n, nullptr, sigma);
+    if ((rc = s.begin())) return rc;
+    if ((rc = density_batch_device(c, which, s.at(i_pts), n, s.at(i_sig), c->stream))) return rc;
+    return s.finish();
 } NERF_CATCH(c)
 
 // everything nerf_density_grid* can refuse without a device; *n_cells = dims[0] dims[1] dims[2]
@@ -168,13 +165,13 @@ int nerf_density_grid_device(nerf_ctx *c, int which, const float lo[3], const fl
     if ((rc = density_grid_check(c, which, lo, step, dims, d_sigma_out, threshold, d_occ_bits, n_occupied, bounds, &n_cells))) return rc;
     DeviceGuard dg(c->device);
     const bool stats = n_occupied || bounds;
-    if (stats && (rc = ensure_bytes(c, &c->d_scratch, &c->scratch_bytes, 8 * sizeof(int)))) return rc;
-    int *d_stats = stats ? (int *)c->d_scratch : nullptr;
-    if ((rc = density_grid_launch(c, which, lo, step, dims, n_cells, d_sigma_out, threshold, d_occ_bits, d_stats, (hipStream_t)stream))) return rc;
+    int h[8];
+    Staging s(c, BUF_SCRATCH, (hipStream_t)stream);
+    const int i_stats = s.opt(stats, sizeof(int), 8, nullptr, h);
+    if ((rc = s.begin())) return rc;
+    if ((rc = density_grid_launch(c, which, lo, step, dims, n_cells, d_sigma_out, threshold, d_occ_bits, s.at<int>(i_stats), s.st))) return rc;
     if (stats) {
-        int h[8];
-        HIP_TRY(c, hipMemcpyAsync(h, d_stats, sizeof h, hipMemcpyDeviceToHost, (hipStream_t)stream));
-        HIP_TRY(c, hipStreamSynchronize((hipStream_t)stream));
+        if ((rc = s.finish())) return rc;
         density_grid_stats_out(h, n_occupied, bounds);
     }
     return NERF_OK;
@@ -188,18 +185,13 @@ int nerf_density_grid(nerf_ctx *c, int which, const float lo[3], const float ste
     DeviceGuard dg(c->device);
     // staging: [8 ints of statistics][occupancy words][sigma], each only if asked for
     const bool stats = n_occupied || bounds;
-    const size_t n_words = occ_bits ? (n_cells + 31) / 32 : 0;
-    const size_t bytes = 8 * sizeof(int) + n_words * sizeof(uint32_t) + (sigma_out ? n_cells * sizeof(float) : 0);
-    if ((rc = ensure_bytes(c, &c->d_scratch, &c->scratch_bytes, bytes))) return rc;
-    int *d_stats = (int *)c->d_scratch;
-    uint32_t *d_bits = occ_bits ? (uint32_t *)(d_stats + 8) : nullptr;
-    float *d_sigma = sigma_out ? (float *)(d_stats + 8) + n_words : nullptr;
-    if ((rc = density_grid_launch(c, which, lo, step, dims, n_cells, d_sigma, threshold, d_bits, stats ? d_stats : nullptr, c->stream))) return rc;
     int h[8];
-    if (sigma_out) HIP_TRY(c, hipMemcpyAsync(sigma_out, d_sigma, n_cells * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (occ_bits) HIP_TRY(c, hipMemcpyAsync(occ_bits, d_bits, n_words * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    if (stats) HIP_TRY(c, hipMemcpyAsync(h, d_stats, sizeof h, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    Staging s(c, BUF_SCRATCH, c->stream);
+    const int i_stats = s.opt(stats, sizeof(int), 8, nullptr, h), i_bits = s.opt(occ_bits, sizeof(uint32_t), (n_cells + 31) / 32, nullptr, occ_bits),
+              i_sigma = s.opt(sigma_out, F, n_cells, nullptr, sigma_out);
+    if ((rc = s.begin())) return rc;
+    if ((rc = density_grid_launch(c, which, lo, step, dims, n_cells, s.at(i_sigma), threshold, s.at<uint32_t>(i_bits), s.at<int>(i_stats), c->stream))) return rc;
+    if ((rc = s.finish())) return rc;
     if (stats) density_grid_stats_out(h, n_occupied, bounds);
     return NERF_OK;
 } NERF_CATCH(c)
@@ -221,7 +213,7 @@ static int dilate_check(nerf_ctx *c, const uint32_t *in, const int32_t *dims, in
     return NERF_OK;
 }
 
-// the dilation and, when asked for, the statistics of its output (through c->d_scratch: 8 ints); arguments already checked
+// the dilation and, when asked for, the statistics of its output (d_stats: 8 ints on the device); arguments already checked
 static int dilate_device(nerf_ctx *c, const uint32_t *d_in, const int32_t *dims, int radius, uint32_t *d_out, size_t n_cells, int *d_stats,
                          uint64_t *n_occupied, int32_t *bounds, hipStream_t st) {
     HIP_TRY(c, launch_occupancy_dilate(d_in, d_out, dims[0], dims[1], dims[2], radius, st));
@@ -241,8 +233,8 @@ int nerf_occupancy_dilate_device(nerf_ctx *c, const uint32_t *d_occ_bits, const 
     if ((rc = dilate_check(c, d_occ_bits, dims, radius, d_occ_out, &n_cells))) return rc;
     DeviceGuard dg(c->device);
     const bool stats = n_occupied || bounds;
-    if (stats && (rc = ensure_bytes(c, &c->d_scratch, &c->scratch_bytes, 8 * sizeof(int)))) return rc;
-    return dilate_device(c, d_occ_bits, dims, radius, d_occ_out, n_cells, stats ? (int *)c->d_scratch : nullptr, n_occupied, bounds, (hipStream_t)stream);
+    if (stats && (rc = c->buf[BUF_SCRATCH].ensure(c, 8 * sizeof(int)))) return rc;
+    return dilate_device(c, d_occ_bits, dims, radius, d_occ_out, n_cells, stats ? c->dev<int>(BUF_SCRATCH) : nullptr, n_occupied, bounds, (hipStream_t)stream);
 } NERF_CATCH(c)
 
 int nerf_occupancy_dilate(nerf_ctx *c, const uint32_t *occ_bits, const int32_t dims[3], int radius, uint32_t *occ_out, uint64_t *n_occupied,
@@ -253,14 +245,12 @@ int nerf_occupancy_dilate(nerf_ctx *c, const uint32_t *occ_bits, const int32_t d
     DeviceGuard dg(c->device);
     // staging: [8 ints of statistics][input words][output words]
     const size_t n_words = (n_cells + 31) / 32;
-    if ((rc = ensure_bytes(c, &c->d_scratch, &c->scratch_bytes, 8 * sizeof(int) + 2 * n_words * sizeof(uint32_t)))) return rc;
-    int *d_stats = (int *)c->d_scratch;
-    uint32_t *d_in = (uint32_t *)(d_stats + 8), *d_out = d_in + n_words;
-    HIP_TRY(c, hipMemcpyAsync(d_in, occ_bits, n_words * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    if ((rc = dilate_device(c, d_in, dims, radius, d_out, n_cells, (n_occupied || bounds) ? d_stats : nullptr, n_occupied, bounds, c->stream))) return rc;
-    HIP_TRY(c, hipMemcpyAsync(occ_out, d_out, n_words * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return NERF_OK;
+    Staging s(c, BUF_SCRATCH, c->stream);
+    const int i_stats = s.opt(n_occupied || bounds, sizeof(int), 8), i_in = s.add(sizeof(uint32_t), n_words, occ_bits),
+              i_out = s.add(sizeof(uint32_t), n_words, nullptr, occ_out);
+    if ((rc = s.begin())) return rc;
+    if ((rc = dilate_device(c, s.at<uint32_t>(i_in), dims, radius, s.at<uint32_t>(i_out), n_cells, s.at<int>(i_stats), n_occupied, bounds, c->stream))) return rc;
+    return s.finish();
 } NERF_CATCH(c)
 
 // everything nerf_clip_rays* can refuse without a device
@@ -273,7 +263,7 @@ static int clip_check(nerf_ctx *c, const void *occ_bits, const float *lo, const 
     return NERF_OK;
 }
 
-// the clip launch on device pointers; with n_hit the block sums go through c->d_clip and the total comes back (one synchronisation)
+// the clip launch on device pointers; with n_hit the block sums go through BUF_CLIP and the total comes back (one synchronisation)
 static int clip_device(nerf_ctx *c, const uint32_t *d_bits, const float *lo, const float *step, const int32_t *dims, const float *d_origins,
                        size_t n_origins, const float *d_dirs, size_t n_rays, int normalize, float near_, float far_, const float *d_bounds,
                        float *d_bounds_out, uint8_t *d_hit_out, uint64_t *n_hit, hipStream_t st) {
@@ -286,8 +276,8 @@ static int clip_device(nerf_ctx *c, const uint32_t *d_bits, const float *lo, con
     if (n_hit) {
         const size_t n_blocks = (n_rays + kClipBlock - 1) / kClipBlock;
         int rc;
-        if ((rc = ensure_bytes(c, &c->d_clip, &c->clip_bytes, (n_blocks + 2) * sizeof(uint32_t)))) return rc;
-        d_totals = (uint32_t *)c->d_clip;
+        if ((rc = c->buf[BUF_CLIP].ensure(c, (n_blocks + 2) * sizeof(uint32_t)))) return rc;
+        d_totals = c->dev<uint32_t>(BUF_CLIP);
         a.bsum = d_totals + 2;
     }
     HIP_TRY(c, launch_clip_rays(a, st));
@@ -321,22 +311,15 @@ int nerf_clip_rays(nerf_ctx *c, const uint32_t *occ_bits, const float lo[3], con
     if (n_hit) *n_hit = 0;
     if (n_rays == 0) return NERF_OK;
     DeviceGuard dg(c->device);
-    // staging (words): occupancy, dirs, origins, [bounds], bounds_out, hit flags
-    const size_t R = n_rays, n_words = ((size_t)dims[0] * dims[1] * dims[2] + 31) / 32, n_o = n_origins == 1 ? 1 : R;
-    const size_t o_g = 0, o_d = o_g + n_words, o_o = o_d + 3 * R, o_b = o_o + 3 * n_o, o_c = o_b + (bounds ? 2 * R : 0), o_h = o_c + 2 * R,
-                 total = o_h + (R + 3) / 4;
-    if ((rc = ensure_bytes(c, &c->d_scratch, &c->scratch_bytes, total * 4))) return rc;
-    uint32_t *d = (uint32_t *)c->d_scratch;
-    HIP_TRY(c, hipMemcpyAsync(d + o_g, occ_bits, n_words * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(d + o_d, dirs, 3 * R * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(d + o_o, origins, 3 * n_o * 4, hipMemcpyHostToDevice, c->stream));
-    if (bounds) HIP_TRY(c, hipMemcpyAsync(d + o_b, bounds, 2 * R * 4, hipMemcpyHostToDevice, c->stream));
-    if ((rc = clip_device(c, d + o_g, lo, step, dims, (const float *)(d + o_o), n_origins, (const float *)(d + o_d), R, normalize, near_, far_,
-                          bounds ? (const float *)(d + o_b) : nullptr, (float *)(d + o_c), (uint8_t *)(d + o_h), n_hit, c->stream))) return rc;
-    HIP_TRY(c, hipMemcpyAsync(bounds_out, d + o_c, 2 * R * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(hit_out, d + o_h, R, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return NERF_OK;
+    // staging: occupancy, dirs, origins, [bounds], bounds_out, hit flags
+    const size_t R = n_rays, n_words = ((size_t)dims[0] * dims[1] * dims[2] + 31) / 32;
+    Staging s(c, BUF_SCRATCH, c->stream);
+    const int i_occ = s.add(sizeof(uint32_t), n_words, occ_bits), i_dirs = s.add(F, 3 * R, dirs), i_origins = s.add(F, 3 * n_origins, origins),
+              i_bounds = s.opt(bounds, F, 2 * R, bounds), i_out = s.add(F, 2 * R, nullptr, bounds_out), i_hit = s.add(1, R, nullptr, hit_out);
+    if ((rc = s.begin())) return rc;
+    if ((rc = clip_device(c, s.at<uint32_t>(i_occ), lo, step, dims, s.at(i_origins), n_origins, s.at(i_dirs), R, normalize, near_, far_, s.at(i_bounds),
+                          s.at(i_out), s.at<uint8_t>(i_hit), n_hit, c->stream))) return rc;
+    return s.finish();
 } NERF_CATCH(c)
 
 // ---- isosurface meshes (isosurface_kernels.hip): marching tetrahedra on a sigma lattice -------------------------------------------------
@@ -402,27 +385,18 @@ static int mesh_extract(nerf_ctx *c, int colour_net, const MeshLattice &g, const
     const size_t nv = totals[0], nt = totals[1];
     *n_vertices = nv; *n_triangles = nt;
     if (!(o.vertices || o.normals || o.rgb || o.triangles) || nv > o.cap_vertices || nt > o.cap_triangles || nv == 0) return NERF_OK;
-    // staging in the scratch, in 256-byte slots: what the caller cannot receive directly, and the inputs / sigma output of the colour launch
-    size_t words = 0;
-    auto slot = [&](bool wanted, size_t n) { const size_t at = words; if (wanted) words += (n + 63) / 64 * 64; return at; };
-    const size_t v_at = slot(host_out && o.vertices, 3 * nv), n_at = slot(host_out && o.normals, 3 * nv), c_at = slot(host_out && o.rgb, 3 * nv),
-                 t_at = slot(host_out && o.triangles, 3 * nt), soa_at = slot(o.rgb, 3 * nv), dir_at = slot(o.rgb, 3 * nv), sig_at = slot(o.rgb, nv);
+    // staging in the scratch: what the caller cannot receive directly, and the inputs / sigma output of the colour launch
+    Staging s(c, BUF_SCRATCH, st);
+    const int i_v = s.opt(host_out && o.vertices, F, 3 * nv, nullptr, o.vertices), i_n = s.opt(host_out && o.normals, F, 3 * nv, nullptr, o.normals),
+              i_c = s.opt(host_out && o.rgb, F, 3 * nv, nullptr, o.rgb), i_t = s.opt(host_out && o.triangles, sizeof(uint32_t), 3 * nt, nullptr, o.triangles),
+              i_soa = s.opt(o.rgb, F, 3 * nv), i_dir = s.opt(o.rgb, F, 3 * nv), i_sig = s.opt(o.rgb, F, nv);
     int rc;
-    if (words && (rc = ensure_bytes(c, &c->d_scratch, &c->scratch_bytes, words * sizeof(float)))) return rc;
-    float *s = (float *)c->d_scratch;
-    float *d_v = !o.vertices ? nullptr : host_out ? s + v_at : o.vertices, *d_n = !o.normals ? nullptr : host_out ? s + n_at : o.normals;
-    float *d_c = !o.rgb ? nullptr : host_out ? s + c_at : o.rgb;
-    uint32_t *d_t = !o.triangles ? nullptr : host_out ? (uint32_t *)(s + t_at) : o.triangles;
-    HIP_TRY(c, launch_mesh_emit(g, w, (uint32_t)nv, d_v, d_n, o.rgb ? s + soa_at : nullptr, o.rgb ? s + dir_at : nullptr, (uint32_t)nt, d_t, st));
-    if (o.rgb && (rc = forward_device(c, colour_net, NERF_MLP_F32, s + soa_at, s + dir_at, nv, d_c, s + sig_at, st))) return rc;
-    if (host_out) {
-        if (o.vertices) HIP_TRY(c, hipMemcpyAsync(o.vertices, d_v, 3 * nv * sizeof(float), hipMemcpyDeviceToHost, st));
-        if (o.normals) HIP_TRY(c, hipMemcpyAsync(o.normals, d_n, 3 * nv * sizeof(float), hipMemcpyDeviceToHost, st));
-        if (o.rgb) HIP_TRY(c, hipMemcpyAsync(o.rgb, d_c, 3 * nv * sizeof(float), hipMemcpyDeviceToHost, st));
-        if (o.triangles && nt) HIP_TRY(c, hipMemcpyAsync(o.triangles, d_t, 3 * nt * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        HIP_TRY(c, hipStreamSynchronize(st));
-    }
-    return NERF_OK;
+    if ((rc = s.begin())) return rc;
+    float *d_v = host_out ? s.at(i_v) : o.vertices, *d_n = host_out ? s.at(i_n) : o.normals, *d_c = host_out ? s.at(i_c) : o.rgb;
+    uint32_t *d_t = host_out ? s.at<uint32_t>(i_t) : o.triangles;
+    HIP_TRY(c, launch_mesh_emit(g, w, (uint32_t)nv, d_v, d_n, s.at(i_soa), s.at(i_dir), (uint32_t)nt, d_t, st));
+    if (o.rgb && (rc = forward_device(c, colour_net, NERF_MLP_F32, s.at(i_soa), s.at(i_dir), nv, d_c, s.at(i_sig), st))) return rc;
+    return host_out ? s.finish() : NERF_OK;
 }
 
 // ---- lattice components (components_kernels.hip) -----------------------------------------------------------------------------------------------
@@ -436,9 +410,9 @@ static int filter_check(nerf_ctx *c, const nerf_component_filter *f) {
 static int components_launch(nerf_ctx *c, const float *d_sigma, const int32_t *dims, float iso, size_t n, uint32_t keep_largest, uint32_t min_points,
                              uint32_t cap_table, CompWorkspace *out, hipStream_t st) {
     int rc;
-    if ((rc = ensure_bytes(c, &c->d_comp, &c->comp_bytes, comp_workspace_bytes(n)))) return rc;
-    const MeshWorkspace mw = mesh_workspace_carve(c->d_mesh, n);
-    *out = comp_workspace_carve(c->d_comp, n, mw.vbase, mw.tbase);
+    if ((rc = c->buf[BUF_COMP].ensure(c, comp_workspace_bytes(n)))) return rc;
+    const MeshWorkspace mw = mesh_workspace_carve(c->buf[BUF_MESH].p, n);
+    *out = comp_workspace_carve(c->buf[BUF_COMP].p, n, mw.vbase, mw.tbase);
     HIP_TRY(c, launch_components(d_sigma, dims[0], dims[1], dims[2], iso, *out, keep_largest, min_points, cap_table, st));
     return NERF_OK;
 }
@@ -462,8 +436,8 @@ int nerf_isosurface_grid_filtered(nerf_ctx *c, const float *sigma, const float l
     if ((rc = filter_check(c, (const nerf_component_filter *)filter))) return rc;
     if ((rc = mesh_check(c, false, 0, sigma, lo, step, dims, iso, n_vertices, n_triangles, &n))) return rc;
     DeviceGuard dg(c->device);
-    if ((rc = ensure_bytes(c, &c->d_mesh, &c->mesh_bytes, mesh_workspace_bytes(n)))) return rc;
-    const MeshWorkspace w = mesh_workspace_carve(c->d_mesh, n);
+    if ((rc = c->buf[BUF_MESH].ensure(c, mesh_workspace_bytes(n)))) return rc;
+    const MeshWorkspace w = mesh_workspace_carve(c->buf[BUF_MESH].p, n);
     HIP_TRY(c, hipMemcpyAsync(w.sigma, sigma, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
     MeshComponents mc{};
     bool use = false;
@@ -524,8 +498,8 @@ int nerf_lattice_components(nerf_ctx *c, const float *sigma, const int32_t dims[
     int rc;
     if ((rc = components_check(c, sigma, dims, iso, table, cap_table, n_components, &n))) return rc;
     DeviceGuard dg(c->device);
-    if ((rc = ensure_bytes(c, &c->d_mesh, &c->mesh_bytes, mesh_workspace_bytes(n)))) return rc;
-    const MeshWorkspace mw = mesh_workspace_carve(c->d_mesh, n);
+    if ((rc = c->buf[BUF_MESH].ensure(c, mesh_workspace_bytes(n)))) return rc;
+    const MeshWorkspace mw = mesh_workspace_carve(c->buf[BUF_MESH].p, n);
     HIP_TRY(c, hipMemcpyAsync(mw.sigma, sigma, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
     return lattice_components(c, mw.sigma, dims, iso, n, labels_out, true, (nerf_component *)table, cap_table, n_components, c->stream);
 } NERF_CATCH(c)
@@ -536,7 +510,7 @@ int nerf_lattice_components_device(nerf_ctx *c, const float *d_sigma, const int3
     int rc;
     if ((rc = components_check(c, d_sigma, dims, iso, table, cap_table, n_components, &n))) return rc;
     DeviceGuard dg(c->device);
-    if ((rc = ensure_bytes(c, &c->d_mesh, &c->mesh_bytes, mesh_workspace_bytes(n)))) return rc;
+    if ((rc = c->buf[BUF_MESH].ensure(c, mesh_workspace_bytes(n)))) return rc;
     return lattice_components(c, d_sigma, dims, iso, n, d_labels_out, false, (nerf_component *)table, cap_table, n_components, (hipStream_t)stream);
 } NERF_CATCH(c)
 
@@ -549,8 +523,8 @@ static int extract_mesh(nerf_ctx *c, int which, const float *lo, const float *st
     if ((rc = filter_check(c, filter))) return rc;
     if ((rc = mesh_check(c, true, which, nullptr, lo, step, dims, iso, n_vertices, n_triangles, &n))) return rc;
     DeviceGuard dg(c->device);
-    if ((rc = ensure_bytes(c, &c->d_mesh, &c->mesh_bytes, mesh_workspace_bytes(n)))) return rc;
-    const MeshWorkspace w = mesh_workspace_carve(c->d_mesh, n);
+    if ((rc = c->buf[BUF_MESH].ensure(c, mesh_workspace_bytes(n)))) return rc;
+    const MeshWorkspace w = mesh_workspace_carve(c->buf[BUF_MESH].p, n);
     if ((rc = density_grid_launch(c, which, lo, step, dims, n, w.sigma, 0.0f, nullptr, nullptr, st))) return rc;
     MeshComponents mc{};
     bool use = false;
@@ -608,10 +582,10 @@ static int density_gradient_device(nerf_ctx *c, int which, const float *d_pts, s
     if ((rc = density_gradient_check(c, which, d_pts, n, h, d_grad)) || n == 0) return rc;
     DeviceGuard dg(c->device);
     const size_t chunk = std::max<size_t>(1, std::min({c->gradient_chunk, n, max_batch_points(c->n_cus) / 6}));
-    if ((rc = ensure_bytes(c, &c->d_stencil, &c->stencil_bytes, 6 * chunk * 4 * sizeof(float)))) return rc;
+    if ((rc = c->buf[BUF_STENCIL].ensure(c, 6 * chunk * 4 * sizeof(float)))) return rc;
     for (size_t i0 = 0; i0 < n; i0 += chunk) {
         const size_t m = std::min(chunk, n - i0);
-        float *d_spts = (float *)c->d_stencil, *d_ssig = d_spts + 18 * m;
+        float *d_spts = c->dev(BUF_STENCIL), *d_ssig = d_spts + 18 * m;
         NormalStencilArgs sa{};
         sa.n_live = (uint32_t)m; sa.h = h; sa.src = d_pts + i0; sa.src_stride = n; sa.pts = d_spts;
         HIP_TRY(c, launch_normal_stencil(sa, st));
@@ -630,13 +604,11 @@ int nerf_density_gradient_batch(nerf_ctx *c, int which, const float *pts, size_t
     int rc;
     if ((rc = density_gradient_check(c, which, pts, n, h, grad)) || n == 0) return rc;
     DeviceGuard dg(c->device);
-    if ((rc = ensure_bytes(c, &c->d_scratch, &c->scratch_bytes, n * 6 * sizeof(float)))) return rc;
-    float *d_pts = (float *)c->d_scratch, *d_grad = d_pts + 3 * n;
-    HIP_TRY(c, hipMemcpyAsync(d_pts, pts, 3 * n * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    if ((rc = density_gradient_device(c, which, d_pts, n, h, d_grad, c->stream))) return rc;
-    HIP_TRY(c, hipMemcpyAsync(grad, d_grad, 3 * n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return NERF_OK;
+    Staging s(c, BUF_SCRATCH, c->stream);
+    const int i_pts = s.add(F, 3 * n, pts), i_grad = s.add(F, 3 * n, nullptr, grad);
+    if ((rc = s.begin())) return rc;
+    if ((rc = density_gradient_device(c, which, s.at(i_pts), n, h, s.at(i_grad), c->stream))) return rc;
+    return s.finish();
 } NERF_CATCH(c)
 
 // ---- stage entry points ------------------------------------------------------------------------------------
@@ -656,12 +628,11 @@ int nerf_stage_ray_dirs(nerf_ctx *c, const nerf_camera *cam, int x0, int y0, int
     RayGenArgs g; int rc;
     if ((rc = stage_rect(c, cam, x0, y0, w, h, g))) return rc;
     g.normalize = normalize ? 1 : 0;
-    const size_t bytes = (size_t)g.n_rays * 3 * sizeof(float);
-    if ((rc = ensure_bytes(c, &c->d_scratch, &c->scratch_bytes, bytes))) return rc;
-    HIP_TRY(c, launch_ray_dirs(g, (float *)c->d_scratch, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(out, c->d_scratch, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return NERF_OK;
+    Staging s(c, BUF_SCRATCH, c->stream);
+    const int i_out = s.add(F, (size_t)g.n_rays * 3, nullptr, out);
+    if ((rc = s.begin())) return rc;
+    HIP_TRY(c, launch_ray_dirs(g, s.at(i_out), c->stream));
+    return s.finish();
 } NERF_CATCH(c)
 
 int nerf_stage_stratified(nerf_ctx *c, const nerf_camera *cam, int x0, int y0, int w, int h, int count, uint64_t seed, float *out) try {
@@ -671,12 +642,11 @@ int nerf_stage_stratified(nerf_ctx *c, const nerf_camera *cam, int x0, int y0, i
     DeviceGuard dg(c->device);
     RayGenArgs g; int rc;
     if ((rc = stage_rect(c, cam, x0, y0, w, h, g))) return rc;
-    const size_t bytes = (size_t)g.n_rays * count * sizeof(float);
-    if ((rc = ensure_bytes(c, &c->d_scratch, &c->scratch_bytes, bytes))) return rc;
-    HIP_TRY(c, launch_stratified(g, count, cam->near_, cam->far_, seed, (float *)c->d_scratch, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(out, c->d_scratch, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return NERF_OK;
+    Staging s(c, BUF_SCRATCH, c->stream);
+    const int i_out = s.add(F, (size_t)g.n_rays * count, nullptr, out);
+    if ((rc = s.begin())) return rc;
+    HIP_TRY(c, launch_stratified(g, count, cam->near_, cam->far_, seed, s.at(i_out), c->stream));
+    return s.finish();
 } NERF_CATCH(c)
 
 static int stage_resample(nerf_ctx *c, size_t n_rays, int nc, int nf, float far_, uint64_t seed, const uint32_t *pixel_index,
@@ -690,33 +660,22 @@ static int stage_resample(nerf_ctx *c, size_t n_rays, int nc, int nf, float far_
     if (resample_lds_bytes(nc, nf) > 160 * 1024 || n_rays > 0x7fffffff / (size_t)(nc + nf)) return fail(c, NERF_ERR_INVALID, "too many samples");
     DeviceGuard dg(c->device);
     const size_t R = n_rays, M = (size_t)nc + nf;
-    // layout in scratch (floats): tc, sc, u, w, cdf, tnew, tfine, pix
-    const size_t o_tc = 0, o_sc = o_tc + R * nc, o_u = o_sc + R * nc, o_w = o_u + R * nf, o_cdf = o_w + R * nc,
-                 o_tn = o_cdf + R * (nc - 1), o_tf = o_tn + R * nf, o_px = o_tf + R * M, o_fl = o_px + R, total = o_fl + (R + 3) / 4;
+    Staging s(c, BUF_SCRATCH, c->stream);
+    const int i_tc = s.add(F, R * nc, t_coarse), i_sc = s.add(F, R * nc, sigma_coarse), i_u = s.opt(u, F, R * nf, u), i_w = s.add(F, R * nc, nullptr, w_out),
+              i_cdf = s.add(F, R * (nc - 1), nullptr, cdf_out), i_tn = s.add(F, R * nf, nullptr, t_new_out), i_tf = s.add(F, R * M, nullptr, t_fine_out),
+              i_px = s.opt(pixel_index, sizeof(uint32_t), R, pixel_index), i_fl = s.opt(flags_out, 1, R, nullptr, flags_out);
     int rc;
-    if ((rc = ensure_bytes(c, &c->d_scratch, &c->scratch_bytes, total * sizeof(float)))) return rc;
-    float *d = (float *)c->d_scratch;
-    HIP_TRY(c, hipMemcpyAsync(d + o_tc, t_coarse, R * nc * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(d + o_sc, sigma_coarse, R * nc * 4, hipMemcpyHostToDevice, c->stream));
-    if (u) HIP_TRY(c, hipMemcpyAsync(d + o_u, u, R * nf * 4, hipMemcpyHostToDevice, c->stream));
-    if (pixel_index) HIP_TRY(c, hipMemcpyAsync(d + o_px, pixel_index, R * 4, hipMemcpyHostToDevice, c->stream));
+    if ((rc = s.begin())) return rc;
     ResampleArgs ra{};
     ra.n_rays = (int)R; ra.nc = nc; ra.nf = nf; ra.far_ = far_;
     ra.seed_lo = (uint32_t)seed; ra.seed_hi = (uint32_t)(seed >> 32);
-    ra.t_coarse = d + o_tc; ra.sigma_coarse = d + o_sc; ra.t_fine = d + o_tf;
-    ra.pixel_index = pixel_index ? (const uint32_t *)(d + o_px) : nullptr;
-    ra.u_in = u ? d + o_u : nullptr;
-    ra.w_out = d + o_w; ra.cdf_out = d + o_cdf; ra.t_new_out = d + o_tn;
+    ra.t_coarse = s.at(i_tc); ra.sigma_coarse = s.at(i_sc); ra.t_fine = s.at(i_tf);
+    ra.pixel_index = s.at<uint32_t>(i_px); ra.u_in = s.at(i_u);
+    ra.w_out = s.at(i_w); ra.cdf_out = s.at(i_cdf); ra.t_new_out = s.at(i_tn);
     ra.g.rw = 1; ra.g.rnx = 1; // unused when pixel_index/u are given
-    if (flags_out) { ra.flag_tau = tau; ra.flag_out = (unsigned char *)(d + o_fl); }
+    if (flags_out) { ra.flag_tau = tau; ra.flag_out = s.at<unsigned char>(i_fl); }
     HIP_TRY(c, launch_resample(ra, c->stream));
-    if (flags_out) HIP_TRY(c, hipMemcpyAsync(flags_out, d + o_fl, R, hipMemcpyDeviceToHost, c->stream));
-    if (w_out) HIP_TRY(c, hipMemcpyAsync(w_out, d + o_w, R * nc * 4, hipMemcpyDeviceToHost, c->stream));
-    if (cdf_out) HIP_TRY(c, hipMemcpyAsync(cdf_out, d + o_cdf, R * (nc - 1) * 4, hipMemcpyDeviceToHost, c->stream));
-    if (t_new_out) HIP_TRY(c, hipMemcpyAsync(t_new_out, d + o_tn, R * nf * 4, hipMemcpyDeviceToHost, c->stream));
-    if (t_fine_out) HIP_TRY(c, hipMemcpyAsync(t_fine_out, d + o_tf, R * M * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return NERF_OK;
+    return s.finish();
 }
 
 int nerf_stage_resample(nerf_ctx *c, size_t n_rays, int nc, int nf, float far_, uint64_t seed, const uint32_t *pixel_index,
@@ -745,16 +704,13 @@ int nerf_stage_depth_order(nerf_ctx *c, int rows, int rays_per_row, int samples_
     if (d.tiles == 0) return fail(c, NERF_ERR_INVALID, "this window is not depth-ordered: rays_per_row % 8 == 0, rows >= 4, samples_per_ray % 32 == 0 and <= 512");
     DeviceGuard dg(c->device);
     int rc;
-    if ((rc = ensure_bytes(c, &c->d_scratch, &c->scratch_bytes, ((size_t)n + d.points) * 4))) return rc;
-    float *d_t = (float *)c->d_scratch;
-    unsigned int *d_table = (unsigned int *)(d_t + n);
-    HIP_TRY(c, hipMemcpyAsync(d_t, t, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    Staging s(c, BUF_SCRATCH, c->stream);
+    const int i_t = s.add(F, (size_t)n, t), i_table = s.add(sizeof(uint32_t), (size_t)d.points, nullptr, table_out);
+    if ((rc = s.begin())) return rc;
     DepthOrderArgs q{};
-    q.t = d_t; q.rw = rays_per_row; q.spr = samples_per_ray; q.blocks_x = d.blocks_x; q.blocks = d.blocks; q.table = d_table;
+    q.t = s.at(i_t); q.rw = rays_per_row; q.spr = samples_per_ray; q.blocks_x = d.blocks_x; q.blocks = d.blocks; q.table = s.at<unsigned int>(i_table);
     HIP_TRY(c, launch_depth_order(q, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(table_out, d_table, (size_t)d.points * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return NERF_OK;
+    return s.finish();
 } NERF_CATCH(c)
 
 int nerf_stage_integrate(nerf_ctx *c, size_t n_rays, int n, float far_, const float *rgb, const float *sigma, const float *t,
@@ -767,20 +723,15 @@ int nerf_stage_integrate(nerf_ctx *c, size_t n_rays, int n, float far_, const fl
     if (composite_lds_bytes(n) > 160 * 1024 || n_rays > 0x7fffffff / (size_t)n) return fail(c, NERF_ERR_INVALID, "too many samples");
     DeviceGuard dg(c->device);
     const size_t R = n_rays, N = (size_t)n;
-    const size_t o_t = 0, o_s = o_t + R * N, o_c = o_s + R * N, o_w = o_c + 3 * R * N, o_o = o_w + R * N, total = o_o + 3 * R;
+    Staging s(c, BUF_SCRATCH, c->stream);
+    const int i_t = s.add(F, R * N, t), i_s = s.add(F, R * N, sigma), i_c = s.add(F, 3 * R * N, rgb), i_w = s.add(F, R * N, nullptr, w_out),
+              i_o = s.add(F, 3 * R, nullptr, rgb_out);
     int rc;
-    if ((rc = ensure_bytes(c, &c->d_scratch, &c->scratch_bytes, total * sizeof(float)))) return rc;
-    float *d = (float *)c->d_scratch;
-    HIP_TRY(c, hipMemcpyAsync(d + o_t, t, R * N * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(d + o_s, sigma, R * N * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(d + o_c, rgb, 3 * R * N * 4, hipMemcpyHostToDevice, c->stream));
+    if ((rc = s.begin())) return rc;
     CompositeArgs ca{};
-    ca.n_rays = (int)R; ca.n = n; ca.far_ = far_; ca.t = d + o_t; ca.sigma = d + o_s; ca.rgb = d + o_c; ca.out = d + o_o; ca.w_out = d + o_w;
+    ca.n_rays = (int)R; ca.n = n; ca.far_ = far_; ca.t = s.at(i_t); ca.sigma = s.at(i_s); ca.rgb = s.at(i_c); ca.out = s.at(i_o); ca.w_out = s.at(i_w);
     HIP_TRY(c, launch_composite(ca, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(rgb_out, d + o_o, 3 * R * 4, hipMemcpyDeviceToHost, c->stream));
-    if (w_out) HIP_TRY(c, hipMemcpyAsync(w_out, d + o_w, R * N * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return NERF_OK;
+    return s.finish();
 } NERF_CATCH(c)
 
 int nerf_stage_integrate_rgba8(nerf_ctx *c, size_t n_rays, int n, float far_, const float *rgb, const float *sigma, const float *t,
@@ -794,22 +745,17 @@ int nerf_stage_integrate_rgba8(nerf_ctx *c, size_t n_rays, int n, float far_, co
     if (composite_lds_bytes(n) > 160 * 1024 || n_rays > 0x7fffffff / (size_t)n) return fail(c, NERF_ERR_INVALID, "too many samples");
     DeviceGuard dg(c->device);
     const size_t R = n_rays, N = (size_t)n;
-    // scratch (floats): t, sigma, rgb, per-ray colour, per-ray opacity, packed words
-    const size_t o_t = 0, o_s = o_t + R * N, o_c = o_s + R * N, o_o = o_c + 3 * R * N, o_a = o_o + 3 * R, o_p = o_a + R, total = o_p + R;
-    if ((rc = ensure_bytes(c, &c->d_scratch, &c->scratch_bytes, total * sizeof(float)))) return rc;
-    float *d = (float *)c->d_scratch;
-    HIP_TRY(c, hipMemcpyAsync(d + o_t, t, R * N * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(d + o_s, sigma, R * N * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(d + o_c, rgb, 3 * R * N * 4, hipMemcpyHostToDevice, c->stream));
+    // per-ray colour, [per-ray opacity] and the packed words behind the inputs
+    Staging s(c, BUF_SCRATCH, c->stream);
+    const int i_t = s.add(F, R * N, t), i_s = s.add(F, R * N, sigma), i_c = s.add(F, 3 * R * N, rgb), i_o = s.add(F, 3 * R),
+              i_a = s.opt(alpha_mode != NERF_ALPHA_OPAQUE, F, R), i_p = s.add(4, R, nullptr, rgba_out);
+    if ((rc = s.begin())) return rc;
     CompositeArgs ca{};
-    ca.n_rays = (int)R; ca.n = n; ca.far_ = far_; ca.t = d + o_t; ca.sigma = d + o_s; ca.rgb = d + o_c; ca.out = d + o_o;
-    ca.opacity = alpha_mode == NERF_ALPHA_OPAQUE ? nullptr : d + o_a;
+    ca.n_rays = (int)R; ca.n = n; ca.far_ = far_; ca.t = s.at(i_t); ca.sigma = s.at(i_s); ca.rgb = s.at(i_c); ca.out = s.at(i_o); ca.opacity = s.at(i_a);
     if (bg) { ca.use_bg = 1; ca.bg[0] = bg[0]; ca.bg[1] = bg[1]; ca.bg[2] = bg[2]; }
     HIP_TRY(c, launch_composite(ca, c->stream));
-    HIP_TRY(c, launch_pack_rgba8(ca.out, ca.opacity, (uint32_t *)(d + o_p), R, alpha_mode, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(rgba_out, d + o_p, R * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return NERF_OK;
+    HIP_TRY(c, launch_pack_rgba8(ca.out, ca.opacity, s.at<uint32_t>(i_p), R, alpha_mode, c->stream));
+    return s.finish();
 } NERF_CATCH(c)
 
 // ---- certify_zero's device pieces on caller data (cert_pass's launches, one at a time) ---------------------------------------------
@@ -851,29 +797,20 @@ int nerf_stage_cert_plan(nerf_ctx *c, size_t n_rays, int spr, float far_, float 
     memset(aux_out, 0xFF, n_aux * 4);
     if (n_rays == 0) return NERF_OK;
     DeviceGuard dg(c->device);
-    // scratch (words): pre, t, jstar, three counters (+ 1), guarded list, guarded aux
-    const size_t o_pre = 0, o_t = o_pre + N, o_j = o_t + N, o_cnt = o_j + n_rays, o_list = o_cnt + 4, o_aux = o_list + n_list, total = o_aux + n_aux;
-    if ((rc = ensure_bytes(c, &c->d_scratch, &c->scratch_bytes, total * 4))) return rc;
-    uint32_t *d = (uint32_t *)c->d_scratch;
-    HIP_TRY(c, hipMemcpyAsync(d + o_pre, pre, N * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(d + o_t, t, N * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemsetAsync(d + o_j, 0xFF, n_rays * 4, c->stream));
-    HIP_TRY(c, hipMemsetAsync(d + o_cnt, 0, 4 * 4, c->stream));
-    HIP_TRY(c, hipMemsetAsync(d + o_list, 0xFF, (n_list + n_aux) * 4, c->stream));
+    // pre, t, jstar, the three counters, the guarded list and the guarded aux records (each guarded region one part)
+    Staging s(c, BUF_SCRATCH, c->stream);
+    const int i_pre = s.add(4, N, pre, pre), i_t = s.add(4, N, t), i_j = s.add(4, n_rays, nullptr, jstar_out, 0xFF), i_cnt = s.add(4, 3, nullptr, counts_out, 0x00),
+              i_list = s.add(4, n_list, nullptr, list_out, 0xFF), i_aux = s.add(4, n_aux, nullptr, aux_out, 0xFF);
+    if ((rc = s.begin())) return rc;
+    uint32_t *cnt = s.at<uint32_t>(i_cnt);
     CertPlanArgs q{};
-    q.pre = (float *)(d + o_pre); q.t = (const float *)(d + o_t); q.n_rays = (int)n_rays; q.spr = spr; q.far_ = far_;
+    q.pre = s.at(i_pre); q.t = s.at(i_t); q.n_rays = (int)n_rays; q.spr = spr; q.far_ = far_;
     q.margin = margin; q.depth_limit = depth_limit; q.audit_mask = audit_mask; q.audit_mask_near = audit_mask_near; q.audit_salt = audit_salt;
-    q.list = d + o_list + kStageGuard; q.count = d + o_cnt; q.capacity = list_capacity; q.jstar = (int *)(d + o_j);
-    if (back_part) { q.count_back = d + o_cnt + 1; q.zero_threshold = zero_threshold; }
-    q.aux = d + o_aux + kStageGuard; q.aux_count = d + o_cnt + 2; q.aux_capacity = aux_capacity;
+    q.list = s.at<uint32_t>(i_list) + kStageGuard; q.count = cnt; q.capacity = list_capacity; q.jstar = s.at<int>(i_j);
+    if (back_part) { q.count_back = cnt + 1; q.zero_threshold = zero_threshold; }
+    q.aux = s.at<uint32_t>(i_aux) + kStageGuard; q.aux_count = cnt + 2; q.aux_capacity = aux_capacity;
     HIP_TRY(c, launch_cert_plan(q, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(pre, d + o_pre, N * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(jstar_out, d + o_j, n_rays * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(counts_out, d + o_cnt, 3 * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(list_out, d + o_list, n_list * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(aux_out, d + o_aux, n_aux * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return NERF_OK;
+    return s.finish();
 } NERF_CATCH(c)
 
 int nerf_stage_cert_verify(nerf_ctx *c, size_t n_rays, int spr, float far_, uint32_t list_capacity, const float *t, const int32_t *jstar,
@@ -889,26 +826,18 @@ int nerf_stage_cert_verify(nerf_ctx *c, size_t n_rays, int spr, float far_, uint
     memset(list_out, 0xFF, n_list * 4);
     if (n_rays == 0) return NERF_OK;
     DeviceGuard dg(c->device);
-    // scratch (words): sigma, t, jstar, {count, fall-back rays}, guarded list
-    const size_t o_s = 0, o_t = o_s + N, o_j = o_t + N, o_cnt = o_j + n_rays, o_list = o_cnt + 2, total = o_list + n_list;
-    if ((rc = ensure_bytes(c, &c->d_scratch, &c->scratch_bytes, total * 4))) return rc;
-    uint32_t *d = (uint32_t *)c->d_scratch;
-    const uint32_t cnt[2] = {*count, *fallback_rays};
-    HIP_TRY(c, hipMemcpyAsync(d + o_s, sigma, N * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(d + o_t, t, N * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(d + o_j, jstar, n_rays * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(d + o_cnt, cnt, sizeof cnt, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemsetAsync(d + o_list, 0xFF, n_list * 4, c->stream));
+    // sigma, t, jstar, {count, fall-back rays}, the guarded list (one part)
+    uint32_t cnt[2] = {*count, *fallback_rays};
+    Staging s(c, BUF_SCRATCH, c->stream);
+    const int i_s = s.add(4, N, sigma, sigma), i_t = s.add(4, N, t), i_j = s.add(4, n_rays, jstar), i_cnt = s.add(4, 2, cnt, cnt),
+              i_list = s.add(4, n_list, nullptr, list_out, 0xFF);
+    if ((rc = s.begin())) return rc;
     CertVerifyArgs v{};
-    v.t = (const float *)(d + o_t); v.sigma = (float *)(d + o_s); v.n_rays = (int)n_rays; v.spr = spr; v.far_ = far_; v.jstar = (const int *)(d + o_j);
-    v.list = d + o_list + kStageGuard; v.count = d + o_cnt; v.capacity = list_capacity; v.fallback_rays = d + o_cnt + 1;
+    v.t = s.at(i_t); v.sigma = s.at(i_s); v.n_rays = (int)n_rays; v.spr = spr; v.far_ = far_; v.jstar = s.at<int>(i_j);
+    v.list = s.at<uint32_t>(i_list) + kStageGuard; v.count = s.at<uint32_t>(i_cnt); v.capacity = list_capacity; v.fallback_rays = v.count + 1;
     HIP_TRY(c, launch_cert_verify(v, c->stream));
-    uint32_t back[2] = {0, 0};
-    HIP_TRY(c, hipMemcpyAsync(sigma, d + o_s, N * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(back, d + o_cnt, sizeof back, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(list_out, d + o_list, n_list * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    *count = back[0]; *fallback_rays = back[1];
+    if ((rc = s.finish())) return rc;
+    *count = cnt[0]; *fallback_rays = cnt[1];
     return NERF_OK;
 } NERF_CATCH(c)
 
@@ -921,20 +850,13 @@ int nerf_stage_cert_audit(nerf_ctx *c, const uint32_t *aux, uint32_t aux_count, 
         if (aux[2 * k] >= n_sigma) return fail(c, NERF_ERR_INVALID, "an aux record names a sample outside sigma");
     if (!c) return fail(nullptr, NERF_ERR_INVALID, "ctx is NULL");
     DeviceGuard dg(c->device);
-    // scratch (words): sigma, the records, the count, the four audit words
-    const size_t o_s = 0, o_a = o_s + n_sigma, o_cnt = o_a + 2 * n_rec, o_w = o_cnt + 1, total = o_w + 4;
+    // sigma, the records, the count, the four audit words
     int rc;
-    if ((rc = ensure_bytes(c, &c->d_scratch, &c->scratch_bytes, total * 4))) return rc;
-    uint32_t *d = (uint32_t *)c->d_scratch;
-    if (n_sigma) HIP_TRY(c, hipMemcpyAsync(d + o_s, sigma, n_sigma * 4, hipMemcpyHostToDevice, c->stream));
-    if (n_rec) HIP_TRY(c, hipMemcpyAsync(d + o_a, aux, 2 * n_rec * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(d + o_cnt, &aux_count, 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(d + o_w, audit, 4 * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, launch_cert_audit(d + o_a, d + o_cnt, aux_capacity, (float *)(d + o_s), d + o_w, c->n_cus, c->stream));
-    if (n_sigma) HIP_TRY(c, hipMemcpyAsync(sigma, d + o_s, n_sigma * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(audit, d + o_w, 4 * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return NERF_OK;
+    Staging s(c, BUF_SCRATCH, c->stream);
+    const int i_s = s.add(4, n_sigma, sigma, sigma), i_a = s.add(4, 2 * n_rec, aux), i_cnt = s.add(4, 1, &aux_count), i_w = s.add(4, 4, audit, audit);
+    if ((rc = s.begin())) return rc;
+    HIP_TRY(c, launch_cert_audit(s.at<uint32_t>(i_a), s.at<uint32_t>(i_cnt), aux_capacity, s.at(i_s), s.at<uint32_t>(i_w), c->n_cus, c->stream));
+    return s.finish();
 } NERF_CATCH(c)
 
 } // extern "C"
@@ -955,29 +877,24 @@ static int stage_prefilter(nerf_ctx *c, int which, int f16, const float *origin,
     if (n_rays == 0) return NERF_OK;
     DeviceGuard dg(c->device);
     const size_t N = n_rays * (size_t)spr;
-    // scratch (words): directions, t, pre-activations, {ray queue, non-finite tiles, samples evaluated (64 bits)}, [origins]
-    const size_t o_d = 0, o_t = o_d + 3 * n_rays, o_p = o_t + N, o_cnt = (o_p + N + 1) & ~(size_t)1, o_o = o_cnt + 4, total = o_o + (origins ? 3 * n_rays : 0);
+    // directions, t, pre-activations (NaN = "not evaluated", as cert_pass fills them), {ray queue, non-finite tiles, samples evaluated (64 bits)}, [origins]
     int rc;
-    if ((rc = ensure_bytes(c, &c->d_scratch, &c->scratch_bytes, total * 4))) return rc;
-    uint32_t *d = (uint32_t *)c->d_scratch;
-    HIP_TRY(c, hipMemcpyAsync(d + o_d, dirs, 3 * n_rays * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(d + o_t, t, N * 4, hipMemcpyHostToDevice, c->stream));
-    if (origins) HIP_TRY(c, hipMemcpyAsync(d + o_o, origins, 3 * n_rays * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemsetAsync(d + o_p, 0xFF, N * 4, c->stream)); // NaN = "not evaluated", as cert_pass fills it
-    HIP_TRY(c, hipMemsetAsync(d + o_cnt, 0, 4 * 4, c->stream));
+    Staging s(c, BUF_SCRATCH, c->stream);
+    const int i_d = s.add(F, 3 * n_rays, dirs), i_t = s.add(F, N, t), i_p = s.add(F, N, nullptr, pre_out, 0xFF), i_cnt = s.add(4, 4, nullptr, nullptr, 0x00),
+              i_o = s.opt(origins, F, 3 * n_rays, origins);
+    if ((rc = s.begin())) return rc;
+    uint32_t *cnt = s.at<uint32_t>(i_cnt);
     SeqArgs q{};
     q.wstream = f16 ? (const float *)net.wstream_f16v2 : stream_of(net, NERF_MLP_BF16); q.small_params = net.small;
-    q.n_rays = (int)n_rays; q.samples_per_ray = spr; q.ray_dirs = (const float *)(d + o_d); q.t = (const float *)(d + o_t); q.far_ = far_;
-    if (origins) q.ray_origins = (const float *)(d + o_o);
+    q.n_rays = (int)n_rays; q.samples_per_ray = spr; q.ray_dirs = s.at(i_d); q.t = s.at(i_t); q.far_ = far_;
+    if (origins) q.ray_origins = s.at(i_o);
     else copy3(q.origin, origin);
-    q.sigma_out = (float *)(d + o_p);
-    q.ray_counter = d + o_cnt; q.nonfinite = d + o_cnt + 1; q.stats = (unsigned long long *)(d + o_cnt + 2);
+    q.sigma_out = s.at(i_p);
+    q.ray_counter = cnt; q.nonfinite = cnt + 1; q.stats = (unsigned long long *)(cnt + 2);
     q.prefilter = 1; q.prefilter_cut_T = cut_T;
     HIP_TRY(c, f16 ? nerf_trunk_seq_f16v2_launch(q, c->n_cus, c->stream) : nerf_trunk_seq_bf16_launch(q, false, c->n_cus, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(pre_out, d + o_p, N * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(nonfinite_tiles, d + o_cnt + 1, 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return NERF_OK;
+    HIP_TRY(c, hipMemcpyAsync(nonfinite_tiles, cnt + 1, 4, hipMemcpyDeviceToHost, c->stream));
+    return s.finish();
 }
 
 extern "C" {

@@ -58,60 +58,60 @@ int check_rgba8(nerf_ctx *c, const float *background, int alpha_mode, const void
 
 namespace {
 
-// The rays of a batch, already on the device (but for a shared origin).
-struct RayBatch {
-    const float *h_origin;     // n_origins == 1: the shared origin (HOST, 3 floats); else NULL
-    const float *d_origins;    // n_origins == n_rays: n_rays x 3 (device); else NULL
-    const float *d_dirs;       // n_rays x 3 (device)
-    size_t n_rays;
+// What the ten nerf_render_rays* entry points receive.  A host form stages its request (render_rays_entry) into one whose pointers are
+// device pointers and hands that to the device form.
+struct RayRequest {
+    const float *origins; size_t n_origins; // n_origins x 3; n_origins is 1 (one origin for every ray) or n_rays
+    const float *dirs; size_t n_rays;       // n_rays x 3
     int normalize;
     float near_, far_;
-    const float *d_bounds;     // n_rays x 2 (device) or NULL
-    const uint32_t *d_rng;     // n_rays (device) or NULL
+    const float *bounds;                    // n_rays x 2, or NULL
+    const uint32_t *rng_index;              // n_rays, or NULL
+    const nerf_render_opts *opts;
+    const float *background;                // 3 floats on the host, or NULL
+    float *rgb, *depth, *opacity;           // per ray; depth and opacity may be NULL
+    bool want_normals; float h; float *normals; // nerf_render_rays_normals*
+    bool clipped;                           // nerf_render_rays_clipped*: the grid (lo, step, dims on the host), the flags and the hit count
+    const uint32_t *occ_bits; const float *lo, *step; const int32_t *dims; uint8_t *hit; uint64_t *n_hit;
+    bool certified;                         // nerf_render_rays*_certified*
+    hipStream_t st;
+    nerf_stats *stats;
+    const float *h_origin;                  // device requests with n_origins == 1: the shared origin on the HOST once it is known
 };
 
-// The pass workspace of a normals render in c->d_normal, every part 256-byte aligned.
+// The pass workspace of a normals render in BUF_NORMAL (StageLayout: every part 256-byte aligned).
 struct NormalWorkspace {
     float *w = nullptr; uint32_t *list = nullptr, *count = nullptr, *base = nullptr, *bsum = nullptr, *totals = nullptr;
+    size_t bytes = 0;
     NormalWorkspace() = default;
-    static size_t al(size_t bytes) { return (bytes + 255) / 256 * 256; }
-    static size_t blocks(size_t rays) { return (rays + kNormalBlock - 1) / kNormalBlock; }
-    static size_t bytes(size_t rays, size_t samples) { return 2 * al(4 * samples) + 2 * al(4 * rays) + al(4 * blocks(rays)) + 256; }
-    NormalWorkspace(void *p, size_t rays, size_t samples) {
-        char *q = (char *)p;
-        w = (float *)q; q += al(4 * samples);
-        list = (uint32_t *)q; q += al(4 * samples);
-        count = (uint32_t *)q; q += al(4 * rays);
-        base = (uint32_t *)q; q += al(4 * rays);
-        bsum = (uint32_t *)q; q += al(4 * blocks(rays));
-        totals = (uint32_t *)q;
+    NormalWorkspace(void *p, size_t rays, size_t samples) { // p == NULL: only `bytes`
+        StageLayout l;
+        const int i_w = l.add(4, samples), i_list = l.add(4, samples), i_count = l.add(4, rays), i_base = l.add(4, rays),
+                  i_bsum = l.add(4, (rays + kNormalBlock - 1) / kNormalBlock), i_totals = l.add(4, 2);
+        bytes = l.total;
+        if (!p) return;
+        w = l.at<float>(p, i_w); list = l.at<uint32_t>(p, i_list); count = l.at<uint32_t>(p, i_count); base = l.at<uint32_t>(p, i_base);
+        bsum = l.at<uint32_t>(p, i_bsum); totals = l.at<uint32_t>(p, i_totals);
     }
 };
 
-// The workspace of a clipped render (nerf_render_rays_clipped) in c->d_clip for a batch of n rays, every part 256-byte aligned: the clip's
-// outputs, the block sums, and the compacted batch with its outputs (sized for n hits, so that the hit count never reallocates).
+// The workspace of a clipped render (nerf_render_rays_clipped) in BUF_CLIP for a batch of n rays (StageLayout: every part 256-byte aligned):
+// the clip's outputs, the block sums, and the compacted batch with its outputs (sized for n hits, so that the hit count never reallocates).
 struct ClipWorkspace {
     uint32_t *totals = nullptr, *bsum = nullptr, *ray_of = nullptr, *rng_c = nullptr;
     float *clip_bounds = nullptr, *dirs_c = nullptr, *origins_c = nullptr, *bounds_c = nullptr, *rgb_c = nullptr, *depth_c = nullptr, *opacity_c = nullptr;
     uint8_t *hit = nullptr;
-    static size_t al(size_t bytes) { return (bytes + 255) / 256 * 256; }
-    static size_t bytes(size_t n, bool per_ray_origins) { return ClipWorkspace(nullptr, n, per_ray_origins).end; }
-    size_t end = 0;
-    ClipWorkspace(void *p, size_t n, bool per_ray_origins) {
-        char *base = (char *)p;
-        auto take = [&](size_t b) { char *q = base ? base + end : nullptr; end += al(b); return (void *)q; };
-        totals = (uint32_t *)take(8);
-        bsum = (uint32_t *)take(4 * ((n + kClipBlock - 1) / kClipBlock));
-        hit = (uint8_t *)take(n);
-        clip_bounds = (float *)take(8 * n);
-        ray_of = (uint32_t *)take(4 * n);
-        rng_c = (uint32_t *)take(4 * n);
-        dirs_c = (float *)take(12 * n);
-        origins_c = (float *)take(per_ray_origins ? 12 * n : 0);
-        bounds_c = (float *)take(8 * n);
-        rgb_c = (float *)take(12 * n);
-        depth_c = (float *)take(4 * n);
-        opacity_c = (float *)take(4 * n);
+    size_t bytes = 0;
+    ClipWorkspace(void *p, size_t n, bool per_ray_origins) { // p == NULL: only `bytes`
+        StageLayout l;
+        const int i_totals = l.add(4, 2), i_bsum = l.add(4, (n + kClipBlock - 1) / kClipBlock), i_hit = l.add(1, n), i_cb = l.add(8, n),
+                  i_ray = l.add(4, n), i_rng = l.add(4, n), i_dirs = l.add(12, n), i_org = l.add(12, per_ray_origins ? n : 0), i_bounds = l.add(8, n),
+                  i_rgb = l.add(12, n), i_depth = l.add(4, n), i_opacity = l.add(4, n);
+        bytes = l.total;
+        if (!p) return;
+        totals = l.at<uint32_t>(p, i_totals); bsum = l.at<uint32_t>(p, i_bsum); hit = l.at<uint8_t>(p, i_hit); clip_bounds = l.at<float>(p, i_cb);
+        ray_of = l.at<uint32_t>(p, i_ray); rng_c = l.at<uint32_t>(p, i_rng); dirs_c = l.at<float>(p, i_dirs); origins_c = l.at<float>(p, i_org);
+        bounds_c = l.at<float>(p, i_bounds); rgb_c = l.at<float>(p, i_rgb); depth_c = l.at<float>(p, i_depth); opacity_c = l.at<float>(p, i_opacity);
     }
 };
 
@@ -122,10 +122,6 @@ struct ClipWorkspace {
 // run as launches on one stream with no host round trip (a normals render has one per pass, normals_pass).  Image renders (render_once) and
 // ray batches (render_rays_device) validate their own arguments, fill a RenderJob and run the same loop, render_passes; they differ in
 // where a pass's rays come from (prepare_rays) and in how a network is evaluated over a pass's samples (eval_net).
-
-// per (pass, network) of a certify_zero render: {list 1 length, list 2 length, audited, violations, headroom code, max-error bits, fallback rays,
-//     audit-record count, pre-filter ray queue head, list 1 back-part length, u64 samples the pre-filter evaluated, f16 range exits, ...}
-constexpr int kCertSlots = 16;
 
 // What a render does, as plain data: filled by the two drivers after validation, read-only afterwards.
 struct RenderJob {
@@ -141,7 +137,7 @@ struct RenderJob {
     // outputs, per ray: the pass that starts at ray r0 writes out + 3 r0, depth + r0, opacity + r0 (r0 = row x RW of an image)
     float *out, *depth, *opacity;
     size_t n_rays, pass_rays; // all rays, rays of a full pass
-    int kind_colour;          // event kind of the colour-producing launch: 1 for images (-> c->dominant), 5 for batches
+    EvKind kind_colour;       // of the colour-producing launch: EV_IMAGE_COLOUR (-> c->dominant) or EV_BATCH_COLOUR
     const char *what;         // "frame" / "batch", for the non-finite error
     hipStream_t st;
     // modes (skip_empty, skip_dead, hybrid_sampling: images only, ray batches refuse them)
@@ -150,7 +146,7 @@ struct RenderJob {
     size_t cert_cap, aux_cap;  // certify_zero: capacity of the sample list and of the audit records
     unsigned long long *clock_out; // NERF_DEBUG_CLOCK: where the fine launch leaves its clocks
     // the ray source: a camera window (g: everything but the pass's own n_rays and first row) or the caller's rays
-    const RayBatch *batch;
+    const RayRequest *batch;   // device pointers
     RayGenArgs g;
     float origin[3];           // the shared origin (batches with per-ray origins: unused)
     float *d_pts, *d_daos;     // per-ray origins, uncertified: the points and per-sample directions of one launch (k_batch_points)
@@ -212,27 +208,27 @@ void plan_job(const nerf_ctx *c, const nerf_render_opts *o, RenderJob &j) {
 // a pass must keep rays * samples within int32 (kernel indices) as well as within the configured budget
 size_t pass_capacity(const nerf_ctx *c, int M) { return std::max<size_t>(1, std::min<size_t>(c->max_rays_per_pass, (size_t)0x3fffffff / (size_t)M)); }
 
-// step 1: c->d_dirs and the coarse t in c->d_tc for the rays of pass p; fills what the later steps need to know about those rays
+// step 1: c->dev(BUF_DIRS) and the coarse t in c->dev(BUF_TC) for the rays of pass p; fills what the later steps need to know about those rays
 int prepare_rays(nerf_ctx *c, const RenderJob &j, Pass &p) {
     if (!j.batch) {
         p.g = j.g; p.g.n_rays = p.n_rays; p.g.ry0 += (int)(p.r0 / (size_t)j.g.rw);
-        return timed(c, j.st, 2, 0, [&]() -> int {
-            HIP_TRY(c, launch_ray_dirs(p.g, c->d_dirs, j.st));
-            HIP_TRY(c, launch_stratified(p.g, j.nc, j.near_, j.far_, j.seed, c->d_tc, j.st));
+        return timed(c, j.st, EV_OTHER, 0, [&]() -> int {
+            HIP_TRY(c, launch_ray_dirs(p.g, c->dev(BUF_DIRS), j.st));
+            HIP_TRY(c, launch_stratified(p.g, j.nc, j.near_, j.far_, j.seed, c->dev(BUF_TC), j.st));
             return NERF_OK;
         });
     }
-    const RayBatch &b = *j.batch;
+    const RayRequest &b = *j.batch;
     const size_t r0 = p.r0;
-    p.rng = b.d_rng ? b.d_rng + r0 : nullptr;
-    p.origins = b.d_origins ? b.d_origins + 3 * r0 : nullptr;
+    p.rng = b.rng_index ? b.rng_index + r0 : nullptr;
+    p.origins = b.n_origins != 1 ? b.origins + 3 * r0 : nullptr;
     p.g.n_rays = p.n_rays; p.g.rx0 = (int)r0; p.g.ry0 = 0; p.g.rw = p.n_rays; p.g.rnx = p.n_rays; p.g.rny = 1;
     BatchPrepareArgs q{};
-    q.n_rays = p.n_rays; q.first_ray = (uint32_t)r0; q.dirs = b.d_dirs + 3 * r0; q.normalize = b.normalize;
-    q.bounds = b.d_bounds ? b.d_bounds + 2 * r0 : nullptr; q.rng_index = p.rng;
+    q.n_rays = p.n_rays; q.first_ray = (uint32_t)r0; q.dirs = b.dirs + 3 * r0; q.normalize = b.normalize ? 1 : 0;
+    q.bounds = b.bounds ? b.bounds + 2 * r0 : nullptr; q.rng_index = p.rng;
     q.near_ = b.near_; q.far_ = b.far_; q.count = j.nc; q.seed_lo = (uint32_t)j.seed; q.seed_hi = (uint32_t)(j.seed >> 32);
-    q.dirs_out = c->d_dirs; q.t_out = c->d_tc; q.far_out = j.d_far;
-    return timed(c, j.st, 2, 0, [&]() -> int { HIP_TRY(c, launch_batch_prepare(q, j.st)); return NERF_OK; });
+    q.dirs_out = c->dev(BUF_DIRS); q.t_out = c->dev(BUF_TC); q.far_out = j.d_far;
+    return timed(c, j.st, EV_OTHER, 0, [&]() -> int { HIP_TRY(c, launch_batch_prepare(q, j.st)); return NERF_OK; });
 }
 
 // what every ray-sequential launch of a pass has in common: one network's trunk over the pass's rays from the shared origin
@@ -240,7 +236,7 @@ SeqArgs seq_args(const nerf_ctx *c, const RenderJob &j, const Pass &p, const flo
                  float *sigma_out) {
     SeqArgs q{};
     q.wstream = wstream; q.small_params = small_params; q.n_rays = p.n_rays; q.samples_per_ray = spr;
-    q.ray_dirs = c->d_dirs; q.t = t; q.far_ = j.far_;
+    q.ray_dirs = c->dev(BUF_DIRS); q.t = t; q.far_ = j.far_;
     copy3(q.origin, j.origin);
     q.sigma_out = sigma_out;
     return q;
@@ -248,16 +244,16 @@ SeqArgs seq_args(const nerf_ctx *c, const RenderJob &j, const Pass &p, const flo
 
 // skip_dead: one network over the rays of the pass as ray-sequential trunk [+ colour head on the live samples]
 int seq_pass(nerf_ctx *c, const RenderJob &j, const Pass &p, const DevNet &net, int dt, int spr, const float *t_in, float *sigma_out, float *rgb_out,
-             int slot, int kind_trunk) {
+             int slot, EvKind kind_trunk) {
     const hipStream_t st = j.st;
-    unsigned int *ctr = c->d_seq + 4 * (size_t)slot;
+    SeqCounters *ctr = c->dev<SeqCounters>(BUF_SEQ) + slot;
     HIP_TRY(c, hipMemsetAsync(sigma_out, 0, (size_t)p.n_rays * spr * sizeof(float), st)); // samples behind the cut stay 0
     if (rgb_out) HIP_TRY(c, hipMemsetAsync(rgb_out, 0, (size_t)p.n_rays * spr * 3 * sizeof(float), st)); // weight-0 samples: 0 * 0
     SeqArgs q = seq_args(c, j, p, stream_of(net, dt), small_of(net, dt), spr, t_in, sigma_out);
     zskip_of(c, net, q);
-    q.ray_counter = ctr; q.live_count = ctr + 1; q.h8 = c->d_h8; q.slot_point = c->d_slot_point;
+    q.ray_counter = &ctr->ray_head; q.live_count = &ctr->live_count; q.h8 = c->dev(BUF_H8); q.slot_point = c->dev<unsigned int>(BUF_SLOT_POINT);
     q.rgb_out = rgb_out; // f32: colour passes inside the trunk launch
-    q.stats = (unsigned long long *)(ctr + 2);
+    q.stats = &ctr->evaluated;
     q.nonfinite = nonfinite_of(c, dt);
     int rc = timed(c, st, kind_trunk, (uint64_t)p.n_rays * spr, [&]() -> int {
         HIP_TRY(c, dt == NERF_MLP_BF16X3 ? nerf_trunk_seq_x3_launch(q, rgb_out != nullptr, c->n_cus, st)
@@ -268,9 +264,9 @@ int seq_pass(nerf_ctx *c, const RenderJob &j, const Pass &p, const DevNet &net, 
     });
     if (rc || !rgb_out || dt == NERF_MLP_F32) return rc;
     ColourArgs k{};
-    k.wstream = stream_of(net, dt); k.small_params = net.small; k.live_count = ctr + 1; k.h8 = c->d_h8; k.slot_point = c->d_slot_point;
-    k.ray_dirs = c->d_dirs; k.samples_per_ray = spr; k.rgb_out = rgb_out; k.nonfinite = nonfinite_of(c, dt);
-    return timed(c, st, 4, 0, [&]() -> int {
+    k.wstream = stream_of(net, dt); k.small_params = net.small; k.live_count = &ctr->live_count; k.h8 = c->dev(BUF_H8); k.slot_point = c->dev<unsigned int>(BUF_SLOT_POINT);
+    k.ray_dirs = c->dev(BUF_DIRS); k.samples_per_ray = spr; k.rgb_out = rgb_out; k.nonfinite = nonfinite_of(c, dt);
+    return timed(c, st, EV_COLOUR_SIDE, 0, [&]() -> int {
         HIP_TRY(c, dt == NERF_MLP_BF16X3 ? nerf_colour_x3_launch(k, c->n_cus, st)
                    : dt == NERF_MLP_F16X2 ? nerf_colour_f16x2_launch(k, c->n_cus, st)
                                           : nerf_colour_bf16_launch(k, c->n_cus, st));
@@ -292,22 +288,22 @@ int seq_pass(nerf_ctx *c, const RenderJob &j, const Pass &p, const DevNet &net, 
 // points, and the fused pre-filter (NERF_CERTIFY_SEQ_PREFILTER=0), which knows one origin only, gives way to the ray-sequential one.
 // far_: only the interval behind a ray's LAST sample depends on it, and no certify kernel's result does: the kernels get
 // j.far_cert, the exact per-ray far stays with k_resample and k_composite.
-int cert_pass(nerf_ctx *c, const RenderJob &j, const Pass &p, const MlpArgs &a, const DevNet &net, int which, int dt, int kind) {
+int cert_pass(nerf_ctx *c, const RenderJob &j, const Pass &p, const MlpArgs &a, const DevNet &net, int which, int dt, EvKind kind) {
     const hipStream_t st = j.st;
     const int n_pts = a.n_points, spr = a.samples_per_ray;
     const float *t_in = a.t;
     float *sigma_out = a.sigma_out, *rgb_out = a.rgb_out;
-    unsigned int *slots = c->d_cert + kCertSlots * (2 * (size_t)p.index + which);
+    CertCounters *ctr = c->dev<CertCounters>(BUF_CERT) + (2 * (size_t)p.index + which);
     const unsigned cap = (unsigned)std::min<size_t>(j.cert_cap, (size_t)n_pts);
     // the pre-filter's arithmetic: f16 where the network fits its range (8 x closer to the exact pre-activations: tighter margins, a shorter
-    // list), else bf16; a tile of the f16 pass that saw an activation leave the range counts in slots[12] and render_device goes back to bf16
+    // list), else bf16; a tile of the f16 pass that saw an activation leave the range counts in range_left and render_device goes back to bf16
     const bool pf16 = c->cert_prefilter_f16[which];
     const float *pf_stream = pf16 ? (const float *)net.wstream_f16v2 : stream_of(net, NERF_MLP_BF16);
     MlpArgs b = a;
     b.ray_origins = p.origins;
     b.wstream = pf_stream; b.small_params = net.small;
-    b.rgb_out = nullptr; b.raw_pre = 1; b.skip_empty = 0; b.skip_counter = nullptr; b.nonfinite = pf16 ? slots + 12 : nullptr;
-    const int kind_side = which == 0 && !rgb_out ? 0 : 4;
+    b.rgb_out = nullptr; b.raw_pre = 1; b.skip_empty = 0; b.skip_counter = nullptr; b.nonfinite = pf16 ? &ctr->range_left : nullptr;
+    const EvKind kind_side = which == 0 && !rgb_out ? EV_COARSE_MLP : EV_COLOUR_SIDE;
     int rc = timed(c, st, kind_side, 0, [&]() -> int {
         if (c->cert_seq_prefilter || p.origins) {
             // the pre-filter walks each ray front to back and stops where its own (bf16) transmittance predicts the cut, a little
@@ -315,9 +311,9 @@ int cert_pass(nerf_ctx *c, const RenderJob &j, const Pass &p, const MlpArgs &a, 
             HIP_TRY(c, hipMemsetAsync(sigma_out, 0xFF, (size_t)n_pts * sizeof(float), st));
             SeqArgs q = seq_args(c, j, p, pf_stream, net.small, spr, t_in, sigma_out);
             q.far_ = j.far_cert; q.ray_origins = p.origins;
-            q.ray_counter = slots + 8; q.stats = (unsigned long long *)(slots + 10);
+            q.ray_counter = &ctr->pf_ray_head; q.stats = &ctr->pf_samples;
             q.prefilter = 1; q.prefilter_cut_T = expf(-(c->cert_depth_limit + 0.5f));
-            q.nonfinite = pf16 ? slots + 12 : nullptr;
+            q.nonfinite = pf16 ? &ctr->range_left : nullptr;
             HIP_TRY(c, pf16 ? nerf_trunk_seq_f16v2_launch(q, c->n_cus, st) : nerf_trunk_seq_bf16_launch(q, false, c->n_cus, st));
         } else HIP_TRY(c, pf16 ? nerf_mlp_f16v2_launch(b, c->n_cus, st) : launch_mlp(c, NERF_MLP_BF16, b, false, st));
         CertPlanArgs q{};
@@ -325,12 +321,12 @@ int cert_pass(nerf_ctx *c, const RenderJob &j, const Pass &p, const MlpArgs &a, 
         q.margin = c->cert_margin[which]; q.depth_limit = c->cert_depth_limit;
         q.audit_mask = c->cert_audit_mask; q.audit_mask_near = c->cert_audit_mask_near;
         q.audit_salt = (unsigned)(j.seed * 0x9E3779B97F4A7C15ull >> 32) + 0x632BE5ABu * p.index + (unsigned)which;
-        q.list = c->d_point_list; q.count = slots; q.capacity = cap; q.jstar = c->d_jstar;
+        q.list = c->dev<unsigned int>(BUF_POINT_LIST); q.count = &ctr->list1_len; q.capacity = cap; q.jstar = c->dev<int>(BUF_JSTAR);
         // full evaluations: probable zeros (pre-filter pre-activation below -margin x cert_zero_frac: several times the largest pre-filter error
         // the lego audits see is not needed for a skip -- a positive density among them only keeps its tile's colour heads) and the audited
         // certificates go to the back part of the list, whose all-zero tiles skip the colour head (exact: skip_empty)
-        if (rgb_out && c->cert_zero_tiles) { q.count_back = slots + 9; q.zero_threshold = c->cert_margin[which] * c->cert_zero_frac; }
-        q.aux = c->d_cert_aux; q.aux_count = slots + 7; q.aux_capacity = (unsigned)j.aux_cap;
+        if (rgb_out && c->cert_zero_tiles) { q.count_back = &ctr->list1_back_len; q.zero_threshold = c->cert_margin[which] * c->cert_zero_frac; }
+        q.aux = c->dev<unsigned int>(BUF_CERT_AUX); q.aux_count = &ctr->aux_count; q.aux_capacity = (unsigned)j.aux_cap;
         HIP_TRY(c, launch_cert_plan(q, st));
         if (rgb_out) HIP_TRY(c, hipMemsetAsync(rgb_out, 0, (size_t)n_pts * 3 * sizeof(float), st)); // weight 0 either way: 0 * 0
         return NERF_OK;
@@ -338,18 +334,18 @@ int cert_pass(nerf_ctx *c, const RenderJob &j, const Pass &p, const MlpArgs &a, 
     if (rc) return rc;
     MlpArgs l = b;
     l.wstream = stream_of(net, dt); l.small_params = small_of(net, dt); zskip_of(c, net, l); l.raw_pre = 0; l.mode = MLP_MODE_LIST; l.rgb_out = rgb_out; l.n_points = (int)cap;
-    l.point_list = c->d_point_list; l.point_list_count = slots;
-    if (rgb_out && c->cert_zero_tiles) { l.point_list_count_back = slots + 9; l.skip_empty = 1; l.skip_counter = c->d_skip; }
+    l.point_list = c->dev<unsigned int>(BUF_POINT_LIST); l.point_list_count = &ctr->list1_len;
+    if (rgb_out && c->cert_zero_tiles) { l.point_list_count_back = &ctr->list1_back_len; l.skip_empty = 1; l.skip_counter = c->d_skip; }
     l.nonfinite = nonfinite_of(c, dt);
     // points = 0: the list's length is known on the device only (nerf_stats.n_exec_* report it after the frame)
     if (cap > 0 && (rc = timed(c, st, kind, 0, [&]() -> int { HIP_TRY(c, launch_mlp(c, dt, l, rgb_out != nullptr, st)); return NERF_OK; }))) return rc;
     return timed(c, st, kind_side, 0, [&]() -> int {
-        HIP_TRY(c, launch_cert_audit(c->d_cert_aux, slots + 7, (unsigned)j.aux_cap, sigma_out, slots + 2, c->n_cus, st));
+        HIP_TRY(c, launch_cert_audit(c->dev<unsigned int>(BUF_CERT_AUX), &ctr->aux_count, (unsigned)j.aux_cap, sigma_out, &ctr->audited, c->n_cus, st));
         CertVerifyArgs v{};
-        v.t = t_in; v.sigma = sigma_out; v.n_rays = p.n_rays; v.spr = spr; v.far_ = j.far_cert; v.jstar = c->d_jstar;
-        v.list = c->d_point_list; v.count = slots + 1; v.capacity = cap; v.fallback_rays = slots + 6;
+        v.t = t_in; v.sigma = sigma_out; v.n_rays = p.n_rays; v.spr = spr; v.far_ = j.far_cert; v.jstar = c->dev<int>(BUF_JSTAR);
+        v.list = c->dev<unsigned int>(BUF_POINT_LIST); v.count = &ctr->list2_len; v.capacity = cap; v.fallback_rays = &ctr->fallback_rays;
         HIP_TRY(c, launch_cert_verify(v, st));
-        l.point_list_count = slots + 1; l.point_list_count_back = nullptr;
+        l.point_list_count = &ctr->list2_len; l.point_list_count_back = nullptr;
         if (cap > 0) HIP_TRY(c, launch_mlp(c, dt, l, rgb_out != nullptr, st)); // usually an empty list: the launch returns at once
         return NERF_OK;
     });
@@ -360,12 +356,12 @@ int cert_pass(nerf_ctx *c, const RenderJob &j, const Pass &p, const MlpArgs &a, 
 // mode from the shared origin (the origin rides in the kernel arguments), or for per-ray origins in points mode behind k_batch_points, which
 // expands the samples into points + per-sample directions; points mode forms nothing itself and then runs the same per-column arithmetic:
 // the two plain paths carry the same bits.
-int eval_net(nerf_ctx *c, const RenderJob &j, const Pass &p, int which, int dt, int spr, const float *t, float *sigma_out, float *rgb_out, int kind) {
+int eval_net(nerf_ctx *c, const RenderJob &j, const Pass &p, int which, int dt, int spr, const float *t, float *sigma_out, float *rgb_out, EvKind kind) {
     const DevNet &net = c->net[which];
     if (j.seq) return seq_pass(c, j, p, net, dt, spr, t, sigma_out, rgb_out, 3 * (int)p.index + which, kind);
     const hipStream_t st = j.st;
     MlpArgs a{};
-    a.ray_dirs = c->d_dirs;
+    a.ray_dirs = c->dev(BUF_DIRS);
     if (p.origins && !j.certify) a.mode = MLP_MODE_POINTS;
     else { a.mode = MLP_MODE_RAYS; copy3(a.origin, j.origin); }
     a.wstream = stream_of(net, dt); a.small_params = small_of(net, dt); zskip_of(c, net, a);
@@ -380,13 +376,13 @@ int eval_net(nerf_ctx *c, const RenderJob &j, const Pass &p, int which, int dt, 
     if (p.origins) {
         // only the f32 kernel has a sigma-only points mode: a bf16 sampling pass over expanded points runs the full kernel (the same
         // densities) and leaves its colours in the fine pass's buffer, which that pass overwrites
-        if (!full && dt != NERF_MLP_F32) { full = true; a.rgb_out = c->d_rgbf; }
+        if (!full && dt != NERF_MLP_F32) { full = true; a.rgb_out = c->dev(BUF_RGBF); }
         BatchPointsArgs q{};
-        q.n_rays = p.n_rays; q.spr = spr; q.origins = p.origins; q.dirs = c->d_dirs; q.t = t;
+        q.n_rays = p.n_rays; q.spr = spr; q.origins = p.origins; q.dirs = c->dev(BUF_DIRS); q.t = t;
         q.pts_soa = j.d_pts; q.dirs_aos = j.d_daos;
         a.pts_soa = j.d_pts; a.dirs_aos = j.d_daos;
         int rc;
-        if ((rc = timed(c, st, 2, 0, [&]() -> int { HIP_TRY(c, launch_batch_points(q, st)); return NERF_OK; }))) return rc;
+        if ((rc = timed(c, st, EV_OTHER, 0, [&]() -> int { HIP_TRY(c, launch_batch_points(q, st)); return NERF_OK; }))) return rc;
     }
     // depth ordering (mlp_layout.h DepthOrder): the fine f32 launch of an image pass takes its waves from the pass's depth-sorted pixel blocks;
     // the table is built here, behind the resampler that wrote t, on the render's stream
@@ -394,11 +390,11 @@ int eval_net(nerf_ctx *c, const RenderJob &j, const Pass &p, int which, int dt, 
         const nerfmlp::DepthOrder d = nerf_mlp_depth_order(a, full);
         if (d.tiles > 0) {
             int rc;
-            if ((rc = ensure_bytes(c, (void **)&c->d_order, &c->order_bytes, (size_t)d.points * sizeof(unsigned int)))) return rc;
+            if ((rc = c->buf[BUF_ORDER].ensure(c, (size_t)d.points * sizeof(unsigned int)))) return rc;
             DepthOrderArgs q{};
-            q.t = t; q.rw = a.rays_per_row; q.spr = spr; q.blocks_x = d.blocks_x; q.blocks = d.blocks; q.table = c->d_order;
-            if ((rc = timed(c, st, 2, 0, [&]() -> int { HIP_TRY(c, launch_depth_order(q, st)); return NERF_OK; }))) return rc;
-            a.order_table = c->d_order;
+            q.t = t; q.rw = a.rays_per_row; q.spr = spr; q.blocks_x = d.blocks_x; q.blocks = d.blocks; q.table = c->dev<unsigned int>(BUF_ORDER);
+            if ((rc = timed(c, st, EV_OTHER, 0, [&]() -> int { HIP_TRY(c, launch_depth_order(q, st)); return NERF_OK; }))) return rc;
+            a.order_table = c->dev<unsigned int>(BUF_ORDER);
         }
     }
     return timed(c, st, kind, (uint64_t)a.n_points, [&]() -> int { HIP_TRY(c, launch_mlp(c, dt, a, full, st)); return NERF_OK; });
@@ -406,21 +402,21 @@ int eval_net(nerf_ctx *c, const RenderJob &j, const Pass &p, int which, int dt, 
 
 // hybrid_sampling, after the first resample ra: the coarse densities came from the split arithmetic.  Redo, in exact f32, the rays with a
 // draw in a light CDF bin (their sample positions are the ill-conditioned ones) and resample just those: same positions as the f32 path.
-// hctr: {queue head, flagged-ray count, u64 chunks}
-int hybrid_redo(nerf_ctx *c, const RenderJob &j, const Pass &p, const ResampleArgs &ra, unsigned int *hctr) {
+// hctr: the pass's third SeqCounters; its live_count is the number of flagged rays
+int hybrid_redo(nerf_ctx *c, const RenderJob &j, const Pass &p, const ResampleArgs &ra, SeqCounters *hctr) {
     const hipStream_t st = j.st;
     const DevNet &NC = c->net[NERF_NET_COARSE];
-    SeqArgs q = seq_args(c, j, p, NC.wstream, NC.small_f32, j.nc, c->d_tc, c->d_sc);
+    SeqArgs q = seq_args(c, j, p, NC.wstream, NC.small_f32, j.nc, c->dev(BUF_TC), c->dev(BUF_SC));
     zskip_of(c, NC, q);
-    q.ray_counter = hctr; q.stats = (unsigned long long *)(hctr + 2);
-    q.live_count = nullptr; // hctr[1] is the LENGTH of the ray list below: this launch never exports (no colour head)
-    q.ray_list = c->d_flag_list; q.ray_list_count = hctr + 1; q.zero_fill_after_cut = 1;
+    q.ray_counter = &hctr->ray_head; q.stats = &hctr->evaluated;
+    q.live_count = nullptr; // hctr->live_count is the LENGTH of the ray list below: this launch never exports (no colour head)
+    q.ray_list = c->dev<unsigned int>(BUF_FLAG_LIST); q.ray_list_count = &hctr->live_count; q.zero_fill_after_cut = 1;
     int rc;
-    if ((rc = timed(c, st, 0, 0, [&]() -> int { HIP_TRY(c, nerf_trunk_seq_launch(q, false, c->n_cus, st)); return NERF_OK; }))) return rc;
+    if ((rc = timed(c, st, EV_COARSE_MLP, 0, [&]() -> int { HIP_TRY(c, nerf_trunk_seq_launch(q, false, c->n_cus, st)); return NERF_OK; }))) return rc;
     ResampleArgs rb = ra;
     rb.flag_tau = 0.0f; rb.flag_count = nullptr; rb.flag_list = nullptr;
-    rb.ray_list = c->d_flag_list; rb.ray_list_count = hctr + 1;
-    return timed(c, st, 2, 0, [&]() -> int { HIP_TRY(c, launch_resample(rb, st)); return NERF_OK; });
+    rb.ray_list = c->dev<unsigned int>(BUF_FLAG_LIST); rb.ray_list_count = &hctr->live_count;
+    return timed(c, st, EV_OTHER, 0, [&]() -> int { HIP_TRY(c, launch_resample(rb, st)); return NERF_OK; });
 }
 
 // The normals of the pass (j.normals != NULL), from the weights the compositing launch left in nw.w (t: the composited samples' positions):
@@ -435,7 +431,7 @@ int normals_pass(nerf_ctx *c, const RenderJob &j, const Pass &p, const DevNet &n
     const int n_rays = p.n_rays, n_comp = j.n_comp;
     int rc;
     NormalListArgs la{nw.w, n_rays, n_comp, nw.count, nw.base, nw.bsum, nw.totals, nw.list};
-    if ((rc = timed(c, st, 7, 0, [&]() -> int { HIP_TRY(c, launch_normal_list(la, st)); return NERF_OK; }))) return rc;
+    if ((rc = timed(c, st, EV_NORMAL_SMALL, 0, [&]() -> int { HIP_TRY(c, launch_normal_list(la, st)); return NERF_OK; }))) return rc;
     uint32_t totals[2] = {0, 0};
     HIP_TRY(c, hipMemcpyAsync(totals, nw.totals, sizeof totals, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
@@ -444,15 +440,15 @@ int normals_pass(nerf_ctx *c, const RenderJob &j, const Pass &p, const DevNet &n
     float *out = j.normals + 3 * p.r0;
     if (L == 0) { HIP_TRY(c, hipMemsetAsync(out, 0, (size_t)n_rays * 3 * sizeof(float), st)); return NERF_OK; }
     if (L > (size_t)n_rays * (size_t)n_comp) return fail(c, NERF_ERR_HIP, "normals: the live count exceeds the pass's samples");
-    if ((rc = ensure_bytes(c, &c->d_stencil, &c->stencil_bytes, 6 * L * 4 * sizeof(float)))) return rc;
-    float *d_spts = (float *)c->d_stencil, *d_ssig = d_spts + 18 * L;
+    if ((rc = c->buf[BUF_STENCIL].ensure(c, 6 * L * 4 * sizeof(float)))) return rc;
+    float *d_spts = c->dev(BUF_STENCIL), *d_ssig = d_spts + 18 * L;
     NormalStencilArgs sa{};
-    sa.n_live = (uint32_t)L; sa.h = j.h; sa.list = nw.list; sa.spr = n_comp; sa.origins = p.origins; sa.dirs = c->d_dirs; sa.t = t; sa.pts = d_spts;
+    sa.n_live = (uint32_t)L; sa.h = j.h; sa.list = nw.list; sa.spr = n_comp; sa.origins = p.origins; sa.dirs = c->dev(BUF_DIRS); sa.t = t; sa.pts = d_spts;
     if (!p.origins) copy3(sa.origin, j.origin);
-    if ((rc = timed(c, st, 7, 0, [&]() -> int { HIP_TRY(c, launch_normal_stencil(sa, st)); return NERF_OK; }))) return rc;
-    if ((rc = timed(c, st, 6, (uint64_t)(6 * L), [&]() -> int { HIP_TRY(c, launch_sigma_points(c, net, d_spts, 6 * L, d_ssig, st)); return NERF_OK; }))) return rc;
+    if ((rc = timed(c, st, EV_NORMAL_SMALL, 0, [&]() -> int { HIP_TRY(c, launch_normal_stencil(sa, st)); return NERF_OK; }))) return rc;
+    if ((rc = timed(c, st, EV_NORMAL_SIGMA, (uint64_t)(6 * L), [&]() -> int { HIP_TRY(c, launch_sigma_points(c, net, d_spts, 6 * L, d_ssig, st)); return NERF_OK; }))) return rc;
     NormalReduceArgs ra{n_rays, (uint32_t)L, nw.count, nw.base, nw.list, nw.w, d_spts, d_ssig, out};
-    return timed(c, st, 7, 0, [&]() -> int { HIP_TRY(c, launch_normal_reduce(ra, st)); return NERF_OK; });
+    return timed(c, st, EV_NORMAL_SMALL, 0, [&]() -> int { HIP_TRY(c, launch_normal_reduce(ra, st)); return NERF_OK; });
 }
 
 // The loop over passes: everything a render launches between its driver's allocations and its counters' read-back.
@@ -467,36 +463,36 @@ int render_passes(nerf_ctx *c, const RenderJob &j, uint32_t *n_passes) {
         Pass p{};
         p.index = passes; p.r0 = r0; p.n_rays = (int)std::min(j.pass_rays, j.n_rays - r0);
         if ((rc = prepare_rays(c, j, p))) return rc;
-        if ((rc = eval_net(c, j, p, NERF_NET_COARSE, j.dtype_coarse, j.nc, c->d_tc, c->d_sc, j.coarse_only ? c->d_rgbc : nullptr,
-                           j.coarse_only ? j.kind_colour : 0))) return rc;
+        if ((rc = eval_net(c, j, p, NERF_NET_COARSE, j.dtype_coarse, j.nc, c->dev(BUF_TC), c->dev(BUF_SC), j.coarse_only ? c->dev(BUF_RGBC) : nullptr,
+                           j.coarse_only ? j.kind_colour : EV_COARSE_MLP))) return rc;
         CompositeArgs ca{};
         ca.n_rays = p.n_rays; ca.far_ = j.far_; ca.far_per_ray = j.d_far; ca.out = j.out + 3 * r0;
         ca.depth = j.depth ? j.depth + r0 : nullptr; ca.opacity = j.opacity ? j.opacity + r0 : nullptr;
         if (j.background) { ca.use_bg = 1; copy3(ca.bg, j.background); }
         if (j.normals) ca.w_out = j.nw.w;
         if (j.coarse_only) {
-            ca.n = j.nc; ca.t = c->d_tc; ca.sigma = c->d_sc; ca.rgb = c->d_rgbc;
-            if ((rc = timed(c, st, 2, 0, [&]() -> int { HIP_TRY(c, launch_composite(ca, st)); return NERF_OK; }))) return rc;
-            if ((rc = normals_pass(c, j, p, NC, c->d_tc))) return rc;
+            ca.n = j.nc; ca.t = c->dev(BUF_TC); ca.sigma = c->dev(BUF_SC); ca.rgb = c->dev(BUF_RGBC);
+            if ((rc = timed(c, st, EV_OTHER, 0, [&]() -> int { HIP_TRY(c, launch_composite(ca, st)); return NERF_OK; }))) return rc;
+            if ((rc = normals_pass(c, j, p, NC, c->dev(BUF_TC)))) return rc;
             continue;
         }
-        const float *t_fine = c->d_tc;
+        const float *t_fine = c->dev(BUF_TC);
         if (j.nf > 0) {
             ResampleArgs ra{};
             ra.g = p.g; ra.n_rays = p.n_rays; ra.nc = j.nc; ra.nf = j.nf; ra.far_ = j.far_; ra.far_per_ray = j.d_far;
             ra.seed_lo = (uint32_t)j.seed; ra.seed_hi = (uint32_t)(j.seed >> 32);
-            ra.t_coarse = c->d_tc; ra.sigma_coarse = c->d_sc; ra.t_fine = c->d_tf;
+            ra.t_coarse = c->dev(BUF_TC); ra.sigma_coarse = c->dev(BUF_SC); ra.t_fine = c->dev(BUF_TF);
             ra.pixel_index = p.rng;
-            unsigned int *hctr = j.seq ? c->d_seq + 4 * (size_t)(3 * passes + 2) : nullptr;
-            if (j.hybrid) { ra.flag_tau = c->hybrid_tau; ra.flag_count = hctr + 1; ra.flag_list = c->d_flag_list; }
-            if ((rc = timed(c, st, 2, 0, [&]() -> int { HIP_TRY(c, launch_resample(ra, st)); return NERF_OK; }))) return rc;
+            SeqCounters *hctr = j.seq ? c->dev<SeqCounters>(BUF_SEQ) + (3 * (size_t)passes + 2) : nullptr;
+            if (j.hybrid) { ra.flag_tau = c->hybrid_tau; ra.flag_count = &hctr->live_count; ra.flag_list = c->dev<unsigned int>(BUF_FLAG_LIST); }
+            if ((rc = timed(c, st, EV_OTHER, 0, [&]() -> int { HIP_TRY(c, launch_resample(ra, st)); return NERF_OK; }))) return rc;
             if (j.hybrid && (rc = hybrid_redo(c, j, p, ra, hctr))) return rc;
-            t_fine = c->d_tf;
+            t_fine = c->dev(BUF_TF);
         }
         if (j.clock_out) c->clock_valid = true;
-        if ((rc = eval_net(c, j, p, NERF_NET_FINE, j.dtype, j.M, t_fine, c->d_sf, c->d_rgbf, j.kind_colour))) return rc;
-        ca.n = j.M; ca.t = t_fine; ca.sigma = c->d_sf; ca.rgb = c->d_rgbf;
-        if ((rc = timed(c, st, 2, 0, [&]() -> int { HIP_TRY(c, launch_composite(ca, st)); return NERF_OK; }))) return rc;
+        if ((rc = eval_net(c, j, p, NERF_NET_FINE, j.dtype, j.M, t_fine, c->dev(BUF_SF), c->dev(BUF_RGBF), j.kind_colour))) return rc;
+        ca.n = j.M; ca.t = t_fine; ca.sigma = c->dev(BUF_SF); ca.rgb = c->dev(BUF_RGBF);
+        if ((rc = timed(c, st, EV_OTHER, 0, [&]() -> int { HIP_TRY(c, launch_composite(ca, st)); return NERF_OK; }))) return rc;
         if ((rc = normals_pass(c, j, p, NF, t_fine))) return rc;
     }
     *n_passes = passes;
@@ -520,24 +516,25 @@ struct CertOutcome {
 // the audit's outcome decides whether this frame stands (render_device): certify_zero renders synchronise the stream
 int read_cert_outcome(nerf_ctx *c, const RenderJob &j, uint32_t passes, CertOutcome *cert) {
     HIP_TRY(c, hipStreamSynchronize(j.st));
-    std::vector<unsigned int> h((size_t)passes * 2 * kCertSlots);
-    HIP_TRY(c, hipMemcpy(h.data(), c->d_cert, h.size() * sizeof(unsigned int), hipMemcpyDeviceToHost));
+    std::vector<CertCounters> h((size_t)passes * 2);
+    HIP_TRY(c, hipMemcpy(h.data(), c->dev(BUF_CERT), h.size() * sizeof(CertCounters), hipMemcpyDeviceToHost));
     for (uint32_t k = 0; k < passes * 2; ++k) {
-        const unsigned int *q = &h[(size_t)k * kCertSlots];
+        const CertCounters &q = h[k];
         const int w = (int)(k & 1);
         if (w == 1 && j.coarse_only) continue;
         cert->used[w] = true;
-        cert->listed[w] += std::min<uint64_t>((uint64_t)q[0] + q[9], cert->list_capacity) + std::min<uint64_t>(q[1], cert->list_capacity);
-        cert->list_need = std::max<uint64_t>(cert->list_need, std::max<uint64_t>((uint64_t)q[0] + q[9], q[1]));
-        cert->audited[w] += q[2]; cert->violations[w] += q[3];
-        if (q[2]) {
-            const unsigned bits = 0x7f800000u - q[4];
+        const uint64_t list1 = (uint64_t)q.list1_len + q.list1_back_len;
+        cert->listed[w] += std::min<uint64_t>(list1, cert->list_capacity) + std::min<uint64_t>(q.list2_len, cert->list_capacity);
+        cert->list_need = std::max<uint64_t>(cert->list_need, std::max<uint64_t>(list1, q.list2_len));
+        cert->audited[w] += q.audited; cert->violations[w] += q.violations;
+        if (q.audited) {
+            const unsigned bits = 0x7f800000u - q.headroom_code;
             float hr, er;
-            memcpy(&hr, &bits, sizeof hr); memcpy(&er, &q[5], sizeof er);
+            memcpy(&hr, &bits, sizeof hr); memcpy(&er, &q.max_err_bits, sizeof er);
             cert->headroom[w] = std::min(cert->headroom[w], hr); cert->max_err[w] = std::max(cert->max_err[w], er);
         }
-        cert->fallback_rays += q[6];
-        cert->range_left[w] += q[12];
+        cert->fallback_rays += q.fallback_rays;
+        cert->range_left[w] += q.range_left;
     }
     return NERF_OK;
 }
@@ -555,12 +552,12 @@ int finish_stats(nerf_ctx *c, const RenderJob &j, uint32_t passes, nerf_stats *s
     for (const auto &p : c->last_render) {
         float ms = 0.f;
         HIP_TRY(c, hipEventElapsedTime(&ms, p.a, p.b));
-        if (p.kind == 0) { stats->ms_coarse_mlp += ms; stats->n_mlp_launches++; }
-        else if (p.kind == 1 || p.kind == 4 || p.kind == 5) { // the colour-producing launch; 4: colour head on the compacted live samples (skip_dead)
+        if (p.kind == EV_COARSE_MLP) { stats->ms_coarse_mlp += ms; stats->n_mlp_launches++; }
+        else if (p.kind == EV_IMAGE_COLOUR || p.kind == EV_COLOUR_SIDE || p.kind == EV_BATCH_COLOUR) { // the colour-producing launch and its side launches
             stats->n_mlp_launches++;
             if (j.coarse_only) stats->ms_coarse_mlp += ms; else stats->ms_fine_mlp += ms;
-        } else stats->ms_other += ms; // kinds 6 and 7 too: a normals render's own launches are neither network pass of the colour
-        if (p.kind == 6) ms_normal_sigma += ms; else if (p.kind == 7) ms_normal_small += ms;
+        } else stats->ms_other += ms; // EV_NORMAL_* too: a normals render's own launches are neither network pass of the colour
+        if (p.kind == EV_NORMAL_SIGMA) ms_normal_sigma += ms; else if (p.kind == EV_NORMAL_SMALL) ms_normal_small += ms;
     }
     if (!c->last_render.empty()) {
         float ms = 0.f;
@@ -597,15 +594,13 @@ int finish_stats(nerf_ctx *c, const RenderJob &j, uint32_t passes, nerf_stats *s
         for (int w = 0; w < 2; ++w) { stats->certify_margin[w] = c->cert_margin[w]; stats->certify_headroom[w] = cert->headroom[w]; stats->certify_max_error[w] = cert->max_err[w]; }
     }
     if (j.seq) {
-        std::vector<unsigned int> h((size_t)passes * 3 * 4);
-        HIP_TRY(c, hipMemcpy(h.data(), c->d_seq, h.size() * sizeof(unsigned int), hipMemcpyDeviceToHost));
+        std::vector<SeqCounters> h((size_t)passes * 3);
+        HIP_TRY(c, hipMemcpy(h.data(), c->dev(BUF_SEQ), h.size() * sizeof(SeqCounters), hipMemcpyDeviceToHost));
         uint64_t evaluated[3] = {0, 0, 0}, live = 0; // samples the trunk launches evaluated (a ray's last chunk may be partial)
         for (uint32_t k = 0; k < passes * 3; ++k) {
-            unsigned long long ch64;
-            memcpy(&ch64, &h[4 * (size_t)k + 2], sizeof ch64);
-            evaluated[k % 3] += ch64;
-            if (k % 3 == 2) stats->n_hybrid_rays += h[4 * (size_t)k + 1]; // flagged rays redone in f32
-            else live += h[4 * (size_t)k + 1];
+            evaluated[k % 3] += h[k].evaluated;
+            if (k % 3 == 2) stats->n_hybrid_rays += h[k].live_count; // flagged rays redone in f32
+            else live += h[k].live_count;
         }
         stats->n_exec_coarse_trunk = evaluated[0] + evaluated[2];
         stats->n_exec_fine_trunk = j.coarse_only ? 0 : evaluated[1];
@@ -667,7 +662,7 @@ int export_budget(nerf_ctx *c, const RenderJob &j, int RW, size_t *pass_cap) {
     const size_t h8_sample_bytes = j.dtype == NERF_MLP_BF16 ? 512 : 1024;
     size_t budget = c->max_export_bytes, free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) // never more than half of what the device can still give (plus what we already hold)
-        budget = std::min(budget, (free_b + c->h8_bytes) / 2);
+        budget = std::min(budget, (free_b + c->buf[BUF_H8].bytes) / 2);
     const size_t row_bytes = (size_t)RW * j.M * h8_sample_bytes;
     if (row_bytes > budget) {
         char msg[256];
@@ -680,30 +675,22 @@ int export_budget(nerf_ctx *c, const RenderJob &j, int RW, size_t *pass_cap) {
     return NERF_OK;
 }
 
-// skip_dead: the counters, per MLP launch {u32 ray queue head, u32 live-sample count, u64 evaluated samples}, cleared; the export buffer (which
-// releases h8_lock); the hybrid redo's ray list
+// skip_dead: the counters, one SeqCounters per MLP launch, cleared; the export buffer (which releases h8_lock); the hybrid redo's ray list
 int reserve_seq(nerf_ctx *c, const RenderJob &j, size_t n_passes, std::unique_lock<std::mutex> &h8_lock) {
     int rc;
     const size_t slots = n_passes * 3; // per pass: coarse, fine, hybrid f32 redo of the coarse pass
-    if (slots > c->seq_slots) {
-        size_t bytes = c->seq_slots * 16;
-        if ((rc = ensure_bytes(c, (void **)&c->d_seq, &bytes, slots * 16))) return rc;
-        c->seq_slots = slots;
-    }
-    HIP_TRY(c, hipMemsetAsync(c->d_seq, 0, slots * 16, j.st));
+    if ((rc = c->buf[BUF_SEQ].ensure(c, slots * sizeof(SeqCounters)))) return rc;
+    HIP_TRY(c, hipMemsetAsync(c->dev(BUF_SEQ), 0, slots * sizeof(SeqCounters), j.st));
     const size_t pass_samples = j.pass_rays * (size_t)j.M;
     if (exports_h8(j)) {
         const size_t need = j.dtype == NERF_MLP_BF16 ? nerf_seq_h8_bytes_bf16(pass_samples) : nerf_seq_h8_bytes(pass_samples);
-        if (c->d_h8 && need < c->h8_bytes / 4) { // a much smaller render: give the big buffer back
-            HIP_TRY(c, hipDeviceSynchronize());
-            HIP_TRY(c, hipFree(c->d_h8));
-            c->d_h8 = nullptr; c->h8_bytes = 0;
-        }
-        if ((rc = ensure_bytes(c, (void **)&c->d_h8, &c->h8_bytes, need))) return rc;
-        if ((rc = ensure_bytes(c, (void **)&c->d_slot_point, &c->slot_point_bytes, (pass_samples + 256) * sizeof(unsigned int)))) return rc;
+        DevBuf &h8 = c->buf[BUF_H8];
+        if (need < h8.bytes / 4 && (rc = h8.release(c))) return rc; // a much smaller render: give the big buffer back
+        if ((rc = h8.ensure(c, need))) return rc;
+        if ((rc = c->buf[BUF_SLOT_POINT].ensure(c, (pass_samples + 256) * sizeof(unsigned int)))) return rc;
         h8_lock.unlock();
     }
-    if (j.hybrid && (rc = ensure_bytes(c, (void **)&c->d_flag_list, &c->flag_list_bytes, j.pass_rays * sizeof(unsigned int)))) return rc;
+    if (j.hybrid && (rc = c->buf[BUF_FLAG_LIST].ensure(c, j.pass_rays * sizeof(unsigned int)))) return rc;
     return NERF_OK;
 }
 
@@ -716,13 +703,13 @@ int reserve_certify(nerf_ctx *c, RenderJob &j, size_t n_pass, CertOutcome *cert)
     // beyond the capacity are counted, not stored, and render_device renders the frame again with a list that fits
     // (up to 64 MiB the list simply holds every sample: small renders -- a central crop lists 70 % of its samples -- never take that path)
     j.cert_cap = pass_samples <= ((size_t)16 << 20) ? pass_samples : std::min<size_t>(pass_samples, (size_t)((double)pass_samples * c->cert_list_frac) + 4096);
-    if ((rc = ensure_bytes(c, (void **)&c->d_point_list, &c->point_list_bytes, j.cert_cap * sizeof(unsigned int)))) return rc;
-    j.cert_cap = std::min<size_t>(pass_samples, c->point_list_bytes / sizeof(unsigned int)); // an earlier, larger allocation is kept
-    if ((rc = ensure_bytes(c, (void **)&c->d_jstar, &c->jstar_bytes, j.pass_rays * sizeof(int)))) return rc;
+    if ((rc = c->buf[BUF_POINT_LIST].ensure(c, j.cert_cap * sizeof(unsigned int)))) return rc;
+    j.cert_cap = std::min<size_t>(pass_samples, c->buf[BUF_POINT_LIST].bytes / sizeof(unsigned int)); // an earlier, larger allocation is kept
+    if ((rc = c->buf[BUF_JSTAR].ensure(c, j.pass_rays * sizeof(int)))) return rc;
     j.aux_cap = 2 * (pass_samples / ((size_t)std::min(c->cert_audit_mask, c->cert_audit_mask_near) + 1)) + 4096; // more than the audit can select: a certificate that does not fit is not audited
-    if ((rc = ensure_bytes(c, (void **)&c->d_cert_aux, &c->cert_aux_bytes, j.aux_cap * 2 * sizeof(unsigned int)))) return rc;
-    if ((rc = ensure_bytes(c, (void **)&c->d_cert, &c->cert_bytes, kCertSlots * 2 * n_pass * sizeof(unsigned int)))) return rc;
-    HIP_TRY(c, hipMemsetAsync(c->d_cert, 0, kCertSlots * 2 * n_pass * sizeof(unsigned int), j.st));
+    if ((rc = c->buf[BUF_CERT_AUX].ensure(c, j.aux_cap * 2 * sizeof(unsigned int)))) return rc;
+    if ((rc = c->buf[BUF_CERT].ensure(c, 2 * n_pass * sizeof(CertCounters)))) return rc;
+    HIP_TRY(c, hipMemsetAsync(c->dev(BUF_CERT), 0, 2 * n_pass * sizeof(CertCounters), j.st));
     if (cert) { cert->list_capacity = j.cert_cap; cert->pass_samples = pass_samples; }
     return NERF_OK;
 }
@@ -743,7 +730,7 @@ int render_once(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *o, 
     RenderJob j{};
     plan_job(c, o, j);
     j.near_ = cam->near_; j.far_ = cam->far_; j.far_cert = j.far_; j.background = background;
-    j.kind_colour = 1; j.what = "frame"; j.st = st;
+    j.kind_colour = EV_IMAGE_COLOUR; j.what = "frame"; j.st = st;
     j.skip_empty = o->skip_empty; j.seq = o->skip_dead != 0; j.certify = o->certify_zero != 0;
     j.hybrid = o->hybrid_sampling != 0 && j.nf > 0; // without resampling there is nothing to protect
     j.clock_out = c->d_clock; // NULL unless NERF_DEBUG_CLOCK=1
@@ -765,12 +752,12 @@ int render_once(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *o, 
     if ((rc = ensure_workspace(c, j.pass_rays, j.nc, j.M, j.coarse_only))) return rc;
     j.out = d_out; j.depth = d_depth; j.opacity = d_opacity;
     if (s > 1) {
-        if ((rc = ensure_bytes(c, (void **)&c->d_rayfb, &c->rayfb_floats, (size_t)RW * RH * 3 * sizeof(float)))) return rc;
-        j.out = c->d_rayfb;
+        if ((rc = c->buf[BUF_RAYFB].ensure(c, (size_t)RW * RH * 3 * sizeof(float)))) return rc;
+        j.out = c->dev(BUF_RAYFB);
         if (d_depth || d_opacity) { // ray-level maps, one plane each, box-filtered like the colour below
-            if ((rc = ensure_bytes(c, (void **)&c->d_rayaux, &c->rayaux_bytes, (size_t)RW * RH * 2 * sizeof(float)))) return rc;
-            j.depth = d_depth ? c->d_rayaux : nullptr;
-            j.opacity = d_opacity ? c->d_rayaux + (size_t)RW * RH : nullptr;
+            if ((rc = c->buf[BUF_RAYAUX].ensure(c, (size_t)RW * RH * 2 * sizeof(float)))) return rc;
+            j.depth = d_depth ? c->dev(BUF_RAYAUX) : nullptr;
+            j.opacity = d_opacity ? c->dev(BUF_RAYAUX) + (size_t)RW * RH : nullptr;
         }
     }
     const size_t n_passes_total = ((size_t)RH + rows_per_pass - 1) / rows_per_pass;
@@ -778,27 +765,21 @@ int render_once(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *o, 
     if (j.certify && (rc = reserve_certify(c, j, n_passes_total, cert))) return rc;
     recycle_render(c);
     recycle_dominant(c, 4096); // bound the backlog if the caller never queries
-    // If this render returns early (a launch failed), its dominant-kernel event pairs never reach c->dominant: hand them back
-    // to last_render's ownership so that the next recycle_render returns them to the pool.
-    struct RenderScope {
-        nerf_ctx *c; bool ok = false;
-        ~RenderScope() { if (!ok) for (auto &p : c->last_render) if (p.kind == 1) p.kind = 2; }
-    } scope{c};
     j.g = make_raygen(*cam, s);
     j.g.rx0 = RX0; j.g.rw = RW; j.g.ry0 = w.stripe > 0 ? 0 : RY0;
     if (w.stripe > 0) { j.g.stripe = w.stripe * s; j.g.stripe_n = o->band_count; j.g.stripe_i = o->band_index; j.g.stripe_y0 = RY0; }
     uint32_t passes = 0;
     if ((rc = render_passes(c, j, &passes))) return rc;
-    if (s > 1 && (rc = timed(c, st, 2, 0, [&]() -> int {
-            HIP_TRY(c, launch_box_downsample(c->d_rayfb, d_out, w.cw, w.ch, s, 3, st));
+    if (s > 1 && (rc = timed(c, st, EV_OTHER, 0, [&]() -> int {
+            HIP_TRY(c, launch_box_downsample(c->dev(BUF_RAYFB), d_out, w.cw, w.ch, s, 3, st));
             if (d_depth) HIP_TRY(c, launch_box_downsample(j.depth, d_depth, w.cw, w.ch, s, 1, st));
             if (d_opacity) HIP_TRY(c, launch_box_downsample(j.opacity, d_opacity, w.cw, w.ch, s, 1, st));
             return NERF_OK;
         }))) return rc;
-    // the dominant-kernel events also feed nerf_kernel_time_query (ownership: see recycle_render)
-    for (const auto &p : c->last_render)
-        if (p.kind == 1) c->dominant.push_back(p);
-    scope.ok = true;
+    // the dominant-kernel events also feed nerf_kernel_time_query: from here on c->dominant owns them (a render that returned early above
+    // never gets here, and the next recycle_render returns its pairs to the pool with the others)
+    for (auto &p : c->last_render)
+        if (p.kind == EV_IMAGE_COLOUR) { p.dominant = true; c->dominant.push_back(p); }
     if (cert && (rc = read_cert_outcome(c, j, passes, cert))) return rc;
     return finish_stats(c, j, passes, stats, cert);
 }
@@ -806,91 +787,91 @@ int render_once(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *o, 
 // ---- ray batches (nerf_render_rays) -------------------------------------------------------------------------------------
 // What the header's contract needs beside render_once: the rays are the caller's, so there is no camera, no window and none of the modes
 // tied to either; a pass is at most max_rays_per_pass rays (rays * samples <= 0x3fffffff, as above).
-// arguments already checked (check_ray_batch, check_normals); asynchronous on st unless stats != NULL or d_normals != NULL (n_rays x 3: the
-// compositing launch then also hands out its weights, and normals_pass follows it in every pass).
-// cert != NULL: one attempt at a certified batch (nerf_render_rays_certified; certify_retry decides whether it stands) -- zero certification
-// inside every pass, per-ray origins as ray_origins of the certified kernels (no expansion, no 24-byte-per-sample workspace); synchronises
-// st, because the audit is read on the host.
-int render_rays_device(nerf_ctx *c, const RayBatch &b, const nerf_render_opts *o, const float *background, float *d_out, float *d_depth,
-                       float *d_opacity, hipStream_t st, nerf_stats *stats, float h = 0.0f, float *d_normals = nullptr, CertOutcome *cert = nullptr) {
+// q: a device request, already checked (check_request), with h_origin set when n_origins == 1; asynchronous on q.st unless q.stats or
+// q.want_normals (normals: n_rays x 3; the compositing launch then also hands out its weights, and normals_pass follows it in every pass).
+// cert != NULL: one attempt at a certified batch (run_rays' retry loop decides whether it stands) -- zero certification inside every pass,
+// per-ray origins as ray_origins of the certified kernels (no expansion, no 24-byte-per-sample workspace); synchronises q.st, because the
+// audit is read on the host.
+int render_rays_device(nerf_ctx *c, const RayRequest &q, CertOutcome *cert) {
     int rc;
-    if ((rc = check_sample_plan(c, o, PLAN_NETWORKS))) return rc;
+    if ((rc = check_sample_plan(c, q.opts, PLAN_NETWORKS))) return rc;
     RenderJob j{};
-    plan_job(c, o, j);
-    j.near_ = b.near_; j.far_ = b.far_; j.background = background;
-    j.out = d_out; j.depth = d_depth; j.opacity = d_opacity;
-    // events: all owned by last_render (kind 5, not 1, for the colour-producing network: c->dominant and with it nerf_kernel_time_query
+    plan_job(c, q.opts, j);
+    j.near_ = q.near_; j.far_ = q.far_; j.background = q.background;
+    j.out = q.rgb; j.depth = q.depth; j.opacity = q.opacity;
+    // events: all owned by last_render (EV_BATCH_COLOUR for the colour-producing network: c->dominant and with it nerf_kernel_time_query
     // belong to image renders)
-    j.kind_colour = 5; j.what = "batch"; j.st = st;
-    j.batch = &b; j.normals = d_normals; j.h = h;
+    j.kind_colour = EV_BATCH_COLOUR; j.what = "batch"; j.st = q.st;
+    j.batch = &q; j.normals = q.want_normals ? q.normals : nullptr; j.h = q.h;
     j.certify = cert != nullptr;
     // per-ray bounds: a finite far below every t -- the certify kernels' interval behind the last sample is clamped to 0 (cert_pass)
-    j.far_cert = b.d_bounds ? -3.0e38f : b.far_;
+    j.far_cert = q.bounds ? -3.0e38f : q.far_;
     size_t pass_cap = pass_capacity(c, j.M);
     // normals: if every sample of a pass were live its 6 stencil points each must still fit one MLP launch
-    if (d_normals) pass_cap = std::max<size_t>(1, std::min<size_t>(pass_cap, max_batch_points(c->n_cus) / (6 * (size_t)j.M)));
-    j.n_rays = b.n_rays; j.pass_rays = std::min(b.n_rays, pass_cap);
+    if (j.normals) pass_cap = std::max<size_t>(1, std::min<size_t>(pass_cap, max_batch_points(c->n_cus) / (6 * (size_t)j.M)));
+    j.n_rays = q.n_rays; j.pass_rays = std::min(q.n_rays, pass_cap);
     if ((rc = ensure_workspace(c, j.pass_rays, j.nc, j.M, j.coarse_only))) return rc;
     j.n_comp = j.coarse_only ? j.nc : j.M;
-    if (d_normals && (rc = ensure_bytes(c, &c->d_normal, &c->normal_bytes, NormalWorkspace::bytes(j.pass_rays, j.pass_rays * (size_t)j.n_comp)))) return rc;
-    j.nw = NormalWorkspace(c->d_normal, j.pass_rays, j.pass_rays * (size_t)j.n_comp);
+    const size_t n_comp_max = j.pass_rays * (size_t)j.n_comp;
+    if (j.normals && (rc = c->buf[BUF_NORMAL].ensure(c, NormalWorkspace(nullptr, j.pass_rays, n_comp_max).bytes))) return rc;
+    j.nw = NormalWorkspace(c->buf[BUF_NORMAL].p, j.pass_rays, n_comp_max);
     c->normal_live = 0; c->normal_samples = 0;
-    // c->d_batch (floats): [far per ray, padded to 64][points 3 x n SoA][directions n x 3 AoS], n = the pass's rays x M
-    const bool expand = b.d_origins != nullptr && !j.certify;
-    const size_t far_floats = b.d_bounds ? (j.pass_rays + 63) / 64 * 64 : 0, n_max = j.pass_rays * (size_t)j.M;
+    // BUF_BATCH (floats): [far per ray, padded to 64][points 3 x n SoA][directions n x 3 AoS], n = the pass's rays x M
+    const bool expand = q.n_origins != 1 && !j.certify;
+    const size_t far_floats = q.bounds ? (j.pass_rays + 63) / 64 * 64 : 0, n_max = j.pass_rays * (size_t)j.M;
     if (far_floats || expand) {
-        if ((rc = ensure_bytes(c, &c->d_batch, &c->batch_bytes, (far_floats + (expand ? 6 * n_max : 0)) * sizeof(float)))) return rc;
-        j.d_far = b.d_bounds ? (float *)c->d_batch : nullptr;
-        j.d_pts = (float *)c->d_batch + far_floats; j.d_daos = j.d_pts + 3 * n_max;
+        if ((rc = c->buf[BUF_BATCH].ensure(c, (far_floats + (expand ? 6 * n_max : 0)) * sizeof(float)))) return rc;
+        j.d_far = q.bounds ? c->dev(BUF_BATCH) : nullptr;
+        j.d_pts = c->dev(BUF_BATCH) + far_floats; j.d_daos = j.d_pts + 3 * n_max;
     }
-    if (b.h_origin) copy3(j.origin, b.h_origin);
+    if (q.h_origin) copy3(j.origin, q.h_origin);
     if (j.certify && (rc = reserve_certify(c, j, (j.n_rays + j.pass_rays - 1) / j.pass_rays, cert))) return rc;
     recycle_render(c);
     uint32_t passes = 0;
     if ((rc = render_passes(c, j, &passes))) return rc;
     if (cert && (rc = read_cert_outcome(c, j, passes, cert))) return rc;
-    return finish_stats(c, j, passes, stats, cert);
+    return finish_stats(c, j, passes, q.stats, cert);
 }
 
 // everything nerf_render_rays* can refuse without a context or a device, in the header's order
-// certified: the nerf_render_rays*_certified forms -- the entry point is the switch, opts->certify_zero is only checked for its range
-int check_ray_batch(nerf_ctx *c, const void *origins, size_t n_origins, const void *dirs, size_t n_rays, float near_, float far_, const void *bounds,
-                    const nerf_render_opts *o, const float *background, const void *rgb_out, bool certified = false) {
+// q.certified: the nerf_render_rays*_certified forms -- the entry point is the switch, opts->certify_zero is only checked for its range
+int check_ray_batch(nerf_ctx *c, const RayRequest &q) {
+    const nerf_render_opts *o = q.opts;
     if (!o) return fail(c, NERF_ERR_INVALID, "opts is NULL");
-    if (n_rays > (size_t)0x7fffffff) return fail(c, NERF_ERR_INVALID, "n_rays must be at most INT32_MAX");
-    if (n_rays > 0 && (!origins || !dirs || !rgb_out)) return fail(c, NERF_ERR_INVALID, "origins, dirs and rgb_out must not be NULL");
-    if (n_origins != 1 && n_origins != n_rays) return fail(c, NERF_ERR_INVALID, "n_origins must be 1 (one origin for every ray) or n_rays");
+    if (q.n_rays > (size_t)0x7fffffff) return fail(c, NERF_ERR_INVALID, "n_rays must be at most INT32_MAX");
+    if (q.n_rays > 0 && (!q.origins || !q.dirs || !q.rgb)) return fail(c, NERF_ERR_INVALID, "origins, dirs and rgb_out must not be NULL");
+    if (q.n_origins != 1 && q.n_origins != q.n_rays) return fail(c, NERF_ERR_INVALID, "n_origins must be 1 (one origin for every ray) or n_rays");
     if (o->crop_x0 || o->crop_y0 || o->crop_w || o->crop_h) return fail(c, NERF_ERR_INVALID, "ray batches have no pixel grid: crop_* must be 0");
     if (o->ssaa > 1) return fail(c, NERF_ERR_INVALID, "ray batches have no pixel grid: ssaa must be 0 or 1");
     if (o->band_count > 1) return fail(c, NERF_ERR_INVALID, "ray batches have no rows: band_count must be 0 or 1");
-    if (o->skip_empty || o->skip_dead || o->hybrid_sampling || (o->certify_zero && !certified))
+    if (o->skip_empty || o->skip_dead || o->hybrid_sampling || (o->certify_zero && !q.certified))
         return fail(c, NERF_ERR_INVALID, "skip_empty, skip_dead, hybrid_sampling and certify_zero are not available for ray batches (first version)");
     if (o->certify_zero != 0 && o->certify_zero != 1) return fail(c, NERF_ERR_INVALID, "certify_zero must be 0 or 1");
     int rc;
     if ((rc = check_sample_plan(c, o, PLAN_COUNTS))) return rc;
-    if (certified && o->mlp_dtype == NERF_MLP_BF16) // the image path's refusal (check_image_modes)
+    if (q.certified && o->mlp_dtype == NERF_MLP_BF16) // the image path's refusal (check_image_modes)
         return fail(c, NERF_ERR_INVALID, "certify_zero needs mlp_dtype F32, BF16X3 or F16X2 and neither skip_empty nor skip_dead");
-    if (!bounds) {
-        if (!std::isfinite(near_) || !std::isfinite(far_)) return fail(c, NERF_ERR_INVALID, "near_ and far_ must be finite when bounds is NULL");
-        if (!(far_ > near_)) return fail(c, NERF_ERR_INVALID, "far_ must be greater than near_ when bounds is NULL");
+    if (!q.bounds) {
+        if (!std::isfinite(q.near_) || !std::isfinite(q.far_)) return fail(c, NERF_ERR_INVALID, "near_ and far_ must be finite when bounds is NULL");
+        if (!(q.far_ > q.near_)) return fail(c, NERF_ERR_INVALID, "far_ must be greater than near_ when bounds is NULL");
     }
-    if (background && !(std::isfinite(background[0]) && std::isfinite(background[1]) && std::isfinite(background[2])))
+    if (q.background && !(std::isfinite(q.background[0]) && std::isfinite(q.background[1]) && std::isfinite(q.background[2])))
         return fail(c, NERF_ERR_INVALID, "background components must be finite");
     return check_sample_plan(c, o, PLAN_LIMITS);
 }
 
-// the host entry point's per-ray checks: the first offending ray is named
-int check_ray_batch_rays(nerf_ctx *c, const float *origins, size_t n_origins, const float *dirs, size_t n_rays, int normalize, const float *bounds) {
+// the host entry points' per-ray checks: the first offending ray is named
+int check_ray_batch_rays(nerf_ctx *c, const RayRequest &q) {
     char msg[160];
     auto finite3 = [](const float *v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); };
-    for (size_t r = 0; r < n_rays; ++r) {
+    for (size_t r = 0; r < q.n_rays; ++r) {
         const char *what = nullptr;
-        const float *d = dirs + 3 * r;
-        if (r < n_origins && !finite3(origins + 3 * r)) what = "its origin is not finite";
+        const float *d = q.dirs + 3 * r, *b = q.bounds ? q.bounds + 2 * r : nullptr;
+        if (r < q.n_origins && !finite3(q.origins + 3 * r)) what = "its origin is not finite";
         else if (!finite3(d)) what = "its direction is not finite";
-        else if (normalize && d[0] == 0.0f && d[1] == 0.0f && d[2] == 0.0f) what = "its direction is zero and cannot be normalised";
-        else if (bounds && !(std::isfinite(bounds[2 * r]) && std::isfinite(bounds[2 * r + 1]))) what = "its bounds are not finite";
-        else if (bounds && !(bounds[2 * r + 1] > bounds[2 * r])) what = "its far is not greater than its near";
+        else if (q.normalize && d[0] == 0.0f && d[1] == 0.0f && d[2] == 0.0f) what = "its direction is zero and cannot be normalised";
+        else if (b && !(std::isfinite(b[0]) && std::isfinite(b[1]))) what = "its bounds are not finite";
+        else if (b && !(b[1] > b[0])) what = "its far is not greater than its near";
         if (what) {
             snprintf(msg, sizeof msg, "ray %zu: %s", r, what);
             return fail(c, NERF_ERR_INVALID, msg);
@@ -900,9 +881,29 @@ int check_ray_batch_rays(nerf_ctx *c, const float *origins, size_t n_origins, co
 }
 
 // what nerf_render_rays_normals* adds to check_ray_batch
-int check_normals(nerf_ctx *c, float h, const void *normals_out) {
-    if (!(std::isfinite(h) && h > 0.0f)) return fail(c, NERF_ERR_INVALID, "h (the central-difference step) must be finite and greater than 0");
-    if (!normals_out) return fail(c, NERF_ERR_INVALID, "normals_out must not be NULL");
+int check_normals(nerf_ctx *c, const RayRequest &q) {
+    if (!(std::isfinite(q.h) && q.h > 0.0f)) return fail(c, NERF_ERR_INVALID, "h (the central-difference step) must be finite and greater than 0");
+    if (!q.normals) return fail(c, NERF_ERR_INVALID, "normals_out must not be NULL");
+    return NERF_OK;
+}
+
+// what nerf_render_rays_clipped* refuses without a context or a device: nerf_render_rays' refusals, then the grid's
+int check_rays_clipped(nerf_ctx *c, const RayRequest &q) {
+    int rc;
+    if ((rc = check_ray_batch(c, q))) return rc;
+    if (const char *why = nerfclip::check_grid(q.occ_bits, q.lo, q.step, q.dims)) return fail(c, NERF_ERR_INVALID, why);
+    return NERF_OK;
+}
+
+// Everything one of the ten entry points refuses before it touches the device, in the header's order; host: the arrays are host memory,
+// so their rays are checked one by one.  "ctx is NULL" comes last, and *n_hit is cleared behind it (before the n_rays == 0 return).
+int check_request(nerf_ctx *c, const RayRequest &q, bool host) {
+    int rc;
+    if ((rc = q.clipped ? check_rays_clipped(c, q) : check_ray_batch(c, q))) return rc;
+    if (q.want_normals && (rc = check_normals(c, q))) return rc;
+    if (host && (rc = check_ray_batch_rays(c, q))) return rc;
+    if (!c) return fail(nullptr, NERF_ERR_INVALID, "ctx is NULL");
+    if (q.clipped && q.n_hit) *q.n_hit = 0;
     return NERF_OK;
 }
 
@@ -913,7 +914,7 @@ int check_normals(nerf_ctx *c, float h, const void *normals_out) {
 // measurements, not proofs: what this buys is that a network on which bf16 is less accurate than on the lego scene
 // calibrates itself or fails loudly (NERF_ERR_STATE) instead of returning a silently different frame.
 // Every attempt writes the whole frame -- colour and the requested maps -- so the maps returned are those of the frame that stands.
-// One copy for image renders (render_device) and certified ray batches (rays_certified_device, rays_clipped_device): attempt(&outcome)
+// One copy for image renders (render_device) and certified ray batches (run_rays): attempt(&outcome)
 // renders the whole frame / batch once; what = "frame" / "batch".
 template <class Attempt>
 int certify_retry(nerf_ctx *c, nerf_stats *stats, const char *what, Attempt attempt) {
@@ -999,8 +1000,8 @@ int nerfint::render_rgba8_device(nerf_ctx *c, const nerf_camera *cam, const nerf
     size_t w = 0, h = 0;
     if ((rc = output_window(c, cam, o, &w, &h))) return rc;
     const size_t px = w * h, op_at = align4(3 * px);
-    if ((rc = ensure_bytes(c, (void **)&c->d_pack, &c->pack_bytes, (op_at + px) * sizeof(float)))) return rc;
-    float *d_rgb = c->d_pack, *d_opacity = alpha_mode == NERF_ALPHA_OPAQUE ? nullptr : c->d_pack + op_at;
+    if ((rc = c->buf[BUF_PACK].ensure(c, (op_at + px) * sizeof(float)))) return rc;
+    float *d_rgb = c->dev(BUF_PACK), *d_opacity = alpha_mode == NERF_ALPHA_OPAQUE ? nullptr : d_rgb + op_at;
     if ((rc = render_device(c, cam, o, d_rgb, nullptr, d_opacity, st, stats, bg))) return rc;
     HIP_TRY(c, launch_pack_rgba8(d_rgb, d_opacity, (uint32_t *)d_rgba, px, alpha_mode, st));
     if (stats) HIP_TRY(c, hipStreamSynchronize(st)); // as the float variant: with stats the output is complete on return
@@ -1030,18 +1031,14 @@ int nerf_render_image_aux(nerf_ctx *c, const nerf_camera *cam, const nerf_render
     if ((rc = output_window(c, cam, opts, &w, &h))) return rc;
     DeviceGuard dg(c->device);
     // staging: the colour, then each requested map (w x h floats)
-    const size_t px = w * h, bytes = px * 3 * sizeof(float);
-    const size_t maps = (depth_out ? 1 : 0) + (opacity_out ? 1 : 0);
-    if ((rc = ensure_bytes(c, (void **)&c->d_out, &c->out_floats, bytes + maps * px * sizeof(float)))) return rc;
-    float *d_depth = depth_out ? c->d_out + 3 * px : nullptr;
-    float *d_opacity = opacity_out ? c->d_out + (3 + (depth_out ? 1 : 0)) * px : nullptr;
+    const size_t px = w * h;
+    Staging s(c, BUF_OUT, c->stream);
+    const int i_rgb = s.add(sizeof(float), 3 * px, nullptr, rgb_out), i_depth = s.opt(depth_out, sizeof(float), px, nullptr, depth_out),
+              i_opacity = s.opt(opacity_out, sizeof(float), px, nullptr, opacity_out);
+    if ((rc = s.begin())) return rc;
     nerf_stats local; // a synchronous render always reads its counters: a frame computed outside a split arithmetic's range is an error
-    if ((rc = render_device(c, cam, opts, c->d_out, d_depth, d_opacity, c->stream, stats ? stats : &local))) return rc;
-    HIP_TRY(c, hipMemcpyAsync(rgb_out, c->d_out, bytes, hipMemcpyDeviceToHost, c->stream));
-    if (d_depth) HIP_TRY(c, hipMemcpyAsync(depth_out, d_depth, px * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (d_opacity) HIP_TRY(c, hipMemcpyAsync(opacity_out, d_opacity, px * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return NERF_OK;
+    if ((rc = render_device(c, cam, opts, s.at(i_rgb), s.at(i_depth), s.at(i_opacity), c->stream, stats ? stats : &local))) return rc;
+    return s.finish();
 } NERF_CATCH(c)
 
 int nerf_render_image(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *opts, float *rgb_out, nerf_stats *stats) {
@@ -1064,235 +1061,197 @@ int nerf_render_image_rgba8(nerf_ctx *c, const nerf_camera *cam, const nerf_rend
     size_t w = 0, h = 0;
     if ((rc = output_window(c, cam, opts, &w, &h))) return rc;
     DeviceGuard dg(c->device);
-    const size_t bytes = w * h * 4; // 4 bytes per pixel come back instead of 12 (16 with the opacity)
-    if ((rc = ensure_bytes(c, (void **)&c->d_out, &c->out_floats, bytes))) return rc;
+    Staging s(c, BUF_OUT, c->stream); // 4 bytes per pixel come back instead of 12 (16 with the opacity)
+    const int i_rgba = s.add(4, w * h, nullptr, rgba_out);
+    if ((rc = s.begin())) return rc;
     nerf_stats local; // a synchronous render always reads its counters (see nerf_render_image_aux)
-    if ((rc = render_rgba8_device(c, cam, opts, background, alpha_mode, (uint8_t *)c->d_out, c->stream, stats ? stats : &local))) return rc;
-    HIP_TRY(c, hipMemcpyAsync(rgba_out, c->d_out, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return NERF_OK;
+    if ((rc = render_rgba8_device(c, cam, opts, background, alpha_mode, s.at<uint8_t>(i_rgba), c->stream, stats ? stats : &local))) return rc;
+    return s.finish();
 } NERF_CATCH(c)
 
 // ---- ray batches ---------------------------------------------------------------------------------------------------------------------
-// nerf_render_rays_device, nerf_render_rays_normals_device (want_normals) and nerf_render_rays_certified_device (certified)
-static int rays_device(nerf_ctx *c, const float *d_origins, size_t n_origins, const float *d_dirs, size_t n_rays, int normalize, float near_,
-                       float far_, const float *d_bounds, const uint32_t *d_rng_index, const nerf_render_opts *opts, const float background[3],
-                       float *d_rgb_out, float *d_depth_out, float *d_opacity_out, bool want_normals, float h, float *d_normals_out, void *stream,
-                       nerf_stats *stats, bool certified = false) {
-    int rc;
-    if ((rc = check_ray_batch(c, d_origins, n_origins, d_dirs, n_rays, near_, far_, d_bounds, opts, background, d_rgb_out, certified))) return rc;
-    if (want_normals && (rc = check_normals(c, h, d_normals_out))) return rc;
-    if (!c) return fail(nullptr, NERF_ERR_INVALID, "ctx is NULL");
-    if (n_rays == 0) return NERF_OK;
-    DeviceGuard dg(c->device);
-    const hipStream_t st = (hipStream_t)stream;
-    RayBatch b{nullptr, nullptr, d_dirs, n_rays, normalize ? 1 : 0, near_, far_, d_bounds, d_rng_index};
-    float origin[3];
-    if (n_origins == 1) { // the shared origin rides in the MLP kernels' arguments: 12 bytes come back first
-        HIP_TRY(c, hipMemcpyAsync(origin, d_origins, sizeof origin, hipMemcpyDeviceToHost, st));
-        HIP_TRY(c, hipStreamSynchronize(st));
-        b.h_origin = origin;
-    } else b.d_origins = d_origins;
-    if (certified) // a retry renders the batch again
-        return certify_retry(c, stats, "batch", [&](CertOutcome *oc) {
-            return render_rays_device(c, b, opts, background, d_rgb_out, d_depth_out, d_opacity_out, st, stats, 0.0f, nullptr, oc);
-        });
-    return render_rays_device(c, b, opts, background, d_rgb_out, d_depth_out, d_opacity_out, st, stats, h, want_normals ? d_normals_out : nullptr);
+// one render of a device request whose shared origin (if any) is known on the host; a certified one goes through the retry loop, which
+// renders the batch again
+static int run_rays(nerf_ctx *c, const RayRequest &q) {
+    if (!q.certified) return render_rays_device(c, q, nullptr);
+    return certify_retry(c, q.stats, "batch", [&](CertOutcome *oc) { return render_rays_device(c, q, oc); });
 }
+
+// nerf_render_rays*_device without a grid
+static int rays_device(nerf_ctx *c, RayRequest q) {
+    float origin[3];
+    if (q.n_origins == 1 && !q.h_origin) { // the shared origin rides in the MLP kernels' arguments: 12 bytes come back first
+        HIP_TRY(c, hipMemcpyAsync(origin, q.origins, sizeof origin, hipMemcpyDeviceToHost, q.st));
+        HIP_TRY(c, hipStreamSynchronize(q.st));
+        q.h_origin = origin;
+    }
+    return run_rays(c, q);
+}
+
+// ---- clipped ray batches (DESIGN 4.15) -----------------------------------------------------------------------------------------------------
+// nerf_render_rays_clipped*_device: clip -> count -> [gather -> the compacted batch through run_rays -> scatter].  certified: the compacted
+// batch is rendered with zero certification; a retry renders the compacted batch again and does not clip again
+static int rays_clipped_device(nerf_ctx *c, const RayRequest &q) {
+    int rc;
+    const hipStream_t st = q.st;
+    const bool per_ray = q.n_origins != 1;
+    if ((rc = c->buf[BUF_CLIP].ensure(c, ClipWorkspace(nullptr, q.n_rays, per_ray).bytes))) return rc;
+    const ClipWorkspace w(c->buf[BUF_CLIP].p, q.n_rays, per_ray);
+    ClipRaysArgs a{};
+    a.bits = q.occ_bits;
+    for (int k = 0; k < 3; ++k) { a.lo[k] = q.lo[k]; a.step[k] = q.step[k]; a.dims[k] = q.dims[k]; a.bg[k] = q.background ? q.background[k] : 1.0f; }
+    a.origins = q.origins; a.per_ray_origins = per_ray ? 1 : 0; a.dirs = q.dirs; a.n_rays = (int)q.n_rays; a.normalize = q.normalize ? 1 : 0;
+    a.near_ = q.near_; a.far_ = q.far_; a.bounds = q.bounds; a.bounds_out = w.clip_bounds; a.hit_out = q.hit ? q.hit : w.hit; a.bsum = w.bsum;
+    a.rgb_fill = q.rgb; a.depth_fill = q.depth; a.opacity_fill = q.opacity; // the missed rays are finished here
+    HIP_TRY(c, launch_clip_rays(a, st));
+    HIP_TRY(c, launch_clip_scan(w.bsum, a.n_rays, w.totals, st));
+    uint32_t totals[2] = {0, 0};
+    float origin[3] = {0.0f, 0.0f, 0.0f};
+    HIP_TRY(c, hipMemcpyAsync(totals, w.totals, sizeof totals, hipMemcpyDeviceToHost, st));
+    if (!per_ray) HIP_TRY(c, hipMemcpyAsync(origin, q.origins, sizeof origin, hipMemcpyDeviceToHost, st)); // rides in the MLP kernels' arguments
+    HIP_TRY(c, hipStreamSynchronize(st)); // the hit count sizes every launch that follows
+    const size_t H = totals[0];
+    if (H > q.n_rays) return fail(c, NERF_ERR_HIP, "clipped render: the hit count exceeds the batch");
+    if (q.n_hit) *q.n_hit = H;
+    if (H == 0) { // nothing to render: the clip launch has written every ray
+        if (q.stats) memset(q.stats, 0, sizeof *q.stats);
+        return NERF_OK;
+    }
+    ClipGatherArgs g{};
+    g.n_rays = a.n_rays; g.hit = a.hit_out; g.bsum = w.bsum; g.dirs = q.dirs; g.origins = per_ray ? q.origins : nullptr; g.clip_bounds = w.clip_bounds;
+    g.rng_index = q.rng_index; g.ray_of = w.ray_of; g.dirs_c = w.dirs_c; g.origins_c = w.origins_c; g.bounds_c = w.bounds_c; g.rng_c = w.rng_c;
+    HIP_TRY(c, launch_clip_gather(g, st));
+    RayRequest b = q; // the compacted batch
+    b.origins = per_ray ? w.origins_c : q.origins; b.n_origins = per_ray ? H : 1; b.h_origin = per_ray ? nullptr : origin;
+    b.dirs = w.dirs_c; b.n_rays = H; b.bounds = w.bounds_c; b.rng_index = w.rng_c;
+    b.rgb = w.rgb_c; b.depth = q.depth ? w.depth_c : nullptr; b.opacity = q.opacity ? w.opacity_c : nullptr;
+    if ((rc = run_rays(c, b))) return rc;
+    const ClipScatterArgs s{(uint32_t)H, w.ray_of, w.rgb_c, w.depth_c, w.opacity_c, q.rgb, q.depth, q.opacity};
+    HIP_TRY(c, launch_clip_scatter(s, st));
+    if (q.stats || q.certified) HIP_TRY(c, hipStreamSynchronize(st)); // as nerf_render_rays_device: with stats the outputs are complete on return; certified forms always are
+    return NERF_OK;
+}
+
+// The ten entry points: refuse, [stage the host arrays], run the device form, [download].  host: every array of q is host memory.
+static int render_rays_entry(nerf_ctx *c, const RayRequest &q, bool host) {
+    int rc;
+    if ((rc = check_request(c, q, host)) || q.n_rays == 0) return rc;
+    DeviceGuard dg(c->device);
+    if (!host) return q.clipped ? rays_clipped_device(c, q) : rays_device(c, q);
+    // staging: [occupancy], dirs, [origins], [bounds], [rng_index], rgb, [depth], [opacity], [normals], [hit flags].  One origin for every
+    // ray stays on the host (h_origin) unless the clip launch reads it
+    const size_t R = q.n_rays, F = sizeof(float);
+    const bool up_origins = q.clipped || q.n_origins != 1;
+    Staging s(c, BUF_OUT, c->stream);
+    const int i_occ = s.opt(q.clipped, sizeof(uint32_t), q.clipped ? ((size_t)q.dims[0] * q.dims[1] * q.dims[2] + 31) / 32 : 0, q.occ_bits),
+              i_dirs = s.add(F, 3 * R, q.dirs), i_origins = s.opt(up_origins, F, 3 * q.n_origins, q.origins), i_bounds = s.opt(q.bounds, F, 2 * R, q.bounds),
+              i_rng = s.opt(q.rng_index, sizeof(uint32_t), R, q.rng_index), i_rgb = s.add(F, 3 * R, nullptr, q.rgb),
+              i_depth = s.opt(q.depth, F, R, nullptr, q.depth), i_opacity = s.opt(q.opacity, F, R, nullptr, q.opacity),
+              i_normals = s.opt(q.want_normals, F, 3 * R, nullptr, q.normals), i_hit = s.opt(q.clipped && q.hit, 1, R, nullptr, q.hit);
+    if ((rc = s.begin())) return rc;
+    nerf_stats local; // a synchronous render always reads its counters (see nerf_render_image_aux)
+    RayRequest d = q;
+    d.occ_bits = s.at<uint32_t>(i_occ); d.dirs = s.at(i_dirs); d.origins = s.at(i_origins); d.bounds = s.at(i_bounds); d.rng_index = s.at<uint32_t>(i_rng);
+    d.rgb = s.at(i_rgb); d.depth = s.at(i_depth); d.opacity = s.at(i_opacity); d.normals = s.at(i_normals); d.hit = s.at<uint8_t>(i_hit);
+    d.h_origin = up_origins ? nullptr : q.origins;
+    d.st = c->stream; d.stats = q.stats ? q.stats : &local;
+    if ((rc = q.clipped ? rays_clipped_device(c, d) : rays_device(c, d))) return rc;
+    return s.finish();
+}
+
+int nerf_render_rays(nerf_ctx *c, const float *origins, size_t n_origins, const float *dirs, size_t n_rays, int normalize, float near_, float far_,
+                     const float *bounds, const uint32_t *rng_index, const nerf_render_opts *opts, const float background[3], float *rgb_out,
+                     float *depth_out, float *opacity_out, nerf_stats *stats) try {
+    RayRequest q{};
+    q.n_origins = n_origins; q.n_rays = n_rays; q.normalize = normalize; q.near_ = near_; q.far_ = far_; q.opts = opts; q.background = background;
+    q.stats = stats;
+    q.origins = origins; q.dirs = dirs; q.bounds = bounds; q.rng_index = rng_index; q.rgb = rgb_out; q.depth = depth_out; q.opacity = opacity_out;
+    return render_rays_entry(c, q, true);
+} NERF_CATCH(c)
 
 int nerf_render_rays_device(nerf_ctx *c, const float *d_origins, size_t n_origins, const float *d_dirs, size_t n_rays, int normalize, float near_,
                             float far_, const float *d_bounds, const uint32_t *d_rng_index, const nerf_render_opts *opts, const float background[3],
                             float *d_rgb_out, float *d_depth_out, float *d_opacity_out, void *stream, nerf_stats *stats) try {
-    return rays_device(c, d_origins, n_origins, d_dirs, n_rays, normalize, near_, far_, d_bounds, d_rng_index, opts, background, d_rgb_out, d_depth_out,
-                       d_opacity_out, false, 0.0f, nullptr, stream, stats);
+    RayRequest q{};
+    q.n_origins = n_origins; q.n_rays = n_rays; q.normalize = normalize; q.near_ = near_; q.far_ = far_; q.opts = opts; q.background = background;
+    q.stats = stats;
+    q.origins = d_origins; q.dirs = d_dirs; q.bounds = d_bounds; q.rng_index = d_rng_index; q.rgb = d_rgb_out; q.depth = d_depth_out;
+    q.opacity = d_opacity_out; q.st = (hipStream_t)stream;
+    return render_rays_entry(c, q, false);
+} NERF_CATCH(c)
+
+int nerf_render_rays_normals(nerf_ctx *c, const float *origins, size_t n_origins, const float *dirs, size_t n_rays, int normalize, float near_,
+                             float far_, const float *bounds, const uint32_t *rng_index, const nerf_render_opts *opts, const float background[3],
+                             float *rgb_out, float *depth_out, float *opacity_out, float h, float *normals_out, nerf_stats *stats) try {
+    RayRequest q{};
+    q.n_origins = n_origins; q.n_rays = n_rays; q.normalize = normalize; q.near_ = near_; q.far_ = far_; q.opts = opts; q.background = background;
+    q.stats = stats;
+    q.origins = origins; q.dirs = dirs; q.bounds = bounds; q.rng_index = rng_index; q.rgb = rgb_out; q.depth = depth_out; q.opacity = opacity_out;
+    q.want_normals = true; q.h = h; q.normals = normals_out;
+    return render_rays_entry(c, q, true);
 } NERF_CATCH(c)
 
 int nerf_render_rays_normals_device(nerf_ctx *c, const float *d_origins, size_t n_origins, const float *d_dirs, size_t n_rays, int normalize,
                                     float near_, float far_, const float *d_bounds, const uint32_t *d_rng_index, const nerf_render_opts *opts,
                                     const float background[3], float *d_rgb_out, float *d_depth_out, float *d_opacity_out, float h,
                                     float *d_normals_out, void *stream, nerf_stats *stats) try {
-    return rays_device(c, d_origins, n_origins, d_dirs, n_rays, normalize, near_, far_, d_bounds, d_rng_index, opts, background, d_rgb_out, d_depth_out,
-                       d_opacity_out, true, h, d_normals_out, stream, stats);
+    RayRequest q{};
+    q.n_origins = n_origins; q.n_rays = n_rays; q.normalize = normalize; q.near_ = near_; q.far_ = far_; q.opts = opts; q.background = background;
+    q.stats = stats;
+    q.origins = d_origins; q.dirs = d_dirs; q.bounds = d_bounds; q.rng_index = d_rng_index; q.rgb = d_rgb_out; q.depth = d_depth_out;
+    q.opacity = d_opacity_out; q.want_normals = true; q.h = h; q.normals = d_normals_out; q.st = (hipStream_t)stream;
+    return render_rays_entry(c, q, false);
 } NERF_CATCH(c)
 
-// nerf_render_rays, nerf_render_rays_normals (want_normals) and nerf_render_rays_certified (certified)
-static int rays_host(nerf_ctx *c, const float *origins, size_t n_origins, const float *dirs, size_t n_rays, int normalize, float near_, float far_,
-                     const float *bounds, const uint32_t *rng_index, const nerf_render_opts *opts, const float background[3], float *rgb_out,
-                     float *depth_out, float *opacity_out, bool want_normals, float h, float *normals_out, nerf_stats *stats, bool certified = false) {
-    int rc;
-    if ((rc = check_ray_batch(c, origins, n_origins, dirs, n_rays, near_, far_, bounds, opts, background, rgb_out, certified))) return rc;
-    if (want_normals && (rc = check_normals(c, h, normals_out))) return rc;
-    if ((rc = check_ray_batch_rays(c, origins, n_origins, dirs, n_rays, normalize, bounds))) return rc;
-    if (!c) return fail(nullptr, NERF_ERR_INVALID, "ctx is NULL");
-    if (n_rays == 0) return NERF_OK;
-    DeviceGuard dg(c->device);
-    // staging (floats): dirs, [origins], [bounds], [rng_index], rgb, [depth], [opacity], [normals]
-    const size_t R = n_rays, o_d = 0, o_o = o_d + 3 * R, o_b = o_o + (n_origins == 1 ? 0 : 3 * R), o_i = o_b + (bounds ? 2 * R : 0),
-                 o_c = o_i + (rng_index ? R : 0), o_z = o_c + 3 * R, o_a = o_z + (depth_out ? R : 0), o_n = o_a + (opacity_out ? R : 0),
-                 total = o_n + (want_normals ? 3 * R : 0);
-    if ((rc = ensure_bytes(c, (void **)&c->d_out, &c->out_floats, total * sizeof(float)))) return rc;
-    float *d = c->d_out;
-    HIP_TRY(c, hipMemcpyAsync(d + o_d, dirs, 3 * R * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    if (n_origins != 1) HIP_TRY(c, hipMemcpyAsync(d + o_o, origins, 3 * R * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    if (bounds) HIP_TRY(c, hipMemcpyAsync(d + o_b, bounds, 2 * R * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    if (rng_index) HIP_TRY(c, hipMemcpyAsync(d + o_i, rng_index, R * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    RayBatch b{n_origins == 1 ? origins : nullptr, n_origins == 1 ? nullptr : d + o_o, d + o_d, n_rays, normalize ? 1 : 0, near_, far_,
-               bounds ? d + o_b : nullptr, rng_index ? (const uint32_t *)(d + o_i) : nullptr};
-    nerf_stats local; // a synchronous render always reads its counters (see nerf_render_image_aux)
-    nerf_stats *const sp = stats ? stats : &local;
-    float *const d_depth = depth_out ? d + o_z : nullptr, *const d_opacity = opacity_out ? d + o_a : nullptr;
-    if (certified) rc = certify_retry(c, sp, "batch", [&](CertOutcome *oc) {
-            return render_rays_device(c, b, opts, background, d + o_c, d_depth, d_opacity, c->stream, sp, 0.0f, nullptr, oc);
-        });
-    else rc = render_rays_device(c, b, opts, background, d + o_c, d_depth, d_opacity, c->stream, sp, h, want_normals ? d + o_n : nullptr);
-    if (rc) return rc;
-    HIP_TRY(c, hipMemcpyAsync(rgb_out, d + o_c, 3 * R * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (want_normals) HIP_TRY(c, hipMemcpyAsync(normals_out, d + o_n, 3 * R * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (depth_out) HIP_TRY(c, hipMemcpyAsync(depth_out, d + o_z, R * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (opacity_out) HIP_TRY(c, hipMemcpyAsync(opacity_out, d + o_a, R * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return NERF_OK;
-}
+int nerf_render_rays_certified(nerf_ctx *c, const float *origins, size_t n_origins, const float *dirs, size_t n_rays, int normalize, float near_,
+                               float far_, const float *bounds, const uint32_t *rng_index, const nerf_render_opts *opts, const float background[3],
+                               float *rgb_out, float *depth_out, float *opacity_out, nerf_stats *stats) try {
+    RayRequest q{};
+    q.n_origins = n_origins; q.n_rays = n_rays; q.normalize = normalize; q.near_ = near_; q.far_ = far_; q.opts = opts; q.background = background;
+    q.stats = stats;
+    q.origins = origins; q.dirs = dirs; q.bounds = bounds; q.rng_index = rng_index; q.rgb = rgb_out; q.depth = depth_out; q.opacity = opacity_out;
+    q.certified = true;
+    return render_rays_entry(c, q, true);
+} NERF_CATCH(c)
 
-// ---- clipped ray batches (DESIGN 4.15) -----------------------------------------------------------------------------------------------------
-// what nerf_render_rays_clipped* refuses without a context or a device: nerf_render_rays' refusals, then the grid's
-static int check_rays_clipped(nerf_ctx *c, const void *occ_bits, const float *lo, const float *step, const int32_t *dims, const void *origins,
-                              size_t n_origins, const void *dirs, size_t n_rays, float near_, float far_, const void *bounds,
-                              const nerf_render_opts *opts, const float *background, const void *rgb_out, bool certified) {
-    int rc;
-    if ((rc = check_ray_batch(c, origins, n_origins, dirs, n_rays, near_, far_, bounds, opts, background, rgb_out, certified))) return rc;
-    if (const char *why = nerfclip::check_grid(occ_bits, lo, step, dims)) return fail(c, NERF_ERR_INVALID, why);
-    return NERF_OK;
-}
+int nerf_render_rays_certified_device(nerf_ctx *c, const float *d_origins, size_t n_origins, const float *d_dirs, size_t n_rays, int normalize,
+                                      float near_, float far_, const float *d_bounds, const uint32_t *d_rng_index, const nerf_render_opts *opts,
+                                      const float background[3], float *d_rgb_out, float *d_depth_out, float *d_opacity_out, void *stream,
+                                      nerf_stats *stats) try {
+    RayRequest q{};
+    q.n_origins = n_origins; q.n_rays = n_rays; q.normalize = normalize; q.near_ = near_; q.far_ = far_; q.opts = opts; q.background = background;
+    q.stats = stats;
+    q.origins = d_origins; q.dirs = d_dirs; q.bounds = d_bounds; q.rng_index = d_rng_index; q.rgb = d_rgb_out; q.depth = d_depth_out;
+    q.opacity = d_opacity_out; q.certified = true; q.st = (hipStream_t)stream;
+    return render_rays_entry(c, q, false);
+} NERF_CATCH(c)
 
-// clip -> count -> [gather -> render_rays_device on the compacted batch -> scatter]; every pointer but lo / step / dims / opts / background /
-// n_hit / stats is a device pointer; arguments already checked, n_rays > 0.  certified: the compacted batch is rendered with zero
-// certification; a retry renders the compacted batch again and does not clip again
-static int rays_clipped_device(nerf_ctx *c, const uint32_t *d_bits, const float *lo, const float *step, const int32_t *dims, const float *d_origins,
-                               size_t n_origins, const float *d_dirs, size_t n_rays, int normalize, float near_, float far_, const float *d_bounds,
-                               const uint32_t *d_rng_index, const nerf_render_opts *opts, const float *background, float *d_rgb_out,
-                               float *d_depth_out, float *d_opacity_out, uint8_t *d_hit_out, uint64_t *n_hit, hipStream_t st, nerf_stats *stats,
-                               bool certified) {
-    int rc;
-    const bool per_ray = n_origins != 1;
-    if ((rc = ensure_bytes(c, &c->d_clip, &c->clip_bytes, ClipWorkspace::bytes(n_rays, per_ray)))) return rc;
-    const ClipWorkspace w(c->d_clip, n_rays, per_ray);
-    ClipRaysArgs a{};
-    a.bits = d_bits;
-    for (int k = 0; k < 3; ++k) { a.lo[k] = lo[k]; a.step[k] = step[k]; a.dims[k] = dims[k]; a.bg[k] = background ? background[k] : 1.0f; }
-    a.origins = d_origins; a.per_ray_origins = per_ray ? 1 : 0; a.dirs = d_dirs; a.n_rays = (int)n_rays; a.normalize = normalize ? 1 : 0;
-    a.near_ = near_; a.far_ = far_; a.bounds = d_bounds; a.bounds_out = w.clip_bounds; a.hit_out = d_hit_out ? d_hit_out : w.hit; a.bsum = w.bsum;
-    a.rgb_fill = d_rgb_out; a.depth_fill = d_depth_out; a.opacity_fill = d_opacity_out; // the missed rays are finished here
-    HIP_TRY(c, launch_clip_rays(a, st));
-    HIP_TRY(c, launch_clip_scan(w.bsum, a.n_rays, w.totals, st));
-    uint32_t totals[2] = {0, 0};
-    float origin[3] = {0.0f, 0.0f, 0.0f};
-    HIP_TRY(c, hipMemcpyAsync(totals, w.totals, sizeof totals, hipMemcpyDeviceToHost, st));
-    if (!per_ray) HIP_TRY(c, hipMemcpyAsync(origin, d_origins, sizeof origin, hipMemcpyDeviceToHost, st)); // rides in the MLP kernels' arguments
-    HIP_TRY(c, hipStreamSynchronize(st)); // the hit count sizes every launch that follows
-    const size_t H = totals[0];
-    if (H > n_rays) return fail(c, NERF_ERR_HIP, "clipped render: the hit count exceeds the batch");
-    if (n_hit) *n_hit = H;
-    if (H == 0) { // nothing to render: the clip launch has written every ray
-        if (stats) memset(stats, 0, sizeof *stats);
-        return NERF_OK;
-    }
-    ClipGatherArgs g{};
-    g.n_rays = a.n_rays; g.hit = a.hit_out; g.bsum = w.bsum; g.dirs = d_dirs; g.origins = per_ray ? d_origins : nullptr; g.clip_bounds = w.clip_bounds;
-    g.rng_index = d_rng_index; g.ray_of = w.ray_of; g.dirs_c = w.dirs_c; g.origins_c = w.origins_c; g.bounds_c = w.bounds_c; g.rng_c = w.rng_c;
-    HIP_TRY(c, launch_clip_gather(g, st));
-    const RayBatch b{per_ray ? nullptr : origin, per_ray ? w.origins_c : nullptr, w.dirs_c, H, normalize ? 1 : 0, near_, far_, w.bounds_c, w.rng_c};
-    float *const depth_c = d_depth_out ? w.depth_c : nullptr, *const opacity_c = d_opacity_out ? w.opacity_c : nullptr;
-    if (certified) rc = certify_retry(c, stats, "batch", [&](CertOutcome *oc) {
-            return render_rays_device(c, b, opts, background, w.rgb_c, depth_c, opacity_c, st, stats, 0.0f, nullptr, oc);
-        });
-    else rc = render_rays_device(c, b, opts, background, w.rgb_c, depth_c, opacity_c, st, stats);
-    if (rc) return rc;
-    const ClipScatterArgs s{(uint32_t)H, w.ray_of, w.rgb_c, w.depth_c, w.opacity_c, d_rgb_out, d_depth_out, d_opacity_out};
-    HIP_TRY(c, launch_clip_scatter(s, st));
-    if (stats || certified) HIP_TRY(c, hipStreamSynchronize(st)); // as nerf_render_rays_device: with stats the outputs are complete on return; certified forms always are
-    return NERF_OK;
-}
-
-// nerf_render_rays_clipped_device and nerf_render_rays_clipped_certified_device (certified)
-static int clipped_device(nerf_ctx *c, const uint32_t *d_occ_bits, const float lo[3], const float step[3], const int32_t dims[3],
-                          const float *d_origins, size_t n_origins, const float *d_dirs, size_t n_rays, int normalize, float near_,
-                          float far_, const float *d_bounds, const uint32_t *d_rng_index, const nerf_render_opts *opts,
-                          const float background[3], float *d_rgb_out, float *d_depth_out, float *d_opacity_out, uint8_t *d_hit_out,
-                          uint64_t *n_hit, void *stream, nerf_stats *stats, bool certified) {
-    int rc;
-    if ((rc = check_rays_clipped(c, d_occ_bits, lo, step, dims, d_origins, n_origins, d_dirs, n_rays, near_, far_, d_bounds, opts, background, d_rgb_out,
-                                 certified)))
-        return rc;
-    if (!c) return fail(nullptr, NERF_ERR_INVALID, "ctx is NULL");
-    if (n_hit) *n_hit = 0;
-    if (n_rays == 0) return NERF_OK;
-    DeviceGuard dg(c->device);
-    return rays_clipped_device(c, d_occ_bits, lo, step, dims, d_origins, n_origins, d_dirs, n_rays, normalize, near_, far_, d_bounds, d_rng_index, opts,
-                               background, d_rgb_out, d_depth_out, d_opacity_out, d_hit_out, n_hit, (hipStream_t)stream, stats, certified);
-}
-
-// nerf_render_rays_clipped and nerf_render_rays_clipped_certified (certified)
-static int clipped_host(nerf_ctx *c, const uint32_t *occ_bits, const float lo[3], const float step[3], const int32_t dims[3],
-                        const float *origins, size_t n_origins, const float *dirs, size_t n_rays, int normalize, float near_, float far_,
-                        const float *bounds, const uint32_t *rng_index, const nerf_render_opts *opts, const float background[3], float *rgb_out,
-                        float *depth_out, float *opacity_out, uint8_t *hit_out, uint64_t *n_hit, nerf_stats *stats, bool certified) {
-    int rc;
-    if ((rc = check_rays_clipped(c, occ_bits, lo, step, dims, origins, n_origins, dirs, n_rays, near_, far_, bounds, opts, background, rgb_out, certified)))
-        return rc;
-    if ((rc = check_ray_batch_rays(c, origins, n_origins, dirs, n_rays, normalize, bounds))) return rc;
-    if (!c) return fail(nullptr, NERF_ERR_INVALID, "ctx is NULL");
-    if (n_hit) *n_hit = 0;
-    if (n_rays == 0) return NERF_OK;
-    DeviceGuard dg(c->device);
-    // staging (words): occupancy, dirs, origins, [bounds], [rng_index], rgb, [depth], [opacity], [hit flags]
-    const size_t R = n_rays, n_words = ((size_t)dims[0] * dims[1] * dims[2] + 31) / 32, n_o = n_origins == 1 ? 1 : R;
-    const size_t o_g = 0, o_d = o_g + n_words, o_o = o_d + 3 * R, o_b = o_o + 3 * n_o, o_i = o_b + (bounds ? 2 * R : 0), o_c = o_i + (rng_index ? R : 0),
-                 o_z = o_c + 3 * R, o_a = o_z + (depth_out ? R : 0), o_h = o_a + (opacity_out ? R : 0), total = o_h + (hit_out ? (R + 3) / 4 : 0);
-    if ((rc = ensure_bytes(c, (void **)&c->d_out, &c->out_floats, total * sizeof(float)))) return rc;
-    float *d = c->d_out;
-    HIP_TRY(c, hipMemcpyAsync(d + o_g, occ_bits, n_words * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(d + o_d, dirs, 3 * R * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(d + o_o, origins, 3 * n_o * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    if (bounds) HIP_TRY(c, hipMemcpyAsync(d + o_b, bounds, 2 * R * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    if (rng_index) HIP_TRY(c, hipMemcpyAsync(d + o_i, rng_index, R * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    nerf_stats local; // a synchronous render always reads its counters (see nerf_render_image_aux)
-    if ((rc = rays_clipped_device(c, (const uint32_t *)(d + o_g), lo, step, dims, d + o_o, n_origins, d + o_d, R, normalize, near_, far_,
-                                  bounds ? d + o_b : nullptr, rng_index ? (const uint32_t *)(d + o_i) : nullptr, opts, background, d + o_c,
-                                  depth_out ? d + o_z : nullptr, opacity_out ? d + o_a : nullptr, hit_out ? (uint8_t *)(d + o_h) : nullptr, n_hit,
-                                  c->stream, stats ? stats : &local, certified))) return rc;
-    HIP_TRY(c, hipMemcpyAsync(rgb_out, d + o_c, 3 * R * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (depth_out) HIP_TRY(c, hipMemcpyAsync(depth_out, d + o_z, R * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (opacity_out) HIP_TRY(c, hipMemcpyAsync(opacity_out, d + o_a, R * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (hit_out) HIP_TRY(c, hipMemcpyAsync(hit_out, d + o_h, R, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return NERF_OK;
-}
+// the four clipped forms: the grid, the flags and the hit count on top
+int nerf_render_rays_clipped(nerf_ctx *c, const uint32_t *occ_bits, const float lo[3], const float step[3], const int32_t dims[3],
+                             const float *origins, size_t n_origins, const float *dirs, size_t n_rays, int normalize, float near_, float far_,
+                             const float *bounds, const uint32_t *rng_index, const nerf_render_opts *opts, const float background[3], float *rgb_out,
+                             float *depth_out, float *opacity_out, uint8_t *hit_out, uint64_t *n_hit, nerf_stats *stats) try {
+    RayRequest q{};
+    q.n_origins = n_origins; q.n_rays = n_rays; q.normalize = normalize; q.near_ = near_; q.far_ = far_; q.opts = opts; q.background = background;
+    q.stats = stats;
+    q.clipped = true; q.lo = lo; q.step = step; q.dims = dims; q.n_hit = n_hit;
+    q.occ_bits = occ_bits; q.origins = origins; q.dirs = dirs; q.bounds = bounds; q.rng_index = rng_index; q.rgb = rgb_out; q.depth = depth_out;
+    q.opacity = opacity_out; q.hit = hit_out;
+    return render_rays_entry(c, q, true);
+} NERF_CATCH(c)
 
 int nerf_render_rays_clipped_device(nerf_ctx *c, const uint32_t *d_occ_bits, const float lo[3], const float step[3], const int32_t dims[3],
                                     const float *d_origins, size_t n_origins, const float *d_dirs, size_t n_rays, int normalize, float near_,
                                     float far_, const float *d_bounds, const uint32_t *d_rng_index, const nerf_render_opts *opts,
                                     const float background[3], float *d_rgb_out, float *d_depth_out, float *d_opacity_out, uint8_t *d_hit_out,
                                     uint64_t *n_hit, void *stream, nerf_stats *stats) try {
-    return clipped_device(c, d_occ_bits, lo, step, dims, d_origins, n_origins, d_dirs, n_rays, normalize, near_, far_, d_bounds, d_rng_index, opts,
-                          background, d_rgb_out, d_depth_out, d_opacity_out, d_hit_out, n_hit, stream, stats, false);
-} NERF_CATCH(c)
-
-int nerf_render_rays_clipped_certified_device(nerf_ctx *c, const uint32_t *d_occ_bits, const float lo[3], const float step[3], const int32_t dims[3],
-                                              const float *d_origins, size_t n_origins, const float *d_dirs, size_t n_rays, int normalize,
-                                              float near_, float far_, const float *d_bounds, const uint32_t *d_rng_index,
-                                              const nerf_render_opts *opts, const float background[3], float *d_rgb_out, float *d_depth_out,
-                                              float *d_opacity_out, uint8_t *d_hit_out, uint64_t *n_hit, void *stream, nerf_stats *stats) try {
-    return clipped_device(c, d_occ_bits, lo, step, dims, d_origins, n_origins, d_dirs, n_rays, normalize, near_, far_, d_bounds, d_rng_index, opts,
-                          background, d_rgb_out, d_depth_out, d_opacity_out, d_hit_out, n_hit, stream, stats, true);
-} NERF_CATCH(c)
-
-int nerf_render_rays_clipped(nerf_ctx *c, const uint32_t *occ_bits, const float lo[3], const float step[3], const int32_t dims[3],
-                             const float *origins, size_t n_origins, const float *dirs, size_t n_rays, int normalize, float near_, float far_,
-                             const float *bounds, const uint32_t *rng_index, const nerf_render_opts *opts, const float background[3], float *rgb_out,
-                             float *depth_out, float *opacity_out, uint8_t *hit_out, uint64_t *n_hit, nerf_stats *stats) try {
-    return clipped_host(c, occ_bits, lo, step, dims, origins, n_origins, dirs, n_rays, normalize, near_, far_, bounds, rng_index, opts, background,
-                        rgb_out, depth_out, opacity_out, hit_out, n_hit, stats, false);
+    RayRequest q{};
+    q.n_origins = n_origins; q.n_rays = n_rays; q.normalize = normalize; q.near_ = near_; q.far_ = far_; q.opts = opts; q.background = background;
+    q.stats = stats;
+    q.clipped = true; q.lo = lo; q.step = step; q.dims = dims; q.n_hit = n_hit;
+    q.occ_bits = d_occ_bits; q.origins = d_origins; q.dirs = d_dirs; q.bounds = d_bounds; q.rng_index = d_rng_index; q.rgb = d_rgb_out;
+    q.depth = d_depth_out; q.opacity = d_opacity_out; q.hit = d_hit_out; q.st = (hipStream_t)stream;
+    return render_rays_entry(c, q, false);
 } NERF_CATCH(c)
 
 int nerf_render_rays_clipped_certified(nerf_ctx *c, const uint32_t *occ_bits, const float lo[3], const float step[3], const int32_t dims[3],
@@ -1300,37 +1259,27 @@ int nerf_render_rays_clipped_certified(nerf_ctx *c, const uint32_t *occ_bits, co
                                        float far_, const float *bounds, const uint32_t *rng_index, const nerf_render_opts *opts,
                                        const float background[3], float *rgb_out, float *depth_out, float *opacity_out, uint8_t *hit_out,
                                        uint64_t *n_hit, nerf_stats *stats) try {
-    return clipped_host(c, occ_bits, lo, step, dims, origins, n_origins, dirs, n_rays, normalize, near_, far_, bounds, rng_index, opts, background,
-                        rgb_out, depth_out, opacity_out, hit_out, n_hit, stats, true);
+    RayRequest q{};
+    q.n_origins = n_origins; q.n_rays = n_rays; q.normalize = normalize; q.near_ = near_; q.far_ = far_; q.opts = opts; q.background = background;
+    q.stats = stats;
+    q.clipped = true; q.lo = lo; q.step = step; q.dims = dims; q.n_hit = n_hit;
+    q.occ_bits = occ_bits; q.origins = origins; q.dirs = dirs; q.bounds = bounds; q.rng_index = rng_index; q.rgb = rgb_out; q.depth = depth_out;
+    q.opacity = opacity_out; q.hit = hit_out; q.certified = true;
+    return render_rays_entry(c, q, true);
 } NERF_CATCH(c)
 
-int nerf_render_rays(nerf_ctx *c, const float *origins, size_t n_origins, const float *dirs, size_t n_rays, int normalize, float near_, float far_,
-                     const float *bounds, const uint32_t *rng_index, const nerf_render_opts *opts, const float background[3], float *rgb_out,
-                     float *depth_out, float *opacity_out, nerf_stats *stats) try {
-    return rays_host(c, origins, n_origins, dirs, n_rays, normalize, near_, far_, bounds, rng_index, opts, background, rgb_out, depth_out, opacity_out,
-                     false, 0.0f, nullptr, stats);
-} NERF_CATCH(c)
-
-int nerf_render_rays_normals(nerf_ctx *c, const float *origins, size_t n_origins, const float *dirs, size_t n_rays, int normalize, float near_,
-                             float far_, const float *bounds, const uint32_t *rng_index, const nerf_render_opts *opts, const float background[3],
-                             float *rgb_out, float *depth_out, float *opacity_out, float h, float *normals_out, nerf_stats *stats) try {
-    return rays_host(c, origins, n_origins, dirs, n_rays, normalize, near_, far_, bounds, rng_index, opts, background, rgb_out, depth_out, opacity_out,
-                     true, h, normals_out, stats);
-} NERF_CATCH(c)
-
-int nerf_render_rays_certified(nerf_ctx *c, const float *origins, size_t n_origins, const float *dirs, size_t n_rays, int normalize, float near_,
-                               float far_, const float *bounds, const uint32_t *rng_index, const nerf_render_opts *opts, const float background[3],
-                               float *rgb_out, float *depth_out, float *opacity_out, nerf_stats *stats) try {
-    return rays_host(c, origins, n_origins, dirs, n_rays, normalize, near_, far_, bounds, rng_index, opts, background, rgb_out, depth_out, opacity_out,
-                     false, 0.0f, nullptr, stats, true);
-} NERF_CATCH(c)
-
-int nerf_render_rays_certified_device(nerf_ctx *c, const float *d_origins, size_t n_origins, const float *d_dirs, size_t n_rays, int normalize,
-                                      float near_, float far_, const float *d_bounds, const uint32_t *d_rng_index, const nerf_render_opts *opts,
-                                      const float background[3], float *d_rgb_out, float *d_depth_out, float *d_opacity_out, void *stream,
-                                      nerf_stats *stats) try {
-    return rays_device(c, d_origins, n_origins, d_dirs, n_rays, normalize, near_, far_, d_bounds, d_rng_index, opts, background, d_rgb_out, d_depth_out,
-                       d_opacity_out, false, 0.0f, nullptr, stream, stats, true);
+int nerf_render_rays_clipped_certified_device(nerf_ctx *c, const uint32_t *d_occ_bits, const float lo[3], const float step[3], const int32_t dims[3],
+                                              const float *d_origins, size_t n_origins, const float *d_dirs, size_t n_rays, int normalize,
+                                              float near_, float far_, const float *d_bounds, const uint32_t *d_rng_index,
+                                              const nerf_render_opts *opts, const float background[3], float *d_rgb_out, float *d_depth_out,
+                                              float *d_opacity_out, uint8_t *d_hit_out, uint64_t *n_hit, void *stream, nerf_stats *stats) try {
+    RayRequest q{};
+    q.n_origins = n_origins; q.n_rays = n_rays; q.normalize = normalize; q.near_ = near_; q.far_ = far_; q.opts = opts; q.background = background;
+    q.stats = stats;
+    q.clipped = true; q.lo = lo; q.step = step; q.dims = dims; q.n_hit = n_hit;
+    q.occ_bits = d_occ_bits; q.origins = d_origins; q.dirs = d_dirs; q.bounds = d_bounds; q.rng_index = d_rng_index; q.rgb = d_rgb_out;
+    q.depth = d_depth_out; q.opacity = d_opacity_out; q.hit = d_hit_out; q.certified = true; q.st = (hipStream_t)stream;
+    return render_rays_entry(c, q, false);
 } NERF_CATCH(c)
 
 } // extern "C"

@@ -51,6 +51,14 @@ def test_valid_inputs_under_sanitizers(asan, tmp_path):
     assert asan("save_ppm", tmp_path / "no" / "dir" / "b.ppm", 2, 2)[0] == -2
 
 
+def test_stage_layout_under_sanitizers(asan):
+    """stage_layout.h, the bump allocator of every staging layout and pass workspace: parts absent and present, a zero-length part, a
+    guarded part, the alignment of every offset, the total, and sizes beyond size_t refused instead of wrapped (the driver's checks: rc
+    names the first that failed)."""
+    rc, msg, out = asan("stage_layout")
+    assert rc == 0 and "stage_layout total 1792 parts 5" in out, (rc, msg, out)
+
+
 def test_malformed_weight_directories(asan, tmp_path):
     src = os.path.join(SCENE, "coarse")
     good_shapes = open(os.path.join(src, "shapes.txt")).read()
