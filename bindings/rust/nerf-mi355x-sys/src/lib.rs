@@ -30,6 +30,11 @@ pub const NERF_MLP_F32: i32 = 0;
 pub const NERF_MLP_BF16: i32 = 1;
 pub const NERF_MLP_BF16X3: i32 = 2;
 pub const NERF_MLP_F16X2: i32 = 3;
+/// `nerf_debug_network_stream_dir`'s `kind`: which 16-bit weight stream.
+pub const NERF_STREAM_BF16V2: c_int = 0;
+pub const NERF_STREAM_F16V2: c_int = 1;
+pub const NERF_STREAM_BF16X3: c_int = 2;
+pub const NERF_STREAM_F16X2: c_int = 3;
 
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -139,6 +144,7 @@ extern "C" {
                                        small_cap: usize, wstream_len: *mut usize, small_len: *mut usize) -> c_int;
     pub fn nerf_debug_fold_network_dir(dir: *const c_char, wstream: *mut f32, wstream_cap: usize, small: *mut f32,
                                        small_cap: usize, wstream_len: *mut usize, small_len: *mut usize) -> c_int;
+    pub fn nerf_debug_network_stream_dir(dir: *const c_char, kind: c_int, out: *mut u16, cap: usize, n: *mut usize, available: *mut c_int) -> c_int;
     pub fn nerf_debug_zero_skip_network_dir(dir: *const c_char, eligible: *mut c_int) -> c_int;
     pub fn nerf_debug_split_bf16x3(values: *const f32, n: usize, parts: *mut u16) -> c_int;
     pub fn nerf_debug_split_f16x2(values: *const f32, n: usize, parts: *mut u16) -> c_int;

@@ -229,6 +229,12 @@ int nerf_debug_pack_network_dir(const char *dir, float *wstream, size_t wstream_
  * kChunksFullFolded); the small block differs in the viewdirs bias only.  Same calling convention as above.  Host-only. */
 int nerf_debug_fold_network_dir(const char *dir, float *wstream, size_t wstream_cap, float *small, size_t small_cap,
                                 size_t *wstream_len, size_t *small_len);
+/* Diagnostic: one of the four 16-bit weight streams every loader builds from the packed image (layouts: nerf-rs_amd/csrc/mlp_layout.h), as raw
+ * 16-bit patterns: NERF_STREAM_BF16V2 (NERF_MLP_BF16), NERF_STREAM_F16V2 (certify_zero's f16 pre-filter), NERF_STREAM_BF16X3, NERF_STREAM_F16X2.
+ * *n = its length in elements, *available = 0 and *n = 0 if a weight exceeds the f16 range (the two f16 streams only; nothing is written).
+ * out == NULL queries; a buffer of cap < *n elements is refused with NERF_ERR_INVALID and left untouched.  n, available may be NULL.  Host-only. */
+enum { NERF_STREAM_BF16V2 = 0, NERF_STREAM_F16V2 = 1, NERF_STREAM_BF16X3 = 2, NERF_STREAM_F16X2 = 3 };
+int nerf_debug_network_stream_dir(const char *dir, int kind, uint16_t *out, size_t cap, size_t *n, int *available);
 /* Diagnostic: what the loaders decide for zero-step skipping of the NERF_MLP_F32 kernels (see NERF_ZERO_STEP_SKIP at nerf_create): *eligible = 1 iff
  * every value of the folded image of this weight directory is finite.  Host-only: it reports the loaders' predicate, not a context; what a
  * context did with a loaded network shows in NERF_DEBUG_ZSKIP's counters (executed == total: every k-step was executed). */

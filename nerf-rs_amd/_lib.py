@@ -77,6 +77,8 @@ PROTOTYPES = {
                                               C.POINTER(C.c_size_t)]),
     "nerf_debug_fold_network_dir": (C.c_int, [C.c_char_p, f32p, C.c_size_t, f32p, C.c_size_t, C.POINTER(C.c_size_t),
                                               C.POINTER(C.c_size_t)]),
+    "nerf_debug_network_stream_dir": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(C.c_uint16), C.c_size_t, C.POINTER(C.c_size_t),
+                                                C.POINTER(C.c_int)]),
     "nerf_debug_zero_skip_network_dir": (C.c_int, [C.c_char_p, C.POINTER(C.c_int)]),
     "nerf_debug_split_bf16x3": (C.c_int, [f32p, C.c_size_t, C.POINTER(C.c_uint16)]),
     "nerf_debug_split_f16x2": (C.c_int, [f32p, C.c_size_t, C.POINTER(C.c_uint16)]),

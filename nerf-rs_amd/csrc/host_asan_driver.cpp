@@ -3,7 +3,7 @@
 // touches the device).  tests/test_host_asan.py feeds it valid, truncated, oversized and malformed weight directories, blobs and
 // camera JSON files: every call must come back with a status code and a message -- a sanitizer report aborts with a non-zero exit.
 //   host_asan_driver check_dir <dir> | pack_dir <dir> <blob> | check_blob <blob> | camera_json <json> <w> <h> |
-//                    debug_pack <dir> | debug_fold <dir> | quantize | save_ppm <path> <w> <h> | save_pfm <path> <w> <h> | save_pam <path> <w> <h> | split |
+//                    debug_pack <dir> | debug_fold <dir> | streams_dir <dir> | quantize | save_ppm <path> <w> <h> | save_pfm <path> <w> <h> | save_pam <path> <w> <h> | split |
 //                    ply <path> <n_vertices> <n_triangles> <normals 0|1> <colours 0|1> | stage_layout
 #include <math.h>
 #include <stdio.h>
@@ -58,6 +58,23 @@ int main(int argc, char **argv) {
             printf("folded %zu + %zu floats, sum %.6f\n", nw, ns, s);
         }
         return report("debug_fold", rc);
+    }
+    if (cmd == "streams_dir" && argc == 3) { // the four 16-bit streams (host_util.cpp build_streams), each into a buffer of exactly its length
+        int rc = 0;
+        for (int kind = NERF_STREAM_BF16V2; kind <= NERF_STREAM_F16X2 && !rc; ++kind) {
+            size_t n = 0;
+            int available = -1;
+            rc = nerf_debug_network_stream_dir(argv[2], kind, nullptr, 0, &n, &available);
+            if (rc) break;
+            std::vector<uint16_t> s(n);
+            rc = nerf_debug_network_stream_dir(argv[2], kind, s.data(), s.size(), &n, &available);
+            if (!rc && n && nerf_debug_network_stream_dir(argv[2], kind, s.data(), n - 1, &n, &available) != NERF_ERR_INVALID) rc = 99; // short buffer refused
+            if (!rc && available != (n ? 1 : 0)) rc = 98;
+            unsigned long long sum = 0; for (uint16_t v : s) sum += v;
+            printf("stream %d: %zu elements, available %d, sum %llu\n", kind, n, available, sum);
+        }
+        if (!rc && nerf_debug_network_stream_dir(argv[2], 4, nullptr, 0, nullptr, nullptr) != NERF_ERR_INVALID) rc = 97;
+        return report("streams_dir", rc);
     }
     if (cmd == "quantize") { // clamp + NaN/inf through the quantisers (src/lib.rs:573-577, :582-592)
         const float v[] = {-1.f, 0.f, 0.5f, 1.f, 2.f, NAN, INFINITY, -INFINITY, 1e-9f, 0.999999f, 0.25f, 0.75f};

@@ -238,51 +238,6 @@ uint16_t f32_to_bf16_rne(float v) {
     return (uint16_t)(u >> 16);
 }
 
-// rowfn(tile, r, h): weight row held by register r (0..15) of input tile `tile` on lane-half h, or -1.
-// Emits the layer's 1-KiB pieces (64 lanes x 8 elements) in the order (input tile, k-step, output tile) as f32 values.
-template <class RowFn>
-static void pack_layer_v1order(std::vector<float> &s, const HostNet::L &L, int n_tiles, int NT, RowFn row) {
-    for (int tt = 0; tt < n_tiles; ++tt)
-        for (int ks = 0; ks < 2; ++ks)
-            for (int nt = 0; nt < NT; ++nt)
-                for (int l = 0; l < 64; ++l)
-                    for (int j = 0; j < 8; ++j) { // B-fragment element j of k-step ks = register 8 ks + j of the tile
-                        const int r = row(tt, 8 * ks + j, l >> 5);
-                        const int n = 32 * nt + (l & 31);
-                        s.push_back((r >= 0 && r < L.K && n < L.N) ? L.w[(size_t)r * L.N + n] : 0.0f);
-                    }
-}
-
-void pack_network_v1order_f32(const HostNet &net, std::vector<float> &ws) {
-    ws.clear();
-    ws.reserve((size_t)kPiecesV1 * 512);
-    auto hid = [](int tt, int r, int h) { return 32 * tt + regFeature(r, h); };
-    pack_layer_v1order(ws, net.dense[0], 2, 8, [](int tt, int r, int h) { return posSlotFeature(16 * tt + r, h); });
-    for (int i = 1; i < 5; ++i) pack_layer_v1order(ws, net.dense[i], 8, 8, hid);
-    pack_layer_v1order(ws, net.dense[5], 10, 8, [](int tt, int r, int h) {
-        return tt < 2 ? posSlotFeature(16 * tt + r, h) : 63 + 32 * (tt - 2) + regFeature(r, h);
-    });
-    for (int i = 6; i < 8; ++i) pack_layer_v1order(ws, net.dense[i], 8, 8, hid);
-    pack_layer_v1order(ws, net.bottleneck, 8, 8, hid);
-    pack_layer_v1order(ws, net.viewdirs, 9, 4, [](int tt, int r, int h) {
-        if (tt < 8) return 32 * tt + regFeature(r, h);
-        const int f = dirSlotFeature(r, h);
-        return f < 0 ? -1 : 256 + f;
-    });
-}
-
-void bf16_stream_from_v1order(const std::vector<float> &v1f, std::vector<uint16_t> &ws) {
-    ws.resize(v1f.size());
-    for (size_t i = 0; i < v1f.size(); ++i) ws[i] = f32_to_bf16_rne(v1f[i]);
-    ws.resize((size_t)kChunksFullBf16 * kChunkBytesBf16 / 2, (uint16_t)0); // pad viewdirs to whole chunks
-}
-
-void pack_network_bf16(const HostNet &net, std::vector<uint16_t> &ws) {
-    std::vector<float> v1f;
-    pack_network_v1order_f32(net, v1f);
-    bf16_stream_from_v1order(v1f, ws);
-}
-
 static float bf16_to_f32(uint16_t b) {
     const uint32_t u = (uint32_t)b << 16;
     float f;
@@ -299,18 +254,6 @@ void split_bf16x3(float v, uint16_t out[3]) {
     out[2] = f32_to_bf16_rne(r2);
 }
 
-// x3 stream: every piece of the v1 order followed by the pieces of the second and third part of the same weights
-void x3_stream_from_v1order(const std::vector<float> &v1f, std::vector<uint16_t> &ws) {
-    const size_t n_pieces = v1f.size() / 512;
-    ws.assign(n_pieces * 3 * 512, (uint16_t)0);
-    for (size_t pc = 0; pc < n_pieces; ++pc)
-        for (int e = 0; e < 512; ++e) {
-            uint16_t parts[3];
-            split_bf16x3(v1f[pc * 512 + e], parts);
-            for (int s3 = 0; s3 < 3; ++s3) ws[(pc * 3 + s3) * 512 + e] = parts[s3];
-        }
-}
-
 // w = w1 + w2 (+ at most 2^-22 |w|): w1 = f16(w), w2 = f16(w - w1), round to nearest even; the subtraction is exact in f32.
 // Values beyond the f16 range (|w| > 65504) would become infinite: the loader rejects such networks for this arithmetic.
 void split_f16x2(float v, uint16_t out[2]) {
@@ -320,36 +263,47 @@ void split_f16x2(float v, uint16_t out[2]) {
     memcpy(&out[1], &l, 2);
 }
 
-// f16x2 stream: every piece of the v1 order followed by the piece of the second part of the same weights
-// The f16 twin of bf16_stream_from_v1order (mlp_kernel_f16v2.hip: certify_zero's pre-filter): every weight rounded to f16 (RNE).  Returns false
-// if a weight is outside the f16 range (the pre-filter then stays bf16 for that network).
-bool f16_stream_from_v1order(const std::vector<float> &v1f, std::vector<uint16_t> &ws) {
-    ws.resize(v1f.size());
-    bool in_range = true;
-    for (size_t i = 0; i < v1f.size(); ++i) {
-        const float v = v1f[i];
-        if (!(fabsf(v) <= 65504.0f)) in_range = false;
-        const _Float16 h = (_Float16)v;
-        memcpy(&ws[i], &h, sizeof(uint16_t));
-    }
-    ws.resize((size_t)kChunksFullBf16 * kChunkBytesBf16 / 2, (uint16_t)0); // pad viewdirs to whole chunks
-    return in_range;
-}
-
-bool x2_stream_from_v1order(const std::vector<float> &v1f, std::vector<uint16_t> &ws) {
-    const size_t n_pieces = v1f.size() / 512;
-    ws.assign(n_pieces * 2 * 512, (uint16_t)0);
-    bool in_range = true;
-    for (size_t pc = 0; pc < n_pieces; ++pc)
-        for (int e = 0; e < 512; ++e) {
-            const float v = v1f[pc * 512 + e];
-            if (!(fabsf(v) <= 65504.0f)) in_range = false;
-            uint16_t parts[2];
-            split_f16x2(v, parts);
-            ws[(pc * 2 + 0) * 512 + e] = parts[0];
-            ws[(pc * 2 + 1) * 512 + e] = parts[1];
-        }
-    return in_range;
+// ---- the four 16-bit streams ---------------------------------------------------------------------
+// They hold the packed image's weights in 1-KiB pieces of 64 lanes x 8 elements (mlp_layout.h "16-bit pieces"): element j of lane l of piece
+// (ks, nt) of a layer is the f32 stream's k-step st = 8 ks + j, output tile nt, lane l -- element l * 4 + (nt & 3) of f32 piece (st, nt / 4).
+bool build_streams(const std::vector<float> &ws, NetStreams &out) {
+    if (ws.size() != (size_t)kChunksFull * kChunkFloats) return false;
+    constexpr size_t E = 512; // elements per piece
+    out.bf16v2.assign((size_t)kChunksFullBf16V2 * kChunkBytesBf16V2 / 2, (uint16_t)0); // viewdirs' 72 pieces end half-way into a chunk: zeros behind them
+    out.f16v2.assign(out.bf16v2.size(), (uint16_t)0);
+    out.x3.resize((size_t)kPieces16 * 3 * E);
+    out.x2.resize((size_t)kPieces16 * 2 * E);
+    bool fits_f16 = true;
+    size_t f32_base = 0, piece_base = 0; // of the layer: floats of the f32 stream, 16-bit pieces
+    auto layer = [&](int KS, int NT) {   // KS k-steps of K = 16 (two per 32-row input tile), NT output tiles
+        for (int ks = 0; ks < KS; ++ks)
+            for (int nt = 0; nt < NT; ++nt) {
+                const size_t tile_major = (piece_base + (size_t)nt * KS + ks) * E; // bf16v2 / f16v2: per output tile, per k-step
+                const size_t step_major = piece_base + (size_t)ks * NT + nt;       // x3 / x2: per k-step, per output tile; a unit = the piece's parts
+                for (int l = 0; l < 64; ++l)
+                    for (int j = 0; j < 8; ++j) {
+                        const float v = ws[f32_base + ((size_t)(8 * ks + j) * (NT / 4) + nt / 4) * 256 + (size_t)l * 4 + (nt & 3)];
+                        const size_t e = (size_t)l * 8 + j;
+                        if (!(fabsf(v) <= 65504.0f)) fits_f16 = false;
+                        uint16_t p3[3], p2[2];
+                        split_bf16x3(v, p3);
+                        split_f16x2(v, p2);
+                        out.bf16v2[tile_major + e] = p3[0]; // the first parts are the weight itself, rounded once
+                        out.f16v2[tile_major + e] = p2[0];
+                        for (int k = 0; k < 3; ++k) out.x3[(step_major * 3 + k) * E + e] = p3[k];
+                        for (int k = 0; k < 2; ++k) out.x2[(step_major * 2 + k) * E + e] = p2[k];
+                    }
+            }
+        f32_base += (size_t)KS * 8 * NT * 64;
+        piece_base += (size_t)KS * NT;
+    };
+    layer(4, 8);                                   // dense0: 64 encoding slots
+    for (int i = 0; i < 4; ++i) layer(16, 8);      // dense1..4
+    layer(20, 8);                                  // dense5: encoding + 256
+    for (int i = 0; i < 3; ++i) layer(16, 8);      // dense6, dense7, bottleneck
+    layer(18, 4);                                  // viewdirs: 256 + 32 direction slots
+    if (!fits_f16) { out.f16v2.clear(); out.x2.clear(); } // the loader rejects such networks for the two f16 arithmetics
+    return f32_base == ws.size() && piece_base == (size_t)kPieces16;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -39,19 +39,21 @@ bool fold_network(const std::vector<float> &wstream, const std::vector<float> &s
 // true iff every value of an f32 device image (stream + small block) is finite: the condition under which the f32 kernels may skip
 // k-steps whose ReLU inputs are all zero (fma(a, 0, c) = c needs a finite a; a NaN bias must take the dense path's quieting too)
 bool zero_skip_safe(const std::vector<float> &wstream, const std::vector<float> &small);
-// bf16 weight stream in the v1 piece order (round-to-nearest-even; the host's intermediate order that every 16-bit stream is re-packed from); the small-parameter block is shared with fp32.
-void pack_network_bf16(const HostNet &net, std::vector<uint16_t> &wstream);
 uint16_t f32_to_bf16_rne(float v);
-// the first bf16 design's piece order as f32 values, no padding (mlp_layout.h kPiecesV1 x 512): common source of all bf16 streams
-void pack_network_v1order_f32(const HostNet &net, std::vector<float> &v1f);
-void bf16_stream_from_v1order(const std::vector<float> &v1f, std::vector<uint16_t> &wstream);
-// f32 by three-way bf16 split (mlp_kernel_bf16x3.hip): w = w1 + w2 + w3, three pieces per v1 piece
+// f32 by three-way bf16 split (mlp_kernel_bf16x3.hip): w = w1 + w2 + w3
 void split_bf16x3(float v, uint16_t out[3]);
-void x3_stream_from_v1order(const std::vector<float> &v1f, std::vector<uint16_t> &wstream);
-// f32 by two-way f16 split (mlp_kernel_f16x2.hip): w = w1 + w2, two pieces per v1 piece; false if a weight exceeds the f16 range
+// f32 by two-way f16 split (mlp_kernel_f16x2.hip): w = w1 + w2
 void split_f16x2(float v, uint16_t out[2]);
-bool x2_stream_from_v1order(const std::vector<float> &v1f, std::vector<uint16_t> &wstream);
-bool f16_stream_from_v1order(const std::vector<float> &v1f, std::vector<uint16_t> &wstream); // one f16 per weight, bf16_stream_from_v1order's order
+// The four 16-bit weight streams of a network (layouts: mlp_layout.h), each the same weights in the arithmetic's element type and piece order.
+// The two f16 streams are EMPTY if a weight lies outside the f16 range: that arithmetic is then unavailable for the network.
+struct NetStreams {
+    std::vector<uint16_t> bf16v2; // mlp_kernel_bf16v2.hip: one bf16 per weight (round-to-nearest-even), output-tile-major
+    std::vector<uint16_t> f16v2;  // mlp_kernel_f16v2.hip (certify_zero's pre-filter): its f16 twin, the same order
+    std::vector<uint16_t> x3;     // mlp_kernel_bf16x3.hip: three bf16 parts per weight
+    std::vector<uint16_t> x2;     // mlp_kernel_f16x2.hip: two f16 parts per weight
+};
+// All four from the packed f32 image (pack_network's stream or a blob's): every loader calls this.  false if the image has the wrong size.
+bool build_streams(const std::vector<float> &packed_ws, NetStreams &out);
 
 // camera_from_samples (src/lib.rs:614-645)
 void camera_from_values(float near_, float far_, const float origin[3], const float forward[3], const float up[3],

@@ -245,15 +245,12 @@ constexpr int kSmallBytes = kSmallFloats * 4;
 
 constexpr int kLdsBytes = kRingSlots * kChunkBytes + kSmallBytes;
 
-// ---- v1 bf16 stream (no kernel reads it any more: the host's intermediate piece order that every 16-bit stream is re-packed from,
-// nerf_networks.cpp upload_bf16_family): macro-step = 8 KiB (8 pieces of 64 lanes x 8 bf16), 32-KiB chunks.
-// Per input tile (32 k-rows) an 8-tile layer has 2 k-steps x 8 pieces = 2 macro-steps; the 4-tile viewdirs layer
-// 2 k-steps x 4 pieces = 1 macro-step.  viewdirs (9 tiles = 72 KiB) is zero-padded to 3 chunks.
-constexpr int kChunkBytesBf16 = 32768;
-constexpr int kRingSlotsBf16 = 3;
-constexpr int kChunksSigmaBf16 = 1 + 4 * 4 + 5 + 2 * 4;        // dense0 (2 tiles), dense1-4, dense5 (10 tiles), dense6-7 = 30
-constexpr int kChunksFullBf16 = kChunksSigmaBf16 + 4 + 3;       // + bottleneck + viewdirs (padded) = 37
-constexpr int kLdsBytesBf16 = kRingSlotsBf16 * kChunkBytesBf16 + kSmallBytes;
+// ---- 16-bit pieces (what the four 16-bit streams below are made of; host_util.cpp build_streams): a layer's weights in 1-KiB pieces of
+// 64 lanes x 8 elements, one per k-step ks of K = 16 (two per 32-row input tile: ks >> 1 is the tile, ks & 1 its half) and output tile nt:
+//       piece(ks, nt)[l * 8 + j] = W[row(ks >> 1, 8 (ks & 1) + j, l >> 5)][32 nt + (l & 31)]
+// where row(tile, r, h) is the weight row that register r of input tile `tile` holds on lane-half h (regFeature / posSlotFeature /
+// dirSlotFeature below; 0 for a padding slot): element j of the MFMA's B fragment.  K-steps per layer: dense0 4, hidden 16, dense5 20, viewdirs 18.
+constexpr int kPieces16 = 8 * (4 + 4 * 16 + 20 + 3 * 16) + 4 * 18;  // 1160 pieces per network
 
 // ---- bf16 stream v2 (mlp_kernel_bf16v2.hip): output-tile-major.  Per layer, per output tile nt, per k-step (K = 16) one
 // 1-KiB piece; 16-KiB chunks of 16 pieces.  Pieces per layer: dense0 8 x 4, hidden 8 x 16, dense5 8 x 20, viewdirs 4 x 18
@@ -268,8 +265,8 @@ constexpr int kChunksFullBf16V2 = kChunksSigmaBf16V2 + (128 + 72 + 8) / 16; // 7
 constexpr int kLdsBytesBf16V2 = kRingSlotsBf16V2 * kChunkBytesBf16V2 + kSmallBytes;
 constexpr int kPointsPerBlockBf16V2 = 256;
 
-// ---- bf16x3 stream (mlp_kernel_bf16x3.hip, f32 by three-way bf16 split): the first bf16 design's pieces in the same order
-// (layer, input tile, k-step, output tile), each followed by the pieces of the second and third bf16 part of the same
+// ---- bf16x3 stream (mlp_kernel_bf16x3.hip, f32 by three-way bf16 split): the 16-bit pieces in the order
+// (layer, k-step, output tile), each followed by the pieces of the second and third bf16 part of the same
 // weights: a unit = 3 KiB, a k-step of an 8-tile layer = 24 KiB = one chunk, a k-step of viewdirs half a chunk.  No padding.
 constexpr int kChunkBytesX3 = 24576;
 #ifndef NERF_X3_RING_SLOTS
@@ -279,7 +276,6 @@ constexpr int kRingSlotsX3 = NERF_X3_RING_SLOTS; // 3..5 (measured equal: the ke
 constexpr int kChunksSigmaX3 = 2 * 2 + 4 * 16 + 20 + 2 * 16;  // dense0 (2 tiles x 2 k-steps), dense1-4, dense5, dense6-7 = 120
 constexpr int kChunksFullX3 = kChunksSigmaX3 + 16 + 9;        // + bottleneck + viewdirs (9 tiles, one chunk each) = 145
 constexpr int kLdsBytesX3 = kRingSlotsX3 * kChunkBytesX3 + kSmallBytes;
-constexpr int kPiecesV1 = 8 * (4 + 4 * 16 + 20 + 3 * 16) + 4 * 18;  // 1160 pieces of the first bf16 design, without its padding
 
 // ---- f16x2 stream (mlp_kernel_f16x2.hip, f32 by two-way f16 split): the x3 stream's units with two pieces (the f16 parts w1, w2 of
 // the same 32 x 16 weight block) instead of three: a unit = 2 KiB, a k-step of an 8-tile layer = 16 KiB = one chunk, a k-step of

@@ -168,14 +168,14 @@ int nerf_create(int device_id, nerf_ctx **out) try {
     if (const char *env = getenv("NERF_DEPTH_ORDER")) c->depth_order = atoi(env) != 0;
     if (const char *env = getenv("NERF_TILE_ROTATION")) c->tile_rotation = atoi(env) != 0;
     if (const char *env = getenv("NERF_DEBUG_ZSKIP")) {
-        if (atoi(env) > 0 && hipMalloc((void **)&c->d_zskip, 2 * sizeof(unsigned long long)) != hipSuccess) c->d_zskip = nullptr;
+        if (atoi(env) > 0) (void)c->buf[BUF_ZSKIP].ensure(c, 2 * sizeof(unsigned long long));
     }
     if (const char *env = getenv("NERF_DEBUG_CLOCK")) {
-        if (atoi(env) > 0 && hipMalloc((void **)&c->d_clock, (size_t)c->n_cus * 2 * sizeof(unsigned long long)) != hipSuccess) c->d_clock = nullptr;
+        if (atoi(env) > 0) (void)c->buf[BUF_CLOCK].ensure(c, (size_t)c->n_cus * 2 * sizeof(unsigned long long));
         c->clock_coarse = atoi(env) == 2; // 2: the sampling (coarse) launch leaves its clocks instead of the fine one
     }
-    if (hipMalloc((void **)&c->d_skip, sizeof(unsigned long long)) != hipSuccess) c->d_skip = nullptr;
-    if (hipMalloc((void **)&c->d_nonfinite, sizeof(unsigned int)) != hipSuccess) c->d_nonfinite = nullptr;
+    (void)c->buf[BUF_SKIP].ensure(c, sizeof(unsigned long long)); // a counter that could not be allocated stays NULL: its statistic reads 0
+    (void)c->buf[BUF_NONFINITE].ensure(c, sizeof(unsigned int));
     // kernel attributes (dynamic LDS sizes) are per device, not per context: set them once per device and process
     static std::mutex init_mu;
     static std::set<int> init_done;
@@ -202,10 +202,8 @@ void nerf_destroy(nerf_ctx *c) {
     if (!c) return;
     DeviceGuard dg(c->device);
     (void)hipDeviceSynchronize();
-    for (auto &n : c->net) { if (n.wstream) (void)hipFree(n.wstream); if (n.small) (void)hipFree(n.small); if (n.small_f32) (void)hipFree(n.small_f32); if (n.wstream_bf16v2) (void)hipFree(n.wstream_bf16v2); if (n.wstream_x3) (void)hipFree(n.wstream_x3); if (n.wstream_x2) (void)hipFree(n.wstream_x2); if (n.wstream_f16v2) (void)hipFree(n.wstream_f16v2); }
+    for (DevNet &n : c->net) for (DevBuf &b : n.buf) if (b.p) (void)hipFree(b.p);
     for (DevBuf &b : c->buf) if (b.p) (void)hipFree(b.p);
-    void *counters[] = {c->d_clock, c->d_zskip, c->d_skip, c->d_nonfinite}; // fixed-size, allocated by nerf_create
-    for (void *p : counters) if (p) (void)hipFree(p);
     recycle_render(c);
     recycle_dominant(c, 0);
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
@@ -249,11 +247,11 @@ int nerf_kernel_time_query(nerf_ctx *c, double *ms, uint64_t *points, uint32_t *
 
 int nerf_debug_shader_clock_mhz(nerf_ctx *c, double *mhz) try {
     if (!c || !mhz) return fail(c, NERF_ERR_INVALID, "NULL argument");
-    if (!c->d_clock || !c->clock_valid) return fail(c, NERF_ERR_STATE, "set NERF_DEBUG_CLOCK=1 before nerf_create and render a frame first");
+    if (!c->buf[BUF_CLOCK].p || !c->clock_valid) return fail(c, NERF_ERR_STATE, "set NERF_DEBUG_CLOCK=1 before nerf_create and render a frame first");
     DeviceGuard dg(c->device);
     std::vector<unsigned long long> h((size_t)c->n_cus * 2);
     HIP_TRY(c, hipDeviceSynchronize());
-    HIP_TRY(c, hipMemcpy(h.data(), c->d_clock, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(h.data(), c->buf[BUF_CLOCK].p, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     std::vector<double> f;
     for (int i = 0; i < c->n_cus; ++i) if (h[2 * i + 1] > 0) f.push_back(100.0 * (double)h[2 * i] / (double)h[2 * i + 1]);
     if (f.empty()) return fail(c, NERF_ERR_STATE, "no clock samples");
@@ -264,11 +262,11 @@ int nerf_debug_shader_clock_mhz(nerf_ctx *c, double *mhz) try {
 
 int nerf_debug_workgroup_clocks(nerf_ctx *c, uint64_t *out, size_t n_workgroups) try {
     if (!c || !out) return fail(c, NERF_ERR_INVALID, "NULL argument");
-    if (!c->d_clock || !c->clock_valid) return fail(c, NERF_ERR_STATE, "set NERF_DEBUG_CLOCK=1 (or 2) before nerf_create and render a frame first");
+    if (!c->buf[BUF_CLOCK].p || !c->clock_valid) return fail(c, NERF_ERR_STATE, "set NERF_DEBUG_CLOCK=1 (or 2) before nerf_create and render a frame first");
     if (n_workgroups > (size_t)c->n_cus) return fail(c, NERF_ERR_INVALID, "more workgroups than the context launches");
     DeviceGuard dg(c->device);
     HIP_TRY(c, hipDeviceSynchronize());
-    HIP_TRY(c, hipMemcpy(out, c->d_clock, n_workgroups * 2 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(out, c->buf[BUF_CLOCK].p, n_workgroups * 2 * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return NERF_OK;
 } NERF_CATCH(c)
 

@@ -158,6 +158,23 @@ int nerf_debug_fold_network_dir(const char *dir, float *wstream, size_t wstream_
     return debug_pack(dir, true, wstream, wstream_cap, small, small_cap, wstream_len, small_len);
 } NERF_HOST_CATCH
 
+int nerf_debug_network_stream_dir(const char *dir, int kind, uint16_t *out, size_t cap, size_t *n, int *available) try {
+    if (kind < NERF_STREAM_BF16V2 || kind > NERF_STREAM_F16X2) return fail_noctx(NERF_ERR_INVALID, "kind must be one of NERF_STREAM_*");
+    size_t nw = 0;
+    int rc = debug_pack(dir, false, nullptr, 0, nullptr, 0, &nw, nullptr);
+    if (rc) return rc;
+    std::vector<float> ws(nw);
+    if ((rc = debug_pack(dir, false, ws.data(), nw, nullptr, 0, nullptr, nullptr))) return rc;
+    NetStreams s;
+    if (!build_streams(ws, s)) return fail_noctx(NERF_ERR_SHAPE, "internal: packed image has the wrong size");
+    const std::vector<uint16_t> *of[] = {&s.bf16v2, &s.f16v2, &s.x3, &s.x2};
+    const std::vector<uint16_t> &v = *of[kind];
+    if (available) *available = v.empty() ? 0 : 1;
+    if (n) *n = v.size();
+    if (out && !v.empty()) { if (cap < v.size()) return fail_noctx(NERF_ERR_INVALID, "stream buffer too small"); memcpy(out, v.data(), v.size() * sizeof(uint16_t)); }
+    return NERF_OK;
+} NERF_HOST_CATCH
+
 int nerf_debug_zero_skip_network_dir(const char *dir, int *eligible) try {
     if (!eligible) return fail_noctx(NERF_ERR_INVALID, "eligible is NULL");
     size_t nw = 0, ns = 0;

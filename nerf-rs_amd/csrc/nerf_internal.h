@@ -18,21 +18,10 @@
 
 struct MlpArgs;    // mlp_kernel.h
 struct SeqArgs;
+struct ColourArgs;
 struct RayGenArgs; // sampling_kernels.h
 
 namespace nerfint {
-
-struct DevNet {
-    float *wstream = nullptr;   // the f32 kernels' stream: the FOLDED image (mlp_layout.h kChunksFullFolded; host_util.h fold_network)
-    float *small = nullptr;     // small block of the packed image: the 16-bit arithmetics, which run the unfolded head
-    float *small_f32 = nullptr; // small block of the folded image (viewdirs bias = b'): the f32 kernels
-    uint16_t *wstream_bf16v2 = nullptr; // bf16 pieces in output-tile-major order (mlp_kernel_bf16v2.hip)
-    uint16_t *wstream_x3 = nullptr;     // three bf16 parts per weight (mlp_kernel_bf16x3.hip)
-    uint16_t *wstream_x2 = nullptr;     // two f16 parts per weight (mlp_kernel_f16x2.hip); NULL if a weight exceeds the f16 range
-    uint16_t *wstream_f16v2 = nullptr;  // one f16 per weight in wstream_bf16v2's order (mlp_kernel_f16v2.hip: certify_zero's pre-filter); NULL likewise
-    bool loaded = false;
-    bool zero_skip = false; // the f32 kernels may skip all-zero ReLU k-steps: the context allows it and every parameter of the folded image is finite
-};
 
 // certify_zero: a sample is a certain zero iff its 16-bit (pre-filter) density pre-activation is below -margin.  Floors per network WITH THE bf16
 // PRE-FILTER (networks beyond the f16 range), set by the statistic
@@ -75,6 +64,25 @@ struct DevBuf {
     int release(nerf_ctx *c);             // synchronises the device and frees
 };
 
+// A network on the device: every arithmetic's weight stream and the two small blocks, each an owned buffer (nerf_networks.cpp upload_network
+// fills them, nerf_destroy walks them).  A released stream = that arithmetic is unavailable for this network (a weight exceeds the f16 range).
+enum NetBuf {
+    NET_F32,       // the f32 kernels' stream: the FOLDED image (mlp_layout.h kChunksFullFolded; host_util.h fold_network)
+    NET_SMALL,     // small block of the packed image: the 16-bit arithmetics, which run the unfolded head
+    NET_SMALL_F32, // small block of the folded image (viewdirs bias = b'): the f32 kernels
+    NET_BF16V2,    // bf16 pieces in output-tile-major order (mlp_kernel_bf16v2.hip)
+    NET_X3,        // three bf16 parts per weight (mlp_kernel_bf16x3.hip)
+    NET_X2,        // two f16 parts per weight (mlp_kernel_f16x2.hip)
+    NET_F16V2,     // one f16 per weight in NET_BF16V2's order (mlp_kernel_f16v2.hip: certify_zero's pre-filter)
+    NET_BUF_COUNT
+};
+struct DevNet {
+    DevBuf buf[NET_BUF_COUNT];
+    const float *at(NetBuf id) const { return (const float *)buf[id].p; } // as MlpArgs / SeqArgs carry every stream
+    bool loaded = false;    // set once, after every stream of a load is on the device; a load that fails part-way leaves it false
+    bool zero_skip = false; // the f32 kernels may skip all-zero ReLU k-steps: the context allows it and every parameter of the folded image is finite
+};
+
 enum BufId {
     // pass workspace: ensure_workspace grows the seven together (BUF_RGBC only once a coarse_only render asks for it)
     BUF_DIRS, BUF_TC, BUF_SC, BUF_RGBC, BUF_TF, BUF_SF, BUF_RGBF,
@@ -98,6 +106,11 @@ enum BufId {
     BUF_JSTAR,      // ... per ray of a pass: first sample behind the predicted cut
     BUF_CERT_AUX,   // ... {sample, 16-bit (pre-filter) pre-activation} of the audited certificates of a launch
     BUF_ORDER,      // depth-order table of the pass under way: one slot per point of its ordered region
+    // fixed size, allocated by nerf_create (NULL where that failed or the diagnostic is off)
+    BUF_SKIP,       // u64: skipped 128-point tiles (skip_empty)
+    BUF_NONFINITE,  // u32: non-finite density pre-activations (Arith::counts_range)
+    BUF_CLOCK,      // NERF_DEBUG_CLOCK: per workgroup {cycles, 100 MHz ticks} of the last fine-MLP launch
+    BUF_ZSKIP,      // NERF_DEBUG_ZSKIP=1: {executed, total} ReLU k-steps of the f32 launch under way
     BUF_COUNT
 };
 
@@ -158,9 +171,6 @@ struct nerf_ctx {
     float hybrid_tau = 1e-5f;                                        // a draw predicted to move by more than this (in t) flags its ray
     size_t max_export_bytes = (size_t)16 << 30; // budget of BUF_H8: bounds the rays per pass of skip_dead in a SPLIT arithmetic (NERF_MAX_EXPORT_BYTES);
                                                 // 16 GiB = 8 passes per 800x800 frame, 1.4 % slower than one pass of 128 GiB
-    unsigned long long *d_skip = nullptr;  // device counter of skipped 128-point tiles (skip_empty)
-    unsigned int *d_nonfinite = nullptr;   // device counter of non-finite density pre-activations (split arithmetics)
-    unsigned long long *d_clock = nullptr; // diagnostic: per-workgroup {cycles, 100 MHz ticks} of the last fine-MLP launch
     bool clock_valid = false;
     bool clock_coarse = false;             // NERF_DEBUG_CLOCK=2: the clocks are those of the last sampling (coarse) launch
     bool zero_step_skip = true;            // NERF_ZERO_STEP_SKIP=0 at nerf_create: the f32 kernels execute every k-step (networks loaded afterwards)
@@ -168,7 +178,6 @@ struct nerf_ctx {
     bool wave_tiling = true;               // NERF_WAVE_TILING=0 at nerf_create: a wave of a ray-mode f32 launch keeps 32 consecutive samples of one ray (mlp_layout.h)
     bool depth_order = true;               // NERF_DEPTH_ORDER=0 at nerf_create: the fine launch of an image pass keeps the static wave tiling (mlp_layout.h DepthOrder)
     bool tile_rotation = true;             // NERF_TILE_ROTATION=0 at nerf_create: round k's tile of persistent workgroup c of the f32 fused kernel is k G + c (mlp_layout.h rotated_tile)
-    unsigned long long *d_zskip = nullptr; // diagnostic (NERF_DEBUG_ZSKIP=1): {executed, total} ReLU k-steps of the f32 launch under way
     size_t max_rays_per_pass = (size_t)1 << 20;
     std::vector<hipEvent_t> ev_pool;
     std::vector<nerfint::EvPair> last_render; // events of the last render
@@ -260,18 +269,38 @@ int timed(nerf_ctx *c, hipStream_t st, EvKind kind, uint64_t points, F &&fn) {
     return NERF_OK;
 }
 
-// ---- nerf_networks.cpp: weight stream + launcher of the selected arithmetic ---------------------------------------------------------
+// ---- nerf_networks.cpp: one record per arithmetic -- which stream it reads and which kernels run it ---------------------------------------
 inline bool valid_dtype(int d) { return d == NERF_MLP_F32 || d == NERF_MLP_BF16 || d == NERF_MLP_BF16X3 || d == NERF_MLP_F16X2; }
 inline bool split_dtype(int d) { return d == NERF_MLP_BF16X3 || d == NERF_MLP_F16X2; } // f32-accurate operand-splitting arithmetics
-// where a launch in `dtype` counts the points that left its range: the split arithmetics only
-inline unsigned int *nonfinite_of(const nerf_ctx *c, int dtype) { return split_dtype(dtype) ? c->d_nonfinite : nullptr; }
-const float *stream_of(const DevNet &n, int dtype);
-const float *small_of(const DevNet &n, int dtype); // the f32 kernels read the folded image's small block, every other arithmetic the packed one
-// zero-step skipping of the f32 kernels (per network, decided at load) and, for MlpArgs, the context's ray grouping
-void zskip_of(const nerf_ctx *c, const DevNet &n, MlpArgs &a);
-void zskip_of(const nerf_ctx *c, const DevNet &n, SeqArgs &a);
-hipError_t init_mlp_kernels(); // the dynamic-LDS attributes of every MLP kernel of this build, on the current device
-hipError_t launch_mlp(const nerf_ctx *c, int dtype, const MlpArgs &a, bool full, hipStream_t st);
+struct Arith {
+    NetBuf stream, small;    // the f32 kernels read the folded image and its small block, every other arithmetic the packed image's
+    hipError_t (*init[2])(); // the dynamic-LDS attributes of the fused and of the ray-sequential kernels
+    hipError_t (*fused)(const MlpArgs &, bool full, int n_blocks, hipStream_t);
+    hipError_t (*trunk)(const SeqArgs &, bool export_live, int n_blocks, hipStream_t); // skip_dead: ray-sequential trunk ...
+    hipError_t (*colour)(const ColourArgs &, int n_blocks, hipStream_t);               // ... and the colour head of its second launch; NULL: in the trunk launch
+    size_t h8_sample_bytes;            // what the trunk exports per live sample for the colour launch: 0, 512 (packed bf16) or 1024 (f32 tiles)
+    size_t (*h8_bytes)(size_t samples); // ... and the export buffer for so many samples
+    bool counts_range;                 // its launches count the points that left its range (BUF_NONFINITE)
+};
+const Arith &arith_of(int dtype); // dtype: valid_dtype
+inline bool available(const DevNet &n, int dtype) { return n.buf[arith_of(dtype).stream].p != nullptr; } // of a loaded network: all but NERF_MLP_F16X2 always are
+// certify_zero's 16-bit pre-filter (cert_pass, nerf_stage_prefilter*): bf16, or f16 where the network fits its range; sigma-only launches
+// on the packed image's small block.  The f16 twin counts the wave tiles in which an activation left the f16 range.
+struct Prefilter {
+    NetBuf stream;
+    hipError_t (*init)(); // NULL: the arithmetic's own
+    hipError_t (*fused)(const MlpArgs &, bool full, int n_blocks, hipStream_t);
+    hipError_t (*trunk)(const SeqArgs &, bool export_live, int n_blocks, hipStream_t);
+    bool counts_range;
+};
+const Prefilter &prefilter_of(bool f16);
+// What a launch of network n in arithmetic dtype takes from the network and the context: stream, small block, zero-step skipping (f32 kernels;
+// per network, decided at load), the range counter and, for MlpArgs, the context's four launch switches (ray grouping, wave tiling, depth order,
+// tile rotation: the ray-mode launcher of the f32 kernels reads them; tiling also needs rays_per_row, which only an image pass knows)
+void fill_net(const nerf_ctx *c, const DevNet &n, int dtype, MlpArgs &a);
+void fill_net(const nerf_ctx *c, const DevNet &n, int dtype, SeqArgs &a);
+hipError_t init_mlp_kernels(); // every record's init, on the current device
+inline hipError_t launch_mlp(const nerf_ctx *c, int dtype, const MlpArgs &a, bool full, hipStream_t st) { return arith_of(dtype).fused(a, full, c->n_cus, st); }
 // largest batch of nerf_forward_batch*: INT32_MAX minus (persistent workgroups + 1) tiles of the widest kernel (256 points)
 inline size_t max_batch_points(int n_cus) { return (size_t)0x7fffffff - ((size_t)n_cus + 1) * 256; }
 // the f32 sigma-only MLP_MODE_POINTS launch (nerf_density_batch's) over n points

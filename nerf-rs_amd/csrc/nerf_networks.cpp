@@ -1,5 +1,5 @@
-// nerf_networks.cpp -- the networks on the device: upload of a loaded network in every arithmetic's weight stream (the 16-bit streams are
-// re-packed here from one piece order), which stream and which kernel a dtype selects, and the nerf_load_network_* entry points.
+// nerf_networks.cpp -- the networks on the device: the table that says which stream and which kernels an arithmetic selects, the upload of a
+// loaded network in every arithmetic's weight stream, and the nerf_load_network_* entry points.
 #include <hip/hip_runtime.h>
 
 #include <map>
@@ -17,47 +17,57 @@ using namespace nerfint;
 
 namespace nerfint {
 
-const float *stream_of(const DevNet &n, int dtype) {
-    if (dtype == NERF_MLP_BF16X3) return (const float *)n.wstream_x3;
-    if (dtype == NERF_MLP_F16X2) return (const float *)n.wstream_x2;
-    if (dtype == NERF_MLP_F32) return n.wstream;
-    return (const float *)n.wstream_bf16v2;
+const Arith &arith_of(int dtype) {
+    static const Arith table[] = { // indexed by NERF_MLP_*
+        {NET_F32, NET_SMALL_F32, {nerf_mlp_init, nerf_seq_init}, nerf_mlp_launch, nerf_trunk_seq_launch, nullptr, 0, nullptr, false},
+        {NET_BF16V2, NET_SMALL, {nerf_mlp_bf16v2_init, nerf_seq_bf16_init}, nerf_mlp_bf16v2_launch, nerf_trunk_seq_bf16_launch, nerf_colour_bf16_launch,
+         512, nerf_seq_h8_bytes_bf16, false},
+        {NET_X3, NET_SMALL, {nerf_mlp_bf16x3_init, nerf_seq_x3_init}, nerf_mlp_bf16x3_launch, nerf_trunk_seq_x3_launch, nerf_colour_x3_launch,
+         1024, nerf_seq_h8_bytes, true},
+        {NET_X2, NET_SMALL, {nerf_mlp_f16x2_init, nerf_seq_f16x2_init}, nerf_mlp_f16x2_launch, nerf_trunk_seq_f16x2_launch, nerf_colour_f16x2_launch,
+         1024, nerf_seq_h8_bytes, true},
+    };
+    static_assert(NERF_MLP_F32 == 0 && NERF_MLP_BF16 == 1 && NERF_MLP_BF16X3 == 2 && NERF_MLP_F16X2 == 3, "the table's order");
+    return table[dtype];
 }
-const float *small_of(const DevNet &n, int dtype) { return dtype == NERF_MLP_F32 ? n.small_f32 : n.small; }
-// zero-step skipping of the f32 kernels (MlpArgs / SeqArgs; the other arithmetics ignore the two fields): per network, decided at load
-// ... and the context's ray grouping and wave tiling (MlpArgs.ray_grouping, .wave_tiling: the ray-mode launcher of the f32 kernels reads
-// them, nothing else does; tiling also needs MlpArgs.rays_per_row, which only an image pass knows: nerf_render.cpp eval_net)
-void zskip_of(const nerf_ctx *c, const DevNet &n, MlpArgs &a) {
-    a.zero_skip = n.zero_skip ? 1 : 0; a.zskip_stats = c->d_zskip;
+
+const Prefilter &prefilter_of(bool f16) {
+    static const Prefilter table[] = { // the f16 twin's launchers exist sigma-only, without export: they take no such switch
+        {NET_BF16V2, nullptr, nerf_mlp_bf16v2_launch, nerf_trunk_seq_bf16_launch, false},
+        {NET_F16V2, nerf_prefilter_f16v2_init,
+         [](const MlpArgs &a, bool, int n_blocks, hipStream_t st) { return nerf_mlp_f16v2_launch(a, n_blocks, st); },
+         [](const SeqArgs &a, bool, int n_blocks, hipStream_t st) { return nerf_trunk_seq_f16v2_launch(a, n_blocks, st); }, true},
+    };
+    return table[f16 ? 1 : 0];
+}
+
+void fill_net(const nerf_ctx *c, const DevNet &n, int dtype, MlpArgs &a) {
+    const Arith &ar = arith_of(dtype);
+    a.wstream = n.at(ar.stream); a.small_params = n.at(ar.small);
+    a.zero_skip = n.zero_skip ? 1 : 0; a.zskip_stats = c->dev<unsigned long long>(BUF_ZSKIP);
     a.ray_grouping = c->ray_grouping ? 1 : 0; a.wave_tiling = c->wave_tiling ? 1 : 0;
     a.depth_order = c->depth_order ? 1 : 0; a.tile_rotation = c->tile_rotation ? 1 : 0; // the table itself is the pass pipeline's (nerf_render.cpp eval_net)
+    a.nonfinite = ar.counts_range ? c->dev<unsigned int>(BUF_NONFINITE) : nullptr;
 }
-void zskip_of(const nerf_ctx *c, const DevNet &n, SeqArgs &a) { a.zero_skip = n.zero_skip ? 1 : 0; a.zskip_stats = c->d_zskip; }
+void fill_net(const nerf_ctx *c, const DevNet &n, int dtype, SeqArgs &a) {
+    const Arith &ar = arith_of(dtype);
+    a.wstream = n.at(ar.stream); a.small_params = n.at(ar.small);
+    a.zero_skip = n.zero_skip ? 1 : 0; a.zskip_stats = c->dev<unsigned long long>(BUF_ZSKIP);
+    a.nonfinite = ar.counts_range ? c->dev<unsigned int>(BUF_NONFINITE) : nullptr;
+}
 
 hipError_t init_mlp_kernels() {
-    hipError_t e1 = nerf_mlp_init();
-    if (e1 == hipSuccess) e1 = nerf_mlp_bf16v2_init();
-    if (e1 == hipSuccess) e1 = nerf_prefilter_f16v2_init();
-    if (e1 == hipSuccess) e1 = nerf_mlp_bf16x3_init();
-    if (e1 == hipSuccess) e1 = nerf_seq_init();
-    if (e1 == hipSuccess) e1 = nerf_seq_bf16_init();
-    if (e1 == hipSuccess) e1 = nerf_seq_x3_init();
-    if (e1 == hipSuccess) e1 = nerf_mlp_f16x2_init();
-    if (e1 == hipSuccess) e1 = nerf_seq_f16x2_init();
-    return e1;
-}
-
-hipError_t launch_mlp(const nerf_ctx *c, int dtype, const MlpArgs &a, bool full, hipStream_t st) {
-    if (dtype == NERF_MLP_F32) return nerf_mlp_launch(a, full, c->n_cus, st);
-    if (dtype == NERF_MLP_BF16X3) return nerf_mlp_bf16x3_launch(a, full, c->n_cus, st);
-    if (dtype == NERF_MLP_F16X2) return nerf_mlp_f16x2_launch(a, full, c->n_cus, st);
-    return nerf_mlp_bf16v2_launch(a, full, c->n_cus, st);
+    hipError_t e = hipSuccess;
+    for (int dt = NERF_MLP_F32; dt <= NERF_MLP_F16X2 && e == hipSuccess; ++dt)
+        for (auto init : arith_of(dt).init) if (e == hipSuccess) e = init();
+    for (int f16 = 0; f16 < 2 && e == hipSuccess; ++f16) if (prefilter_of(f16).init) e = prefilter_of(f16).init();
+    return e;
 }
 
 hipError_t launch_sigma_points(const nerf_ctx *c, const DevNet &net, const float *d_pts, size_t n, float *d_sigma, hipStream_t st) {
     MlpArgs a{};
     a.mode = MLP_MODE_POINTS;
-    a.wstream = net.wstream; a.small_params = net.small_f32; zskip_of(c, net, a);
+    fill_net(c, net, NERF_MLP_F32, a);
     a.n_points = (int)n; a.pts_soa = d_pts; a.sigma_out = d_sigma;
     return launch_mlp(c, NERF_MLP_F32, a, false, st);
 }
@@ -66,125 +76,42 @@ hipError_t launch_sigma_points(const nerf_ctx *c, const DevNet &net, const float
 
 namespace {
 
-// v1 stream -> v2 stream: the 1-KiB pieces are identical (lane l, element j = W[row(tile, 8 ks + j, l >> 5)][32 nt + (l & 31)]);
-// v1 orders a layer's pieces (k-step, nt), v2 orders them (nt, k-step) and pads viewdirs' 72 pieces to 80.
-static void bf16_v2_from_v1(const std::vector<uint16_t> &v1, std::vector<uint16_t> &v2) {
-    using namespace nerfmlp;
-    v2.clear();
-    v2.reserve((size_t)kChunksFullBf16V2 * kChunkBytesBf16V2 / 2);
-    size_t base = 0; // uint16 elements
-    auto layer = [&](int KS, int NT) {
-        for (int nt = 0; nt < NT; ++nt)
-            for (int ks = 0; ks < KS; ++ks) {
-                const uint16_t *src = &v1[base + ((size_t)ks * NT + nt) * 512];
-                v2.insert(v2.end(), src, src + 512);
-            }
-        base += (size_t)KS * NT * 512;
-    };
-    layer(4, 8);
-    for (int i = 0; i < 4; ++i) layer(16, 8);
-    layer(20, 8);
-    for (int i = 0; i < 3; ++i) layer(16, 8);
-    layer(18, 4);
-    v2.resize((size_t)kChunksFullBf16V2 * kChunkBytesBf16V2 / 2, (uint16_t)0);
-}
-
-int upload_packed(nerf_ctx *c, int which, const std::vector<float> &ws, const std::vector<float> &sm) {
-    if (ws.size() != (size_t)nerfmlp::kChunksFull * nerfmlp::kChunkFloats || sm.size() != (size_t)nerfmlp::kSmallFloats)
-        return fail(c, NERF_ERR_SHAPE, "packed network image has the wrong size for this library build");
-    // the f32 kernels run the bottleneck folded into viewdirs (once per loaded network); the 16-bit arithmetics keep the packed
-    // image's small block (their streams come from upload_bf16_family)
-    std::vector<float> fws, fsm;
-    if (!fold_network(ws, sm, fws, fsm)) return fail(c, NERF_ERR_SHAPE, "internal: folded network image has the wrong size");
-    DevNet &d = c->net[which];
-    if (!d.wstream) HIP_TRY(c, hipMalloc((void **)&d.wstream, fws.size() * sizeof(float)));
-    if (!d.small) HIP_TRY(c, hipMalloc((void **)&d.small, sm.size() * sizeof(float)));
-    if (!d.small_f32) HIP_TRY(c, hipMalloc((void **)&d.small_f32, fsm.size() * sizeof(float)));
-    HIP_TRY(c, hipMemcpy(d.wstream, fws.data(), fws.size() * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(d.small, sm.data(), sm.size() * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(d.small_f32, fsm.data(), fsm.size() * sizeof(float), hipMemcpyHostToDevice));
-    d.loaded = true;
-    d.zero_skip = c->zero_step_skip && zero_skip_safe(fws, fsm); // exact only while every parameter is finite (mlp_f32_core.hip.h tile_steps)
-    c->cert_margin[which] = c->cert_margin_floor[which]; // certify_zero calibrates itself per network (upload_bf16_family, which follows, decides the pre-filter)
+template <class T>
+int upload(nerf_ctx *c, DevBuf &b, const std::vector<T> &v) { // an empty vector releases the buffer: that stream is unavailable
+    if (v.empty()) return b.release(c);
+    const int rc = b.ensure(c, v.size() * sizeof(T));
+    if (rc) return rc;
+    HIP_TRY(c, hipMemcpy(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
     return NERF_OK;
 }
 
-// All bf16-family streams come from one f32 array in the first bf16 design's piece order (host_util.h).
-int upload_bf16_family(nerf_ctx *c, int which, const std::vector<float> &v1f) {
-    if (v1f.size() != (size_t)nerfmlp::kPiecesV1 * 512) return fail(c, NERF_ERR_SHAPE, "internal: bf16 piece array has the wrong size");
+// One network, from its packed f32 image (a directory's or tensor table's pack_network, or a blob), in every arithmetic's form.
+int upload_network(nerf_ctx *c, int which, const std::vector<float> &ws, const std::vector<float> &sm) {
+    if (ws.size() != (size_t)nerfmlp::kChunksFull * nerfmlp::kChunkFloats || sm.size() != (size_t)nerfmlp::kSmallFloats)
+        return fail(c, NERF_ERR_SHAPE, "packed network image has the wrong size for this library build");
+    // the f32 kernels run the bottleneck folded into viewdirs (once per loaded network); the 16-bit arithmetics keep the packed image's small block
+    std::vector<float> fws, fsm;
+    if (!fold_network(ws, sm, fws, fsm)) return fail(c, NERF_ERR_SHAPE, "internal: folded network image has the wrong size");
+    NetStreams s;
+    if (!build_streams(ws, s)) return fail(c, NERF_ERR_SHAPE, "internal: 16-bit stream sizes");
     DevNet &d = c->net[which];
-    std::vector<uint16_t> wb, v2, x3;
-    bf16_stream_from_v1order(v1f, wb);
-    bf16_v2_from_v1(wb, v2);
-    x3_stream_from_v1order(v1f, x3);
-    if (x3.size() != (size_t)nerfmlp::kChunksFullX3 * nerfmlp::kChunkBytesX3 / 2) return fail(c, NERF_ERR_SHAPE, "internal: bf16x3 stream size");
-    if (!d.wstream_bf16v2) HIP_TRY(c, hipMalloc((void **)&d.wstream_bf16v2, v2.size() * sizeof(uint16_t)));
-    HIP_TRY(c, hipMemcpy(d.wstream_bf16v2, v2.data(), v2.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-    if (!d.wstream_x3) HIP_TRY(c, hipMalloc((void **)&d.wstream_x3, x3.size() * sizeof(uint16_t)));
-    HIP_TRY(c, hipMemcpy(d.wstream_x3, x3.data(), x3.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-    {   // the f16 twin of the bf16 v2 stream (certify_zero's pre-filter): the same pieces in the same order, f16-rounded
-        std::vector<uint16_t> hb, h2;
-        const bool fits = f16_stream_from_v1order(v1f, hb);
-        if (fits) {
-            bf16_v2_from_v1(hb, h2); // a permutation of 16-bit elements: the element type does not matter
-            if (h2.size() != v2.size()) return fail(c, NERF_ERR_SHAPE, "internal: f16 v2 stream size");
-            if (!d.wstream_f16v2) HIP_TRY(c, hipMalloc((void **)&d.wstream_f16v2, h2.size() * sizeof(uint16_t)));
-            HIP_TRY(c, hipMemcpy(d.wstream_f16v2, h2.data(), h2.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-        } else if (d.wstream_f16v2) {
-            HIP_TRY(c, hipFree(d.wstream_f16v2));
-            d.wstream_f16v2 = nullptr;
-        }
-        // certify_zero calibrates itself per network: margins start at the floors of the pre-filter this network gets
-        c->cert_prefilter_f16[which] = c->cert_allow_f16 && d.wstream_f16v2 != nullptr;
-        c->cert_margin[which] = c->cert_prefilter_f16[which] ? c->cert_margin_floor_f16[which] : c->cert_margin_floor[which];
-    }
-    std::vector<uint16_t> x2;
-    if (x2_stream_from_v1order(v1f, x2)) { // every weight inside the f16 range (the lego networks: |w| <= 8.3)
-        if (x2.size() != (size_t)nerfmlp::kChunksFullF16X2 * nerfmlp::kChunkBytesF16X2 / 2) return fail(c, NERF_ERR_SHAPE, "internal: f16x2 stream size");
-        if (!d.wstream_x2) HIP_TRY(c, hipMalloc((void **)&d.wstream_x2, x2.size() * sizeof(uint16_t)));
-        HIP_TRY(c, hipMemcpy(d.wstream_x2, x2.data(), x2.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-    } else if (d.wstream_x2) { // a reload with out-of-range weights: NERF_MLP_F16X2 becomes unavailable for this network
-        HIP_TRY(c, hipFree(d.wstream_x2));
-        d.wstream_x2 = nullptr;
-    }
+    d.loaded = false; // until every stream below is on the device
+    int rc;
+    if ((rc = upload(c, d.buf[NET_F32], fws)) || (rc = upload(c, d.buf[NET_SMALL], sm)) || (rc = upload(c, d.buf[NET_SMALL_F32], fsm)) ||
+        (rc = upload(c, d.buf[NET_BF16V2], s.bf16v2)) || (rc = upload(c, d.buf[NET_X3], s.x3)) || (rc = upload(c, d.buf[NET_F16V2], s.f16v2)) ||
+        (rc = upload(c, d.buf[NET_X2], s.x2))) return rc;
+    d.zero_skip = c->zero_step_skip && zero_skip_safe(fws, fsm); // exact only while every parameter is finite (mlp_f32_core.hip.h tile_steps)
+    // certify_zero calibrates itself per network: margins start at the floors of the pre-filter this network gets (f16 where its weights fit)
+    c->cert_prefilter_f16[which] = c->cert_allow_f16 && d.buf[NET_F16V2].p != nullptr;
+    c->cert_margin[which] = c->cert_prefilter_f16[which] ? c->cert_margin_floor_f16[which] : c->cert_margin_floor[which];
+    d.loaded = true;
     return NERF_OK;
 }
 
 int upload_net(nerf_ctx *c, int which, const HostNet &hn) {
     std::vector<float> ws, sm;
     pack_network(hn, ws, sm);
-    int rc = upload_packed(c, which, ws, sm);
-    if (rc) return rc;
-    std::vector<float> v1f;
-    pack_network_v1order_f32(hn, v1f);
-    return upload_bf16_family(c, which, v1f);
-}
-
-// The bf16-family streams hold the same weights in another order; for networks that arrive as a packed f32 blob they are
-// rebuilt from the f32 stream's pieces (piece (s, g): lane l, q -> W[row(s, l >> 5)][32 (4 g + q) + (l & 31)]).
-int bf16_from_f32_stream(nerf_ctx *c, int which, const std::vector<float> &ws) {
-    using namespace nerfmlp;
-    std::vector<float> v1f;
-    v1f.reserve((size_t)kPiecesV1 * 512);
-    size_t layer_base = 0; // floats
-    auto layer = [&](int n_tiles, int NT) {
-        for (int tt = 0; tt < n_tiles; ++tt)
-            for (int ks = 0; ks < 2; ++ks)
-                for (int nt = 0; nt < NT; ++nt)
-                    for (int l = 0; l < 64; ++l)
-                        for (int j = 0; j < 8; ++j) {
-                            const int st = 16 * tt + 8 * ks + j; // f32 k-step that holds register 8 ks + j of tile tt
-                            const size_t piece = layer_base + ((size_t)st * (NT / 4) + nt / 4) * 256;
-                            v1f.push_back(ws[piece + (size_t)l * 4 + (nt & 3)]);
-                        }
-        layer_base += (size_t)n_tiles * 16 * NT * 64;
-    };
-    layer(2, 8);
-    for (int i = 0; i < 4; ++i) layer(8, 8);
-    layer(10, 8);
-    for (int i = 0; i < 3; ++i) layer(8, 8);
-    layer(9, 4);
-    return upload_bf16_family(c, which, v1f);
+    return upload_network(c, which, ws, sm);
 }
 
 } // namespace
@@ -238,8 +165,7 @@ int nerf_load_network_blob(nerf_ctx *c, int which, const char *blob_path) try {
     std::string err;
     const int rrc = read_blob_file(blob_path, ws, sm, err);
     if (rrc) return fail(c, rrc, err);
-    const int rc = upload_packed(c, which, ws, sm);
-    return rc ? rc : bf16_from_f32_stream(c, which, ws);
+    return upload_network(c, which, ws, sm);
 } NERF_CATCH(c)
 
 } // extern "C"

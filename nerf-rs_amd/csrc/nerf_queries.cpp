@@ -39,10 +39,9 @@ static int forward_device(nerf_ctx *c, int which, int dtype, const float *d_pts,
     MlpArgs a{};
     a.mode = MLP_MODE_POINTS;
     if (!valid_dtype(dtype)) return fail(c, NERF_ERR_INVALID, "mlp_dtype must be NERF_MLP_F32, NERF_MLP_BF16, NERF_MLP_BF16X3 or NERF_MLP_F16X2");
-    if (dtype == NERF_MLP_F16X2 && !c->net[which].wstream_x2) return fail(c, NERF_ERR_STATE, "NERF_MLP_F16X2 is unavailable for this network: a weight exceeds the f16 range");
-    a.wstream = stream_of(c->net[which], dtype); a.small_params = small_of(c->net[which], dtype); zskip_of(c, c->net[which], a);
+    if (!available(c->net[which], dtype)) return fail(c, NERF_ERR_STATE, "NERF_MLP_F16X2 is unavailable for this network: a weight exceeds the f16 range");
+    fill_net(c, c->net[which], dtype, a);
     a.n_points = (int)n; a.pts_soa = d_pts; a.dirs_aos = d_dirs; a.sigma_out = d_sigma; a.rgb_out = d_rgb;
-    a.nonfinite = nonfinite_of(c, dtype);
     HIP_TRY(c, launch_mlp(c, dtype, a, true, (hipStream_t)stream));
     return NERF_OK;
 }
@@ -65,11 +64,12 @@ int nerf_forward_batch_ex(nerf_ctx *c, int which, int dtype, const float *pts, c
     Staging s(c, BUF_SCRATCH, c->stream);
     const int i_pts = s.add(F, 3 * n, pts), i_dirs = s.add(F, 3 * n, dirs), i_rgb = s.add(F, 3 * n, nullptr, rgb), i_sig = s.add(F, n, nullptr, sigma);
     if ((rc = s.begin())) return rc;
-    const bool watch = split_dtype(dtype) && c->d_nonfinite;
-    if (watch) HIP_TRY(c, hipMemsetAsync(c->d_nonfinite, 0, sizeof(unsigned int), c->stream));
+    unsigned int *d_bad = c->dev<unsigned int>(BUF_NONFINITE);
+    const bool watch = split_dtype(dtype) && d_bad;
+    if (watch) HIP_TRY(c, hipMemsetAsync(d_bad, 0, sizeof(unsigned int), c->stream));
     if ((rc = forward_device(c, which, dtype, s.at(i_pts), s.at(i_dirs), n, s.at(i_rgb), s.at(i_sig), c->stream))) return rc;
     unsigned int bad = 0;
-    if (watch) HIP_TRY(c, hipMemcpyAsync(&bad, c->d_nonfinite, sizeof bad, hipMemcpyDeviceToHost, c->stream));
+    if (watch) HIP_TRY(c, hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, c->stream));
     if ((rc = s.finish())) return rc;
     if (bad) {
         char msg[320];
@@ -144,11 +144,11 @@ static int density_grid_launch(nerf_ctx *c, int which, const float *lo, const fl
                                float *d_sigma, float threshold, uint32_t *d_bits, int *d_stats, hipStream_t st) {
     MlpArgs a{};
     a.mode = MLP_MODE_GRID;
-    a.wstream = c->net[which].wstream; a.small_params = c->net[which].small_f32; zskip_of(c, c->net[which], a);
+    fill_net(c, c->net[which], NERF_MLP_F32, a);
     a.n_points = (int)n_cells; a.sigma_out = d_sigma;
     for (int k = 0; k < 3; ++k) { a.grid_lo[k] = lo[k]; a.grid_step[k] = step[k]; a.grid_n[k] = dims[k]; }
     a.occ_threshold = threshold; a.occ_bits = d_bits;
-    HIP_TRY(c, nerf_mlp_launch(a, false, c->n_cus, st));
+    HIP_TRY(c, launch_mlp(c, NERF_MLP_F32, a, false, st));
     if (d_stats) HIP_TRY(c, launch_occupancy_stats(d_bits, n_cells, dims[0], dims[1], dims[2], d_stats, st));
     return NERF_OK;
 }
@@ -872,7 +872,8 @@ static int stage_prefilter(nerf_ctx *c, int which, int f16, const float *origin,
     if (!c) return fail(nullptr, NERF_ERR_INVALID, "ctx is NULL");
     const DevNet &net = c->net[which];
     if (!net.loaded) return fail(c, NERF_ERR_STATE, "network not loaded");
-    if (f16 && !net.wstream_f16v2) return fail(c, NERF_ERR_STATE, "the f16 pre-filter is unavailable for this network: a weight exceeds the f16 range");
+    const Prefilter &pf = prefilter_of(f16 != 0);
+    if (!net.buf[pf.stream].p) return fail(c, NERF_ERR_STATE, "the f16 pre-filter is unavailable for this network: a weight exceeds the f16 range");
     *nonfinite_tiles = 0;
     if (n_rays == 0) return NERF_OK;
     DeviceGuard dg(c->device);
@@ -885,14 +886,14 @@ static int stage_prefilter(nerf_ctx *c, int which, int f16, const float *origin,
     if ((rc = s.begin())) return rc;
     uint32_t *cnt = s.at<uint32_t>(i_cnt);
     SeqArgs q{};
-    q.wstream = f16 ? (const float *)net.wstream_f16v2 : stream_of(net, NERF_MLP_BF16); q.small_params = net.small;
+    q.wstream = net.at(pf.stream); q.small_params = net.at(NET_SMALL);
     q.n_rays = (int)n_rays; q.samples_per_ray = spr; q.ray_dirs = s.at(i_d); q.t = s.at(i_t); q.far_ = far_;
     if (origins) q.ray_origins = s.at(i_o);
     else copy3(q.origin, origin);
     q.sigma_out = s.at(i_p);
     q.ray_counter = cnt; q.nonfinite = cnt + 1; q.stats = (unsigned long long *)(cnt + 2);
     q.prefilter = 1; q.prefilter_cut_T = cut_T;
-    HIP_TRY(c, f16 ? nerf_trunk_seq_f16v2_launch(q, c->n_cus, c->stream) : nerf_trunk_seq_bf16_launch(q, false, c->n_cus, c->stream));
+    HIP_TRY(c, pf.trunk(q, false, c->n_cus, c->stream));
     HIP_TRY(c, hipMemcpyAsync(nonfinite_tiles, cnt + 1, 4, hipMemcpyDeviceToHost, c->stream));
     return s.finish();
 }

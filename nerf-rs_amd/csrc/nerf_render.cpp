@@ -164,7 +164,7 @@ struct Pass {
     const float *origins;  // per-ray origins of the pass, or NULL
 };
 
-bool watches_range(const nerf_ctx *c, const RenderJob &j) { return c->d_nonfinite && (split_dtype(j.dtype) || split_dtype(j.dtype_coarse)); }
+bool watches_range(const nerf_ctx *c, const RenderJob &j) { return c->buf[BUF_NONFINITE].p && (arith_of(j.dtype).counts_range || arith_of(j.dtype_coarse).counts_range); }
 
 // sample_importance returns nothing for count == 0 or < 3 coarse samples (src/lib.rs:295-297): the fine net then runs on the coarse samples only
 int fine_samples(const nerf_render_opts *o) { return (o->coarse_only || o->n_fine == 0 || o->n_coarse < 3) ? 0 : o->n_fine; }
@@ -179,8 +179,8 @@ int check_sample_plan(nerf_ctx *c, const nerf_render_opts *o, PlanPart part) {
     } else if (part == PLAN_NETWORKS) {
         if (!c->net[NERF_NET_COARSE].loaded) return fail(c, NERF_ERR_STATE, "coarse network not loaded");
         if (!o->coarse_only && !c->net[NERF_NET_FINE].loaded) return fail(c, NERF_ERR_STATE, "fine network not loaded");
-        if (o->mlp_dtype == NERF_MLP_F16X2 && (!c->net[o->coarse_only ? NERF_NET_COARSE : NERF_NET_FINE].wstream_x2 ||
-                                               (o->hybrid_sampling && !c->net[NERF_NET_COARSE].wstream_x2)))
+        if (!available(c->net[o->coarse_only ? NERF_NET_COARSE : NERF_NET_FINE], o->mlp_dtype) ||
+            (o->hybrid_sampling && !available(c->net[NERF_NET_COARSE], o->mlp_dtype))) // of a loaded network only NERF_MLP_F16X2 can be missing
             return fail(c, NERF_ERR_STATE, "NERF_MLP_F16X2 is unavailable for this network: a weight exceeds the f16 range");
     } else {
         const int nc = o->n_coarse, nf = fine_samples(o);
@@ -201,7 +201,7 @@ void plan_job(const nerf_ctx *c, const nerf_render_opts *o, RenderJob &j) {
     j.coarse_only = o->coarse_only != 0;
     j.seed = o->seed;
     j.dtype = o->mlp_dtype;
-    j.dtype_coarse = o->hybrid_sampling ? (split_dtype(j.dtype) ? j.dtype : c->net[NERF_NET_COARSE].wstream_x2 ? NERF_MLP_F16X2 : NERF_MLP_BF16X3)
+    j.dtype_coarse = o->hybrid_sampling ? (split_dtype(j.dtype) ? j.dtype : available(c->net[NERF_NET_COARSE], NERF_MLP_F16X2) ? NERF_MLP_F16X2 : NERF_MLP_BF16X3)
                                         : (split_dtype(j.dtype) && !o->coarse_only) ? NERF_MLP_F32 : j.dtype;
 }
 
@@ -232,10 +232,9 @@ int prepare_rays(nerf_ctx *c, const RenderJob &j, Pass &p) {
 }
 
 // what every ray-sequential launch of a pass has in common: one network's trunk over the pass's rays from the shared origin
-SeqArgs seq_args(const nerf_ctx *c, const RenderJob &j, const Pass &p, const float *wstream, const float *small_params, int spr, const float *t,
-                 float *sigma_out) {
+SeqArgs seq_args(const nerf_ctx *c, const RenderJob &j, const Pass &p, int spr, const float *t, float *sigma_out) {
     SeqArgs q{};
-    q.wstream = wstream; q.small_params = small_params; q.n_rays = p.n_rays; q.samples_per_ray = spr;
+    q.n_rays = p.n_rays; q.samples_per_ray = spr;
     q.ray_dirs = c->dev(BUF_DIRS); q.t = t; q.far_ = j.far_;
     copy3(q.origin, j.origin);
     q.sigma_out = sigma_out;
@@ -249,29 +248,18 @@ int seq_pass(nerf_ctx *c, const RenderJob &j, const Pass &p, const DevNet &net, 
     SeqCounters *ctr = c->dev<SeqCounters>(BUF_SEQ) + slot;
     HIP_TRY(c, hipMemsetAsync(sigma_out, 0, (size_t)p.n_rays * spr * sizeof(float), st)); // samples behind the cut stay 0
     if (rgb_out) HIP_TRY(c, hipMemsetAsync(rgb_out, 0, (size_t)p.n_rays * spr * 3 * sizeof(float), st)); // weight-0 samples: 0 * 0
-    SeqArgs q = seq_args(c, j, p, stream_of(net, dt), small_of(net, dt), spr, t_in, sigma_out);
-    zskip_of(c, net, q);
+    const Arith &ar = arith_of(dt);
+    SeqArgs q = seq_args(c, j, p, spr, t_in, sigma_out);
+    fill_net(c, net, dt, q);
     q.ray_counter = &ctr->ray_head; q.live_count = &ctr->live_count; q.h8 = c->dev(BUF_H8); q.slot_point = c->dev<unsigned int>(BUF_SLOT_POINT);
     q.rgb_out = rgb_out; // f32: colour passes inside the trunk launch
     q.stats = &ctr->evaluated;
-    q.nonfinite = nonfinite_of(c, dt);
-    int rc = timed(c, st, kind_trunk, (uint64_t)p.n_rays * spr, [&]() -> int {
-        HIP_TRY(c, dt == NERF_MLP_BF16X3 ? nerf_trunk_seq_x3_launch(q, rgb_out != nullptr, c->n_cus, st)
-                   : dt == NERF_MLP_F16X2 ? nerf_trunk_seq_f16x2_launch(q, rgb_out != nullptr, c->n_cus, st)
-                   : dt == NERF_MLP_BF16  ? nerf_trunk_seq_bf16_launch(q, rgb_out != nullptr, c->n_cus, st)
-                                          : nerf_trunk_seq_launch(q, rgb_out != nullptr, c->n_cus, st));
-        return NERF_OK;
-    });
-    if (rc || !rgb_out || dt == NERF_MLP_F32) return rc;
+    int rc = timed(c, st, kind_trunk, (uint64_t)p.n_rays * spr, [&]() -> int { HIP_TRY(c, ar.trunk(q, rgb_out != nullptr, c->n_cus, st)); return NERF_OK; });
+    if (rc || !rgb_out || !ar.colour) return rc;
     ColourArgs k{};
-    k.wstream = stream_of(net, dt); k.small_params = net.small; k.live_count = &ctr->live_count; k.h8 = c->dev(BUF_H8); k.slot_point = c->dev<unsigned int>(BUF_SLOT_POINT);
-    k.ray_dirs = c->dev(BUF_DIRS); k.samples_per_ray = spr; k.rgb_out = rgb_out; k.nonfinite = nonfinite_of(c, dt);
-    return timed(c, st, EV_COLOUR_SIDE, 0, [&]() -> int {
-        HIP_TRY(c, dt == NERF_MLP_BF16X3 ? nerf_colour_x3_launch(k, c->n_cus, st)
-                   : dt == NERF_MLP_F16X2 ? nerf_colour_f16x2_launch(k, c->n_cus, st)
-                                          : nerf_colour_bf16_launch(k, c->n_cus, st));
-        return NERF_OK;
-    });
+    k.wstream = q.wstream; k.small_params = q.small_params; k.live_count = &ctr->live_count; k.h8 = c->dev(BUF_H8); k.slot_point = c->dev<unsigned int>(BUF_SLOT_POINT);
+    k.ray_dirs = c->dev(BUF_DIRS); k.samples_per_ray = spr; k.rgb_out = rgb_out; k.nonfinite = q.nonfinite;
+    return timed(c, st, EV_COLOUR_SIDE, 0, [&]() -> int { HIP_TRY(c, ar.colour(k, c->n_cus, st)); return NERF_OK; });
 }
 
 // Zero certification (nerf_render_opts.certify_zero; DESIGN 4.9, protocol: sampling_kernels.hip k_cert_*): a 16-bit pass (f16 or bf16 operands,
@@ -297,25 +285,24 @@ int cert_pass(nerf_ctx *c, const RenderJob &j, const Pass &p, const MlpArgs &a, 
     const unsigned cap = (unsigned)std::min<size_t>(j.cert_cap, (size_t)n_pts);
     // the pre-filter's arithmetic: f16 where the network fits its range (8 x closer to the exact pre-activations: tighter margins, a shorter
     // list), else bf16; a tile of the f16 pass that saw an activation leave the range counts in range_left and render_device goes back to bf16
-    const bool pf16 = c->cert_prefilter_f16[which];
-    const float *pf_stream = pf16 ? (const float *)net.wstream_f16v2 : stream_of(net, NERF_MLP_BF16);
+    const Prefilter &pf = prefilter_of(c->cert_prefilter_f16[which]);
     MlpArgs b = a;
     b.ray_origins = p.origins;
-    b.wstream = pf_stream; b.small_params = net.small;
-    b.rgb_out = nullptr; b.raw_pre = 1; b.skip_empty = 0; b.skip_counter = nullptr; b.nonfinite = pf16 ? &ctr->range_left : nullptr;
+    b.wstream = net.at(pf.stream); b.small_params = net.at(NET_SMALL);
+    b.rgb_out = nullptr; b.raw_pre = 1; b.skip_empty = 0; b.skip_counter = nullptr; b.nonfinite = pf.counts_range ? &ctr->range_left : nullptr;
     const EvKind kind_side = which == 0 && !rgb_out ? EV_COARSE_MLP : EV_COLOUR_SIDE;
     int rc = timed(c, st, kind_side, 0, [&]() -> int {
         if (c->cert_seq_prefilter || p.origins) {
             // the pre-filter walks each ray front to back and stops where its own (bf16) transmittance predicts the cut, a little
             // later than k_cert_plan will (depth + 0.5): samples it never reaches stay NaN = "not evaluated" = uncertain
             HIP_TRY(c, hipMemsetAsync(sigma_out, 0xFF, (size_t)n_pts * sizeof(float), st));
-            SeqArgs q = seq_args(c, j, p, pf_stream, net.small, spr, t_in, sigma_out);
+            SeqArgs q = seq_args(c, j, p, spr, t_in, sigma_out);
+            q.wstream = b.wstream; q.small_params = b.small_params; q.nonfinite = b.nonfinite;
             q.far_ = j.far_cert; q.ray_origins = p.origins;
             q.ray_counter = &ctr->pf_ray_head; q.stats = &ctr->pf_samples;
             q.prefilter = 1; q.prefilter_cut_T = expf(-(c->cert_depth_limit + 0.5f));
-            q.nonfinite = pf16 ? &ctr->range_left : nullptr;
-            HIP_TRY(c, pf16 ? nerf_trunk_seq_f16v2_launch(q, c->n_cus, st) : nerf_trunk_seq_bf16_launch(q, false, c->n_cus, st));
-        } else HIP_TRY(c, pf16 ? nerf_mlp_f16v2_launch(b, c->n_cus, st) : launch_mlp(c, NERF_MLP_BF16, b, false, st));
+            HIP_TRY(c, pf.trunk(q, false, c->n_cus, st));
+        } else HIP_TRY(c, pf.fused(b, false, c->n_cus, st));
         CertPlanArgs q{};
         q.pre = sigma_out; q.t = t_in; q.n_rays = p.n_rays; q.spr = spr; q.far_ = j.far_cert;
         q.margin = c->cert_margin[which]; q.depth_limit = c->cert_depth_limit;
@@ -333,10 +320,9 @@ int cert_pass(nerf_ctx *c, const RenderJob &j, const Pass &p, const MlpArgs &a, 
     });
     if (rc) return rc;
     MlpArgs l = b;
-    l.wstream = stream_of(net, dt); l.small_params = small_of(net, dt); zskip_of(c, net, l); l.raw_pre = 0; l.mode = MLP_MODE_LIST; l.rgb_out = rgb_out; l.n_points = (int)cap;
+    fill_net(c, net, dt, l); l.raw_pre = 0; l.mode = MLP_MODE_LIST; l.rgb_out = rgb_out; l.n_points = (int)cap;
     l.point_list = c->dev<unsigned int>(BUF_POINT_LIST); l.point_list_count = &ctr->list1_len;
-    if (rgb_out && c->cert_zero_tiles) { l.point_list_count_back = &ctr->list1_back_len; l.skip_empty = 1; l.skip_counter = c->d_skip; }
-    l.nonfinite = nonfinite_of(c, dt);
+    if (rgb_out && c->cert_zero_tiles) { l.point_list_count_back = &ctr->list1_back_len; l.skip_empty = 1; l.skip_counter = c->dev<unsigned long long>(BUF_SKIP); }
     // points = 0: the list's length is known on the device only (nerf_stats.n_exec_* report it after the frame)
     if (cap > 0 && (rc = timed(c, st, kind, 0, [&]() -> int { HIP_TRY(c, launch_mlp(c, dt, l, rgb_out != nullptr, st)); return NERF_OK; }))) return rc;
     return timed(c, st, kind_side, 0, [&]() -> int {
@@ -364,12 +350,11 @@ int eval_net(nerf_ctx *c, const RenderJob &j, const Pass &p, int which, int dt, 
     a.ray_dirs = c->dev(BUF_DIRS);
     if (p.origins && !j.certify) a.mode = MLP_MODE_POINTS;
     else { a.mode = MLP_MODE_RAYS; copy3(a.origin, j.origin); }
-    a.wstream = stream_of(net, dt); a.small_params = small_of(net, dt); zskip_of(c, net, a);
+    fill_net(c, net, dt, a);
     a.n_points = p.n_rays * spr; a.samples_per_ray = spr; a.t = t;
     a.rays_per_row = j.batch ? 0 : p.g.rw; // an image pass is whole rows of the window: the f32 ray-mode launcher may tile its waves over pixel blocks (mlp_layout.h)
     a.sigma_out = sigma_out; a.rgb_out = rgb_out; // the coarse network: sigma only unless its colours are composited (reference discards them, src/lib.rs:404)
-    a.skip_empty = j.skip_empty; a.skip_counter = j.skip_empty ? c->d_skip : nullptr; // only full kernels look at it
-    a.nonfinite = nonfinite_of(c, dt);
+    a.skip_empty = j.skip_empty; a.skip_counter = j.skip_empty ? c->dev<unsigned long long>(BUF_SKIP) : nullptr; // only full kernels look at it
     if (which == (c->clock_coarse ? NERF_NET_COARSE : NERF_NET_FINE)) a.clock_out = j.clock_out;
     if (j.certify) return cert_pass(c, j, p, a, net, which, dt, kind);
     bool full = rgb_out != nullptr;
@@ -406,13 +391,13 @@ int eval_net(nerf_ctx *c, const RenderJob &j, const Pass &p, int which, int dt, 
 int hybrid_redo(nerf_ctx *c, const RenderJob &j, const Pass &p, const ResampleArgs &ra, SeqCounters *hctr) {
     const hipStream_t st = j.st;
     const DevNet &NC = c->net[NERF_NET_COARSE];
-    SeqArgs q = seq_args(c, j, p, NC.wstream, NC.small_f32, j.nc, c->dev(BUF_TC), c->dev(BUF_SC));
-    zskip_of(c, NC, q);
+    SeqArgs q = seq_args(c, j, p, j.nc, c->dev(BUF_TC), c->dev(BUF_SC));
+    fill_net(c, NC, NERF_MLP_F32, q);
     q.ray_counter = &hctr->ray_head; q.stats = &hctr->evaluated;
     q.live_count = nullptr; // hctr->live_count is the LENGTH of the ray list below: this launch never exports (no colour head)
     q.ray_list = c->dev<unsigned int>(BUF_FLAG_LIST); q.ray_list_count = &hctr->live_count; q.zero_fill_after_cut = 1;
     int rc;
-    if ((rc = timed(c, st, EV_COARSE_MLP, 0, [&]() -> int { HIP_TRY(c, nerf_trunk_seq_launch(q, false, c->n_cus, st)); return NERF_OK; }))) return rc;
+    if ((rc = timed(c, st, EV_COARSE_MLP, 0, [&]() -> int { HIP_TRY(c, arith_of(NERF_MLP_F32).trunk(q, false, c->n_cus, st)); return NERF_OK; }))) return rc;
     ResampleArgs rb = ra;
     rb.flag_tau = 0.0f; rb.flag_count = nullptr; rb.flag_list = nullptr;
     rb.ray_list = c->dev<unsigned int>(BUF_FLAG_LIST); rb.ray_list_count = &hctr->live_count;
@@ -455,8 +440,8 @@ int normals_pass(nerf_ctx *c, const RenderJob &j, const Pass &p, const DevNet &n
 int render_passes(nerf_ctx *c, const RenderJob &j, uint32_t *n_passes) {
     const hipStream_t st = j.st;
     int rc;
-    if ((j.skip_empty || j.certify) && c->d_skip) HIP_TRY(c, hipMemsetAsync(c->d_skip, 0, sizeof(unsigned long long), st));
-    if (watches_range(c, j)) HIP_TRY(c, hipMemsetAsync(c->d_nonfinite, 0, sizeof(unsigned int), st));
+    if ((j.skip_empty || j.certify) && c->buf[BUF_SKIP].p) HIP_TRY(c, hipMemsetAsync(c->buf[BUF_SKIP].p, 0, sizeof(unsigned long long), st));
+    if (watches_range(c, j)) HIP_TRY(c, hipMemsetAsync(c->buf[BUF_NONFINITE].p, 0, sizeof(unsigned int), st));
     const DevNet &NC = c->net[NERF_NET_COARSE], &NF = c->net[NERF_NET_FINE];
     uint32_t passes = 0;
     for (size_t r0 = 0; r0 < j.n_rays; r0 += j.pass_rays, ++passes) {
@@ -570,12 +555,12 @@ int finish_stats(nerf_ctx *c, const RenderJob &j, uint32_t passes, nerf_stats *s
                 ms_normal_small);
     if (watches_range(c, j)) {
         unsigned int bad = 0;
-        HIP_TRY(c, hipMemcpy(&bad, c->d_nonfinite, sizeof bad, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(&bad, c->buf[BUF_NONFINITE].p, sizeof bad, hipMemcpyDeviceToHost));
         stats->n_nonfinite_points = bad;
     }
-    if ((j.skip_empty || j.certify) && c->d_skip) { // certify_zero: all-zero tiles of the list's back part (probable zeros, audited certificates)
+    if ((j.skip_empty || j.certify) && c->buf[BUF_SKIP].p) { // certify_zero: all-zero tiles of the list's back part (probable zeros, audited certificates)
         unsigned long long tiles = 0;
-        HIP_TRY(c, hipMemcpy(&tiles, c->d_skip, sizeof tiles, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(&tiles, c->buf[BUF_SKIP].p, sizeof tiles, hipMemcpyDeviceToHost));
         stats->n_colour_skipped_points = (uint64_t)tiles * nerfmlp::kPointsPerBlock;
     }
     // evaluations actually executed
@@ -655,11 +640,11 @@ int image_window(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *o,
 // skip_dead in a split arithmetic or in bf16 (two launches): the compacted trunk outputs are sized for the worst case (every sample
 // of a pass live; 1 KiB each as f32 tiles, 512 B as packed bf16).  The f32 kernel compacts in LDS and runs its colour passes in the
 // same launch: no buffer, no extra passes.
-bool exports_h8(const RenderJob &j) { return j.seq && (split_dtype(j.dtype) || j.dtype == NERF_MLP_BF16); }
+bool exports_h8(const RenderJob &j) { return j.seq && arith_of(j.dtype).h8_sample_bytes > 0; }
 
 // the rays per pass that buffer's budget allows (called with the export mutex held)
 int export_budget(nerf_ctx *c, const RenderJob &j, int RW, size_t *pass_cap) {
-    const size_t h8_sample_bytes = j.dtype == NERF_MLP_BF16 ? 512 : 1024;
+    const size_t h8_sample_bytes = arith_of(j.dtype).h8_sample_bytes;
     size_t budget = c->max_export_bytes, free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) // never more than half of what the device can still give (plus what we already hold)
         budget = std::min(budget, (free_b + c->buf[BUF_H8].bytes) / 2);
@@ -683,7 +668,7 @@ int reserve_seq(nerf_ctx *c, const RenderJob &j, size_t n_passes, std::unique_lo
     HIP_TRY(c, hipMemsetAsync(c->dev(BUF_SEQ), 0, slots * sizeof(SeqCounters), j.st));
     const size_t pass_samples = j.pass_rays * (size_t)j.M;
     if (exports_h8(j)) {
-        const size_t need = j.dtype == NERF_MLP_BF16 ? nerf_seq_h8_bytes_bf16(pass_samples) : nerf_seq_h8_bytes(pass_samples);
+        const size_t need = arith_of(j.dtype).h8_bytes(pass_samples);
         DevBuf &h8 = c->buf[BUF_H8];
         if (need < h8.bytes / 4 && (rc = h8.release(c))) return rc; // a much smaller render: give the big buffer back
         if ((rc = h8.ensure(c, need))) return rc;
@@ -733,7 +718,7 @@ int render_once(nerf_ctx *c, const nerf_camera *cam, const nerf_render_opts *o, 
     j.kind_colour = EV_IMAGE_COLOUR; j.what = "frame"; j.st = st;
     j.skip_empty = o->skip_empty; j.seq = o->skip_dead != 0; j.certify = o->certify_zero != 0;
     j.hybrid = o->hybrid_sampling != 0 && j.nf > 0; // without resampling there is nothing to protect
-    j.clock_out = c->d_clock; // NULL unless NERF_DEBUG_CLOCK=1
+    j.clock_out = c->dev<unsigned long long>(BUF_CLOCK); // NULL unless NERF_DEBUG_CLOCK=1
     copy3(j.origin, cam->pos);
     const int s = w.s, RW = w.cw * s, RH = w.ch * s, RX0 = w.x0 * s, RY0 = w.y0 * s;
     size_t pass_cap = pass_capacity(c, j.M);

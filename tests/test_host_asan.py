@@ -37,6 +37,9 @@ def test_valid_inputs_under_sanitizers(asan, tmp_path):
         assert asan("check_dir", os.path.join(SCENE, net))[0] == 0
         rc, _, out = asan("debug_pack", os.path.join(SCENE, net))
         assert rc == 0 and "packed 593920 + 3136 floats" in out
+        rc, _, out = asan("streams_dir", os.path.join(SCENE, net))
+        assert rc == 0 and "stream 0: 598016 elements, available 1" in out and "stream 1: 598016 elements, available 1" in out
+        assert "stream 2: 1781760 elements, available 1" in out and "stream 3: 1187840 elements, available 1" in out
         blob = tmp_path / f"{net}.nrf"
         assert asan("pack_dir", os.path.join(SCENE, net), blob)[0] == 0
         assert asan("check_blob", blob)[0] == 0
@@ -95,6 +98,7 @@ def test_malformed_weight_directories(asan, tmp_path):
         if name in ("huge dims", "overflowing dim", "negative dim", "non-numeric", "three dims", "no dims", "swapped dims", "zero dims", "empty", "truncated"):
             assert rc != 0, (name, msg)
         assert asan("pack_dir", d, tmp_path / "x.nrf")[0] == rc
+        assert asan("streams_dir", d)[0] == rc
     # tensor files: truncated, empty, oversized by a few bytes, oversized by a lot, not a multiple of four
     for name, data in {"half": None, "empty": b"", "plus3": b"\1\2\3", "odd": b"\0" * 5}.items():
         fresh()
@@ -108,6 +112,17 @@ def test_malformed_weight_directories(asan, tmp_path):
     with open(d / "rgb_bias.bin", "ab") as f:
         f.write(b"\0" * (1 << 20))
     assert asan("check_dir", d)[0] == -4
+
+
+def test_streams_of_a_network_beyond_the_f16_range(asan, tmp_path):
+    """build_streams with a weight of 1e5 and a NaN weight: the two f16 streams are unavailable (no elements), the two bf16 streams are built."""
+    for value in (1e5, np.nan):
+        d = tmp_path / f"net_{value}"
+        shutil.copytree(os.path.join(SCENE, "coarse"), d)
+        w = np.fromfile(d / "dense5_kernel.bin", "<f4"); w[12345] = value; w.tofile(d / "dense5_kernel.bin")
+        rc, _, out = asan("streams_dir", d)
+        assert rc == 0 and "stream 0: 598016 elements, available 1" in out and "stream 2: 1781760 elements, available 1" in out, out
+        assert "stream 1: 0 elements, available 0" in out and "stream 3: 0 elements, available 0" in out, out
 
 
 def test_malformed_blobs(asan, tmp_path):
