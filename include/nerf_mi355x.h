@@ -192,7 +192,15 @@ typedef struct {
  *                           its bits (nerf_stage_depth_order shows the order).
  *   NERF_TILE_ROTATION=0    the persistent workgroups of the fused f32 kernel take tile k G + c in round k, not k G + ((c + k) mod G): the
  *                           rotation spreads tiles of systematically different cost (sample index, depth rank) over all workgroups.
- *   NERF_DEBUG_ZSKIP=1      diagnostic: every f32 MLP launch synchronises and prints its executed / total ReLU k-steps to stderr.
+ *   NERF_EMPTY_TILE_VOTE=0  the colour-producing ray-mode launches of a plain render (NERF_MLP_F32, NERF_MLP_BF16X3, NERF_MLP_F16X2; image renders
+ *                           and ray batches with one origin) evaluate the colour head of every sample.  Default: the four waves of a workgroup
+ *                           vote over the 128 densities of their tile, and a tile whose densities are all 0 writes rgb = 0 and skips the colour
+ *                           head -- such samples have weight 0, every output keeps its bits.  skip_empty keeps its meaning (and its mapping);
+ *                           n_colour_skipped_points of a plain render stays 0.
+ *   NERF_DEBUG_ZSKIP=1      diagnostic: every f32 MLP launch synchronises and prints its executed / total ReLU k-steps to stderr.  The counters
+ *                           describe the dense colour head: such a context runs without the empty-tile vote.
+ *   NERF_DEBUG_EMPTY_TILES=1  diagnostic: every launch that takes the empty-tile vote synchronises and prints "nerf empty tiles: <kernel>
+ *                           tiles_skipped=N tiles=M" to stderr.
  *   NERF_DEBUG_CLOCK=1      diagnostic: nerf_debug_shader_clock_mhz, nerf_debug_workgroup_clocks of the fine launch; 2: of the sampling launch. */
 int nerf_create(int device_id, nerf_ctx **out);
 void nerf_destroy(nerf_ctx *ctx);

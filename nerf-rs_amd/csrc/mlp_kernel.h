@@ -68,6 +68,11 @@ struct MlpArgs {
     int order_tiles, order_points;
     // f32 fused kernel, every mode: round k's tile of workgroup c is k G + ((c + k) mod G) (mlp_layout.h rotated_tile); 0: k G + c
     int tile_rotation;
+    // full f32 and split-arithmetic kernels (appended likewise): take skip_empty's vote and skip path (a tile whose 128 sigmas are all 0 writes
+    // rgb = 0 and skips the colour head; exact) without anything else that skip_empty means -- the launch keeps its mapping, depth ordering
+    // included, and skip_counter stays NULL unless a diagnostic attaches it.  The host sets it for the full ray-mode launches of a plain render
+    // (nerf_render.cpp eval_net; NERF_EMPTY_TILE_VOTE).
+    int empty_vote;
 };
 
 // The ordered region of a launch with these arguments (n_points, samples_per_ray, rays_per_row, mode, skip_empty and the two switches

@@ -174,7 +174,7 @@ __global__ __launch_bounds__(256, 1) void nerf_mlp_kernel(const MlpArgs A) {
             }
         } else
         if (valid && h == 0) A.sigma_out[i] = audit ? pre : sigma;
-        if (FULL && A.skip_empty) {
+        if (FULL && (A.skip_empty || A.empty_vote)) {
             // Empty-tile skip (exact): if sigma == 0 for all 128 points of this workgroup's tile, then
             // alpha = 1 - exp(-0 * delta) = 0 and w = T * 0 = 0 exactly for each of them (src/lib.rs:271-272), so their
             // colours never reach a pixel: skip viewdirs' + rgb (6.9 % of a full evaluation), write rgb = 0.
@@ -186,6 +186,9 @@ __global__ __launch_bounds__(256, 1) void nerf_mlp_kernel(const MlpArgs A) {
                 }
                 if (A.skip_counter && tid == 0) atomicAdd(A.skip_counter, 1ull);
                 pipe_restart(P);
+#if NERF_DIAG_RESTART_TWICE // timing-only variant (make variant): a second, idle restart -- the frame-time difference prices one
+                pipe_restart(P);
+#endif
                 continue;
             }
         }

@@ -170,7 +170,7 @@ __global__ __launch_bounds__(256, 1) void SPLIT_KERNEL_FUSED(const MlpArgs A) {
         if (valid && h == 0) A.sigma_out[i] = audit ? pre : sigma;
         if (!FULL) range_check(P, A.nonfinite, valid);
 
-        if (FULL && A.skip_empty) { // exact empty-tile skip, see mlp_kernel.hip
+        if (FULL && (A.skip_empty || A.empty_vote)) { // exact empty-tile skip, see mlp_kernel.hip
             LDS_AS int *vote = (LDS_AS int *)(lds + kRS * kCB) + kMiscOff + 8;
             const bool any_wg = tile_has_density(vote, valid && sigma > 0.0f, wave, lane);
             if (!any_wg) {

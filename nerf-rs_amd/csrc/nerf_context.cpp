@@ -167,8 +167,13 @@ int nerf_create(int device_id, nerf_ctx **out) try {
     if (const char *env = getenv("NERF_WAVE_TILING")) c->wave_tiling = atoi(env) != 0;
     if (const char *env = getenv("NERF_DEPTH_ORDER")) c->depth_order = atoi(env) != 0;
     if (const char *env = getenv("NERF_TILE_ROTATION")) c->tile_rotation = atoi(env) != 0;
+    if (const char *env = getenv("NERF_EMPTY_TILE_VOTE")) c->empty_tile_vote = atoi(env) != 0;
+    if (const char *env = getenv("NERF_DEBUG_EMPTY_TILES")) c->debug_empty_tiles = atoi(env) > 0;
     if (const char *env = getenv("NERF_DEBUG_ZSKIP")) {
-        if (atoi(env) > 0) (void)c->buf[BUF_ZSKIP].ensure(c, 2 * sizeof(unsigned long long));
+        if (atoi(env) > 0) {
+            (void)c->buf[BUF_ZSKIP].ensure(c, 2 * sizeof(unsigned long long));
+            c->empty_tile_vote = false; // the k-step counters describe the dense colour head: a voted-away head would take its k-steps out of both
+        }
     }
     if (const char *env = getenv("NERF_DEBUG_CLOCK")) {
         if (atoi(env) > 0) (void)c->buf[BUF_CLOCK].ensure(c, (size_t)c->n_cus * 2 * sizeof(unsigned long long));

@@ -107,7 +107,7 @@ enum BufId {
     BUF_CERT_AUX,   // ... {sample, 16-bit (pre-filter) pre-activation} of the audited certificates of a launch
     BUF_ORDER,      // depth-order table of the pass under way: one slot per point of its ordered region
     // fixed size, allocated by nerf_create (NULL where that failed or the diagnostic is off)
-    BUF_SKIP,       // u64: skipped 128-point tiles (skip_empty)
+    BUF_SKIP,       // u64: skipped 128-point tiles (skip_empty; NERF_DEBUG_EMPTY_TILES: of the voted launch under way)
     BUF_NONFINITE,  // u32: non-finite density pre-activations (Arith::counts_range)
     BUF_CLOCK,      // NERF_DEBUG_CLOCK: per workgroup {cycles, 100 MHz ticks} of the last fine-MLP launch
     BUF_ZSKIP,      // NERF_DEBUG_ZSKIP=1: {executed, total} ReLU k-steps of the f32 launch under way
@@ -178,6 +178,8 @@ struct nerf_ctx {
     bool wave_tiling = true;               // NERF_WAVE_TILING=0 at nerf_create: a wave of a ray-mode f32 launch keeps 32 consecutive samples of one ray (mlp_layout.h)
     bool depth_order = true;               // NERF_DEPTH_ORDER=0 at nerf_create: the fine launch of an image pass keeps the static wave tiling (mlp_layout.h DepthOrder)
     bool tile_rotation = true;             // NERF_TILE_ROTATION=0 at nerf_create: round k's tile of persistent workgroup c of the f32 fused kernel is k G + c (mlp_layout.h rotated_tile)
+    bool empty_tile_vote = true;           // NERF_EMPTY_TILE_VOTE=0 at nerf_create (or NERF_DEBUG_ZSKIP=1: the k-step diagnostic describes the dense colour head): full ray-mode launches of a plain render evaluate the colour head of all-empty tiles too (MlpArgs.empty_vote)
+    bool debug_empty_tiles = false;        // NERF_DEBUG_EMPTY_TILES=1 at nerf_create: every voted launch counts its skipped tiles in BUF_SKIP and prints them (synchronises: a diagnostic)
     size_t max_rays_per_pass = (size_t)1 << 20;
     std::vector<hipEvent_t> ev_pool;
     std::vector<nerfint::EvPair> last_render; // events of the last render

@@ -358,6 +358,15 @@ int eval_net(nerf_ctx *c, const RenderJob &j, const Pass &p, int which, int dt, 
     if (which == (c->clock_coarse ? NERF_NET_COARSE : NERF_NET_FINE)) a.clock_out = j.clock_out;
     if (j.certify) return cert_pass(c, j, p, a, net, which, dt, kind);
     bool full = rgb_out != nullptr;
+    // the empty-tile vote of a plain render (MlpArgs.empty_vote; exact): every full ray-mode launch of the f32 and split kernels, whatever its
+    // mapping.  skip_empty renders keep their own switch with all it means; the 16-bit kernel and points mode keep what they have.
+    const bool voted = c->empty_tile_vote && full && a.mode == MLP_MODE_RAYS && !j.skip_empty && dt != NERF_MLP_BF16;
+    a.empty_vote = voted ? 1 : 0;
+    const bool count_votes = voted && c->debug_empty_tiles && c->buf[BUF_SKIP].p; // NERF_DEBUG_EMPTY_TILES: never on in timed runs
+    if (count_votes) {
+        a.skip_counter = c->dev<unsigned long long>(BUF_SKIP);
+        HIP_TRY(c, hipMemsetAsync(a.skip_counter, 0, sizeof(unsigned long long), st));
+    }
     if (p.origins) {
         // only the f32 kernel has a sigma-only points mode: a bf16 sampling pass over expanded points runs the full kernel (the same
         // densities) and leaves its colours in the fine pass's buffer, which that pass overwrites
@@ -382,7 +391,14 @@ int eval_net(nerf_ctx *c, const RenderJob &j, const Pass &p, int which, int dt, 
             a.order_table = c->dev<unsigned int>(BUF_ORDER);
         }
     }
-    return timed(c, st, kind, (uint64_t)a.n_points, [&]() -> int { HIP_TRY(c, launch_mlp(c, dt, a, full, st)); return NERF_OK; });
+    const int rc = timed(c, st, kind, (uint64_t)a.n_points, [&]() -> int { HIP_TRY(c, launch_mlp(c, dt, a, full, st)); return NERF_OK; });
+    if (rc || !count_votes) return rc;
+    unsigned long long tiles = 0; // the read synchronises, as nerf_zskip_print does
+    HIP_TRY(c, hipMemcpyAsync(&tiles, a.skip_counter, sizeof tiles, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    static const char *const kernels[4] = {"nerf_mlp_kernel<full,rays>", "", "nerf_mlp_kernel_bf16x3<full,rays>", "nerf_mlp_kernel_f16x2<full,rays>"}; // by NERF_MLP_*
+    fprintf(stderr, "nerf empty tiles: %s tiles_skipped=%llu tiles=%d\n", kernels[dt], tiles, (a.n_points + nerfmlp::kPointsPerBlock - 1) / nerfmlp::kPointsPerBlock);
+    return NERF_OK;
 }
 
 // hybrid_sampling, after the first resample ra: the coarse densities came from the split arithmetic.  Redo, in exact f32, the rays with a
