@@ -153,6 +153,8 @@ extern "C" {
     pub fn nerf_debug_wave_tiling(rows: c_int, rays_per_row: c_int, samples_per_ray: c_int, full: c_int, ray_grouping: c_int, wave_tiling: c_int,
                                   slot: *mut i32) -> c_int;
     pub fn nerf_debug_tile_rotation(n_tiles: c_int, n_workgroups: c_int, rotation: c_int, workgroup_of_tile: *mut i32, round_of_tile: *mut i32) -> c_int;
+    pub fn nerf_debug_coarse_cut_walk(rows: c_int, rays_per_row: c_int, samples_per_ray: c_int, ray_grouping: c_int, cut_block: c_int, cut_after: c_int,
+                                      tiles: *mut i32, tiles_cap: usize, blocks: *mut i32, block_tiles: *mut i32) -> c_int;
     pub fn nerf_debug_shader_clock_mhz(ctx: *mut nerf_ctx, mhz: *mut f64) -> c_int;
     pub fn nerf_debug_workgroup_clocks(ctx: *mut nerf_ctx, out: *mut u64, n_workgroups: usize) -> c_int;
     pub fn nerf_forward_batch(ctx: *mut nerf_ctx, which: c_int, pts_soa: *const f32, dirs_aos: *const f32, n: usize,

@@ -197,8 +197,19 @@ typedef struct {
  *                           vote over the 128 densities of their tile, and a tile whose densities are all 0 writes rgb = 0 and skips the colour
  *                           head -- such samples have weight 0, every output keeps its bits.  skip_empty keeps its meaning (and its mapping);
  *                           n_colour_skipped_points of a plain render stays 0.
+ *   NERF_COARSE_CUT=0       the density-only NERF_MLP_F32 sampling launch of a plain image render evaluates every coarse sample.  Default, where
+ *                           only the resampler reads the launch's densities (not coarse_only, skip_dead, certify_zero or n_fine = 0 renders, not
+ *                           ray batches) and the launch is tiled 8 x 4 pixels x 1 sample (see NERF_WAVE_TILING): a workgroup walks the samples of
+ *                           a pixel block front to back, keeps each ray's transmittance as the resampler will compute it, and leaves the block
+ *                           once all its 32 rays are behind the reference's T < 1e-4 cut -- the resampler gives every sample behind the cut the
+ *                           weight 0 whatever its density, so every output keeps its bits.  The NERF_MLP_BF16X3 / NERF_MLP_F16X2 renders' f32
+ *                           sampling launch takes it too.  The tiles of such a launch are not grouped (NERF_RAY_GROUPING).  A cut launch hands
+ *                           out whole pixel blocks, so only launches of at least 16 blocks per compute unit are cut (131 072 rays on 256 units:
+ *                           fewer would leave workgroups idle); NERF_COARSE_CUT=2 cuts every qualifying launch (tests, diagnostics).
  *   NERF_DEBUG_ZSKIP=1      diagnostic: every f32 MLP launch synchronises and prints its executed / total ReLU k-steps to stderr.  The counters
- *                           describe the dense colour head: such a context runs without the empty-tile vote.
+ *                           describe the dense colour head and every sample: such a context runs without the empty-tile vote and the coarse cut.
+ *   NERF_DEBUG_COARSE_CUT=1  diagnostic: every launch that takes the coarse cut synchronises and prints "nerf coarse cut: nerf_mlp_kernel<sigma,rays>
+ *                           tiles_skipped=N tiles=M blocks=B" to stderr.
  *   NERF_DEBUG_EMPTY_TILES=1  diagnostic: every launch that takes the empty-tile vote synchronises and prints "nerf empty tiles: <kernel>
  *                           tiles_skipped=N tiles=M" to stderr.
  *   NERF_DEBUG_CLOCK=1      diagnostic: nerf_debug_shader_clock_mhz, nerf_debug_workgroup_clocks of the fine launch; 2: of the sampling launch. */
@@ -275,6 +286,17 @@ int nerf_debug_wave_tiling(int rows, int rays_per_row, int samples_per_ray, int 
  * kernel's own tile walk run on the host (rotation != 0: round k's tile of workgroup c is k G + ((c + k) mod G); 0: k G + c).  Both
  * tables hold n_tiles entries; a tile nobody takes keeps -1, a tile taken twice -2 (neither may occur).  No device needed. */
 int nerf_debug_tile_rotation(int n_tiles, int n_workgroups, int rotation, int32_t *workgroup_of_tile, int32_t *round_of_tile);
+/* The order in which the density-only sampling launch of an image pass of `rows` whole rows of rays_per_row rays walks its workgroup tiles
+ * under the coarse cut (see NERF_COARSE_CUT at nerf_create; ray_grouping: the context's switch, which the rows behind the pixel blocks keep):
+ * the kernel's own unit-to-tile functions run on the host, unit after unit.  *blocks = the launch's 8 x 4 pixel blocks, each *block_tiles =
+ * samples_per_ray / 4 consecutive tiles of nerf_debug_wave_tiling's table with ray_grouping = 0 (wave w of a block's tile k: sample index
+ * 4 k + w of its 32 rays); the tiles behind them are units of their own.  Block cut_block is taken to be cut behind its tile cut_after
+ * (0-based; cut_block < 0: no block is cut) and the walk leaves it there.  tiles[i] = the i-th tile visited; returns how many were (a negative
+ * value: an error code), at most ceil(rows rays_per_row samples_per_ray / 128) <= tiles_cap.  *blocks = 0: the launch does not qualify for the
+ * cut (samples_per_ray no multiple of 32, fewer than 4 rows, rays_per_row no multiple of 8) and the table is 0, 1, 2, ...  blocks, block_tiles
+ * may be NULL.  No device needed. */
+int nerf_debug_coarse_cut_walk(int rows, int rays_per_row, int samples_per_ray, int ray_grouping, int cut_block, int cut_after, int32_t *tiles,
+                               size_t tiles_cap, int32_t *blocks, int32_t *block_tiles);
 
 /* ---- S2: Network::forward_batch (src/network.rs:197-237) -------------------------------------------------- */
 /* host pointers, synchronous.  n == 0 is a no-op (src/network.rs:199-201).

@@ -85,6 +85,8 @@ PROTOTYPES = {
     "nerf_debug_certify_policy": (C.c_int, [C.c_float, C.c_uint64, C.c_uint64, C.c_float, C.c_float, f32p]),
     "nerf_debug_ray_grouping": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
     "nerf_debug_tile_rotation": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "nerf_debug_coarse_cut_walk": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_size_t,
+                                            C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "nerf_debug_wave_tiling": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
     "nerf_forward_batch": (C.c_int, [C.c_void_p, C.c_int, f32p, f32p, C.c_size_t, f32p, f32p]),
     "nerf_forward_batch_ex": (C.c_int, [C.c_void_p, C.c_int, C.c_int, f32p, f32p, C.c_size_t, f32p, f32p]),

@@ -73,7 +73,26 @@ struct MlpArgs {
     // included, and skip_counter stays NULL unless a diagnostic attaches it.  The host sets it for the full ray-mode launches of a plain render
     // (nerf_render.cpp eval_net; NERF_EMPTY_TILE_VOTE).
     int empty_vote;
+    // f32 fused kernel, the sigma-only MLP_MODE_RAYS launch of a plain render whose densities only the resampler reads (appended likewise): the
+    // coarse cut (mlp_layout.h RayCutWalk).  A workgroup walks the samples of an 8 x 4 pixel block front to back, four sample indices per tile,
+    // keeps every ray's transmittance as the resampler will compute it (sample_alpha.hip.h) and leaves the block once all 32 rays are behind
+    // the reference's T < 1e-4 cut; the samples it does not evaluate get sigma = 0 (the resampler gives them the weight 0 whatever they hold).
+    // The host sets it in nerf_render.cpp eval_net alone (NERF_COARSE_CUT), where nerf_mlp_ray_cut says the launch qualifies, with the rays' far
+    // and the context's counters: cut_counters[0] hands out the units (the launcher zeroes it in front of the launch), the u64 at
+    // cut_counters + 2 counts the tiles not evaluated when cut_count is set (NERF_DEBUG_COARSE_CUT; the caller zeroes and reads it).
+    int ray_cut;
+    float ray_cut_far;
+    unsigned int *cut_counters;
+    int cut_count;
 };
+
+// The walk of a launch with these arguments under the coarse cut (n_points, samples_per_ray, rays_per_row, mode and the two switches
+// wave_tiling / ray_grouping); blocks == 0: the launch does not qualify and keeps its static mapping.
+inline nerfmlp::RayCutWalk nerf_mlp_ray_cut(const MlpArgs &a, bool full) {
+    if (full || a.mode != MLP_MODE_RAYS || !a.cut_counters) return nerfmlp::RayCutWalk{0, 0, 0, 0};
+    const nerfmlp::RayLaunchMap m = nerfmlp::ray_launch_map_of(a.n_points, a.samples_per_ray, a.rays_per_row, false, a.ray_grouping != 0, a.wave_tiling != 0);
+    return nerfmlp::ray_cut_walk_of(nerfmlp::ray_cut_map_of(m), a.n_points);
+}
 
 // The ordered region of a launch with these arguments (n_points, samples_per_ray, rays_per_row, mode, skip_empty and the two switches
 // wave_tiling / depth_order); tiles == 0: the launch does not qualify and needs no table.

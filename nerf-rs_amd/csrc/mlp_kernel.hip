@@ -28,6 +28,9 @@
 //     densities are, so depth, not the sample index, says which samples of neighbouring rays lie together.
 //   * the persistent workgroups rotate through the tiles of a round (mlp_layout.h rotated_tile), so that tiles whose cost follows their
 //     position in the launch (sample index, depth rank) are spread over all workgroups.
+//   * the sigma-only ray-mode launch whose densities only the resampler reads walks the samples of each 8 x 4 pixel block front to back and
+//     leaves the block once all its 32 rays are behind the reference's T < 1e-4 cut (mlp_layout.h coarse cut; the CUT instantiation): the
+//     resampler gives those samples the weight 0 whatever their density.
 // Per 32-point wave tile: at most 8256 MFMAs (full; 9280 before the fold) / 7680 (sigma only) x 64 cycles.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -35,14 +38,16 @@
 
 #include "mlp_f32_core.hip.h"
 #include "mlp_kernel.h"
+#include "sample_alpha.hip.h"
 
 using namespace nerfmlp;
 using namespace mlpdev;
 
 using namespace mlpf32;
 
-template <bool FULL, int MODE>
+template <bool FULL, int MODE, bool CUT = false>
 __global__ __launch_bounds__(256, 1) void nerf_mlp_kernel(const MlpArgs A) {
+    static_assert(!CUT || (!FULL && MODE == MLP_MODE_RAYS), "the coarse cut belongs to the sigma-only ray-mode launch");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const LDS_AS char *lds = (const LDS_AS char *)smem;
     const LDS_AS float *small = (const LDS_AS float *)(lds + kRingSlots * kChunkBytes);
@@ -115,21 +120,52 @@ __global__ __launch_bounds__(256, 1) void nerf_mlp_kernel(const MlpArgs A) {
     auto entry_of = [&](int T) {
         return ordered(T) ? (int)min(A.order_table[(size_t)T * kPointsPerBlock + wave * kPointsPerWave + p], (unsigned)order_points - 1u) : 0;
     };
+    // Coarse cut (mlp_layout.h RayCutWalk; the CUT instantiation, launched for A.ray_cut alone -- every other launch of the sigma-only ray-mode
+    // kernel runs the instantiation without it, whose code is what it was): the workgroup takes units -- pixel blocks of
+    // block_tiles consecutive tiles, then the single tiles of the untiled rows -- and walks a block's tiles front to back.  `unit` is the one under
+    // way, unit_next the one held ahead (its first tile is the look-ahead of a block's last tile), unit_next2 the one the counter handed out
+    // during the first tile of `unit`: thread 0 asks for it in that tile's prologue and passes it on through LDS at the tile's exchange barrier.
+    // cT / cdone: the transmittance of this lane's ray behind the block's samples so far and whether it is cut (sample_alpha.hip.h), the same in
+    // all four waves: each applies the tile's four alphas, which the waves exchange through LDS, in index order.  t_end: the t behind this lane's
+    // sample (the next sample's, far behind the last), loaded one tile ahead with the tile's other inputs.
     const int G = gridDim.x;
+    RayCutWalk cw = {0, 0, 0, 0};
+    int unit = (int)blockIdx.x, unit_next = G + (int)blockIdx.x, unit_next2 = 0;
+    bool unit_first = true, cdone = false;
+    float cT = 1.0f, t_end_next = 0.f;
+    unsigned unit_asked = 0;
+    LDS_AS float *xch = (LDS_AS float *)(smem + kLdsBytes); // kCutLdsBytes behind the kernel's own, in a cut launch only
+    if constexpr (CUT) cw = ray_cut_walk_of(A.ray_map, n_points);
+    // t behind the lane's sample in tile T_ of unit u_ (slot_: the lane's slot there); tiles outside the blocks have no cut
+    auto t_end_of = [&](int T_, int u_, int slot_) -> float {
+        if (T_ >= cw.rest_first) return 0.f;
+        const int s = (T_ - u_ * cw.block_tiles) * kWavesPerBlock + wave;
+        return s + 1 < A.samples_per_ray ? A.t[slot_ + 1] : A.ray_cut_far;
+    };
+    const int tile0 = CUT ? ray_cut_unit_tile(cw, unit, n_tiles) : (int)blockIdx.x; // round 0's tile
     TileWalk walk = {0, 0};
     auto next_round_tile = [&]() { return tile_walk_next(walk, (int)blockIdx.x, G, A.tile_rotation != 0); };
     int tile_next = next_round_tile();  // round 1's tile (round 0's is blockIdx.x)
     int tile_next2 = next_round_tile(); // round 2's
-    int base_next = base_of(blockIdx.x); // wave-uniform
-    int ord_cur = entry_of(blockIdx.x), ord_next = entry_of(tile_next); // ORDER only: this lane's table entry of the coming tile and of the one behind it
-    RawIn nxt = load_raw_at<LOAD>(A, ordered(blockIdx.x) ? ord_cur : base_next + lane_of(blockIdx.x)); // the next tile's t / direction are loaded one tile ahead
-    for (int tile = blockIdx.x; tile < n_tiles; tile = tile_next, tile_next = tile_next2, tile_next2 = next_round_tile()) {
+    int base_next = base_of(tile0); // wave-uniform
+    int ord_cur = entry_of(tile0), ord_next = entry_of(tile_next); // ORDER only: this lane's table entry of the coming tile and of the one behind it
+    RawIn nxt = load_raw_at<LOAD>(A, ordered(tile0) ? ord_cur : base_next + lane_of(tile0)); // the next tile's t / direction are loaded one tile ahead
+    if constexpr (CUT) t_end_next = t_end_of(tile0, unit, base_next + lane_of(tile0));
+    for (int tile = tile0; tile < n_tiles; tile = tile_next, tile_next = tile_next2, tile_next2 = next_round_tile()) {
+        if constexpr (CUT) { // the tile to look ahead to: the unit's next one, or the first of the unit held ahead; the unit behind that is asked for
+            const int in_unit = ray_cut_next_in_unit(cw, unit, tile, false);
+            tile_next = in_unit >= 0 ? in_unit : ray_cut_unit_tile(cw, unit_next, n_tiles);
+            if (unit_first && tid == 0) unit_asked = atomicAdd(A.cut_counters, 1u);
+        }
         const int slot = ordered(tile) ? ord_cur : base_next + lane_of(tile);
         const bool valid = slot < n_points;
         base_next = base_of(tile_next);
         if (ORDER) { ord_cur = ord_next; ord_next = entry_of(tile_next2); }
         const RawIn in = nxt;
         nxt = load_raw_at<LOAD>(A, ordered(tile_next) ? ord_cur : base_next + lane_of(tile_next)); // consumed one tile (~250 us) later
+        const float t_end = t_end_next;
+        if constexpr (CUT)
+            t_end_next = t_end_of(tile_next, ray_cut_next_in_unit(cw, unit, tile, false) >= 0 ? unit : unit_next, base_next + lane_of(tile_next));
         float px, py, pz;
         point_of<MODE>(A, in, px, py, pz);
         const float dx = in.dx, dy = in.dy, dz = in.dz;
@@ -174,6 +210,41 @@ __global__ __launch_bounds__(256, 1) void nerf_mlp_kernel(const MlpArgs A) {
             }
         } else
         if (valid && h == 0) A.sigma_out[i] = audit ? pre : sigma;
+        if constexpr (CUT) {
+            // Exchange (one workgroup barrier per tile): every wave leaves its 32 alphas, thread 0 the unit it was handed; then every wave takes
+            // the tile's four samples of its lanes' rays in index order, as weights_scan will.  The skip happens here, at a tile boundary, where
+            // the weight stream has wrapped: the pipeline is left as it is.
+            const float al = sample_alpha_of(in.a, t_end, sigma);
+            LDS_AS unsigned *xch_unit = (LDS_AS unsigned *)(xch + kPointsPerBlock);
+            if (h == 0) xch[wave * kPointsPerWave + p] = al;
+            if (unit_first && tid == 0) *xch_unit = unit_asked;
+            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            if (unit_first) // the first 2 G units are the workgroups' own; clamped: a unit beyond the launch's has no tile
+                unit_next2 = (int)min(2u * (unsigned)G + (unsigned)__builtin_amdgcn_readfirstlane((int)*xch_unit), (unsigned)ray_cut_units(cw));
+            bool all_cut = false;
+            if (tile < cw.rest_first) {
+#pragma unroll
+                for (int w = 0; w < kWavesPerBlock; ++w) transmittance_step(cT, cdone, xch[w * kPointsPerWave + p]);
+                all_cut = __all(cdone || !valid) != 0; // a lane without a sample counts as cut
+            }
+            if (ray_cut_next_in_unit(cw, unit, tile, all_cut) < 0) { // on to the unit held ahead
+                const int end = (unit + 1) * cw.block_tiles;
+                if (all_cut && tile + 1 < end) {
+                    // cut with tiles left: their samples get sigma = 0 (the buffer is defined and the same from frame to frame) -- thread (ray, j)
+                    // of 32 x 8 writes every eighth sample index of its ray; the inputs loaded ahead were the next tile's: take the next unit's
+                    const int s0 = (tile + 1 - unit * cw.block_tiles) * kWavesPerBlock;
+                    float *row = A.sigma_out + (wave_tile_base_slot(A.ray_map.wt, unit * cw.block_tiles, 0) + wave_tile_lane_part(A.ray_map.wt, tid >> 3));
+                    for (int s = s0 + (tid & 7); s < A.samples_per_ray; s += 8) row[s] = 0.f;
+                    if (A.cut_count && tid == 0) atomicAdd((unsigned long long *)(A.cut_counters + 2), (unsigned long long)(end - tile - 1));
+                    tile_next = ray_cut_unit_tile(cw, unit_next, n_tiles);
+                    base_next = base_of(tile_next);
+                    nxt = load_raw_at<LOAD>(A, base_next + lane_of(tile_next));
+                    t_end_next = t_end_of(tile_next, unit_next, base_next + lane_of(tile_next));
+                }
+                unit = unit_next; unit_next = unit_next2; unit_first = true;
+                cT = 1.0f; cdone = false;
+            } else unit_first = false;
+        }
         if (FULL && (A.skip_empty || A.empty_vote)) {
             // Empty-tile skip (exact): if sigma == 0 for all 128 points of this workgroup's tile, then
             // alpha = 1 - exp(-0 * delta) = 0 and w = T * 0 = 0 exactly for each of them (src/lib.rs:271-272), so their
@@ -235,11 +306,11 @@ hipError_t nerf_zskip_print(const char *what, unsigned long long *stats, hipStre
     return e;
 }
 
-template <bool FULL, int MODE>
-static hipError_t launch_t(const MlpArgs &a, int n_blocks, hipStream_t stream) {
+template <bool FULL, int MODE, bool CUT = false>
+static hipError_t launch_t(const MlpArgs &a, int n_blocks, hipStream_t stream, int lds_bytes = kLdsBytes) {
     hipError_t e = nerf_zskip_clear(a.zskip_stats, stream);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((nerf_mlp_kernel<FULL, MODE>), dim3(n_blocks), dim3(256), kLdsBytes, stream, a);
+    hipLaunchKernelGGL((nerf_mlp_kernel<FULL, MODE, CUT>), dim3(n_blocks), dim3(256), lds_bytes, stream, a);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     static const char *const modes[4] = {"points", "rays", "list", "grid"};
@@ -250,12 +321,12 @@ static hipError_t launch_t(const MlpArgs &a, int n_blocks, hipStream_t stream) {
 
 hipError_t nerf_mlp_init() {
     // sigma-only in point mode is nerf_density_batch, in grid mode nerf_density_grid (no colour on a lattice)
-    const void *ks[7] = {(const void *)nerf_mlp_kernel<true, MLP_MODE_POINTS>, (const void *)nerf_mlp_kernel<true, MLP_MODE_RAYS>,
+    const void *ks[8] = {(const void *)nerf_mlp_kernel<true, MLP_MODE_POINTS>, (const void *)nerf_mlp_kernel<true, MLP_MODE_RAYS>,
                          (const void *)nerf_mlp_kernel<false, MLP_MODE_RAYS>, (const void *)nerf_mlp_kernel<true, MLP_MODE_LIST>,
                          (const void *)nerf_mlp_kernel<false, MLP_MODE_LIST>, (const void *)nerf_mlp_kernel<false, MLP_MODE_POINTS>,
-                         (const void *)nerf_mlp_kernel<false, MLP_MODE_GRID>};
-    for (int i = 0; i < 7; ++i) {
-        hipError_t e = hipFuncSetAttribute(ks[i], hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
+                         (const void *)nerf_mlp_kernel<false, MLP_MODE_GRID>, (const void *)nerf_mlp_kernel<false, MLP_MODE_RAYS, true>};
+    for (int i = 0; i < 8; ++i) {
+        hipError_t e = hipFuncSetAttribute(ks[i], hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes + (i == 7 ? kCutLdsBytes : 0)); // the cut instantiation's exchange
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
@@ -274,6 +345,19 @@ static hipError_t launch_mlp_rays(const MlpArgs &a, bool full, int n_blocks, hip
     g.order_tiles = d.tiles; g.order_points = d.points;
     if (!d.tiles) g.order_table = nullptr;
     g.ray_map = ray_launch_map_of(a.n_points - d.points, a.samples_per_ray, a.rays_per_row, full, a.ray_grouping != 0, a.wave_tiling != 0);
+    // the coarse cut (mlp_layout.h RayCutWalk): the tiled region ungrouped, the workgroups take units from the context's counter
+    g.ray_cut = 0;
+    if (a.ray_cut) {
+        const RayCutWalk w = nerf_mlp_ray_cut(a, full);
+        if (w.blocks > 0) {
+            g.ray_cut = 1;
+            g.ray_map = ray_cut_map_of(g.ray_map);
+            if (n_blocks > ray_cut_units(w)) n_blocks = ray_cut_units(w);
+            const hipError_t e = hipMemsetAsync(a.cut_counters, 0, sizeof(unsigned int), stream);
+            if (e != hipSuccess) return e;
+            return launch_t<false, MLP_MODE_RAYS, true>(g, n_blocks, stream, kLdsBytes + kCutLdsBytes);
+        }
+    }
     return full ? launch_t<true, MLP_MODE_RAYS>(g, n_blocks, stream) : launch_t<false, MLP_MODE_RAYS>(g, n_blocks, stream);
 }
 

@@ -212,6 +212,48 @@ NERF_HOST_DEVICE inline int tile_walk_next(TileWalk &w, int c, int G, bool rotat
     return w.round_base + (r >= G ? r - G : r);
 }
 
+// ---- coarse cut (f32 sigma-only ray-mode launch whose densities only the resampler reads): the resampler gives every sample behind the
+// reference's T < 1e-4 cut the weight 0 whatever its sigma (sampling_kernels.hip weights_scan; src/lib.rs:273-279), so a workgroup that walks
+// a pixel block's samples front to back may stop once all 32 rays of the block are cut.  The launch's tiled region then takes the UNGROUPED
+// 8 x 4 x 1 map (ray_cut_map_of): wave w of tile k of block b holds sample index 4 k + w of the block's 32 rays, a block is spr / 4 consecutive
+// workgroup tiles, and a lane keeps its ray for the whole block.  The persistent workgroups take UNITS, not tiles: unit u < blocks is pixel
+// block u (tiles u spr/4 ..., walked in order until the block is cut), every unit behind them one tile of the untiled remainder (tail rows).
+// Workgroup c of G starts with units c and G + c; further units come from a device-side counter (mlp_kernel.hip).  The kernel and
+// nerf_debug_coarse_cut_walk (tests/test_coarse_cut_host.py) call the same functions.
+struct RayCutWalk {
+    int blocks;      // units [0, blocks) are pixel blocks; 0 = the launch does not qualify (the other fields are then 0)
+    int block_tiles; // workgroup tiles per block: spr / 4
+    int rest_first;  // units [blocks, blocks + rest_tiles) are the single tiles rest_first, rest_first + 1, ... (= blocks * block_tiles)
+    int rest_tiles;
+};
+// the map of a cut launch: m with the tiled region ungrouped; the tail keeps its grouping
+NERF_HOST_DEVICE inline RayLaunchMap ray_cut_map_of(RayLaunchMap m) {
+    m.wt.segments = 0; m.wt.group_tiles = 0;
+    return m;
+}
+// qualifies iff the sampling launch's 8 x 4 pixels x 1 sample tiling applies (whole 128-point tiles: spr a multiple of 4 follows from the tiling's 32)
+NERF_HOST_DEVICE inline RayCutWalk ray_cut_walk_of(const RayLaunchMap &m, int n_points) {
+    RayCutWalk w = {0, 0, 0, 0};
+    if (m.wt.ss != 1 || m.wt.tw != kWaveTileSigmaW || m.wt.th != kWaveTileSigmaH || m.wt.segments != 0 || m.wt.spr % kWavesPerBlock != 0 || m.wt.tiled_tiles <= 0) return w;
+    w.block_tiles = m.wt.spr / kWavesPerBlock;
+    w.blocks = m.wt.tiled_tiles / w.block_tiles;
+    w.rest_first = m.wt.tiled_tiles;
+    w.rest_tiles = (n_points + kPointsPerBlock - 1) / kPointsPerBlock - m.wt.tiled_tiles;
+    return w;
+}
+NERF_HOST_DEVICE inline int ray_cut_units(const RayCutWalk &w) { return w.blocks + w.rest_tiles; }
+// first tile of unit u >= 0; n_tiles (no tile) for a unit beyond the launch's
+NERF_HOST_DEVICE inline int ray_cut_unit_tile(const RayCutWalk &w, int u, int n_tiles) {
+    if (u < w.blocks) return u * w.block_tiles;
+    return u - w.blocks < w.rest_tiles ? w.rest_first + (u - w.blocks) : n_tiles;
+}
+// tile `tile` of unit u is done, all_cut: every ray of its block is cut behind it -> the unit's next tile, or -1: the unit is finished
+NERF_HOST_DEVICE inline int ray_cut_next_in_unit(const RayCutWalk &w, int u, int tile, bool all_cut) {
+    if (u >= w.blocks || all_cut) return -1;
+    return tile + 1 < (u + 1) * w.block_tiles ? tile + 1 : -1;
+}
+constexpr int kCutLdsBytes = (kPointsPerBlock + 4) * 4; // behind the kernel's LDS: the tile's 128 alphas, and the unit handed out last
+
 // k-steps per layer (K padded to the 32-slot tiles) and output tiles
 constexpr int kStepsL0 = 32;    // 64 encoding slots (63 used)
 constexpr int kStepsHid = 128;  // 256

@@ -111,6 +111,7 @@ enum BufId {
     BUF_NONFINITE,  // u32: non-finite density pre-activations (Arith::counts_range)
     BUF_CLOCK,      // NERF_DEBUG_CLOCK: per workgroup {cycles, 100 MHz ticks} of the last fine-MLP launch
     BUF_ZSKIP,      // NERF_DEBUG_ZSKIP=1: {executed, total} ReLU k-steps of the f32 launch under way
+    BUF_CUT,        // coarse cut (MlpArgs.cut_counters): u32 unit counter of the cut launch under way, u32 unused, u64 tiles not evaluated (NERF_DEBUG_COARSE_CUT)
     BUF_COUNT
 };
 
@@ -180,6 +181,12 @@ struct nerf_ctx {
     bool tile_rotation = true;             // NERF_TILE_ROTATION=0 at nerf_create: round k's tile of persistent workgroup c of the f32 fused kernel is k G + c (mlp_layout.h rotated_tile)
     bool empty_tile_vote = true;           // NERF_EMPTY_TILE_VOTE=0 at nerf_create (or NERF_DEBUG_ZSKIP=1: the k-step diagnostic describes the dense colour head): full ray-mode launches of a plain render evaluate the colour head of all-empty tiles too (MlpArgs.empty_vote)
     bool debug_empty_tiles = false;        // NERF_DEBUG_EMPTY_TILES=1 at nerf_create: every voted launch counts its skipped tiles in BUF_SKIP and prints them (synchronises: a diagnostic)
+    // A cut launch hands out whole pixel blocks (spr / 4 tiles each), so a launch with few blocks per workgroup loses parallelism: 128 blocks keep
+    // 128 of 256 workgroups busy for 16 tiles each where the static walk gives each of the 256 eight.  With B blocks on G workgroups the queue ends
+    // at most one block behind the mean, a share G / B of the launch: from 16 blocks per workgroup on that is below 1 / 16, whatever the scene cuts.
+    static constexpr int kCutMinBlocksPerWorkgroup = 16;
+    int coarse_cut = 1;                    // 2 (NERF_COARSE_CUT=2): every qualifying launch is cut, however few blocks it has (tests, diagnostics); 1: launches of at least kCutMinBlocksPerWorkgroup blocks per workgroup; NERF_COARSE_CUT=0 at nerf_create (or NERF_DEBUG_ZSKIP=1: the k-step totals describe every sample): the f32 sampling launch of a plain render evaluates the samples behind every ray's T < 1e-4 cut too (MlpArgs.ray_cut)
+    bool debug_coarse_cut = false;         // NERF_DEBUG_COARSE_CUT=1 at nerf_create: every cut launch counts the tiles it did not evaluate in BUF_CUT and prints them (synchronises: a diagnostic)
     size_t max_rays_per_pass = (size_t)1 << 20;
     std::vector<hipEvent_t> ev_pool;
     std::vector<nerfint::EvPair> last_render; // events of the last render

@@ -367,6 +367,22 @@ int eval_net(nerf_ctx *c, const RenderJob &j, const Pass &p, int which, int dt, 
         a.skip_counter = c->dev<unsigned long long>(BUF_SKIP);
         HIP_TRY(c, hipMemsetAsync(a.skip_counter, 0, sizeof(unsigned long long), st));
     }
+    // the coarse cut (MlpArgs.ray_cut; exact): the f32 sampling launch of a plain image render, whose densities go to launch_resample and nowhere
+    // else (render_passes) -- not coarse_only, not nf == 0, not a ray batch; skip_dead and certify_zero renders have left above.  The resampler
+    // ends the rays at j.far_ (per-ray bounds belong to batches).  nerf_mlp_ray_cut says whether the launch's shape qualifies.
+    if (c->coarse_cut && c->buf[BUF_CUT].p && which == NERF_NET_COARSE && !full && dt == NERF_MLP_F32 && a.mode == MLP_MODE_RAYS && !j.batch &&
+        !j.coarse_only && j.nf > 0 && sigma_out == c->dev(BUF_SC)) {
+        a.cut_counters = c->dev<unsigned int>(BUF_CUT); a.ray_cut_far = j.far_;
+        // ... and whether it has the blocks to keep every workgroup busy (nerf_internal.h kCutMinBlocksPerWorkgroup; NERF_COARSE_CUT=2: any number)
+        const long long blocks = nerf_mlp_ray_cut(a, full).blocks;
+        a.ray_cut = blocks > 0 && (c->coarse_cut >= 2 || blocks >= (long long)nerf_ctx::kCutMinBlocksPerWorkgroup * c->n_cus) ? 1 : 0;
+        if (!a.ray_cut) a.cut_counters = nullptr;
+    }
+    const bool count_cut = a.ray_cut && c->debug_coarse_cut; // NERF_DEBUG_COARSE_CUT: never on in timed runs
+    if (count_cut) {
+        a.cut_count = 1;
+        HIP_TRY(c, hipMemsetAsync(a.cut_counters + 2, 0, sizeof(unsigned long long), st));
+    }
     if (p.origins) {
         // only the f32 kernel has a sigma-only points mode: a bf16 sampling pass over expanded points runs the full kernel (the same
         // densities) and leaves its colours in the fine pass's buffer, which that pass overwrites
@@ -392,6 +408,13 @@ int eval_net(nerf_ctx *c, const RenderJob &j, const Pass &p, int which, int dt, 
         }
     }
     const int rc = timed(c, st, kind, (uint64_t)a.n_points, [&]() -> int { HIP_TRY(c, launch_mlp(c, dt, a, full, st)); return NERF_OK; });
+    if (!rc && count_cut) { // the read synchronises, as nerf_zskip_print does
+        unsigned long long skipped = 0;
+        HIP_TRY(c, hipMemcpyAsync(&skipped, a.cut_counters + 2, sizeof skipped, hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipStreamSynchronize(st));
+        fprintf(stderr, "nerf coarse cut: nerf_mlp_kernel<sigma,rays> tiles_skipped=%llu tiles=%d blocks=%d\n", skipped,
+                (a.n_points + nerfmlp::kPointsPerBlock - 1) / nerfmlp::kPointsPerBlock, nerf_mlp_ray_cut(a, full).blocks);
+    }
     if (rc || !count_votes) return rc;
     unsigned long long tiles = 0; // the read synchronises, as nerf_zskip_print does
     HIP_TRY(c, hipMemcpyAsync(&tiles, a.skip_counter, sizeof tiles, hipMemcpyDeviceToHost, st));

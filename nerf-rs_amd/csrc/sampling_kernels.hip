@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include "philox.hip.h"
+#include "sample_alpha.hip.h"
 #include "sampling_kernels.h"
 
 namespace {
@@ -102,9 +103,7 @@ __device__ __forceinline__ bool weights_scan(const float *alpha, float *w, int n
 }
 
 __device__ __forceinline__ float sample_alpha(const float *t, const float *sigma, int i, int n, float far_) {
-    float delta = (i + 1 < n) ? t[i + 1] - t[i] : far_ - t[i];
-    if (delta < 0.0f) delta = 0.0f;
-    return 1.0f - expf(-sigma[i] * delta);
+    return sample_alpha_of(t[i], (i + 1 < n) ? t[i + 1] : far_, sigma[i]);
 }
 
 // ---- hierarchical resampling: one wave per ray --------------------------------------------------------
