@@ -155,6 +155,8 @@ extern "C" {
     pub fn nerf_debug_tile_rotation(n_tiles: c_int, n_workgroups: c_int, rotation: c_int, workgroup_of_tile: *mut i32, round_of_tile: *mut i32) -> c_int;
     pub fn nerf_debug_coarse_cut_walk(rows: c_int, rays_per_row: c_int, samples_per_ray: c_int, ray_grouping: c_int, cut_block: c_int, cut_after: c_int,
                                       tiles: *mut i32, tiles_cap: usize, blocks: *mut i32, block_tiles: *mut i32) -> c_int;
+    pub fn nerf_debug_fine_cut_walk(rows: c_int, rays_per_row: c_int, samples_per_ray: c_int, cut_block: c_int, cut_after: c_int,
+                                    tiles: *mut i32, tiles_cap: usize, blocks: *mut i32, block_tiles: *mut i32) -> c_int;
     pub fn nerf_debug_shader_clock_mhz(ctx: *mut nerf_ctx, mhz: *mut f64) -> c_int;
     pub fn nerf_debug_workgroup_clocks(ctx: *mut nerf_ctx, out: *mut u64, n_workgroups: usize) -> c_int;
     pub fn nerf_forward_batch(ctx: *mut nerf_ctx, which: c_int, pts_soa: *const f32, dirs_aos: *const f32, n: usize,
@@ -344,6 +346,7 @@ extern "C" {
     pub fn nerf_stage_stratified(ctx: *mut nerf_ctx, cam: *const nerf_camera, x0: c_int, y0: c_int, w: c_int, h: c_int,
                                  count: c_int, seed: u64, t_out: *mut f32) -> c_int;
     pub fn nerf_stage_depth_order(ctx: *mut nerf_ctx, rows: c_int, rays_per_row: c_int, samples_per_ray: c_int, t: *const f32, table_out: *mut u32) -> c_int;
+    pub fn nerf_stage_depth_order_flags(ctx: *mut nerf_ctx, rows: c_int, rays_per_row: c_int, samples_per_ray: c_int, t: *const f32, flags_out: *mut u32) -> c_int;
     pub fn nerf_stage_resample(ctx: *mut nerf_ctx, n_rays: usize, nc: c_int, nf: c_int, far: f32, seed: u64,
                                pixel_index: *const u32, t_coarse: *const f32, sigma_coarse: *const f32, u: *const f32,
                                w_out: *mut f32, cdf_out: *mut f32, t_new_out: *mut f32, t_fine_out: *mut f32) -> c_int;

@@ -206,8 +206,19 @@ typedef struct {
  *                           sampling launch takes it too.  The tiles of such a launch are not grouped (NERF_RAY_GROUPING).  A cut launch hands
  *                           out whole pixel blocks, so only launches of at least 16 blocks per compute unit are cut (131 072 rays on 256 units:
  *                           fewer would leave workgroups idle); NERF_COARSE_CUT=2 cuts every qualifying launch (tests, diagnostics).
+ *   NERF_FINE_CUT=0         the depth-ordered full NERF_MLP_F32 launch of a plain image render evaluates every sample.  Default, where the
+ *                           launch's densities and colours go to the pass's compositor and nowhere else (the fine pass, or the coarse network's
+ *                           launch of a coarse_only render; not skip_empty, skip_dead or certify_zero renders, not ray batches, not the stage
+ *                           calls) and the rays end at the camera's far: a workgroup walks the ordered tiles of an 8 x 4 pixel block front to
+ *                           back, keeps each ray's transmittance as the compositor will compute it, and leaves the block once all its 32 rays
+ *                           are behind the reference's T < 1e-4 cut -- the compositor gives every sample behind the cut the weight 0 whatever
+ *                           its density and colour, so every output keeps its bits.  Whole blocks are handed out, and a fine block is three
+ *                           times as long as a coarse one: only launches of at least 48 blocks per compute unit are cut (393 216 rays on 256
+ *                           units); NERF_FINE_CUT=2 cuts every qualifying launch (tests, diagnostics).
  *   NERF_DEBUG_ZSKIP=1      diagnostic: every f32 MLP launch synchronises and prints its executed / total ReLU k-steps to stderr.  The counters
- *                           describe the dense colour head and every sample: such a context runs without the empty-tile vote and the coarse cut.
+ *                           describe the dense colour head and every sample: such a context runs without the empty-tile vote and the two cuts.
+ *   NERF_DEBUG_FINE_CUT=1   diagnostic: every launch that takes the fine cut synchronises and prints "nerf fine cut: nerf_mlp_kernel<full,rays>
+ *                           tiles_skipped=N tiles=M blocks=B" to stderr.
  *   NERF_DEBUG_COARSE_CUT=1  diagnostic: every launch that takes the coarse cut synchronises and prints "nerf coarse cut: nerf_mlp_kernel<sigma,rays>
  *                           tiles_skipped=N tiles=M blocks=B" to stderr.
  *   NERF_DEBUG_EMPTY_TILES=1  diagnostic: every launch that takes the empty-tile vote synchronises and prints "nerf empty tiles: <kernel>
@@ -297,6 +308,15 @@ int nerf_debug_tile_rotation(int n_tiles, int n_workgroups, int rotation, int32_
  * may be NULL.  No device needed. */
 int nerf_debug_coarse_cut_walk(int rows, int rays_per_row, int samples_per_ray, int ray_grouping, int cut_block, int cut_after, int32_t *tiles,
                                size_t tiles_cap, int32_t *blocks, int32_t *block_tiles);
+
+/* The same for the depth-ordered full launch of an image pass under the fine cut (see NERF_FINE_CUT at nerf_create): *blocks = the launch's
+ * 8 x 4 pixel blocks over its first (rows / 4) * 4 rows, each *block_tiles = samples_per_ray / 4 consecutive tiles -- block b's part of the
+ * order table (nerf_stage_depth_order), entries 128 T .. 128 T + 127 per tile T, front to back; the tiles of the rows behind them are units
+ * of their own.  Block cut_block is taken to be cut behind its tile cut_after, as above.  *blocks = 0: the launch is not depth-ordered
+ * (samples_per_ray no multiple of 32 or above 512, fewer than 4 rows, rays_per_row no multiple of 8) and the table is 0, 1, 2, ...  No device
+ * needed. */
+int nerf_debug_fine_cut_walk(int rows, int rays_per_row, int samples_per_ray, int cut_block, int cut_after, int32_t *tiles, size_t tiles_cap,
+                             int32_t *blocks, int32_t *block_tiles);
 
 /* ---- S2: Network::forward_batch (src/network.rs:197-237) -------------------------------------------------- */
 /* host pointers, synchronous.  n == 0 is a no-op (src/network.rs:199-201).
@@ -859,6 +879,11 @@ int nerf_stage_hybrid_flags(nerf_ctx *ctx, size_t n_rays, int nc, int nf, float 
  * mapping of nerf_debug_wave_tiling, as do skip_empty renders and contexts created under NERF_DEPTH_ORDER=0 or NERF_WAVE_TILING=0).
  * table_out: (rows / 4) * 4 * rays_per_row * samples_per_ray entries. */
 int nerf_stage_depth_order(nerf_ctx *ctx, int rows, int rays_per_row, int samples_per_ray, const float *t, uint32_t *table_out);
+/* The same kernel's word per pixel block (debug / tests; what the fine cut relies on, NERF_FINE_CUT): flags_out[b] = 1 iff in every one of
+ * block b's 32 rows the keys (uint32 bits of t) << 32 | ray-in-block * samples_per_ray + sample ascend with the sample index -- a ray's
+ * samples then stand in the table in index order; equal t are in order by the key's low word -- and 0 otherwise (such a block is walked to
+ * its end).  flags_out: (rows / 4) * (rays_per_row / 8) words.  The same conditions as nerf_stage_depth_order. */
+int nerf_stage_depth_order_flags(nerf_ctx *ctx, int rows, int rays_per_row, int samples_per_ray, const float *t, uint32_t *flags_out);
 /* integrate_ray (src/lib.rs:176-195); w_out (n_rays x n) optional */
 int nerf_stage_integrate(nerf_ctx *ctx, size_t n_rays, int n, float far_, const float *rgb_aos, const float *sigma,
                          const float *t, float *rgb_out, float *w_out);

@@ -87,6 +87,8 @@ PROTOTYPES = {
     "nerf_debug_tile_rotation": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "nerf_debug_coarse_cut_walk": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_size_t,
                                             C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "nerf_debug_fine_cut_walk": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_size_t,
+                                          C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "nerf_debug_wave_tiling": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
     "nerf_forward_batch": (C.c_int, [C.c_void_p, C.c_int, f32p, f32p, C.c_size_t, f32p, f32p]),
     "nerf_forward_batch_ex": (C.c_int, [C.c_void_p, C.c_int, C.c_int, f32p, f32p, C.c_size_t, f32p, f32p]),
@@ -172,6 +174,7 @@ PROTOTYPES = {
     "nerf_stage_stratified": (C.c_int, [C.c_void_p, C.POINTER(CCamera), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                         C.c_uint64, f32p]),
     "nerf_stage_depth_order": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, f32p, u32p]),
+    "nerf_stage_depth_order_flags": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, f32p, u32p]),
     "nerf_stage_resample": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_float, C.c_uint64, u32p, f32p, f32p,
                                       f32p, f32p, f32p, f32p, f32p]),
     "nerf_stage_hybrid_flags": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_float, C.c_uint64, u32p, f32p, f32p, f32p,

@@ -147,6 +147,15 @@ class Renderer:
         check(self._L.nerf_stage_depth_order(self.handle, rows, rw, spr, _p(t), out.ctypes.data_as(u32p)), self.handle)
         return out
 
+    def stage_depth_order_flags(self, t):
+        """The order kernel's word per 8 x 4 pixel block of the same pass: 1 where every ray's samples stand in the table in sample-index order
+        (the keys of each of the block's rows ascend), else 0 (nerf_stage_depth_order_flags) -> uint32 ((rows // 4) * (rays_per_row // 8),)."""
+        t = _f32(t)
+        rows, rw, spr = t.shape
+        out = np.empty((rows // 4) * (rw // 8), np.uint32)
+        check(self._L.nerf_stage_depth_order_flags(self.handle, rows, rw, spr, _p(t), out.ctypes.data_as(u32p)), self.handle)
+        return out
+
     def stage_hybrid_flags(self, t_coarse, sigma_coarse, nf, far, seed=0, pixel_index=None, u=None, tau=0.0):
         """hybrid_sampling's per-ray decision for the given coarse densities -> (flags (R,) bool, t_new (R, nf) unsorted draws)."""
         t = _f32(t_coarse); s = _f32(sigma_coarse)

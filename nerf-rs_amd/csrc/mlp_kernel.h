@@ -84,6 +84,15 @@ struct MlpArgs {
     float ray_cut_far;
     unsigned int *cut_counters;
     int cut_count;
+    // f32 fused kernel, the depth-ordered full MLP_MODE_RAYS launch of a plain image render whose sigma and rgb go to the pass's compositor
+    // alone (appended likewise): the fine cut (mlp_layout.h fine_cut_walk_of).  A workgroup walks the ordered tiles of an 8 x 4 pixel block front
+    // to back, keeps every ray's transmittance as k_composite will compute it (sample_alpha.hip.h) and leaves the block once all 32 rays are
+    // behind the reference's T < 1e-4 cut; the table entries it does not evaluate get sigma = 0 and rgb = 0 (the compositor gives them the
+    // weight 0 whatever they hold).  The host sets it in nerf_render.cpp eval_net alone (NERF_FINE_CUT) together with order_table, the table's
+    // per-block words order_flags (k_depth_order: 1 = every row's keys ascend, so a ray's samples stand in index order; a block whose word is 0
+    // is never left early), ray_cut_far and cut_counters, which the two cuts share: their launches are ordered on the stream.
+    int fine_cut;
+    const unsigned int *order_flags;
 };
 
 // The walk of a launch with these arguments under the coarse cut (n_points, samples_per_ray, rays_per_row, mode and the two switches
@@ -94,11 +103,20 @@ inline nerfmlp::RayCutWalk nerf_mlp_ray_cut(const MlpArgs &a, bool full) {
     return nerfmlp::ray_cut_walk_of(nerfmlp::ray_cut_map_of(m), a.n_points);
 }
 
+// The walk of a launch with these arguments under the fine cut (the ordered region's blocks, then the tiles behind it one by one); blocks == 0:
+// the launch does not qualify (no order table, no flags or no counters included) and keeps its rotated static walk.
+inline nerfmlp::RayCutWalk nerf_mlp_fine_cut(const MlpArgs &a, bool full);
+
 // The ordered region of a launch with these arguments (n_points, samples_per_ray, rays_per_row, mode, skip_empty and the two switches
 // wave_tiling / depth_order); tiles == 0: the launch does not qualify and needs no table.
 inline nerfmlp::DepthOrder nerf_mlp_depth_order(const MlpArgs &a, bool full) {
     return nerfmlp::depth_order_of(a.n_points, a.samples_per_ray, a.rays_per_row, full,
                                    a.mode == MLP_MODE_RAYS && a.depth_order != 0 && a.wave_tiling != 0 && a.skip_empty == 0);
+}
+
+inline nerfmlp::RayCutWalk nerf_mlp_fine_cut(const MlpArgs &a, bool full) {
+    if (!full || !a.order_table || !a.order_flags || !a.cut_counters) return nerfmlp::RayCutWalk{0, 0, 0, 0};
+    return nerfmlp::fine_cut_walk_of(nerf_mlp_depth_order(a, full).tiles, a.samples_per_ray, a.n_points);
 }
 
 // Sets the dynamic-LDS attribute of every kernel instantiation on the current device.

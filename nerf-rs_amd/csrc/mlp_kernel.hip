@@ -31,6 +31,8 @@
 //   * the sigma-only ray-mode launch whose densities only the resampler reads walks the samples of each 8 x 4 pixel block front to back and
 //     leaves the block once all its 32 rays are behind the reference's T < 1e-4 cut (mlp_layout.h coarse cut; the CUT instantiation): the
 //     resampler gives those samples the weight 0 whatever their density.
+//   * the depth-ordered full launch whose outputs only the compositor reads walks each block's ordered tiles front to back likewise and leaves
+//     the block once all its rays are cut (mlp_layout.h fine cut; the FULL CUT instantiation): k_composite gives those samples the weight 0.
 // Per 32-point wave tile: at most 8256 MFMAs (full; 9280 before the fold) / 7680 (sigma only) x 64 cycles.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -47,7 +49,8 @@ using namespace mlpf32;
 
 template <bool FULL, int MODE, bool CUT = false>
 __global__ __launch_bounds__(256, 1) void nerf_mlp_kernel(const MlpArgs A) {
-    static_assert(!CUT || (!FULL && MODE == MLP_MODE_RAYS), "the coarse cut belongs to the sigma-only ray-mode launch");
+    static_assert(!CUT || MODE == MLP_MODE_RAYS, "the cuts belong to the ray-mode launches: sigma-only the coarse cut, full the fine cut");
+    constexpr bool CCUT = CUT && !FULL, FCUT = CUT && FULL;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const LDS_AS char *lds = (const LDS_AS char *)smem;
     const LDS_AS float *small = (const LDS_AS float *)(lds + kRingSlots * kChunkBytes);
@@ -135,24 +138,70 @@ __global__ __launch_bounds__(256, 1) void nerf_mlp_kernel(const MlpArgs A) {
     float cT = 1.0f, t_end_next = 0.f;
     unsigned unit_asked = 0;
     LDS_AS float *xch = (LDS_AS float *)(smem + kLdsBytes); // kCutLdsBytes behind the kernel's own, in a cut launch only
-    if constexpr (CUT) cw = ray_cut_walk_of(A.ray_map, n_points);
+    if constexpr (CCUT) cw = ray_cut_walk_of(A.ray_map, n_points);
     // t behind the lane's sample in tile T_ of unit u_ (slot_: the lane's slot there); tiles outside the blocks have no cut
     auto t_end_of = [&](int T_, int u_, int slot_) -> float {
         if (T_ >= cw.rest_first) return 0.f;
         const int s = (T_ - u_ * cw.block_tiles) * kWavesPerBlock + wave;
         return s + 1 < A.samples_per_ray ? A.t[slot_ + 1] : A.ray_cut_far;
     };
+    // Fine cut (mlp_layout.h fine_cut_walk_of; the FULL CUT instantiation, launched for A.fine_cut alone -- every other full ray-mode launch runs
+    // the instantiation without it, whose code is what it was): the same units, a block being the spr / 4 ORDERED tiles of its part of the table.
+    // A lane changes its ray from tile to tile here, so the walk is by ray, not by lane: the lanes that hold a point post its alpha to LDS at
+    // (ray in block, sample index mod 128) and count it there; behind the tile's one barrier (the empty-tile vote's, which it replaces) lane r
+    // of EVERY wave walks ray r's samples of the tile in index order -- fcur: the next index, cT / cdone as above, the same in all four waves.
+    // That order is k_composite's, and a ray's samples of one tile are consecutive indices, if the ray's samples stand in the table in index
+    // order: unit_flag, the block's word of A.order_flags; a block without it posts nothing and is walked to its end.  fkey: (ray in block) << 16
+    // | sample index of this lane's point, formed one tile ahead with t_end.  The alphas and counts of tile k are read behind its barrier and
+    // written again in front of tile k + 1's: the weight chunks' barriers of a whole trunk lie between (as for the vote's four words); the counts
+    // come in two sets taken in turn, and wave 0 clears the other set behind the barrier.
+    unsigned fkey_next = 0, fcur = 0;
+    bool unit_flag = false, fpar = false;
+    LDS_AS float *fstage = (LDS_AS float *)(smem + kLdsBytes); // kFineCutLdsBytes behind the kernel's own, in a fine-cut launch only
+    if constexpr (FCUT) {
+        cw = fine_cut_walk_of(order_tiles, A.samples_per_ray, n_points);
+        if (tid < 64) ((unsigned *)(smem + kLdsBytes))[kFineCutCountOff + tid] = 0u; // both sets; the first tile's trunk lies in front of the first count
+        unit_flag = unit < cw.blocks && A.order_flags[unit] != 0u;
+    }
+    // (the bodies of the fine cut's lambdas exist in its instantiation alone: in every other one they capture nothing)
+    auto unit_succ = [&](int T_, int u_, int u_after) -> int { // the tile behind T_ of unit u_ when no block is cut: u_'s next one, or the first of u_after
+        if constexpr (FCUT) {
+            const int in_unit = ray_cut_next_in_unit(cw, u_, T_, false);
+            return in_unit >= 0 ? in_unit : ray_cut_unit_tile(cw, u_after, n_tiles);
+        } else return 0;
+    };
+    auto fine_ahead = [&](int T_, int slot_) { // fkey_next / t_end_next of the lane's point in tile T_ (slot_: its slot; an ordered tile's is below order_points)
+        if constexpr (FCUT) {
+            fkey_next = 0; t_end_next = 0.f;
+            if (ordered(T_)) {
+                const unsigned spr = (unsigned)A.samples_per_ray, rw = (unsigned)A.rays_per_row;
+                const unsigned ray = (unsigned)slot_ / spr, s = (unsigned)slot_ - ray * spr, row = ray / rw, col = ray - row * rw;
+                fkey_next = ((row % kDepthBlockH) * kDepthBlockW + col % kDepthBlockW) << 16 | s;
+                t_end_next = s + 1u < spr ? A.t[slot_ + 1] : A.ray_cut_far;
+            }
+        }
+    };
     const int tile0 = CUT ? ray_cut_unit_tile(cw, unit, n_tiles) : (int)blockIdx.x; // round 0's tile
     TileWalk walk = {0, 0};
     auto next_round_tile = [&]() { return tile_walk_next(walk, (int)blockIdx.x, G, A.tile_rotation != 0); };
     int tile_next = next_round_tile();  // round 1's tile (round 0's is blockIdx.x)
     int tile_next2 = next_round_tile(); // round 2's
+    if constexpr (FCUT) { tile_next = unit_succ(tile0, unit, unit_next); tile_next2 = n_tiles; } // the loop forms both anew
     int base_next = base_of(tile0); // wave-uniform
     int ord_cur = entry_of(tile0), ord_next = entry_of(tile_next); // ORDER only: this lane's table entry of the coming tile and of the one behind it
     RawIn nxt = load_raw_at<LOAD>(A, ordered(tile0) ? ord_cur : base_next + lane_of(tile0)); // the next tile's t / direction are loaded one tile ahead
-    if constexpr (CUT) t_end_next = t_end_of(tile0, unit, base_next + lane_of(tile0));
+    if constexpr (CCUT) t_end_next = t_end_of(tile0, unit, base_next + lane_of(tile0));
+    if constexpr (FCUT) fine_ahead(tile0, ordered(tile0) ? ord_cur : base_next + lane_of(tile0));
     for (int tile = tile0; tile < n_tiles; tile = tile_next, tile_next = tile_next2, tile_next2 = next_round_tile()) {
-        if constexpr (CUT) { // the tile to look ahead to: the unit's next one, or the first of the unit held ahead; the unit behind that is asked for
+        if constexpr (FCUT) { // as below, two tiles deep: the table entry is loaded two tiles ahead
+            const bool stay = ray_cut_next_in_unit(cw, unit, tile, false) >= 0;
+            tile_next = unit_succ(tile, unit, unit_next);
+            // the unit behind tile_next's: in a unit's first tile the counter's answer is still under way -- it is wanted there only if `unit` is
+            // one tile long, a tile behind the blocks; units ascend, so every later one is such a tile too and has no table entry: "no tile" will do
+            tile_next2 = unit_succ(tile_next, stay ? unit : unit_next, stay ? unit_next : unit_first ? ray_cut_units(cw) : unit_next2);
+            if (unit_first && tid == 0) unit_asked = atomicAdd(A.cut_counters, 1u);
+        }
+        if constexpr (CCUT) { // the tile to look ahead to: the unit's next one, or the first of the unit held ahead; the unit behind that is asked for
             const int in_unit = ray_cut_next_in_unit(cw, unit, tile, false);
             tile_next = in_unit >= 0 ? in_unit : ray_cut_unit_tile(cw, unit_next, n_tiles);
             if (unit_first && tid == 0) unit_asked = atomicAdd(A.cut_counters, 1u);
@@ -164,7 +213,9 @@ __global__ __launch_bounds__(256, 1) void nerf_mlp_kernel(const MlpArgs A) {
         const RawIn in = nxt;
         nxt = load_raw_at<LOAD>(A, ordered(tile_next) ? ord_cur : base_next + lane_of(tile_next)); // consumed one tile (~250 us) later
         const float t_end = t_end_next;
-        if constexpr (CUT)
+        const unsigned fkey = fkey_next;
+        if constexpr (FCUT) fine_ahead(tile_next, ordered(tile_next) ? ord_cur : base_next + lane_of(tile_next));
+        if constexpr (CCUT)
             t_end_next = t_end_of(tile_next, ray_cut_next_in_unit(cw, unit, tile, false) >= 0 ? unit : unit_next, base_next + lane_of(tile_next));
         float px, py, pz;
         point_of<MODE>(A, in, px, py, pz);
@@ -210,7 +261,7 @@ __global__ __launch_bounds__(256, 1) void nerf_mlp_kernel(const MlpArgs A) {
             }
         } else
         if (valid && h == 0) A.sigma_out[i] = audit ? pre : sigma;
-        if constexpr (CUT) {
+        if constexpr (CCUT) {
             // Exchange (one workgroup barrier per tile): every wave leaves its 32 alphas, thread 0 the unit it was handed; then every wave takes
             // the tile's four samples of its lanes' rays in index order, as weights_scan will.  The skip happens here, at a tile boundary, where
             // the weight stream has wrapped: the pipeline is left as it is.
@@ -245,12 +296,70 @@ __global__ __launch_bounds__(256, 1) void nerf_mlp_kernel(const MlpArgs A) {
                 cT = 1.0f; cdone = false;
             } else unit_first = false;
         }
+        bool fine_any = true, fine_leave = false, fine_all_cut = false;
+        if constexpr (FCUT) {
+            // Exchange (the tile's one workgroup barrier, shared with the empty-tile vote): the alphas by (ray, sample index) and their number per
+            // ray, the waves' votes, thread 0 the unit it was handed; then lane r of every wave walks ray r.  What follows from the walk -- leaving
+            // the block -- happens at the END of the tile (fine_tile_end), behind the colour head or the vote's pipe_restart.
+            LDS_AS unsigned *fcnt = (LDS_AS unsigned *)fstage + kFineCutCountOff + (fpar ? 32 : 0);
+            LDS_AS unsigned *fcnt_other = (LDS_AS unsigned *)fstage + kFineCutCountOff + (fpar ? 0 : 32);
+            LDS_AS unsigned *xch_unit = (LDS_AS unsigned *)fstage + kFineCutUnitOff;
+            LDS_AS int *vote = (LDS_AS int *)(lds + kRingSlots * kChunkBytes) + kMiscOff + 8; // the empty-tile vote's four words
+            const bool walked = unit_flag && tile < cw.rest_first; // wave-uniform
+            if (walked && h == 0) {
+                const unsigned r = fkey >> 16; // < 32
+                fstage[r * kFineCutRowWords + (fkey & (kPointsPerBlock - 1))] = sample_alpha_of(in.a, t_end, sigma);
+                __hip_atomic_fetch_add((unsigned *)(fcnt + r), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
+            const bool any_wave = __any(valid && sigma > 0.0f);
+            if (lane == 0) vote[wave] = any_wave ? 1 : 0;
+            if (unit_first && tid == 0) *xch_unit = unit_asked;
+            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            if (unit_first) // the first 2 G units are the workgroups' own; clamped: a unit beyond the launch's has no tile
+                unit_next2 = (int)min(2u * (unsigned)G + (unsigned)__builtin_amdgcn_readfirstlane((int)*xch_unit), (unsigned)ray_cut_units(cw));
+            fine_any = (vote[0] | vote[1] | vote[2] | vote[3]) != 0;
+            const unsigned n_mine = min(fcnt[p], (unsigned)kPointsPerBlock); // ray p's samples in this tile: indices fcur .. fcur + n_mine - 1
+            for (unsigned k = 0; k < n_mine; ++k)
+                transmittance_step(cT, cdone, fstage[p * kFineCutRowWords + ((fcur + k) & (kPointsPerBlock - 1))]);
+            fcur += n_mine;
+            if (tid < 32) fcnt_other[tid] = 0u; // the next tile's set: last read behind the previous tile's barrier
+            fpar = !fpar;
+            fine_all_cut = walked && __all(cdone) != 0;
+            fine_leave = ray_cut_next_in_unit(cw, unit, tile, fine_all_cut) < 0;
+        }
+        auto fine_tile_end = [&]() { // FCUT: the tile is done, its outputs are on their way; the weight stream stands at chunk 0 of the next tile
+          if constexpr (FCUT) {
+            if (!fine_leave) { unit_first = false; return; }
+            const int end = (unit + 1) * cw.block_tiles;
+            if (fine_all_cut && tile + 1 < end) {
+                // cut with tiles left: the points of their table entries get sigma = 0 and rgb = 0 (k_composite multiplies them by the weight 0: the
+                // buffers hold finite values, the same from frame to frame); the entries and inputs loaded ahead were the block's: take the next unit's
+                for (size_t q = (size_t)(tile + 1) * kPointsPerBlock + tid; q < (size_t)end * kPointsPerBlock; q += 256) {
+                    const size_t e = min(A.order_table[q], (unsigned)order_points - 1u);
+                    A.sigma_out[e] = 0.f;
+                    A.rgb_out[3 * e + 0] = 0.f; A.rgb_out[3 * e + 1] = 0.f; A.rgb_out[3 * e + 2] = 0.f;
+                }
+                if (A.cut_count && tid == 0) atomicAdd((unsigned long long *)(A.cut_counters + 2), (unsigned long long)(end - tile - 1));
+                tile_next = ray_cut_unit_tile(cw, unit_next, n_tiles);
+                tile_next2 = unit_succ(tile_next, unit_next, unit_next2);
+                ord_cur = entry_of(tile_next); ord_next = entry_of(tile_next2);
+                base_next = base_of(tile_next);
+                const int slot_next = ordered(tile_next) ? ord_cur : base_next + lane_of(tile_next);
+                nxt = load_raw_at<LOAD>(A, slot_next);
+                fine_ahead(tile_next, slot_next);
+            }
+            unit = unit_next; unit_next = unit_next2; unit_first = true;
+            cT = 1.0f; cdone = false; fcur = 0;
+            unit_flag = unit < cw.blocks && A.order_flags[unit] != 0u;
+          }
+        };
         if (FULL && (A.skip_empty || A.empty_vote)) {
             // Empty-tile skip (exact): if sigma == 0 for all 128 points of this workgroup's tile, then
             // alpha = 1 - exp(-0 * delta) = 0 and w = T * 0 = 0 exactly for each of them (src/lib.rs:271-272), so their
             // colours never reach a pixel: skip viewdirs' + rgb (6.9 % of a full evaluation), write rgb = 0.
             LDS_AS int *vote = (LDS_AS int *)(lds + kRingSlots * kChunkBytes) + kMiscOff + 8;
-            const bool any_wg = tile_has_density(vote, valid && sigma > 0.0f, wave, lane);
+            bool any_wg = fine_any;
+            if constexpr (!FCUT) any_wg = tile_has_density(vote, valid && sigma > 0.0f, wave, lane);
             if (!any_wg) {
                 if (valid && h == 0) {
                     A.rgb_out[3 * (size_t)i + 0] = 0.f; A.rgb_out[3 * (size_t)i + 1] = 0.f; A.rgb_out[3 * (size_t)i + 2] = 0.f;
@@ -260,6 +369,7 @@ __global__ __launch_bounds__(256, 1) void nerf_mlp_kernel(const MlpArgs A) {
 #if NERF_DIAG_RESTART_TWICE // timing-only variant (make variant): a second, idle restart -- the frame-time difference prices one
                 pipe_restart(P);
 #endif
+                if constexpr (FCUT) fine_tile_end();
                 continue;
             }
         }
@@ -281,6 +391,7 @@ __global__ __launch_bounds__(256, 1) void nerf_mlp_kernel(const MlpArgs A) {
                 A.rgb_out[3 * (size_t)i + 2] = c[2];
             }
         }
+        if constexpr (FCUT) fine_tile_end();
     }
     // drain the (unused) prefetches before the LDS allocation is released
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -321,12 +432,13 @@ static hipError_t launch_t(const MlpArgs &a, int n_blocks, hipStream_t stream, i
 
 hipError_t nerf_mlp_init() {
     // sigma-only in point mode is nerf_density_batch, in grid mode nerf_density_grid (no colour on a lattice)
-    const void *ks[8] = {(const void *)nerf_mlp_kernel<true, MLP_MODE_POINTS>, (const void *)nerf_mlp_kernel<true, MLP_MODE_RAYS>,
+    const void *ks[9] = {(const void *)nerf_mlp_kernel<true, MLP_MODE_POINTS>, (const void *)nerf_mlp_kernel<true, MLP_MODE_RAYS>,
                          (const void *)nerf_mlp_kernel<false, MLP_MODE_RAYS>, (const void *)nerf_mlp_kernel<true, MLP_MODE_LIST>,
                          (const void *)nerf_mlp_kernel<false, MLP_MODE_LIST>, (const void *)nerf_mlp_kernel<false, MLP_MODE_POINTS>,
-                         (const void *)nerf_mlp_kernel<false, MLP_MODE_GRID>, (const void *)nerf_mlp_kernel<false, MLP_MODE_RAYS, true>};
-    for (int i = 0; i < 8; ++i) {
-        hipError_t e = hipFuncSetAttribute(ks[i], hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes + (i == 7 ? kCutLdsBytes : 0)); // the cut instantiation's exchange
+                         (const void *)nerf_mlp_kernel<false, MLP_MODE_GRID>, (const void *)nerf_mlp_kernel<false, MLP_MODE_RAYS, true>,
+                         (const void *)nerf_mlp_kernel<true, MLP_MODE_RAYS, true>};
+    for (int i = 0; i < 9; ++i) {
+        hipError_t e = hipFuncSetAttribute(ks[i], hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes + (i == 7 ? kCutLdsBytes : i == 8 ? kFineCutLdsBytes : 0)); // the cut instantiations' exchange
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
@@ -356,6 +468,18 @@ static hipError_t launch_mlp_rays(const MlpArgs &a, bool full, int n_blocks, hip
             const hipError_t e = hipMemsetAsync(a.cut_counters, 0, sizeof(unsigned int), stream);
             if (e != hipSuccess) return e;
             return launch_t<false, MLP_MODE_RAYS, true>(g, n_blocks, stream, kLdsBytes + kCutLdsBytes);
+        }
+    }
+    // the fine cut (mlp_layout.h fine_cut_walk_of): the ordered launch as it is mapped above, its workgroups take units from the same counter
+    g.fine_cut = 0;
+    if (a.fine_cut && d.tiles) {
+        const RayCutWalk w = nerf_mlp_fine_cut(a, full);
+        if (w.blocks > 0) {
+            g.fine_cut = 1;
+            if (n_blocks > ray_cut_units(w)) n_blocks = ray_cut_units(w);
+            const hipError_t e = hipMemsetAsync(a.cut_counters, 0, sizeof(unsigned int), stream);
+            if (e != hipSuccess) return e;
+            return launch_t<true, MLP_MODE_RAYS, true>(g, n_blocks, stream, kLdsBytes + kFineCutLdsBytes);
         }
     }
     return full ? launch_t<true, MLP_MODE_RAYS>(g, n_blocks, stream) : launch_t<false, MLP_MODE_RAYS>(g, n_blocks, stream);

@@ -254,6 +254,32 @@ NERF_HOST_DEVICE inline int ray_cut_next_in_unit(const RayCutWalk &w, int u, int
 }
 constexpr int kCutLdsBytes = (kPointsPerBlock + 4) * 4; // behind the kernel's LDS: the tile's 128 alphas, and the unit handed out last
 
+// ---- fine cut (f32 full ray-mode launch of a plain image render, depth-ordered; its sigma and rgb go to the compositor alone): k_composite
+// freezes T and gives every later sample the weight 0 once a ray's T < 1e-4 (sampling_kernels.hip; src/lib.rs:273-279), so a workgroup that
+// walks a pixel block's ORDERED tiles front to back may leave the block once all 32 rays are cut.  The same unit walk as the coarse cut's:
+// unit u < DepthOrder.blocks is pixel block u = the spr / 4 consecutive tiles of its part of the order table, every tile of the static
+// remainder behind order_tiles a unit of its own.  A lane changes its ray from tile to tile here, so the tile's alphas are posted by (ray in
+// block, sample index) to LDS and lane r of every wave walks ray r's samples in index order.  That needs a ray's samples to stand in the
+// table in index order, which holds exactly when the keys of every row of the block ascend: k_depth_order leaves one word per block
+// (1: they do) and a block whose word is 0 is walked to its end.  The kernel and nerf_debug_fine_cut_walk (tests/test_fine_cut_host.py)
+// call the same functions.
+NERF_HOST_DEVICE inline RayCutWalk fine_cut_walk_of(int order_tiles, int samples_per_ray, int n_points) { // order_tiles: DepthOrder.tiles
+    RayCutWalk w = {0, 0, 0, 0};
+    if (order_tiles <= 0 || samples_per_ray <= 0 || samples_per_ray % kPointsPerWave != 0) return w;
+    w.block_tiles = samples_per_ray / kWavesPerBlock; // 32 spr points / 128
+    w.blocks = order_tiles / w.block_tiles;           // DepthOrder.blocks
+    w.rest_first = order_tiles;
+    w.rest_tiles = (n_points + kPointsPerBlock - 1) / kPointsPerBlock - order_tiles;
+    return w;
+}
+// Behind the kernel's LDS in a fine-cut launch: the alphas of the tile by (ray in block, sample index mod 128) -- a ray has at most 128 samples
+// in a tile, and those are consecutive indices; rows padded to 129 words so that 32 rays at the same index read 32 banks --, each ray's number
+// of samples in the tile (two sets, taken in turn), and the unit handed out last.
+constexpr int kFineCutRowWords = kPointsPerBlock + 1;
+constexpr int kFineCutCountOff = 32 * kFineCutRowWords;      // words
+constexpr int kFineCutUnitOff = kFineCutCountOff + 2 * 32;
+constexpr int kFineCutLdsBytes = (kFineCutUnitOff + 4) * 4;  // 16 784
+
 // k-steps per layer (K padded to the 32-slot tiles) and output tiles
 constexpr int kStepsL0 = 32;    // 64 encoding slots (63 used)
 constexpr int kStepsHid = 128;  // 256

@@ -171,11 +171,14 @@ int nerf_create(int device_id, nerf_ctx **out) try {
     if (const char *env = getenv("NERF_DEBUG_EMPTY_TILES")) c->debug_empty_tiles = atoi(env) > 0;
     if (const char *env = getenv("NERF_COARSE_CUT")) c->coarse_cut = atoi(env) <= 0 ? 0 : atoi(env) >= 2 ? 2 : 1;
     if (const char *env = getenv("NERF_DEBUG_COARSE_CUT")) c->debug_coarse_cut = atoi(env) > 0;
+    if (const char *env = getenv("NERF_FINE_CUT")) c->fine_cut = atoi(env) <= 0 ? 0 : atoi(env) >= 2 ? 2 : 1;
+    if (const char *env = getenv("NERF_DEBUG_FINE_CUT")) c->debug_fine_cut = atoi(env) > 0;
     if (const char *env = getenv("NERF_DEBUG_ZSKIP")) {
         if (atoi(env) > 0) {
             (void)c->buf[BUF_ZSKIP].ensure(c, 2 * sizeof(unsigned long long));
             c->empty_tile_vote = false; // the k-step counters describe the dense colour head: a voted-away head would take its k-steps out of both
             c->coarse_cut = 0;          // ... and every sample of the sampling launch
+            c->fine_cut = 0;            // ... and of the fine launch
         }
     }
     if (const char *env = getenv("NERF_DEBUG_CLOCK")) {
@@ -184,7 +187,7 @@ int nerf_create(int device_id, nerf_ctx **out) try {
     }
     (void)c->buf[BUF_SKIP].ensure(c, sizeof(unsigned long long)); // a counter that could not be allocated stays NULL: its statistic reads 0
     (void)c->buf[BUF_NONFINITE].ensure(c, sizeof(unsigned int));
-    if (c->coarse_cut) (void)c->buf[BUF_CUT].ensure(c, 2 * sizeof(unsigned long long)); // without its counters a context renders without the cut
+    if (c->coarse_cut || c->fine_cut) (void)c->buf[BUF_CUT].ensure(c, 2 * sizeof(unsigned long long)); // without its counters a context renders without the cut
     // kernel attributes (dynamic LDS sizes) are per device, not per context: set them once per device and process
     static std::mutex init_mu;
     static std::set<int> init_done;

@@ -263,6 +263,33 @@ int nerf_debug_coarse_cut_walk(int rows, int rays_per_row, int samples_per_ray, 
     return visited;
 } NERF_HOST_CATCH
 
+int nerf_debug_fine_cut_walk(int rows, int rays_per_row, int samples_per_ray, int cut_block, int cut_after, int32_t *tiles, size_t tiles_cap,
+                             int32_t *blocks, int32_t *block_tiles) try {
+    using namespace nerfmlp;
+    if (rows <= 0 || rays_per_row <= 0 || samples_per_ray <= 0 || !tiles) return fail_noctx(NERF_ERR_INVALID, "rows, rays_per_row and samples_per_ray must be > 0, the table not NULL");
+    const long long n_points = (long long)rows * rays_per_row * samples_per_ray;
+    if (n_points > INT32_MAX - kPointsPerBlock) return fail_noctx(NERF_ERR_INVALID, "too many samples for one launch");
+    const int n = (int)n_points, n_tiles = (n + kPointsPerBlock - 1) / kPointsPerBlock;
+    if (tiles_cap < (size_t)n_tiles) return fail_noctx(NERF_ERR_INVALID, "the table holds fewer entries than the launch has tiles");
+    // as the ray-mode launcher of the f32 kernels (mlp_kernel.hip launch_mlp_rays) for the ordered full launch of an image pass, then unit by
+    // unit as the kernel's workgroups: a unit's first tile, then ray_cut_next_in_unit until it says the unit is finished
+    const RayCutWalk w = fine_cut_walk_of(depth_order_of(n, samples_per_ray, rays_per_row, true, true).tiles, samples_per_ray, n);
+    if (blocks) *blocks = w.blocks;
+    if (block_tiles) *block_tiles = w.block_tiles;
+    int visited = 0;
+    if (w.blocks == 0) { // the launch does not qualify: it keeps the static walk (nerf_debug_tile_rotation), every tile in turn here
+        for (int t = 0; t < n_tiles; ++t) tiles[visited++] = t;
+        return visited;
+    }
+    for (int u = 0; u < ray_cut_units(w); ++u)
+        for (int tile = ray_cut_unit_tile(w, u, n_tiles); tile >= 0 && tile < n_tiles;
+             tile = ray_cut_next_in_unit(w, u, tile, u == cut_block && tile - u * w.block_tiles >= cut_after)) {
+            if (visited >= n_tiles) return fail_noctx(NERF_ERR_INVALID, "internal error: the walk visits more tiles than the launch has");
+            tiles[visited++] = tile;
+        }
+    return visited;
+} NERF_HOST_CATCH
+
 int nerf_debug_clip_rays(const uint32_t *occ_bits, const float lo[3], const float step[3], const int32_t dims[3], const float *origins,
                          size_t n_origins, const float *dirs, size_t n_rays, int normalize, float near_, float far_, const float *bounds,
                          float *bounds_out, uint8_t *hit_out, uint64_t *n_hit, uint64_t *n_refused_reads) try {

@@ -106,12 +106,13 @@ enum BufId {
     BUF_JSTAR,      // ... per ray of a pass: first sample behind the predicted cut
     BUF_CERT_AUX,   // ... {sample, 16-bit (pre-filter) pre-activation} of the audited certificates of a launch
     BUF_ORDER,      // depth-order table of the pass under way: one slot per point of its ordered region
+    BUF_ORDER_FLAGS, // ... and one word per pixel block of it: 1 = every ray's samples stand in the table in index order (fine cut; DepthOrderArgs.flags)
     // fixed size, allocated by nerf_create (NULL where that failed or the diagnostic is off)
     BUF_SKIP,       // u64: skipped 128-point tiles (skip_empty; NERF_DEBUG_EMPTY_TILES: of the voted launch under way)
     BUF_NONFINITE,  // u32: non-finite density pre-activations (Arith::counts_range)
     BUF_CLOCK,      // NERF_DEBUG_CLOCK: per workgroup {cycles, 100 MHz ticks} of the last fine-MLP launch
     BUF_ZSKIP,      // NERF_DEBUG_ZSKIP=1: {executed, total} ReLU k-steps of the f32 launch under way
-    BUF_CUT,        // coarse cut (MlpArgs.cut_counters): u32 unit counter of the cut launch under way, u32 unused, u64 tiles not evaluated (NERF_DEBUG_COARSE_CUT)
+    BUF_CUT,        // coarse and fine cut (MlpArgs.cut_counters; their launches are ordered on the stream): u32 unit counter of the cut launch under way, u32 unused, u64 tiles not evaluated (NERF_DEBUG_COARSE_CUT, NERF_DEBUG_FINE_CUT)
     BUF_COUNT
 };
 
@@ -187,6 +188,13 @@ struct nerf_ctx {
     static constexpr int kCutMinBlocksPerWorkgroup = 16;
     int coarse_cut = 1;                    // 2 (NERF_COARSE_CUT=2): every qualifying launch is cut, however few blocks it has (tests, diagnostics); 1: launches of at least kCutMinBlocksPerWorkgroup blocks per workgroup; NERF_COARSE_CUT=0 at nerf_create (or NERF_DEBUG_ZSKIP=1: the k-step totals describe every sample): the f32 sampling launch of a plain render evaluates the samples behind every ray's T < 1e-4 cut too (MlpArgs.ray_cut)
     bool debug_coarse_cut = false;         // NERF_DEBUG_COARSE_CUT=1 at nerf_create: every cut launch counts the tiles it did not evaluate in BUF_CUT and prints them (synchronises: a diagnostic)
+    // The fine cut hands out whole blocks too, and a fine block is three times as long (spr / 4 = 48 tiles at 64 + 128, 7.5 ms of a 590 ms launch):
+    // the queue ends at most one block behind the mean, a share G / B of the launch, and what the cut can win on the lego frame is about 5 %
+    // of the launch (the tiles behind the last ray's cut, profiles/finecut_cpu_model.txt).  From 48 blocks per workgroup on the worst case of
+    // the tail is 2.1 %, its mean half of that: below the gain.  The bench frame has 78 per workgroup.  (fine cut.)
+    static constexpr int kFineCutMinBlocksPerWorkgroup = 48;
+    int fine_cut = 1;                      // as coarse_cut, for the depth-ordered full f32 launch of a plain image render whose sigma and rgb go to the compositor alone (MlpArgs.fine_cut); NERF_FINE_CUT=0 / 2 at nerf_create (or NERF_DEBUG_ZSKIP=1: off)
+    bool debug_fine_cut = false;           // NERF_DEBUG_FINE_CUT=1 at nerf_create: every fine-cut launch counts the tiles it did not evaluate in BUF_CUT and prints them (synchronises: a diagnostic)
     size_t max_rays_per_pass = (size_t)1 << 20;
     std::vector<hipEvent_t> ev_pool;
     std::vector<nerfint::EvPair> last_render; // events of the last render

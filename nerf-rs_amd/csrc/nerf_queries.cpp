@@ -694,9 +694,10 @@ int nerf_stage_hybrid_flags(nerf_ctx *c, size_t n_rays, int nc, int nf, float fa
                           tau > 0.0f ? tau : c->hybrid_tau, flags_out);
 } NERF_CATCH(c)
 
-int nerf_stage_depth_order(nerf_ctx *c, int rows, int rays_per_row, int samples_per_ray, const float *t, uint32_t *table_out) try {
+// the order kernel over a caller's t: the table, the per-block flags, or both
+static int stage_depth_order(nerf_ctx *c, int rows, int rays_per_row, int samples_per_ray, const float *t, uint32_t *table_out, uint32_t *flags_out) {
     if (!c) return fail(nullptr, NERF_ERR_INVALID, "ctx is NULL");
-    if (!t || !table_out) return fail(c, NERF_ERR_INVALID, "NULL buffer");
+    if (!t || (!table_out && !flags_out)) return fail(c, NERF_ERR_INVALID, "NULL buffer");
     if (rows <= 0 || rays_per_row <= 0 || samples_per_ray <= 0 || (long long)rows * rays_per_row * samples_per_ray > 0x3fffffff)
         return fail(c, NERF_ERR_INVALID, "rows, rays_per_row and samples_per_ray must be > 0 and within one pass");
     const int n = rows * rays_per_row * samples_per_ray;
@@ -706,11 +707,23 @@ int nerf_stage_depth_order(nerf_ctx *c, int rows, int rays_per_row, int samples_
     int rc;
     Staging s(c, BUF_SCRATCH, c->stream);
     const int i_t = s.add(F, (size_t)n, t), i_table = s.add(sizeof(uint32_t), (size_t)d.points, nullptr, table_out);
+    const int i_flags = flags_out ? s.add(sizeof(uint32_t), (size_t)d.blocks, nullptr, flags_out) : -1;
     if ((rc = s.begin())) return rc;
     DepthOrderArgs q{};
     q.t = s.at(i_t); q.rw = rays_per_row; q.spr = samples_per_ray; q.blocks_x = d.blocks_x; q.blocks = d.blocks; q.table = s.at<unsigned int>(i_table);
+    if (flags_out) q.flags = s.at<unsigned int>(i_flags);
     HIP_TRY(c, launch_depth_order(q, c->stream));
     return s.finish();
+}
+
+int nerf_stage_depth_order(nerf_ctx *c, int rows, int rays_per_row, int samples_per_ray, const float *t, uint32_t *table_out) try {
+    if (c && !table_out) return fail(c, NERF_ERR_INVALID, "NULL buffer");
+    return stage_depth_order(c, rows, rays_per_row, samples_per_ray, t, table_out, nullptr);
+} NERF_CATCH(c)
+
+int nerf_stage_depth_order_flags(nerf_ctx *c, int rows, int rays_per_row, int samples_per_ray, const float *t, uint32_t *flags_out) try {
+    if (c && !flags_out) return fail(c, NERF_ERR_INVALID, "NULL buffer");
+    return stage_depth_order(c, rows, rays_per_row, samples_per_ray, t, nullptr, flags_out);
 } NERF_CATCH(c)
 
 int nerf_stage_integrate(nerf_ctx *c, size_t n_rays, int n, float far_, const float *rgb, const float *sigma, const float *t,

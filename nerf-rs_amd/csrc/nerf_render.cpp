@@ -403,6 +403,23 @@ int eval_net(nerf_ctx *c, const RenderJob &j, const Pass &p, int which, int dt, 
             if ((rc = c->buf[BUF_ORDER].ensure(c, (size_t)d.points * sizeof(unsigned int)))) return rc;
             DepthOrderArgs q{};
             q.t = t; q.rw = a.rays_per_row; q.spr = spr; q.blocks_x = d.blocks_x; q.blocks = d.blocks; q.table = c->dev<unsigned int>(BUF_ORDER);
+            // the fine cut (MlpArgs.fine_cut; exact): this ordered full launch, if it belongs to a plain image render whose sigma and rgb go to
+            // launch_composite and nowhere else (render_passes: the fine pass, or the coarse network's of a coarse_only render) -- not a ray batch
+            // (per-ray bounds), not a normals render (its stencil pass is a second reader of the pass); skip_dead and certify_zero renders have
+            // left above, a skip_empty launch has no table, the stage calls do not come through here.  The compositor ends the rays at j.far_.
+            // Only launches with the blocks to keep every workgroup busy (nerf_internal.h kFineCutMinBlocksPerWorkgroup; NERF_FINE_CUT=2: any number).
+            if (c->fine_cut && c->buf[BUF_CUT].p && full && a.mode == MLP_MODE_RAYS && !j.batch && !j.normals && rgb_out &&
+                (c->fine_cut >= 2 || (long long)d.blocks >= (long long)nerf_ctx::kFineCutMinBlocksPerWorkgroup * c->n_cus) &&
+                (which == NERF_NET_FINE ? sigma_out == c->dev(BUF_SF) && rgb_out == c->dev(BUF_RGBF)
+                                        : j.coarse_only && sigma_out == c->dev(BUF_SC) && rgb_out == c->dev(BUF_RGBC))) {
+                if ((rc = c->buf[BUF_ORDER_FLAGS].ensure(c, (size_t)d.blocks * sizeof(unsigned int)))) return rc;
+                q.flags = c->dev<unsigned int>(BUF_ORDER_FLAGS);
+                a.fine_cut = 1; a.order_flags = q.flags; a.cut_counters = c->dev<unsigned int>(BUF_CUT); a.ray_cut_far = j.far_;
+                if (c->debug_fine_cut) { // NERF_DEBUG_FINE_CUT: never on in timed runs
+                    a.cut_count = 1;
+                    HIP_TRY(c, hipMemsetAsync(a.cut_counters + 2, 0, sizeof(unsigned long long), st));
+                }
+            }
             if ((rc = timed(c, st, EV_OTHER, 0, [&]() -> int { HIP_TRY(c, launch_depth_order(q, st)); return NERF_OK; }))) return rc;
             a.order_table = c->dev<unsigned int>(BUF_ORDER);
         }
@@ -414,6 +431,13 @@ int eval_net(nerf_ctx *c, const RenderJob &j, const Pass &p, int which, int dt, 
         HIP_TRY(c, hipStreamSynchronize(st));
         fprintf(stderr, "nerf coarse cut: nerf_mlp_kernel<sigma,rays> tiles_skipped=%llu tiles=%d blocks=%d\n", skipped,
                 (a.n_points + nerfmlp::kPointsPerBlock - 1) / nerfmlp::kPointsPerBlock, nerf_mlp_ray_cut(a, full).blocks);
+    }
+    if (!rc && a.fine_cut && a.cut_count) {
+        unsigned long long skipped = 0;
+        HIP_TRY(c, hipMemcpyAsync(&skipped, a.cut_counters + 2, sizeof skipped, hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipStreamSynchronize(st));
+        fprintf(stderr, "nerf fine cut: nerf_mlp_kernel<full,rays> tiles_skipped=%llu tiles=%d blocks=%d\n", skipped,
+                (a.n_points + nerfmlp::kPointsPerBlock - 1) / nerfmlp::kPointsPerBlock, nerf_mlp_fine_cut(a, full).blocks);
     }
     if (rc || !count_votes) return rc;
     unsigned long long tiles = 0; // the read synchronises, as nerf_zskip_print does

@@ -90,6 +90,9 @@ struct DepthOrderArgs {
     int rw, spr, blocks_x, blocks;
     unsigned int *table;
     int row_pow2 = 0;    // set by launch_depth_order: smallest power of two >= spr
+    // optional, `blocks` words: word b = 1 iff the keys of every row of block b ascend, i.e. each of its rays' samples stand in the table in
+    // sample-index order (ties included: the key's low word is ray * spr + sample) -- what the fine cut relies on (mlp_layout.h); else 0
+    unsigned int *flags = nullptr;
 };
 hipError_t launch_depth_order(const DepthOrderArgs &a, hipStream_t st);
 size_t depth_order_lds_bytes(int spr);

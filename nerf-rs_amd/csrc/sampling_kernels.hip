@@ -788,6 +788,7 @@ __global__ __launch_bounds__(kOrderThreads) void k_depth_order(const DepthOrderA
         if (s + 1 < spr && s_key[i] > s_key[i + 1]) out_of_order = 1;
     }
     const bool full_sort = __syncthreads_or(out_of_order) != 0; // block-uniform
+    if (a.flags && tid == 0) a.flags[b] = full_sort ? 0u : 1u;
     if (!full_sort) { // mirror the odd rows: run r ascends iff r is even
         constexpr int kPerThread = 32 * nerfmlp::kDepthOrderMaxSpr / kOrderThreads; // P <= 32 * kDepthOrderMaxSpr
         unsigned long long keep[kPerThread];
