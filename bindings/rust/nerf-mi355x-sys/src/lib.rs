@@ -266,6 +266,32 @@ extern "C" {
                                            opts: *const nerf_render_opts, background: *const f32, d_rgb_out: *mut f32,
                                            d_depth_out: *mut f32, d_opacity_out: *mut f32, h: f32, d_normals_out: *mut f32,
                                            stream: *mut c_void, stats: *mut nerf_stats) -> c_int;
+    /// Quantile depths (include/nerf_mi355x.h, "quantile depth and point clouds"): nerf_render_rays plus `n_q` (1..8) targets in (0, 1]
+    /// (`quantiles`: host memory in both forms) and one plane of n_rays depths per target (`depth_q_out`, n_q x n_rays).
+    pub fn nerf_render_rays_quantiles(ctx: *mut nerf_ctx, origins: *const f32, n_origins: usize, dirs: *const f32, n_rays: usize,
+                                      normalize: c_int, near: f32, far: f32, bounds: *const f32, rng_index: *const u32,
+                                      opts: *const nerf_render_opts, background: *const f32, rgb_out: *mut f32, depth_out: *mut f32,
+                                      opacity_out: *mut f32, quantiles: *const f32, n_q: c_int, depth_q_out: *mut f32,
+                                      stats: *mut nerf_stats) -> c_int;
+    pub fn nerf_render_rays_quantiles_device(ctx: *mut nerf_ctx, d_origins: *const f32, n_origins: usize, d_dirs: *const f32, n_rays: usize,
+                                             normalize: c_int, near: f32, far: f32, d_bounds: *const f32, d_rng_index: *const u32,
+                                             opts: *const nerf_render_opts, background: *const f32, d_rgb_out: *mut f32,
+                                             d_depth_out: *mut f32, d_opacity_out: *mut f32, quantiles: *const f32, n_q: c_int,
+                                             d_depth_q_out: *mut f32, stream: *mut c_void, stats: *mut nerf_stats) -> c_int;
+    /// The rays that reach `quantile` with opacity >= `min_opacity`, compacted in ray order into point records (`capacity` each; the
+    /// optional arrays may be NULL, `normals_out` goes with h > 0).  NERF_ERR_STATE when more rays are kept than fit: `n_points` then
+    /// carries the full count and the first `capacity` points are written.
+    pub fn nerf_render_rays_points(ctx: *mut nerf_ctx, origins: *const f32, n_origins: usize, dirs: *const f32, n_rays: usize,
+                                   normalize: c_int, near: f32, far: f32, bounds: *const f32, rng_index: *const u32,
+                                   opts: *const nerf_render_opts, quantile: f32, min_opacity: f32, h: f32, capacity: usize,
+                                   xyz_out: *mut f32, rgb_out: *mut f32, normals_out: *mut f32, ray_out: *mut u32, depth_out: *mut f32,
+                                   opacity_out: *mut f32, n_points: *mut usize, stats: *mut nerf_stats) -> c_int;
+    pub fn nerf_render_rays_points_device(ctx: *mut nerf_ctx, d_origins: *const f32, n_origins: usize, d_dirs: *const f32, n_rays: usize,
+                                          normalize: c_int, near: f32, far: f32, d_bounds: *const f32, d_rng_index: *const u32,
+                                          opts: *const nerf_render_opts, quantile: f32, min_opacity: f32, h: f32, capacity: usize,
+                                          d_xyz_out: *mut f32, d_rgb_out: *mut f32, d_normals_out: *mut f32, d_ray_out: *mut u32,
+                                          d_depth_out: *mut f32, d_opacity_out: *mut f32, n_points: *mut usize, d_n_points: *mut u32,
+                                          stream: *mut c_void, stats: *mut nerf_stats) -> c_int;
     /// Ray clipping (include/nerf_mi355x.h, "ray clipping"): grow an occupancy grid (nerf_density_grid's words) by `radius` cells (1..4,
     /// Chebyshev); `occ_bits` and `occ_out` must not overlap.  `n_occupied` / `bounds` optional, as nerf_density_grid reports them.
     pub fn nerf_occupancy_dilate(ctx: *mut nerf_ctx, occ_bits: *const u32, dims: *const i32, radius: c_int, occ_out: *mut u32,
@@ -358,6 +384,14 @@ extern "C" {
     pub fn nerf_stage_integrate_rgba8(ctx: *mut nerf_ctx, n_rays: usize, n: c_int, far: f32, rgb_aos: *const f32,
                                       sigma: *const f32, t: *const f32, background: *const f32, alpha_mode: c_int,
                                       rgba_out: *mut u8) -> c_int;
+    /// The quantile walk and the point compaction on caller data (one launch group each); the outputs of the second carry
+    /// NERF_STAGE_GUARD_WORDS (64) guard words behind their `capacity` records.
+    pub fn nerf_stage_ray_quantiles(ctx: *mut nerf_ctx, n_rays: usize, n: c_int, w: *const f32, t: *const f32, quantiles: *const f32,
+                                    n_q: c_int, depth_q_out: *mut f32) -> c_int;
+    pub fn nerf_stage_gather_points(ctx: *mut nerf_ctx, n_rays: usize, origins: *const f32, n_origins: usize, dirs: *const f32,
+                                    depth_q: *const f32, premultiplied_rgb: *const f32, opacity: *const f32, normals: *const f32,
+                                    min_opacity: f32, capacity: usize, xyz_out: *mut f32, rgb_out: *mut f32, normals_out: *mut f32,
+                                    ray_out: *mut u32, depth_out: *mut f32, opacity_out: *mut f32, n_points: *mut usize) -> c_int;
     /// certify_zero's plan kernel on caller data; `list_out` / `aux_out` carry NERF_STAGE_GUARD_WORDS (64) guard words on either side
     pub fn nerf_stage_cert_plan(ctx: *mut nerf_ctx, n_rays: usize, spr: c_int, far: f32, margin: f32, depth_limit: f32, audit_mask: u32,
                                 audit_mask_near: u32, audit_salt: u32, back_part: c_int, zero_threshold: f32, list_capacity: u32,

@@ -83,6 +83,16 @@ pub struct Mesh {
     pub triangles: Vec<u32>,
 }
 
+/// What `Gpu::point_cloud` returns: one record per kept ray, in ray order (`ray`: the ray's index in the batch).
+pub struct PointCloud {
+    pub xyz: Vec<f32>,
+    pub rgb: Vec<f32>,
+    pub normals: Option<Vec<f32>>,
+    pub ray: Vec<u32>,
+    pub depth: Vec<f32>,
+    pub opacity: Vec<f32>,
+}
+
 /// A mesh as a binary little-endian PLY (nerf_save_ply); colours are written as uchar red / green / blue.
 pub fn save_ply(path: &Path, mesh: &Mesh) -> Result<(), Error> {
     let (nv, nt) = (mesh.vertices.len() / 3, mesh.triangles.len() / 3);
@@ -351,6 +361,33 @@ impl Gpu {
                                           bg, rgb.as_mut_ptr(), depth.as_mut_ptr(), opacity.as_mut_ptr(), h, normals.as_mut_ptr(), &mut stats)
         })?;
         Ok((rgb, depth, opacity, normals, stats))
+    }
+
+    /// The coloured point cloud of a ray batch (nerf_render_rays_points): one point per ray whose running sum of compositing weights
+    /// reaches `quantile` (0.5: the median depth) with opacity >= `min_opacity`, in ray order.  `h`: central-difference step of the
+    /// normals, or None for a cloud without them.  The ray arguments are `render_rays`'.
+    #[allow(clippy::too_many_arguments)]
+    pub fn point_cloud(&self, origins: &[f32], dirs: &[f32], normalize: bool, near: f32, far: f32, bounds: Option<&[f32]>,
+                       rng_index: Option<&[u32]>, opts: &RenderOpts, quantile: f32, min_opacity: f32, h: Option<f32>)
+                       -> Result<PointCloud, Error> {
+        let n = dirs.len() / 3;
+        assert_eq!(dirs.len(), 3 * n, "dirs.len() must be 3 * n_rays");
+        assert!(origins.len() == 3 || origins.len() == 3 * n, "origins must hold one origin or one per ray");
+        assert!(bounds.map_or(true, |b| b.len() == 2 * n), "bounds.len() must be 2 * n_rays");
+        assert!(rng_index.map_or(true, |i| i.len() == n), "rng_index.len() must be n_rays");
+        let (mut xyz, mut rgb, mut depth, mut opacity, mut ray) = (vec![0f32; 3 * n], vec![0f32; 3 * n], vec![0f32; n], vec![0f32; n], vec![0u32; n]);
+        let mut normals = h.map(|_| vec![0f32; 3 * n]);
+        let mut kept = 0usize;
+        check(self.ctx, unsafe {
+            sys::nerf_render_rays_points(self.ctx, origins.as_ptr(), origins.len() / 3, dirs.as_ptr(), n, normalize as i32, near, far,
+                                         bounds.map_or(std::ptr::null(), |b| b.as_ptr()), rng_index.map_or(std::ptr::null(), |i| i.as_ptr()), opts,
+                                         quantile, min_opacity, h.unwrap_or(0.0), n, xyz.as_mut_ptr(), rgb.as_mut_ptr(),
+                                         normals.as_mut().map_or(std::ptr::null_mut(), |v| v.as_mut_ptr()), ray.as_mut_ptr(), depth.as_mut_ptr(),
+                                         opacity.as_mut_ptr(), &mut kept, std::ptr::null_mut())
+        })?;
+        xyz.truncate(3 * kept); rgb.truncate(3 * kept); depth.truncate(kept); opacity.truncate(kept); ray.truncate(kept);
+        if let Some(v) = normals.as_mut() { v.truncate(3 * kept); }
+        Ok(PointCloud { xyz, rgb, normals, ray, depth, opacity })
     }
 
     /// Grow the occupancy words of `density_grid` by `radius` cells (1..4, Chebyshev distance; nerf_occupancy_dilate)

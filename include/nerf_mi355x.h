@@ -659,6 +659,86 @@ int nerf_render_rays_normals_device(nerf_ctx *ctx, const float *d_origins, size_
                                     float *d_rgb_out, float *d_depth_out, float *d_opacity_out, float h, float *d_normals_out,
                                     void *stream, nerf_stats *stats);
 
+/* ---- quantile depth and point clouds: where a ray meets the surface, and the rays that hit as a coloured point list --------------------------
+ * depth_out of the ray batches is the expected termination distance sum_i w_i t_i.  At a silhouette a ray is absorbed partly by the model and
+ * partly far behind it, and that number lies in the empty space between the two: unprojected, it gives flying pixels along every edge.  These
+ * entry points add the robust depth -- the distance at which the ray has lost a given share of its light; the median depth is the 0.5
+ * quantile -- and, on top of it, the export NeRF -> coloured point cloud: one surface point per ray that hit something, with colour and
+ * normal (nerf-rs_amd/csrc/surface_kernels.hip behind the compositing launch of every pass).  All arithmetic is f32; every operation is
+ * rounded once and never contracted; division is correctly rounded.  A host can restate every output bit for bit from nerf_render_rays,
+ * nerf_render_rays_normals and the stage calls (tests/helpers/surface_restatement.py does).
+ * QUANTILE DEPTH of a ray, over the samples the final compositing integrates (as for the ray normal: the fine pass's merged samples, or the
+ *            coarse ones under coarse_only and in nerf_render_rays' other branches), t_i their positions in ascending i:
+ *              w_i   = the weight the compositing kernel computes for sample i: the bits of nerf_stage_integrate's w_out, in the render's own
+ *                      mlp_dtype;
+ *              cum_0 = +0, cum_i = fl(cum_{i-1} + w_i) in ascending i: exactly the partial sums of the opacity, the last one is the bits of
+ *                      opacity_out;
+ *              k(q)  = for a quantile q in (0, 1] the smallest i with cum_i >= q; a NaN cum_i compares false, such a sample is never k(q);
+ *              depth_q = t_{k(q)}, the sample's own position without interpolation inside the interval; +0 if no such i exists.
+ * CONSEQUENCE depth_q is non-zero only if opacity >= q; it does not decrease as q grows, as long as it is non-zero; nerf_render_rays'
+ *            clauses extend to it -- a ray's depth_q depends on that ray's inputs, opts and the weights alone, permuting a batch permutes
+ *            it, the pass size changes no bit, shared and repeated origins give the same bits -- and colour, depth and opacity of a call
+ *            that asks for quantiles are the bits of the same call without them.
+ * POINTS     for ONE quantile q and a threshold min_opacity in [0, 1]: ray r is KEPT iff opacity_r >= min_opacity and k(q) exists (a NaN
+ *            opacity keeps nothing; a crossing at a position of exactly 0 cannot be told from none and is not kept either).  The kept
+ *            rays are written in ascending ray order, over the whole batch and across passes.  Per kept ray:
+ *              xyz     = fl(o_r + fl(d * depth_q)) per coordinate, d the direction the networks saw: nerf_render_rays' POINTS formula;
+ *              rgb     = C / A per channel; C = sum_i w_i c_i is the colour nerf_render_rays returns over background (0, 0, 0), A the
+ *                        opacity: the NERF_ALPHA_STRAIGHT arithmetic.  A > 0 for every kept ray, because cum >= q > 0;
+ *              normal  = the bits of nerf_render_rays_normals for that ray with step h; written only when h > 0 is given (normals_out is
+ *                        then required); with h == 0 no normals launch is made;
+ *              ray     = the index r (uint32), depth = depth_q, opacity = A: three optional arrays.
+ *            The compaction is deterministic (prefix sums, no atomics); the running offset between passes stays on the device.
+ * CAPACITY   the caller gives the capacity of the output arrays in points; n_rays always suffices.  If more rays are kept than fit, the
+ *            first `capacity` points are written and nothing behind them, *n_points carries the full count and the call returns
+ *            NERF_ERR_STATE with a message that names both numbers.
+ * WORKSPACE  in the context, grown on demand (a warm call allocates nothing): 4 bytes per composited sample of a pass (the weights; shared
+ *            with the normals workspace when normals are made too, which then holds them); a points render adds 20 bytes per ray of the
+ *            batch (32 with normals) + 4 per ray of a pass.  Per composited sample the walk reads 8 bytes (w, t) and the compositing
+ *            launch writes 4 (w).
+ * REFUSED    NERF_ERR_INVALID, checked before the context or the device is needed, "ctx is NULL" last: everything nerf_render_rays refuses,
+ *            with its messages and in its order (a points call's rgb_out is the points' colour array); then n_q outside 1 ..
+ *            NERF_MAX_QUANTILES or a NULL `quantiles`; a quantile that is not finite or lies outside (0, 1]; min_opacity not finite or
+ *            outside [0, 1]; h not finite or negative; a missing required output (depth_q_out; xyz_out); normals_out without h > 0, and
+ *            h > 0 without normals_out.  The host forms' per-ray checks follow, as for nerf_render_rays.
+ * The certified and the clipped forms do not offer quantiles or points. */
+#define NERF_MAX_QUANTILES 8
+/* nerf_render_rays + `quantiles` (n_q values, HOST memory in both forms) and depth_q_out (n_q x n_rays: one plane of n_rays floats per
+ * quantile, in the order given).  Host pointers, synchronous. */
+int nerf_render_rays_quantiles(nerf_ctx *ctx, const float *origins /* n_origins x 3 */, size_t n_origins /* 1 or n_rays */,
+                               const float *dirs /* n_rays x 3 */, size_t n_rays, int normalize,
+                               float near_, float far_, const float *bounds /* n_rays x 2 or NULL */,
+                               const uint32_t *rng_index /* n_rays or NULL */,
+                               const nerf_render_opts *opts, const float background[3] /* NULL = white */,
+                               float *rgb_out /* n_rays x 3 */, float *depth_out /* n_rays or NULL */, float *opacity_out /* n_rays or NULL */,
+                               const float *quantiles /* n_q, host */, int n_q, float *depth_q_out /* n_q x n_rays */,
+                               nerf_stats *stats /* may be NULL */);
+/* nerf_render_rays_device + quantiles (host) and d_depth_q_out (device, n_q x n_rays); asynchronous as nerf_render_rays_device */
+int nerf_render_rays_quantiles_device(nerf_ctx *ctx, const float *d_origins, size_t n_origins, const float *d_dirs, size_t n_rays, int normalize,
+                                      float near_, float far_, const float *d_bounds, const uint32_t *d_rng_index,
+                                      const nerf_render_opts *opts, const float background[3],
+                                      float *d_rgb_out, float *d_depth_out, float *d_opacity_out,
+                                      const float *quantiles, int n_q, float *d_depth_q_out, void *stream, nerf_stats *stats);
+/* The point cloud of a batch: nerf_render_rays' ray arguments and opts, then the quantile, the threshold, the normals' step (0: no normals)
+ * and the capacity; the outputs hold `capacity` records each, of which the first min(*n_points, capacity) are written.  normals_out,
+ * ray_out, depth_out, opacity_out and n_points may be NULL (normals_out goes with h > 0).  Host pointers, synchronous. */
+int nerf_render_rays_points(nerf_ctx *ctx, const float *origins /* n_origins x 3 */, size_t n_origins /* 1 or n_rays */,
+                            const float *dirs /* n_rays x 3 */, size_t n_rays, int normalize,
+                            float near_, float far_, const float *bounds /* n_rays x 2 or NULL */,
+                            const uint32_t *rng_index /* n_rays or NULL */, const nerf_render_opts *opts,
+                            float quantile, float min_opacity, float h, size_t capacity,
+                            float *xyz_out /* capacity x 3 */, float *rgb_out /* capacity x 3 */, float *normals_out /* capacity x 3 or NULL */,
+                            uint32_t *ray_out /* capacity or NULL */, float *depth_out /* capacity or NULL */,
+                            float *opacity_out /* capacity or NULL */, size_t *n_points /* may be NULL */, nerf_stats *stats /* may be NULL */);
+/* device pointers; d_n_points (device, may be NULL) receives the full count as a uint32.  Asynchronous on `stream` like
+ * nerf_render_rays_device; the stream is synchronised only when the host n_points or stats is asked for -- without them an overflow of
+ * the capacity is visible in *d_n_points alone -- and with h > 0 once per pass, as nerf_render_rays_normals_device does. */
+int nerf_render_rays_points_device(nerf_ctx *ctx, const float *d_origins, size_t n_origins, const float *d_dirs, size_t n_rays, int normalize,
+                                   float near_, float far_, const float *d_bounds, const uint32_t *d_rng_index, const nerf_render_opts *opts,
+                                   float quantile, float min_opacity, float h, size_t capacity,
+                                   float *d_xyz_out, float *d_rgb_out, float *d_normals_out, uint32_t *d_ray_out, float *d_depth_out,
+                                   float *d_opacity_out, size_t *n_points, uint32_t *d_n_points, void *stream, nerf_stats *stats);
+
 /* ---- ray clipping: per-ray [near, far] from an occupancy grid, on the device -----------------------------------------------------------
  * nerf_density_grid packs one occupancy bit per lattice cell; nerf_render_rays takes per-ray bounds.  These entry points are the step
  * between them -- the "occupancy grid -> ray marching bounds" of other NeRF renderers (nerf-rs_amd/csrc/ray_clip_kernels.hip) -- and a render
@@ -891,6 +971,19 @@ int nerf_stage_integrate(nerf_ctx *ctx, size_t n_rays, int n, float far_, const 
  * rgba_out: n_rays x 4 bytes */
 int nerf_stage_integrate_rgba8(nerf_ctx *ctx, size_t n_rays, int n, float far_, const float *rgb_aos, const float *sigma,
                                const float *t, const float background[3], int alpha_mode, uint8_t *rgba_out);
+/* The quantile walk ("quantile depth and point clouds") over n_rays rays of n > 0 samples: w, t n_rays x n; depth_q_out n_q x n_rays.
+ * Argument errors are reported before the context is looked at. */
+int nerf_stage_ray_quantiles(nerf_ctx *ctx, size_t n_rays, int n, const float *w, const float *t, const float *quantiles, int n_q,
+                             float *depth_q_out);
+/* The compaction of the kept rays (opacity >= min_opacity and depth_q != 0) into point records, in one pass: origins n_origins x 3
+ * (n_origins 1 or n_rays), dirs as the networks saw them, premultiplied_rgb the colour C over black, normals n_rays x 3 or NULL (with
+ * normals_out).  Every output array is returned as the device held it: `capacity` records, then NERF_STAGE_GUARD_WORDS (64) words, every
+ * word 0xFFFFFFFF before the launches.  *n_points: the full count; NERF_ERR_STATE if it exceeds the capacity.  Argument errors are
+ * reported before the context is looked at. */
+int nerf_stage_gather_points(nerf_ctx *ctx, size_t n_rays, const float *origins, size_t n_origins, const float *dirs, const float *depth_q,
+                             const float *premultiplied_rgb, const float *opacity, const float *normals, float min_opacity, size_t capacity,
+                             float *xyz_out, float *rgb_out, float *normals_out, uint32_t *ray_out, float *depth_out, float *opacity_out,
+                             size_t *n_points);
 
 /* ---- the device pieces of nerf_render_opts.certify_zero, one launch each on caller data (the launches a certified render makes).
  * Argument errors are reported before the context is looked at.  A list or aux buffer is returned as the device held it, between
@@ -949,7 +1042,8 @@ const char *nerf_build_variant(void);
  * nerf_stage_cert_verify, nerf_stage_cert_audit, nerf_stage_prefilter, nerf_occupancy_dilate, nerf_occupancy_dilate_device, nerf_clip_rays,
  * nerf_clip_rays_device, nerf_debug_clip_rays, nerf_render_rays_clipped, nerf_render_rays_clipped_device, nerf_render_rays_certified,
  * nerf_render_rays_certified_device, nerf_render_rays_clipped_certified, nerf_render_rays_clipped_certified_device,
- * nerf_stage_prefilter_rays). */
+ * nerf_stage_prefilter_rays, nerf_render_rays_quantiles, nerf_render_rays_quantiles_device, nerf_render_rays_points,
+ * nerf_render_rays_points_device, nerf_stage_ray_quantiles, nerf_stage_gather_points, NERF_MAX_QUANTILES). */
 int nerf_abi_version(void);
 /* sizeof(nerf_camera), sizeof(nerf_render_opts), sizeof(nerf_stats) as this library was built: lets a binding written in
  * another language (the Rust `-sys` crate, ctypes) check its struct mirrors at start-up. */

@@ -8,7 +8,7 @@ from ._lib import NerfError, build_native, lib_path, load_library  # noqa: F401
 from .api import (Camera, Component, Mesh, Network, RenderOpts, Renderer, Stats, band_row_indices, band_rows, camera_from_pose, camera_from_samples,  # noqa: F401
                   isosurface, lattice_components, lattice_components_device, load_network_blob, load_network_from_dir, pack_network_dir, quantize_rgb8, quantize_rgba8, render_image, render_image_multi, render_image_multi_rgba8, render_image_normals, render_image_rgba8, render_rays, render_rays_device, save_pam,
                   clip_rays, clip_rays_device, dilate_occupancy, dilate_occupancy_device, render_rays_clipped, render_rays_clipped_device,
-                  save_pfm, save_ply, save_ppm, unpack_occupancy)
+                  save_pfm, save_ply, save_ppm, unpack_occupancy, point_cloud, point_cloud_device, render_image_points, save_point_cloud_ply)
 from .distributed import band_of_rank, partition_for, render_image_distributed  # noqa: F401
 
 # FLOPs per evaluated point.  FULL is what the f32 kernels EXECUTE: they run the activation-free bottleneck folded into the viewdirs

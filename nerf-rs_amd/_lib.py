@@ -142,6 +142,21 @@ PROTOTYPES = {
     "nerf_render_rays_normals_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_float,
                                                   C.c_void_p, C.c_void_p, C.POINTER(COpts), f32p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
                                                   C.c_void_p, C.c_void_p, C.POINTER(CStats)]),
+    "nerf_render_rays_quantiles": (C.c_int, [C.c_void_p, f32p, C.c_size_t, f32p, C.c_size_t, C.c_int, C.c_float, C.c_float, f32p, u32p,
+                                             C.POINTER(COpts), f32p, f32p, f32p, f32p, f32p, C.c_int, f32p, C.POINTER(CStats)]),
+    "nerf_render_rays_quantiles_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_float,
+                                                    C.c_void_p, C.c_void_p, C.POINTER(COpts), f32p, C.c_void_p, C.c_void_p, C.c_void_p, f32p, C.c_int,
+                                                    C.c_void_p, C.c_void_p, C.POINTER(CStats)]),
+    "nerf_render_rays_points": (C.c_int, [C.c_void_p, f32p, C.c_size_t, f32p, C.c_size_t, C.c_int, C.c_float, C.c_float, f32p, u32p,
+                                          C.POINTER(COpts), C.c_float, C.c_float, C.c_float, C.c_size_t, f32p, f32p, f32p, u32p, f32p, f32p,
+                                          C.POINTER(C.c_size_t), C.POINTER(CStats)]),
+    "nerf_render_rays_points_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_float,
+                                                 C.c_void_p, C.c_void_p, C.POINTER(COpts), C.c_float, C.c_float, C.c_float, C.c_size_t, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t), C.c_void_p,
+                                                 C.c_void_p, C.POINTER(CStats)]),
+    "nerf_stage_ray_quantiles": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, f32p, f32p, f32p, C.c_int, f32p]),
+    "nerf_stage_gather_points": (C.c_int, [C.c_void_p, C.c_size_t, f32p, C.c_size_t, f32p, f32p, f32p, f32p, f32p, C.c_float, C.c_size_t, f32p, f32p,
+                                           f32p, u32p, f32p, f32p, C.POINTER(C.c_size_t)]),
     "nerf_occupancy_dilate": (C.c_int, [C.c_void_p, u32p, i32p, C.c_int, u32p, C.POINTER(C.c_uint64), i32p]),
     "nerf_occupancy_dilate_device": (C.c_int, [C.c_void_p, C.c_void_p, i32p, C.c_int, C.c_void_p, C.POINTER(C.c_uint64), i32p, C.c_void_p]),
     "nerf_clip_rays": (C.c_int, [C.c_void_p, u32p, f32p, f32p, i32p, f32p, C.c_size_t, f32p, C.c_size_t, C.c_int, C.c_float, C.c_float, f32p,

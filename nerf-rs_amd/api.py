@@ -175,6 +175,46 @@ class Renderer:
         check(self._L.nerf_stage_integrate(self.handle, R, n, far, _p(c), _p(s), _p(t), _p(out), _p(w)), self.handle)
         return out, w
 
+    def stage_ray_quantiles(self, w, t, quantiles):
+        """The quantile walk on caller data (nerf_stage_ray_quantiles): w, t (R, n) -> depth_q (n_q, R)."""
+        ww = _f32(w); tt = _f32(t)
+        if ww.ndim != 2 or ww.shape != tt.shape:
+            raise NerfError(-1, "w and t must be (n_rays, n) arrays of one shape")
+        qs = _quantile_args(quantiles)
+        R, n = tt.shape
+        out = np.empty((qs.size, R), np.float32)
+        check(self._L.nerf_stage_ray_quantiles(self.handle, R, n, _p(ww), _p(tt), _p(qs), qs.size, _p(out)), self.handle)
+        return out
+
+    def stage_gather_points(self, origins, dirs, depth_q, rgb, opacity, normals=None, min_opacity=0.5, capacity=None):
+        """The point compaction on caller data (nerf_stage_gather_points) -> a dict: n_points (the full count), overflow (True when it
+        exceeds the capacity: the library's NERF_ERR_STATE), xyz, rgb, [normals,] ray, depth, opacity -- each the `capacity` records as
+        the device held them (0xFFFFFFFF words = never written) -- and guards = the words behind every array."""
+        o, d, _, n = _ray_args(origins, dirs, None)
+        dq, c, a = _f32(depth_q), _f32(rgb), _f32(opacity)
+        nr = None if normals is None else _f32(normals)
+        if dq.shape != (n,) or a.shape != (n,) or c.shape != (n, 3) or (nr is not None and nr.shape != (n, 3)):
+            raise NerfError(-1, "depth_q and opacity must be (n,) arrays, rgb and normals (n, 3)")
+        cap = n if capacity is None else int(capacity)
+        if cap < 0:
+            raise NerfError(-1, "capacity must not be negative")
+        G = 64  # NERF_STAGE_GUARD_WORDS
+        bufs = {k: np.zeros(w * cap + G, np.uint32) for k, w in (("xyz", 3), ("rgb", 3), ("normals", 3), ("ray", 1), ("depth", 1), ("opacity", 1))
+                if k != "normals" or nr is not None}
+        cnt = C.c_size_t(0)
+        code = self._L.nerf_stage_gather_points(self.handle, n, _p(o), 1 if o.ndim == 1 else n, _p(d), _p(dq), _p(c), _p(a),
+                                                None if nr is None else _p(nr), float(min_opacity), cap,
+                                                bufs["xyz"].ctypes.data_as(f32p), bufs["rgb"].ctypes.data_as(f32p),
+                                                bufs["normals"].ctypes.data_as(f32p) if nr is not None else None, bufs["ray"].ctypes.data_as(u32p),
+                                                bufs["depth"].ctypes.data_as(f32p), bufs["opacity"].ctypes.data_as(f32p), C.byref(cnt))
+        if code != 0 and not (code == -6 and cnt.value > cap):
+            check(code, self.handle)
+        out = {"n_points": int(cnt.value), "overflow": code != 0, "guards": {k: v[len(v) - G:].copy() for k, v in bufs.items()}}
+        for k, v in bufs.items():
+            body = v[:len(v) - G]
+            out[k] = body.copy() if k == "ray" else body.view(np.float32).reshape((cap, 3) if k in ("xyz", "rgb", "normals") else (cap,)).copy()
+        return out
+
     def stage_integrate_rgba8(self, rgb, sigma, t, far, background=None, alpha="opaque"):
         """integrate_ray + the RGBA8 pack (nerf_stage_integrate_rgba8) -> (R, 4) uint8."""
         c = _f32(rgb); s = _f32(sigma); t = _f32(t)
@@ -722,6 +762,16 @@ def _ptr(a):
     return a.ctypes.data_as({np.dtype(np.uint32): u32p, np.dtype(np.uint8): u8p}.get(a.dtype, f32p))
 
 
+def _quantile_args(quantiles):
+    """1 .. 8 quantiles in (0, 1] -> a contiguous float32 vector, or NerfError."""
+    qs = np.ascontiguousarray(np.atleast_1d(np.asarray(quantiles, dtype=np.float32)))
+    if qs.ndim != 1 or not 1 <= qs.size <= 8:
+        raise NerfError(-1, "quantiles must hold between 1 and 8 values")
+    if not np.all(np.isfinite(qs) & (qs > 0) & (qs <= 1)):
+        raise NerfError(-1, "a quantile must be finite and lie in (0, 1]")
+    return qs
+
+
 def _ray_head(origins, n_origins, dirs, n_rays, normalize, near, far, bounds, rng_index, opts, bg, rgb, depth, opacity):
     """What every nerf_render_rays* entry point takes from `origins` to `opacity_out`; arrays or raw device pointers."""
     return (_ptr(origins), int(n_origins), _ptr(dirs), int(n_rays), int(bool(normalize)), float(near), float(far), _ptr(bounds), _ptr(rng_index),
@@ -730,7 +780,7 @@ def _ray_head(origins, n_origins, dirs, n_rays, normalize, near, far, bounds, rn
 
 def render_rays(coarse, fine, origins, dirs, near, far, fine_samples_per_ray=128, *, n_coarse=64, bounds=None, normalize=True,
                 rng_index=None, seed=0, coarse_only=False, dtype="f32", background=None, aux=False, return_stats=False, normals_h=None,
-                certify_zero=False):
+                certify_zero=False, quantiles=None):
     """The caller's rays instead of a camera's (nerf_render_rays) -> rgb (n, 3) float32.
 
     origins: (3,) -- one origin for every ray -- or (n, 3); dirs: (n, 3), normalised on the device unless normalize=False (the caller
@@ -743,9 +793,15 @@ def render_rays(coarse, fine, origins, dirs, near, far, fine_samples_per_ray=128
     (nerf_render_rays_normals).  Colour, depth and opacity keep their bits.
     certify_zero=True: zero certification inside every pass, as render_image(certify_zero=True) -- the same bits for a fraction of the
     network evaluations (nerf_render_rays_certified; dtype f32, bf16x3 or f16x2; not with normals_h); the stats carry the audit.
+    quantiles: 1 .. 8 values q in (0, 1] -> depth_q (n_q, n) follows the other arrays (nerf_render_rays_quantiles): per ray the position of
+    the first sample at which the running sum of the weights reaches q -- 0.5 is the median depth --, 0 for a ray that never reaches it.
+    Colour, depth and opacity keep their bits.  Not together with normals_h or certify_zero.
     The other per-pixel options of render_image (crop, ssaa, bands, skip_empty, skip_dead, hybrid_sampling) do not exist for rays."""
     if certify_zero and normals_h is not None:
         raise NerfError(-1, "normals are not offered on a certified batch")
+    if quantiles is not None and (certify_zero or normals_h is not None):
+        raise NerfError(-1, "quantiles are offered on a plain batch only: not with normals_h or certify_zero")
+    qs = None if quantiles is None else _quantile_args(quantiles)
     R = coarse.renderer
     if fine is not None and fine.renderer is not R:
         raise NerfError(-1, "coarse and fine networks must live in the same Renderer")
@@ -761,6 +817,9 @@ def render_rays(coarse, fine, origins, dirs, near, far, fine_samples_per_ray=128
     head = _ray_head(o, 1 if o.ndim == 1 else n, d, n, normalize, near, far, b, idx, opts, bg, rgb, depth, opacity)
     if certify_zero:
         check(R._L.nerf_render_rays_certified(R.handle, *head, C.byref(st)), R.handle)
+    elif qs is not None:
+        depth_q = np.empty((qs.size, n), np.float32)
+        check(R._L.nerf_render_rays_quantiles(R.handle, *head, _p(qs), qs.size, _p(depth_q), C.byref(st)), R.handle)
     elif normals_h is None:
         check(R._L.nerf_render_rays(R.handle, *head, C.byref(st)), R.handle)
     else:
@@ -769,6 +828,8 @@ def render_rays(coarse, fine, origins, dirs, near, far, fine_samples_per_ray=128
     out = (rgb, depth, opacity) if aux else (rgb,)
     if normals_h is not None:
         out += (normals,)
+    if qs is not None:
+        out += (depth_q,)
     if return_stats:
         out += (Stats(st),)
     return out if len(out) > 1 else out[0]
@@ -776,14 +837,21 @@ def render_rays(coarse, fine, origins, dirs, near, far, fine_samples_per_ray=128
 
 def render_rays_device(coarse, fine, d_origins, n_origins, d_dirs, n_rays, near, far, fine_samples_per_ray, d_rgb, *, n_coarse=64,
                        d_bounds=None, normalize=True, d_rng_index=None, seed=0, coarse_only=False, dtype="f32", background=None,
-                       d_depth=None, d_opacity=None, stream=0, return_stats=False, d_normals=None, normals_h=None, certify_zero=False):
+                       d_depth=None, d_opacity=None, stream=0, return_stats=False, d_normals=None, normals_h=None, certify_zero=False,
+                       d_depth_q=None, quantiles=None):
     """nerf_render_rays_device: raw device pointers (ints; d_bounds, d_rng_index, d_depth, d_opacity may be None), asynchronous on
     `stream` (n_origins == 1 reads the origin back first and synchronises the stream once; return_stats synchronises it at the end).
     n_origins is 1 or n_rays.  d_normals (n_rays x 3 floats) together with normals_h: nerf_render_rays_normals_device, which
     synchronises the stream once per pass to read that pass's live count.  certify_zero=True: nerf_render_rays_certified_device, which
-    always synchronises the stream before returning (the audit is read on the host); not with normals.  Returns None / the stats."""
+    always synchronises the stream before returning (the audit is read on the host); not with normals.  d_depth_q (n_q x n_rays floats)
+    together with quantiles (host values): nerf_render_rays_quantiles_device; not with normals or certify_zero.  Returns None / the stats."""
     if (d_normals is None) != (normals_h is None):
         raise NerfError(-1, "d_normals and normals_h go together")
+    if (d_depth_q is None) != (quantiles is None):
+        raise NerfError(-1, "d_depth_q and quantiles go together")
+    if quantiles is not None and (certify_zero or d_normals is not None):
+        raise NerfError(-1, "quantiles are offered on a plain batch only: not with normals_h or certify_zero")
+    qs = None if quantiles is None else _quantile_args(quantiles)
     if certify_zero and d_normals is not None:
         raise NerfError(-1, "normals are not offered on a certified batch")
     R = coarse.renderer
@@ -795,6 +863,8 @@ def render_rays_device(coarse, fine, d_origins, n_origins, d_dirs, n_rays, near,
     head = _ray_head(d_origins, n_origins, d_dirs, n_rays, normalize, near, far, d_bounds, d_rng_index, opts, bg, d_rgb, d_depth, d_opacity)
     if certify_zero:
         check(R._L.nerf_render_rays_certified_device(R.handle, *head, stream, C.byref(st) if return_stats else None), R.handle)
+    elif qs is not None:
+        check(R._L.nerf_render_rays_quantiles_device(R.handle, *head, _p(qs), qs.size, d_depth_q, stream, C.byref(st) if return_stats else None), R.handle)
     elif d_normals is None:
         check(R._L.nerf_render_rays_device(R.handle, *head, stream, C.byref(st) if return_stats else None), R.handle)
     else:
@@ -958,6 +1028,101 @@ def render_image_normals(coarse, fine, camera, fine_samples_per_ray=128, *, h, s
     rgb, depth, opacity, normals = out[:4]
     shaped = (rgb.reshape(hh, w, 3), depth.reshape(hh, w), opacity.reshape(hh, w), normals.reshape(hh, w, 3))
     return shaped + (out[4],) if return_stats else shaped
+
+
+def _point_args(quantile, min_opacity, normals_h):
+    """The three scalars of a point cloud, checked as the library checks them -> (quantile, min_opacity, h)."""
+    q = float(_quantile_args([quantile])[0])
+    a = float(min_opacity)
+    if not (np.isfinite(a) and 0.0 <= a <= 1.0):
+        raise NerfError(-1, "min_opacity must be finite and lie in [0, 1]")
+    h = 0.0 if normals_h is None else float(normals_h)
+    if not (np.isfinite(h) and h >= 0.0) or (normals_h is not None and h == 0.0):
+        raise NerfError(-1, "normals_h must be finite and greater than 0 (None: no normals)")
+    return q, a, h
+
+
+def point_cloud(coarse, fine, origins, dirs, near, far, fine_samples_per_ray=128, *, quantile=0.5, min_opacity=0.5, normals_h=None, n_coarse=64,
+                bounds=None, normalize=True, rng_index=None, seed=0, coarse_only=False, dtype="f32", capacity=None, return_stats=False):
+    """The coloured point cloud of a ray batch (nerf_render_rays_points) -> a dict of arrays trimmed to the n kept rays, in ray order:
+    xyz (n, 3) = origin + direction * depth_q, rgb (n, 3) = the ray's colour over black divided by its opacity, ray (n,) uint32 = the
+    ray's index in the batch, depth (n,) = depth_q, opacity (n,), and normals (n, 3) when normals_h (a central-difference step > 0) is
+    given -- the bits of render_rays(normals_h=...) for those rays.  A ray is kept iff its opacity >= min_opacity and the running sum of
+    its weights reaches `quantile` (0.5: the point sits at the median depth).  The ray arguments are render_rays'.  capacity (points;
+    default: one per ray, which always suffices): with fewer, NerfError (code -6) names the count.  The stats follow if return_stats."""
+    R = coarse.renderer
+    if fine is not None and fine.renderer is not R:
+        raise NerfError(-1, "coarse and fine networks must live in the same Renderer")
+    o, d, b, n = _ray_args(origins, dirs, bounds)
+    idx = None if rng_index is None else np.ascontiguousarray(rng_index, dtype=np.uint32)
+    if idx is not None and idx.shape != (n,):
+        raise NerfError(-1, "rng_index must have one entry per ray")
+    q, a, h = _point_args(quantile, min_opacity, normals_h)
+    cap = n if capacity is None else int(capacity)
+    if cap < 0:
+        raise NerfError(-1, "capacity must not be negative")
+    opts = _ray_opts(n_coarse, fine_samples_per_ray, seed, coarse_only, dtype)
+    xyz, rgb = np.empty((cap, 3), np.float32), np.empty((cap, 3), np.float32)
+    normals = np.empty((cap, 3), np.float32) if h > 0 else None
+    ray, depth, opacity = np.empty(cap, np.uint32), np.empty(cap, np.float32), np.empty(cap, np.float32)
+    cnt, st = C.c_size_t(0), CStats()
+    check(R._L.nerf_render_rays_points(R.handle, _p(o), 1 if o.ndim == 1 else n, _p(d), n, int(bool(normalize)), float(near), float(far),
+                                       None if b is None else _p(b), _ptr(idx), C.byref(opts), q, a, h, cap, _p(xyz), _p(rgb),
+                                       None if normals is None else _p(normals), ray.ctypes.data_as(u32p), _p(depth), _p(opacity),
+                                       C.byref(cnt), C.byref(st)), R.handle)
+    m = int(cnt.value)
+    out = {"xyz": xyz[:m], "rgb": rgb[:m], "ray": ray[:m], "depth": depth[:m], "opacity": opacity[:m]}
+    if normals is not None:
+        out["normals"] = normals[:m]
+    return (out, Stats(st)) if return_stats else out
+
+
+def point_cloud_device(coarse, fine, d_origins, n_origins, d_dirs, n_rays, near, far, fine_samples_per_ray, capacity, d_xyz, d_rgb, *,
+                       quantile=0.5, min_opacity=0.5, normals_h=None, d_normals=None, d_ray=None, d_depth=None, d_opacity=None, d_n_points=None,
+                       n_coarse=64, d_bounds=None, normalize=True, d_rng_index=None, seed=0, coarse_only=False, dtype="f32", stream=0,
+                       want_count=False, return_stats=False):
+    """nerf_render_rays_points_device: raw device pointers (ints; the optional ones may be None), `capacity` records per output array.
+    d_n_points: a device uint32 that receives the full count.  Asynchronous on `stream` as render_rays_device, unless want_count or
+    return_stats (which synchronise it) or normals_h (once per pass).  Returns None, the count, the stats or (count, stats)."""
+    if (d_normals is None) != (normals_h is None):
+        raise NerfError(-1, "d_normals and normals_h go together")
+    R = coarse.renderer
+    if fine is not None and fine.renderer is not R:
+        raise NerfError(-1, "coarse and fine networks must live in the same Renderer")
+    q, a, h = _point_args(quantile, min_opacity, normals_h)
+    if int(capacity) < 0:
+        raise NerfError(-1, "capacity must not be negative")
+    opts = _ray_opts(n_coarse, fine_samples_per_ray, seed, coarse_only, dtype)
+    cnt, st = C.c_size_t(0), CStats()
+    check(R._L.nerf_render_rays_points_device(R.handle, d_origins, int(n_origins), d_dirs, int(n_rays), int(bool(normalize)), float(near), float(far),
+                                              d_bounds, d_rng_index, C.byref(opts), q, a, h, int(capacity), d_xyz, d_rgb, d_normals, d_ray, d_depth,
+                                              d_opacity, C.byref(cnt) if want_count else None, d_n_points, stream,
+                                              C.byref(st) if return_stats else None), R.handle)
+    out = ((int(cnt.value),) if want_count else ()) + ((Stats(st),) if return_stats else ())
+    return None if not out else out[0] if len(out) == 1 else out
+
+
+def render_image_points(coarse, fine, camera, fine_samples_per_ray=128, *, quantile=0.5, min_opacity=0.5, normals_h=None, seed=0,
+                        coarse_only=False, crop=None, dtype="f32", return_stats=False):
+    """The point cloud of a camera's window: point_cloud over the window's ray batch, built as render_image_normals builds it (unit
+    directions from stage_ray_dirs, origin camera.pos, the camera's near / far, rng_index = row * nx + col).  `ray` is the pixel's
+    index in the window, row-major."""
+    R = coarse.renderer
+    c = camera.c
+    x0, y0, w, hh = crop if crop else (0, 0, c.nx, c.ny)
+    if w <= 0 or hh <= 0 or x0 < 0 or y0 < 0 or x0 + w > c.nx or y0 + hh > c.ny:
+        raise NerfError(-1, "crop window outside the frame")
+    dirs = R.stage_ray_dirs(camera, x0, y0, w, hh, normalize=True).reshape(-1, 3)
+    rows, cols = np.meshgrid(np.arange(y0, y0 + hh), np.arange(x0, x0 + w), indexing="ij")
+    pix = (rows * c.nx + cols).reshape(-1).astype(np.uint32)
+    return point_cloud(coarse, fine, np.float32(list(c.pos)), dirs, c.near, c.far, fine_samples_per_ray, quantile=quantile,
+                       min_opacity=min_opacity, normals_h=normals_h, n_coarse=camera.samples_per_ray, normalize=False, rng_index=pix, seed=seed,
+                       coarse_only=coarse_only, dtype=dtype, return_stats=return_stats)
+
+
+def save_point_cloud_ply(path, cloud):
+    """A point_cloud dict as a binary little-endian PLY with zero faces (nerf_save_ply): x y z [nx ny nz] red green blue per vertex."""
+    save_ply(path, cloud["xyz"], np.zeros((0, 3), np.uint32), normals=cloud.get("normals"), colours=cloud["rgb"])
 
 
 GATHER_HOST, GATHER_PEER, GATHER_RCCL = 0, 1, 2

@@ -22,6 +22,10 @@
 // --rays-occupancy FILE.bits beside --rays clips the rays to the occupied cells of an occupancy grid first (nerf_render_rays_clipped): FILE holds the
 // words --grid-occupancy wrote for the lattice that --density-grid / --grid-lo / --grid-step name (no grid output flag is then needed);
 // --occupancy-dilate R (1..4) grows it by R cells first (nerf_occupancy_dilate).  Rays that cross no occupied cell get the background.
+// --points FILE.ply writes the coloured point cloud (nerf_render_rays_points) of the --rays batch, or without --rays of the scene camera's rays
+// (the window's, rng_index = row * nx + col): one vertex per ray that reaches --points-quantile Q (default 0.5, the median depth) with an opacity
+// of at least --points-min-opacity A (default 0.5), with vertex normals when --normals-step H is given; a PLY with zero faces (nerf_save_ply).
+// --depth-quantile FILE.pfm writes the median-depth map of the image run next to --depth (nerf_render_rays_quantiles on the window's rays).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -46,6 +50,9 @@ static void usage(const char *argv0) {
             "           [--rays-occupancy FILE.bits --density-grid NX,NY,NZ --grid-lo X,Y,Z --grid-step SX,SY,SZ [--occupancy-dilate R]]]\n"
             "           (n x 6 f32 in, n x 3 f32 out; no image flag: no render; --rays-occupancy: clip the rays to the grid's occupied cells first)\n"
             "          [--normals FILE.ppm] [--normals-step H]   (normal map of the image run, 0.5 n + 0.5; H: central-difference step, default 1e-3)\n"
+            "          [--points FILE.ply [--points-quantile Q] [--points-min-opacity A] [--normals-step H]]\n"
+            "           (the point cloud of the --rays batch, else of the camera's rays; --rays then needs no --rays-out; normals only with --normals-step)\n"
+            "          [--depth-quantile FILE.pfm]   (median-depth map of the image run)\n"
             "defaults: --scene lego_rust --width 256 --height 256 --coarse 64 --fine 128 --out output.ppm --mesh-iso 10\n",
             argv0);
 }
@@ -54,6 +61,9 @@ int main(int argc, char **argv) {
     std::string scene = getenv("NERF_SCENE_DIR") ? getenv("NERF_SCENE_DIR") : "lego_rust";
     std::string out = "output.ppm", depth_path, opacity_path, rgba_path;
     std::string grid_out, grid_bits_path, mesh_path, rays_path, rays_out_path, rays_bounds_path, rays_normals_path, normals_path, rays_occ_path;
+    std::string points_path, depth_q_path;
+    float points_quantile = 0.5f, points_min_opacity = 0.5f;
+    bool have_normals_step = false;
     int occ_dilate = 0;
     float normals_step = 1e-3f;
     float mesh_iso = 10.0f;
@@ -118,7 +128,11 @@ int main(int argc, char **argv) {
         else if (a == "--rays-occupancy") rays_occ_path = next();
         else if (a == "--occupancy-dilate") occ_dilate = atoi(next());
         else if (a == "--normals") { normals_path = next(); want_image = true; }
-        else if (a == "--normals-step") normals_step = strtof(next(), nullptr);
+        else if (a == "--normals-step") { normals_step = strtof(next(), nullptr); have_normals_step = true; }
+        else if (a == "--points") points_path = next();
+        else if (a == "--points-quantile") points_quantile = strtof(next(), nullptr);
+        else if (a == "--points-min-opacity") points_min_opacity = strtof(next(), nullptr);
+        else if (a == "--depth-quantile") { depth_q_path = next(); want_image = true; }
         else if (a == "--mesh-iso") { mesh_iso = strtof(next(), nullptr); have_mesh_opt = true; }
         else if (a == "--mesh-colour") { mesh_colour = true; have_mesh_opt = true; }
         else if (a == "--mesh-keep-largest") { mesh_filter.keep_largest = (uint32_t)strtoul(next(), nullptr, 10); have_mesh_opt = true; }
@@ -144,7 +158,8 @@ int main(int argc, char **argv) {
     if (occ_dilate != 0 && (rays_occ_path.empty() || occ_dilate < 1 || occ_dilate > 4)) { usage(argv[0]); return 2; }
     if (!want_grid && (have_grid_lo || have_grid_step || !grid_out.empty() || !grid_bits_path.empty() || !mesh_path.empty())) { usage(argv[0]); return 2; }
     if (mesh_path.empty() && have_mesh_opt) { usage(argv[0]); return 2; }
-    if (rays_path.empty() != rays_out_path.empty() || (rays_path.empty() && !(rays_bounds_path.empty() && rays_normals_path.empty()))) { usage(argv[0]); return 2; }
+    if (rays_path.empty() ? !(rays_out_path.empty() && rays_bounds_path.empty() && rays_normals_path.empty()) : (rays_out_path.empty() && points_path.empty())) { usage(argv[0]); return 2; }
+    if (rays_out_path.empty() && !(rays_normals_path.empty() && rays_occ_path.empty())) { usage(argv[0]); return 2; }
 
     // one context per GPU (--gpus N: devices 0..N-1, the rayon fan-out of src/lib.rs:533-550 becomes a fan-out over devices)
     if (gpus < 1) { usage(argv[0]); return 2; }
@@ -157,6 +172,38 @@ int main(int argc, char **argv) {
             fprintf(stderr, "error: %s\n", nerf_last_error(c));
             return 1;
         }
+    // --points: the cloud of a batch on the first context into a PLY without faces (a batch keeps at most one point per ray)
+    auto write_points = [&](const float *origins, size_t n_origins, const float *dirs, size_t n, int normalize, float near_, float far_, const float *bounds,
+                            const uint32_t *index, const nerf_render_opts &ro) {
+        const float h = have_normals_step ? normals_step : 0.0f;
+        std::vector<float> xyz(3 * n + 1), colour(3 * n + 1), nrm(h > 0.0f ? 3 * n + 1 : 0);
+        size_t kept = 0;
+        nerf_stats pst;
+        if (nerf_render_rays_points(ctx, origins, n_origins, dirs, n, normalize, near_, far_, bounds, index, &ro, points_quantile, points_min_opacity, h, n,
+                                    xyz.data(), colour.data(), nrm.empty() ? nullptr : nrm.data(), nullptr, nullptr, nullptr, &kept, &pst)) {
+            fprintf(stderr, "error: %s\n", nerf_last_error(ctx));
+            return false;
+        }
+        if (nerf_save_ply(points_path.c_str(), kept, xyz.data(), nrm.empty() ? nullptr : nrm.data(), colour.data(), 0, nullptr)) {
+            fprintf(stderr, "error: %s\n", nerf_last_error(nullptr));
+            return false;
+        }
+        printf("point cloud at quantile %g, opacity >= %g: %zu of %zu rays kept%s: device %.2f ms in %u pass(es)\n", (double)points_quantile, (double)points_min_opacity,
+               kept, n, nrm.empty() ? "" : ", with normals", n ? pst.ms_total : 0.0, n ? pst.n_passes : 0u);
+        return true;
+    };
+    // the window's rays as a batch (nerf_stage_ray_dirs, rng_index = row * nx + col): what --normals, --points and --depth-quantile render
+    auto window_batch = [&](const nerf_camera &cam, std::vector<float> &dirs, std::vector<uint32_t> &index, nerf_render_opts &ro) {
+        const int ow = opts.crop_w > 0 ? opts.crop_w : width, oh = opts.crop_h > 0 ? opts.crop_h : height;
+        const int x0 = opts.crop_w > 0 ? opts.crop_x0 : 0, y0 = opts.crop_h > 0 ? opts.crop_y0 : 0;
+        dirs.resize(3 * (size_t)ow * oh); index.resize((size_t)ow * oh);
+        for (int i = 0; i < oh; ++i)
+            for (int j = 0; j < ow; ++j) index[(size_t)i * ow + j] = (uint32_t)(y0 + i) * (uint32_t)width + (uint32_t)(x0 + j);
+        ro = opts; // ray batches have no pixel grid; what else they refuse (ssaa, the skip modes) is the library's error
+        ro.crop_x0 = ro.crop_y0 = ro.crop_w = ro.crop_h = 0;
+        if (nerf_stage_ray_dirs(ctx, &cam, x0, y0, ow, oh, 1, dirs.data())) { fprintf(stderr, "error: %s\n", nerf_last_error(ctx)); return false; }
+        return true;
+    };
     if (!rays_path.empty()) { // the caller's rays on the first context
         auto slurp = [](const std::string &path, std::vector<float> &v) { // the host is little-endian: the bytes as they are
             FILE *f = fopen(path.c_str(), "rb");
@@ -202,40 +249,48 @@ int main(int argc, char **argv) {
                 occ.swap(grown);
             }
         }
-        const bool certified = opts.certify_zero != 0; // --certify-zero: the certified forms of the two calls, the same bytes in --rays-out
-        if (certified && !normals.empty()) { fprintf(stderr, "error: --rays-normals is not offered with --certify-zero\n"); return 1; }
-        if (!occ.empty() ? (certified ? nerf_render_rays_clipped_certified : nerf_render_rays_clipped)(ctx, occ.data(), grid_lo, grid_step, grid_dims, o.data(), n, d.data(), n, 1,
-                                                    jc.near_, jc.far_, rb, nullptr, &opts, bg, rgb.data(), nullptr, nullptr, nullptr, &n_hit, &rst)
-            : certified ? nerf_render_rays_certified(ctx, o.data(), n, d.data(), n, 1, jc.near_, jc.far_, rb, nullptr, &opts, bg, rgb.data(), nullptr, nullptr, &rst)
-            : normals.empty() ? nerf_render_rays(ctx, o.data(), n, d.data(), n, 1, jc.near_, jc.far_, rb, nullptr, &opts, bg, rgb.data(), nullptr, nullptr, &rst)
-                            : nerf_render_rays_normals(ctx, o.data(), n, d.data(), n, 1, jc.near_, jc.far_, rb, nullptr, &opts, bg, rgb.data(), nullptr, nullptr,
-                                                       normals_step, normals.data(), &rst)) {
-            fprintf(stderr, "error: %s\n", nerf_last_error(ctx));
-            return 1;
-        }
-        auto put = [](const std::string &path, const float *v, size_t count) {
-            FILE *f = fopen(path.c_str(), "wb");
-            const bool ok = f && fwrite(v, sizeof(float), count, f) == count;
-            if ((f && fclose(f)) || !ok) { fprintf(stderr, "error: cannot write %s\n", path.c_str()); return false; }
-            return true;
-        };
-        if (!put(rays_out_path, rgb.data(), rgb.size())) return 1;
-        if (!normals.empty() && !put(rays_normals_path, normals.data(), 3 * n)) return 1;
-        if (!occ.empty()) { // the stats are those of the compacted batch
-            printf("%zu rays, %llu of them cross an occupied cell (%d coarse + %d fine samples): device %.2f ms in %u pass(es)\n", n, (unsigned long long)n_hit,
-                   opts.n_coarse, opts.coarse_only ? 0 : opts.n_fine, n_hit ? rst.ms_total : 0.0, n_hit ? rst.n_passes : 0u);
-            if (!grid_files) want_grid = false; // the lattice flags only described the occupancy file
-        } else
-            printf("%zu rays (%d coarse + %d fine samples): device %.2f ms in %u pass(es)\n", n, opts.n_coarse, opts.coarse_only ? 0 : opts.n_fine, n ? rst.ms_total : 0.0,
-                   n ? rst.n_passes : 0u);
-        if (certified && (occ.empty() ? n > 0 : n_hit > 0)) // the audit of the batch, as an image render prints it below
-            printf("certify_zero audit: %llu certificates evaluated all the same, %llu violations, margins %.3g / %.3g, least headroom %.3g / %.3g, largest bf16 error %.3g / %.3g, "
-                   "batch rendered again %u time(s), %u rays beyond their predicted cut\n", (unsigned long long)rst.n_certify_audited, (unsigned long long)rst.n_certify_violations,
-                   (double)rst.certify_margin[0], (double)rst.certify_margin[1], (double)rst.certify_headroom[0], (double)rst.certify_headroom[1],
-                   (double)rst.certify_max_error[0], (double)rst.certify_max_error[1], rst.n_certify_retries, rst.n_certify_fallback_rays);
-        if (!want_image && !want_grid) {
-            for (nerf_ctx *c : ctxs) nerf_destroy(c);
-            return 0;
+        if (!points_path.empty() && !write_points(o.data(), n, d.data(), n, 1, jc.near_, jc.far_, rb, nullptr, opts)) return 1;
+        if (rays_out_path.empty()) {
+            if (!want_image && !want_grid) {
+                for (nerf_ctx *c : ctxs) nerf_destroy(c);
+                return 0;
+            }
+        } else {
+            const bool certified = opts.certify_zero != 0; // --certify-zero: the certified forms of the two calls, the same bytes in --rays-out
+            if (certified && !normals.empty()) { fprintf(stderr, "error: --rays-normals is not offered with --certify-zero\n"); return 1; }
+            if (!occ.empty() ? (certified ? nerf_render_rays_clipped_certified : nerf_render_rays_clipped)(ctx, occ.data(), grid_lo, grid_step, grid_dims, o.data(), n, d.data(), n, 1,
+                                                        jc.near_, jc.far_, rb, nullptr, &opts, bg, rgb.data(), nullptr, nullptr, nullptr, &n_hit, &rst)
+                : certified ? nerf_render_rays_certified(ctx, o.data(), n, d.data(), n, 1, jc.near_, jc.far_, rb, nullptr, &opts, bg, rgb.data(), nullptr, nullptr, &rst)
+                : normals.empty() ? nerf_render_rays(ctx, o.data(), n, d.data(), n, 1, jc.near_, jc.far_, rb, nullptr, &opts, bg, rgb.data(), nullptr, nullptr, &rst)
+                                : nerf_render_rays_normals(ctx, o.data(), n, d.data(), n, 1, jc.near_, jc.far_, rb, nullptr, &opts, bg, rgb.data(), nullptr, nullptr,
+                                                           normals_step, normals.data(), &rst)) {
+                fprintf(stderr, "error: %s\n", nerf_last_error(ctx));
+                return 1;
+            }
+            auto put = [](const std::string &path, const float *v, size_t count) {
+                FILE *f = fopen(path.c_str(), "wb");
+                const bool ok = f && fwrite(v, sizeof(float), count, f) == count;
+                if ((f && fclose(f)) || !ok) { fprintf(stderr, "error: cannot write %s\n", path.c_str()); return false; }
+                return true;
+            };
+            if (!put(rays_out_path, rgb.data(), rgb.size())) return 1;
+            if (!normals.empty() && !put(rays_normals_path, normals.data(), 3 * n)) return 1;
+            if (!occ.empty()) { // the stats are those of the compacted batch
+                printf("%zu rays, %llu of them cross an occupied cell (%d coarse + %d fine samples): device %.2f ms in %u pass(es)\n", n, (unsigned long long)n_hit,
+                       opts.n_coarse, opts.coarse_only ? 0 : opts.n_fine, n_hit ? rst.ms_total : 0.0, n_hit ? rst.n_passes : 0u);
+                if (!grid_files) want_grid = false; // the lattice flags only described the occupancy file
+            } else
+                printf("%zu rays (%d coarse + %d fine samples): device %.2f ms in %u pass(es)\n", n, opts.n_coarse, opts.coarse_only ? 0 : opts.n_fine, n ? rst.ms_total : 0.0,
+                       n ? rst.n_passes : 0u);
+            if (certified && (occ.empty() ? n > 0 : n_hit > 0)) // the audit of the batch, as an image render prints it below
+                printf("certify_zero audit: %llu certificates evaluated all the same, %llu violations, margins %.3g / %.3g, least headroom %.3g / %.3g, largest bf16 error %.3g / %.3g, "
+                       "batch rendered again %u time(s), %u rays beyond their predicted cut\n", (unsigned long long)rst.n_certify_audited, (unsigned long long)rst.n_certify_violations,
+                       (double)rst.certify_margin[0], (double)rst.certify_margin[1], (double)rst.certify_headroom[0], (double)rst.certify_headroom[1],
+                       (double)rst.certify_max_error[0], (double)rst.certify_max_error[1], rst.n_certify_retries, rst.n_certify_fallback_rays);
+            if (!want_image && !want_grid) {
+                for (nerf_ctx *c : ctxs) nerf_destroy(c);
+                return 0;
+            }
         }
     }
     if (want_grid && !mesh_path.empty()) { // the level set of the lattice as a mesh: size query, then the fill (the lattice is evaluated twice)
@@ -310,6 +365,16 @@ int main(int argc, char **argv) {
         fprintf(stderr, "error: %s\n", nerf_last_error(nullptr));
         return 1;
     }
+    if (!points_path.empty() && rays_path.empty()) { // the camera's rays; with no image flag beside it the render is skipped
+        std::vector<float> dirs;
+        std::vector<uint32_t> index;
+        nerf_render_opts ro;
+        if (!window_batch(cam, dirs, index, ro) || !write_points(cam.pos, 1, dirs.data(), index.size(), 0, cam.near_, cam.far_, nullptr, index.data(), ro)) return 1;
+        if (!want_image) {
+            for (nerf_ctx *c : ctxs) nerf_destroy(c);
+            return 0;
+        }
+    }
     printf("Rendering with %d coarse samples and %d fine samples per ray\n", opts.n_coarse, opts.n_fine); // :660-663
     const int ow = opts.crop_w > 0 ? opts.crop_w : width, oh = opts.crop_h > 0 ? opts.crop_h : height;
     std::vector<float> image((size_t)ow * oh * 3);
@@ -381,6 +446,21 @@ int main(int argc, char **argv) {
     if ((d_map && nerf_save_pfm(depth_path.c_str(), ow, oh, d_map)) || (o_map && nerf_save_pfm(opacity_path.c_str(), ow, oh, o_map))) {
         fprintf(stderr, "error: %s\n", nerf_last_error(nullptr));
         return 1;
+    }
+    if (!depth_q_path.empty()) { // the median depth of the window's rays, next to the expected depth above
+        std::vector<float> dirs;
+        std::vector<uint32_t> index;
+        nerf_render_opts ro;
+        if (!window_batch(cam, dirs, index, ro)) return 1;
+        const size_t n = index.size();
+        const float median = 0.5f;
+        std::vector<float> rgb(3 * n), depth_q(n);
+        if (nerf_render_rays_quantiles(ctx, cam.pos, 1, dirs.data(), n, 0, cam.near_, cam.far_, nullptr, index.data(), &ro, nullptr, rgb.data(), nullptr, nullptr,
+                                       &median, 1, depth_q.data(), nullptr)) {
+            fprintf(stderr, "error: %s\n", nerf_last_error(ctx));
+            return 1;
+        }
+        if (nerf_save_pfm(depth_q_path.c_str(), ow, oh, depth_q.data())) { fprintf(stderr, "error: %s\n", nerf_last_error(nullptr)); return 1; }
     }
     if (!normals_path.empty()) { // the window's rays as a batch: colour as the frame above, plus the normals (there is no image entry point for them)
         const int x0 = opts.crop_w > 0 ? opts.crop_x0 : 0, y0 = opts.crop_h > 0 ? opts.crop_y0 : 0;

@@ -96,6 +96,8 @@ enum BufId {
     BUF_COMP,       // lattice components (components_kernels.h): labels, sizes / keep flags; only when a filter or a component query is asked for
     BUF_NORMAL,     // surface normals (normal_kernels.h): per pass {weights, live list: 4 B per sample each; count, base per ray; block sums; total}
     BUF_STENCIL,    // per stencil point 16 B {3 coordinates, sigma}; also serves nerf_density_gradient_batch, chunk by chunk
+    BUF_SURFACE,    // quantile depths and point clouds (surface_kernels.h): per pass the weights (4 B per sample, unless a normals workspace holds them) and the
+                    // kept-ray list; a points render: per ray of the batch colour, opacity, quantile depth [, normal]; block sums; the running count
     BUF_CLIP,       // ray clipping (ray_clip_kernels.h): per ray of a batch the clipped bounds, hit flag and compacted copies of a clipped render; block sums
     BUF_SEQ,        // skip_dead: one SeqCounters per MLP launch of a render
     BUF_H8,         // ... the compacted trunk outputs of the live samples (reserve_seq gives a much too large one back)

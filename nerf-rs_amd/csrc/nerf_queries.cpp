@@ -17,6 +17,7 @@
 #include "ray_clip_core.h"
 #include "ray_clip_kernels.h"
 #include "sampling_kernels.h"
+#include "surface_kernels.h"
 
 #include "nerf_internal.h"
 
@@ -921,6 +922,80 @@ int nerf_stage_prefilter(nerf_ctx *c, int which, int f16, const float origin[3],
 int nerf_stage_prefilter_rays(nerf_ctx *c, int which, int f16, const float *origins, const float *dirs, const float *t, size_t n_rays, int spr,
                               float far_, float cut_T, float *pre_out, uint32_t *nonfinite_tiles) try {
     return stage_prefilter(c, which, f16, nullptr, origins, dirs, t, n_rays, spr, far_, cut_T, pre_out, nonfinite_tiles);
+} NERF_CATCH(c)
+
+// ---- the two kernels of nerf_render_rays_quantiles / nerf_render_rays_points on caller data (surface_kernels.h) ------------------------
+int nerf_stage_ray_quantiles(nerf_ctx *c, size_t n_rays, int n, const float *w, const float *t, const float *quantiles, int n_q,
+                             float *depth_q_out) try {
+    if (n_q < 1 || n_q > NERF_MAX_QUANTILES) return fail(c, NERF_ERR_INVALID, "n_q must be between 1 and NERF_MAX_QUANTILES (8)");
+    if (!quantiles) return fail(c, NERF_ERR_INVALID, "quantiles must not be NULL");
+    for (int k = 0; k < n_q; ++k)
+        if (!(std::isfinite(quantiles[k]) && quantiles[k] > 0.0f && quantiles[k] <= 1.0f)) return fail(c, NERF_ERR_INVALID, "a quantile must be finite and lie in (0, 1]");
+    if (n <= 0) return fail(c, NERF_ERR_INVALID, "n must be positive");
+    if (n_rays > (size_t)0x7fffffff / (size_t)n) return fail(c, NERF_ERR_INVALID, "too many samples");
+    if (n_rays > 0 && (!w || !t || !depth_q_out)) return fail(c, NERF_ERR_INVALID, "NULL buffer");
+    if (!c) return fail(nullptr, NERF_ERR_INVALID, "ctx is NULL");
+    if (n_rays == 0) return NERF_OK;
+    DeviceGuard dg(c->device);
+    const size_t R = n_rays, N = (size_t)n;
+    Staging s(c, BUF_SCRATCH, c->stream);
+    const int i_w = s.add(F, R * N, w), i_t = s.add(F, R * N, t), i_o = s.add(F, (size_t)n_q * R, nullptr, depth_q_out);
+    int rc;
+    if ((rc = s.begin())) return rc;
+    RayQuantileArgs a{};
+    a.n_rays = (int)R; a.n = n; a.w = s.at(i_w); a.t = s.at(i_t); a.n_q = n_q;
+    for (int k = 0; k < n_q; ++k) a.q[k] = quantiles[k];
+    a.out = s.at(i_o); a.plane_stride = R;
+    HIP_TRY(c, launch_ray_quantiles(a, c->stream));
+    return s.finish();
+} NERF_CATCH(c)
+
+// Every output array holds `capacity` records and NERF_STAGE_GUARD_WORDS words behind them, all 0xFFFFFFFF before the launches, and comes
+// back as the device held it: a word the kernels did not write still reads 0xFFFFFFFF.
+int nerf_stage_gather_points(nerf_ctx *c, size_t n_rays, const float *origins, size_t n_origins, const float *dirs, const float *depth_q,
+                             const float *premultiplied_rgb, const float *opacity, const float *normals, float min_opacity, size_t capacity,
+                             float *xyz_out, float *rgb_out, float *normals_out, uint32_t *ray_out, float *depth_out, float *opacity_out,
+                             size_t *n_points) try {
+    if (n_rays > (size_t)0x7fffffff) return fail(c, NERF_ERR_INVALID, "n_rays must be at most INT32_MAX");
+    if (n_origins != 1 && n_origins != n_rays) return fail(c, NERF_ERR_INVALID, "n_origins must be 1 (one origin for every ray) or n_rays");
+    if (!(std::isfinite(min_opacity) && min_opacity >= 0.0f && min_opacity <= 1.0f)) return fail(c, NERF_ERR_INVALID, "min_opacity must be finite and lie in [0, 1]");
+    if (capacity > (size_t)0x7fffffff) return fail(c, NERF_ERR_INVALID, "capacity must be at most INT32_MAX");
+    if (n_rays > 0 && (!origins || !dirs || !depth_q || !premultiplied_rgb || !opacity)) return fail(c, NERF_ERR_INVALID, "NULL buffer");
+    if (!xyz_out || !rgb_out || !n_points) return fail(c, NERF_ERR_INVALID, "xyz_out, rgb_out and n_points must not be NULL");
+    if ((normals != nullptr) != (normals_out != nullptr)) return fail(c, NERF_ERR_INVALID, "normals and normals_out go together");
+    if (!c) return fail(nullptr, NERF_ERR_INVALID, "ctx is NULL");
+    *n_points = 0;
+    DeviceGuard dg(c->device);
+    const size_t R = n_rays, G = kStageGuard, cap = capacity;
+    Staging s(c, BUF_SCRATCH, c->stream);
+    const int i_org = s.opt(R > 0 && n_origins != 1, F, 3 * R, origins), i_dirs = s.add(F, 3 * R, dirs), i_dq = s.add(F, R, depth_q),
+              i_rgb = s.add(F, 3 * R, premultiplied_rgb), i_op = s.add(F, R, opacity), i_nrm = s.opt(normals, F, 3 * R, normals),
+              i_bsum = s.add(4, (R + kSurfaceBlock - 1) / kSurfaceBlock), i_ray_of = s.add(4, R), i_state = s.add(sizeof(PointState), 1, nullptr, nullptr, 0),
+              i_xyz = s.add(4, 3 * cap + G, nullptr, xyz_out, 0xFF), i_c = s.add(4, 3 * cap + G, nullptr, rgb_out, 0xFF),
+              i_n = s.opt(normals_out, 4, 3 * cap + G, nullptr, normals_out, 0xFF), i_r = s.opt(ray_out, 4, cap + G, nullptr, ray_out, 0xFF),
+              i_d = s.opt(depth_out, 4, cap + G, nullptr, depth_out, 0xFF), i_a = s.opt(opacity_out, 4, cap + G, nullptr, opacity_out, 0xFF);
+    int rc;
+    if ((rc = s.begin())) return rc;
+    PointGatherArgs a{};
+    a.n_rays = (int)R; a.first_ray = 0; a.origins = s.at(i_org);
+    if (R > 0 && n_origins == 1) copy3(a.origin, origins);
+    a.dirs = s.at(i_dirs); a.depth_q = s.at(i_dq); a.rgb = s.at(i_rgb); a.opacity = s.at(i_op); a.normals = s.at(i_nrm);
+    a.min_opacity = min_opacity; a.capacity = (uint32_t)cap;
+    a.bsum = s.at<uint32_t>(i_bsum); a.ray_of = s.at<uint32_t>(i_ray_of); a.state = s.at<PointState>(i_state);
+    a.xyz_out = s.at(i_xyz); a.rgb_out = s.at(i_c); a.normals_out = s.at(i_n); a.ray_out = s.at<uint32_t>(i_r); a.depth_out = s.at(i_d);
+    a.opacity_out = s.at(i_a);
+    HIP_TRY(c, launch_point_gather(a, c->stream));
+    HIP_TRY(c, launch_point_total(a.state, nullptr, c->stream));
+    PointState hs{};
+    HIP_TRY(c, hipMemcpyAsync(&hs, a.state, sizeof hs, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = s.finish())) return rc;
+    *n_points = hs.running;
+    if ((size_t)hs.running > cap) {
+        char msg[160];
+        snprintf(msg, sizeof msg, "point cloud: %u rays are kept but the capacity is %zu points; the first %zu are written", hs.running, cap, cap);
+        return fail(c, NERF_ERR_STATE, msg);
+    }
+    return NERF_OK;
 } NERF_CATCH(c)
 
 } // extern "C"

@@ -18,6 +18,7 @@
 #include "ray_clip_core.h"
 #include "ray_clip_kernels.h"
 #include "sampling_kernels.h"
+#include "surface_kernels.h"
 
 using namespace nerfhost;
 
@@ -58,7 +59,7 @@ int check_rgba8(nerf_ctx *c, const float *background, int alpha_mode, const void
 
 namespace {
 
-// What the ten nerf_render_rays* entry points receive.  A host form stages its request (render_rays_entry) into one whose pointers are
+// What the fourteen nerf_render_rays* entry points receive.  A host form stages its request (render_rays_entry) into one whose pointers are
 // device pointers and hands that to the device form.
 struct RayRequest {
     const float *origins; size_t n_origins; // n_origins x 3; n_origins is 1 (one origin for every ray) or n_rays
@@ -74,6 +75,10 @@ struct RayRequest {
     bool clipped;                           // nerf_render_rays_clipped*: the grid (lo, step, dims on the host), the flags and the hit count
     const uint32_t *occ_bits; const float *lo, *step; const int32_t *dims; uint8_t *hit; uint64_t *n_hit;
     bool certified;                         // nerf_render_rays*_certified*
+    bool want_quantiles; int n_q; const float *quantiles; float *depth_q; // nerf_render_rays_quantiles*: n_q targets on the HOST, n_q x n_rays planes
+    // nerf_render_rays_points*: one target, the threshold, the normals' step h above (0: none), the outputs (capacity points each) and the count
+    bool points; float quantile, min_opacity; size_t capacity;
+    float *p_xyz, *p_rgb, *p_normals, *p_depth, *p_opacity; uint32_t *p_ray; size_t *n_points; uint32_t *d_n_points;
     hipStream_t st;
     nerf_stats *stats;
     const float *h_origin;                  // device requests with n_origins == 1: the shared origin on the HOST once it is known
@@ -92,6 +97,27 @@ struct NormalWorkspace {
         if (!p) return;
         w = l.at<float>(p, i_w); list = l.at<uint32_t>(p, i_list); count = l.at<uint32_t>(p, i_count); base = l.at<uint32_t>(p, i_base);
         bsum = l.at<uint32_t>(p, i_bsum); totals = l.at<uint32_t>(p, i_totals);
+    }
+};
+
+// The workspace of a quantile or points render in BUF_SURFACE (StageLayout: every part 256-byte aligned): per pass the weights (unless a normals
+// workspace holds them: samples == 0) and, for a points render, per ray of the BATCH what the compaction reads -- the compositing kernel's
+// outputs land there pass by pass -- with the pass's kept-ray list, its block sums and the running count.
+struct SurfaceWorkspace {
+    float *w = nullptr, *rgb = nullptr, *opacity = nullptr, *depth_q = nullptr, *normals = nullptr;
+    uint32_t *ray_of = nullptr, *bsum = nullptr; PointState *state = nullptr;
+    size_t bytes = 0;
+    SurfaceWorkspace() = default;
+    SurfaceWorkspace(void *p, size_t samples, size_t pass_rays, size_t batch_rays, bool with_normals) { // p == NULL: only `bytes`; batch_rays == 0: no points
+        StageLayout l;
+        const bool pts = batch_rays > 0;
+        const int i_w = l.opt(samples > 0, 4, samples), i_rgb = l.opt(pts, 12, batch_rays), i_op = l.opt(pts, 4, batch_rays), i_dq = l.opt(pts, 4, batch_rays),
+                  i_nrm = l.opt(pts && with_normals, 12, batch_rays), i_ray = l.opt(pts, 4, pass_rays),
+                  i_bsum = l.opt(pts, 4, (pass_rays + kSurfaceBlock - 1) / kSurfaceBlock), i_state = l.opt(pts, sizeof(PointState), 1);
+        bytes = l.total;
+        if (!p) return;
+        w = l.at<float>(p, i_w); rgb = l.at<float>(p, i_rgb); opacity = l.at<float>(p, i_op); depth_q = l.at<float>(p, i_dq); normals = l.at<float>(p, i_nrm);
+        ray_of = l.at<uint32_t>(p, i_ray); bsum = l.at<uint32_t>(p, i_bsum); state = l.at<PointState>(p, i_state);
     }
 };
 
@@ -152,6 +178,11 @@ struct RenderJob {
     float *d_pts, *d_daos;     // per-ray origins, uncertified: the points and per-sample directions of one launch (k_batch_points)
     // normals (batches only): per-ray output, central-difference step, samples per ray the final compositing integrates, pass workspace
     float *normals; float h; int n_comp; NormalWorkspace nw;
+    // quantile depths (batches only): n_q targets, the planes (plane k of the batch at depth_q + k * depth_q_stride) and the weights the walk
+    // reads -- the normals workspace's when the render also makes normals, else the surface workspace's; points: the compaction's pass
+    // template (outputs, thresholds, workspace) or points == false
+    int n_q; float quant[kSurfaceMaxQuantiles]; float *depth_q; size_t depth_q_stride; float *w_surface;
+    bool points; PointGatherArgs pg;
 };
 
 struct Pass {
@@ -499,6 +530,27 @@ int normals_pass(nerf_ctx *c, const RenderJob &j, const Pass &p, const DevNet &n
     return timed(c, st, EV_NORMAL_SMALL, 0, [&]() -> int { HIP_TRY(c, launch_normal_reduce(ra, st)); return NERF_OK; });
 }
 
+// The quantile depths of the pass (j.n_q > 0) from the weights the compositing launch left in j.w_surface (t: the composited samples'
+// positions), and for a points render the compaction of the pass's kept rays behind those of the passes before it: the running offset is
+// a word on the device, nothing comes back to the host.  Runs behind normals_pass, whose normals the point records carry.
+int surface_pass(nerf_ctx *c, const RenderJob &j, const Pass &p, const float *t) {
+    if (!j.n_q) return NERF_OK;
+    const hipStream_t st = j.st;
+    RayQuantileArgs qa{};
+    qa.n_rays = p.n_rays; qa.n = j.n_comp; qa.w = j.w_surface; qa.t = t; qa.n_q = j.n_q;
+    for (int k = 0; k < j.n_q; ++k) qa.q[k] = j.quant[k];
+    qa.out = j.depth_q + p.r0; qa.plane_stride = j.depth_q_stride;
+    int rc;
+    if ((rc = timed(c, st, EV_OTHER, 0, [&]() -> int { HIP_TRY(c, launch_ray_quantiles(qa, st)); return NERF_OK; }))) return rc;
+    if (!j.points) return NERF_OK;
+    PointGatherArgs g = j.pg;
+    g.n_rays = p.n_rays; g.first_ray = (uint32_t)p.r0;
+    g.origins = p.origins; copy3(g.origin, j.origin);
+    g.dirs = c->dev(BUF_DIRS); g.depth_q = j.depth_q + p.r0; g.rgb = j.out + 3 * p.r0; g.opacity = j.opacity + p.r0;
+    g.normals = j.normals ? j.normals + 3 * p.r0 : nullptr;
+    return timed(c, st, EV_OTHER, 0, [&]() -> int { HIP_TRY(c, launch_point_gather(g, st)); return NERF_OK; });
+}
+
 // The loop over passes: everything a render launches between its driver's allocations and its counters' read-back.
 int render_passes(nerf_ctx *c, const RenderJob &j, uint32_t *n_passes) {
     const hipStream_t st = j.st;
@@ -518,10 +570,12 @@ int render_passes(nerf_ctx *c, const RenderJob &j, uint32_t *n_passes) {
         ca.depth = j.depth ? j.depth + r0 : nullptr; ca.opacity = j.opacity ? j.opacity + r0 : nullptr;
         if (j.background) { ca.use_bg = 1; copy3(ca.bg, j.background); }
         if (j.normals) ca.w_out = j.nw.w;
+        else if (j.n_q) ca.w_out = j.w_surface;
         if (j.coarse_only) {
             ca.n = j.nc; ca.t = c->dev(BUF_TC); ca.sigma = c->dev(BUF_SC); ca.rgb = c->dev(BUF_RGBC);
             if ((rc = timed(c, st, EV_OTHER, 0, [&]() -> int { HIP_TRY(c, launch_composite(ca, st)); return NERF_OK; }))) return rc;
             if ((rc = normals_pass(c, j, p, NC, c->dev(BUF_TC)))) return rc;
+            if ((rc = surface_pass(c, j, p, c->dev(BUF_TC)))) return rc;
             continue;
         }
         const float *t_fine = c->dev(BUF_TC);
@@ -542,6 +596,7 @@ int render_passes(nerf_ctx *c, const RenderJob &j, uint32_t *n_passes) {
         ca.n = j.M; ca.t = t_fine; ca.sigma = c->dev(BUF_SF); ca.rgb = c->dev(BUF_RGBF);
         if ((rc = timed(c, st, EV_OTHER, 0, [&]() -> int { HIP_TRY(c, launch_composite(ca, st)); return NERF_OK; }))) return rc;
         if ((rc = normals_pass(c, j, p, NF, t_fine))) return rc;
+        if ((rc = surface_pass(c, j, p, t_fine))) return rc;
     }
     *n_passes = passes;
     return NERF_OK;
@@ -850,20 +905,45 @@ int render_rays_device(nerf_ctx *c, const RayRequest &q, CertOutcome *cert) {
     // events: all owned by last_render (EV_BATCH_COLOUR for the colour-producing network: c->dominant and with it nerf_kernel_time_query
     // belong to image renders)
     j.kind_colour = EV_BATCH_COLOUR; j.what = "batch"; j.st = q.st;
-    j.batch = &q; j.normals = q.want_normals ? q.normals : nullptr; j.h = q.h;
+    const bool with_normals = q.want_normals || (q.points && q.h > 0.0f); // a points render with h > 0 makes its normals in the surface workspace
+    j.batch = &q; j.h = q.h;
     j.certify = cert != nullptr;
     // per-ray bounds: a finite far below every t -- the certify kernels' interval behind the last sample is clamped to 0 (cert_pass)
     j.far_cert = q.bounds ? -3.0e38f : q.far_;
     size_t pass_cap = pass_capacity(c, j.M);
     // normals: if every sample of a pass were live its 6 stencil points each must still fit one MLP launch
-    if (j.normals) pass_cap = std::max<size_t>(1, std::min<size_t>(pass_cap, max_batch_points(c->n_cus) / (6 * (size_t)j.M)));
+    if (with_normals) pass_cap = std::max<size_t>(1, std::min<size_t>(pass_cap, max_batch_points(c->n_cus) / (6 * (size_t)j.M)));
     j.n_rays = q.n_rays; j.pass_rays = std::min(q.n_rays, pass_cap);
     if ((rc = ensure_workspace(c, j.pass_rays, j.nc, j.M, j.coarse_only))) return rc;
     j.n_comp = j.coarse_only ? j.nc : j.M;
     const size_t n_comp_max = j.pass_rays * (size_t)j.n_comp;
-    if (j.normals && (rc = c->buf[BUF_NORMAL].ensure(c, NormalWorkspace(nullptr, j.pass_rays, n_comp_max).bytes))) return rc;
+    if (with_normals && (rc = c->buf[BUF_NORMAL].ensure(c, NormalWorkspace(nullptr, j.pass_rays, n_comp_max).bytes))) return rc;
     j.nw = NormalWorkspace(c->buf[BUF_NORMAL].p, j.pass_rays, n_comp_max);
     c->normal_live = 0; c->normal_samples = 0;
+    j.normals = q.want_normals ? q.normals : nullptr;
+    // quantile depths and points: the weights are the normals workspace's when there is one; a points render composites over black into the
+    // surface workspace (colour C, opacity A per ray of the batch) and compacts from there
+    SurfaceWorkspace sw;
+    if (q.want_quantiles || q.points) {
+        const size_t w_samples = with_normals ? 0 : n_comp_max, batch_rays = q.points ? q.n_rays : 0;
+        if ((rc = c->buf[BUF_SURFACE].ensure(c, SurfaceWorkspace(nullptr, w_samples, j.pass_rays, batch_rays, with_normals).bytes))) return rc;
+        sw = SurfaceWorkspace(c->buf[BUF_SURFACE].p, w_samples, j.pass_rays, batch_rays, with_normals);
+        j.w_surface = with_normals ? j.nw.w : sw.w;
+        j.n_q = q.points ? 1 : q.n_q;
+        for (int k = 0; k < j.n_q; ++k) j.quant[k] = q.points ? q.quantile : q.quantiles[k];
+        j.depth_q = q.points ? sw.depth_q : q.depth_q; j.depth_q_stride = q.n_rays;
+    }
+    if (q.points) {
+        static const float kBlack[3] = {0.0f, 0.0f, 0.0f};
+        j.background = kBlack; j.out = sw.rgb; j.depth = nullptr; j.opacity = sw.opacity;
+        if (with_normals) j.normals = sw.normals;
+        j.points = true;
+        j.pg.min_opacity = q.min_opacity; j.pg.capacity = (uint32_t)std::min<size_t>(q.capacity, 0xffffffffu);
+        j.pg.bsum = sw.bsum; j.pg.ray_of = sw.ray_of; j.pg.state = sw.state;
+        j.pg.xyz_out = q.p_xyz; j.pg.rgb_out = q.p_rgb; j.pg.normals_out = with_normals ? q.p_normals : nullptr;
+        j.pg.ray_out = q.p_ray; j.pg.depth_out = q.p_depth; j.pg.opacity_out = q.p_opacity;
+        HIP_TRY(c, hipMemsetAsync(sw.state, 0, sizeof(PointState), q.st));
+    }
     // BUF_BATCH (floats): [far per ray, padded to 64][points 3 x n SoA][directions n x 3 AoS], n = the pass's rays x M
     const bool expand = q.n_origins != 1 && !j.certify;
     const size_t far_floats = q.bounds ? (j.pass_rays + 63) / 64 * 64 : 0, n_max = j.pass_rays * (size_t)j.M;
@@ -877,8 +957,21 @@ int render_rays_device(nerf_ctx *c, const RayRequest &q, CertOutcome *cert) {
     recycle_render(c);
     uint32_t passes = 0;
     if ((rc = render_passes(c, j, &passes))) return rc;
+    if (j.points) HIP_TRY(c, launch_point_total(sw.state, q.d_n_points, q.st));
     if (cert && (rc = read_cert_outcome(c, j, passes, cert))) return rc;
-    return finish_stats(c, j, passes, q.stats, cert);
+    if ((rc = finish_stats(c, j, passes, q.stats, cert))) return rc;
+    if (j.points && (q.n_points || q.stats)) { // the count on the host: 16 bytes and one stream synchronisation
+        PointState hs{};
+        HIP_TRY(c, hipMemcpyAsync(&hs, sw.state, sizeof hs, hipMemcpyDeviceToHost, q.st));
+        HIP_TRY(c, hipStreamSynchronize(q.st));
+        if (q.n_points) *q.n_points = hs.running;
+        if ((size_t)hs.running > q.capacity) {
+            char msg[160];
+            snprintf(msg, sizeof msg, "point cloud: %u rays are kept but the capacity is %zu points; the first %zu are written", hs.running, q.capacity, q.capacity);
+            return fail(c, NERF_ERR_STATE, msg);
+        }
+    }
+    return NERF_OK;
 }
 
 // everything nerf_render_rays* can refuse without a context or a device, in the header's order
@@ -935,6 +1028,26 @@ int check_normals(nerf_ctx *c, const RayRequest &q) {
     return NERF_OK;
 }
 
+// what nerf_render_rays_quantiles* and nerf_render_rays_points* add to check_ray_batch, in the header's order
+int check_surface(nerf_ctx *c, const RayRequest &q) {
+    auto quantile_ok = [](float v) { return std::isfinite(v) && v > 0.0f && v <= 1.0f; };
+    if (q.want_quantiles) {
+        if (q.n_q < 1 || q.n_q > NERF_MAX_QUANTILES) return fail(c, NERF_ERR_INVALID, "n_q must be between 1 and NERF_MAX_QUANTILES (8)");
+        if (!q.quantiles) return fail(c, NERF_ERR_INVALID, "quantiles must not be NULL");
+        for (int k = 0; k < q.n_q; ++k)
+            if (!quantile_ok(q.quantiles[k])) return fail(c, NERF_ERR_INVALID, "a quantile must be finite and lie in (0, 1]");
+        if (q.n_rays > 0 && !q.depth_q) return fail(c, NERF_ERR_INVALID, "depth_q_out must not be NULL");
+        return NERF_OK;
+    }
+    if (!quantile_ok(q.quantile)) return fail(c, NERF_ERR_INVALID, "a quantile must be finite and lie in (0, 1]");
+    if (!(std::isfinite(q.min_opacity) && q.min_opacity >= 0.0f && q.min_opacity <= 1.0f)) return fail(c, NERF_ERR_INVALID, "min_opacity must be finite and lie in [0, 1]");
+    if (!(std::isfinite(q.h) && q.h >= 0.0f)) return fail(c, NERF_ERR_INVALID, "h (the central-difference step) must be finite and not negative");
+    if (q.n_rays > 0 && q.capacity > 0 && !q.p_xyz) return fail(c, NERF_ERR_INVALID, "xyz_out must not be NULL");
+    if (q.p_normals && !(q.h > 0.0f)) return fail(c, NERF_ERR_INVALID, "normals_out needs h > 0");
+    if (q.h > 0.0f && !q.p_normals) return fail(c, NERF_ERR_INVALID, "h > 0 needs normals_out");
+    return NERF_OK;
+}
+
 // what nerf_render_rays_clipped* refuses without a context or a device: nerf_render_rays' refusals, then the grid's
 int check_rays_clipped(nerf_ctx *c, const RayRequest &q) {
     int rc;
@@ -943,15 +1056,17 @@ int check_rays_clipped(nerf_ctx *c, const RayRequest &q) {
     return NERF_OK;
 }
 
-// Everything one of the ten entry points refuses before it touches the device, in the header's order; host: the arrays are host memory,
+// Everything one of the fourteen entry points refuses before it touches the device, in the header's order; host: the arrays are host memory,
 // so their rays are checked one by one.  "ctx is NULL" comes last, and *n_hit is cleared behind it (before the n_rays == 0 return).
 int check_request(nerf_ctx *c, const RayRequest &q, bool host) {
     int rc;
     if ((rc = q.clipped ? check_rays_clipped(c, q) : check_ray_batch(c, q))) return rc;
     if (q.want_normals && (rc = check_normals(c, q))) return rc;
+    if ((q.want_quantiles || q.points) && (rc = check_surface(c, q))) return rc;
     if (host && (rc = check_ray_batch_rays(c, q))) return rc;
     if (!c) return fail(nullptr, NERF_ERR_INVALID, "ctx is NULL");
     if (q.clipped && q.n_hit) *q.n_hit = 0;
+    if (q.points && q.n_points) *q.n_points = 0;
     return NERF_OK;
 }
 
@@ -1180,12 +1295,57 @@ static int rays_clipped_device(nerf_ctx *c, const RayRequest &q) {
     return NERF_OK;
 }
 
-// The ten entry points: refuse, [stage the host arrays], run the device form, [download].  host: every array of q is host memory.
+// nerf_render_rays_points on host arrays: the rays go up, the device form runs, and of every output array the records that were written --
+// the first min(count, capacity) -- come down; the caller's arrays behind them stay untouched.
+static int points_host(nerf_ctx *c, const RayRequest &q) {
+    int rc;
+    const size_t R = q.n_rays, F = sizeof(float), cap = std::min(q.capacity, R); // a batch keeps at most n_rays points
+    const bool up_origins = q.n_origins != 1;
+    Staging s(c, BUF_OUT, c->stream);
+    const int i_dirs = s.add(F, 3 * R, q.dirs), i_origins = s.opt(up_origins, F, 3 * q.n_origins, q.origins), i_bounds = s.opt(q.bounds, F, 2 * R, q.bounds),
+              i_rng = s.opt(q.rng_index, sizeof(uint32_t), R, q.rng_index), i_xyz = s.add(F, 3 * cap), i_rgb = s.add(F, 3 * cap),
+              i_nrm = s.opt(q.p_normals, F, 3 * cap), i_ray = s.opt(q.p_ray, sizeof(uint32_t), cap), i_depth = s.opt(q.p_depth, F, cap),
+              i_opacity = s.opt(q.p_opacity, F, cap);
+    if ((rc = s.begin())) return rc;
+    nerf_stats local; // a synchronous render always reads its counters (see nerf_render_image_aux)
+    size_t count = 0;
+    RayRequest d = q;
+    d.dirs = s.at(i_dirs); d.origins = s.at(i_origins); d.bounds = s.at(i_bounds); d.rng_index = s.at<uint32_t>(i_rng);
+    d.p_xyz = s.at(i_xyz); d.p_rgb = s.at(i_rgb); d.p_normals = s.at(i_nrm); d.p_ray = s.at<uint32_t>(i_ray); d.p_depth = s.at(i_depth);
+    d.p_opacity = s.at(i_opacity); d.capacity = cap; d.n_points = &count; d.d_n_points = nullptr;
+    d.h_origin = up_origins ? nullptr : q.origins;
+    d.st = c->stream; d.stats = q.stats ? q.stats : &local;
+    rc = rays_device(c, d);
+    if (rc && rc != NERF_ERR_STATE) return rc; // NERF_ERR_STATE with a count: more rays are kept than fit, the first `capacity` points stand
+    if (q.n_points) *q.n_points = count;
+    const size_t m = std::min(count, cap);
+    if (m > 0) {
+        HIP_TRY(c, hipMemcpyAsync(q.p_xyz, d.p_xyz, 3 * m * F, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(q.p_rgb, d.p_rgb, 3 * m * F, hipMemcpyDeviceToHost, c->stream));
+        if (q.p_normals) HIP_TRY(c, hipMemcpyAsync(q.p_normals, d.p_normals, 3 * m * F, hipMemcpyDeviceToHost, c->stream));
+        if (q.p_ray) HIP_TRY(c, hipMemcpyAsync(q.p_ray, d.p_ray, m * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        if (q.p_depth) HIP_TRY(c, hipMemcpyAsync(q.p_depth, d.p_depth, m * F, hipMemcpyDeviceToHost, c->stream));
+        if (q.p_opacity) HIP_TRY(c, hipMemcpyAsync(q.p_opacity, d.p_opacity, m * F, hipMemcpyDeviceToHost, c->stream));
+    }
+    const std::string why = rc ? c->err : std::string();
+    const int rc2 = s.finish();
+    return rc2 ? rc2 : rc ? fail(c, rc, why) : NERF_OK;
+}
+
+// The fourteen entry points: refuse, [stage the host arrays], run the device form, [download].  host: every array of q is host memory.
 static int render_rays_entry(nerf_ctx *c, const RayRequest &q, bool host) {
     int rc;
-    if ((rc = check_request(c, q, host)) || q.n_rays == 0) return rc;
+    if ((rc = check_request(c, q, host))) return rc;
+    if (q.n_rays == 0) { // a no-op; only an empty point cloud with a device count has something to write
+        if (q.points && q.d_n_points) {
+            DeviceGuard dg(c->device);
+            HIP_TRY(c, hipMemsetAsync(q.d_n_points, 0, sizeof(uint32_t), q.st));
+        }
+        return NERF_OK;
+    }
     DeviceGuard dg(c->device);
     if (!host) return q.clipped ? rays_clipped_device(c, q) : rays_device(c, q);
+    if (q.points) return points_host(c, q);
     // staging: [occupancy], dirs, [origins], [bounds], [rng_index], rgb, [depth], [opacity], [normals], [hit flags].  One origin for every
     // ray stays on the host (h_origin) unless the clip launch reads it
     const size_t R = q.n_rays, F = sizeof(float);
@@ -1195,12 +1355,14 @@ static int render_rays_entry(nerf_ctx *c, const RayRequest &q, bool host) {
               i_dirs = s.add(F, 3 * R, q.dirs), i_origins = s.opt(up_origins, F, 3 * q.n_origins, q.origins), i_bounds = s.opt(q.bounds, F, 2 * R, q.bounds),
               i_rng = s.opt(q.rng_index, sizeof(uint32_t), R, q.rng_index), i_rgb = s.add(F, 3 * R, nullptr, q.rgb),
               i_depth = s.opt(q.depth, F, R, nullptr, q.depth), i_opacity = s.opt(q.opacity, F, R, nullptr, q.opacity),
-              i_normals = s.opt(q.want_normals, F, 3 * R, nullptr, q.normals), i_hit = s.opt(q.clipped && q.hit, 1, R, nullptr, q.hit);
+              i_normals = s.opt(q.want_normals, F, 3 * R, nullptr, q.normals), i_hit = s.opt(q.clipped && q.hit, 1, R, nullptr, q.hit),
+              i_dq = s.opt(q.want_quantiles, F, (size_t)(q.want_quantiles ? q.n_q : 0) * R, nullptr, q.depth_q);
     if ((rc = s.begin())) return rc;
     nerf_stats local; // a synchronous render always reads its counters (see nerf_render_image_aux)
     RayRequest d = q;
     d.occ_bits = s.at<uint32_t>(i_occ); d.dirs = s.at(i_dirs); d.origins = s.at(i_origins); d.bounds = s.at(i_bounds); d.rng_index = s.at<uint32_t>(i_rng);
     d.rgb = s.at(i_rgb); d.depth = s.at(i_depth); d.opacity = s.at(i_opacity); d.normals = s.at(i_normals); d.hit = s.at<uint8_t>(i_hit);
+    d.depth_q = s.at(i_dq);
     d.h_origin = up_origins ? nullptr : q.origins;
     d.st = c->stream; d.stats = q.stats ? q.stats : &local;
     if ((rc = q.clipped ? rays_clipped_device(c, d) : rays_device(c, d))) return rc;
@@ -1271,6 +1433,61 @@ int nerf_render_rays_certified_device(nerf_ctx *c, const float *d_origins, size_
     q.stats = stats;
     q.origins = d_origins; q.dirs = d_dirs; q.bounds = d_bounds; q.rng_index = d_rng_index; q.rgb = d_rgb_out; q.depth = d_depth_out;
     q.opacity = d_opacity_out; q.certified = true; q.st = (hipStream_t)stream;
+    return render_rays_entry(c, q, false);
+} NERF_CATCH(c)
+
+// quantile depths: `quantiles` is host memory in both forms
+int nerf_render_rays_quantiles(nerf_ctx *c, const float *origins, size_t n_origins, const float *dirs, size_t n_rays, int normalize, float near_,
+                               float far_, const float *bounds, const uint32_t *rng_index, const nerf_render_opts *opts, const float background[3],
+                               float *rgb_out, float *depth_out, float *opacity_out, const float *quantiles, int n_q, float *depth_q_out,
+                               nerf_stats *stats) try {
+    RayRequest q{};
+    q.n_origins = n_origins; q.n_rays = n_rays; q.normalize = normalize; q.near_ = near_; q.far_ = far_; q.opts = opts; q.background = background;
+    q.stats = stats;
+    q.origins = origins; q.dirs = dirs; q.bounds = bounds; q.rng_index = rng_index; q.rgb = rgb_out; q.depth = depth_out; q.opacity = opacity_out;
+    q.want_quantiles = true; q.quantiles = quantiles; q.n_q = n_q; q.depth_q = depth_q_out;
+    return render_rays_entry(c, q, true);
+} NERF_CATCH(c)
+
+int nerf_render_rays_quantiles_device(nerf_ctx *c, const float *d_origins, size_t n_origins, const float *d_dirs, size_t n_rays, int normalize,
+                                      float near_, float far_, const float *d_bounds, const uint32_t *d_rng_index, const nerf_render_opts *opts,
+                                      const float background[3], float *d_rgb_out, float *d_depth_out, float *d_opacity_out, const float *quantiles,
+                                      int n_q, float *d_depth_q_out, void *stream, nerf_stats *stats) try {
+    RayRequest q{};
+    q.n_origins = n_origins; q.n_rays = n_rays; q.normalize = normalize; q.near_ = near_; q.far_ = far_; q.opts = opts; q.background = background;
+    q.stats = stats;
+    q.origins = d_origins; q.dirs = d_dirs; q.bounds = d_bounds; q.rng_index = d_rng_index; q.rgb = d_rgb_out; q.depth = d_depth_out;
+    q.opacity = d_opacity_out; q.want_quantiles = true; q.quantiles = quantiles; q.n_q = n_q; q.depth_q = d_depth_q_out; q.st = (hipStream_t)stream;
+    return render_rays_entry(c, q, false);
+} NERF_CATCH(c)
+
+// point clouds: q.rgb is the points' colour array, so that nerf_render_rays' "rgb_out must not be NULL" covers it
+int nerf_render_rays_points(nerf_ctx *c, const float *origins, size_t n_origins, const float *dirs, size_t n_rays, int normalize, float near_,
+                            float far_, const float *bounds, const uint32_t *rng_index, const nerf_render_opts *opts, float quantile,
+                            float min_opacity, float h, size_t capacity, float *xyz_out, float *rgb_out, float *normals_out, uint32_t *ray_out,
+                            float *depth_out, float *opacity_out, size_t *n_points, nerf_stats *stats) try {
+    RayRequest q{};
+    q.n_origins = n_origins; q.n_rays = n_rays; q.normalize = normalize; q.near_ = near_; q.far_ = far_; q.opts = opts;
+    q.stats = stats;
+    q.origins = origins; q.dirs = dirs; q.bounds = bounds; q.rng_index = rng_index; q.rgb = rgb_out;
+    q.points = true; q.quantile = quantile; q.min_opacity = min_opacity; q.h = h; q.capacity = capacity;
+    q.p_xyz = xyz_out; q.p_rgb = rgb_out; q.p_normals = normals_out; q.p_ray = ray_out; q.p_depth = depth_out; q.p_opacity = opacity_out;
+    q.n_points = n_points;
+    return render_rays_entry(c, q, true);
+} NERF_CATCH(c)
+
+int nerf_render_rays_points_device(nerf_ctx *c, const float *d_origins, size_t n_origins, const float *d_dirs, size_t n_rays, int normalize,
+                                   float near_, float far_, const float *d_bounds, const uint32_t *d_rng_index, const nerf_render_opts *opts,
+                                   float quantile, float min_opacity, float h, size_t capacity, float *d_xyz_out, float *d_rgb_out,
+                                   float *d_normals_out, uint32_t *d_ray_out, float *d_depth_out, float *d_opacity_out, size_t *n_points,
+                                   uint32_t *d_n_points, void *stream, nerf_stats *stats) try {
+    RayRequest q{};
+    q.n_origins = n_origins; q.n_rays = n_rays; q.normalize = normalize; q.near_ = near_; q.far_ = far_; q.opts = opts;
+    q.stats = stats;
+    q.origins = d_origins; q.dirs = d_dirs; q.bounds = d_bounds; q.rng_index = d_rng_index; q.rgb = d_rgb_out;
+    q.points = true; q.quantile = quantile; q.min_opacity = min_opacity; q.h = h; q.capacity = capacity;
+    q.p_xyz = d_xyz_out; q.p_rgb = d_rgb_out; q.p_normals = d_normals_out; q.p_ray = d_ray_out; q.p_depth = d_depth_out; q.p_opacity = d_opacity_out;
+    q.n_points = n_points; q.d_n_points = d_n_points; q.st = (hipStream_t)stream;
     return render_rays_entry(c, q, false);
 } NERF_CATCH(c)
 

@@ -14,38 +14,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "block_scan.hip.h"
 #include "normal_kernels.h"
 
 namespace {
 
 constexpr int kB = kNormalBlock;
-static_assert(kB == 256, "four waves of 64 rays per workgroup");
-
-__device__ __forceinline__ uint32_t wave_inclusive(uint32_t v, int lane) {
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t o = __shfl_up(v, off, 64);
-        if (lane >= off) v += o;
-    }
-    return v;
-}
-
-// exclusive prefix sum of v over the kB threads of the workgroup; sum = the workgroup's total.  Ends with a barrier: s is free again.
-__device__ __forceinline__ void block_exclusive(uint32_t &v, uint32_t &sum, uint32_t *s) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t iv = wave_inclusive(v, lane);
-    if (lane == 63) s[wave] = iv;
-    __syncthreads();
-    uint32_t ov = 0;
-    sum = 0;
-#pragma unroll
-    for (int k = 0; k < kB / 64; ++k) {
-        if (k < wave) ov += s[k];
-        sum += s[k];
-    }
-    v = iv - v + ov;
-    __syncthreads();
-}
+static_assert(kB == kScanBlock, "four waves of 64 rays per workgroup (block_scan.hip.h)");
 
 // A wave owns 64 consecutive rays and visits them one after the other, its lanes striding over the ray's samples: the weight loads are
 // contiguous.  Returns in lane j the number of live samples of ray first + j (0 behind the last ray).  Trip counts are wave-uniform.

@@ -12,39 +12,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "block_scan.hip.h"
 #include "ray_clip_core.h"
 #include "ray_clip_kernels.h"
 
 namespace {
 
 constexpr int kB = kClipBlock;
-static_assert(kB == 256, "four waves of 64 rays per workgroup");
-
-__device__ __forceinline__ uint32_t wave_inclusive(uint32_t v, int lane) {
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t o = __shfl_up(v, off, 64);
-        if (lane >= off) v += o;
-    }
-    return v;
-}
-
-// exclusive prefix sum of v over the kB threads of the workgroup; sum = the workgroup's total.  Ends with a barrier: s is free again.
-__device__ __forceinline__ void block_exclusive(uint32_t &v, uint32_t &sum, uint32_t *s) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t iv = wave_inclusive(v, lane);
-    if (lane == 63) s[wave] = iv;
-    __syncthreads();
-    uint32_t ov = 0;
-    sum = 0;
-#pragma unroll
-    for (int k = 0; k < kB / 64; ++k) {
-        if (k < wave) ov += s[k];
-        sum += s[k];
-    }
-    v = iv - v + ov;
-    __syncthreads();
-}
+static_assert(kB == kScanBlock, "four waves of 64 rays per workgroup (block_scan.hip.h)");
 
 // any set bit among the linear cells c0 .. c1 (inclusive; both inside the grid)
 __device__ __forceinline__ bool any_set(const uint32_t *__restrict__ bits, int c0, int c1) {
@@ -99,11 +74,8 @@ __global__ __launch_bounds__(kB) void k_clip_rays(ClipRaysArgs a) {
         }
     }
     if (a.bsum) { // uniform: every thread of the workgroup reaches the barrier
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        const uint32_t c = (uint32_t)__popcll(__ballot(hit));
-        if (lane == 0) s[wave] = c;
-        __syncthreads();
-        if (threadIdx.x == 0) a.bsum[blockIdx.x] = s[0] + s[1] + s[2] + s[3];
+        const uint32_t c = block_count(hit, s);
+        if (threadIdx.x == 0) a.bsum[blockIdx.x] = c;
     }
 }
 
